@@ -8,10 +8,16 @@ A "step" = one Gibbs sweep (gibbs_sample!, gibbs.jl:663-677) of every chain resi
 n=500, V=100 (q=5050), R=7 (SURVEY.md 8d generator, seed 20240501), the 8 chains of BASELINE.json configs[2] IN ALL:
 chain c lives on rank (c-1) % N (the reference's pmap over chains, gibbs.jl:946-948), the 8/N chains of a GPU advance as one
 lockstep group (one launch per kernel for all of them; N = 8: one chain per GPU, configs[2]'s literal layout).  Chains are
-independent: no data-path collective; total work is fixed as N grows ("scaling": "strong").  After the timed region the
-per-chain split-Rhat messages are all-gathered over RCCL (reported, not timed).  Sub-records of the same line: at N = 1
-"single_chain" (one chain alone on the GPU, latency-bound), at N > 1 "weak_scaling" (8 chains on EVERY GPU).
+independent: no data-path collective; total work is fixed as N grows ("scaling": "strong").
 Inputs are resident in HBM when the timed region starts.  Prints ONE JSON line on rank 0.
+
+A plain run only sets up, warms up, times the K steps (and writes --dump-outputs).  --full adds, after the timed region: the
+HIP-event pass around the Gram and the roofline, the per-chain split-Rhat messages all-gathered over RCCL and the ESS, the
+sub-records "single_chain" and "expected_scaling" (N = 1; one chain alone on the GPU is latency-bound) or "weak_scaling"
+(N > 1: 8 chains on EVERY GPU), and the CPU baselines (N = 1, unless --no-cpu-baseline).
+
+--dump-outputs DIR: the table row the last timed sweep wrote for every chain of the fit (what Chain.fetch hands a caller), one
+float64 file per column, DIR/<column>.npy of shape (chains, d1, d2), chains in chain-id order (gathered over the ranks).
 """
 import argparse
 import json
@@ -29,6 +35,7 @@ CONFIGS = {
     "cfg5": dict(n=500, V=300, R=10),
 }
 FP64_MFMA_PEAK_TFLOPS = 78.6               # AMD MI355X FP64 matrix spec (not in the local guide)
+DUMP_LIMIT_BYTES = 64 << 20                # --dump-outputs: beyond this, only the first chains (by id) are written
 
 
 _CPU_WORKER = r"""
@@ -174,6 +181,29 @@ def spawn_ranks(a):
     return rc
 
 
+def dump_outputs(path, chains, ids, row, dist, world, rank):
+    """--dump-outputs: table row `row` of every chain of the fit, gathered on rank 0 and written as DIR/<column>.npy (float64,
+    shape (chains, d1, d2), chains in chain-id order; the first chains only if all of them would exceed DUMP_LIMIT_BYTES)."""
+    import numpy as np
+    import bnr_amd
+    cols = bnr_amd._capi.TABLE_COLUMNS
+    rows = {cid: {k: v[0] for k, v in ch.fetch(row, row).items()} for cid, ch in zip(ids, chains)}
+    if world > 1:
+        box = [None] * world
+        dist.all_gather_object(box, rows)
+        rows = {cid: t for part in box for cid, t in part.items()}
+    if rank != 0:
+        return
+    cids = sorted(rows)
+    per_chain = sum(rows[cids[0]][k].nbytes for k in cols)
+    keep = cids[:max(1, DUMP_LIMIT_BYTES // per_chain)]
+    if len(keep) < len(cids):
+        sys.stderr.write("bench.py: --dump-outputs writes chains %d..%d of %d (%d MiB limit)\n" % (keep[0], keep[-1], len(cids), DUMP_LIMIT_BYTES >> 20))
+    os.makedirs(path, exist_ok=True)
+    for k in cols:
+        np.save(os.path.join(path, k + ".npy"), np.stack([rows[c][k] for c in keep]).astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -190,10 +220,15 @@ def main():
     ap.add_argument("--binary-x", action="store_true", help="NOT the headline: the same shape with a 0/1 model matrix given as Bool (the reference's adjacency inputs), whose Gram "
                     "runs on the i8 matrix pipe (SURVEY 8f-2); the line says so in config.workload and roofline.kernel, dtype stays f64 (S, G and everything else are f64)")
     ap.add_argument("--dry-ranks", action="store_true", help="no GPU: every rank only reports which chains it would hold (checks the N-rank plumbing on a CPU)")
+    ap.add_argument("--full", action="store_true", help="also the measurements beyond the headline figure: Gram event pass and roofline, Rhat / ESS, "
+                    "single-chain / expected-scaling / weak-scaling sub-records, CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the table row of every chain's last timed sweep as DIR/<column>.npy (float64)")
     a = ap.parse_args()
 
     if a.gpus < 1:
         raise SystemExit("bench.py: --gpus must be at least 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("bench.py: --steps must be at least 1 and --warmup at least 0")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         sys.exit(spawn_ranks(a))                           # the parent never touches the GPU: it only starts the ranks and relays rank 0's line
     if "WORLD_SIZE" in os.environ and int(os.environ["WORLD_SIZE"]) != a.gpus:
@@ -347,25 +382,29 @@ def main():
     dt = time.perf_counter() - t0
     eager_sweeps, replayed_sweeps = runner.last_timing(2)
     dt = max_over_ranks(dt)                                # MAX over ranks (an RCCL all-gather of one double per rank)
+    if a.dump_outputs:                                     # row W + K + 1: the last timed sweep's (the --full passes below write later rows)
+        dump_outputs(a.dump_outputs, chains, ids, W + K + 1, dist, world, rank)
 
+    # --full only from here to the result line (a plain run reports the timed region and stops)
     # kernel-duration pass: the same sweeps continue, launched eagerly with HIP events recorded around every k_gram launch
     # on the stream it runs on (the timed region above replays captured graphs, where events cannot be read back)
     # first half: two-branch schedule as in the timed region (the events then also cover the time the launch waits for CUs
     # held by the concurrent scalar branch); second half: single-stream schedule, the events bracket the kernel alone --
     # that is the kernel duration the roofline uses (and what rocprofv3 --kernel-trace reports as its duration)
-    P1 = P // 2
-    run_all(W + K + 2, W + K + P1 + 1, profile=True)
-    gram_us_pipe, _ = runner.last_timing(1)
-    runner.set_option("overlap", 0)
-    run_all(W + K + P1 + 2, W + K + P + 1, profile=True)
-    runner.set_option("overlap", a.overlap)
-    gram_us, gram_n = runner.last_timing(1)
+    if a.full:
+        P1 = P // 2
+        run_all(W + K + 2, W + K + P1 + 1, profile=True)
+        gram_us_pipe, _ = runner.last_timing(1)
+        runner.set_option("overlap", 0)
+        run_all(W + K + P1 + 2, W + K + P + 1, profile=True)
+        runner.set_option("overlap", a.overlap)
+        gram_us, gram_n = runner.last_timing(1)
     counters = chains[0].counters()
 
     # N = 1: one chain alone on the GPU (what every GPU does at N = 8; latency-bound).  N > 1: the weak-scaling figure, 8 chains on
     # EVERY GPU as one lockstep group.  Both continue from chain 1's data in the same process; reported as sub-records.
     single, weak, expected = None, None, None
-    if C > 1 and world == 1:
+    if a.full and C > 1 and world == 1:
         runner.close()
         runner = None
         Ks = min(max(K, 200), 1000)                   # (a sub-record with its own step count: at least 200 sweeps, so that the driver's short run reports the same one-chain rate as a long one)
@@ -406,7 +445,7 @@ def main():
                     ch.close()
             expected[str(Nr)] = {"chains_per_gpu": Cr, "it_per_s_per_gpu": per_rank, "it_per_s_all_chains": Nr * per_rank,
                                  "speedup_over_1_gpu": Nr * per_rank / (total_chains * K / dt), "measured": "per-rank workload on one GPU x %d" % Nr}
-    elif world > 1 and a.chains_per_gpu == 0:
+    elif a.full and world > 1 and a.chains_per_gpu == 0:
         if C > 1:
             runner.close()
         runner = None
@@ -436,12 +475,12 @@ def main():
     from bnr_amd import _capi
     nsamp = K
     rh = None
-    if nsamp >= 4:                                               # split-Rhat needs two samples per half
+    if a.full and nsamp >= 4:                                    # split-Rhat needs two samples per half
         rg, rx = _capi.rhat(chains, total_chains, comm, W + 1, nsamp)
         rh = np.concatenate([rg, rx])
     # effective sample size of the timed window over all chains (an addition to the reference's Rhat; same exchange pattern)
     ess = None
-    if nsamp >= 64:
+    if a.full and nsamp >= 64:
         Lag = min(250, nsamp // 4)
         local_e = {cid: ch.ess_stats(W + 2, nsamp, Lag) for cid, ch in zip(ids, chains)}
         stats_e = bnr_amd.allgather_stats(local_e, total_chains, comm) if comm is not None else np.stack([local_e[c] for c in sorted(local_e)])
@@ -451,17 +490,6 @@ def main():
 
     if rank == 0:
         value = total_chains * K / dt
-        flops_gram = float(n) * n * q * C                         # algorithmic: symmetric X diag(S) X'  per chain of the launch
-        traffic = None                                            # HBM bytes per k_gram launch from the PMC passes (tools/pmc_gram_round3.sh)
-        pmc_file = os.path.join(ROOT, "profiles", "round6_gram_pmc.json")
-        if not os.path.exists(pmc_file):
-            pmc_file = os.path.join(ROOT, "profiles", "round5_gram_pmc.json")
-        if a.config == "cfg3" and C in (1, 8) and not a.binary_x and os.path.exists(pmc_file):
-            traffic = json.load(open(pmc_file))["k_gram<bnr_one,2>" if C == 1 else "k_gram8<bnr_many>"].get("traffic_bytes_per_launch")
-        achieved = flops_gram / (gram_us * 1e-6) / 1e12 if gram_us > 0 else 0.0
-        # whole-sweep roofline: F_iter = n^2 q + n^3/3 + 8 n q flops per chain-iteration, r = iterations/s per GPU
-        f_iter = float(n) * n * q + float(n) ** 3 / 3.0 + 8.0 * n * q
-        sweep_tflops = f_iter * (C * K / dt) / 1e12
         out = {
             "metric": "Gibbs iterations/sec (all chains)", "value": value, "unit": "iterations/s",
             "n_gpus": world, "steps": K, "warmup": W, "ms_per_step": 1e3 * dt / K, "higher_is_better": True,
@@ -472,34 +500,51 @@ def main():
                                       "the chains of a GPU advance as one lockstep group)" % (total_chains, world, world)),
                        "chains_total": total_chains, "chains_per_gpu": C, "seed": a.seed},
             "timed_region": {"sweeps_replayed_from_graphs": int(replayed_sweeps), "sweeps_launched_eagerly": int(eager_sweeps)},
-            "roofline": {"bound": "mfma", "kernel": ("k_sdigits + k_gram_i8 (X diag(S) X' of a 0/1 X: i8L exact v_mfma_i32_16x16x64_i8 Grams recombined in f64; achieved / frac are the f64-equivalent "
-                                                      "algorithmic rate against the f64 peak, i.e. they may exceed 1)" if a.binary_x else "k_gram8 / k_gram (X diag(S) X', v_mfma_f64_16x16x4_f64)"), "achieved": achieved,
-                         "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / FP64_MFMA_PEAK_TFLOPS,
-                         "traffic": traffic, "traffic_source": "profiles/%s (FETCH_SIZE x2 + WRITE_SIZE of a launch of this shape, separate --pmc passes, tools/round6_profiles.sh / round5_profiles.sh)" % os.path.basename(pmc_file),
-                         "sweep_frac": sweep_tflops / FP64_MFMA_PEAK_TFLOPS, "sweep_achieved": sweep_tflops, "sweep_flops_per_chain_iteration": f_iter,
-                         "flops_per_launch": flops_gram, "avg_launch_us": gram_us, "launches_timed": gram_n,
-                         "avg_launch_us_two_branch_schedule": gram_us_pipe,
-                         "peak_measured_microbench": _measured_mfma_peak(),
-                         "peak_measured_source": "profiles/round5_mfma_f64_peak.txt (tools/mfma_f64_peak.hip: pure v_mfma_f64_16x16x4_f64 loop, census-checked, median of the lines marked sustained); "
-                                                 "the product kernel's K loop holds 2.39 GHz (median over its workgroups after 2.5 s of back-to-back launches, both clocks stamped in the kernel: profiles/round6_gram_clock.txt) -- the 2.10 GHz of "
-                                                 "profiles/round5_gram_lab2_ablation.txt was a lab kernel's clock, not k_gram8's"},
-            "max_rhat_gamma": None if rh is None else float(np.nanmax(rh[:q])), "max_rhat_xi": None if rh is None else float(np.nanmax(rh[q:])),
-            "ess_gamma": None if ess is None else {"min": float(np.nanmin(ess[:q])), "median": float(np.nanmedian(ess[:q])),
-                                                   "draws": int(nsamp * total_chains), "min_per_second": float(np.nanmin(ess[:q]) / dt)},
-            "counters": counters, "rhat_exchange": exchange,
+            "counters": counters,
             "rccl_ranks": int(comm_info["rccl_ranks"]), "comm_kind": comm_info["kind"], "chains_held": [int(r[2]) for r in held],
             "ranks": [{"rank": int(r[0]), "local_rank": int(r[1]), "chains_held": int(r[2]), "rccl_ranks_seen": int(r[3])} for r in held],
         }
+        if a.full:
+            flops_gram = float(n) * n * q * C                         # algorithmic: symmetric X diag(S) X'  per chain of the launch
+            traffic = None                                            # HBM bytes per k_gram launch from the PMC passes (tools/pmc_gram_round3.sh)
+            pmc_file = os.path.join(ROOT, "profiles", "round6_gram_pmc.json")
+            if not os.path.exists(pmc_file):
+                pmc_file = os.path.join(ROOT, "profiles", "round5_gram_pmc.json")
+            if a.config == "cfg3" and C in (1, 8) and not a.binary_x and os.path.exists(pmc_file):
+                traffic = json.load(open(pmc_file))["k_gram<bnr_one,2>" if C == 1 else "k_gram8<bnr_many>"].get("traffic_bytes_per_launch")
+            achieved = flops_gram / (gram_us * 1e-6) / 1e12 if gram_us > 0 else 0.0
+            # whole-sweep roofline: F_iter = n^2 q + n^3/3 + 8 n q flops per chain-iteration, r = iterations/s per GPU
+            f_iter = float(n) * n * q + float(n) ** 3 / 3.0 + 8.0 * n * q
+            sweep_tflops = f_iter * (C * K / dt) / 1e12
+            out.update({
+                "roofline": {"bound": "mfma", "kernel": ("k_sdigits + k_gram_i8 (X diag(S) X' of a 0/1 X: i8L exact v_mfma_i32_16x16x64_i8 Grams recombined in f64; achieved / frac are the f64-equivalent "
+                                                          "algorithmic rate against the f64 peak, i.e. they may exceed 1)" if a.binary_x else "k_gram8 / k_gram (X diag(S) X', v_mfma_f64_16x16x4_f64)"), "achieved": achieved,
+                             "peak": FP64_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": achieved / FP64_MFMA_PEAK_TFLOPS,
+                             "traffic": traffic, "traffic_source": "profiles/%s (FETCH_SIZE x2 + WRITE_SIZE of a launch of this shape, separate --pmc passes, tools/round6_profiles.sh / round5_profiles.sh)" % os.path.basename(pmc_file),
+                             "sweep_frac": sweep_tflops / FP64_MFMA_PEAK_TFLOPS, "sweep_achieved": sweep_tflops, "sweep_flops_per_chain_iteration": f_iter,
+                             "flops_per_launch": flops_gram, "avg_launch_us": gram_us, "launches_timed": gram_n,
+                             "avg_launch_us_two_branch_schedule": gram_us_pipe,
+                             "peak_measured_microbench": _measured_mfma_peak(),
+                             "peak_measured_source": "profiles/round5_mfma_f64_peak.txt (tools/mfma_f64_peak.hip: pure v_mfma_f64_16x16x4_f64 loop, census-checked, median of the lines marked sustained); "
+                                                     "the product kernel's K loop holds 2.39 GHz (median over its workgroups after 2.5 s of back-to-back launches, both clocks stamped in the kernel: profiles/round6_gram_clock.txt) -- the 2.10 GHz of "
+                                                     "profiles/round5_gram_lab2_ablation.txt was a lab kernel's clock, not k_gram8's"},
+                "max_rhat_gamma": None if rh is None else float(np.nanmax(rh[:q])), "max_rhat_xi": None if rh is None else float(np.nanmax(rh[q:])),
+                "ess_gamma": None if ess is None else {"min": float(np.nanmin(ess[:q])), "median": float(np.nanmedian(ess[:q])),
+                                                       "draws": int(nsamp * total_chains), "min_per_second": float(np.nanmin(ess[:q]) / dt)},
+                "rhat_exchange": exchange,
+            })
         if single is not None:
             out["single_chain"] = single
         if expected is not None:
             out["expected_scaling"] = expected
         if weak is not None:
             out["weak_scaling"] = weak
-        if not a.no_cpu_baseline and world == 1:            # the host-core baseline is taken at N = 1 only
+        if a.full and not a.no_cpu_baseline and world == 1:    # the host-core baseline is taken at N = 1 only
             out["cpu_baseline"] = cpu_baseline(n, V, R, a.seed, total_chains, 15.0, 2)
             out["cpu_baseline_no_blas"] = cpu_baseline(n, V, R, a.seed, total_chains, 6.0, 1)
         print(json.dumps(out))
+    if runner is not None and runner is not chains[0]:    # the lockstep group goes before its chains
+        runner.close()
     for ch in chains:
         ch.close()
     if dist:

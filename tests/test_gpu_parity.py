@@ -15,6 +15,7 @@ import pytest
 
 import bnr_amd
 from oracle import bnr_oracle as bo
+from golden_data import load_golden
 from pit import pit_trace
 
 pytestmark = pytest.mark.gpu
@@ -136,7 +137,7 @@ def test_golden_run_is_a_typical_gpu_run(gpu, test1):
     grp = bnr_amd.Group(chains)
     assert grp.run(2, 200, 400) == 401
     reps = np.array([window_stats(c.fetch(), 200, 200) for c in chains])
-    g = np.load(os.path.join(G, "golden_res2.npz"))
+    g = load_golden("res2")
     golden = window_stats({k: g[k] for k in bo.COLUMNS}, 200, 200)
     assert reps.shape == (N, len(STAT_NAMES)) and np.all(np.isfinite(reps))
     p = assert_golden_is_typical(golden, reps, what="GPU:")

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import bnr_amd
+from golden_data import load_golden
 from oracle import bnr_oracle as bo
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -101,7 +102,7 @@ def _stats_from_table(g, xi, first, nsamp):
 
 @pytest.mark.parametrize("name", ["res", "res2"])
 def test_rhat_from_stats_known_answer(name):
-    g = dict(np.load(os.path.join(G, "golden_%s.npz" % name)))
+    g = load_golden(name)
     b, s = int(g["burn_in"]), int(g["sampled"])
     st = _stats_from_table(g["gamma"], g["xi"], b, s)[None, :]
     r = bnr_amd.rhat_from_stats(st, s)

@@ -16,6 +16,7 @@ import pytest
 from scipy import stats
 
 from oracle import bnr_oracle as bo
+from golden_data import load_golden
 from pit import pit_trace
 
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -26,12 +27,12 @@ Z_MAX = 4.0
 
 @pytest.fixture(scope="module")
 def res2():
-    return dict(np.load(os.path.join(G, "golden_res2.npz")))
+    return load_golden("res2")
 
 
 @pytest.fixture(scope="module")
 def res():
-    return dict(np.load(os.path.join(G, "golden_res.npz")))
+    return load_golden("res")
 
 
 @pytest.fixture(scope="module")
@@ -50,7 +51,7 @@ def test_philox_known_answers():
 
 @pytest.mark.parametrize("name", ["res", "res2"])
 def test_rhat_known_answer(name):
-    g = dict(np.load(os.path.join(G, "golden_%s.npz" % name)))
+    g = load_golden(name)
     b, s = int(g["burn_in"]), int(g["sampled"])
     rg = bo.rhat(g["gamma"][b:b + s, :, 0][:, :, None])
     rx = bo.rhat(g["xi"][b:b + s, :, 0][:, :, None])

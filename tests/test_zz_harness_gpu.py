@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import bnr_amd
 from oracle import bnr_oracle as bo
 
 pytestmark = pytest.mark.gpu
@@ -57,7 +58,7 @@ def test_bench_multi_rank_path_rehearsal(gpu, tmp_path):
     layout -- 8 chains IN ALL, chain c on rank (c-1) % 2, i.e. 4 per rank as one lockstep group -- rank 0 prints ONE JSON line whose
     value aggregates the chains of both ranks ("strong": the total work does not grow with N); the 8-chains-on-every-GPU figure is
     the weak_scaling sub-record."""
-    d = _run_bench_ranks(tmp_path, 2, ["--steps", "40", "--warmup", "8", "--config", "cfg2", "--no-cpu-baseline"], dict(BNR_BENCH_ONE_DEVICE="1"))
+    d = _run_bench_ranks(tmp_path, 2, ["--steps", "40", "--warmup", "8", "--config", "cfg2", "--no-cpu-baseline", "--full"], dict(BNR_BENCH_ONE_DEVICE="1"))
     assert d["n_gpus"] == 2 and d["steps"] == 40 and d["warmup"] == 8 and d["scaling"] == "strong" and d["higher_is_better"] is True
     assert "8 chains total, 4 per GPU" in d["config"]["workload"] and d["config"]["chains_total"] == 8 and d["config"]["chains_per_gpu"] == 4
     assert d["value"] > 0 and d["roofline"]["achieved"] > 0
@@ -69,19 +70,53 @@ def test_bench_multi_rank_path_rehearsal(gpu, tmp_path):
     assert d["timed_region"]["sweeps_launched_eagerly"] == 0 and d["timed_region"]["sweeps_replayed_from_graphs"] == 40
 
 
-def test_bench_plain_command_starts_two_ranks(gpu):
-    """The driver's own spelling, `python bench.py --gpus 2 ...` with no launcher in front: bench.py starts the two ranks itself (fresh
-    children, before the parent touched the GPU) and relays rank 0's line -- rehearsed on this one GPU (BNR_BENCH_ONE_DEVICE=1)."""
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    env["BNR_BENCH_ONE_DEVICE"] = "1"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "24", "--warmup", "4", "--config", "cfg2", "--no-cpu-baseline"],
-                         env=env, capture_output=True, text=True, timeout=900)
+def _bench_line(args, env, cwd=None):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, env=env, capture_output=True, text=True, timeout=900, cwd=cwd)
     assert out.returncode == 0, "rc %d\n%s" % (out.returncode, out.stderr[-6000:])
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, out.stdout[-3000:]
-    d = json.loads(lines[0])
+    return json.loads(lines[0])
+
+
+def _dumped(d):
+    return {k: np.load(os.path.join(d, k + ".npy")) for k in bnr_amd._capi.TABLE_COLUMNS}
+
+
+def test_bench_plain_command_starts_two_ranks(gpu, tmp_path):
+    """The driver's own spelling, `python bench.py --gpus 2 ...` with no launcher in front: bench.py starts the two ranks itself (fresh
+    children, before the parent touched the GPU) and relays rank 0's line -- rehearsed on this one GPU (BNR_BENCH_ONE_DEVICE=1).
+    --dump-outputs gathers both ranks' chains: the 8 chains of the fit in chain-id order, one row each."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env["BNR_BENCH_ONE_DEVICE"] = "1"
+    d = _bench_line(["--gpus", "2", "--steps", "24", "--warmup", "4", "--config", "cfg2", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "dump")], env)
     assert d["n_gpus"] == 2 and d["steps"] == 24 and d["scaling"] == "strong" and d["config"]["chains_per_gpu"] == 4 and d["value"] > 0
     assert d["timed_region"]["sweeps_replayed_from_graphs"] == 24
+    shapes = bnr_amd._capi.table_shapes(50, 5)
+    for k, v in _dumped(tmp_path / "dump").items():
+        assert v.dtype == np.float64 and v.shape == (8,) + shapes[k] and np.isfinite(v).all(), (k, v.dtype, v.shape)
+
+
+def test_bench_plain_run_is_lean_and_computes_what_full_computes(gpu, tmp_path):
+    """A plain run (no --full) times the steps and reports the headline only -- no roofline, Rhat, sub-records or CPU baseline --
+    and its --dump-outputs (the last timed sweep's row of every chain) is bitwise what a --full run of the same arguments dumps:
+    the extra passes of --full come after the timed region and write later rows."""
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    args = ["--gpus", "1", "--steps", "16", "--warmup", "4", "--config", "cfg2"]
+    plain = _bench_line(args + ["--dump-outputs", "plain"], env, cwd=str(tmp_path))
+    full = _bench_line(args + ["--full", "--no-cpu-baseline", "--dump-outputs", "full"], env, cwd=str(tmp_path))
+    for d in (plain, full):
+        assert d["steps"] == 16 and d["warmup"] == 4 and d["value"] > 0 and d["higher_is_better"] is True and d["dtype"] == "f64"
+        assert abs(d["value"] - 8 * 16 / (d["ms_per_step"] * 16 / 1e3)) < 1e-6 * d["value"]
+        assert d["timed_region"]["sweeps_replayed_from_graphs"] == 16 and d["counters"]["chol_fail"] == 0
+    for k in ("roofline", "max_rhat_gamma", "ess_gamma", "single_chain", "expected_scaling", "cpu_baseline"):
+        assert k not in plain, k
+    assert full["roofline"]["achieved"] > 0 and full["max_rhat_gamma"] > 0 and full["single_chain"]["value"] > 0 and "cpu_baseline" not in full
+    a, b = _dumped(tmp_path / "plain"), _dumped(tmp_path / "full")
+    shapes = bnr_amd._capi.table_shapes(50, 5)
+    for k in a:
+        assert a[k].shape == (8,) + shapes[k] and np.isfinite(a[k]).all(), k
+        assert np.array_equal(a[k], b[k]), k
+    assert not np.array_equal(a["gamma"][0], a["gamma"][1])          # chains are distinct streams
 
 
 def test_bench_one_rank_rccl_path(gpu, tmp_path):
@@ -90,7 +125,7 @@ def test_bench_one_rank_rccl_path(gpu, tmp_path):
     per-chain messages into the communicator's device buffer, ncclAllGather (also with one rank the collective itself is called:
     the dlsym'd signature, the datatype code, the staging buffers and the stream are the ones eight ranks use), one copy to the
     host.  Everything of the N > 1 path except the peers."""
-    d = _run_bench_ranks(tmp_path, 1, ["--steps", "24", "--warmup", "3", "--chains", "2", "--config", "cfg2", "--no-cpu-baseline"],
+    d = _run_bench_ranks(tmp_path, 1, ["--steps", "24", "--warmup", "3", "--chains", "2", "--config", "cfg2", "--no-cpu-baseline", "--full"],
                          dict(BNR_BENCH_FORCE_DIST="1"))
     assert d["n_gpus"] == 1 and d["steps"] == 24 and d["value"] > 0 and d["max_rhat_gamma"] > 0 and d["config"]["chains_total"] == 2
     assert d["rhat_exchange"].startswith("bnr_rhat: ncclAllGather"), d["rhat_exchange"]

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-4 measurement pass on the GPU box.  Everything lands in gpurun_out/r4prof/ (what is to be judged is copied into profiles/round4_*).
+# Round-4 measurement pass on the GPU box.  Everything lands in prof_out/r4prof/ (what is to be judged is copied into profiles/round4_*).
 #   1. bench lines: default (2000 steps) and driver-style (20 steps, 5 warm-up)
 #   2. rocprofv3 --kernel-trace --stats of the bench command (>= 400 k_gram8 launches) for three builds of the library:
 #        default            (no Gram progress count, dead blocks of the diagonal tiles skipped)
@@ -9,13 +9,13 @@
 #   3. one line per BASELINE config with one chain and with eight
 #   4. config 5 (the "HBM-bound large-q regime"): kernel stats with the byte image of a 0/1 model matrix on and off
 R=$GRAFT_REPO_ROOT
-O=$R/gpurun_out/r4prof
+O=$R/prof_out/r4prof
 mkdir -p $O
 cd $R
 V=$R/bayesiannetworkregression.jl_amd/csrc/_var
 echo "== 1. bench lines" | tee $O/progress.log
-python bench.py --gpus 1 > $O/bench_default.json 2> $O/bench_default.err || { echo "bench failed"; tail -5 $O/bench_default.err; exit 1; }
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err || exit 1
+python bench.py --full --gpus 1 > $O/bench_default.json 2> $O/bench_default.err || { echo "bench failed"; tail -5 $O/bench_default.err; exit 1; }
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err || exit 1
 python - <<PY | tee -a $O/progress.log
 import json
 for f in ("bench_default", "bench_driver_style"):
@@ -27,7 +27,7 @@ cd /tmp && export TMPDIR=/tmp
 for b in default noskip r3like; do
   if [ $b = default ]; then unset BNR_HIP_LIB; else export BNR_HIP_LIB=$V/$b.so; fi
   rm -rf $O/prof_$b
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$b -o r4 -- python3 $R/bench.py --steps 480 --warmup 24 --no-cpu-baseline > $O/prof_$b.log 2>&1 || { echo "rocprofv3 ($b) failed"; tail -5 $O/prof_$b.log; exit 1; }
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$b -o r4 -- python3 $R/bench.py --full --steps 480 --warmup 24 --no-cpu-baseline > $O/prof_$b.log 2>&1 || { echo "rocprofv3 ($b) failed"; tail -5 $O/prof_$b.log; exit 1; }
   python3 $R/tools/prof_summary.py $O/prof_$b > $O/kernel_stats_$b.txt
   echo "-- $b" | tee -a $O/progress.log; head -6 $O/kernel_stats_$b.txt | tee -a $O/progress.log
 done
@@ -51,10 +51,10 @@ rm -f $O/configs.txt
 for cfg in cfg2 cfg4 cfg5; do
   for c in 1 8; do
     st=200; [ $cfg = cfg4 ] && [ $c = 8 ] && st=40
-    python bench.py --config $cfg --chains-per-gpu $c --steps $st --warmup 16 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$cfg $c chain(s):', round(d['value'],1), 'it/s', round(d['ms_per_step']*1e3,1), 'us/sweep; k_gram', round(r['avg_launch_us'],1), 'us', round(r['achieved'],1), 'TFLOP/s frac', round(r['frac'],3), 'sweep_frac', round(r['sweep_frac'],3))" | tee -a $O/configs.txt || exit 1
+    python bench.py --full --config $cfg --chains-per-gpu $c --steps $st --warmup 16 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$cfg $c chain(s):', round(d['value'],1), 'it/s', round(d['ms_per_step']*1e3,1), 'us/sweep; k_gram', round(r['avg_launch_us'],1), 'us', round(r['achieved'],1), 'TFLOP/s frac', round(r['frac'],3), 'sweep_frac', round(r['sweep_frac'],3))" | tee -a $O/configs.txt || exit 1
   done
 done
-python bench.py --config cfg3 --chains-per-gpu 16 --steps 400 --warmup 40 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('cfg3 16 chains:', round(d['value'],1), 'it/s', round(d['ms_per_step']*1e3,1), 'us/sweep; sweep_frac', round(r['sweep_frac'],3))" | tee -a $O/configs.txt
+python bench.py --full --config cfg3 --chains-per-gpu 16 --steps 400 --warmup 40 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('cfg3 16 chains:', round(d['value'],1), 'it/s', round(d['ms_per_step']*1e3,1), 'us/sweep; sweep_frac', round(r['sweep_frac'],3))" | tee -a $O/configs.txt
 echo "== 4. config 5, byte image on / off" | tee -a $O/progress.log
 cd /tmp
 for b in 0 1; do

@@ -1,14 +1,15 @@
 #!/bin/bash
 # Round-2 measurement pass on the GPU box: driver-style and default bench lines, rocprofv3 kernel stats of the bench command,
-# per-config single-chain lines.  Everything lands in gpurun_out/ (copy what is to be judged into profiles/).
+# per-config single-chain lines.  Everything lands in prof_out/ (copy what is to be judged into profiles/).
 R=$GRAFT_REPO_ROOT
-python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/round2_bench_driver_style.json 2> gpurun_out/round2_bench_driver_style.err || exit 1
-python bench.py > gpurun_out/round2_bench_default.json 2> gpurun_out/round2_bench_default.err || exit 1
+P=$R/prof_out; mkdir -p $P
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $P/round2_bench_driver_style.json 2> $P/round2_bench_driver_style.err || exit 1
+python bench.py --full > $P/round2_bench_default.json 2> $P/round2_bench_default.err || exit 1
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $R/gpurun_out/prof_round2 -o r2 -- python3 $R/bench.py --steps 200 --warmup 24 --no-cpu-baseline > $R/gpurun_out/prof_round2.log 2>&1 || exit 1
-cd $R && python tools/prof_summary.py gpurun_out/prof_round2 > gpurun_out/round2_kernel_stats.txt
-head -14 gpurun_out/round2_kernel_stats.txt
+rocprofv3 --kernel-trace --stats --output-format csv -d $P/prof_round2 -o r2 -- python3 $R/bench.py --full --steps 200 --warmup 24 --no-cpu-baseline > $P/prof_round2.log 2>&1 || exit 1
+cd $R && python tools/prof_summary.py $P/prof_round2 > $P/round2_kernel_stats.txt
+head -14 $P/round2_kernel_stats.txt
 for cfg in cfg2 cfg4 cfg5; do
-  python bench.py --config $cfg --chains-per-gpu 1 --steps 200 --warmup 24 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$cfg one chain:', round(d['value'],1), 'it/s', round(d['ms_per_step']*1e3,1), 'us/sweep; k_gram', round(r['avg_launch_us'],1), 'us', round(r['achieved'],1), 'TFLOP/s frac', round(r['frac'],3), 'sweep_frac', round(r['sweep_frac'],3))" | tee -a gpurun_out/round2_configs.txt || exit 1
+  python bench.py --full --config $cfg --chains-per-gpu 1 --steps 200 --warmup 24 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$cfg one chain:', round(d['value'],1), 'it/s', round(d['ms_per_step']*1e3,1), 'us/sweep; k_gram', round(r['avg_launch_us'],1), 'us', round(r['achieved'],1), 'TFLOP/s frac', round(r['frac'],3), 'sweep_frac', round(r['sweep_frac'],3))" | tee -a $P/round2_configs.txt || exit 1
 done
-python bench.py --config cfg3 --chains-per-gpu 16 --steps 400 --warmup 40 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('cfg3 16 chains:', round(d['value'],1), 'it/s', round(d['ms_per_step']*1e3,1), 'us/sweep')" | tee -a gpurun_out/round2_configs.txt
+python bench.py --full --config cfg3 --chains-per-gpu 16 --steps 400 --warmup 40 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('cfg3 16 chains:', round(d['value'],1), 'it/s', round(d['ms_per_step']*1e3,1), 'us/sweep')" | tee -a $P/round2_configs.txt

@@ -1,17 +1,17 @@
 #!/bin/bash
-# Round-6 measurement pass on the GPU box.  Everything lands in gpurun_out/r6prof/ (what is to be judged is copied into profiles/round6_*).
+# Round-6 measurement pass on the GPU box.  Everything lands in prof_out/r6prof/ (what is to be judged is copied into profiles/round6_*).
 #   1. bench lines: default (2000 steps), driver-style (20 steps, 5 warm-up), --binary-x
 #   2. rocprofv3 --kernel-trace --stats of the bench command (>= 400 k_gram8 launches), kernel resources from the trace
 #   3. one line per BASELINE config with one chain and with eight
 #   4. PMC passes of the group Gram (k_gram8) and of the one-chain Gram (k_gram), one --pmc pass per counter group
 R=$GRAFT_REPO_ROOT
-O=$R/gpurun_out/r6prof
+O=$R/prof_out/r6prof
 mkdir -p $O
 cd $R
 echo "== 1. bench lines" | tee $O/progress.log
-python bench.py --gpus 1 > $O/bench_default.json 2> $O/bench_default.err || { echo "bench failed"; tail -5 $O/bench_default.err; exit 1; }
-python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err || exit 1
-python bench.py --gpus 1 --binary-x --no-cpu-baseline > $O/bench_binary_x.json 2> $O/bench_binary_x.err || exit 1
+python bench.py --full --gpus 1 > $O/bench_default.json 2> $O/bench_default.err || { echo "bench failed"; tail -5 $O/bench_default.err; exit 1; }
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err || exit 1
+python bench.py --full --gpus 1 --binary-x --no-cpu-baseline > $O/bench_binary_x.json 2> $O/bench_binary_x.err || exit 1
 python - <<PY | tee -a $O/progress.log
 import json
 for f in ("bench_default", "bench_driver_style", "bench_binary_x"):
@@ -21,7 +21,7 @@ PY
 echo "== 2. kernel stats of the bench command" | tee -a $O/progress.log
 cd /tmp && export TMPDIR=/tmp
 rm -rf $O/prof_default
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -o r6 -- python3 $R/bench.py --steps 480 --warmup 24 --no-cpu-baseline > $O/prof_default.log 2>&1 || { echo "rocprofv3 failed"; tail -5 $O/prof_default.log; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_default -o r6 -- python3 $R/bench.py --full --steps 480 --warmup 24 --no-cpu-baseline > $O/prof_default.log 2>&1 || { echo "rocprofv3 failed"; tail -5 $O/prof_default.log; exit 1; }
 python3 $R/tools/prof_summary.py $O/prof_default > $O/kernel_stats.txt
 head -8 $O/kernel_stats.txt | tee -a $O/progress.log
 cp $O/prof_default/r6_kernel_stats.csv $O/rocprofv3_kernel_stats.csv 2>/dev/null
@@ -36,7 +36,7 @@ print("%-40s %8s %6s %6s %8s %6s" % ("kernel", "scratch", "vgpr", "sgpr", "lds",
 for k, v in sorted(seen.items()): print("%-40s %8s %6s %6s %8s %6s" % ((k[:40],) + v))
 PY
 rm -rf $O/prof_binary
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_binary -o r6b -- python3 $R/bench.py --steps 480 --warmup 24 --no-cpu-baseline --binary-x > $O/prof_binary.log 2>&1 || { echo "rocprofv3 (binary) failed"; exit 1; }
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_binary -o r6b -- python3 $R/bench.py --full --steps 480 --warmup 24 --no-cpu-baseline --binary-x > $O/prof_binary.log 2>&1 || { echo "rocprofv3 (binary) failed"; exit 1; }
 python3 $R/tools/prof_summary.py $O/prof_binary > $O/kernel_stats_binary_x.txt
 head -8 $O/kernel_stats_binary_x.txt | tee -a $O/progress.log
 cd $R
@@ -47,12 +47,12 @@ rm -f $O/configs.txt
 for cfg in cfg2 cfg4 cfg5; do
   for c in 1 8; do
     st=200; [ $cfg = cfg4 ] && [ $c = 8 ] && st=40
-    python bench.py --config $cfg --chains-per-gpu $c --steps $st --warmup 16 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$cfg $c chain(s):', round(d['value'],1), 'it/s', round(d['ms_per_step']*1e3,1), 'us/sweep; k_gram', round(r['avg_launch_us'],1), 'us', round(r['achieved'],1), 'TFLOP/s frac', round(r['frac'],3), 'sweep_frac', round(r['sweep_frac'],3))" | tee -a $O/configs.txt || exit 1
+    python bench.py --full --config $cfg --chains-per-gpu $c --steps $st --warmup 16 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$cfg $c chain(s):', round(d['value'],1), 'it/s', round(d['ms_per_step']*1e3,1), 'us/sweep; k_gram', round(r['avg_launch_us'],1), 'us', round(r['achieved'],1), 'TFLOP/s frac', round(r['frac'],3), 'sweep_frac', round(r['sweep_frac'],3))" | tee -a $O/configs.txt || exit 1
   done
 done
-python bench.py --config cfg3 --chains-per-gpu 16 --steps 400 --warmup 40 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('cfg3 16 chains:', round(d['value'],1), 'it/s', round(d['ms_per_step']*1e3,1), 'us/sweep; sweep_frac', round(r['sweep_frac'],3))" | tee -a $O/configs.txt
+python bench.py --full --config cfg3 --chains-per-gpu 16 --steps 400 --warmup 40 --no-cpu-baseline 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('cfg3 16 chains:', round(d['value'],1), 'it/s', round(d['ms_per_step']*1e3,1), 'us/sweep; sweep_frac', round(r['sweep_frac'],3))" | tee -a $O/configs.txt
 for cfg in cfg4 cfg5; do
-  python bench.py --config $cfg --chains-per-gpu 1 --steps 200 --warmup 16 --no-cpu-baseline --binary-x 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$cfg 1 chain, BINARY X (i8 Gram):', round(d['value'],1), 'it/s', round(d['ms_per_step']*1e3,1), 'us/sweep; digits + Gram', round(r['avg_launch_us'],1), 'us')" | tee -a $O/configs.txt
+  python bench.py --full --config $cfg --chains-per-gpu 1 --steps 200 --warmup 16 --no-cpu-baseline --binary-x 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); r=d['roofline']; print('$cfg 1 chain, BINARY X (i8 Gram):', round(d['value'],1), 'it/s', round(d['ms_per_step']*1e3,1), 'us/sweep; digits + Gram', round(r['avg_launch_us'],1), 'us')" | tee -a $O/configs.txt
 done
 [ -n "$BNR_SKIP_PMC" ] && { echo "(PMC passes skipped)" | tee -a $O/progress.log; exit 0; }
 echo "== 4. PMC passes of the Gram kernels" | tee -a $O/progress.log
