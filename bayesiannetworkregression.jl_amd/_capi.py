@@ -94,6 +94,7 @@ _SIGS = {
     "bnr_host_gamma": (C.c_double, [C.c_uint64, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32]),
     "bnr_host_gig": (C.c_double, [C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_uint32]),
     "bnr_host_edge_index": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
+    "bnr_host_xi_weight": (C.c_double, [C.c_double, C.c_double, C.c_double]),
     "bnr_host_gram_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
 }
 for _u in ("tau2", "u_xi", "gamma", "D", "theta", "Delta", "M", "mu", "Lambda", "pi"):
@@ -224,11 +225,24 @@ class XInput:
         self.dtype_code = X_DTYPES[dt]
 
 
+XI_WEIGHTS = {"log": 0, "reference": 1}      # model option "xi_weights" of include/bnr_hip.h
+
+
+def xi_weights_code(xi_weights):
+    """the library's value of the `xi_weights` model option: "log" (default: log-space node weights) or "reference" (the reference's
+    ratio of pdfs with its under/overflow, gibbs.jl:349-360); anything else is a ValueError, raised before any GPU call"""
+    if not isinstance(xi_weights, str) or xi_weights not in XI_WEIGHTS:
+        raise ValueError("xi_weights must be one of %s, not %r" % (", ".join(map(repr, XI_WEIGHTS)), xi_weights))
+    return XI_WEIGHTS[xi_weights]
+
+
 class Chain:
-    """One Gibbs chain resident on one GPU (handle of include/bnr_hip.h)."""
+    """One Gibbs chain resident on one GPU (handle of include/bnr_hip.h).  xi_weights: "log" (default) or "reference" (model
+    option "xi_weights": the reference's node weights with their under/overflow, see include/bnr_hip.h)."""
 
     def __init__(self, X, y, R, tot_save, seed, chain_id, device=0, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0,
-                 bDelta=1.0, nu=10):
+                 bDelta=1.0, nu=10, xi_weights="log"):
+        xw = xi_weights_code(xi_weights)
         xi = X if isinstance(X, XInput) else XInput(X)
         yf = np.ascontiguousarray(y, dtype=np.float64)
         n, q, V = xi.n, xi.q, xi.V
@@ -248,16 +262,20 @@ class Chain:
             check(self.L.bnr_chain_create(n, V, int(R), _ptr(xi.data), *common))
         else:
             check(self.L.bnr_chain_create_typed(n, V, int(R), _ptr(xi.data), xi.dtype_code, *common))
+        self.xi_weights = xi_weights
+        if xw:
+            self.set_option("xi_weights", xw)
 
     @classmethod
     def like(cls, donor, seed, chain_id, tot_save=None):
-        """Another chain of the same fit (same X, y, hyper-parameters; device inputs shared with `donor`)."""
+        """Another chain of the same fit (same X, y, hyper-parameters and xi_weights; device inputs shared with `donor`)."""
         self = cls.__new__(cls)
         self.n, self.q, self.V, self.R = donor.n, donor.q, donor.V, donor.R
         self.tot = int(donor.tot if tot_save is None else tot_save)
         self.h = C.c_void_p()
         self.L = donor.L
         check(self.L.bnr_chain_create_like(donor.h, C.c_uint64(int(seed) & (2**64 - 1)), int(chain_id), self.tot, C.byref(self.h)))
+        self.xi_weights = donor.xi_weights                  # inherited by the library (bnr_chain_create_like)
         return self
 
     def close(self):
@@ -399,7 +417,11 @@ class Chain:
         return np.tril(G)
 
     def set_option(self, name, value):
+        if name == "xi_weights" and isinstance(value, str):
+            value = xi_weights_code(value)
         check(self.L.bnr_chain_set_option(self.h, name.encode(), int(value)))
+        if name == "xi_weights":
+            self.xi_weights = {v: k for k, v in XI_WEIGHTS.items()}[int(value)]
 
 
 class Group:

@@ -31,7 +31,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from . import _capi
-from ._capi import Chain, Comm, Group, XInput, ess_from_stats, new_table, rhat_from_stats
+from ._capi import Chain, Comm, Group, XInput, ess_from_stats, new_table, rhat_from_stats, xi_weights_code
 
 CITATION = ("If you use BayesianNetworkRegression.jl, please cite:\n@article{Ozminkowski2022,\n"
             "author = {Ozminkowski, S. and Sol\\'{i}s-Lemus, C.},\nyear = {2022},\n"
@@ -270,16 +270,18 @@ def allgather_stats(local_stats, num_chains, comm=None):
 
 
 class ChainSet:
-    """The chains of one fit that live on this rank's GPU."""
+    """The chains of one fit that live on this rank's GPU.  xi_weights: the model option of every chain ("log" or "reference")."""
 
-    def __init__(self, X_new, y, R, num_chains, tot_save, seed, hyper, device=None):
+    def __init__(self, X_new, y, R, num_chains, tot_save, seed, hyper, device=None, xi_weights="log"):
+        xi_weights_code(xi_weights)
         self.num_chains = num_chains
         self.ids = local_chain_ids(num_chains)
         dev = _default_device() if device is None else device
         self.chains = {}
         for c in self.ids:                                  # X, y are uploaded once per GPU and shared by its chains
             first = next(iter(self.chains.values()), None)
-            self.chains[c] = Chain(X_new, y, R, tot_save, seed, c, device=dev, **hyper) if first is None else Chain.like(first, seed, c, tot_save)
+            self.chains[c] = (Chain(X_new, y, R, tot_save, seed, c, device=dev, xi_weights=xi_weights, **hyper) if first is None
+                              else Chain.like(first, seed, c, tot_save))
         # several chains share this GPU: they advance in lockstep, one launch per kernel for all of them (the sequential
         # panel chain of the n x n factorization is paid once per sweep of the whole group)
         self.group = Group([self.chains[c] for c in self.ids]) if len(self.chains) > 1 else None
@@ -419,8 +421,11 @@ def _normalize_purge(purge_burn, nburn):
 
 def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=10, nburn=30000, nsamp=20000,
                      maxburn=50000, psrf_cutoff=1.2, x_transform=True, suppress_timer=False, num_chains=2, seed=None,
-                     purge_burn=None, device=None, _keep=None, return_state=True, summary_interval=None, ess_max_lag=None):
-    """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds."""
+                     purge_burn=None, device=None, _keep=None, return_state=True, summary_interval=None, ess_max_lag=None,
+                     xi_weights="log"):
+    """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
+    xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
+    xi_weights_code(xi_weights)
     if nu < R:
         pass                                       # the reference constructs an ArgumentError without throwing it (901-902)
     elif nu == R:
@@ -435,7 +440,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
     purge_burn = _normalize_purge(purge_burn, nburn)
     tot_save = total if purge_burn is None else nsamp + purge_burn
     hyper = dict(eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu)
-    cs = ChainSet(X_new, y, R, num_chains, tot_save, seed_eff, hyper, device)
+    cs = ChainSet(X_new, y, R, num_chains, tot_save, seed_eff, hyper, device, xi_weights)
     if _keep is not None:
         _keep.append(cs)
     p = _Progress((total - 1) // prog_freq, not suppress_timer)
@@ -475,8 +480,10 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
 
 def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=10, mingen=10000,
                          maxgen=100000, psrf_cutoff=1.01, x_transform=True, suppress_timer=False, num_chains=2,
-                         seed=None, purge_burn=None, device=None, return_state=True, summary_interval=None, ess_max_lag=None):
-    """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme."""
+                         seed=None, purge_burn=None, device=None, return_state=True, summary_interval=None, ess_max_lag=None,
+                         xi_weights="log"):
+    """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
+    xi_weights_code(xi_weights)
     if nu == R:
         print("Warning: ν==R may give poor accuracy. Consider increasing ν")
     nburn = _julia_round(mingen / 2)
@@ -491,7 +498,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
     purge_burn = _normalize_purge(purge_burn, nburn)
     tot_save = total if purge_burn is None else nsamp + purge_burn
     hyper = dict(eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu)
-    cs = ChainSet(X_new, y, R, num_chains, tot_save, seed_eff, hyper, device)
+    cs = ChainSet(X_new, y, R, num_chains, tot_save, seed_eff, hyper, device, xi_weights)
     p = _Progress((total - 1) // prog_freq, not suppress_timer)
     cs.init_prior()
     cs.run(2, nburn, total, purge_burn, prog_freq, p.tick)
@@ -532,11 +539,15 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
 
 def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=10, nburn=30000, nsamples=20000,
         mingen=0, maxgen=0, psrf_cutoff=1.01, x_transform=True, suppress_timer=False, num_chains=2, seed=None,
-        purge_burn=None, filename="parameters.log", device=None, return_state=True, summary_interval=None, ess_max_lag=None):
+        purge_burn=None, filename="parameters.log", device=None, return_state=True, summary_interval=None, ess_max_lag=None,
+        xi_weights="log"):
     """Fit! (gibbs.jl:725-751).  The `V` keyword is accepted and ignored, as in the reference.
     Extensions: summary_interval=95 computes Summary's statistics on the GPU (Results.summary_device);
     return_state=False then leaves the (large) state table on the device and frees it; ess_max_lag=0 (default lag
-    window) or a lag count adds bulk effective sample sizes over all chains (Results.essgamma / essxi)."""
+    window) or a lag count adds bulk effective sample sizes over all chains (Results.essgamma / essxi);
+    xi_weights="reference" samples xi with the reference's own weight arithmetic, under/overflow included (the default "log" never
+    under/overflows; include/bnr_hip.h, option "xi_weights").  parameters.log keeps the reference's lines only."""
+    xi_weights_code(xi_weights)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
         with open(filename, "w") as f:
@@ -552,8 +563,10 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
         return generate_samples_dbl(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, mingen=mingen,
                                     maxgen=maxgen, psrf_cutoff=psrf_cutoff, x_transform=x_transform, suppress_timer=suppress_timer,
                                     num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
-                                    return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag)
+                                    return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
+                                    xi_weights=xi_weights)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
-                            return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag)
+                            return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
+                            xi_weights=xi_weights)

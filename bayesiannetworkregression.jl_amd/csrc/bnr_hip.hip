@@ -210,6 +210,8 @@ double bnr_host_gig(uint64_t seed, double lambda, double chi, double psi, uint32
 { int cap = 0; return bnr_gig(seed, lambda, chi, psi, it, elem, &cap); }
 int32_t bnr_host_edge_index(int32_t V, int32_t l, int32_t k)
 { return l >= k ? bnr_edge_index(V, l, k) : bnr_edge_index(V, k, l); }
+double bnr_host_xi_weight(double lt, double lb, double Delta)
+{ return bnr_xi_weight_ref(lt, lb, Delta); }
 
 static int alloc_trace(bnr_chain *c, int tot, double **out)
 {
@@ -388,6 +390,7 @@ static int chain_build(const bnr_chain *donor, int32_t n, int32_t V, int32_t R, 
         c->x8_kept = donor->x8_kept;                     // the image belongs to the shared inputs: a chain made from a donor with byte_x = 0 can switch it on again
         c->xm_kept = donor->xm_kept;
         d.X = donor->d.X; d.X8 = donor->d.X8; d.XM = donor->d.XM; d.y = donor->d.y; d.ek = donor->d.ek; d.el = donor->d.el; d.gmap = donor->d.gmap; d.gmapc = donor->d.gmapc;
+        d.xi_ref = donor->d.xi_ref;                      // a model option, not a path: the chains of one fit sample the same model
     } else {
         c->in = std::make_shared<bnr_inputs>();
         double *Xd = nullptr, *yd = nullptr;
@@ -2290,6 +2293,18 @@ int bnr_chain_set_option(bnr_chain *c, const char *name, int64_t value)
         if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
         if (value && !c->xm_kept) return fail(BNR_ERR_BAD_ARG, "gram_i8 needs a binary (0 / 1) integer-typed model matrix");
         c->d.XM = value ? c->xm_kept : nullptr;
+        drop_graph(c->x);
+        if (c->group) drop_graph(c->group->x);
+        return sync_dev(c);
+    }
+    if (!strcmp(name, "xi_weights")) {
+        // model option (changes results): 0 log-space node weights, 1 the reference's ratio of pdfs with its under/overflow (gibbs.jl:349-360).
+        // Takes effect from the next sweep: the descriptor is refreshed and every graph that baked the old one in is dropped (a group re-uploads
+        // its members' descriptors at every run call).
+        if (value != 0 && value != 1) return fail(BNR_ERR_BAD_ARG, "xi_weights must be 0 (log) or 1 (reference)");
+        if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+        HIPCHK(hipSetDevice(c->device));
+        c->d.xi_ref = (int)value;
         drop_graph(c->x);
         if (c->group) drop_graph(c->group->x);
         return sync_dev(c);

@@ -52,6 +52,7 @@ struct bnr_dev {
                                  // (every K slice padded with zeros to a multiple of 64 columns = one v_mfma_i32_16x16x64_i8 step); nullptr: no such image
     unsigned char *Sdig;         // [i8L][kslab] the balanced base-256 digits of the chain's S in the same column order (k_sdigits), its scale in scal[SC_I8SCALE]
     int kcp, kslab, i8L;         // padded K slice, bytes per row of XM, number of digit planes (7 or 8)
+    int xi_ref;                  // model option "xi_weights": 0 log-space node weights (default), 1 the reference's pdf ratio (k_node; in the padding in front of trace)
     // state
     double *trace;
     const bnr_plan_entry *plan;
@@ -265,7 +266,9 @@ __device__ __forceinline__ double edge_W(const double *u, const double *lam, int
 // update_u_xi! (gibbs.jl:293-371) for node k = blockIdx.x, all inputs from row prev (no Gauss-Seidel).  Weights in
 // log space (determinant lemma + Woodbury): log w_bot - log w_top = log(D/(1-D)) - 1/2[logdet M + logdet Sigma^-1]
 // + 1/2 b' Sigma b,  b = U'H^-1 gamma_k / tau2 -- equal to the reference's ratio of dense (V-1)-dim pdfs whenever
-// those do not under/overflow (gibbs.jl:349-351).
+// those do not under/overflow (gibbs.jl:349-351).  Option "xi_weights" = reference (cd.xi_ref): the two log densities themselves,
+// l_top = log N(gamma_k; 0, tau2 H) (one more sum over the staged nodes) and l_bot = l_top - 1/2[logdet M + logdet Sigma^-1]
+// + 1/2 b' Sigma b (the same lemma), and the reference's w = w_top / (w_bot + w_top) with its under/overflow (bnr_xi_weight_ref).
 // The V-1 other nodes are staged through LDS in chunks of 64 (one per lane: U_a = u_a .* lambda, V_a = U_a / h_a,
 // g_a / h_a), then lane p accumulates the p-th of the R(R+1)/2 + R sums sequentially over a (the reference's order).
 #define BNR_NODE_MAXSUM 9      // ceil((32*33/2 + 32) / 64)
@@ -338,6 +341,8 @@ __global__ __launch_bounds__(64) void k_node(const SRC chain_src, int s, int mod
         if (p < npair) { int rem = p; while (rem >= R - x + 1) { rem -= R - x + 1; ++x; } px[m] = x; py[m] = x + rem; }
         else { px[m] = 0; py[m] = 0; }
     }
+    const bool xref = cd.xi_ref != 0;
+    double ltp = 0.0;                                         // xi_weights = reference: this lane's part of l_top (its staged nodes, in the order of a)
     for (int a0 = 0; a0 < V - 1; a0 += 64) {
         const int a = a0 + lane;
         if (a < V - 1) {
@@ -347,6 +352,7 @@ __global__ __launch_bounds__(64) void k_node(const SRC chain_src, int s, int mod
             double *dst = shn + (size_t)lane * W2;
             for (int x = 0; x < R; ++x) { double ux = pu[x + R * l] * slam[x]; dst[x] = ux; dst[R + x] = ux / h; }
             dst[2 * R] = g / h;
+            if (xref) { const double th = tau2 * h; ltp += -0.5 * (log(2.0 * BNR_PI) + log(th) + g * g / th); }   // logpdf N(gamma_kl; 0, tau2 h), gibbs.jl:349
         }
         __syncthreads();
         const int na = min(64, V - 1 - a0);
@@ -428,8 +434,16 @@ __global__ __launch_bounds__(64) void k_node(const SRC chain_src, int s, int mod
     double mt = wave_fwd_solve(sL, R, lane, b);
     mt = wave_bwd_solve_T(sL, R, lane, mt);
     double qf = wave_sum((lane < R) ? b * mt : 0.0);
-    double logit = log(Delta) - log1p(-Delta) - 0.5 * (logdetM + ldS) + 0.5 * qf;
-    double w = 1.0 / (1.0 + exp(logit));
+    double w;
+    if (xref) {
+        // the reference's two dense (V-1)-dim pdfs (gibbs.jl:349-351) by the determinant lemma and Woodbury
+        const double lt = wave_sum(ltp);
+        const double lb = lt - 0.5 * (logdetM + ldS) + 0.5 * qf;
+        w = bnr_xi_weight_ref(lt, lb, Delta);
+    } else {
+        double logit = log(Delta) - log1p(-Delta) - 0.5 * (logdetM + ldS) + 0.5 * qf;
+        w = 1.0 / (1.0 + exp(logit));
+    }
     // update_xi (gibbs.jl:385-402)
     double xi;
     if (w <= 0.0) xi = 1.0;

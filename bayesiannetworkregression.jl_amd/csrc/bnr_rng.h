@@ -278,3 +278,13 @@ BNR_HD double bnr_lambda_value(int c) { return c == 0 ? 0.0 : (c == 1 ? 1.0 : -1
 
 // edge e <-> (l,k), l >= k, column-wise lower triangle incl. diagonal (utils.jl:50-55), all 0-based
 BNR_HD int bnr_edge_index(int V, int l, int k) { return k * V - (k * (k - 1)) / 2 + (l - k); }
+
+// update_u_xi!'s inclusion weight as the reference forms it (gibbs.jl:349-351) from the two log densities l_top = log N(gamma_k; 0, tau2 H),
+// l_bot = log N(gamma_k; 0, tau2 H + U M U'): w_top = (1 - Delta) exp(l_top), w_bot = Delta exp(l_bot), w = w_top / (w_bot + w_top), written
+// literally -- no clamp, no rescaling -- so that under/overflow gives the reference's outcomes: 0 exp(..) = 0 over a positive w_bot is 0 (xi = 1
+// without a draw), a w_bot that underflows under a positive w_top gives 1 (xi = 0), 0/0 and Inf/Inf are NaN (the fair coin of gibbs.jl:392-400).
+BNR_HD double bnr_xi_weight_ref(double lt, double lb, double Delta)
+{
+    const double w_top = (1.0 - Delta) * exp(lt), w_bot = Delta * exp(lb);
+    return w_top / (w_bot + w_top);
+}

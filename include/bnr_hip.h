@@ -28,8 +28,9 @@
 extern "C" {
 #endif
 
-#define BNR_ABI_VERSION 6   /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
-                               5: + bnr_chain_create_typed, bnr_chain_create_from_matrices, bnr_device_synchronize; 6: + bnr_comm_info (all additive) */
+#define BNR_ABI_VERSION 7   /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
+                               5: + bnr_chain_create_typed, bnr_chain_create_from_matrices, bnr_device_synchronize; 6: + bnr_comm_info;
+                               7: + option "xi_weights", bnr_host_xi_weight (all additive) */
 
 enum {
     BNR_OK = 0,
@@ -77,7 +78,7 @@ int bnr_chain_create_typed(int32_t n, int32_t V, int32_t R, const void *X, int32
 int bnr_chain_create_from_matrices(int32_t n, int32_t V, int32_t R, const void *const *A, int32_t x_dtype, const double *y,
                                    const bnr_hyper *hyper, uint64_t seed, int32_t chain_id, int32_t device, int32_t tot_save,
                                    bnr_chain **out);
-/* Another chain of the same fit on the same device: same X, y, sizes and hyper-parameters as `donor`, own seed /
+/* Another chain of the same fit on the same device: same X, y, sizes, hyper-parameters and model options as `donor`, own seed /
  * chain id, own table and work space.  The read-only device inputs (X, y, index maps) are SHARED with the donor, not
  * copied -- the reference hands the same X, y to every pmap worker (gibbs.jl:946-948) -- and live until the last chain
  * using them is destroyed. */
@@ -212,7 +213,8 @@ int bnr_rhat(bnr_chain *const *chains, int32_t nchains_local, int32_t nchains_to
  * rhat: q+V doubles (gamma first, then xi).  Replaces convergence.jl:49-61. */
 int bnr_rhat_from_stats(const double *stats, int32_t nchains, int32_t nparams, int32_t nsamp, double *rhat);
 
-/* event counters: out[0]=Cholesky jitter events, out[1]=NaN-weight events (always 0: log-space weights),
+/* event counters: out[0]=Cholesky jitter events, out[1]=NaN-weight events (node updates that took the fair coin of gibbs.jl:392-400; always 0
+ * with the default log-space weights, which cannot under/overflow; see "xi_weights"),
  * out[2]=sampler attempt-cap events, out[3]=Cholesky hard failures, out[4..7] reserved */
 int bnr_chain_counters(bnr_chain *chain, int64_t out[8]);
 
@@ -238,7 +240,16 @@ int bnr_chain_debug_dims(bnr_chain *chain, int32_t *out8);
  * kernels of the scalar branch return at once -- what the critical chain costs without company.) */
 int bnr_debug_set_exp(int32_t device, int32_t flags);
 
-/* tunables (performance only; never change results):
+/* model options (change results):
+ *   "xi_weights" 0 (default): update_u_xi!'s inclusion weight in log space, w = 1 / (1 + exp(log w_bot - log w_top)) -- never under/overflows;
+ *               1: the reference's own arithmetic (gibbs.jl:349-360): w_top = (1 - Delta) pdf_top, w_bot = Delta pdf_bot from the two (V-1)-dim
+ *               log densities (same determinant lemma and Woodbury identity), w = w_top / (w_bot + w_top) with its under/overflow: w = 0 or 1
+ *               without a draw where one density underflows, NaN -> fair coin (counted in bnr_chain_counters out[1]) where both do.  Residual
+ *               differences from the reference's dense pdf: the lemma uses the jittered Sigma^-1 when the jitter ladder fired (out[0]); where the
+ *               dense covariance is not positive definite the reference throws PosDefException, here the lemma's value is used.
+ *               Takes effect from the next sweep (also on a group member); bnr_chain_create_like inherits the donor's setting.  Any other value:
+ *               BNR_ERR_BAD_ARG.  Default: same tables bit for bit as without the option.
+ * tunables (performance only; never change results):
  *   "graph"     1 (default): replay captured hipGraphs of graph_k sweeps; 0: launch every kernel eagerly
  *   "graph_k"   sweeps per captured graph (default 16; a ladder graph_k, graph_k / 2, ..., 1 is captured so that a batch of any length is pure replay)
  *   "overlap"   1 (default): scalar branch and Gram/factorization branch of a sweep on two streams; 0: one stream
@@ -289,6 +300,9 @@ double bnr_host_normal(uint64_t seed, uint32_t it, uint32_t site, uint32_t elem,
 double bnr_host_gamma(uint64_t seed, double shape, uint32_t it, uint32_t site, uint32_t elem);
 double bnr_host_gig(uint64_t seed, double lambda, double chi, double psi, uint32_t it, uint32_t elem);
 int32_t bnr_host_edge_index(int32_t V, int32_t l, int32_t k);   /* 0-based (l,k) -> 0-based e; utils.jl:50-55 */
+/* the node weight of option "xi_weights" = 1 (the kernel's own function): w = (1 - Delta) exp(lt) / (Delta exp(lb) + (1 - Delta) exp(lt)),
+ * written literally (gibbs.jl:349-351), so 0, 1 and NaN arise where they arise in the reference */
+double bnr_host_xi_weight(double lt, double lb, double Delta);
 /* The K split the library would choose for the Gram  X diag(S) X'  of gibbs.jl:434 on a device with `ncu` compute units (no GPU needed):
  * out[0] = K slices, out[1] = columns per slice (padded), out[2] = q_pad, out[3] = MiB of X one K-group of a workgroup addresses through its
  * 2 GiB buffer window.  The split is raised beyond what fills the chip until that span fits the window (n up to the 14 000-row limit with any V

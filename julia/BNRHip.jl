@@ -50,9 +50,17 @@ mutable struct Chain
 end
 destroy(ch::Chain) = ccall((:bnr_chain_destroy, LIB), Cint, (Ptr{Cvoid},), ch.h)
 
+# model option "xi_weights" (include/bnr_hip.h): :log (default; log-space node weights, never under/overflow) or :reference (the reference's
+# w_top / (w_bot + w_top) with its under/overflow and NaN coin, gibbs.jl:349-360)
+xi_weights_code(w::Symbol) = w === :log ? 0 : w === :reference ? 1 : throw(ArgumentError("xi_weights must be :log or :reference, not :$w"))
+# the setting generate_samples!, generate_samples_dbl! and Fit! give the chains they create (their keyword lists stay the reference's):
+# BNRHip.XI_WEIGHTS[] = :reference before the call reproduces the reference's sampler also where its weights under/overflow
+const XI_WEIGHTS = Ref(:log)
+
 # X: the vector of n adjacency matrices (x_transform = true; setup_X!, gibbs.jl:239-247, runs on the device) or the n x q matrix
 # X_new (gibbs.jl:917-918) in its own element type
-function Chain(X, y::Vector{Float64}, R, tot_save, seed, c; x_transform=true, Î·=1.01, Î¶=1.0, Î¹=1.0, aÎ”=1.0, bÎ”=1.0, Î½=10, device=0)
+function Chain(X, y::Vector{Float64}, R, tot_save, seed, c; x_transform=true, Î·=1.01, Î¶=1.0, Î¹=1.0, aÎ”=1.0, bÎ”=1.0, Î½=10, device=0, xi_weights=:log)
+    xw = xi_weights_code(xi_weights)
     hy = Ref(Hyper(Î·, Î¶, Î¹, aÎ”, bÎ”, Î½))
     out = Ref{Ptr{Cvoid}}(C_NULL)
     if x_transform
@@ -74,10 +82,11 @@ function Chain(X, y::Vector{Float64}, R, tot_save, seed, c; x_transform=true, Î·
     end
     ch = Chain(out[], n, V, R, V * (V + 1) Ã· 2, tot_save)
     finalizer(destroy, ch)
+    xw == 0 || set_option!(ch, "xi_weights", xw)
     ch
 end
 
-# another chain of the same fit on the same GPU: X, y stay shared on the device (bnr_chain_create_like)
+# another chain of the same fit on the same GPU: X, y stay shared on the device, xi_weights is the donor's (bnr_chain_create_like)
 function chain_like(donor::Chain, seed, c, tot_save=donor.tot)
     out = Ref{Ptr{Cvoid}}(C_NULL)
     check(ccall((:bnr_chain_create_like, LIB), Cint, (Ptr{Cvoid}, UInt64, Int32, Int32, Ref{Ptr{Cvoid}}), donor.h, UInt64(seed), c, tot_save, out))
@@ -213,7 +222,7 @@ function generate_samples!(X, y, R; Î·=1.01, Î¶=1.0, Î¹=1.0, aÎ”=1.0, bÎ”=1.0, Î
     yv = Vector{Float64}(y)
     chains = Chain[]
     for c in ids
-        push!(chains, isempty(chains) ? Chain(X, yv, R, tot_save, seed, c; x_transform, Î·, Î¶, Î¹, aÎ”, bÎ”, Î½, device) :
+        push!(chains, isempty(chains) ? Chain(X, yv, R, tot_save, seed, c; x_transform, Î·, Î¶, Î¹, aÎ”, bÎ”, Î½, device, xi_weights = XI_WEIGHTS[]) :
                                         chain_like(chains[1], seed, c, tot_save))
     end
     foreach(init_prior!, chains)
@@ -272,7 +281,7 @@ function generate_samples_dbl!(X, y, R; Î·=1.01, Î¶=1.0, Î¹=1.0, aÎ”=1.0, bÎ”=1.
     yv = Vector{Float64}(y)
     chains = Chain[]
     for c in ids
-        push!(chains, isempty(chains) ? Chain(X, yv, R, tot_save, seed, c; x_transform, Î·, Î¶, Î¹, aÎ”, bÎ”, Î½, device) :
+        push!(chains, isempty(chains) ? Chain(X, yv, R, tot_save, seed, c; x_transform, Î·, Î¶, Î¹, aÎ”, bÎ”, Î½, device, xi_weights = XI_WEIGHTS[]) :
                                         chain_like(chains[1], seed, c, tot_save))
     end
     foreach(init_prior!, chains)
@@ -315,6 +324,7 @@ function Fit!(X, y, R; Î·=1.01, V=30, Î¶=1.0, Î¹=1.0, aÎ”=1.0, bÎ”=1.0, Î½=10, n
     # several ranks (comm given): every rank must run the SAME seed, or chain c on one rank is not the chain c the others assume -- refuse to draw one per rank
     isnothing(seed) && !isnothing(comm) && error("BNRHip: with a communicator the caller must pass ONE seed to every rank (draw it on rank 0 and broadcast it, gibbs.jl:739, 928)")
     seed = isnothing(seed) ? rand(1:55555) : seed                # (with several ranks the caller passes ONE seed to all of them, see generate_samples!)
+    xi_weights_code(XI_WEIGHTS[])                                 # a bad XI_WEIGHTS[] fails here, before parameters.log is written (its lines stay the reference's)
     if comm === nothing || comm.rank == 0
         open(filename, "w") do logfile
             write(logfile, "BayesianNetworkRegression.jl Fit! function\n")
