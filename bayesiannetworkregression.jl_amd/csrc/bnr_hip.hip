@@ -2257,6 +2257,7 @@ int bnr_chain_debug_time_gram(bnr_chain *c, int32_t reps, double *avg_us)
     for (int r = 0; r < reps; ++r) launch_gram_only(c);
     HIPNOTE(hipEventRecord(e1, c->x.stream));
     HIPCHK(hipMemsetAsync(c->d.gprog, 0, sizeof(unsigned int) * (c->d.ntile + 1), c->x.stream));   // these launches were not consumed by a factorization
+    HIPCHK(hipMemsetAsync(c->d.counters + 9, 0, sizeof(long long), c->x.stream));      // ... nor by a solve: a flag k_sdigits raised is not a gamma update's failure
     HIPCHK(hipStreamSynchronize(c->x.stream));
     float ms = 0;
     HIPNOTE(hipEventElapsedTime(&ms, e0, e1));

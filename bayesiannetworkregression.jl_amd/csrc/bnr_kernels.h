@@ -70,7 +70,8 @@ struct bnr_dev {
     double *Minv;                // R*R + 1: inv(M) and logdet M of the state the next k_node reads (written by k_tail)
     double *Psum;                // nblk_bp x (1+3R) partial sums from k_backproj
     int nblk_bp, chunk_bp;
-    long long *counters;         // [0] jitter, [1] nan_w, [2] sampler cap, [3] chol fail, [4..7] where, [8] branch-order violations
+    long long *counters;         // [0] jitter, [1] nan_w, [2] sampler cap, [3] chol fail, [4..7] where, [8] branch-order violations,
+                                 // [9] the G + I factorization of the running gamma update failed (bnr_flag_gfail; counted once by k_solve_w)
     unsigned long long *dbg;     // in-kernel s_memtime stamps (diagnostics only; never read by any kernel)
     unsigned int *stamp;         // one word per k_gram_reduce workgroup: iteration id of the Gram it finished (checked by k_chol_step)
     unsigned int *gprog;         // Gram progress: [tc] = finished (tile, K slice) tasks of tile column tc of the running sweep (read by
@@ -133,6 +134,11 @@ struct bnr_few {
     __device__ __forceinline__ bnr_dev get() const { return get_x(); }
     __device__ __forceinline__ bnr_dev at(int) const { return get_x(); }
 };
+// A failed factorization of G + I (a non-positive or non-finite pivot in any panel, a column of the panel pipeline that never arrived, a non-finite S in front of
+// the i8 Gram) is the reference's ONE PosDefException of gibbs.jl:434: every wave and launch that meets it only raises the chain's flag word, and k_solve_w --
+// the first launch behind the whole factorization -- turns the flag into one count (counters[3] and the "G+I" place counters[7]) and clears it.  So the count
+// is one per failed gamma update whatever the family, the number of panels that see the bad pivot or the group the chain runs in.
+__device__ __forceinline__ void bnr_flag_gfail(const bnr_dev &cd) { atomicOr((unsigned long long *)&cd.counters[9], 1ull); }
 
 #define BNR_EXP_SKIP_SCALAR() 0
 #define BNR_EXP_SKIP_CHOL(p) 0
@@ -1656,6 +1662,7 @@ __device__ __forceinline__ int bnr_panel_sweep(bnr_panel_lds &sh, const bnr_d4 &
 #define BNR_PIPE_HEAVY 0    // 1: a starved wave polls with all ten reads instead of one (one chain 169.5 against 168.0 us per sweep)
 #endif
 #define BNR_PIPE_SENT_HI 0x7FF8DEAD
+__device__ __forceinline__ double bnr_canon_nan(double v) { return v == v ? v : __hiloint2double(0x7FF80000, 0); }
 struct alignas(16) bnr_panelp_lds {
     double sD[BNR_NB * BNR_LP], sB[BNR_NB * BNR_LP];
     double sL[BNR_NB][64];
@@ -1976,10 +1983,12 @@ __device__ __forceinline__ int bnr_panel_sweep_pipe(bnr_panelp_lds &sh, const bn
 #pragma unroll
         for (int i = 0; i < 6; ++i) sl[tid + 256 * i] = sent;      // columns 0..23: what the waves 0..2 will publish
     }
+    // every NaN of the panel is staged as the canonical quiet NaN: data (a NaN loaded into S or X, its payload carried through the Gram and the updates) can
+    // then never alias the "not there yet" mark, whose payload no arithmetic on canonical NaNs produces -- a NaN panel fails at once instead of after the polls
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        sh.sD[(nt * 16 + ln) + BNR_LP * (mt * 16 + lq + 4 * r)] = cD[r];
-        sh.sB[(nt * 16 + ln) + BNR_LP * (mt * 16 + lq + 4 * r)] = cB[r];
+        sh.sD[(nt * 16 + ln) + BNR_LP * (mt * 16 + lq + 4 * r)] = bnr_canon_nan(cD[r]);
+        sh.sB[(nt * 16 + ln) + BNR_LP * (mt * 16 + lq + 4 * r)] = bnr_canon_nan(cB[r]);
     }
     __syncthreads();
 #ifdef BNR_STAMPS
@@ -2302,14 +2311,14 @@ __global__ __launch_bounds__(256, 1) void k_chol_step(const SRC chain_src, int p
 #else
     const int bad = bnr_panel_sweep_pipe(sh, cD, cB, tid, dst, ld);
 #endif
-    if (bad && lane == 0 && b == 0) { atomicAdd((unsigned long long *)&cd.counters[3], 1ull); atomicAdd((unsigned long long *)&cd.counters[7], 1ull); }
+    if (bad && lane == 0) bnr_flag_gfail(cd);
 #else
 #ifdef BNR_STAMPS
     const int bad = bnr_panel_sweep(sh, cD, cB, tid, dst, ld, b == 0 ? cd.dbg + 128 + p * 8 : nullptr);
 #else
     const int bad = bnr_panel_sweep(sh, cD, cB, tid, dst, ld);
 #endif
-    if (bad && tid == 0 && b == 0) { atomicAdd((unsigned long long *)&cd.counters[3], 1ull); atomicAdd((unsigned long long *)&cd.counters[7], 1ull); }
+    if (bad && tid == 0) bnr_flag_gfail(cd);
 #endif
     BNR_STAMP(3);
     BNR_STAMP(4);
@@ -2578,7 +2587,7 @@ __global__ __launch_bounds__(256, 1) void k_chol_step2(const SRC chain_src, int 
         }
     }
     __syncthreads();
-    if (bad && tid == 0 && bi == 0) { atomicAdd((unsigned long long *)&cd.counters[3], 1ull); atomicAdd((unsigned long long *)&cd.counters[7], 1ull); }
+    if (bad && tid == 0) bnr_flag_gfail(cd);
     // the swept own blocks; the diagonal blocks and block row b of panel a are needed by nobody later
     {
         const int r = tid & 31, c0 = tid >> 5;
@@ -2658,6 +2667,10 @@ __global__ __launch_bounds__(256) void k_solve_w(const SRC chain_src)
     for (int r = lane; r < rend; r += 64) acc = fma(col[r], cd.bw[r], acc);
     acc = wave_sum(acc);
     if (lane == 0) cd.wv[c] = acc;
+    if (blockIdx.x == 0 && threadIdx.x == 0 && cd.counters[9]) {    // (see bnr_flag_gfail: the healthy path reads one word off the solve's own chain)
+        cd.counters[9] = 0;
+        atomicAdd((unsigned long long *)&cd.counters[3], 1ull); atomicAdd((unsigned long long *)&cd.counters[7], 1ull);
+    }
     BNR_TL_OUT(cd, TL_SOLVE_W);
 }
 // k_solve_a4: a4_r = sum_{c >= block(r)} Y[r,c] w_c, then X gamma_new = X W + tau X sz + tau G a4, G a4 = b - a4
@@ -3614,6 +3627,7 @@ __global__ __launch_bounds__(1024) void k_sdigits(const SRC chain_src, int s)
     __shared__ double red[16];
     __shared__ int s_nonfinite;
     if (tid == 0) s_nonfinite = 0;
+    __syncthreads();                                          // the flag is cleared before any wave can set it
     double m = 0.0, m1 = 0.0, m2 = 0.0, m3 = 0.0;
     int k = tid;
     for (; k + 3072 < cd.q; k += 4096) { m = fmax(m, S[k]); m1 = fmax(m1, S[k + 1024]); m2 = fmax(m2, S[k + 2048]); m3 = fmax(m3, S[k + 3072]); }
@@ -3634,7 +3648,7 @@ __global__ __launch_bounds__(1024) void k_sdigits(const SRC chain_src, int s)
     m = red[0];
     for (int w = 1; w < 16; ++w) m = fmax(m, red[w]);
     if (s_nonfinite) {                                        // reported like a factorization that met a non-finite G + I (status 3, "G+I"); the digits below are then of no interest
-        if (tid == 0 && blockIdx.y == 0) { atomicAdd((unsigned long long *)&cd.counters[3], 1ull); atomicAdd((unsigned long long *)&cd.counters[7], 1ull); }
+        if (tid == 0) bnr_flag_gfail(cd);
         m = 1.0;
     }
     int e;

@@ -215,7 +215,9 @@ int bnr_rhat_from_stats(const double *stats, int32_t nchains, int32_t nparams, i
 
 /* event counters: out[0]=Cholesky jitter events, out[1]=NaN-weight events (node updates that took the fair coin of gibbs.jl:392-400; always 0
  * with the default log-space weights, which cannot under/overflow; see "xi_weights"),
- * out[2]=sampler attempt-cap events, out[3]=Cholesky hard failures, out[4..7] reserved */
+ * out[2]=sampler attempt-cap events, out[3]=Cholesky hard failures, out[4..7] where they happened (node, Psi, M, G+I).  A failed factorization of
+ * G + I counts ONE in out[3] and out[7] per chain and gamma update -- the reference's one PosDefException of gibbs.jl:434 -- whatever the
+ * factorization variant, the number of panels that meet the bad pivot, or the group the chain runs in */
 int bnr_chain_counters(bnr_chain *chain, int64_t out[8]);
 
 /* kernel timing: average device time in microseconds of the kernels of the last bnr_chain_run call, measured
@@ -285,7 +287,7 @@ int bnr_debug_set_exp(int32_t device, int32_t flags);
  *               larger; smaller problems default to 0): the model matrix came integer-typed with every entry 0 or 1
  *               (the reference's adjacency data, docs/src/man/inputdata.md:5-10) -- its Gram X diag(S) X' (gibbs.jl:434) runs on the i8 matrix pipe:
  *               S as i8L = 7 or 8 planes of balanced base-256 digits under the exponent of its largest entry (k_sdigits), one exact i32 Gram per plane
- *               (k_gram_i8, v_mfma_i32_16x16x64_i8), recombined in f64.  |G_i8 - G_exact| <= 8 q 2^(-8 i8L) max S <= 1e-12 max |G|; the tables
+ *               (k_gram_i8, v_mfma_i32_16x16x64_i8), recombined in f64.  |G_i8 - G_exact|_ij <= (X X')_ij 2^(e - 8 i8L + 1) <= 8 q 2^(-8 i8L) max S <= 1e-12 max |G| (S rounded to nearest: two-sided); the tables
  *               agree with the f64 Gram's to that size of perturbation (NOT bit for bit) and with the oracle to the same 1e-6 as everything
  *               else.  0: the f64 Gram also for a binary matrix.  A matrix that is not binary has no i8 path (setting 1 is refused).
  *               bnr_chain_last_timing(which = 4): *avg_us = 1 when the chain's (its group's) Gram runs on the i8 pipe, *launches = i8L.

@@ -1277,6 +1277,8 @@ def test_group_reports_the_most_severe_member_status(gpu):
             g.run(2, 2, 2)
         assert e.value.code == 3 and "Cholesky" in str(e.value), (order, e.value.code, str(e.value))
         assert capped.counters()["sampler_cap"] >= 1 and broken.counters()["chol_fail"] >= 1
+        c = broken.counters()      # the failed G + I is one count (one gamma update), whatever else the infinite S broke
+        assert c["where"][3] == 1 and c["chol_fail"] == sum(c["where"]), c
         g.close()
         capped.close(); broken.close()
 
@@ -1299,7 +1301,8 @@ def test_a_non_finite_S_is_reported_on_the_i8_gram_path_too(gpu):
             with pytest.raises(bnr_amd.BnrError) as e:
                 ch.run(2, 2, 2)
             assert e.value.code == 3, (gram_i8, bad, e.value.code, str(e.value))
-            assert ch.counters()["chol_fail"] >= 1
+            c = ch.counters()       # one gamma update: one G + I count, whether k_sdigits or the factorization found it
+            assert c["chol_fail"] >= 1 and c["where"][3] == 1 and c["chol_fail"] == sum(c["where"]), (gram_i8, bad, c)
             ch.close()
 
 
