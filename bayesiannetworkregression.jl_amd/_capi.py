@@ -69,6 +69,10 @@ _SIGS = {
     "bnr_chain_resize": (C.c_int, [C.c_void_p, C.c_int32]),
     "bnr_chain_rhat_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp]),
     "bnr_chain_summary": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
+    "bnr_chain_predict": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, C.c_int32] + [_dp] * 5),
+    "bnr_chain_predict_from_matrices": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_int32,
+                                                  C.c_int32] + [_dp] * 5),
+    "bnr_chain_loglik_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp]),
     "bnr_comm_unique_id": (C.c_int, [C.POINTER(UniqueId)]),
     "bnr_comm_create_rccl": (C.c_int, [C.POINTER(UniqueId), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "bnr_comm_create_callback": (C.c_int, [C.c_int32, C.c_int32, ALLGATHER_CB, C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -365,6 +369,35 @@ class Chain:
         mean, lo, hi, pxi = np.empty(self.q), np.empty(self.q), np.empty(self.q), np.empty(self.V)
         check(self.L.bnr_chain_summary(self.h, first_row, nsamp, k_lo, k_hi, _ptr(mean), _ptr(lo), _ptr(hi), _ptr(pxi)))
         return mean, lo, hi, pxi
+
+    def predict(self, X, first_row, nsamp, k_lo, k_hi, y=None, x_transform=False):
+        """Posterior of the mean response mu + x.gamma of new rows over the row window, on the device (bnr_chain_predict): (mean, k_lo-th
+        smallest, k_hi-th smallest, lpd, pwaic) per row; lpd / pwaic are None without y.  X as for Chain(): an m x q matrix in its own element
+        type, or (x_transform=True) a list of m V x V matrices."""
+        xi = X if isinstance(X, XInput) else XInput(X, x_transform)
+        if xi.q != self.q:
+            raise ValueError("the new rows have %d edge columns, the chain %d" % (xi.q, self.q))
+        m = xi.n
+        yf = None
+        if y is not None:
+            yf = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+            if yf.shape != (m,):
+                raise ValueError("y must have one entry per new row (%d), not %d" % (m, yf.size))
+        mean, lo, hi = np.empty(m), np.empty(m), np.empty(m)
+        lpd, pw = (np.empty(m), np.empty(m)) if yf is not None else (None, None)
+        tail = (_ptr(yf), int(k_lo), int(k_hi), _ptr(mean), _ptr(lo), _ptr(hi), _ptr(lpd), _ptr(pw))
+        if xi.from_matrices:
+            ptrs = (C.c_void_p * m)(*[a.ctypes.data for a in xi.data])
+            check(self.L.bnr_chain_predict_from_matrices(self.h, int(first_row), int(nsamp), m, ptrs, xi.dtype_code, *tail))
+        else:
+            check(self.L.bnr_chain_predict(self.h, int(first_row), int(nsamp), m, _ptr(xi.data), xi.dtype_code, *tail))
+        return mean, lo, hi, lpd, pw
+
+    def loglik_stats(self, first_row, nsamp):
+        """(lpd, pwaic) of the chain's own training rows over the row window, on the device (bnr_chain_loglik_stats)."""
+        lpd, pw = np.empty(self.n), np.empty(self.n)
+        check(self.L.bnr_chain_loglik_stats(self.h, int(first_row), int(nsamp), _ptr(lpd), _ptr(pw)))
+        return lpd, pw
 
     def ess_stats(self, first_row, nsamp, max_lag):
         out = np.empty(2 * (2 + max_lag) * (self.q + self.V))

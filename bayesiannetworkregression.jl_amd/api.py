@@ -15,6 +15,7 @@ Julia is not available in this image, so the thin host layer a Julia user would 
   return_psrf_VOI        gibbs.jl:771-789   -> return_psrf_VOI
   Results / BNRSummary   gibbs.jl:23-43     -> Results / BNRSummary
   Summary                gibbs.jl:1214-1250 -> Summary
+  (additions)                               -> Predict / BNRPrediction (posterior of the mean response of new rows), WAIC
   lower_triangle / create_lower_tri / setup_X!  utils.jl:17-57, gibbs.jl:239-247
 
 All sampling runs on the GPU through libbnr_hip.so; this file holds only the schedule logic (chain fan-out,
@@ -87,6 +88,8 @@ class Results:
     summary_device: dict = None      # filled on request: Summary statistics computed on the GPU (see Summary)
     essxi: np.ndarray = None         # filled on request (ess_max_lag=...): bulk effective sample sizes over all chains
     essgamma: np.ndarray = None
+    prediction: "BNRPrediction" = None   # filled on request (predict_X=...): posterior of the mean response of new rows, computed on the GPU (see Predict)
+    waic: dict = None                # filled on request (waic=True): WAIC of the training rows from the GPU's pointwise numbers (see WAIC)
 
 
 @dataclass
@@ -155,6 +158,113 @@ def Summary(results, interval=95, digits=3):
                 lower_bound=np.round(lo, digits), upper_bound=np.round(up, digits))
     xi = dict(probability=np.round(pxi, digits))
     return BNRSummary(edge, xi, interval)
+
+
+# ------------------------------------------------------------------------------------------ prediction and WAIC (additions to the reference)
+@dataclass
+class BNRPrediction:
+    """Posterior of the mean response eta = mu + x.gamma of new rows (y = mu + X gamma + eps, gibbs.jl:270, 432, 566) over chain 1's window:
+    estimate = posterior mean, lower_bound / upper_bound = the order statistics Summary uses for a ci_level% interval.  This is a credible
+    interval of the MEAN response, not a predictive interval for a new observation (which would add eps ~ N(0, tau2)).  With observed
+    responses: lpd = pointwise log predictive density log mean_s N(y_i | eta_is, tau2_s), elpd = its sum."""
+    estimate: np.ndarray
+    lower_bound: np.ndarray
+    upper_bound: np.ndarray
+    ci_level: int
+    lpd: np.ndarray = None
+    elpd: float = None
+
+
+def _prediction(mean, lo, hi, interval, lpd=None, digits=None):
+    r = (lambda a: a) if digits is None else (lambda a: np.round(a, digits))
+    return BNRPrediction(r(mean), r(lo), r(hi), interval, lpd, None if lpd is None else float(np.sum(lpd)))
+
+
+def _new_rows(X_new, x_transform, q, y_new=None):
+    """the new rows as an XInput (element type kept) after the checks every prediction path makes first: q columns, one y per row"""
+    xi = X_new if isinstance(X_new, XInput) else XInput(X_new, x_transform)
+    if xi.q != q:
+        raise ValueError("the new rows have %d edge columns (V = %d), the fit %d" % (xi.q, xi.V, q))
+    if y_new is not None and np.asarray(y_new).reshape(-1).shape[0] != xi.n:
+        raise ValueError("y_new must have one entry per new row (%d), not %d" % (xi.n, np.asarray(y_new).size))
+    return xi
+
+
+def _dense_rows(xi):
+    """an XInput as the n x q float64 matrix (host paths)"""
+    if xi.from_matrices:
+        return np.stack([lower_triangle(a) for a in xi.data]).astype(np.float64)
+    return np.asarray(xi.data, dtype=np.float64)
+
+
+def _host_eta(state, X, nburn, nsamp):
+    """eta[i, s] = mu_s + X[i] . gamma_s over rows nburn+1 .. nburn+nsamp of a fetched table"""
+    g = state["gamma"][nburn:nburn + nsamp, :, 0]
+    mu = state["mu"][nburn:nburn + nsamp, 0, 0]
+    return mu[None, :] + X @ g.T
+
+
+def _host_pointwise(state, X, y, nburn, nsamp):
+    """(lpd, pwaic) per row: log-mean-exp and the ddof-1 variance over the draws of log N(y_i | eta_is, tau2_s)"""
+    eta = _host_eta(state, X, nburn, nsamp)
+    tau2 = state["tau2"][nburn:nburn + nsamp, 0, 0]
+    ll = -0.5 * (math.log(2 * math.pi) + np.log(tau2))[None, :] - (np.asarray(y, dtype=np.float64).reshape(-1, 1) - eta) ** 2 / (2 * tau2[None, :])
+    mx = ll.max(axis=1)
+    return mx + np.log(np.mean(np.exp(ll - mx[:, None]), axis=1)), ll.var(axis=1, ddof=1)
+
+
+def _waic_from_pointwise(lpd, pwaic):
+    """WAIC as in Vehtari, Gelman & Gabry (2017) / ArviZ: elpd_waic = sum(lpd_i - p_waic_i), waic = -2 elpd_waic, se = sqrt(n Var_i(elpd_i))"""
+    lpd, pwaic = np.asarray(lpd, dtype=np.float64), np.asarray(pwaic, dtype=np.float64)
+    e = lpd - pwaic
+    elpd = float(np.sum(e))
+    return dict(elpd_waic=elpd, p_waic=float(np.sum(pwaic)), waic=-2.0 * elpd, se=float(math.sqrt(e.size * np.var(e))),
+                lpd_i=lpd, p_waic_i=pwaic, elpd_waic_i=e)
+
+
+def device_predict(chain, nburn, nsamp, X_new, y_new=None, interval=95, x_transform=False):
+    """Predict's statistics for new rows computed on the GPU over rows nburn+1 .. nburn+nsamp of `chain` (bnr_chain_predict)."""
+    xi = _new_rows(X_new, x_transform, chain.q, y_new)
+    lw, hi = _summary_ranks(nsamp, interval)
+    mean, lo, up, lpd, _pw = chain.predict(xi, nburn + 1, nsamp, lw, hi, y=y_new)
+    return _prediction(mean, lo, up, interval, lpd)
+
+
+def Predict(results, X_new=None, y_new=None, interval=95, x_transform=True, digits=None):
+    """Posterior of the mean response mu + x.gamma of new rows over chain 1's sampled window (the rows Summary reads) -> BNRPrediction.
+    X_new None: the prediction the fit computed on the GPU (Fit(..., predict_X=..., predict_y=..., predict_interval=...)).  X_new given: computed
+    on the host from results.state (needs return_state=True); X_new in the fit's x_transform format (list of V x V matrices, or n x q)."""
+    nburn, nsamp = results.burn_in, results.sampled
+    if X_new is None:
+        p = results.prediction
+        if p is None:
+            raise ValueError("the fit computed no prediction: pass X_new (with return_state=True) or fit with predict_X=...")
+        if p.ci_level != interval:
+            raise ValueError("the fit's prediction has a %s%% interval, not %s%%: pass X_new to recompute" % (p.ci_level, interval))
+        return _prediction(p.estimate, p.lower_bound, p.upper_bound, p.ci_level, p.lpd, digits)
+    if results.state is None:
+        raise ValueError("Predict with X_new needs the state table (Fit(..., return_state=True)), or fit with predict_X=... to predict on the GPU")
+    q = results.state["gamma"].shape[1]
+    xi = _new_rows(X_new, x_transform, q, y_new)
+    lw, hi = _summary_ranks(nsamp, interval)
+    X = _dense_rows(xi)
+    eta = _host_eta(results.state, X, nburn, nsamp)
+    srt = np.sort(eta, axis=1)
+    lpd = None if y_new is None else _host_pointwise(results.state, X, y_new, nburn, nsamp)[0]
+    return _prediction(eta.mean(axis=1), srt[:, lw - 1], srt[:, hi - 1], interval, lpd, digits)
+
+
+def WAIC(results, X=None, y=None, x_transform=True):
+    """WAIC of the training rows over chain 1's sampled window (Vehtari, Gelman & Gabry 2017; names as ArviZ): dict with elpd_waic, p_waic,
+    waic = -2 elpd_waic, se and the pointwise lpd_i, p_waic_i, elpd_waic_i.  Uses the GPU's numbers when the fit carried them (waic=True);
+    otherwise the host formula over results.state with the training X, y passed in."""
+    if results.waic is not None:
+        return results.waic
+    if results.state is None or X is None or y is None:
+        raise ValueError("WAIC needs Fit(..., waic=True), or the state table (return_state=True) together with the training X and y")
+    xi = _new_rows(X, x_transform, results.state["gamma"].shape[1], y)
+    lpd, pw = _host_pointwise(results.state, _dense_rows(xi), y, results.burn_in, results.sampled)
+    return _waic_from_pointwise(lpd, pw)
 
 
 # ------------------------------------------------------------------------------------------ chain placement
@@ -381,8 +491,9 @@ def return_psrf_VOI(chainset, nburn, nsamp, fetch_state=True, summary_interval=N
     return Results(state, rx, rg, nburn, nsamp, dev)
 
 
-def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None):
-    """The Results a fit returns: chain 1's table (states[1], gibbs.jl:788) and/or its Summary statistics from the device."""
+def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None, predict=None, waic=False):
+    """The Results a fit returns: chain 1's table (states[1], gibbs.jl:788) and/or its Summary statistics from the device; predict =
+    (new rows, their y or None, interval) and waic=True add the prediction and WAIC computed on the device over the same window."""
     if ess_max_lag is not None:                       # collective over ranks, like the PSRF
         res.essgamma, res.essxi = chainset.ess(res.burn_in + 1, res.sampled, ess_max_lag if ess_max_lag > 0 else None)
     if 1 in chainset.chains:
@@ -392,7 +503,21 @@ def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None):
             ch.fetch(1, ch.tot, res.state)
         if summary_interval is not None:
             res.summary_device = device_summary(ch, res.burn_in, res.sampled, summary_interval)
+        if predict is not None:
+            res.prediction = device_predict(ch, res.burn_in, res.sampled, predict[0], predict[1], predict[2])
+        if waic:
+            res.waic = _waic_from_pointwise(*ch.loglik_stats(res.burn_in + 1, res.sampled))
     return res
+
+
+def _predict_request(predict_X, predict_y, predict_interval, x_transform, X_new):
+    """Fit's predict_X / predict_y checked before any sampling: (new rows, y, interval) for _finish, or None"""
+    if predict_X is None:
+        if predict_y is not None:
+            raise ValueError("predict_y needs predict_X")
+        return None
+    xi = _new_rows(predict_X, x_transform, X_new.q, predict_y)
+    return xi, None if predict_y is None else np.asarray(predict_y, dtype=np.float64).reshape(-1), predict_interval
 
 
 class _Progress:
@@ -422,7 +547,7 @@ def _normalize_purge(purge_burn, nburn):
 def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=10, nburn=30000, nsamp=20000,
                      maxburn=50000, psrf_cutoff=1.2, x_transform=True, suppress_timer=False, num_chains=2, seed=None,
                      purge_burn=None, device=None, _keep=None, return_state=True, summary_interval=None, ess_max_lag=None,
-                     xi_weights="log"):
+                     xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False):
     """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
     xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
     xi_weights_code(xi_weights)
@@ -431,6 +556,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
     elif nu == R:
         print("Warning: ν==R may give poor accuracy. Consider increasing ν")
     X_new = XInput(X, x_transform)                 # X_new of gibbs.jl:907-918: element type kept, setup_X! runs on the device
+    pred = _predict_request(predict_X, predict_y, predict_interval, x_transform, X_new)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -472,7 +598,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
         print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()), file=sys.stderr)
     print("R = %s nu=%s nburn= %d nsamp = %d" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f\n" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
-    res = _finish(cs, res, return_state, summary_interval, ess_max_lag)
+    res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic)
     if _keep is None:
         cs.close()
     return res
@@ -481,7 +607,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
 def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=10, mingen=10000,
                          maxgen=100000, psrf_cutoff=1.01, x_transform=True, suppress_timer=False, num_chains=2,
                          seed=None, purge_burn=None, device=None, return_state=True, summary_interval=None, ess_max_lag=None,
-                         xi_weights="log"):
+                         xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False):
     """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
     xi_weights_code(xi_weights)
     if nu == R:
@@ -489,6 +615,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
     nburn = _julia_round(mingen / 2)
     nsamp = mingen - nburn
     X_new = XInput(X, x_transform)
+    pred = _predict_request(predict_X, predict_y, predict_interval, x_transform, X_new)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -532,7 +659,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
         print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()), file=sys.stderr)
     print("\nR = %s nu=%s nburn= %d nsamp = %d\n" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.4f. Max PSRF Gamma: %.4f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
-    res = _finish(cs, res, return_state, summary_interval, ess_max_lag)
+    res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic)
     cs.close()
     return res
 
@@ -540,13 +667,16 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
 def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=10, nburn=30000, nsamples=20000,
         mingen=0, maxgen=0, psrf_cutoff=1.01, x_transform=True, suppress_timer=False, num_chains=2, seed=None,
         purge_burn=None, filename="parameters.log", device=None, return_state=True, summary_interval=None, ess_max_lag=None,
-        xi_weights="log"):
+        xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False):
     """Fit! (gibbs.jl:725-751).  The `V` keyword is accepted and ignored, as in the reference.
     Extensions: summary_interval=95 computes Summary's statistics on the GPU (Results.summary_device);
     return_state=False then leaves the (large) state table on the device and frees it; ess_max_lag=0 (default lag
     window) or a lag count adds bulk effective sample sizes over all chains (Results.essgamma / essxi);
     xi_weights="reference" samples xi with the reference's own weight arithmetic, under/overflow included (the default "log" never
-    under/overflows; include/bnr_hip.h, option "xi_weights").  parameters.log keeps the reference's lines only."""
+    under/overflows; include/bnr_hip.h, option "xi_weights"); predict_X (new rows in the x_transform format of X), predict_y (their observed
+    responses, optional) and predict_interval compute the posterior of the mean response of those rows on the GPU (Results.prediction, see
+    Predict), waic=True the WAIC of the training rows (Results.waic, see WAIC) -- over chain 1's window, as Summary.  parameters.log keeps the
+    reference's lines only."""
     xi_weights_code(xi_weights)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
@@ -564,9 +694,10 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                                     maxgen=maxgen, psrf_cutoff=psrf_cutoff, x_transform=x_transform, suppress_timer=suppress_timer,
                                     num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
                                     return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
-                                    xi_weights=xi_weights)
+                                    xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval,
+                                    waic=waic)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
                             return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
-                            xi_weights=xi_weights)
+                            xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic)

@@ -1,7 +1,7 @@
 // bnr_hip.hip -- C ABI (include/bnr_hip.h) over the gfx950 kernels in bnr_kernels.h.
 // Host side: chain allocation (own or shared device inputs), the run! loop with the purge ring (gibbs.jl:849-864) for one
 // chain or for a lockstep group of chains (one launch per kernel for all members), the test hooks that mirror the
-// reference's update_*! functions, table fetch/load, the split-Rhat / ESS messages and the device-side Summary.
+// reference's update_*! functions, table fetch/load, the split-Rhat / ESS messages, the device-side Summary and posterior prediction.
 #include "../../include/bnr_hip.h"
 #include "bnr_kernels.h"
 
@@ -114,6 +114,7 @@ struct bnr_chain {
     const unsigned char *x8_kept = nullptr;   // the byte image of X (also while option "byte_x" is 0); nullptr: the input had none
     const unsigned char *xm_kept = nullptr;   // the byte MASK of a 0/1 model matrix for the i8 Gram (also while option "gram_i8" is 0); nullptr: the input was not binary
     long long cap_seen = 0;      // sampler-cap events already reported (the device counter is cumulative: a capped draw is reported by the call it happened in, once)
+    int predict_block_rows = 0;  // tunable "predict_block_rows": rows per block of bnr_chain_predict / bnr_chain_loglik_stats (0: automatic)
 };
 
 struct bnr_group {
@@ -148,6 +149,23 @@ struct bnr_exec;
 static int late_kernels_lds_attributes(int bytes);
 static void launch_late_xpass_group2(bnr_exec &x, int s);
 static void launch_late_backproj64(bnr_exec &x, int s, int flags, size_t lds64);
+// device temporaries of one call, freed on every path (zeroed on the chain's stream, see dev_alloc)
+struct dev_tmp {
+    std::vector<void *> p;
+    ~dev_tmp() { for (void *q : p) (void)hipFree(q); }
+    template <typename T>
+    int alloc(T **out, size_t count, hipStream_t st)
+    {
+        void *q = nullptr;
+        HIPCHK(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
+        p.push_back(q);
+        HIPCHK(hipMemsetAsync(q, 0, std::max<size_t>(count, 1) * sizeof(T), st));
+        *out = (T *)q;
+        return BNR_OK;
+    }
+};
+static int predict_rows(bnr_chain *c, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, int k_lo, int k_hi,
+                        double *mean_d, double *lo_d, double *hi_d, double *lpd_d, double *pwaic_d, dev_tmp &tmp);
 static int ensure_lds_attributes(int device)
 {
     static std::mutex mu;
@@ -2114,6 +2132,105 @@ int bnr_chain_ess_stats(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t 
     return check_launch("k_acov");
 }
 
+// Posterior of the mean response mu + x . gamma of m new rows over rows first_row .. first_row+nsamp-1 of this chain (an addition to the
+// reference): X_pred goes to the device in its own element type and is converted there (k_x_convert with m rows), then predict_rows.
+static int predict_call(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const x_source &xs, const double *y, int32_t k_lo, int32_t k_hi,
+                        double *mean, double *lower, double *upper, double *lpd, double *pwaic)
+{
+    if (!c || !mean || !lower || !upper || (!xs.X && !xs.mats) || (y && (!lpd || !pwaic))) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+    const bnr_dev &d = c->d;
+    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    if (k_lo < 1 || k_lo > nsamp || k_hi < 1 || k_hi > nsamp) return fail(BNR_ERR_BAD_ARG, "order statistics must be between 1 and nsamp");
+    if (m < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows");
+    if (xs.dtype < BNR_F64 || xs.dtype > BNR_F32) return fail(BNR_ERR_BAD_ARG, "unknown element type of X");
+    if (xs.mats) for (int i = 0; i < m; ++i) if (!xs.mats[i]) return fail(BNR_ERR_BAD_ARG, "NULL adjacency matrix");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->x.stream;
+    const int m_pad = round_up(m, 32), q16 = round_up(d.q, 16);
+    dev_tmp tmp;
+    double *Xd = nullptr, *yd = nullptr, *out = nullptr;
+    int rc;
+    if ((rc = tmp.alloc(&Xd, (size_t)m_pad * q16, st))) return rc;             // zero rows m .. m_pad - 1 and columns q .. q16 - 1 (k_predict)
+    if ((rc = tmp.alloc(&out, (size_t)5 * m, st))) return rc;
+    const size_t es = dtype_size(xs.dtype);
+    if (!xs.mats && xs.dtype == BNR_F64) {
+        HIPCHK(hipMemcpy2DAsync(Xd, (size_t)m_pad * sizeof(double), xs.X, (size_t)m * sizeof(double), (size_t)m * sizeof(double), d.q, hipMemcpyHostToDevice, st));
+    } else {
+        char *raw = nullptr;
+        const size_t count = xs.mats ? (size_t)m * d.V * d.V : (size_t)m * d.q;
+        if ((rc = tmp.alloc(&raw, count * es, st))) return rc;
+        if (xs.mats) {
+            for (int i = 0; i < m; ++i) HIPCHK(hipMemcpyAsync(raw + (size_t)i * d.V * d.V * es, xs.mats[i], (size_t)d.V * d.V * es, hipMemcpyHostToDevice, st));
+        } else HIPCHK(hipMemcpyAsync(raw, xs.X, count * es, hipMemcpyHostToDevice, st));
+        const dim3 grid((m + 63) / 64, std::min(d.q, 65535)), block(64);
+        const bool fm = xs.mats != nullptr;
+        switch (xs.dtype) {
+        case BNR_U8:  hipLaunchKernelGGL(k_x_convert<uint8_t>, grid, block, 0, st, (const uint8_t *)raw, fm, m, d.V, d.q, m_pad, d.ek, d.el, Xd, (unsigned char *)nullptr, (int *)nullptr); break;
+        case BNR_I32: hipLaunchKernelGGL(k_x_convert<int32_t>, grid, block, 0, st, (const int32_t *)raw, fm, m, d.V, d.q, m_pad, d.ek, d.el, Xd, (unsigned char *)nullptr, (int *)nullptr); break;
+        case BNR_I64: hipLaunchKernelGGL(k_x_convert<int64_t>, grid, block, 0, st, (const int64_t *)raw, fm, m, d.V, d.q, m_pad, d.ek, d.el, Xd, (unsigned char *)nullptr, (int *)nullptr); break;
+        case BNR_F32: hipLaunchKernelGGL(k_x_convert<float>, grid, block, 0, st, (const float *)raw, fm, m, d.V, d.q, m_pad, d.ek, d.el, Xd, (unsigned char *)nullptr, (int *)nullptr); break;
+        default:      hipLaunchKernelGGL(k_x_convert<double>, grid, block, 0, st, (const double *)raw, fm, m, d.V, d.q, m_pad, d.ek, d.el, Xd, (unsigned char *)nullptr, (int *)nullptr); break;
+        }
+    }
+    if (y) {
+        if ((rc = tmp.alloc(&yd, (size_t)m, st))) return rc;
+        HIPCHK(hipMemcpyAsync(yd, y, sizeof(double) * m, hipMemcpyHostToDevice, st));
+    }
+    if ((rc = predict_rows(c, first_row, nsamp, m, Xd, m_pad, yd, k_lo, k_hi, out, out + m, out + 2 * (size_t)m, y ? out + 3 * (size_t)m : nullptr,
+                           y ? out + 4 * (size_t)m : nullptr, tmp))) return rc;
+    std::vector<double> host(5 * (size_t)m);
+    hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("predict: ") + hipGetErrorString(e));
+    if ((rc = check_launch("k_predict"))) return rc;
+    memcpy(mean, host.data(), sizeof(double) * m);
+    memcpy(lower, host.data() + m, sizeof(double) * m);
+    memcpy(upper, host.data() + 2 * (size_t)m, sizeof(double) * m);
+    if (y) {
+        memcpy(lpd, host.data() + 3 * (size_t)m, sizeof(double) * m);
+        memcpy(pwaic, host.data() + 4 * (size_t)m, sizeof(double) * m);
+    }
+    return BNR_OK;
+}
+int bnr_chain_predict(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const void *X, int32_t x_dtype, const double *y,
+                      int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic)
+{
+    x_source xs;
+    xs.X = X; xs.dtype = x_dtype;
+    return predict_call(c, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic);
+}
+int bnr_chain_predict_from_matrices(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const void *const *A, int32_t x_dtype,
+                                    const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic)
+{
+    x_source xs;
+    xs.mats = A; xs.dtype = x_dtype;
+    return predict_call(c, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic);
+}
+// pointwise lpd and WAIC penalty of the chain's own training rows: X (n_pad x q_pad, zero padded) and y are on the device already
+int bnr_chain_loglik_stats(bnr_chain *c, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic)
+{
+    if (!c || !lpd || !pwaic) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+    const bnr_dev &d = c->d;
+    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->x.stream;
+    dev_tmp tmp;
+    double *out = nullptr;
+    int rc;
+    if ((rc = tmp.alloc(&out, (size_t)2 * d.n, st))) return rc;
+    if ((rc = predict_rows(c, first_row, nsamp, d.n, d.X, d.n_pad, d.y, 0, 0, nullptr, nullptr, nullptr, out, out + d.n, tmp))) return rc;
+    std::vector<double> host(2 * (size_t)d.n);
+    hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("loglik_stats: ") + hipGetErrorString(e));
+    if ((rc = check_launch("k_pred_loglik"))) return rc;
+    memcpy(lpd, host.data(), sizeof(double) * d.n);
+    memcpy(pwaic, host.data() + d.n, sizeof(double) * d.n);
+    return BNR_OK;
+}
+
 // Bulk effective sample size over all chains from the gathered messages (the estimator of Vehtari et al. 2021 as in
 // Stan / MCMCDiagnosticTools.ess: split chains, rho_t = 1 - (W - mean acov_t) / var+, Geyer's initial positive and monotone
 // sequence on the pair sums), truncated at max_lag.  NaN for a constant parameter.
@@ -2310,6 +2427,12 @@ int bnr_chain_set_option(bnr_chain *c, const char *name, int64_t value)
         if (c->group) drop_graph(c->group->x);
         return sync_dev(c);
     }
+    if (!strcmp(name, "predict_block_rows")) {
+        // performance only: rows per block of the prediction calls (their E buffer holds rows x nsamp doubles); rounded up to whole 32-row tiles
+        if (value < 0 || value > (1 << 24)) return fail(BNR_ERR_BAD_ARG, "predict_block_rows must be between 0 (automatic) and 2^24");
+        c->predict_block_rows = (int)value;
+        return BNR_OK;
+    }
     if (!strcmp(name, "byte_x")) {
         // 0: the X passes read the f64 matrix also when a byte image exists; 1: back to the byte image (if the input had one)
         if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
@@ -2338,4 +2461,42 @@ static void launch_late_xpass_group2(bnr_exec &x, int s)
 { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_xpass_group2<0>), dim3(x.shape->nblk_x * ((x.shape->n_pad + 255) / 256)), dim3(256), 16 * x.shape->chunk_x * sizeof(double), x.stream, bnr_many{x.cds}, s, x.nb); }
 static void launch_late_backproj64(bnr_exec &x, int s, int flags, size_t lds64)
 { BNR_LAUNCH(k_backproj64, dim3(round_up((x.shape->nblk_bp + 1) / 2, 8) * x.nb), dim3(256), lds64, x.stream, x, s, flags, x.nb); }
+
+// The device work of bnr_chain_predict / bnr_chain_loglik_stats, eagerly on the chain's own stream: the m rows of X (device, column-major,
+// leading dimension ldx, zero in columns q .. q16 - 1 and readable for whole 32-row tiles) in blocks of rows whose E buffer (rows x nsamp
+// doubles) stays near 1 GiB; per block k_predict, then k_summary (mean, k_lo-th / k_hi-th smallest of every E column; skipped when mean_d is
+// NULL) and k_pred_loglik (when yd is given).  Blocks start at multiples of 32 rows, so an output's MFMA tile position and K order -- and
+// with them every result, bit for bit -- do not depend on the block size.
+static int predict_rows(bnr_chain *c, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, int k_lo, int k_hi,
+                        double *mean_d, double *lo_d, double *hi_d, double *lpd_d, double *pwaic_d, dev_tmp &tmp)
+{
+    const bnr_dev &d = c->d;
+    hipStream_t st = c->x.stream;
+    const size_t budget = (size_t)1 << 30;
+    long long blk = c->predict_block_rows > 0 ? c->predict_block_rows : (long long)(budget / ((size_t)nsamp * sizeof(double))) / 32 * 32;
+    blk = std::min<long long>(round_up((int)std::max<long long>(blk, 1), 32), round_up(m, 32));
+    double *E = nullptr, *tau2 = nullptr;
+    int rc;
+    if ((rc = tmp.alloc(&E, (size_t)blk * nsamp, st))) return rc;
+    if (yd) {
+        if ((rc = tmp.alloc(&tau2, (size_t)nsamp, st))) return rc;
+        hipLaunchKernelGGL(k_fetch_cols, dim3(1, (nsamp + 31) / 32), dim3(32, 8), 0, st, (const double *)d.trace, d.rowlen, (int)ROW_TAU2, 1, first_row - 1, nsamp, tau2);
+    }
+    const int q16 = round_up(d.q, 16);
+    for (int i0 = 0; i0 < m; i0 += (int)blk) {
+        const int mr = std::min<int>((int)blk, m - i0);
+        if (mr > 16)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<2>), dim3((nsamp + 127) / 128, (mr + 31) / 32), dim3(256), 0, st, Xd + i0, ldx, q16,
+                               (const double *)d.trace, d.rowlen, d.o_gamma, first_row - 1, nsamp, mr, E);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<1>), dim3((nsamp + 127) / 128, 1), dim3(256), 0, st, Xd + i0, ldx, q16,
+                               (const double *)d.trace, d.rowlen, d.o_gamma, first_row - 1, nsamp, mr, E);
+        if (mean_d)
+            hipLaunchKernelGGL(k_summary, dim3(mr), dim3(256), 0, st, (const double *)E, nsamp, mr, k_lo, k_hi, mean_d + i0, lo_d + i0, hi_d + i0);
+        if (yd)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pred_loglik<0>), dim3(mr), dim3(256), 0, st, (const double *)E, nsamp, yd + i0, (const double *)tau2,
+                               lpd_d + i0, pwaic_d + i0);
+    }
+    return check_launch("k_predict");
+}
 }

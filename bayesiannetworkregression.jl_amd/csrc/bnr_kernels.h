@@ -21,7 +21,7 @@
 // Every sweep kernel exists for ONE chain (descriptor by value: bnr_one) and for a lockstep group of chains (device array
 // of descriptors indexed by the grid's chain coordinate: bnr_many); the arithmetic of a chain is the same in both.
 // Outside the sweep: k_init_prior (initialize_variables!), k_fetch_cols / k_load_cols (Table layout), k_rhat_stats
-// (split-Rhat message), k_summary (Summary statistics).
+// (split-Rhat message), k_summary (Summary statistics), k_predict / k_pred_loglik (posterior of the mean response of new rows, lpd and WAIC penalty).
 //   k_x_mask, k_sdigits, k_gram_i8   the Gram of a binary (0/1) model matrix on the i8 matrix pipe (round 5)
 // The measured experiments of rounds 3-4 (persistent / resident Gram kernels, left-looking and data-flow factorizations, gates, ...) are not
 // part of this tree any more: tools/experiments/ keeps their kernels and drivers for the record (they built against the round-4 tree).
@@ -3670,4 +3670,100 @@ __global__ __launch_bounds__(1024) void k_sdigits(const SRC chain_src, int s)
             cd.Sdig[(size_t)l * cd.kslab + idx] = (unsigned char)(b & 255u);
         }
     }
+}
+
+// ===================================================================================== posterior prediction (an addition to the reference)
+// The mean response of a row x under draw s of the window is eta_s = mu_s + x . gamma_s (y = mu + X gamma + eps, gibbs.jl:270, 432, 566).
+// Both kernels are templates referenced only from the end of bnr_hip.hip, so that they sit behind the sweep kernels in the code object.
+//
+// k_predict: E[i nsamp + s] = mu_s + sum_e X[i, e] gamma_s[e] for the rows i < mrows of a block and the samples s < nsamp, by
+// v_mfma_f64_16x16x4_f64 with A = a 16-row tile of X, B = gamma^T of 16 samples.  X: column-major, leading dimension ldx, zero in
+// the columns q .. q16 - 1 (q16 = q rounded up to 16) and readable (zero) for 16 TI rows of every tile; gamma_s: trace row
+// first0 + s at o_gamma, K-contiguous (the columns q .. q16 - 1 of a trace row are the zero padding in front of S).
+// K order: one accumulator per output, k0 = 0, 16, ... < q16; inside a step the MFMA t (0..3) takes k = k0 + 4 g + t from lane group
+// g = lane >> 4 -- so a lane reads 32 contiguous bytes of its gamma row per step, and X one coalesced 128-byte column piece per
+// (tile, t).  The order of an output's sum is fixed by q alone (not by the grid, the block of rows, m or nsamp); its place in an MFMA
+// tile is (i mod 16, s mod 16) whatever the launch.  D layout of the f64 MFMA: lane l, reg r = row (l >> 4) + 4 r, column l & 15.
+// grid = (ceil(nsamp / 128), ceil(mrows / (16 TI))), 256 threads: wave w owns samples blockIdx.x 128 + 32 w .. + 31 and the TI row
+// tiles of blockIdx.y.  Samples past nsamp read the last sample's row and are not stored.
+template <int TI>
+__global__ __launch_bounds__(256) void k_predict(const double *X, int ldx, int q16, const double *trace, int rowlen, int o_gamma, int first0,
+                                                 int nsamp, int mrows, double *E)
+{
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
+    const int i0 = blockIdx.y * 16 * TI, s0 = blockIdx.x * 128 + w * 32;
+    if (s0 >= nsamp) return;
+    const double *xa[TI];
+#pragma unroll
+    for (int a = 0; a < TI; ++a) xa[a] = X + (size_t)(i0 + 16 * a + c) + (size_t)ldx * (4 * g);
+    const double *gb[2];
+    double mu[2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const double *row = trace + (size_t)(first0 + min(s0 + 16 * b + c, nsamp - 1)) * rowlen;
+        gb[b] = row + o_gamma + 4 * g;
+        mu[b] = row[ROW_MU];
+    }
+    const size_t xstep = (size_t)ldx * 16;
+    bnr_d4 acc[TI][2];
+#pragma unroll
+    for (int a = 0; a < TI; ++a) { acc[a][0] = bnr_d4{0.0, 0.0, 0.0, 0.0}; acc[a][1] = bnr_d4{0.0, 0.0, 0.0, 0.0}; }
+    for (int k0 = 0; k0 < q16; k0 += 16) {
+        double av[TI][4];
+#pragma unroll
+        for (int a = 0; a < TI; ++a) {
+#pragma unroll
+            for (int t = 0; t < 4; ++t) av[a][t] = xa[a][(size_t)ldx * t];
+            xa[a] += xstep;
+        }
+        const bnr_d4 b0 = *(const bnr_d4 *)(gb[0] + k0), b1 = *(const bnr_d4 *)(gb[1] + k0);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+#pragma unroll
+            for (int a = 0; a < TI; ++a) {
+                acc[a][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[a][t], b0[t], acc[a][0], 0, 0, 0);
+                acc[a][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[a][t], b1[t], acc[a][1], 0, 0, 0);
+            }
+        }
+    }
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const int s = s0 + 16 * b + c;
+        if (s >= nsamp) continue;
+#pragma unroll
+        for (int a = 0; a < TI; ++a)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int i = i0 + 16 * a + g + 4 * r;
+                if (i < mrows) E[(size_t)i * nsamp + s] = mu[b] + acc[a][b][r];
+            }
+    }
+}
+
+// k_pred_loglik: pointwise log predictive density and WAIC penalty of the observed responses y[i] of the rows of a block, from the
+// column E[i nsamp ..] of k_predict and tau2_s (fetched by k_fetch_cols):  l_s = -(log 2 pi + log tau2_s) / 2 - (y_i - E_is)^2 / (2 tau2_s),
+// lpd_i = max_s l_s + log(sum_s exp(l_s - max) / nsamp) (log-mean-exp), pwaic_i = Var_s(l_s) (ddof 1, two passes).  One workgroup of
+// 256 threads per row; every sum in the fixed order of k_summary (thread-strided partial sums, then a tree).
+#define BNR_LOG_2PI 1.8378770664093454836
+template <int LATE>
+__global__ __launch_bounds__(256) void k_pred_loglik(const double *E, int nsamp, const double *y, const double *tau2, double *lpd, double *pwaic)
+{
+    __shared__ double ra[256], rb[256];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const double *e = E + (size_t)i * nsamp;
+    const double yi = y[i];
+    auto ell = [&](int s) { const double t = tau2[s], r = yi - e[s]; return -0.5 * (BNR_LOG_2PI + log(t)) - r * r / (2.0 * t); };
+    double mx = -INFINITY, sum = 0.0;
+    for (int s = tid; s < nsamp; s += 256) { const double l = ell(s); mx = fmax(mx, l); sum += l; }
+    ra[tid] = mx; rb[tid] = sum;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) { if (tid < w) { ra[tid] = fmax(ra[tid], ra[tid + w]); rb[tid] += rb[tid + w]; } __syncthreads(); }
+    const double M = ra[0], mean = rb[0] / nsamp;
+    __syncthreads();
+    double se = 0.0, sv = 0.0;
+    for (int s = tid; s < nsamp; s += 256) { const double l = ell(s), dl = l - mean; se += exp(l - M); sv += dl * dl; }
+    ra[tid] = se; rb[tid] = sv;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) { if (tid < w) { ra[tid] += ra[tid + w]; rb[tid] += rb[tid + w]; } __syncthreads(); }
+    if (tid == 0) { lpd[i] = M + log(ra[0] / nsamp); pwaic[i] = rb[0] / (nsamp - 1); }
 }

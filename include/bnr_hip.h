@@ -28,9 +28,10 @@
 extern "C" {
 #endif
 
-#define BNR_ABI_VERSION 7   /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
+#define BNR_ABI_VERSION 8   /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
                                5: + bnr_chain_create_typed, bnr_chain_create_from_matrices, bnr_device_synchronize; 6: + bnr_comm_info;
-                               7: + option "xi_weights", bnr_host_xi_weight (all additive) */
+                               7: + option "xi_weights", bnr_host_xi_weight; 8: + bnr_chain_predict, bnr_chain_predict_from_matrices,
+                               bnr_chain_loglik_stats, option "predict_block_rows" (all additive) */
 
 enum {
     BNR_OK = 0,
@@ -172,6 +173,26 @@ int bnr_chain_rhat_stats(bnr_chain *chain, int32_t first_row, int32_t nsamp, dou
 int bnr_chain_summary(bnr_chain *chain, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
                       double *mean_gamma, double *lower, double *upper, double *prob_xi);
 
+/* Posterior prediction -- an ADDITION to the reference (y = mu + X gamma + eps, eps ~ N(0, tau2): gibbs.jl:270, 432, 566).
+ * posterior of the mean response mu + x.gamma of m new rows over rows first_row..first_row+nsamp-1 of this chain; X: m x q column-major in
+ * x_dtype (as bnr_chain_create_typed) or m V x V matrices (as bnr_chain_create_from_matrices); y (nullable): observed responses of the rows
+ * -> lpd / pwaic (NULL when y is NULL)
+ *   mean[m]           posterior mean of eta_s = mu_s + x.gamma_s over the draws s of the window
+ *   lower[m], upper[m] the k_lo-th / k_hi-th smallest eta_s (1-based; exact selection, as bnr_chain_summary).  A credible interval of the MEAN
+ *                     response, not a predictive interval for a new observation (that would add eps ~ N(0, tau2_s)).
+ *   lpd[m]            log (1/nsamp) sum_s N(y_i | eta_is, tau2_s): the pointwise log predictive density (log-mean-exp, no overflow)
+ *   pwaic[m]          the sample variance (ddof 1) over s of log N(y_i | eta_is, tau2_s): the pointwise WAIC penalty
+ * Computed on the device (k_predict: f64 MFMA GEMM over the trace rows; k_summary; k_pred_loglik) in blocks of rows (tunable
+ * "predict_block_rows"); only 5 m doubles cross PCIe back.  The table, the iteration counter, the RNG and the counters are not touched; the
+ * chain may be a member of a group.  BNR_ERR_BAD_ARG: a NULL output, a pending asynchronous run, a window outside the table, ranks outside
+ * 1..nsamp, m < 1, an unknown x_dtype. */
+int bnr_chain_predict(bnr_chain *chain, int32_t first_row, int32_t nsamp, int32_t m, const void *X, int32_t x_dtype, const double *y,
+                      int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic);
+int bnr_chain_predict_from_matrices(bnr_chain *chain, int32_t first_row, int32_t nsamp, int32_t m, const void *const *A, int32_t x_dtype,
+                      const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic);
+/* pointwise log predictive density and WAIC penalty of the chain's own training rows (X, y already on the device): lpd[n], pwaic[n] */
+int bnr_chain_loglik_stats(bnr_chain *chain, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic);
+
 /* Effective sample size -- an ADDITION to the reference (which only has split-Rhat; north-star item "Rhat/ESS check").
  * bnr_chain_ess_stats: this chain's message over rows first_row .. first_row+nsamp-1: for both halves of the window (the
  *   halves of split-Rhat) the mean, the variance and the autocovariances at lags 0..max_lag-1 of gamma (q) then xi (V):
@@ -281,6 +302,9 @@ int bnr_debug_set_exp(int32_t device, int32_t flags);
  *   Experiments ("nop_fork", "pipeline", "gate_us", "linear", "linear_merge", "linear_debug", "group_backproj", "resv_mask", "crit_origin"; rounds 3-4,
  *               profiles/round*_experiments_notes.txt): all measured no faster, part of them polled device memory.  Removed from the tree in
  *               round 5 (tools/experiments/README.md): the library refuses them by name.
+ *   "predict_block_rows" (chains only) rows per block of bnr_chain_predict / bnr_chain_loglik_stats, whose work buffer holds rows x nsamp
+ *               doubles; rounded up to whole 32-row tiles.  0 (default): as many rows as fit in about 1 GiB.  The results are bitwise the same
+ *               for every value.
  *   "byte_x"    (chains only) 0: the X passes read the f64 matrix although a byte image of X exists; 1 (default): the byte image
  *               (kept when the model matrix came as Bool/UInt8, or as Int32/Int64 with every value in 0..255; docs/src/man/inputdata.md)
  *   "gram_i8"   (chains only; round 5) 1 (the default from n_pad^2 q >= 2.5e8 on, where it was measured faster -- n = 500, V = 100 and

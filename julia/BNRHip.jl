@@ -172,6 +172,45 @@ function summary_stats(ch::Chain, nburn, nsamp; interval=95)
     m, lo, hi, p
 end
 
+# Posterior of the mean response μ + x⋅γ of new rows over rows nburn+1 .. nburn+nsamp (an addition to the reference; y = μ + Xγ + ε,
+# gibbs.jl:270, 432, 566), on the device: (mean, lower, upper, lpd, pwaic); lower / upper are Summary's order statistics -- a credible
+# interval of the MEAN response, not a predictive interval.  lpd / pwaic (pointwise log predictive density, WAIC penalty) are `nothing`
+# without y.  Xnew: the vector of m adjacency matrices (x_transform = true) or the m x q matrix, in its own element type.
+function predict_stats(ch::Chain, nburn, nsamp, Xnew; y=nothing, interval=95, x_transform=true)
+    lb = (100 - interval) / 200
+    klo, khi = Int(round(nsamp * lb)), Int(round(nsamp * (1 - lb)))
+    m = x_transform ? length(Xnew) : size(Xnew, 1)
+    y === nothing || length(y) == m || throw(ArgumentError("y must have one entry per new row"))
+    yv = y === nothing ? Float64[] : Vector{Float64}(y)
+    yp = y === nothing ? Ptr{Cdouble}(C_NULL) : pointer(yv)
+    mean, lo, hi, lpd, pw = zeros(m), zeros(m), zeros(m), zeros(m), zeros(m)
+    if x_transform
+        T = dtype_code(eltype(Xnew[1])) >= 0 ? eltype(Xnew[1]) : Float64
+        mats = [Matrix{T}(a) for a in Xnew]
+        all(size(a) == (ch.V, ch.V) for a in mats) || throw(ArgumentError("every matrix must be V x V"))
+        ptrs = [Ptr{Cvoid}(pointer(a)) for a in mats]
+        GC.@preserve mats ptrs yv check(ccall((:bnr_chain_predict_from_matrices, LIB), Cint,
+            (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Ptr{Cvoid}}, Int32, Ptr{Cdouble}, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+            ch.h, nburn + 1, nsamp, m, ptrs, dtype_code(T), yp, klo, khi, mean, lo, hi, lpd, pw))
+    else
+        T = dtype_code(eltype(Xnew)) >= 0 ? eltype(Xnew) : Float64
+        Xm = Matrix{T}(Xnew)
+        size(Xm, 2) == ch.q || throw(ArgumentError("X must have q = V(V+1)/2 columns"))
+        GC.@preserve Xm yv check(ccall((:bnr_chain_predict, LIB), Cint,
+            (Ptr{Cvoid}, Int32, Int32, Int32, Ptr{Cvoid}, Int32, Ptr{Cdouble}, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+            ch.h, nburn + 1, nsamp, m, Xm, dtype_code(T), yp, klo, khi, mean, lo, hi, lpd, pw))
+    end
+    y === nothing ? (mean, lo, hi, nothing, nothing) : (mean, lo, hi, lpd, pw)
+end
+
+# pointwise log predictive density and WAIC penalty of the chain's own training rows over rows nburn+1 .. nburn+nsamp: (lpd, pwaic);
+# WAIC = -2 sum(lpd - pwaic)
+function loglik_stats(ch::Chain, nburn, nsamp)
+    lpd, pw = zeros(ch.n), zeros(ch.n)
+    check(ccall((:bnr_chain_loglik_stats, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}), ch.h, nburn + 1, nsamp, lpd, pw))
+    lpd, pw
+end
+
 # ---- the ranks of a fit (bnr_comm): nothing (one process), or the library's RCCL communicator.  Rank 0 calls `unique_id()`, the
 # 128 bytes travel to the other workers by whatever connects them (e.g. `remotecall_fetch`), then EVERY rank calls `rccl_comm`.
 struct Comm
