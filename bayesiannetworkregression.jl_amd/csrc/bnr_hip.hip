@@ -2332,6 +2332,15 @@ int bnr_chain_debug_copy(bnr_chain *c, int32_t which, double *out, int64_t count
     if (!c || !out) return fail(BNR_ERR_BAD_ARG, "bad argument");
     HIPCHK(hipSetDevice(c->device));
     HIPCHK(hipStreamSynchronize(c->x.stream));
+    if (which >= 4) {
+        // the scalar branch's carried state: sizes are checked (the buffers are small and a test reads them whole)
+        const bnr_dev &d = c->d;
+        const double *s4 = which == 4 ? d.Minv : (which == 5 ? d.scal : (which == 6 ? d.Psum : nullptr));
+        const int64_t n4 = which == 4 ? (int64_t)d.R * d.R + 1 : (which == 5 ? 8 : (int64_t)d.nblk_bp * (1 + 3 * d.R));
+        if (!s4 || count < 0 || count > n4) return fail(BNR_ERR_BAD_ARG, "debug_copy: unknown buffer or count beyond its size");
+        HIPCHK(hipMemcpy(out, s4, sizeof(double) * count, hipMemcpyDeviceToHost));
+        return BNR_OK;
+    }
     const double *src = which == 0 ? c->d.E : (which == 1 ? c->d.bw : (which == 2 ? c->d.a4 : c->d.Gpart));
     HIPCHK(hipMemcpy(out, src, sizeof(double) * count, hipMemcpyDeviceToHost));
     return BNR_OK;

@@ -253,7 +253,14 @@ int bnr_chain_last_timing(bnr_chain *chain, int32_t which, double *avg_us, int64
 int bnr_chain_debug_read(bnr_chain *chain, uint64_t *out, int32_t count);
 /* diagnostics: average duration of `reps` back-to-back launches of the Gram kernel on the chain's stream */
 int bnr_chain_debug_time_gram(bnr_chain *chain, int32_t reps, double *avg_us);
-/* diagnostics: copy an internal work buffer to the host (0 = factorization matrix E, 1 = rhs b, 2 = a4, 3 = Gram partials) */
+/* diagnostics: copy an internal work buffer to the host (0 = factorization matrix E, 1 = rhs b, 2 = a4, 3 = Gram partials; the scalar branch's
+ * carried state, count checked against the buffer's size (BNR_ERR_BAD_ARG beyond it):
+ *   4 = inv(M) (R x R, column-major) then logdet M: R^2 + 1 doubles, as the next node update of a sweep reads them (written by update_M!'s
+ *       workgroup of the scalar tail, or by the refresh of the carried sums after init, load or a hook);
+ *   5 = the carried sums: [0] rr = |y - mu - X gamma|^2, [1] sig_q = sum_e ((gamma_e - W_e)^2 / 2) / S_e, [2] tau = sqrt(tau2),
+ *       [3] the pre-drawn next tau2, [4] the iteration id it belongs to (-1: none), [5..7] unused: at most 8 doubles;
+ *   6 = the back-projection's per-block partial sums [nblk_bp][1 + 3R] (nblk_bp = ceil(q / 32)): [0] sum of S over the block's edges,
+ *       [1 + 3r + c] the log-likelihood sums of update_Lambda! with lambda_r set to (0, 1, -1)[c].) */
 int bnr_chain_debug_copy(bnr_chain *chain, int32_t which, double *out, int64_t count);
 /* diagnostics: internal sizes {n_pad, q_pad, ksplit (K slices = planes of Gram partials), ntile (64-row tiles), kcp, kslab, i8L (i8 Gram: padded K slice,
  * bytes per mask row, digit planes), rowlen (doubles per trace row on the device)}; the Gram partials of debug_copy(3) are [ksplit][ntile (ntile + 1) / 2][64 x 64],
