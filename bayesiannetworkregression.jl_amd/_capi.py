@@ -73,6 +73,8 @@ _SIGS = {
     "bnr_chain_predict_from_matrices": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_int32,
                                                   C.c_int32] + [_dp] * 5),
     "bnr_chain_loglik_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp]),
+    "bnr_chain_loo": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
+    "bnr_psis_loo": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp]),
     "bnr_comm_unique_id": (C.c_int, [C.POINTER(UniqueId)]),
     "bnr_comm_create_rccl": (C.c_int, [C.POINTER(UniqueId), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "bnr_comm_create_callback": (C.c_int, [C.c_int32, C.c_int32, ALLGATHER_CB, C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -192,6 +194,35 @@ def runtime_version():
     v = C.c_int(0)
     check(lib().bnr_runtime_version(C.byref(v)))
     return v.value
+
+
+def r_eff_array(r_eff, m):
+    """PSIS's relative efficiencies as m float64 values, or None for the library's default (1): a scalar is repeated; every value must be
+    positive and finite (ValueError before any library call)"""
+    if r_eff is None:
+        return None
+    r = np.asarray(r_eff, dtype=np.float64)
+    r = np.full(m, float(r)) if r.ndim == 0 else np.ascontiguousarray(r.reshape(-1))
+    if r.shape != (m,):
+        raise ValueError("r_eff must be a scalar or have one entry per row (%d), not %d" % (m, r.size))
+    if not np.all(np.isfinite(r) & (r > 0)):
+        raise ValueError("r_eff must be positive and finite")
+    return r
+
+
+def psis_loo_raw(loglik, r_eff=None, device=0):
+    """(lpd, elpd_loo, pareto_k) of every row of an m x S log-likelihood matrix, PSIS on the device (bnr_psis_loo)"""
+    ll = np.ascontiguousarray(loglik, dtype=np.float64)
+    if ll.ndim != 2 or ll.shape[0] < 1 or ll.shape[1] < 1:
+        raise ValueError("loglik must be an m x S matrix (rows x draws) with m, S >= 1")
+    m, S = ll.shape
+    r = r_eff_array(r_eff, m)
+    lpd, elpd, k = np.empty(m), np.empty(m), np.empty(m)
+    L = lib()
+    if _foreign_hip:
+        raise BnrError(BNR_ERR_HIP, _foreign_hip)
+    check(L.bnr_psis_loo(int(device), m, S, _ptr(ll), _ptr(r), _ptr(elpd), _ptr(k), _ptr(lpd)))
+    return lpd, elpd, k
 
 
 X_DTYPES = {np.dtype(np.float64): 0, np.dtype(np.bool_): 1, np.dtype(np.uint8): 1, np.dtype(np.int32): 2, np.dtype(np.int64): 3,
@@ -398,6 +429,14 @@ class Chain:
         lpd, pw = np.empty(self.n), np.empty(self.n)
         check(self.L.bnr_chain_loglik_stats(self.h, int(first_row), int(nsamp), _ptr(lpd), _ptr(pw)))
         return lpd, pw
+
+    def loo(self, first_row, nsamp, r_eff=None):
+        """(lpd, elpd_loo, pareto_k) of the chain's own training rows over the row window: PSIS-LOO on the device (bnr_chain_loo).
+        r_eff: None (1), a scalar, or one relative efficiency per training row."""
+        r = r_eff_array(r_eff, self.n)
+        lpd, elpd, k = np.empty(self.n), np.empty(self.n), np.empty(self.n)
+        check(self.L.bnr_chain_loo(self.h, int(first_row), int(nsamp), _ptr(r), _ptr(lpd), _ptr(elpd), _ptr(k)))
+        return lpd, elpd, k
 
     def ess_stats(self, first_row, nsamp, max_lag):
         out = np.empty(2 * (2 + max_lag) * (self.q + self.V))

@@ -15,7 +15,7 @@ Julia is not available in this image, so the thin host layer a Julia user would 
   return_psrf_VOI        gibbs.jl:771-789   -> return_psrf_VOI
   Results / BNRSummary   gibbs.jl:23-43     -> Results / BNRSummary
   Summary                gibbs.jl:1214-1250 -> Summary
-  (additions)                               -> Predict / BNRPrediction (posterior of the mean response of new rows), WAIC
+  (additions)                               -> Predict / BNRPrediction (posterior of the mean response of new rows), WAIC, LOO / psis_loo
   lower_triangle / create_lower_tri / setup_X!  utils.jl:17-57, gibbs.jl:239-247
 
 All sampling runs on the GPU through libbnr_hip.so; this file holds only the schedule logic (chain fan-out,
@@ -90,6 +90,7 @@ class Results:
     essgamma: np.ndarray = None
     prediction: "BNRPrediction" = None   # filled on request (predict_X=...): posterior of the mean response of new rows, computed on the GPU (see Predict)
     waic: dict = None                # filled on request (waic=True): WAIC of the training rows from the GPU's pointwise numbers (see WAIC)
+    loo: dict = None                 # filled on request (loo=True): PSIS-LOO of the training rows computed on the GPU (see LOO)
 
 
 @dataclass
@@ -204,11 +205,16 @@ def _host_eta(state, X, nburn, nsamp):
     return mu[None, :] + X @ g.T
 
 
-def _host_pointwise(state, X, y, nburn, nsamp):
-    """(lpd, pwaic) per row: log-mean-exp and the ddof-1 variance over the draws of log N(y_i | eta_is, tau2_s)"""
+def _host_loglik(state, X, y, nburn, nsamp):
+    """ll[i, s] = log N(y_i | eta_is, tau2_s) over rows nburn+1 .. nburn+nsamp of a fetched table"""
     eta = _host_eta(state, X, nburn, nsamp)
     tau2 = state["tau2"][nburn:nburn + nsamp, 0, 0]
-    ll = -0.5 * (math.log(2 * math.pi) + np.log(tau2))[None, :] - (np.asarray(y, dtype=np.float64).reshape(-1, 1) - eta) ** 2 / (2 * tau2[None, :])
+    return -0.5 * (math.log(2 * math.pi) + np.log(tau2))[None, :] - (np.asarray(y, dtype=np.float64).reshape(-1, 1) - eta) ** 2 / (2 * tau2[None, :])
+
+
+def _host_pointwise(state, X, y, nburn, nsamp):
+    """(lpd, pwaic) per row: log-mean-exp and the ddof-1 variance over the draws of log N(y_i | eta_is, tau2_s)"""
+    ll = _host_loglik(state, X, y, nburn, nsamp)
     mx = ll.max(axis=1)
     return mx + np.log(np.mean(np.exp(ll - mx[:, None]), axis=1)), ll.var(axis=1, ddof=1)
 
@@ -265,6 +271,113 @@ def WAIC(results, X=None, y=None, x_transform=True):
     xi = _new_rows(X, x_transform, results.state["gamma"].shape[1], y)
     lpd, pw = _host_pointwise(results.state, _dense_rows(xi), y, results.burn_in, results.sampled)
     return _waic_from_pointwise(lpd, pw)
+
+
+# ------------------------------------------------------------------------------------------ PSIS-LOO (an addition to the reference)
+# The host restatement of what k_psis computes (include/bnr_hip.h, bnr_chain_loo), pinned to loo 2.x (psis.R, gpdfit.R):
+# the fallback of LOO over a fetched table, and the yardstick of the GPU tests.
+def _tail_length(S, r_eff):
+    """loo's n_pareto: M = ceil(min(0.2 S, 3 sqrt(S / r_eff)))"""
+    return int(math.ceil(min(0.2 * S, 3.0 * math.sqrt(S / r_eff))))
+
+
+def _logsumexp(a):
+    m = np.max(a)
+    if not np.isfinite(m):
+        return float(m)
+    return float(m + np.log(np.sum(np.exp(a - m))))
+
+
+def _gpdfit(x):
+    """loo's gpdfit on ascending x: the generalized Pareto fit of Zhang & Stephens (2009) with the weakly informative prior -> (k, sigma);
+    k is the shape after the prior adjustment (k M + 5) / (M + 10), +inf when it is NaN"""
+    N = x.size
+    mg = 30 + int(math.floor(math.sqrt(N)))
+    jj = np.arange(1, mg + 1, dtype=np.float64)
+    xstar = x[int(math.floor(N / 4 + 0.5)) - 1]
+    with np.errstate(all="ignore"):
+        theta = 1.0 / x[N - 1] + (1.0 - np.sqrt(mg / (jj - 0.5))) / 3.0 / xstar
+        kk = np.log1p(-theta[:, None] * x[None, :]).mean(axis=1)
+        l_theta = N * (np.log(-theta / kk) - kk - 1.0)
+        jm = int(np.argmax(l_theta))                       # matrixStats' logSumExp: max + log1p(sum over the other points)
+        lse = l_theta[jm] + np.log1p(np.sum(np.exp(np.delete(l_theta, jm) - l_theta[jm])))
+        theta_hat = np.sum(theta * np.exp(l_theta - lse))
+        k = np.mean(np.log1p(-theta_hat * x))
+        sigma = -k / theta_hat
+        k = k * N / (N + 10) + 10 * 0.5 / (N + 10)
+    return (math.inf if math.isnan(k) else float(k)), float(sigma)
+
+
+def _psis_row(ll, M):
+    """loo's do_psis_i + pointwise_loo_calcs for one row of log-likelihood draws with tail length M -> (lpd, elpd_loo, pareto_k)"""
+    S = ll.size
+    with np.errstate(all="ignore"):
+        mx = np.max(ll)
+        lpd = float(mx + np.log(np.sum(np.exp(ll - mx)) / S))
+    if not np.all(np.isfinite(ll)):
+        return lpd, math.nan, math.inf
+    r = -ll
+    lw = r - np.max(r)
+    k = math.inf
+    if M >= 5:
+        order = np.argsort(lw, kind="stable")
+        tail = order[S - M:]
+        lw_tail = lw[tail]
+        if not abs(lw_tail[-1] - lw_tail[0]) < np.finfo(np.float64).eps / 100:
+            ec = math.exp(lw[order[S - M - 1]])
+            k, sigma = _gpdfit(np.exp(lw_tail) - ec)
+            if math.isfinite(k):
+                p = (np.arange(1, M + 1) - 0.5) / M
+                with np.errstate(all="ignore"):
+                    q = np.full(M, np.nan) if (math.isnan(sigma) or sigma <= 0) else sigma * np.expm1(-k * np.log1p(-p)) / k
+                    lw[tail] = np.log(q + ec)
+    lw = np.where(lw > 0, 0.0, lw)                         # truncation at the largest raw weight (a NaN stays NaN)
+    return lpd, _logsumexp(lw + ll) - _logsumexp(lw), float(k)
+
+
+def _psis_host(loglik, r_eff=None):
+    """(lpd, elpd_loo, pareto_k) of every row of an m x S log-likelihood matrix, on the host"""
+    ll = np.asarray(loglik, dtype=np.float64)
+    if ll.ndim != 2 or ll.shape[0] < 1 or ll.shape[1] < 1:
+        raise ValueError("loglik must be an m x S matrix (rows x draws) with m, S >= 1")
+    m, S = ll.shape
+    r = _capi.r_eff_array(r_eff, m)
+    out = np.empty((3, m))
+    for i in range(m):
+        out[:, i] = _psis_row(ll[i], _tail_length(S, 1.0 if r is None else r[i]))
+    return out[0], out[1], out[2]
+
+
+def _loo_from_pointwise(lpd, elpd_i, pareto_k, S):
+    """LOO totals with the conventions of WAIC: elpd_loo = sum elpd_i, p_loo = sum(lpd_i - elpd_i), looic = -2 elpd_loo,
+    se = sqrt(n Var_i(elpd_i)) (ddof 0); the k-hat threshold min(1 - 1/log10(S), 0.7) of loo 2.x and the count of rows above it"""
+    lpd, e, k = (np.asarray(a, dtype=np.float64) for a in (lpd, elpd_i, pareto_k))
+    p = lpd - e
+    elpd = float(np.sum(e))
+    thr = -math.inf if S == 1 else min(1.0 - 1.0 / math.log10(S), 0.7)
+    return dict(elpd_loo=elpd, p_loo=float(np.sum(p)), looic=-2.0 * elpd, se=float(math.sqrt(e.size * np.var(e))), elpd_loo_i=e,
+                p_loo_i=p, lpd_i=lpd, pareto_k=k, khat_threshold=thr, n_high_k=int(np.sum(k > thr)))
+
+
+def psis_loo(loglik, r_eff=None, device=None):
+    """PSIS-LOO of an m x S log-likelihood matrix (rows x draws) on the GPU (bnr_psis_loo) -> the dict of LOO.  r_eff: None (1), a scalar,
+    or one relative efficiency per row."""
+    lpd, e, k = _capi.psis_loo_raw(loglik, r_eff, 0 if device is None else int(device))
+    return _loo_from_pointwise(lpd, e, k, np.shape(loglik)[1])
+
+
+def LOO(results, X=None, y=None, x_transform=True, r_eff=None):
+    """PSIS-LOO cross-validation of the training rows over chain 1's sampled window (Vehtari, Gelman & Gabry 2017, as loo 2.x): dict with
+    elpd_loo, p_loo, looic = -2 elpd_loo, se, the pointwise elpd_loo_i, p_loo_i, lpd_i, pareto_k, and khat_threshold / n_high_k (the rows
+    whose estimate is not to be trusted).  Uses the GPU's numbers when the fit carried them (loo=True) and no r_eff is passed; otherwise the
+    host restatement over results.state with the training X, y passed in."""
+    if results.loo is not None and r_eff is None:
+        return results.loo
+    if results.state is None or X is None or y is None:
+        raise ValueError("LOO needs Fit(..., loo=True), or the state table (return_state=True) together with the training X and y")
+    xi = _new_rows(X, x_transform, results.state["gamma"].shape[1], y)
+    ll = _host_loglik(results.state, _dense_rows(xi), y, results.burn_in, results.sampled)
+    return _loo_from_pointwise(*_psis_host(ll, r_eff), results.sampled)
 
 
 # ------------------------------------------------------------------------------------------ chain placement
@@ -491,9 +604,10 @@ def return_psrf_VOI(chainset, nburn, nsamp, fetch_state=True, summary_interval=N
     return Results(state, rx, rg, nburn, nsamp, dev)
 
 
-def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None, predict=None, waic=False):
+def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None, predict=None, waic=False, loo=False, loo_r_eff=None):
     """The Results a fit returns: chain 1's table (states[1], gibbs.jl:788) and/or its Summary statistics from the device; predict =
-    (new rows, their y or None, interval) and waic=True add the prediction and WAIC computed on the device over the same window."""
+    (new rows, their y or None, interval), waic=True and loo=True add the prediction, WAIC and PSIS-LOO computed on the device over the
+    same window."""
     if ess_max_lag is not None:                       # collective over ranks, like the PSRF
         res.essgamma, res.essxi = chainset.ess(res.burn_in + 1, res.sampled, ess_max_lag if ess_max_lag > 0 else None)
     if 1 in chainset.chains:
@@ -507,6 +621,8 @@ def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None, pre
             res.prediction = device_predict(ch, res.burn_in, res.sampled, predict[0], predict[1], predict[2])
         if waic:
             res.waic = _waic_from_pointwise(*ch.loglik_stats(res.burn_in + 1, res.sampled))
+        if loo:
+            res.loo = _loo_from_pointwise(*ch.loo(res.burn_in + 1, res.sampled, loo_r_eff), res.sampled)
     return res
 
 
@@ -547,7 +663,7 @@ def _normalize_purge(purge_burn, nburn):
 def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=10, nburn=30000, nsamp=20000,
                      maxburn=50000, psrf_cutoff=1.2, x_transform=True, suppress_timer=False, num_chains=2, seed=None,
                      purge_burn=None, device=None, _keep=None, return_state=True, summary_interval=None, ess_max_lag=None,
-                     xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False):
+                     xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None):
     """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
     xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
     xi_weights_code(xi_weights)
@@ -557,6 +673,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
         print("Warning: ν==R may give poor accuracy. Consider increasing ν")
     X_new = XInput(X, x_transform)                 # X_new of gibbs.jl:907-918: element type kept, setup_X! runs on the device
     pred = _predict_request(predict_X, predict_y, predict_interval, x_transform, X_new)
+    _capi.r_eff_array(loo_r_eff, X_new.n)              # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -598,7 +715,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
         print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()), file=sys.stderr)
     print("R = %s nu=%s nburn= %d nsamp = %d" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f\n" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
-    res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic)
+    res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff)
     if _keep is None:
         cs.close()
     return res
@@ -607,7 +724,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
 def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=10, mingen=10000,
                          maxgen=100000, psrf_cutoff=1.01, x_transform=True, suppress_timer=False, num_chains=2,
                          seed=None, purge_burn=None, device=None, return_state=True, summary_interval=None, ess_max_lag=None,
-                         xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False):
+                         xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None):
     """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
     xi_weights_code(xi_weights)
     if nu == R:
@@ -616,6 +733,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
     nsamp = mingen - nburn
     X_new = XInput(X, x_transform)
     pred = _predict_request(predict_X, predict_y, predict_interval, x_transform, X_new)
+    _capi.r_eff_array(loo_r_eff, X_new.n)              # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -659,7 +777,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
         print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()), file=sys.stderr)
     print("\nR = %s nu=%s nburn= %d nsamp = %d\n" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.4f. Max PSRF Gamma: %.4f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
-    res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic)
+    res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff)
     cs.close()
     return res
 
@@ -667,7 +785,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
 def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=10, nburn=30000, nsamples=20000,
         mingen=0, maxgen=0, psrf_cutoff=1.01, x_transform=True, suppress_timer=False, num_chains=2, seed=None,
         purge_burn=None, filename="parameters.log", device=None, return_state=True, summary_interval=None, ess_max_lag=None,
-        xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False):
+        xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None):
     """Fit! (gibbs.jl:725-751).  The `V` keyword is accepted and ignored, as in the reference.
     Extensions: summary_interval=95 computes Summary's statistics on the GPU (Results.summary_device);
     return_state=False then leaves the (large) state table on the device and frees it; ess_max_lag=0 (default lag
@@ -675,7 +793,8 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     xi_weights="reference" samples xi with the reference's own weight arithmetic, under/overflow included (the default "log" never
     under/overflows; include/bnr_hip.h, option "xi_weights"); predict_X (new rows in the x_transform format of X), predict_y (their observed
     responses, optional) and predict_interval compute the posterior of the mean response of those rows on the GPU (Results.prediction, see
-    Predict), waic=True the WAIC of the training rows (Results.waic, see WAIC) -- over chain 1's window, as Summary.  parameters.log keeps the
+    Predict), waic=True the WAIC of the training rows (Results.waic, see WAIC), loo=True their PSIS-LOO (Results.loo, see LOO; loo_r_eff: the
+    relative efficiencies, a scalar or one per training row, default 1) -- over chain 1's window, as Summary.  parameters.log keeps the
     reference's lines only."""
     xi_weights_code(xi_weights)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
@@ -695,9 +814,10 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                                     num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
                                     return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
                                     xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval,
-                                    waic=waic)
+                                    waic=waic, loo=loo, loo_r_eff=loo_r_eff)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
                             return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
-                            xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic)
+                            xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic,
+                            loo=loo, loo_r_eff=loo_r_eff)

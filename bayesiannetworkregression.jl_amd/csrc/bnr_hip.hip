@@ -164,8 +164,15 @@ struct dev_tmp {
         return BNR_OK;
     }
 };
+// PSIS-LOO outputs of a predict_rows call (k_psis behind k_predict on every block): per-row tail lengths on the device, k_psis's dynamic LDS
+struct psis_out {
+    const int *tail_len;
+    int lds;
+    double *lpd, *elpd, *khat;
+};
 static int predict_rows(bnr_chain *c, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, int k_lo, int k_hi,
-                        double *mean_d, double *lo_d, double *hi_d, double *lpd_d, double *pwaic_d, dev_tmp &tmp);
+                        double *mean_d, double *lo_d, double *hi_d, double *lpd_d, double *pwaic_d, dev_tmp &tmp, const psis_out *ps = nullptr);
+static int psis_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *elpd, double *khat, double *lpd);
 static int ensure_lds_attributes(int device)
 {
     static std::mutex mu;
@@ -2231,6 +2238,74 @@ int bnr_chain_loglik_stats(bnr_chain *c, int32_t first_row, int32_t nsamp, doubl
     return BNR_OK;
 }
 
+// loo 2.x's tail length M = ceil(min(0.2 S, 3 sqrt(S / r_eff))) of every row (r_eff NULL: 1), checked against BNR_PSIS_MAX_TAIL, and the
+// dynamic LDS of k_psis for the longest tail that is smoothed (M >= 5)
+static int psis_tail_lengths(int m, int nsamp, const double *r_eff, std::vector<int> &M, int &lds)
+{
+    M.assign(m, 0);
+    int pmax = 0;
+    for (int i = 0; i < m; ++i) {
+        const double r = r_eff ? r_eff[i] : 1.0;
+        if (!(r > 0.0) || !std::isfinite(r)) return fail(BNR_ERR_BAD_ARG, "r_eff must be positive and finite");
+        const double t = std::ceil(std::min(0.2 * nsamp, 3.0 * std::sqrt(nsamp / r)));
+        if (t > BNR_PSIS_MAX_TAIL)
+            return fail(BNR_ERR_BAD_ARG, "PSIS tail length " + std::to_string((long long)t) + " of row " + std::to_string(i + 1) + " exceeds the supported " +
+                                             std::to_string(BNR_PSIS_MAX_TAIL) + " (raise r_eff or shorten the window)");
+        M[i] = (int)t;
+        if (M[i] >= 5) {
+            int p = 8;
+            while (p < M[i]) p <<= 1;
+            pmax = std::max(pmax, p);
+        }
+    }
+    lds = std::max(8192, 16 * pmax);
+    return BNR_OK;
+}
+// PSIS-LOO of the chain's own training rows over rows first_row .. first_row+nsamp-1 (k_predict, then k_psis on every block of rows)
+int bnr_chain_loo(bnr_chain *c, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo, double *pareto_k)
+{
+    if (!c || !elpd_loo || !pareto_k) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+    const bnr_dev &d = c->d;
+    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    std::vector<int> M;
+    int lds = 0, rc;
+    if ((rc = psis_tail_lengths(d.n, nsamp, r_eff, M, lds))) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->x.stream;
+    dev_tmp tmp;
+    double *out = nullptr;
+    int *tl = nullptr;
+    if ((rc = tmp.alloc(&out, (size_t)3 * d.n, st))) return rc;
+    if ((rc = tmp.alloc(&tl, (size_t)d.n, st))) return rc;
+    HIPCHK(hipMemcpyAsync(tl, M.data(), sizeof(int) * d.n, hipMemcpyHostToDevice, st));
+    const psis_out ps{tl, lds, out, out + d.n, out + 2 * (size_t)d.n};
+    if ((rc = predict_rows(c, first_row, nsamp, d.n, d.X, d.n_pad, d.y, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, tmp, &ps))) return rc;
+    std::vector<double> host(3 * (size_t)d.n);
+    hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("loo: ") + hipGetErrorString(e));
+    if ((rc = check_launch("k_psis"))) return rc;
+    if (lpd) memcpy(lpd, host.data(), sizeof(double) * d.n);
+    memcpy(elpd_loo, host.data() + d.n, sizeof(double) * d.n);
+    memcpy(pareto_k, host.data() + 2 * (size_t)d.n, sizeof(double) * d.n);
+    return BNR_OK;
+}
+// the same PSIS on a caller's m x nsamp log-likelihood matrix (host, row-major)
+int bnr_psis_loo(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *elpd_loo, double *pareto_k, double *lpd)
+{
+    if (!loglik || !elpd_loo || !pareto_k) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (m < 1 || nsamp < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows and nsamp >= 1 draws");
+    std::vector<int> M;
+    int lds = 0, rc, ndev = 0;
+    if ((rc = psis_tail_lengths(m, nsamp, r_eff, M, lds))) return rc;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
+    HIPCHK(hipSetDevice(device));
+    if ((rc = ensure_lds_attributes(device))) return rc;
+    return psis_matrix(m, nsamp, loglik, M, lds, elpd_loo, pareto_k, lpd);
+}
+
 // Bulk effective sample size over all chains from the gathered messages (the estimator of Vehtari et al. 2021 as in
 // Stan / MCMCDiagnosticTools.ess: split chains, rho_t = 1 - (W - mean acov_t) / var+, Geyer's initial positive and monotone
 // sequence on the pair sums), truncated at max_lag.  NaN for a constant parameter.
@@ -2464,6 +2539,9 @@ static int late_kernels_lds_attributes(int bytes)
     // k_tail outside a sweep (hooks, a loaded row): u (up to BNR_TAIL_U_LDS doubles) and the R x R work matrices of update_M! side by side
     const void *tails[] = {(const void *)&k_tail<bnr_one>, (const void *)&k_tail<bnr_many>, (const void *)&k_tail<bnr_one, false>, (const void *)&k_tail<bnr_many, false>};
     for (const void *f : tails) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
+    // k_psis: the sorted tail, 16 bytes per entry for up to BNR_PSIS_MAX_TAIL entries
+    const void *psis[] = {(const void *)&k_psis<0>, (const void *)&k_psis<1>};
+    for (const void *f : psis) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * BNR_PSIS_MAX_TAIL));
     return BNR_OK;
 }
 static void launch_late_xpass_group2(bnr_exec &x, int s)
@@ -2477,7 +2555,7 @@ static void launch_late_backproj64(bnr_exec &x, int s, int flags, size_t lds64)
 // NULL) and k_pred_loglik (when yd is given).  Blocks start at multiples of 32 rows, so an output's MFMA tile position and K order -- and
 // with them every result, bit for bit -- do not depend on the block size.
 static int predict_rows(bnr_chain *c, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, int k_lo, int k_hi,
-                        double *mean_d, double *lo_d, double *hi_d, double *lpd_d, double *pwaic_d, dev_tmp &tmp)
+                        double *mean_d, double *lo_d, double *hi_d, double *lpd_d, double *pwaic_d, dev_tmp &tmp, const psis_out *ps)
 {
     const bnr_dev &d = c->d;
     hipStream_t st = c->x.stream;
@@ -2502,10 +2580,51 @@ static int predict_rows(bnr_chain *c, int first_row, int nsamp, int m, const dou
                                (const double *)d.trace, d.rowlen, d.o_gamma, first_row - 1, nsamp, mr, E);
         if (mean_d)
             hipLaunchKernelGGL(k_summary, dim3(mr), dim3(256), 0, st, (const double *)E, nsamp, mr, k_lo, k_hi, mean_d + i0, lo_d + i0, hi_d + i0);
-        if (yd)
+        if (yd && lpd_d)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pred_loglik<0>), dim3(mr), dim3(256), 0, st, (const double *)E, nsamp, yd + i0, (const double *)tau2,
                                lpd_d + i0, pwaic_d + i0);
+        if (ps)                                        // last: k_psis turns the block's E into l in place
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis<1>), dim3(mr), dim3(256), ps->lds, st, E, nsamp, yd + i0, (const double *)tau2, ps->tail_len + i0,
+                               ps->lpd + i0, ps->elpd + i0, ps->khat + i0);
     }
     return check_launch("k_predict");
+}
+
+// The device work of bnr_psis_loo on its own stream: the rows of the caller's matrix in blocks of about 1 GiB, k_psis<0> on every block.
+static int psis_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *elpd, double *khat, double *lpd)
+{
+    struct stream_guard {
+        hipStream_t s = nullptr;
+        ~stream_guard() { if (s) (void)hipStreamDestroy(s); }
+    } sg;
+    HIPCHK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    hipStream_t st = sg.s;
+    const size_t budget = (size_t)1 << 30;
+    const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, budget / ((size_t)nsamp * sizeof(double))));
+    int rc;
+    {
+        dev_tmp tmp;
+        double *Ld = nullptr, *out = nullptr;
+        int *tl = nullptr;
+        if ((rc = tmp.alloc(&Ld, (size_t)blk * nsamp, st))) return rc;
+        if ((rc = tmp.alloc(&out, (size_t)3 * m, st))) return rc;
+        if ((rc = tmp.alloc(&tl, (size_t)m, st))) return rc;
+        HIPCHK(hipMemcpyAsync(tl, tail_len.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
+        for (int i0 = 0; i0 < m; i0 += blk) {
+            const int mr = std::min(blk, m - i0);
+            HIPCHK(hipMemcpyAsync(Ld, loglik + (size_t)i0 * nsamp, sizeof(double) * (size_t)mr * nsamp, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis<0>), dim3(mr), dim3(256), lds, st, Ld, nsamp, (const double *)nullptr, (const double *)nullptr,
+                               (const int *)tl + i0, out + i0, out + m + i0, out + 2 * (size_t)m + i0);
+        }
+        std::vector<double> host(3 * (size_t)m);
+        hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("psis_loo: ") + hipGetErrorString(e));
+        if ((rc = check_launch("k_psis"))) return rc;
+        if (lpd) memcpy(lpd, host.data(), sizeof(double) * m);
+        memcpy(elpd, host.data() + m, sizeof(double) * m);
+        memcpy(khat, host.data() + 2 * (size_t)m, sizeof(double) * m);
+    }
+    return BNR_OK;
 }
 }

@@ -21,7 +21,8 @@
 // Every sweep kernel exists for ONE chain (descriptor by value: bnr_one) and for a lockstep group of chains (device array
 // of descriptors indexed by the grid's chain coordinate: bnr_many); the arithmetic of a chain is the same in both.
 // Outside the sweep: k_init_prior (initialize_variables!), k_fetch_cols / k_load_cols (Table layout), k_rhat_stats
-// (split-Rhat message), k_summary (Summary statistics), k_predict / k_pred_loglik (posterior of the mean response of new rows, lpd and WAIC penalty).
+// (split-Rhat message), k_summary (Summary statistics), k_predict / k_pred_loglik (posterior of the mean response of new rows, lpd and WAIC penalty),
+// k_psis (PSIS-LOO: Pareto-smoothed importance sampling over the draws of a row).
 //   k_x_mask, k_sdigits, k_gram_i8   the Gram of a binary (0/1) model matrix on the i8 matrix pipe (round 5)
 // The measured experiments of rounds 3-4 (persistent / resident Gram kernels, left-looking and data-flow factorizations, gates, ...) are not
 // part of this tree any more: tools/experiments/ keeps their kernels and drivers for the record (they built against the round-4 tree).
@@ -3745,6 +3746,12 @@ __global__ __launch_bounds__(256) void k_predict(const double *X, int ldx, int q
 // lpd_i = max_s l_s + log(sum_s exp(l_s - max) / nsamp) (log-mean-exp), pwaic_i = Var_s(l_s) (ddof 1, two passes).  One workgroup of
 // 256 threads per row; every sum in the fixed order of k_summary (thread-strided partial sums, then a tree).
 #define BNR_LOG_2PI 1.8378770664093454836
+// l_s = log N(y_i | E_is, tau2_s), one expression for k_pred_loglik and k_psis (the library is built with -ffp-contract=off, so both get it bit for bit)
+__device__ __forceinline__ double bnr_pred_ell(double yi, double e, double t)
+{
+    const double r = yi - e;
+    return -0.5 * (BNR_LOG_2PI + log(t)) - r * r / (2.0 * t);
+}
 template <int LATE>
 __global__ __launch_bounds__(256) void k_pred_loglik(const double *E, int nsamp, const double *y, const double *tau2, double *lpd, double *pwaic)
 {
@@ -3752,7 +3759,7 @@ __global__ __launch_bounds__(256) void k_pred_loglik(const double *E, int nsamp,
     const int i = blockIdx.x, tid = threadIdx.x;
     const double *e = E + (size_t)i * nsamp;
     const double yi = y[i];
-    auto ell = [&](int s) { const double t = tau2[s], r = yi - e[s]; return -0.5 * (BNR_LOG_2PI + log(t)) - r * r / (2.0 * t); };
+    auto ell = [&](int s) { return bnr_pred_ell(yi, e[s], tau2[s]); };
     double mx = -INFINITY, sum = 0.0;
     for (int s = tid; s < nsamp; s += 256) { const double l = ell(s); mx = fmax(mx, l); sum += l; }
     ra[tid] = mx; rb[tid] = sum;
@@ -3766,4 +3773,253 @@ __global__ __launch_bounds__(256) void k_pred_loglik(const double *E, int nsamp,
     __syncthreads();
     for (int w = 128; w > 0; w >>= 1) { if (tid < w) { ra[tid] += ra[tid + w]; rb[tid] += rb[tid + w]; } __syncthreads(); }
     if (tid == 0) { lpd[i] = M + log(ra[0] / nsamp); pwaic[i] = rb[0] / (nsamp - 1); }
+}
+
+// ===================================================================================== PSIS-LOO (an addition to the reference)
+// Pareto-smoothed importance sampling leave-one-out over the draws s < nsamp of a row, as loo 2.x (Vehtari, Gelman & Gabry 2017; psis.R,
+// gpdfit.R): log ratios r_s = -l_s, lw_s = r_s - max r; with the tail length M = tail_len[i] >= 5 and a tail of spread >= DBL_EPSILON / 100
+// the M largest lw are replaced by the quantiles of a generalized Pareto fit (Zhang & Stephens 2009 with the weakly informative prior) above
+// the cutoff, the (M+1)-th largest lw; then lw <- min(lw, 0) and
+//   lpd_i = log mean_s exp(l_s)                       (k_pred_loglik's expression and reduction order: bit for bit its lpd)
+//   elpd_i = log sum_s exp(lw_s + l_s) - log sum_s exp(lw_s)
+//   khat_i = the fitted shape after the prior adjustment; +inf when there is no fit (M < 5, a constant tail, a NaN shape).
+// A row with a non-finite l gets elpd NaN, khat +inf.
+// One workgroup of 256 threads per row (blockIdx.x); L + i nsamp holds the row's E column (FROM_E = 1: l_s = bnr_pred_ell(y_i, E_is, tau2_s),
+// written back over E) or its l row (FROM_E = 0).  The row is streamed from L2 / HBM on every pass:
+//   1  l, its max and min, finiteness;  2  sum exp(l - max) (lpd) and the first digit histogram;  3-7  the other digit histograms: exact
+//   radix select of the (M+1)-th largest order-preserving 64-bit key of lw (11-bit digits, 6 passes, integer LDS atomics: exact);
+//   8  gather: keys above the cutoff key K_c into LDS, the max l over keys equal to K_c, the per-thread log-sum-exps of the rest.
+// Ties: the tail is every key > K_c plus (M - #{key > K_c}) copies of (K_c, l_c), l_c = max l over key == K_c; the other keys == K_c enter
+// the sums as a counted multiple of (K_c, l_c).  Tied ratios have tied l, so this is the tail any sort would pick; a tie created only by the
+// rounding of r - max r moves a result by an ulp of that l.  The tail is sorted by (key, key of l) with a bitonic sort in LDS.
+// Every sum is in a fixed order (thread-strided partial sums, then a tree; the GPD grid: lane-strided partial sums, then a fixed butterfly of
+// the wave), so results are bitwise independent of the grid and of the block of rows.  Dynamic LDS: max(8 KiB, 16 P) bytes, P = the
+// smallest power of two >= the largest M of the launch; M <= BNR_PSIS_MAX_TAIL (the host refuses longer tails).
+// Both instantiations are referenced only from the end of bnr_hip.hip, so that they sit behind the sweep kernels in the code object.
+#define BNR_PSIS_MAX_TAIL 8192
+#define BNR_PSIS_MAX_GRID 128          // 30 + floor(sqrt(BNR_PSIS_MAX_TAIL)) = 120 grid points
+__device__ __forceinline__ unsigned long long bnr_okey(double v)
+{
+    const unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double bnr_okey_inv(unsigned long long k)
+{
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k));
+}
+// running log-sum-exp: sum = s exp(m); a NaN term makes the sum NaN
+__device__ __forceinline__ void bnr_lse_merge(double &m, double &s, double m2, double s2)
+{
+    if (isnan(m2) || isnan(s2)) s = NAN;
+    else if (m2 > m) { s = s * exp(m - m2) + s2; m = m2; }
+    else if (m2 > -INFINITY) s += s2 * exp(m2 - m);
+}
+template <int FROM_E>
+__global__ __launch_bounds__(256) void k_psis(double *L, int nsamp, const double *y, const double *tau2, const int *tail_len, double *lpd,
+                                              double *elpd, double *khat)
+{
+    extern __shared__ unsigned long long psis_dyn[];
+    __shared__ double ra[256], rb[256], rc[256], rd[256], lth[BNR_PSIS_MAX_GRID];
+    __shared__ unsigned s_bin, s_above, s_cnt, s_pos;
+    __shared__ double s_theta;
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    double *l = L + (size_t)i * nsamp;
+    const int M = tail_len[i];
+
+    // pass 1: l (written back over E), its max and min, finiteness
+    double mx = -INFINITY, mn = INFINITY;
+    int bad = 0;
+    for (int s = tid; s < nsamp; s += 256) {
+        double v;
+        if (FROM_E) { v = bnr_pred_ell(y[i], l[s], tau2[s]); l[s] = v; }
+        else v = l[s];
+        mx = fmax(mx, v); mn = fmin(mn, v);
+        bad |= !isfinite(v);
+    }
+    ra[tid] = mx; rb[tid] = mn;
+    bad = __syncthreads_or(bad);
+    for (int w = 128; w > 0; w >>= 1) { if (tid < w) { ra[tid] = fmax(ra[tid], ra[tid + w]); rb[tid] = fmin(rb[tid], rb[tid + w]); } __syncthreads(); }
+    const double lmax = ra[0], rmax = -rb[0];          // max r = -min l
+    __syncthreads();
+    const bool select = !bad && M >= 5;
+
+    // passes 2-7: radix select of the (M+1)-th largest key of lw = -l - rmax; pass 2 also sums exp(l - lmax) for lpd
+    unsigned *hist = (unsigned *)psis_dyn;
+    unsigned long long prefix = 0, mask = 0;
+    unsigned want = (unsigned)M + 1, above_all = 0, cnt_eq = 0;
+    double se = 0.0;
+    for (int p = 0; p < 6; ++p) {
+        const int shift = p < 5 ? 53 - 11 * p : 0, nbins = p < 5 ? 2048 : 512;
+        if (select) {
+            for (int b = tid; b < nbins; b += 256) hist[b] = 0u;
+            __syncthreads();
+        }
+        for (int s = tid; s < nsamp; s += 256) {
+            const double v = l[s];
+            if (p == 0) se += exp(v - lmax);
+            if (select) {
+                const unsigned long long k = bnr_okey(-v - rmax);
+                if ((k & mask) == prefix) atomicAdd(&hist[(unsigned)(k >> shift) & (unsigned)(nbins - 1)], 1u);
+            }
+        }
+        if (!select) break;
+        __syncthreads();
+        if (wv == 0) {
+            // lane owns the bins [lane per, lane per + per); suffix sums over the lanes find the bin that holds the want-th largest key
+            const int per = nbins / 64;
+            unsigned c = 0;
+            for (int b = 0; b < per; ++b) c += hist[lane * per + b];
+            unsigned suf = c;
+            for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_down(suf, o); if (lane + o < 64) suf += t; }
+            const unsigned long long ge = __ballot(suf >= want);
+            const int owner = 63 - __clzll((long long)ge);
+            if (lane == owner) {
+                unsigned acc = suf - c;
+                for (int b = per - 1; b >= 0; --b) {
+                    const unsigned h = hist[lane * per + b];
+                    if (acc + h >= want) { s_bin = (unsigned)(lane * per + b); s_above = acc; s_cnt = h; break; }
+                    acc += h;
+                }
+            }
+        }
+        __syncthreads();
+        prefix |= (unsigned long long)s_bin << shift;
+        mask |= (unsigned long long)(nbins - 1) << shift;
+        above_all += s_above; want -= s_above; cnt_eq = s_cnt;
+        __syncthreads();
+    }
+    // lpd: k_pred_loglik's tree
+    ra[tid] = se;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) { if (tid < w) ra[tid] += ra[tid + w]; __syncthreads(); }
+    if (tid == 0 && lpd) lpd[i] = lmax + log(ra[0] / nsamp);
+    __syncthreads();
+    if (bad) {
+        if (tid == 0) { elpd[i] = NAN; khat[i] = INFINITY; }
+        return;
+    }
+
+    // pass 8: the tail (keys > K_c) into LDS, l_c, and the log-sum-exps of every other draw (K_c = all ones: no tail, every draw)
+    const unsigned long long Kc = select ? prefix : ~0ull;
+    const int P = select ? (int)(1u << (32 - __clz(M - 1))) : 0;        // the smallest power of two >= M
+    unsigned long long *tk = psis_dyn;
+    double *tl = (double *)(psis_dyn + P);
+    if (tid == 0) s_pos = 0u;
+    __syncthreads();
+    double mA = -INFINITY, sA = 0.0, mB = -INFINITY, sB = 0.0, lc = -INFINITY;
+    for (int s = tid; s < nsamp; s += 256) {
+        const double v = l[s], lw = -v - rmax;
+        const unsigned long long k = bnr_okey(lw);
+        if (k > Kc) {
+            const unsigned pos = atomicAdd(&s_pos, 1u);
+            if (pos < (unsigned)M) { tk[pos] = k; tl[pos] = v; }
+        } else if (k == Kc) lc = fmax(lc, v);
+        else { bnr_lse_merge(mA, sA, lw + v, 1.0); bnr_lse_merge(mB, sB, lw, 1.0); }
+    }
+    double kh = INFINITY;
+    bool smooth = false;
+    double sigma = 0.0, ec = 0.0;
+    if (select) {
+        ra[tid] = lc;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) { if (tid < w) ra[tid] = fmax(ra[tid], ra[tid + w]); __syncthreads(); }
+        lc = ra[0];
+        const int g = (int)above_all;                  // #{key > K_c}; M - g copies of (K_c, l_c) complete the tail
+        for (int j = g + tid; j < P; j += 256) {
+            if (j < M) { tk[j] = Kc; tl[j] = lc; }
+            else { tk[j] = ~0ull; tl[j] = 0.0; }
+        }
+        __syncthreads();
+        // bitonic sort of (key, key of l) ascending; the padding (all-ones keys) ends behind the tail
+        for (int kk = 2; kk <= P; kk <<= 1)
+            for (int jj = kk >> 1; jj > 0; jj >>= 1) {
+                for (int t = tid; t < P / 2; t += 256) {
+                    const int a = (t / jj) * 2 * jj + (t % jj), b = a + jj;
+                    const unsigned long long ka = tk[a], kb = tk[b];
+                    const bool gt = ka > kb || (ka == kb && bnr_okey(tl[a]) > bnr_okey(tl[b]));
+                    if (gt == ((a & kk) == 0)) {
+                        tk[a] = kb; tk[b] = ka;
+                        const double x = tl[a]; tl[a] = tl[b]; tl[b] = x;
+                    }
+                }
+                __syncthreads();
+            }
+        const double cutoff = bnr_okey_inv(Kc);
+        const double lo = bnr_okey_inv(tk[0]), hi = bnr_okey_inv(tk[M - 1]);
+        if (!(fabs(hi - lo) < 2.220446049250313e-16 / 100)) {         // .Machine$double.eps / 100
+            // gpdfit on x_j = exp(lw_(j)) - exp(cutoff), ascending
+            ec = exp(cutoff);
+            auto xv = [&](int j) { return exp(bnr_okey_inv(tk[j])) - ec; };
+            const double xN = xv(M - 1), xstar = xv((int)floor(M / 4.0 + 0.5) - 1);
+            const int mg = 30 + (int)floor(sqrt((double)M));
+            auto theta = [&](int j) { return 1.0 / xN + (1.0 - sqrt((double)mg / ((double)j + 0.5))) / 3.0 / xstar; };
+            for (int j = wv; j < mg; j += 4) {
+                const double a = -theta(j);
+                double acc = 0.0;
+                for (int t = lane; t < M; t += 64) acc += log1p(a * xv(t));
+                acc += __shfl_xor(acc, 32); acc += __shfl_xor(acc, 16); acc += __shfl_xor(acc, 8);
+                acc += __shfl_xor(acc, 4); acc += __shfl_xor(acc, 2); acc += __shfl_xor(acc, 1);
+                const double kj = acc / M;
+                if (lane == 0) lth[j] = M * (log(a / kj) - kj - 1.0);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                // weights exp(l_j - logSumExp(l)) with matrixStats' logSumExp (max + log1p of the sum over the other points)
+                int jm = 0;
+                for (int j = 1; j < mg; ++j) if (lth[j] > lth[jm]) jm = j;
+                const double lm = lth[jm];
+                double sum = 0.0;
+                for (int j = 0; j < mg; ++j) if (j != jm) sum += exp(lth[j] - lm);
+                const double lse = lm + log1p(sum);
+                double th = 0.0;
+                for (int j = 0; j < mg; ++j) th += theta(j) * exp(lth[j] - lse);
+                s_theta = th;
+            }
+            __syncthreads();
+            const double th = s_theta;
+            double acc = 0.0;
+            for (int t = tid; t < M; t += 256) acc += log1p(-th * xv(t));
+            ra[tid] = acc;
+            __syncthreads();
+            for (int w = 128; w > 0; w >>= 1) { if (tid < w) ra[tid] += ra[tid + w]; __syncthreads(); }
+            const double k0 = ra[0] / M;
+            sigma = -k0 / th;
+            kh = k0 * M / (M + 10) + 10 * 0.5 / (M + 10);
+            if (isnan(kh)) kh = INFINITY;
+            smooth = isfinite(kh);
+        }
+        // the tail's terms, smoothed (qgpd quantiles above the cutoff) or as they were, truncated at 0
+        for (int j = tid; j < M; j += 256) {
+            double lw;
+            if (smooth) {
+                const double pj = ((double)j + 0.5) / M;
+                const double qq = (isnan(sigma) || sigma <= 0.0) ? NAN : sigma * expm1(-kh * log1p(-pj)) / kh;
+                lw = log(qq + ec);
+            } else lw = bnr_okey_inv(tk[j]);
+            if (lw > 0.0) lw = 0.0;
+            bnr_lse_merge(mA, sA, lw + tl[j], 1.0);
+            bnr_lse_merge(mB, sB, lw, 1.0);
+        }
+    }
+    __syncthreads();                                   // (every thread has read ra[0] above)
+    ra[tid] = mA; rb[tid] = sA; rc[tid] = mB; rd[tid] = sB;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) {
+            double m1 = ra[tid], s1 = rb[tid], m2 = rc[tid], s2 = rd[tid];
+            bnr_lse_merge(m1, s1, ra[tid + w], rb[tid + w]);
+            bnr_lse_merge(m2, s2, rc[tid + w], rd[tid + w]);
+            ra[tid] = m1; rb[tid] = s1; rc[tid] = m2; rd[tid] = s2;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        double m1 = ra[0], s1 = rb[0], m2 = rc[0], s2 = rd[0];
+        if (select) {
+            const double ne = (double)(cnt_eq - (want - 1)), lwc = bnr_okey_inv(Kc);   // the keys == K_c outside the tail
+            if (ne > 0) { bnr_lse_merge(m1, s1, lwc + lc, ne); bnr_lse_merge(m2, s2, lwc, ne); }
+        }
+        elpd[i] = (m1 + log(s1)) - (m2 + log(s2));
+        khat[i] = kh;
+    }
 }

@@ -28,10 +28,10 @@
 extern "C" {
 #endif
 
-#define BNR_ABI_VERSION 8   /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
+#define BNR_ABI_VERSION 9   /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
                                5: + bnr_chain_create_typed, bnr_chain_create_from_matrices, bnr_device_synchronize; 6: + bnr_comm_info;
                                7: + option "xi_weights", bnr_host_xi_weight; 8: + bnr_chain_predict, bnr_chain_predict_from_matrices,
-                               bnr_chain_loglik_stats, option "predict_block_rows" (all additive) */
+                               bnr_chain_loglik_stats, option "predict_block_rows"; 9: + bnr_chain_loo, bnr_psis_loo (all additive) */
 
 enum {
     BNR_OK = 0,
@@ -192,6 +192,25 @@ int bnr_chain_predict_from_matrices(bnr_chain *chain, int32_t first_row, int32_t
                       const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic);
 /* pointwise log predictive density and WAIC penalty of the chain's own training rows (X, y already on the device): lpd[n], pwaic[n] */
 int bnr_chain_loglik_stats(bnr_chain *chain, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic);
+
+/* PSIS-LOO -- an ADDITION to the reference: Pareto-smoothed importance-sampling leave-one-out cross-validation (Vehtari, Gelman & Gabry 2017)
+ * as loo 2.x computes it, per row i over the draws s of the window with l_s = log N(y_i | mu_s + x_i.gamma_s, tau2_s): log ratios -l_s,
+ * tail length M = ceil(min(0.2 nsamp, 3 sqrt(nsamp / r_eff_i))); with M >= 5 the M largest log weights are replaced by the quantiles of a
+ * generalized Pareto fit (Zhang & Stephens 2009, weakly informative prior), then truncated at the largest raw weight.
+ *   lpd[i]       log (1/nsamp) sum_s exp(l_s): bit for bit bnr_chain_loglik_stats's lpd (NULL: not returned)
+ *   elpd_loo[i]  log sum_s w_s exp(l_s) / sum_s w_s over the smoothed weights w_s
+ *   pareto_k[i]  the fitted shape k-hat after the prior adjustment (k M + 5) / (M + 10); +inf where no tail was fitted (M < 5, a constant
+ *                tail, a NaN shape).  A row with a non-finite l gets elpd_loo NaN and pareto_k +inf (not an error).
+ * r_eff: NULL (every r_eff_i = 1) or one relative efficiency per row.  Tails are sorted in LDS: M <= BNR_PSIS_MAX_TAIL (8192) per row; a
+ * longer tail (0.2 nsamp and 3 sqrt(nsamp / r_eff_i) both above 8192) is refused with BNR_ERR_BAD_ARG, as is r_eff_i <= 0 or non-finite.  Results are bitwise the same for
+ * every "predict_block_rows" and every call.  DESIGN.md section 8.
+ * bnr_chain_loo: the chain's own n training rows over rows first_row..first_row+nsamp-1 (k_predict, then k_psis on the device); checks as
+ *   bnr_chain_loglik_stats (NULL outputs, a pending asynchronous run, the window).  The table, the iteration counter, the RNG and the counters
+ *   are not touched.
+ * bnr_psis_loo: the same kernel on a caller's m x nsamp log-likelihood matrix (host, ROW-major: row i's nsamp draws contiguous) on `device`. */
+int bnr_chain_loo(bnr_chain *chain, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo, double *pareto_k);
+int bnr_psis_loo(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *elpd_loo, double *pareto_k,
+                 double *lpd);
 
 /* Effective sample size -- an ADDITION to the reference (which only has split-Rhat; north-star item "Rhat/ESS check").
  * bnr_chain_ess_stats: this chain's message over rows first_row .. first_row+nsamp-1: for both halves of the window (the

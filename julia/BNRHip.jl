@@ -211,6 +211,18 @@ function loglik_stats(ch::Chain, nburn, nsamp)
     lpd, pw
 end
 
+# PSIS-LOO of the chain's own training rows over rows nburn+1 .. nburn+nsamp (an addition to the reference; as loo 2.x), on the device:
+# (lpd, elpd_loo, pareto_k); elpd_loo = sum(elpd_loo), p_loo = sum(lpd - elpd_loo).  r_eff: nothing (1), a number, or one per training row.
+function loo_stats(ch::Chain, nburn, nsamp; r_eff=nothing)
+    rv = r_eff === nothing ? Float64[] : (r_eff isa Number ? fill(Float64(r_eff), ch.n) : Vector{Float64}(r_eff))
+    r_eff === nothing || length(rv) == ch.n || throw(ArgumentError("r_eff must be a number or have one entry per training row"))
+    rp = r_eff === nothing ? Ptr{Cdouble}(C_NULL) : pointer(rv)
+    lpd, elpd, k = zeros(ch.n), zeros(ch.n), zeros(ch.n)
+    GC.@preserve rv check(ccall((:bnr_chain_loo, LIB), Cint, (Ptr{Cvoid}, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        ch.h, nburn + 1, nsamp, rp, lpd, elpd, k))
+    lpd, elpd, k
+end
+
 # ---- the ranks of a fit (bnr_comm): nothing (one process), or the library's RCCL communicator.  Rank 0 calls `unique_id()`, the
 # 128 bytes travel to the other workers by whatever connects them (e.g. `remotecall_fetch`), then EVERY rank calls `rccl_comm`.
 struct Comm
