@@ -75,6 +75,13 @@ _SIGS = {
     "bnr_chain_loglik_stats": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp]),
     "bnr_chain_loo": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
     "bnr_psis_loo": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp]),
+    "bnr_chains_summary": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
+    "bnr_chains_predict": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, C.c_int32]
+                           + [_dp] * 5 + [C.c_uint64] + [_dp] * 3),
+    "bnr_chains_predict_from_matrices": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
+                                                   _dp, C.c_int32, C.c_int32] + [_dp] * 5 + [C.c_uint64] + [_dp] * 3),
+    "bnr_chains_loglik_stats": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
+    "bnr_chains_loo": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
     "bnr_comm_unique_id": (C.c_int, [C.POINTER(UniqueId)]),
     "bnr_comm_create_rccl": (C.c_int, [C.POINTER(UniqueId), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "bnr_comm_create_callback": (C.c_int, [C.c_int32, C.c_int32, ALLGATHER_CB, C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -101,6 +108,7 @@ _SIGS = {
     "bnr_host_gig": (C.c_double, [C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_uint32]),
     "bnr_host_edge_index": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
     "bnr_host_xi_weight": (C.c_double, [C.c_double, C.c_double, C.c_double]),
+    "bnr_host_pred_noise": (None, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _dp]),
     "bnr_host_gram_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
 }
 for _u in ("tau2", "u_xi", "gamma", "D", "theta", "Delta", "M", "mu", "Lambda", "pi"):
@@ -534,6 +542,83 @@ class Group:
         us, n = C.c_double(0), C.c_int64(0)
         check(self.L.bnr_group_last_timing(self.h, which, C.byref(us), C.byref(n)))
         return us.value, n.value
+
+
+# ------------------------------------------------------------------------------------------ pooled chains (bnr_chains_* of include/bnr_hip.h)
+def _pooled(chains):
+    """(list of the chains, their handles as a C array): the chains of one fit on one device whose windows are pooled, in this order"""
+    chains = list(chains)
+    if not chains:
+        raise ValueError("need at least one chain")
+    return chains, (C.c_void_p * len(chains))(*[ch.h for ch in chains])
+
+
+def host_pred_noise(seed, s0, ns, i0, ni):
+    """the noise z of the predictive draws as the device draws it (bnr_host_pred_noise; no GPU): an (ni, ns) array, element [i - i0, s - s0] for
+    row i of the call and pooled draw s"""
+    out = np.empty((int(ni), int(ns)))
+    lib().bnr_host_pred_noise(C.c_uint64(int(seed) & (2**64 - 1)), int(s0), int(ns), int(i0), int(ni), _ptr(out))
+    return out
+
+
+def pooled_summary(chains, first_row, nsamp, k_lo, k_hi):
+    """Chain.summary over the pooled window of `chains` (bnr_chains_summary); ranks in 1 .. len(chains) * nsamp"""
+    chains, arr = _pooled(chains)
+    c0 = chains[0]
+    mean, lo, hi, pxi = np.empty(c0.q), np.empty(c0.q), np.empty(c0.q), np.empty(c0.V)
+    check(c0.L.bnr_chains_summary(arr, len(chains), int(first_row), int(nsamp), int(k_lo), int(k_hi), _ptr(mean), _ptr(lo), _ptr(hi), _ptr(pxi)))
+    return mean, lo, hi, pxi
+
+
+def pooled_predict(chains, X, first_row, nsamp, k_lo, k_hi, y=None, x_transform=False, pred_seed=None, pit=False):
+    """Chain.predict over the pooled window of `chains` (bnr_chains_predict / _from_matrices): (mean, lower, upper, lpd, pwaic, pred_lower,
+    pred_upper, pit) per row.  pred_seed given: the k_lo-th / k_hi-th smallest draw of a new observation (None otherwise); pit=True (needs y):
+    the PIT of the observed responses."""
+    chains, arr = _pooled(chains)
+    c0 = chains[0]
+    xi = X if isinstance(X, XInput) else XInput(X, x_transform)
+    if xi.q != c0.q:
+        raise ValueError("the new rows have %d edge columns, the chain %d" % (xi.q, c0.q))
+    m = xi.n
+    yf = None
+    if y is not None:
+        yf = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        if yf.shape != (m,):
+            raise ValueError("y must have one entry per new row (%d), not %d" % (m, yf.size))
+    if pit and yf is None:
+        raise ValueError("the PIT needs the observed responses y")
+    mean, lo, hi = np.empty(m), np.empty(m), np.empty(m)
+    lpd, pw = (np.empty(m), np.empty(m)) if yf is not None else (None, None)
+    plo, phi = (np.empty(m), np.empty(m)) if pred_seed is not None else (None, None)
+    pt = np.empty(m) if pit else None
+    tail = (_ptr(yf), int(k_lo), int(k_hi), _ptr(mean), _ptr(lo), _ptr(hi), _ptr(lpd), _ptr(pw),
+            C.c_uint64((0 if pred_seed is None else int(pred_seed)) & (2**64 - 1)), _ptr(plo), _ptr(phi), _ptr(pt))
+    if xi.from_matrices:
+        ptrs = (C.c_void_p * m)(*[a.ctypes.data for a in xi.data])
+        check(c0.L.bnr_chains_predict_from_matrices(arr, len(chains), int(first_row), int(nsamp), m, ptrs, xi.dtype_code, *tail))
+    else:
+        check(c0.L.bnr_chains_predict(arr, len(chains), int(first_row), int(nsamp), m, _ptr(xi.data), xi.dtype_code, *tail))
+    return mean, lo, hi, lpd, pw, plo, phi, pt
+
+
+def pooled_loglik_stats(chains, first_row, nsamp, pit=False):
+    """(lpd, pwaic, pit or None) of the training rows over the pooled window of `chains` (bnr_chains_loglik_stats)"""
+    chains, arr = _pooled(chains)
+    n = chains[0].n
+    lpd, pw = np.empty(n), np.empty(n)
+    pt = np.empty(n) if pit else None
+    check(chains[0].L.bnr_chains_loglik_stats(arr, len(chains), int(first_row), int(nsamp), _ptr(lpd), _ptr(pw), _ptr(pt)))
+    return lpd, pw, pt
+
+
+def pooled_loo(chains, first_row, nsamp, r_eff=None):
+    """(lpd, elpd_loo, pareto_k) of the training rows over the pooled window of `chains`: PSIS-LOO on the device (bnr_chains_loo)"""
+    chains, arr = _pooled(chains)
+    n = chains[0].n
+    r = r_eff_array(r_eff, n)
+    lpd, elpd, k = np.empty(n), np.empty(n), np.empty(n)
+    check(chains[0].L.bnr_chains_loo(arr, len(chains), int(first_row), int(nsamp), _ptr(r), _ptr(lpd), _ptr(elpd), _ptr(k)))
+    return lpd, elpd, k
 
 
 class Comm:

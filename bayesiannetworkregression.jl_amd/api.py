@@ -15,7 +15,8 @@ Julia is not available in this image, so the thin host layer a Julia user would 
   return_psrf_VOI        gibbs.jl:771-789   -> return_psrf_VOI
   Results / BNRSummary   gibbs.jl:23-43     -> Results / BNRSummary
   Summary                gibbs.jl:1214-1250 -> Summary
-  (additions)                               -> Predict / BNRPrediction (posterior of the mean response of new rows), WAIC, LOO / psis_loo
+  (additions)                               -> Predict / BNRPrediction (posterior of the mean response of new rows), WAIC, LOO / psis_loo;
+                                               pooled chains, predictive intervals and PIT: device_*_pooled, _host_pooled_*
   lower_triangle / create_lower_tri / setup_X!  utils.jl:17-57, gibbs.jl:239-247
 
 All sampling runs on the GPU through libbnr_hip.so; this file holds only the schedule logic (chain fan-out,
@@ -91,6 +92,8 @@ class Results:
     prediction: "BNRPrediction" = None   # filled on request (predict_X=...): posterior of the mean response of new rows, computed on the GPU (see Predict)
     waic: dict = None                # filled on request (waic=True): WAIC of the training rows from the GPU's pointwise numbers (see WAIC)
     loo: dict = None                 # filled on request (loo=True): PSIS-LOO of the training rows computed on the GPU (see LOO)
+    stat_chains: int = None          # how many chains the device statistics above (summary_device, prediction, waic, loo) cover: 1 (chain 1's window), or
+                                     # every chain of the fit with pool_chains=True; None when the fit computed none
 
 
 @dataclass
@@ -167,18 +170,26 @@ class BNRPrediction:
     """Posterior of the mean response eta = mu + x.gamma of new rows (y = mu + X gamma + eps, gibbs.jl:270, 432, 566) over chain 1's window:
     estimate = posterior mean, lower_bound / upper_bound = the order statistics Summary uses for a ci_level% interval.  This is a credible
     interval of the MEAN response, not a predictive interval for a new observation (which would add eps ~ N(0, tau2)).  With observed
-    responses: lpd = pointwise log predictive density log mean_s N(y_i | eta_is, tau2_s), elpd = its sum."""
+    responses: lpd = pointwise log predictive density log mean_s N(y_i | eta_is, tau2_s), elpd = its sum.
+    With predict_observation (device_predict_pooled, Fit(..., predict_observation=True)): pred_lower_bound / pred_upper_bound = the same order
+    statistics of draws of a NEW OBSERVATION eta_s + sqrt(tau2_s) z_s -- the ci_level% predictive interval -- and, with observed responses,
+    pit = the probability integral transform mean_s Phi((y_i - eta_is) / sqrt(tau2_s)) of every y_i (uniform over rows when the predictive
+    distribution is calibrated).  draws = the number of posterior draws behind the statistics (chains x window rows; None on the older paths)."""
     estimate: np.ndarray
     lower_bound: np.ndarray
     upper_bound: np.ndarray
     ci_level: int
     lpd: np.ndarray = None
     elpd: float = None
+    pred_lower_bound: np.ndarray = None
+    pred_upper_bound: np.ndarray = None
+    pit: np.ndarray = None
+    draws: int = None
 
 
-def _prediction(mean, lo, hi, interval, lpd=None, digits=None):
-    r = (lambda a: a) if digits is None else (lambda a: np.round(a, digits))
-    return BNRPrediction(r(mean), r(lo), r(hi), interval, lpd, None if lpd is None else float(np.sum(lpd)))
+def _prediction(mean, lo, hi, interval, lpd=None, digits=None, pred_lo=None, pred_hi=None, pit=None, draws=None):
+    r = (lambda a: a) if digits is None else (lambda a: None if a is None else np.round(a, digits))
+    return BNRPrediction(r(mean), r(lo), r(hi), interval, lpd, None if lpd is None else float(np.sum(lpd)), r(pred_lo), r(pred_hi), pit, draws)
 
 
 def _new_rows(X_new, x_transform, q, y_new=None):
@@ -247,7 +258,7 @@ def Predict(results, X_new=None, y_new=None, interval=95, x_transform=True, digi
             raise ValueError("the fit computed no prediction: pass X_new (with return_state=True) or fit with predict_X=...")
         if p.ci_level != interval:
             raise ValueError("the fit's prediction has a %s%% interval, not %s%%: pass X_new to recompute" % (p.ci_level, interval))
-        return _prediction(p.estimate, p.lower_bound, p.upper_bound, p.ci_level, p.lpd, digits)
+        return _prediction(p.estimate, p.lower_bound, p.upper_bound, p.ci_level, p.lpd, digits, p.pred_lower_bound, p.pred_upper_bound, p.pit, p.draws)
     if results.state is None:
         raise ValueError("Predict with X_new needs the state table (Fit(..., return_state=True)), or fit with predict_X=... to predict on the GPU")
     q = results.state["gamma"].shape[1]
@@ -378,6 +389,110 @@ def LOO(results, X=None, y=None, x_transform=True, r_eff=None):
     xi = _new_rows(X, x_transform, results.state["gamma"].shape[1], y)
     ll = _host_loglik(results.state, _dense_rows(xi), y, results.burn_in, results.sampled)
     return _loo_from_pointwise(*_psis_host(ll, r_eff), results.sampled)
+
+
+# ------------------------------------------------------------------------------------------ pooled chains, predictive intervals, PIT (additions)
+# Statistics over the POOLED window of several chains of a fit (include/bnr_hip.h, bnr_chains_*): draw c nsamp + s is the s-th window row of the
+# c-th chain.  The device_* functions take live Chain objects; the _host_pooled_* restatements take the fetched tables of the same chains: the
+# fallback of users who hold the tables, and the yardstick of the GPU tests.  By construction they ARE the single-table formulas above applied
+# to the row-concatenated windows (one table: to that table itself).
+def _pool_tables(states, nburn, nsamp):
+    """(table, nburn', S): the windows nburn+1 .. nburn+nsamp of the tables concatenated in order (columns gamma, mu, tau2, xi), as one table
+    with nburn' = 0; a single table is passed through untouched"""
+    states = list(states)
+    if not states:
+        raise ValueError("need at least one table")
+    if len(states) == 1:
+        return states[0], nburn, nsamp
+    cat = {k: np.asfortranarray(np.concatenate([st[k][nburn:nburn + nsamp] for st in states], axis=0)) for k in ("gamma", "mu", "tau2", "xi")}
+    return cat, 0, nsamp * len(states)
+
+
+def _erfc(a):
+    try:
+        from scipy.special import erfc
+        return erfc(a)
+    except ImportError:
+        return np.vectorize(math.erfc, otypes=[np.float64])(a)
+
+
+def _host_pit(eta, tau2, y):
+    """pit_i = mean_s Phi((y_i - eta_is) / sqrt(tau2_s)), Phi(z) = erfc(-z / sqrt 2) / 2"""
+    z = (np.asarray(y, dtype=np.float64).reshape(-1, 1) - eta) / np.sqrt(tau2)[None, :]
+    return np.mean(0.5 * _erfc(-z / math.sqrt(2.0)), axis=1)
+
+
+def _host_pooled_summary(states, nburn, nsamp, interval=95):
+    """device_summary_pooled's statistics from the fetched tables: the dict of device_summary"""
+    t, nb, S = _pool_tables(states, nburn, nsamp)
+    lw, hi = _summary_ranks(S, interval)
+    g = t["gamma"][nb:nb + S, :, 0]
+    srt = np.sort(g, axis=0)
+    return dict(interval=interval, estimate=g.mean(axis=0), lower_bound=srt[lw - 1, :], upper_bound=srt[hi - 1, :],
+                probability=t["xi"][nb:nb + S, :, 0].mean(axis=0))
+
+
+def _host_pooled_predict(states, X_new, y_new=None, nburn=0, nsamp=None, interval=95, x_transform=False, pred_seed=None):
+    """device_predict_pooled's BNRPrediction from the fetched tables.  pred_seed given: the predictive bounds from y~ = eta + sqrt(tau2) z with the
+    device's own z (bnr_host_pred_noise) and, with y_new, the PIT."""
+    t, nb, S = _pool_tables(states, nburn, nsamp)
+    xi = _new_rows(X_new, x_transform, t["gamma"].shape[1], y_new)
+    lw, hi = _summary_ranks(S, interval)
+    X = _dense_rows(xi)
+    eta = _host_eta(t, X, nb, S)
+    srt = np.sort(eta, axis=1)
+    lpd = None if y_new is None else _host_pointwise(t, X, y_new, nb, S)[0]
+    plo = phi = pit = None
+    if pred_seed is not None:
+        tau2 = t["tau2"][nb:nb + S, 0, 0]
+        ysrt = np.sort(eta + np.sqrt(tau2)[None, :] * _capi.host_pred_noise(pred_seed, 0, S, 0, xi.n), axis=1)
+        plo, phi = ysrt[:, lw - 1], ysrt[:, hi - 1]
+        if y_new is not None:
+            pit = _host_pit(eta, tau2, y_new)
+    return _prediction(eta.mean(axis=1), srt[:, lw - 1], srt[:, hi - 1], interval, lpd, None, plo, phi, pit, S)
+
+
+def _host_pooled_pointwise(states, X, y, nburn, nsamp, x_transform=False):
+    """(lpd, pwaic, pit) of the rows X, y over the pooled windows of the fetched tables"""
+    t, nb, S = _pool_tables(states, nburn, nsamp)
+    Xd = _dense_rows(_new_rows(X, x_transform, t["gamma"].shape[1], y))
+    lpd, pw = _host_pointwise(t, Xd, y, nb, S)
+    return lpd, pw, _host_pit(_host_eta(t, Xd, nb, S), t["tau2"][nb:nb + S, 0, 0], y)
+
+
+def _host_pooled_waic(states, X, y, nburn, nsamp, x_transform=False):
+    """WAIC's dict over the pooled windows of the fetched tables"""
+    return _waic_from_pointwise(*_host_pooled_pointwise(states, X, y, nburn, nsamp, x_transform)[:2])
+
+
+def _host_pooled_loo(states, X, y, nburn, nsamp, x_transform=False, r_eff=None):
+    """LOO's dict over the pooled windows of the fetched tables"""
+    t, nb, S = _pool_tables(states, nburn, nsamp)
+    Xd = _dense_rows(_new_rows(X, x_transform, t["gamma"].shape[1], y))
+    return _loo_from_pointwise(*_psis_host(_host_loglik(t, Xd, y, nb, S), r_eff), S)
+
+
+def device_summary_pooled(chains, nburn, nsamp, interval=95):
+    """device_summary over rows nburn+1 .. nburn+nsamp of ALL the chains listed, pooled (bnr_chains_summary)"""
+    chains = list(chains)
+    lw, hi = _summary_ranks(nsamp * len(chains), interval)
+    mean, lo, up, pxi = _capi.pooled_summary(chains, nburn + 1, nsamp, lw, hi)
+    return dict(interval=interval, estimate=mean, lower_bound=lo, upper_bound=up, probability=pxi)
+
+
+def device_predict_pooled(chains, nburn, nsamp, X_new, y_new=None, interval=95, pred_seed=0, x_transform=False, predict_observation=True):
+    """device_predict over rows nburn+1 .. nburn+nsamp of ALL the chains listed, pooled (bnr_chains_predict).  predict_observation adds the
+    predictive interval of a new observation (noise keyed by pred_seed, the pooled draw and the row's index in X_new) and, with y_new, the PIT."""
+    chains = list(chains)
+    if not chains:
+        raise ValueError("need at least one chain")
+    xi = _new_rows(X_new, x_transform, chains[0].q, y_new)
+    S = nsamp * len(chains)
+    lw, hi = _summary_ranks(S, interval)
+    mean, lo, up, lpd, _pw, plo, phi, pit = _capi.pooled_predict(chains, xi, nburn + 1, nsamp, lw, hi, y=y_new,
+                                                                pred_seed=pred_seed if predict_observation else None,
+                                                                pit=bool(predict_observation) and y_new is not None)
+    return _prediction(mean, lo, up, interval, lpd, None, plo, phi, pit, S)
 
 
 # ------------------------------------------------------------------------------------------ chain placement
@@ -604,10 +719,15 @@ def return_psrf_VOI(chainset, nburn, nsamp, fetch_state=True, summary_interval=N
     return Results(state, rx, rg, nburn, nsamp, dev)
 
 
-def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None, predict=None, waic=False, loo=False, loo_r_eff=None):
+def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None, predict=None, waic=False, loo=False, loo_r_eff=None,
+            pool_chains=False, predict_observation=False, pred_seed=0):
     """The Results a fit returns: chain 1's table (states[1], gibbs.jl:788) and/or its Summary statistics from the device; predict =
     (new rows, their y or None, interval), waic=True and loo=True add the prediction, WAIC and PSIS-LOO computed on the device over the
-    same window."""
+    same window.  pool_chains: those statistics over the pooled windows of all chains of the fit (one rank holds them all);
+    predict_observation: the prediction through the pooled entry point (one chain unless pool_chains) with the predictive bounds and the PIT."""
+    if pool_chains or predict_observation:
+        return _finish_pooled(chainset, res, return_state, summary_interval, ess_max_lag, predict, waic, loo, loo_r_eff, pool_chains,
+                              predict_observation, pred_seed)
     if ess_max_lag is not None:                       # collective over ranks, like the PSRF
         res.essgamma, res.essxi = chainset.ess(res.burn_in + 1, res.sampled, ess_max_lag if ess_max_lag > 0 else None)
     if 1 in chainset.chains:
@@ -623,7 +743,45 @@ def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None, pre
             res.waic = _waic_from_pointwise(*ch.loglik_stats(res.burn_in + 1, res.sampled))
         if loo:
             res.loo = _loo_from_pointwise(*ch.loo(res.burn_in + 1, res.sampled, loo_r_eff), res.sampled)
+        if summary_interval is not None or predict is not None or waic or loo:
+            res.stat_chains = 1
     return res
+
+
+def _finish_pooled(chainset, res, return_state, summary_interval, ess_max_lag, predict, waic, loo, loo_r_eff, pool_chains, predict_observation,
+                   pred_seed):
+    """_finish through the pooled entry points: over every chain of the fit (pool_chains), or over chain 1 alone with the predictive extras"""
+    if ess_max_lag is not None:
+        res.essgamma, res.essxi = chainset.ess(res.burn_in + 1, res.sampled, ess_max_lag if ess_max_lag > 0 else None)
+    if 1 not in chainset.chains:
+        return res
+    ch = chainset.chains[1]
+    chains = [chainset.chains[c] for c in chainset.ids] if pool_chains else [ch]
+    nb, ns = res.burn_in, res.sampled
+    S = ns * len(chains)
+    if return_state:
+        res.state = new_table(ch.tot, ch.V, ch.R, dead=True)
+        ch.fetch(1, ch.tot, res.state)
+    if summary_interval is not None:
+        res.summary_device = device_summary_pooled(chains, nb, ns, summary_interval)
+    if predict is not None:
+        res.prediction = device_predict_pooled(chains, nb, ns, predict[0], predict[1], predict[2], pred_seed, predict_observation=predict_observation)
+    if waic:
+        lpd, pw, pit = _capi.pooled_loglik_stats(chains, nb + 1, ns, pit=True)
+        res.waic = dict(_waic_from_pointwise(lpd, pw), pit_i=pit)
+    if loo:
+        res.loo = _loo_from_pointwise(*_capi.pooled_loo(chains, nb + 1, ns, loo_r_eff), S)
+    if summary_interval is not None or predict is not None or waic or loo:
+        res.stat_chains = len(chains)
+    return res
+
+
+def _pooled_request(pool_chains, predict_observation, predict_X):
+    """Fit's pool_chains / predict_observation checked before any sampling"""
+    if predict_observation and predict_X is None:
+        raise ValueError("predict_observation needs predict_X")
+    if pool_chains and _rank_world()[1] > 1:
+        raise ValueError("pool_chains needs every chain of the fit on one rank: the chains are spread over %d torch.distributed ranks" % _rank_world()[1])
 
 
 def _predict_request(predict_X, predict_y, predict_interval, x_transform, X_new):
@@ -663,7 +821,8 @@ def _normalize_purge(purge_burn, nburn):
 def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=10, nburn=30000, nsamp=20000,
                      maxburn=50000, psrf_cutoff=1.2, x_transform=True, suppress_timer=False, num_chains=2, seed=None,
                      purge_burn=None, device=None, _keep=None, return_state=True, summary_interval=None, ess_max_lag=None,
-                     xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None):
+                     xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
+                     pool_chains=False, predict_observation=False, pred_seed=None):
     """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
     xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
     xi_weights_code(xi_weights)
@@ -673,6 +832,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
         print("Warning: ν==R may give poor accuracy. Consider increasing ν")
     X_new = XInput(X, x_transform)                 # X_new of gibbs.jl:907-918: element type kept, setup_X! runs on the device
     pred = _predict_request(predict_X, predict_y, predict_interval, x_transform, X_new)
+    _pooled_request(pool_chains, predict_observation, predict_X)
     _capi.r_eff_array(loo_r_eff, X_new.n)              # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
@@ -715,7 +875,8 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
         print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()), file=sys.stderr)
     print("R = %s nu=%s nburn= %d nsamp = %d" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f\n" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
-    res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff)
+    res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff, pool_chains, predict_observation,
+                  seed_eff if pred_seed is None else pred_seed)
     if _keep is None:
         cs.close()
     return res
@@ -724,7 +885,8 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
 def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=10, mingen=10000,
                          maxgen=100000, psrf_cutoff=1.01, x_transform=True, suppress_timer=False, num_chains=2,
                          seed=None, purge_burn=None, device=None, return_state=True, summary_interval=None, ess_max_lag=None,
-                         xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None):
+                         xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
+                         pool_chains=False, predict_observation=False, pred_seed=None):
     """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
     xi_weights_code(xi_weights)
     if nu == R:
@@ -733,6 +895,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
     nsamp = mingen - nburn
     X_new = XInput(X, x_transform)
     pred = _predict_request(predict_X, predict_y, predict_interval, x_transform, X_new)
+    _pooled_request(pool_chains, predict_observation, predict_X)
     _capi.r_eff_array(loo_r_eff, X_new.n)              # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
@@ -777,7 +940,8 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
         print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()), file=sys.stderr)
     print("\nR = %s nu=%s nburn= %d nsamp = %d\n" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.4f. Max PSRF Gamma: %.4f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
-    res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff)
+    res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff, pool_chains, predict_observation,
+                  seed_eff if pred_seed is None else pred_seed)
     cs.close()
     return res
 
@@ -785,7 +949,8 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
 def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=10, nburn=30000, nsamples=20000,
         mingen=0, maxgen=0, psrf_cutoff=1.01, x_transform=True, suppress_timer=False, num_chains=2, seed=None,
         purge_burn=None, filename="parameters.log", device=None, return_state=True, summary_interval=None, ess_max_lag=None,
-        xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None):
+        xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
+        pool_chains=False, predict_observation=False, pred_seed=None):
     """Fit! (gibbs.jl:725-751).  The `V` keyword is accepted and ignored, as in the reference.
     Extensions: summary_interval=95 computes Summary's statistics on the GPU (Results.summary_device);
     return_state=False then leaves the (large) state table on the device and frees it; ess_max_lag=0 (default lag
@@ -794,9 +959,13 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     under/overflows; include/bnr_hip.h, option "xi_weights"); predict_X (new rows in the x_transform format of X), predict_y (their observed
     responses, optional) and predict_interval compute the posterior of the mean response of those rows on the GPU (Results.prediction, see
     Predict), waic=True the WAIC of the training rows (Results.waic, see WAIC), loo=True their PSIS-LOO (Results.loo, see LOO; loo_r_eff: the
-    relative efficiencies, a scalar or one per training row, default 1) -- over chain 1's window, as Summary.  parameters.log keeps the
-    reference's lines only."""
+    relative efficiencies, a scalar or one per training row, default 1) -- over chain 1's window, as Summary.  pool_chains=True computes
+    summary_interval, predict_X, waic and loo over the pooled windows of ALL chains of the fit instead (num_chains x nsamples draws; every chain
+    must live on this rank; Results.stat_chains says how many were covered); predict_observation=True adds to the prediction the predictive
+    interval of a new observation and, with predict_y, the PIT (BNRPrediction.pred_lower_bound / pred_upper_bound / pit), its noise keyed by
+    pred_seed (default: the fit's seed).  parameters.log keeps the reference's lines only."""
     xi_weights_code(xi_weights)
+    _pooled_request(pool_chains, predict_observation, predict_X)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
         with open(filename, "w") as f:
@@ -814,10 +983,11 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                                     num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
                                     return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
                                     xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval,
-                                    waic=waic, loo=loo, loo_r_eff=loo_r_eff)
+                                    waic=waic, loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation,
+                                    pred_seed=pred_seed)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
                             return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
                             xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic,
-                            loo=loo, loo_r_eff=loo_r_eff)
+                            loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed)

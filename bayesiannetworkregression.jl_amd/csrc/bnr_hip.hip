@@ -115,6 +115,7 @@ struct bnr_chain {
     const unsigned char *xm_kept = nullptr;   // the byte MASK of a 0/1 model matrix for the i8 Gram (also while option "gram_i8" is 0); nullptr: the input was not binary
     long long cap_seen = 0;      // sampler-cap events already reported (the device counter is cumulative: a capped draw is reported by the call it happened in, once)
     int predict_block_rows = 0;  // tunable "predict_block_rows": rows per block of bnr_chain_predict / bnr_chain_loglik_stats (0: automatic)
+    int summary_block_cols = 0;  // tunable "summary_block_cols": parameter columns per staging block of the Summary calls (0: automatic)
 };
 
 struct bnr_group {
@@ -170,8 +171,15 @@ struct psis_out {
     int lds;
     double *lpd, *elpd, *khat;
 };
-static int predict_rows(bnr_chain *c, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, int k_lo, int k_hi,
-                        double *mean_d, double *lo_d, double *hi_d, double *lpd_d, double *pwaic_d, dev_tmp &tmp, const psis_out *ps = nullptr);
+// the extras of the pooled entry points (all device pointers, each nullable): the PIT of the observed responses, and the k_lo-th / k_hi-th smallest
+// draw of a new observation (k_pred_noise with `seed`, then a second k_summary)
+struct pred_extra {
+    unsigned long long seed;
+    double *plo, *phi, *pit;
+};
+static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, int k_lo, int k_hi,
+                        double *mean_d, double *lo_d, double *hi_d, double *lpd_d, double *pwaic_d, dev_tmp &tmp, const psis_out *ps = nullptr,
+                        const pred_extra *ex = nullptr);
 static int psis_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *elpd, double *khat, double *lpd);
 static int ensure_lds_attributes(int device)
 {
@@ -1754,7 +1762,7 @@ static int table_io(bnr_chain *c, bool fetch, int first_row, int last_row, int h
             double *hbase = cols[k] + (size_t)(first_row - 1 + host_off) + (size_t)host_tot * c0;
             hipError_t e;
             if (fetch) {
-                hipLaunchKernelGGL(k_fetch_cols, grid, block, 0, c->x.stream, (const double *)d.trace, d.rowlen, cdsc[k].off + c0, nc, first_row - 1, nrows, stage);
+                hipLaunchKernelGGL(k_fetch_cols, grid, block, 0, c->x.stream, (const double *)d.trace, d.rowlen, cdsc[k].off + c0, nc, first_row - 1, nrows, stage, (long long)nrows);
                 e = hipMemcpy2DAsync(hbase, (size_t)host_tot * sizeof(double), stage, (size_t)nrows * sizeof(double),
                                      (size_t)nrows * sizeof(double), nc, hipMemcpyDeviceToHost, c->x.stream);
             } else {
@@ -2082,25 +2090,77 @@ int bnr_rhat(bnr_chain *const *chains, int32_t nchains_local, int32_t nchains_to
     return BNR_OK;
 }
 
-// Summary(results) on the device (gibbs.jl:1214-1250): posterior mean and two order statistics of every gamma_e over rows
-// first_row .. first_row+nsamp-1, and the mean of every xi_v.  3q + V doubles cross PCIe instead of the gamma trace.
-int bnr_chain_summary(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
-                      double *mean_gamma, double *lower, double *upper, double *prob_xi)
+// The chains of a pooled call (bnr_chains_*): one device, equal n, V, R, none listed twice, none with a pending asynchronous run, the window
+// inside every table, the pooled draw count within int32
+static int pooled_check(bnr_chain *const *cs, int nc, int first_row, int nsamp)
 {
-    if (!c || !mean_gamma || !lower || !upper || !prob_xi) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+    if (!cs) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (nc < 1) return fail(BNR_ERR_BAD_ARG, "need nchains >= 1");
+    for (int i = 0; i < nc; ++i) {
+        if (!cs[i]) return fail(BNR_ERR_BAD_ARG, "NULL chain");
+        for (int k = 0; k < i; ++k) if (cs[k] == cs[i]) return fail(BNR_ERR_BAD_ARG, "chain listed twice");
+        const bnr_dev &a = cs[0]->d, &b = cs[i]->d;
+        if (cs[i]->device != cs[0]->device || a.n != b.n || a.V != b.V || a.R != b.R)
+            return fail(BNR_ERR_BAD_ARG, "pooled chains must live on one device and have equal n, V, R");
+    }
+    for (int i = 0; i < nc; ++i) if (cs[i]->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+    for (int i = 0; i < nc; ++i)
+        if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > cs[i]->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    if ((long long)nc * nsamp > 0x7FFFFFFFll) return fail(BNR_ERR_BAD_ARG, "more than 2^31 - 1 pooled draws");
+    return BNR_OK;
+}
+// The pooled work runs on the first chain's stream and reads the other chains' tables: whatever their own streams (and their group's) still
+// hold -- a table load, the tail of a synchronous run -- is waited for here.  (One chain: nothing to order, as before.)
+static int pooled_quiesce(bnr_chain *const *cs, int nc)
+{
+    for (int i = 1; i < nc; ++i) {
+        HIPCHK(hipStreamSynchronize(cs[i]->x.stream));
+        if (cs[i]->group) HIPCHK(hipStreamSynchronize(cs[i]->group->x.stream));
+    }
+    return BNR_OK;
+}
+
+// Summary(results) on the device (gibbs.jl:1214-1250): posterior mean and two order statistics of every gamma_e over rows
+// first_row .. first_row+nsamp-1 of every chain listed (pooled: S = nc nsamp draws, draw c nsamp + s = chain c's s-th window row), and the mean
+// of every xi_v.  3q + V doubles cross PCIe instead of the gamma traces.  The q + V parameter columns are staged (k_fetch_cols, one launch per
+// chain into its nsamp rows of the S-row column) in blocks of columns that keep the staging buffer near 1 GiB ("summary_block_cols" overrides);
+// k_summary works on one column per workgroup, so the block size cannot change a result.
+static int summary_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
+                        double *mean_gamma, double *lower, double *upper, double *prob_xi)
+{
+    bnr_chain *c = cs[0];
     const bnr_dev &d = c->d;
-    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
-    if (k_lo < 1 || k_lo > nsamp || k_hi < 1 || k_hi > nsamp) return fail(BNR_ERR_BAD_ARG, "order statistics must be between 1 and nsamp");
+    const long long S = (long long)nc * nsamp;
+    if (k_lo < 1 || k_lo > S || k_hi < 1 || k_hi > S)
+        return fail(BNR_ERR_BAD_ARG, nc == 1 ? "order statistics must be between 1 and nsamp" : "order statistics must be between 1 and nchains * nsamp");
     HIPCHK(hipSetDevice(c->device));
+    int rc;
+    if ((rc = pooled_quiesce(cs, nc))) return rc;
     const int np = d.q + d.V;
+    const size_t budget = (size_t)1 << 30;
+    long long blk = c->summary_block_cols > 0 ? c->summary_block_cols : (long long)(budget / ((size_t)S * sizeof(double)));
+    blk = std::min<long long>(std::max<long long>(blk, 1), np);
     double *buf = nullptr, *out = nullptr;
-    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (size_t)np * nsamp));
+    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (size_t)blk * (size_t)S));
     if (hipMalloc((void **)&out, sizeof(double) * 3 * (size_t)np) != hipSuccess) { (void)hipFree(buf); return fail(BNR_ERR_HIP, "hipMalloc failed"); }
-    dim3 block(32, 8);
-    hipLaunchKernelGGL(k_fetch_cols, dim3((d.q + 31) / 32, (nsamp + 31) / 32), block, 0, c->x.stream, (const double *)d.trace, d.rowlen, d.o_gamma, d.q, first_row - 1, nsamp, buf);
-    hipLaunchKernelGGL(k_fetch_cols, dim3((d.V + 31) / 32, (nsamp + 31) / 32), block, 0, c->x.stream, (const double *)d.trace, d.rowlen, d.o_xi, d.V, first_row - 1, nsamp, buf + (size_t)d.q * nsamp);
-    hipLaunchKernelGGL(k_summary, dim3(np), dim3(256), 0, c->x.stream, (const double *)buf, nsamp, d.q, k_lo, k_hi, out, out + np, out + 2 * (size_t)np);
+    const dim3 block(32, 8);
+    for (int p0 = 0; p0 < np; p0 += (int)blk) {
+        const int pc = std::min<int>((int)blk, np - p0);
+        const int g0 = std::min(p0, d.q), g1 = std::min(p0 + pc, d.q);          // gamma columns g0 .. g1 - 1 first, then xi columns x0 .. x1 - 1
+        const int x0 = std::max(p0, d.q) - d.q, x1 = std::max(p0 + pc, d.q) - d.q;
+        for (int k = 0; k < nc; ++k) {
+            const bnr_dev &dk = cs[k]->d;
+            double *dst = buf + (size_t)k * nsamp;
+            if (g1 > g0)
+                hipLaunchKernelGGL(k_fetch_cols, dim3((g1 - g0 + 31) / 32, (nsamp + 31) / 32), block, 0, c->x.stream, (const double *)dk.trace, dk.rowlen,
+                                   dk.o_gamma + g0, g1 - g0, first_row - 1, nsamp, dst, S);
+            if (x1 > x0)
+                hipLaunchKernelGGL(k_fetch_cols, dim3((x1 - x0 + 31) / 32, (nsamp + 31) / 32), block, 0, c->x.stream, (const double *)dk.trace, dk.rowlen,
+                                   dk.o_xi + x0, x1 - x0, first_row - 1, nsamp, dst + (size_t)(g1 - g0) * (size_t)S, S);
+        }
+        hipLaunchKernelGGL(k_summary, dim3(pc), dim3(256), 0, c->x.stream, (const double *)buf, (int)S, g1 - g0, k_lo, k_hi, out + p0, out + np + p0,
+                           out + 2 * (size_t)np + p0);
+    }
     std::vector<double> host(3 * (size_t)np);
     hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, c->x.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->x.stream);
@@ -2111,6 +2171,21 @@ int bnr_chain_summary(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t k_
     memcpy(lower, host.data() + np, sizeof(double) * d.q);
     memcpy(upper, host.data() + 2 * (size_t)np, sizeof(double) * d.q);
     return check_launch("k_summary");
+}
+int bnr_chain_summary(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
+                      double *mean_gamma, double *lower, double *upper, double *prob_xi)
+{
+    if (!c || !mean_gamma || !lower || !upper || !prob_xi) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > c->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    return summary_call(&c, 1, first_row, nsamp, k_lo, k_hi, mean_gamma, lower, upper, prob_xi);
+}
+int bnr_chains_summary(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
+                       double *mean_gamma, double *lower, double *upper, double *prob_xi)
+{
+    if (!chains || !mean_gamma || !lower || !upper || !prob_xi) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
+    return summary_call(chains, nchains, first_row, nsamp, k_lo, k_hi, mean_gamma, lower, upper, prob_xi);
 }
 
 // Effective sample size (an addition: the reference only has split-Rhat).  Per-chain message: for both halves of the window
@@ -2129,8 +2204,8 @@ int bnr_chain_ess_stats(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t 
     HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (size_t)np * nsamp));
     if (hipMalloc((void **)&out, sizeof(double) * width) != hipSuccess) { (void)hipFree(buf); return fail(BNR_ERR_HIP, "hipMalloc failed"); }
     dim3 block(32, 8);
-    hipLaunchKernelGGL(k_fetch_cols, dim3((d.q + 31) / 32, (nsamp + 31) / 32), block, 0, c->x.stream, (const double *)d.trace, d.rowlen, d.o_gamma, d.q, first_row - 1, nsamp, buf);
-    hipLaunchKernelGGL(k_fetch_cols, dim3((d.V + 31) / 32, (nsamp + 31) / 32), block, 0, c->x.stream, (const double *)d.trace, d.rowlen, d.o_xi, d.V, first_row - 1, nsamp, buf + (size_t)d.q * nsamp);
+    hipLaunchKernelGGL(k_fetch_cols, dim3((d.q + 31) / 32, (nsamp + 31) / 32), block, 0, c->x.stream, (const double *)d.trace, d.rowlen, d.o_gamma, d.q, first_row - 1, nsamp, buf, (long long)nsamp);
+    hipLaunchKernelGGL(k_fetch_cols, dim3((d.V + 31) / 32, (nsamp + 31) / 32), block, 0, c->x.stream, (const double *)d.trace, d.rowlen, d.o_xi, d.V, first_row - 1, nsamp, buf + (size_t)d.q * nsamp, (long long)nsamp);
     hipLaunchKernelGGL(k_acov, dim3(np, 2), dim3(256), 0, c->x.stream, (const double *)buf, nsamp, np, max_lag, out);
     hipError_t e = hipMemcpyAsync(stats, out, sizeof(double) * width, hipMemcpyDeviceToHost, c->x.stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->x.stream);
@@ -2139,16 +2214,18 @@ int bnr_chain_ess_stats(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t 
     return check_launch("k_acov");
 }
 
-// Posterior of the mean response mu + x . gamma of m new rows over rows first_row .. first_row+nsamp-1 of this chain (an addition to the
+// Posterior of the mean response mu + x . gamma of m new rows over rows first_row .. first_row+nsamp-1 of the chains listed (an addition to the
 // reference): X_pred goes to the device in its own element type and is converted there (k_x_convert with m rows), then predict_rows.
-static int predict_call(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const x_source &xs, const double *y, int32_t k_lo, int32_t k_hi,
-                        double *mean, double *lower, double *upper, double *lpd, double *pwaic)
+// pred_lower / pred_upper / pit (host, nullable): the extras of the pooled entry points.
+static int predict_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t m, const x_source &xs, const double *y, int32_t k_lo,
+                        int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic, uint64_t pred_seed, double *pred_lower,
+                        double *pred_upper, double *pit)
 {
-    if (!c || !mean || !lower || !upper || (!xs.X && !xs.mats) || (y && (!lpd || !pwaic))) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+    bnr_chain *c = cs[0];
     const bnr_dev &d = c->d;
-    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
-    if (k_lo < 1 || k_lo > nsamp || k_hi < 1 || k_hi > nsamp) return fail(BNR_ERR_BAD_ARG, "order statistics must be between 1 and nsamp");
+    const long long S = (long long)nc * nsamp;
+    if (k_lo < 1 || k_lo > S || k_hi < 1 || k_hi > S)
+        return fail(BNR_ERR_BAD_ARG, nc == 1 ? "order statistics must be between 1 and nsamp" : "order statistics must be between 1 and nchains * nsamp");
     if (m < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows");
     if (xs.dtype < BNR_F64 || xs.dtype > BNR_F32) return fail(BNR_ERR_BAD_ARG, "unknown element type of X");
     if (xs.mats) for (int i = 0; i < m; ++i) if (!xs.mats[i]) return fail(BNR_ERR_BAD_ARG, "NULL adjacency matrix");
@@ -2158,8 +2235,10 @@ static int predict_call(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t 
     dev_tmp tmp;
     double *Xd = nullptr, *yd = nullptr, *out = nullptr;
     int rc;
+    if ((rc = pooled_quiesce(cs, nc))) return rc;
     if ((rc = tmp.alloc(&Xd, (size_t)m_pad * q16, st))) return rc;             // zero rows m .. m_pad - 1 and columns q .. q16 - 1 (k_predict)
-    if ((rc = tmp.alloc(&out, (size_t)5 * m, st))) return rc;
+    const bool extras = pred_lower || pit;
+    if ((rc = tmp.alloc(&out, (size_t)(extras ? 8 : 5) * m, st))) return rc;
     const size_t es = dtype_size(xs.dtype);
     if (!xs.mats && xs.dtype == BNR_F64) {
         HIPCHK(hipMemcpy2DAsync(Xd, (size_t)m_pad * sizeof(double), xs.X, (size_t)m * sizeof(double), (size_t)m * sizeof(double), d.q, hipMemcpyHostToDevice, st));
@@ -2184,9 +2263,11 @@ static int predict_call(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t 
         if ((rc = tmp.alloc(&yd, (size_t)m, st))) return rc;
         HIPCHK(hipMemcpyAsync(yd, y, sizeof(double) * m, hipMemcpyHostToDevice, st));
     }
-    if ((rc = predict_rows(c, first_row, nsamp, m, Xd, m_pad, yd, k_lo, k_hi, out, out + m, out + 2 * (size_t)m, y ? out + 3 * (size_t)m : nullptr,
-                           y ? out + 4 * (size_t)m : nullptr, tmp))) return rc;
-    std::vector<double> host(5 * (size_t)m);
+    const pred_extra ex{(unsigned long long)pred_seed, pred_lower ? out + 5 * (size_t)m : nullptr, pred_lower ? out + 6 * (size_t)m : nullptr,
+                        pit ? out + 7 * (size_t)m : nullptr};
+    if ((rc = predict_rows(cs, nc, first_row, nsamp, m, Xd, m_pad, yd, k_lo, k_hi, out, out + m, out + 2 * (size_t)m, y ? out + 3 * (size_t)m : nullptr,
+                           y ? out + 4 * (size_t)m : nullptr, tmp, nullptr, extras ? &ex : nullptr))) return rc;
+    std::vector<double> host((size_t)(extras ? 8 : 5) * m);
     hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("predict: ") + hipGetErrorString(e));
@@ -2198,44 +2279,108 @@ static int predict_call(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t 
         memcpy(lpd, host.data() + 3 * (size_t)m, sizeof(double) * m);
         memcpy(pwaic, host.data() + 4 * (size_t)m, sizeof(double) * m);
     }
+    if (pred_lower) {
+        memcpy(pred_lower, host.data() + 5 * (size_t)m, sizeof(double) * m);
+        memcpy(pred_upper, host.data() + 6 * (size_t)m, sizeof(double) * m);
+    }
+    if (pit) memcpy(pit, host.data() + 7 * (size_t)m, sizeof(double) * m);
     return BNR_OK;
+}
+// the checks of the single-chain entry points, in their order
+static int predict_one(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const x_source &xs, const double *y, int32_t k_lo, int32_t k_hi,
+                       double *mean, double *lower, double *upper, double *lpd, double *pwaic)
+{
+    if (!c || !mean || !lower || !upper || (!xs.X && !xs.mats) || (y && (!lpd || !pwaic))) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > c->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    return predict_call(&c, 1, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic, 0, nullptr, nullptr, nullptr);
+}
+// ... and of the pooled ones: pred_lower and pred_upper come together; lpd / pwaic and pit need y
+static int predict_pooled(bnr_chain *const *cs, int32_t nc, int32_t first_row, int32_t nsamp, int32_t m, const x_source &xs, const double *y, int32_t k_lo,
+                          int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic, uint64_t pred_seed, double *pred_lower,
+                          double *pred_upper, double *pit)
+{
+    if (!cs || !mean || !lower || !upper || (!xs.X && !xs.mats) || (y && (!lpd || !pwaic)) || (!pred_lower != !pred_upper))
+        return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (pit && !y) return fail(BNR_ERR_BAD_ARG, "pit needs the observed responses y");
+    if (int rc = pooled_check(cs, nc, first_row, nsamp)) return rc;
+    return predict_call(cs, nc, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic, pred_seed, pred_lower, pred_upper, pit);
 }
 int bnr_chain_predict(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const void *X, int32_t x_dtype, const double *y,
                       int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic)
 {
     x_source xs;
     xs.X = X; xs.dtype = x_dtype;
-    return predict_call(c, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic);
+    return predict_one(c, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic);
 }
 int bnr_chain_predict_from_matrices(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const void *const *A, int32_t x_dtype,
                                     const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic)
 {
     x_source xs;
     xs.mats = A; xs.dtype = x_dtype;
-    return predict_call(c, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic);
+    return predict_one(c, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic);
 }
-// pointwise lpd and WAIC penalty of the chain's own training rows: X (n_pad x q_pad, zero padded) and y are on the device already
-int bnr_chain_loglik_stats(bnr_chain *c, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic)
+int bnr_chains_predict(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t m, const void *X, int32_t x_dtype,
+                       const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic,
+                       uint64_t pred_seed, double *pred_lower, double *pred_upper, double *pit)
 {
-    if (!c || !lpd || !pwaic) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+    x_source xs;
+    xs.X = X; xs.dtype = x_dtype;
+    return predict_pooled(chains, nchains, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic, pred_seed, pred_lower, pred_upper, pit);
+}
+int bnr_chains_predict_from_matrices(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t m, const void *const *A,
+                                     int32_t x_dtype, const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper,
+                                     double *lpd, double *pwaic, uint64_t pred_seed, double *pred_lower, double *pred_upper, double *pit)
+{
+    x_source xs;
+    xs.mats = A; xs.dtype = x_dtype;
+    return predict_pooled(chains, nchains, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic, pred_seed, pred_lower, pred_upper, pit);
+}
+// the element-by-element host mirror of k_pred_noise's draws: out[(i - i0) ns + (s - s0)] = bnr_normal(seed, s, SITE_PRED, i, 0)
+void bnr_host_pred_noise(uint64_t seed, uint32_t s0, uint32_t ns, uint32_t i0, uint32_t ni, double *out)
+{
+    if (!out) return;
+    for (uint32_t i = 0; i < ni; ++i)
+        for (uint32_t s = 0; s < ns; ++s) out[(size_t)i * ns + s] = bnr_normal(seed, s0 + s, SITE_PRED, i0 + i, 0u);
+}
+// pointwise lpd and WAIC penalty (and, pooled entry point only, the PIT) of the chains' own training rows: X (n_pad x q_pad, zero padded) and y
+// are on the device already
+static int loglik_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic, double *pit)
+{
+    bnr_chain *c = cs[0];
     const bnr_dev &d = c->d;
-    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->x.stream;
     dev_tmp tmp;
     double *out = nullptr;
     int rc;
-    if ((rc = tmp.alloc(&out, (size_t)2 * d.n, st))) return rc;
-    if ((rc = predict_rows(c, first_row, nsamp, d.n, d.X, d.n_pad, d.y, 0, 0, nullptr, nullptr, nullptr, out, out + d.n, tmp))) return rc;
-    std::vector<double> host(2 * (size_t)d.n);
+    if ((rc = pooled_quiesce(cs, nc))) return rc;
+    if ((rc = tmp.alloc(&out, (size_t)(pit ? 3 : 2) * d.n, st))) return rc;
+    const pred_extra ex{0ull, nullptr, nullptr, pit ? out + 2 * (size_t)d.n : nullptr};
+    if ((rc = predict_rows(cs, nc, first_row, nsamp, d.n, d.X, d.n_pad, d.y, 0, 0, nullptr, nullptr, nullptr, out, out + d.n, tmp, nullptr, pit ? &ex : nullptr)))
+        return rc;
+    std::vector<double> host((size_t)(pit ? 3 : 2) * d.n);
     hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("loglik_stats: ") + hipGetErrorString(e));
     if ((rc = check_launch("k_pred_loglik"))) return rc;
     memcpy(lpd, host.data(), sizeof(double) * d.n);
     memcpy(pwaic, host.data() + d.n, sizeof(double) * d.n);
+    if (pit) memcpy(pit, host.data() + 2 * (size_t)d.n, sizeof(double) * d.n);
     return BNR_OK;
+}
+int bnr_chain_loglik_stats(bnr_chain *c, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic)
+{
+    if (!c || !lpd || !pwaic) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > c->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    return loglik_call(&c, 1, first_row, nsamp, lpd, pwaic, nullptr);
+}
+int bnr_chains_loglik_stats(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic, double *pit)
+{
+    if (!chains || !lpd || !pwaic) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
+    return loglik_call(chains, nchains, first_row, nsamp, lpd, pwaic, pit);
 }
 
 // loo 2.x's tail length M = ceil(min(0.2 S, 3 sqrt(S / r_eff))) of every row (r_eff NULL: 1), checked against BNR_PSIS_MAX_TAIL, and the
@@ -2261,26 +2406,26 @@ static int psis_tail_lengths(int m, int nsamp, const double *r_eff, std::vector<
     lds = std::max(8192, 16 * pmax);
     return BNR_OK;
 }
-// PSIS-LOO of the chain's own training rows over rows first_row .. first_row+nsamp-1 (k_predict, then k_psis on every block of rows)
-int bnr_chain_loo(bnr_chain *c, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo, double *pareto_k)
+// PSIS-LOO of the chains' own training rows over rows first_row .. first_row+nsamp-1 of every chain listed (k_predict, then k_psis on every block
+// of rows); the tail length comes from the pooled draw count
+static int loo_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo, double *pareto_k)
 {
-    if (!c || !elpd_loo || !pareto_k) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+    bnr_chain *c = cs[0];
     const bnr_dev &d = c->d;
-    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
     std::vector<int> M;
     int lds = 0, rc;
-    if ((rc = psis_tail_lengths(d.n, nsamp, r_eff, M, lds))) return rc;
+    if ((rc = psis_tail_lengths(d.n, nc * nsamp, r_eff, M, lds))) return rc;
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->x.stream;
     dev_tmp tmp;
     double *out = nullptr;
     int *tl = nullptr;
+    if ((rc = pooled_quiesce(cs, nc))) return rc;
     if ((rc = tmp.alloc(&out, (size_t)3 * d.n, st))) return rc;
     if ((rc = tmp.alloc(&tl, (size_t)d.n, st))) return rc;
     HIPCHK(hipMemcpyAsync(tl, M.data(), sizeof(int) * d.n, hipMemcpyHostToDevice, st));
     const psis_out ps{tl, lds, out, out + d.n, out + 2 * (size_t)d.n};
-    if ((rc = predict_rows(c, first_row, nsamp, d.n, d.X, d.n_pad, d.y, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, tmp, &ps))) return rc;
+    if ((rc = predict_rows(cs, nc, first_row, nsamp, d.n, d.X, d.n_pad, d.y, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, tmp, &ps))) return rc;
     std::vector<double> host(3 * (size_t)d.n);
     hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -2290,6 +2435,20 @@ int bnr_chain_loo(bnr_chain *c, int32_t first_row, int32_t nsamp, const double *
     memcpy(elpd_loo, host.data() + d.n, sizeof(double) * d.n);
     memcpy(pareto_k, host.data() + 2 * (size_t)d.n, sizeof(double) * d.n);
     return BNR_OK;
+}
+int bnr_chain_loo(bnr_chain *c, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo, double *pareto_k)
+{
+    if (!c || !elpd_loo || !pareto_k) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > c->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    return loo_call(&c, 1, first_row, nsamp, r_eff, lpd, elpd_loo, pareto_k);
+}
+int bnr_chains_loo(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo,
+                   double *pareto_k)
+{
+    if (!chains || !elpd_loo || !pareto_k) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
+    return loo_call(chains, nchains, first_row, nsamp, r_eff, lpd, elpd_loo, pareto_k);
 }
 // the same PSIS on a caller's m x nsamp log-likelihood matrix (host, row-major)
 int bnr_psis_loo(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *elpd_loo, double *pareto_k, double *lpd)
@@ -2517,6 +2676,12 @@ int bnr_chain_set_option(bnr_chain *c, const char *name, int64_t value)
         c->predict_block_rows = (int)value;
         return BNR_OK;
     }
+    if (!strcmp(name, "summary_block_cols")) {
+        // performance only: parameter columns per staging block of bnr_chain_summary / bnr_chains_summary (the first chain's setting counts)
+        if (value < 0 || value > (1 << 24)) return fail(BNR_ERR_BAD_ARG, "summary_block_cols must be between 0 (automatic) and 2^24");
+        c->summary_block_cols = (int)value;
+        return BNR_OK;
+    }
     if (!strcmp(name, "byte_x")) {
         // 0: the X passes read the f64 matrix also when a byte image exists; 1: back to the byte image (if the input had one)
         if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
@@ -2542,50 +2707,67 @@ static int late_kernels_lds_attributes(int bytes)
     // k_psis: the sorted tail, 16 bytes per entry for up to BNR_PSIS_MAX_TAIL entries
     const void *psis[] = {(const void *)&k_psis<0>, (const void *)&k_psis<1>};
     for (const void *f : psis) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * BNR_PSIS_MAX_TAIL));
-    return BNR_OK;
+    return BNR_OK;                                       // (k_pred_noise / k_pred_pit use no dynamic LDS: first referenced in predict_rows below, behind k_psis)
 }
 static void launch_late_xpass_group2(bnr_exec &x, int s)
 { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_xpass_group2<0>), dim3(x.shape->nblk_x * ((x.shape->n_pad + 255) / 256)), dim3(256), 16 * x.shape->chunk_x * sizeof(double), x.stream, bnr_many{x.cds}, s, x.nb); }
 static void launch_late_backproj64(bnr_exec &x, int s, int flags, size_t lds64)
 { BNR_LAUNCH(k_backproj64, dim3(round_up((x.shape->nblk_bp + 1) / 2, 8) * x.nb), dim3(256), lds64, x.stream, x, s, flags, x.nb); }
 
-// The device work of bnr_chain_predict / bnr_chain_loglik_stats, eagerly on the chain's own stream: the m rows of X (device, column-major,
-// leading dimension ldx, zero in columns q .. q16 - 1 and readable for whole 32-row tiles) in blocks of rows whose E buffer (rows x nsamp
-// doubles) stays near 1 GiB; per block k_predict, then k_summary (mean, k_lo-th / k_hi-th smallest of every E column; skipped when mean_d is
-// NULL) and k_pred_loglik (when yd is given).  Blocks start at multiples of 32 rows, so an output's MFMA tile position and K order -- and
-// with them every result, bit for bit -- do not depend on the block size.
-static int predict_rows(bnr_chain *c, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, int k_lo, int k_hi,
-                        double *mean_d, double *lo_d, double *hi_d, double *lpd_d, double *pwaic_d, dev_tmp &tmp, const psis_out *ps)
+// The device work of the prediction, log-likelihood and LOO calls, eagerly on the first chain's stream: the m rows of X (device, column-major,
+// leading dimension ldx, zero in columns q .. q16 - 1 and readable for whole 32-row tiles) in blocks of rows whose E buffer (rows x S doubles,
+// S = nc nsamp pooled draws: chain c's window in the columns c nsamp ..) stays near 1 GiB; per block one k_predict per chain, then k_summary
+// (mean, k_lo-th / k_hi-th smallest of every E column; skipped when mean_d is NULL), k_pred_loglik (when yd and lpd_d are given), k_pred_pit
+// (ex->pit), and last what overwrites E: k_pred_noise + a second k_summary (ex->plo / phi), or k_psis.  Blocks start at multiples of 32 rows, so
+// an output's MFMA tile position and K order -- and with them every result, bit for bit -- do not depend on the block size; the noise is keyed
+// by the row's index in the call.  With one chain and no extras: the launches of the single-chain entry points, unchanged.
+static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, int k_lo, int k_hi,
+                        double *mean_d, double *lo_d, double *hi_d, double *lpd_d, double *pwaic_d, dev_tmp &tmp, const psis_out *ps, const pred_extra *ex)
 {
+    bnr_chain *c = cs[0];
     const bnr_dev &d = c->d;
     hipStream_t st = c->x.stream;
+    const long long S = (long long)nc * nsamp;
     const size_t budget = (size_t)1 << 30;
-    long long blk = c->predict_block_rows > 0 ? c->predict_block_rows : (long long)(budget / ((size_t)nsamp * sizeof(double))) / 32 * 32;
+    long long blk = c->predict_block_rows > 0 ? c->predict_block_rows : (long long)(budget / ((size_t)S * sizeof(double))) / 32 * 32;
     blk = std::min<long long>(round_up((int)std::max<long long>(blk, 1), 32), round_up(m, 32));
-    double *E = nullptr, *tau2 = nullptr;
+    double *E = nullptr, *tau2 = nullptr, *pmean = nullptr;
     int rc;
-    if ((rc = tmp.alloc(&E, (size_t)blk * nsamp, st))) return rc;
-    if (yd) {
-        if ((rc = tmp.alloc(&tau2, (size_t)nsamp, st))) return rc;
-        hipLaunchKernelGGL(k_fetch_cols, dim3(1, (nsamp + 31) / 32), dim3(32, 8), 0, st, (const double *)d.trace, d.rowlen, (int)ROW_TAU2, 1, first_row - 1, nsamp, tau2);
+    if ((rc = tmp.alloc(&E, (size_t)blk * (size_t)S, st))) return rc;
+    if (yd || ex) {
+        if ((rc = tmp.alloc(&tau2, (size_t)S, st))) return rc;
+        for (int k = 0; k < nc; ++k)
+            hipLaunchKernelGGL(k_fetch_cols, dim3(1, (nsamp + 31) / 32), dim3(32, 8), 0, st, (const double *)cs[k]->d.trace, cs[k]->d.rowlen, (int)ROW_TAU2, 1,
+                               first_row - 1, nsamp, tau2 + (size_t)k * nsamp, S);
     }
+    if (ex && ex->plo && (rc = tmp.alloc(&pmean, (size_t)m, st))) return rc;      // (k_summary also writes the mean of y~: not returned)
     const int q16 = round_up(d.q, 16);
     for (int i0 = 0; i0 < m; i0 += (int)blk) {
         const int mr = std::min<int>((int)blk, m - i0);
-        if (mr > 16)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<2>), dim3((nsamp + 127) / 128, (mr + 31) / 32), dim3(256), 0, st, Xd + i0, ldx, q16,
-                               (const double *)d.trace, d.rowlen, d.o_gamma, first_row - 1, nsamp, mr, E);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<1>), dim3((nsamp + 127) / 128, 1), dim3(256), 0, st, Xd + i0, ldx, q16,
-                               (const double *)d.trace, d.rowlen, d.o_gamma, first_row - 1, nsamp, mr, E);
+        for (int k = 0; k < nc; ++k) {
+            const bnr_dev &dk = cs[k]->d;
+            if (mr > 16)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<2>), dim3((nsamp + 127) / 128, (mr + 31) / 32), dim3(256), 0, st, Xd + i0, ldx, q16,
+                                   (const double *)dk.trace, dk.rowlen, dk.o_gamma, first_row - 1, nsamp, mr, E + (size_t)k * nsamp, S);
+            else
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<1>), dim3((nsamp + 127) / 128, 1), dim3(256), 0, st, Xd + i0, ldx, q16,
+                                   (const double *)dk.trace, dk.rowlen, dk.o_gamma, first_row - 1, nsamp, mr, E + (size_t)k * nsamp, S);
+        }
         if (mean_d)
-            hipLaunchKernelGGL(k_summary, dim3(mr), dim3(256), 0, st, (const double *)E, nsamp, mr, k_lo, k_hi, mean_d + i0, lo_d + i0, hi_d + i0);
+            hipLaunchKernelGGL(k_summary, dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, mr, k_lo, k_hi, mean_d + i0, lo_d + i0, hi_d + i0);
         if (yd && lpd_d)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pred_loglik<0>), dim3(mr), dim3(256), 0, st, (const double *)E, nsamp, yd + i0, (const double *)tau2,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pred_loglik<0>), dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, yd + i0, (const double *)tau2,
                                lpd_d + i0, pwaic_d + i0);
         if (ps)                                        // last: k_psis turns the block's E into l in place
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis<1>), dim3(mr), dim3(256), ps->lds, st, E, nsamp, yd + i0, (const double *)tau2, ps->tail_len + i0,
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis<1>), dim3(mr), dim3(256), ps->lds, st, E, (int)S, yd + i0, (const double *)tau2, ps->tail_len + i0,
                                ps->lpd + i0, ps->elpd + i0, ps->khat + i0);
+        if (ex && ex->pit)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pred_pit<0>), dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, yd + i0, (const double *)tau2, ex->pit + i0);
+        if (ex && ex->plo) {                           // last: the block's E becomes draws of new observations in place
+            const int gx = (int)((S + 255) / 256), gy = std::max(1, std::min(mr, 8192 / gx));
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pred_noise<0>), dim3(gx, gy), dim3(256), 0, st, E, S, (int)S, mr, i0, (const double *)tau2, ex->seed);
+            hipLaunchKernelGGL(k_summary, dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, mr, k_lo, k_hi, pmean + i0, ex->plo + i0, ex->phi + i0);
+        }
     }
     return check_launch("k_predict");
 }

@@ -3268,8 +3268,9 @@ __global__ void k_x_convert(const T *raw, bool from_matrices, int n, int V, int 
 }
 
 // ===================================================================================== table transposes
-// out[r + nrows*d] = trace[(first + r)*rowlen + off + d]   (device row-major -> reference iteration-fastest)
-__global__ void k_fetch_cols(const double *trace, int rowlen, int off, int ncols, int first, int nrows, double *out)
+// out[r + ldo*d] = trace[(first + r)*rowlen + off + d]   (device row-major -> reference iteration-fastest; ldo = nrows for one chain's window,
+// the pooled draw count where the windows of several chains lie side by side in a column)
+__global__ void k_fetch_cols(const double *trace, int rowlen, int off, int ncols, int first, int nrows, double *out, long long ldo)
 {
     __shared__ double tile[32][33];
     int d0 = blockIdx.x * 32, r0 = blockIdx.y * 32;
@@ -3280,7 +3281,7 @@ __global__ void k_fetch_cols(const double *trace, int rowlen, int off, int ncols
     __syncthreads();
     for (int j = threadIdx.y; j < 32; j += blockDim.y) {
         int d = d0 + j, r = r0 + threadIdx.x;
-        if (r < nrows && d < ncols) out[(size_t)r + (size_t)nrows * d] = tile[threadIdx.x][j];
+        if (r < nrows && d < ncols) out[(size_t)r + (size_t)ldo * d] = tile[threadIdx.x][j];
     }
 }
 __global__ void k_load_cols(double *trace, int rowlen, int off, int ncols, int first, int nrows, const double *in)
@@ -3677,7 +3678,8 @@ __global__ __launch_bounds__(1024) void k_sdigits(const SRC chain_src, int s)
 // The mean response of a row x under draw s of the window is eta_s = mu_s + x . gamma_s (y = mu + X gamma + eps, gibbs.jl:270, 432, 566).
 // Both kernels are templates referenced only from the end of bnr_hip.hip, so that they sit behind the sweep kernels in the code object.
 //
-// k_predict: E[i nsamp + s] = mu_s + sum_e X[i, e] gamma_s[e] for the rows i < mrows of a block and the samples s < nsamp, by
+// k_predict: E[i lde + s] = mu_s + sum_e X[i, e] gamma_s[e] for the rows i < mrows of a block and the samples s < nsamp (lde = nsamp for one
+// chain; the pooled draw count where the launches of several chains fill the columns c nsamp .. of one E), by
 // v_mfma_f64_16x16x4_f64 with A = a 16-row tile of X, B = gamma^T of 16 samples.  X: column-major, leading dimension ldx, zero in
 // the columns q .. q16 - 1 (q16 = q rounded up to 16) and readable (zero) for 16 TI rows of every tile; gamma_s: trace row
 // first0 + s at o_gamma, K-contiguous (the columns q .. q16 - 1 of a trace row are the zero padding in front of S).
@@ -3689,7 +3691,7 @@ __global__ __launch_bounds__(1024) void k_sdigits(const SRC chain_src, int s)
 // tiles of blockIdx.y.  Samples past nsamp read the last sample's row and are not stored.
 template <int TI>
 __global__ __launch_bounds__(256) void k_predict(const double *X, int ldx, int q16, const double *trace, int rowlen, int o_gamma, int first0,
-                                                 int nsamp, int mrows, double *E)
+                                                 int nsamp, int mrows, double *E, long long lde)
 {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
     const int i0 = blockIdx.y * 16 * TI, s0 = blockIdx.x * 128 + w * 32;
@@ -3736,7 +3738,7 @@ __global__ __launch_bounds__(256) void k_predict(const double *X, int ldx, int q
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int i = i0 + 16 * a + g + 4 * r;
-                if (i < mrows) E[(size_t)i * nsamp + s] = mu[b] + acc[a][b][r];
+                if (i < mrows) E[(size_t)i * (size_t)lde + s] = mu[b] + acc[a][b][r];
             }
     }
 }
@@ -4022,4 +4024,51 @@ __global__ __launch_bounds__(256) void k_psis(double *L, int nsamp, const double
         elpd[i] = (m1 + log(s1)) - (m2 + log(s2));
         khat[i] = kh;
     }
+}
+
+// ===================================================================================== predictive interval and PIT (additions to the reference)
+// Both kernels work on a block of E as k_predict left it (row i's S pooled draws contiguous, leading dimension lde = S) and on the S-vector of
+// tau2 fetched chain by chain.  Templates referenced only from the end of bnr_hip.hip, so that they sit behind the sweep kernels in the code object.
+//
+// k_pred_noise: E_is <- E_is + sqrt(tau2_s) z_is in place: a draw of a NEW observation y~ = eta + eps, eps ~ N(0, tau2_s), of row i under pooled draw s.
+// z_is = bnr_normal(seed, it = s, SITE_PRED, elem = row0 + i, att = 0): keyed by the pooled draw index and the row's index in the caller's m rows
+// (row0 = first row of the block), so a draw does not depend on the block size, the grid, the input format or earlier calls, and the host gets the
+// same number from bnr_host_pred_noise (same source; the library is built with -ffp-contract=off, so product and sum round separately on both sides).
+// grid = (ceil(S / 256), rows in parallel <= mrows), 256 threads: a thread owns ONE draw s (sqrt(tau2_s) once) and walks the rows blockIdx.y,
+// blockIdx.y + gridDim.y, ...; a wave reads and writes 512 contiguous bytes per row.  One pass over 8 mrows S bytes each way; per element one
+// Philox-4x32-10, a log, a sqrt and bnr_cos2pi -- some 10^2 f64 and quarter-rate 32-bit multiply instructions per 16 bytes of traffic, so the
+// kernel is bound by the vector ALUs, not by HBM.  64-bit addressing; no LDS, no scratch.
+template <int LATE>
+__global__ __launch_bounds__(256) void k_pred_noise(double *E, long long lde, int S, int mrows, int row0, const double *tau2, unsigned long long seed)
+{
+    const int s = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (s >= S) return;
+    const double sd = sqrt(tau2[s]);
+    for (int i = (int)blockIdx.y; i < mrows; i += (int)gridDim.y) {
+        double *e = E + (size_t)i * (size_t)lde + (size_t)s;
+        const double z = bnr_normal((uint64_t)seed, (uint32_t)s, SITE_PRED, (uint32_t)(row0 + i), 0u);
+        *e = *e + sd * z;
+    }
+}
+
+// k_pred_pit: the probability integral transform of the observed response y_i under the posterior predictive, Rao-Blackwellised over the draws:
+// pit_i = (1 / S) sum_s Phi((y_i - E_is) / sqrt(tau2_s)), Phi(z) = erfc(-z / sqrt 2) / 2.  No random numbers.  One workgroup of 256 threads per
+// row; the sum in the fixed order of k_pred_loglik (thread-strided partial sums, then a tree): bitwise independent of the grid and the block of rows.
+#define BNR_SQRT2 1.41421356237309504880
+template <int LATE>
+__global__ __launch_bounds__(256) void k_pred_pit(const double *E, int nsamp, const double *y, const double *tau2, double *pit)
+{
+    __shared__ double ra[256];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const double *e = E + (size_t)i * nsamp;
+    const double yi = y[i];
+    double acc = 0.0;
+    for (int s = tid; s < nsamp; s += 256) {
+        const double z = (yi - e[s]) / sqrt(tau2[s]);
+        acc += 0.5 * erfc(-z / BNR_SQRT2);
+    }
+    ra[tid] = acc;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) { if (tid < w) ra[tid] += ra[tid + w]; __syncthreads(); }
+    if (tid == 0) pit[i] = ra[0] / nsamp;
 }

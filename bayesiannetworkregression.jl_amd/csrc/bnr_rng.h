@@ -19,7 +19,8 @@ enum {
     SITE_INIT_M_CHI = 5, SITE_INIT_M_N = 6, SITE_INIT_U = 7, SITE_INIT_GAMMA = 8,
     SITE_TAU2 = 16, SITE_XI = 17, SITE_U_Z = 18, SITE_G_Z1 = 19, SITE_G_Z2 = 20,
     SITE_D_GIG = 21, SITE_D_GAMMA = 22, SITE_THETA = 23, SITE_DELTA = 24, SITE_DELTA_COIN = 25,
-    SITE_M_CHI = 26, SITE_M_N = 27, SITE_MU = 28, SITE_LAMBDA = 29, SITE_PI = 30
+    SITE_M_CHI = 26, SITE_M_N = 27, SITE_MU = 28, SITE_LAMBDA = 29, SITE_PI = 30,
+    SITE_PRED = 40      // the noise of a new observation (k_pred_noise; not a site of the sweep): counter {pooled draw, SITE_PRED, row of the call, 0}, key = pred_seed
 };
 #define BNR_MAX_ATTEMPTS 100000u
 #define BNR_ATT_BOOST 0xFFFFFFFFu

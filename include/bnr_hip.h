@@ -28,10 +28,12 @@
 extern "C" {
 #endif
 
-#define BNR_ABI_VERSION 9   /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
+#define BNR_ABI_VERSION 10  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
                                5: + bnr_chain_create_typed, bnr_chain_create_from_matrices, bnr_device_synchronize; 6: + bnr_comm_info;
                                7: + option "xi_weights", bnr_host_xi_weight; 8: + bnr_chain_predict, bnr_chain_predict_from_matrices,
-                               bnr_chain_loglik_stats, option "predict_block_rows"; 9: + bnr_chain_loo, bnr_psis_loo (all additive) */
+                               bnr_chain_loglik_stats, option "predict_block_rows"; 9: + bnr_chain_loo, bnr_psis_loo;
+                               10: + bnr_chains_summary, bnr_chains_predict, bnr_chains_predict_from_matrices, bnr_chains_loglik_stats, bnr_chains_loo,
+                               bnr_host_pred_noise, option "summary_block_cols" (all additive) */
 
 enum {
     BNR_OK = 0,
@@ -179,7 +181,7 @@ int bnr_chain_summary(bnr_chain *chain, int32_t first_row, int32_t nsamp, int32_
  * -> lpd / pwaic (NULL when y is NULL)
  *   mean[m]           posterior mean of eta_s = mu_s + x.gamma_s over the draws s of the window
  *   lower[m], upper[m] the k_lo-th / k_hi-th smallest eta_s (1-based; exact selection, as bnr_chain_summary).  A credible interval of the MEAN
- *                     response, not a predictive interval for a new observation (that would add eps ~ N(0, tau2_s)).
+ *                     response, not a predictive interval for a new observation (that adds eps ~ N(0, tau2_s): pred_lower / pred_upper of bnr_chains_predict).
  *   lpd[m]            log (1/nsamp) sum_s N(y_i | eta_is, tau2_s): the pointwise log predictive density (log-mean-exp, no overflow)
  *   pwaic[m]          the sample variance (ddof 1) over s of log N(y_i | eta_is, tau2_s): the pointwise WAIC penalty
  * Computed on the device (k_predict: f64 MFMA GEMM over the trace rows; k_summary; k_pred_loglik) in blocks of rows (tunable
@@ -211,6 +213,42 @@ int bnr_chain_loglik_stats(bnr_chain *chain, int32_t first_row, int32_t nsamp, d
 int bnr_chain_loo(bnr_chain *chain, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo, double *pareto_k);
 int bnr_psis_loo(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *elpd_loo, double *pareto_k,
                  double *lpd);
+
+/* Pooled chains -- an ADDITION to the reference (whose Results keeps states[1] only): the statistics above over the POOLED WINDOW of several
+ * chains of one fit that live on one device.  The pooled window is the concatenation, in the order the chains are passed, of rows
+ * first_row..first_row+nsamp-1 of each of the nchains chains: S = nchains * nsamp draws, pooled draw c * nsamp + s (0-based) = the s-th window
+ * row of chains[c].  Ranks (k_lo, k_hi) are 1..S; the PSIS tail length comes from S (refused above BNR_PSIS_MAX_TAIL as for one chain).
+ *   bnr_chains_summary       = bnr_chain_summary over the pooled window.  The (q + V) S staged doubles are processed in blocks of parameter
+ *                              columns of about 1 GiB (tunable "summary_block_cols" of chains[0]); results do not depend on the block.
+ *   bnr_chains_predict / _from_matrices = bnr_chain_predict / _from_matrices over the pooled window, plus three nullable outputs:
+ *       pred_lower[m], pred_upper[m]  (both or neither) the k_lo-th / k_hi-th smallest draw of a NEW OBSERVATION y~_is = eta_is + sqrt(tau2_s) z_is:
+ *                        a predictive interval, where lower / upper are a credible interval of the mean response.  z_is is counter-based:
+ *                        bnr_host_normal(pred_seed, it = s (pooled draw index, 0-based), site = 40 (SITE_PRED), elem = i, att = 0) with i the
+ *                        0-based index of the row IN THIS CALL'S m rows -- so the same row predicted at another position of another call gets
+ *                        another draw, while the block size, the grid, the input format and earlier calls never change one.  The key is
+ *                        pred_seed itself (no chain id is added).  Host mirror: bnr_host_pred_noise.
+ *       pit[m]           (needs y) the probability integral transform of y_i under the posterior predictive, Rao-Blackwellised (no draws):
+ *                        (1/S) sum_s Phi((y_i - eta_is) / sqrt(tau2_s)), Phi(z) = erfc(-z / sqrt 2) / 2.  Uniform on (0, 1) over rows when the
+ *                        predictive distribution is calibrated.  (LOO-PIT, weighted by the PSIS weights, is not computed.)
+ *   bnr_chains_loglik_stats  = bnr_chain_loglik_stats over the pooled window; pit[n] (nullable): the PIT of the training responses.
+ *   bnr_chains_loo           = bnr_chain_loo over the pooled window.
+ * All work runs eagerly on chains[0]'s stream after the library has waited for the other chains' streams; no table, iteration counter, RNG
+ * state or counter of any chain is touched, and the chains may be members of a group.  BNR_ERR_BAD_ARG: chains NULL, nchains < 1, a NULL or
+ * repeated chain, chains on different devices or of different n, V, R, a pending asynchronous run on ANY of them, a window outside any
+ * chain's table, ranks outside 1..S, more than 2^31 - 1 pooled draws, only one of pred_lower / pred_upper, pit without y; otherwise the checks
+ * of the single-chain call.  With nchains == 1 and pred_lower, pred_upper, pit NULL every result is bit for bit the single-chain function's.
+ * DESIGN.md section 8. */
+int bnr_chains_summary(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
+                       double *mean_gamma, double *lower, double *upper, double *prob_xi);
+int bnr_chains_predict(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t m, const void *X, int32_t x_dtype,
+                       const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic,
+                       uint64_t pred_seed, double *pred_lower, double *pred_upper, double *pit);
+int bnr_chains_predict_from_matrices(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t m, const void *const *A,
+                       int32_t x_dtype, const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd,
+                       double *pwaic, uint64_t pred_seed, double *pred_lower, double *pred_upper, double *pit);
+int bnr_chains_loglik_stats(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic, double *pit);
+int bnr_chains_loo(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd,
+                   double *elpd_loo, double *pareto_k);
 
 /* Effective sample size -- an ADDITION to the reference (which only has split-Rhat; north-star item "Rhat/ESS check").
  * bnr_chain_ess_stats: this chain's message over rows first_row .. first_row+nsamp-1: for both halves of the window (the
@@ -331,6 +369,8 @@ int bnr_debug_set_exp(int32_t device, int32_t flags);
  *   "predict_block_rows" (chains only) rows per block of bnr_chain_predict / bnr_chain_loglik_stats, whose work buffer holds rows x nsamp
  *               doubles; rounded up to whole 32-row tiles.  0 (default): as many rows as fit in about 1 GiB.  The results are bitwise the same
  *               for every value.
+ *   "summary_block_cols" (chains only) parameter columns per staging block of bnr_chain_summary / bnr_chains_summary, whose buffer holds columns x S
+ *               doubles.  0 (default): as many as fit in about 1 GiB.  The results are bitwise the same for every value.
  *   "byte_x"    (chains only) 0: the X passes read the f64 matrix although a byte image of X exists; 1 (default): the byte image
  *               (kept when the model matrix came as Bool/UInt8, or as Int32/Int64 with every value in 0..255; docs/src/man/inputdata.md)
  *   "gram_i8"   (chains only; round 5) 1 (the default from n_pad^2 q >= 2.5e8 on, where it was measured faster -- n = 500, V = 100 and
@@ -352,6 +392,9 @@ double bnr_host_normal(uint64_t seed, uint32_t it, uint32_t site, uint32_t elem,
 double bnr_host_gamma(uint64_t seed, double shape, uint32_t it, uint32_t site, uint32_t elem);
 double bnr_host_gig(uint64_t seed, double lambda, double chi, double psi, uint32_t it, uint32_t elem);
 int32_t bnr_host_edge_index(int32_t V, int32_t l, int32_t k);   /* 0-based (l,k) -> 0-based e; utils.jl:50-55 */
+/* the noise of bnr_chains_predict's predictive draws (the kernel's own function; no GPU needed): an ni x ns block, ROW-major,
+ * out[(i - i0) * ns + (s - s0)] = bnr_host_normal(seed, s, 40 (SITE_PRED), i, 0) for rows i0 <= i < i0 + ni and pooled draws s0 <= s < s0 + ns */
+void bnr_host_pred_noise(uint64_t seed, uint32_t s0, uint32_t ns, uint32_t i0, uint32_t ni, double *out);
 /* the node weight of option "xi_weights" = 1 (the kernel's own function): w = (1 - Delta) exp(lt) / (Delta exp(lb) + (1 - Delta) exp(lt)),
  * written literally (gibbs.jl:349-351), so 0, 1 and NaN arise where they arise in the reference */
 double bnr_host_xi_weight(double lt, double lb, double Delta);

@@ -223,6 +223,86 @@ function loo_stats(ch::Chain, nburn, nsamp; r_eff=nothing)
     lpd, elpd, k
 end
 
+# ---- pooled chains (bnr_chains_* of include/bnr_hip.h; additions to the reference): the statistics above over the POOLED window of several
+# chains of one fit on one device -- S = length(chains) * nsamp draws, draw c * nsamp + s = the s-th window row of chains[c + 1]; ranks in 1..S.
+pooled_ranks(S, interval) = (Int(round(S * (100 - interval) / 200)), Int(round(S * (1 - (100 - interval) / 200))))
+
+function pooled_summary_stats(chains::Vector{Chain}, nburn, nsamp; interval=95)
+    ch = chains[1]
+    klo, khi = pooled_ranks(length(chains) * nsamp, interval)
+    hs = Ptr{Cvoid}[c.h for c in chains]
+    m, lo, hi, p = zeros(ch.q), zeros(ch.q), zeros(ch.q), zeros(ch.V)
+    GC.@preserve hs check(ccall((:bnr_chains_summary, LIB), Cint,
+        (Ptr{Ptr{Cvoid}}, Int32, Int32, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        hs, length(hs), nburn + 1, nsamp, klo, khi, m, lo, hi, p))
+    m, lo, hi, p
+end
+
+# predict_stats over the pooled window: (mean, lower, upper, lpd, pwaic, pred_lower, pred_upper, pit).  predict_observation adds the
+# predictive interval of a NEW observation (draws eta + sqrt(tau2) z, z keyed by pred_seed, the pooled draw and the row's index in Xnew)
+# and, with y, the probability integral transform of every y (uniform over rows when the predictive distribution is calibrated).
+function pooled_predict_stats(chains::Vector{Chain}, nburn, nsamp, Xnew; y=nothing, interval=95, x_transform=true, predict_observation=true, pred_seed=0)
+    ch = chains[1]
+    klo, khi = pooled_ranks(length(chains) * nsamp, interval)
+    hs = Ptr{Cvoid}[c.h for c in chains]
+    m = x_transform ? length(Xnew) : size(Xnew, 1)
+    y === nothing || length(y) == m || throw(ArgumentError("y must have one entry per new row"))
+    yv = y === nothing ? Float64[] : Vector{Float64}(y)
+    yp = y === nothing ? Ptr{Cdouble}(C_NULL) : pointer(yv)
+    mean, lo, hi, lpd, pw, plo, phi, pit = zeros(m), zeros(m), zeros(m), zeros(m), zeros(m), zeros(m), zeros(m), zeros(m)
+    plop = predict_observation ? pointer(plo) : Ptr{Cdouble}(C_NULL)
+    phip = predict_observation ? pointer(phi) : Ptr{Cdouble}(C_NULL)
+    pitp = (predict_observation && y !== nothing) ? pointer(pit) : Ptr{Cdouble}(C_NULL)
+    if x_transform
+        T = dtype_code(eltype(Xnew[1])) >= 0 ? eltype(Xnew[1]) : Float64
+        mats = [Matrix{T}(a) for a in Xnew]
+        all(size(a) == (ch.V, ch.V) for a in mats) || throw(ArgumentError("every matrix must be V x V"))
+        ptrs = [Ptr{Cvoid}(pointer(a)) for a in mats]
+        GC.@preserve hs mats ptrs yv plo phi pit check(ccall((:bnr_chains_predict_from_matrices, LIB), Cint,
+            (Ptr{Ptr{Cvoid}}, Int32, Int32, Int32, Int32, Ptr{Ptr{Cvoid}}, Int32, Ptr{Cdouble}, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, UInt64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+            hs, length(hs), nburn + 1, nsamp, m, ptrs, dtype_code(T), yp, klo, khi, mean, lo, hi, lpd, pw, UInt64(pred_seed), plop, phip, pitp))
+    else
+        T = dtype_code(eltype(Xnew)) >= 0 ? eltype(Xnew) : Float64
+        Xm = Matrix{T}(Xnew)
+        size(Xm, 2) == ch.q || throw(ArgumentError("X must have q = V(V+1)/2 columns"))
+        GC.@preserve hs Xm yv plo phi pit check(ccall((:bnr_chains_predict, LIB), Cint,
+            (Ptr{Ptr{Cvoid}}, Int32, Int32, Int32, Int32, Ptr{Cvoid}, Int32, Ptr{Cdouble}, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, UInt64, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+            hs, length(hs), nburn + 1, nsamp, m, Xm, dtype_code(T), yp, klo, khi, mean, lo, hi, lpd, pw, UInt64(pred_seed), plop, phip, pitp))
+    end
+    (mean, lo, hi, y === nothing ? nothing : lpd, y === nothing ? nothing : pw, predict_observation ? plo : nothing,
+     predict_observation ? phi : nothing, (predict_observation && y !== nothing) ? pit : nothing)
+end
+
+# (lpd, pwaic, pit) of the training rows over the pooled window
+function pooled_loglik_stats(chains::Vector{Chain}, nburn, nsamp)
+    n = chains[1].n
+    hs = Ptr{Cvoid}[c.h for c in chains]
+    lpd, pw, pit = zeros(n), zeros(n), zeros(n)
+    GC.@preserve hs check(ccall((:bnr_chains_loglik_stats, LIB), Cint, (Ptr{Ptr{Cvoid}}, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        hs, length(hs), nburn + 1, nsamp, lpd, pw, pit))
+    lpd, pw, pit
+end
+
+# PSIS-LOO of the training rows over the pooled window (the tail length comes from the pooled draw count): (lpd, elpd_loo, pareto_k)
+function pooled_loo_stats(chains::Vector{Chain}, nburn, nsamp; r_eff=nothing)
+    n = chains[1].n
+    hs = Ptr{Cvoid}[c.h for c in chains]
+    rv = r_eff === nothing ? Float64[] : (r_eff isa Number ? fill(Float64(r_eff), n) : Vector{Float64}(r_eff))
+    r_eff === nothing || length(rv) == n || throw(ArgumentError("r_eff must be a number or have one entry per training row"))
+    rp = r_eff === nothing ? Ptr{Cdouble}(C_NULL) : pointer(rv)
+    lpd, elpd, k = zeros(n), zeros(n), zeros(n)
+    GC.@preserve hs rv check(ccall((:bnr_chains_loo, LIB), Cint, (Ptr{Ptr{Cvoid}}, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        hs, length(hs), nburn + 1, nsamp, rp, lpd, elpd, k))
+    lpd, elpd, k
+end
+
+# the noise of the predictive draws as the device draws it (host code, no GPU): ns x ni, element [s - s0 + 1, i - i0 + 1]
+function pred_noise(seed, s0, ns, i0, ni)
+    out = zeros(ns, ni)
+    ccall((:bnr_host_pred_noise, LIB), Cvoid, (UInt64, UInt32, UInt32, UInt32, UInt32, Ptr{Cdouble}), UInt64(seed), s0, ns, i0, ni, out)
+    out
+end
+
 # ---- the ranks of a fit (bnr_comm): nothing (one process), or the library's RCCL communicator.  Rank 0 calls `unique_id()`, the
 # 128 bytes travel to the other workers by whatever connects them (e.g. `remotecall_fetch`), then EVERY rank calls `rccl_comm`.
 struct Comm
