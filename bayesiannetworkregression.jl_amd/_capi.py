@@ -82,6 +82,9 @@ _SIGS = {
                                                    _dp, C.c_int32, C.c_int32] + [_dp] * 5 + [C.c_uint64] + [_dp] * 3),
     "bnr_chains_loglik_stats": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
     "bnr_chains_loo": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
+    "bnr_chain_loo_predict": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp, C.c_double, C.c_double] + [_dp] * 8),
+    "bnr_chains_loo_predict": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, _dp, C.c_double, C.c_double] + [_dp] * 8),
+    "bnr_psis_weights": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp]),
     "bnr_comm_unique_id": (C.c_int, [C.POINTER(UniqueId)]),
     "bnr_comm_create_rccl": (C.c_int, [C.POINTER(UniqueId), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "bnr_comm_create_callback": (C.c_int, [C.c_int32, C.c_int32, ALLGATHER_CB, C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -231,6 +234,33 @@ def psis_loo_raw(loglik, r_eff=None, device=0):
         raise BnrError(BNR_ERR_HIP, _foreign_hip)
     check(L.bnr_psis_loo(int(device), m, S, _ptr(ll), _ptr(r), _ptr(elpd), _ptr(k), _ptr(lpd)))
     return lpd, elpd, k
+
+
+def psis_weights_raw(loglik, r_eff=None, device=0):
+    """(log_weights m x S, elpd_loo, pareto_k): the normalised PSIS log weights of every row of an m x S log-likelihood matrix, on the device
+    (bnr_psis_weights); a row with a non-finite entry gets NaN weights"""
+    ll = np.ascontiguousarray(loglik, dtype=np.float64)
+    if ll.ndim != 2 or ll.shape[0] < 1 or ll.shape[1] < 1:
+        raise ValueError("loglik must be an m x S matrix (rows x draws) with m, S >= 1")
+    m, S = ll.shape
+    r = r_eff_array(r_eff, m)
+    lw, elpd, k = np.empty((m, S)), np.empty(m), np.empty(m)
+    L = lib()
+    if _foreign_hip:
+        raise BnrError(BNR_ERR_HIP, _foreign_hip)
+    check(L.bnr_psis_weights(int(device), m, S, _ptr(ll), _ptr(r), _ptr(lw), _ptr(elpd), _ptr(k)))
+    return lw, elpd, k
+
+
+def loo_probs(p_lo, p_hi):
+    """the probabilities of the LOO predictive bounds as floats; ValueError (before any library call) unless 0 < p_lo < p_hi < 1"""
+    p_lo, p_hi = float(p_lo), float(p_hi)
+    if not (0.0 < p_lo < p_hi < 1.0):
+        raise ValueError("need 0 < p_lo < p_hi < 1, not p_lo = %r, p_hi = %r" % (p_lo, p_hi))
+    return p_lo, p_hi
+
+
+LOO_PREDICT_FIELDS = ("lpd", "elpd_loo", "pareto_k", "loo_mean", "loo_sd", "loo_pit", "loo_lower", "loo_upper")
 
 
 X_DTYPES = {np.dtype(np.float64): 0, np.dtype(np.bool_): 1, np.dtype(np.uint8): 1, np.dtype(np.int32): 2, np.dtype(np.int64): 3,
@@ -446,6 +476,15 @@ class Chain:
         check(self.L.bnr_chain_loo(self.h, int(first_row), int(nsamp), _ptr(r), _ptr(lpd), _ptr(elpd), _ptr(k)))
         return lpd, elpd, k
 
+    def loo_predict(self, first_row, nsamp, r_eff=None, p_lo=0.025, p_hi=0.975):
+        """The LOO predictive checks of the chain's own training rows over the row window, on the device (bnr_chain_loo_predict): the tuple
+        LOO_PREDICT_FIELDS = (lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper), one entry per row each."""
+        p_lo, p_hi = loo_probs(p_lo, p_hi)
+        r = r_eff_array(r_eff, self.n)
+        out = [np.empty(self.n) for _ in LOO_PREDICT_FIELDS]
+        check(self.L.bnr_chain_loo_predict(self.h, int(first_row), int(nsamp), _ptr(r), p_lo, p_hi, *[_ptr(o) for o in out]))
+        return tuple(out)
+
     def ess_stats(self, first_row, nsamp, max_lag):
         out = np.empty(2 * (2 + max_lag) * (self.q + self.V))
         check(self.L.bnr_chain_ess_stats(self.h, first_row, nsamp, max_lag, _ptr(out)))
@@ -619,6 +658,18 @@ def pooled_loo(chains, first_row, nsamp, r_eff=None):
     lpd, elpd, k = np.empty(n), np.empty(n), np.empty(n)
     check(chains[0].L.bnr_chains_loo(arr, len(chains), int(first_row), int(nsamp), _ptr(r), _ptr(lpd), _ptr(elpd), _ptr(k)))
     return lpd, elpd, k
+
+
+def pooled_loo_predict(chains, first_row, nsamp, r_eff=None, p_lo=0.025, p_hi=0.975, fields=LOO_PREDICT_FIELDS):
+    """Chain.loo_predict over the pooled window of `chains` (bnr_chains_loo_predict): the tuple LOO_PREDICT_FIELDS; an entry not named in
+    `fields` is not requested from the library and comes back as None"""
+    p_lo, p_hi = loo_probs(p_lo, p_hi)
+    chains, arr = _pooled(chains)
+    n = chains[0].n
+    r = r_eff_array(r_eff, n)
+    out = [np.empty(n) if f in fields else None for f in LOO_PREDICT_FIELDS]
+    check(chains[0].L.bnr_chains_loo_predict(arr, len(chains), int(first_row), int(nsamp), _ptr(r), p_lo, p_hi, *[_ptr(o) for o in out]))
+    return tuple(out)
 
 
 class Comm:

@@ -16,7 +16,8 @@ Julia is not available in this image, so the thin host layer a Julia user would 
   Results / BNRSummary   gibbs.jl:23-43     -> Results / BNRSummary
   Summary                gibbs.jl:1214-1250 -> Summary
   (additions)                               -> Predict / BNRPrediction (posterior of the mean response of new rows), WAIC, LOO / psis_loo;
-                                               pooled chains, predictive intervals and PIT: device_*_pooled, _host_pooled_*
+                                               pooled chains, predictive intervals and PIT: device_*_pooled, _host_pooled_*;
+                                               LOO predictive checks: LOOPredict / LOOPredictive, psis_weights, device_loo_predict
   lower_triangle / create_lower_tri / setup_X!  utils.jl:17-57, gibbs.jl:239-247
 
 All sampling runs on the GPU through libbnr_hip.so; this file holds only the schedule logic (chain fan-out,
@@ -92,7 +93,8 @@ class Results:
     prediction: "BNRPrediction" = None   # filled on request (predict_X=...): posterior of the mean response of new rows, computed on the GPU (see Predict)
     waic: dict = None                # filled on request (waic=True): WAIC of the training rows from the GPU's pointwise numbers (see WAIC)
     loo: dict = None                 # filled on request (loo=True): PSIS-LOO of the training rows computed on the GPU (see LOO)
-    stat_chains: int = None          # how many chains the device statistics above (summary_device, prediction, waic, loo) cover: 1 (chain 1's window), or
+    loo_predictive: "LOOPredictive" = None   # filled on request (loo_predict=True): the LOO predictive checks of the training rows (see LOOPredict)
+    stat_chains: int = None          # how many chains the device statistics above (summary_device, prediction, waic, loo, loo_predictive) cover: 1 (chain 1's window), or
                                      # every chain of the fit with pool_chains=True; None when the fit computed none
 
 
@@ -495,6 +497,228 @@ def device_predict_pooled(chains, nburn, nsamp, X_new, y_new=None, interval=95, 
     return _prediction(mean, lo, up, interval, lpd, None, plo, phi, pit, S)
 
 
+# ------------------------------------------------------------------------------------------ LOO predictive checks (an addition to the reference)
+# The PSIS weights themselves and the leave-one-out posterior predictive of every training row (include/bnr_hip.h, bnr_chains_loo_predict;
+# DESIGN.md section 8, "LOO predictive checks").  The host restatements are the fallback of LOOPredict over fetched tables and the yardstick of
+# the GPU tests.
+def _psis_weights_row(ll, M):
+    """_psis_row with the weights kept -> (lpd, elpd_loo, pareto_k, lwn): lwn = the log weights after smoothing and truncation at 0, normalised
+    (lw - logsumexp lw: loo's weights(normalize = TRUE, log = TRUE)); elpd_loo = log sum_s exp(lwn_s + l_s).  The tail is the M largest in
+    (lw, draw index), position j of that order gets the j-th GPD quantile -- _psis_row's stable argsort.  A non-finite l: NaN weights."""
+    S = ll.size
+    with np.errstate(all="ignore"):
+        mx = np.max(ll)
+        lpd = float(mx + np.log(np.sum(np.exp(ll - mx)) / S))
+    if not np.all(np.isfinite(ll)):
+        return lpd, math.nan, math.inf, np.full(S, np.nan)
+    r = -ll
+    lw = r - np.max(r)
+    k = math.inf
+    if M >= 5:
+        order = np.argsort(lw, kind="stable")
+        tail = order[S - M:]
+        lw_tail = lw[tail]
+        if not abs(lw_tail[-1] - lw_tail[0]) < np.finfo(np.float64).eps / 100:
+            ec = math.exp(lw[order[S - M - 1]])
+            k, sigma = _gpdfit(np.exp(lw_tail) - ec)
+            if math.isfinite(k):
+                p = (np.arange(1, M + 1) - 0.5) / M
+                with np.errstate(all="ignore"):
+                    q = np.full(M, np.nan) if (math.isnan(sigma) or sigma <= 0) else sigma * np.expm1(-k * np.log1p(-p)) / k
+                    lw[tail] = np.log(q + ec)
+    lw = np.where(lw > 0, 0.0, lw)
+    lz = _logsumexp(lw)
+    return lpd, _logsumexp(lw + ll) - lz, float(k), lw - lz
+
+
+def _psis_weights_host(loglik, r_eff=None):
+    """(log_weights m x S, elpd_loo, pareto_k) of every row of an m x S log-likelihood matrix, on the host"""
+    ll = np.asarray(loglik, dtype=np.float64)
+    if ll.ndim != 2 or ll.shape[0] < 1 or ll.shape[1] < 1:
+        raise ValueError("loglik must be an m x S matrix (rows x draws) with m, S >= 1")
+    m, S = ll.shape
+    r = _capi.r_eff_array(r_eff, m)
+    lw, e, k = np.empty((m, S)), np.empty(m), np.empty(m)
+    for i in range(m):
+        _lpd, e[i], k[i], lw[i] = _psis_weights_row(ll[i], _tail_length(S, 1.0 if r is None else r[i]))
+    return lw, e, k
+
+
+def psis_weights(loglik, r_eff=None, device=None):
+    """The PSIS weights of an m x S log-likelihood matrix (rows x draws) on the GPU (bnr_psis_weights): dict with log_weights (m x S, each row
+    normalised: loo's weights(log = TRUE)), elpd_loo_i, pareto_k and khat_threshold / n_high_k.  r_eff as for psis_loo."""
+    lw, e, k = _capi.psis_weights_raw(loglik, r_eff, 0 if device is None else int(device))
+    S = lw.shape[1]
+    thr = -math.inf if S == 1 else min(1.0 - 1.0 / math.log10(S), 0.7)
+    return dict(log_weights=lw, elpd_loo_i=e, pareto_k=k, khat_threshold=thr, n_high_k=int(np.sum(k > thr)))
+
+
+@dataclass
+class LOOPredictive:
+    """The leave-one-out posterior predictive of every training row, from the PSIS weights w_is over the `draws` posterior draws:
+    loo_mean = sum_s w eta, loo_sd = the sd of a new observation of the row (sqrt(sum_s w (tau2 + eta^2) - loo_mean^2)), loo_pit =
+    sum_s w Phi((y - eta) / sqrt(tau2)) (uniform over rows when the model is calibrated OUT of sample, which the in-sample PIT cannot show),
+    loo_lower / loo_upper = the (1 - interval/100)/2- and 1 - (1 - interval/100)/2-quantile of the mixture CDF sum_s w Phi((t - eta) / sqrt(tau2))
+    found by a bracketed root search -- the Rao-Blackwellised counterpart of the PIT, not loo's weighted sample quantile (.wquant).
+    Totals over the rows with finite outputs: rmse_loo = sqrt(mean (y - loo_mean)^2), r2_loo = 1 - Var(y - loo_mean) / Var(y) (ddof 0),
+    coverage = the share of y inside [loo_lower, loo_upper], ks = the Kolmogorov-Smirnov distance of loo_pit from U(0, 1); n_high_k = the
+    rows whose pareto_k is above khat_threshold (their numbers are not to be trusted), as in LOO."""
+    loo_mean: np.ndarray
+    loo_sd: np.ndarray
+    loo_pit: np.ndarray
+    loo_lower: np.ndarray
+    loo_upper: np.ndarray
+    lpd_i: np.ndarray
+    elpd_loo_i: np.ndarray
+    pareto_k: np.ndarray
+    rmse_loo: float
+    r2_loo: float
+    coverage: float
+    ks: float
+    interval: float
+    draws: int
+    khat_threshold: float
+    n_high_k: int
+
+
+def _loo_interval_probs(interval):
+    p_lo = (1.0 - interval / 100.0) / 2.0
+    return _capi.loo_probs(p_lo, 1.0 - p_lo)
+
+
+def _ks_uniform(u):
+    """the Kolmogorov-Smirnov distance of the sample u from U(0, 1)"""
+    u = np.sort(np.asarray(u, dtype=np.float64))
+    n = u.size
+    if n == 0:
+        return math.nan
+    i = np.arange(1, n + 1)
+    return float(max(np.max(i / n - u), np.max(u - (i - 1) / n)))
+
+
+def _loo_predictive(y, lpd, elpd, k, mean, sd, pit, lower, upper, interval, S):
+    """LOOPredictive from the pointwise arrays: the totals on the host over the rows whose outputs are all finite"""
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    arrs = [np.asarray(a, dtype=np.float64) for a in (mean, sd, pit, lower, upper)]
+    ok = np.all(np.isfinite(np.stack(arrs)), axis=0)
+    res = (y - arrs[0])[ok]
+    if res.size:
+        rmse = float(math.sqrt(np.mean(res ** 2)))
+        vy = float(np.var(y[ok]))
+        r2 = 1.0 - float(np.var(res)) / vy if vy > 0 else math.nan
+        cov = float(np.mean((y[ok] >= arrs[3][ok]) & (y[ok] <= arrs[4][ok])))
+    else:
+        rmse = r2 = cov = math.nan
+    thr = -math.inf if S == 1 else min(1.0 - 1.0 / math.log10(S), 0.7)
+    k = np.asarray(k, dtype=np.float64)
+    return LOOPredictive(arrs[0], arrs[1], arrs[2], arrs[3], arrs[4], np.asarray(lpd, dtype=np.float64), np.asarray(elpd, dtype=np.float64), k,
+                         rmse, r2, cov, _ks_uniform(arrs[2][ok]), interval, int(S), thr, int(np.sum(k > thr)))
+
+
+def _loo_bracket_c(p_lo, p_hi):
+    """the half-width of the quantile search's bracket in sds: the first c = 1, 1.5, 2, ... with Phi(-c) < min(p_lo, 1 - p_hi) / 2 (the library's loop)"""
+    pm = 0.5 * min(p_lo, 1.0 - p_hi)
+    c = 1.0
+    while not 0.5 * math.erfc(c * 0.70710678118654752440) < pm and c < 40.0:
+        c += 0.5
+    return c
+
+
+def _mixture_cdf(t, w, eta, sd):
+    """F(t) = sum_s w_s Phi((t - eta_s) / sd_s)"""
+    return float(np.sum(w * 0.5 * _erfc(-((t - eta) / sd) / math.sqrt(2.0))))
+
+
+def _bisect_quantile(F, p, lo, hi):
+    """the library's bisection: down to 2^-40 of the bracket, at most 64 halvings, the midpoint"""
+    tol = (hi - lo) * 2.0 ** -40
+    for _ in range(64):
+        if not hi - lo > tol:
+            break
+        mid = 0.5 * (lo + hi)
+        f = F(mid)
+        if f != f:
+            return math.nan
+        if f < p:
+            lo = mid
+        else:
+            hi = mid
+    return 0.5 * (lo + hi)
+
+
+def _mixture_quantile(p, w, eta, sd, c, solver=None):
+    """the p-quantile of the mixture CDF from the bracket [min(eta - c sd), max(eta + c sd)] -> (t, bracket width): scipy.optimize.brentq when
+    scipy is there (solver None) or asked for (solver="brentq"), else the library's bisection (solver="bisect")"""
+    lo, hi = float(np.min(eta - c * sd)), float(np.max(eta + c * sd))
+    width = hi - lo
+    if not (np.all(np.isfinite(w)) and math.isfinite(width) and width > 0):
+        return math.nan, width
+    F = lambda t: _mixture_cdf(t, w, eta, sd)
+    brentq = None
+    if solver != "bisect":
+        try:
+            from scipy.optimize import brentq
+        except ImportError:
+            if solver == "brentq":
+                raise
+    if brentq is None:
+        return _bisect_quantile(F, p, lo, hi), width
+    return float(brentq(lambda t: F(t) - p, lo, hi, xtol=width * 2.0 ** -44, rtol=8.9e-16, maxiter=500)), width
+
+
+def _loo_predict_rows(eta, tau2, y, lwn, p_lo, p_hi, solver=None):
+    """(loo_mean, loo_sd, loo_pit, loo_lower, loo_upper, bracket width) per row from eta (n x S), tau2 (S), y (n) and the normalised log weights"""
+    n = eta.shape[0]
+    sd = np.sqrt(tau2)
+    c = _loo_bracket_c(p_lo, p_hi)
+    out = np.full((6, n), np.nan)
+    for i in range(n):
+        if not np.all(np.isfinite(lwn[i])):
+            continue
+        w = np.exp(lwn[i])
+        m = float(np.sum(w * eta[i]))
+        out[0, i] = m
+        out[1, i] = math.sqrt(float(np.sum(w * (tau2 + eta[i] ** 2))) - m * m)
+        out[2, i] = _mixture_cdf(y[i], w, eta[i], sd)
+        out[3, i], out[5, i] = _mixture_quantile(p_lo, w, eta[i], sd, c, solver)
+        out[4, i], _ = _mixture_quantile(p_hi, w, eta[i], sd, c, solver)
+    return tuple(out)
+
+
+def _host_loo_predict(states, X, y, nburn, nsamp, interval=95, x_transform=False, r_eff=None, solver=None):
+    """device_loo_predict's LOOPredictive from the fetched tables of the chains, pooled in order"""
+    t, nb, S = _pool_tables(states, nburn, nsamp)
+    p_lo, p_hi = _loo_interval_probs(interval)
+    Xd = _dense_rows(_new_rows(X, x_transform, t["gamma"].shape[1], y))
+    yv = np.asarray(y, dtype=np.float64).reshape(-1)
+    ll = _host_loglik(t, Xd, yv, nb, S)
+    lpd = _psis_host(ll, r_eff)[0]
+    lwn, e, k = _psis_weights_host(ll, r_eff)
+    mean, sd, pit, lo, hi, _w = _loo_predict_rows(_host_eta(t, Xd, nb, S), t["tau2"][nb:nb + S, 0, 0], yv, lwn, p_lo, p_hi, solver)
+    return _loo_predictive(yv, lpd, e, k, mean, sd, pit, lo, hi, interval, S)
+
+
+def device_loo_predict(chains, y, nburn, nsamp, interval=95, r_eff=None):
+    """The LOO predictive checks of the training rows over rows nburn+1 .. nburn+nsamp of ALL the chains listed, pooled, on the GPU
+    (bnr_chains_loo_predict) -> LOOPredictive.  y: the training responses (for the totals; the device has its own copy)."""
+    chains = list(chains)
+    p_lo, p_hi = _loo_interval_probs(interval)
+    lpd, e, k, mean, sd, pit, lo, hi = _capi.pooled_loo_predict(chains, nburn + 1, nsamp, r_eff, p_lo, p_hi)
+    return _loo_predictive(y, lpd, e, k, mean, sd, pit, lo, hi, interval, nsamp * len(chains))
+
+
+def LOOPredict(results, X=None, y=None, x_transform=True, r_eff=None, interval=None):
+    """The LOO predictive checks of the training rows -> LOOPredictive.  Uses the GPU's numbers when the fit carried them (loo_predict=True), no
+    r_eff is passed and the interval is the fit's; otherwise the host restatement over results.state (chain 1's window) with the training
+    X, y passed in (interval default 95)."""
+    lp = results.loo_predictive
+    if lp is not None and r_eff is None and (interval is None or interval == lp.interval):
+        return lp
+    if results.state is None or X is None or y is None:
+        raise ValueError("LOOPredict needs Fit(..., loo_predict=True), or the state table (return_state=True) together with the training X and y")
+    return _host_loo_predict([results.state], X, y, results.burn_in, results.sampled, 95 if interval is None else interval, x_transform, r_eff)
+
+
 # ------------------------------------------------------------------------------------------ chain placement
 def _dist():
     """torch.distributed if THE CALLER has imported and initialised it, else None.  Never imports torch itself: a process group can only
@@ -720,14 +944,15 @@ def return_psrf_VOI(chainset, nburn, nsamp, fetch_state=True, summary_interval=N
 
 
 def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None, predict=None, waic=False, loo=False, loo_r_eff=None,
-            pool_chains=False, predict_observation=False, pred_seed=0):
+            pool_chains=False, predict_observation=False, pred_seed=0, loo_predict=None):
     """The Results a fit returns: chain 1's table (states[1], gibbs.jl:788) and/or its Summary statistics from the device; predict =
     (new rows, their y or None, interval), waic=True and loo=True add the prediction, WAIC and PSIS-LOO computed on the device over the
     same window.  pool_chains: those statistics over the pooled windows of all chains of the fit (one rank holds them all);
-    predict_observation: the prediction through the pooled entry point (one chain unless pool_chains) with the predictive bounds and the PIT."""
+    predict_observation: the prediction through the pooled entry point (one chain unless pool_chains) with the predictive bounds and the PIT;
+    loo_predict = (training y, interval): the LOO predictive checks (Results.loo_predictive), and Results.loo from the same call."""
     if pool_chains or predict_observation:
         return _finish_pooled(chainset, res, return_state, summary_interval, ess_max_lag, predict, waic, loo, loo_r_eff, pool_chains,
-                              predict_observation, pred_seed)
+                              predict_observation, pred_seed, loo_predict)
     if ess_max_lag is not None:                       # collective over ranks, like the PSRF
         res.essgamma, res.essxi = chainset.ess(res.burn_in + 1, res.sampled, ess_max_lag if ess_max_lag > 0 else None)
     if 1 in chainset.chains:
@@ -741,15 +966,19 @@ def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None, pre
             res.prediction = device_predict(ch, res.burn_in, res.sampled, predict[0], predict[1], predict[2])
         if waic:
             res.waic = _waic_from_pointwise(*ch.loglik_stats(res.burn_in + 1, res.sampled))
-        if loo:
+        if loo_predict is not None:                   # (implies loo: both from one call)
+            lp = device_loo_predict([ch], loo_predict[0], res.burn_in, res.sampled, loo_predict[1], loo_r_eff)
+            res.loo_predictive = lp
+            res.loo = _loo_from_pointwise(lp.lpd_i, lp.elpd_loo_i, lp.pareto_k, res.sampled)
+        elif loo:
             res.loo = _loo_from_pointwise(*ch.loo(res.burn_in + 1, res.sampled, loo_r_eff), res.sampled)
-        if summary_interval is not None or predict is not None or waic or loo:
+        if summary_interval is not None or predict is not None or waic or loo or loo_predict is not None:
             res.stat_chains = 1
     return res
 
 
 def _finish_pooled(chainset, res, return_state, summary_interval, ess_max_lag, predict, waic, loo, loo_r_eff, pool_chains, predict_observation,
-                   pred_seed):
+                   pred_seed, loo_predict=None):
     """_finish through the pooled entry points: over every chain of the fit (pool_chains), or over chain 1 alone with the predictive extras"""
     if ess_max_lag is not None:
         res.essgamma, res.essxi = chainset.ess(res.burn_in + 1, res.sampled, ess_max_lag if ess_max_lag > 0 else None)
@@ -769,11 +998,26 @@ def _finish_pooled(chainset, res, return_state, summary_interval, ess_max_lag, p
     if waic:
         lpd, pw, pit = _capi.pooled_loglik_stats(chains, nb + 1, ns, pit=True)
         res.waic = dict(_waic_from_pointwise(lpd, pw), pit_i=pit)
-    if loo:
+    if loo_predict is not None:                       # (implies loo: both from one call)
+        lp = device_loo_predict(chains, loo_predict[0], nb, ns, loo_predict[1], loo_r_eff)
+        res.loo_predictive = lp
+        res.loo = _loo_from_pointwise(lp.lpd_i, lp.elpd_loo_i, lp.pareto_k, S)
+    elif loo:
         res.loo = _loo_from_pointwise(*_capi.pooled_loo(chains, nb + 1, ns, loo_r_eff), S)
-    if summary_interval is not None or predict is not None or waic or loo:
+    if summary_interval is not None or predict is not None or waic or loo or loo_predict is not None:
         res.stat_chains = len(chains)
     return res
+
+
+def _loo_predict_request(loo_predict, predict_interval, y):
+    """Fit's loo_predict checked before any sampling: (training y, interval) for _finish, or None.  Refused where pool_chains is: the chains
+    of the fit spread over several ranks."""
+    if not loo_predict:
+        return None
+    if _rank_world()[1] > 1:
+        raise ValueError("loo_predict needs every chain of the fit on one rank: the chains are spread over %d torch.distributed ranks" % _rank_world()[1])
+    _loo_interval_probs(predict_interval)
+    return np.asarray(y, dtype=np.float64).reshape(-1), predict_interval
 
 
 def _pooled_request(pool_chains, predict_observation, predict_X):
@@ -822,7 +1066,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                      maxburn=50000, psrf_cutoff=1.2, x_transform=True, suppress_timer=False, num_chains=2, seed=None,
                      purge_burn=None, device=None, _keep=None, return_state=True, summary_interval=None, ess_max_lag=None,
                      xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
-                     pool_chains=False, predict_observation=False, pred_seed=None):
+                     pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False):
     """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
     xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
     xi_weights_code(xi_weights)
@@ -833,6 +1077,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
     X_new = XInput(X, x_transform)                 # X_new of gibbs.jl:907-918: element type kept, setup_X! runs on the device
     pred = _predict_request(predict_X, predict_y, predict_interval, x_transform, X_new)
     _pooled_request(pool_chains, predict_observation, predict_X)
+    lp_req = _loo_predict_request(loo_predict, predict_interval, y)
     _capi.r_eff_array(loo_r_eff, X_new.n)              # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
@@ -876,7 +1121,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
     print("R = %s nu=%s nburn= %d nsamp = %d" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f\n" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
     res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff, pool_chains, predict_observation,
-                  seed_eff if pred_seed is None else pred_seed)
+                  seed_eff if pred_seed is None else pred_seed, lp_req)
     if _keep is None:
         cs.close()
     return res
@@ -886,7 +1131,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                          maxgen=100000, psrf_cutoff=1.01, x_transform=True, suppress_timer=False, num_chains=2,
                          seed=None, purge_burn=None, device=None, return_state=True, summary_interval=None, ess_max_lag=None,
                          xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
-                         pool_chains=False, predict_observation=False, pred_seed=None):
+                         pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False):
     """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
     xi_weights_code(xi_weights)
     if nu == R:
@@ -896,6 +1141,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
     X_new = XInput(X, x_transform)
     pred = _predict_request(predict_X, predict_y, predict_interval, x_transform, X_new)
     _pooled_request(pool_chains, predict_observation, predict_X)
+    lp_req = _loo_predict_request(loo_predict, predict_interval, y)
     _capi.r_eff_array(loo_r_eff, X_new.n)              # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
@@ -941,7 +1187,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
     print("\nR = %s nu=%s nburn= %d nsamp = %d\n" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.4f. Max PSRF Gamma: %.4f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
     res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff, pool_chains, predict_observation,
-                  seed_eff if pred_seed is None else pred_seed)
+                  seed_eff if pred_seed is None else pred_seed, lp_req)
     cs.close()
     return res
 
@@ -950,7 +1196,7 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
         mingen=0, maxgen=0, psrf_cutoff=1.01, x_transform=True, suppress_timer=False, num_chains=2, seed=None,
         purge_burn=None, filename="parameters.log", device=None, return_state=True, summary_interval=None, ess_max_lag=None,
         xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
-        pool_chains=False, predict_observation=False, pred_seed=None):
+        pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False):
     """Fit! (gibbs.jl:725-751).  The `V` keyword is accepted and ignored, as in the reference.
     Extensions: summary_interval=95 computes Summary's statistics on the GPU (Results.summary_device);
     return_state=False then leaves the (large) state table on the device and frees it; ess_max_lag=0 (default lag
@@ -963,9 +1209,13 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     summary_interval, predict_X, waic and loo over the pooled windows of ALL chains of the fit instead (num_chains x nsamples draws; every chain
     must live on this rank; Results.stat_chains says how many were covered); predict_observation=True adds to the prediction the predictive
     interval of a new observation and, with predict_y, the PIT (BNRPrediction.pred_lower_bound / pred_upper_bound / pit), its noise keyed by
-    pred_seed (default: the fit's seed).  parameters.log keeps the reference's lines only."""
+    pred_seed (default: the fit's seed).  loo_predict=True adds the LOO predictive checks of the training rows (Results.loo_predictive, see
+    LOOPredict: PSIS-weighted mean, sd, PIT and a predict_interval% interval of every row, RMSE, R2, coverage); it implies loo (Results.loo comes
+    from the same device call), honours pool_chains and loo_r_eff, and like pool_chains needs every chain of the fit on this rank.
+    parameters.log keeps the reference's lines only."""
     xi_weights_code(xi_weights)
     _pooled_request(pool_chains, predict_observation, predict_X)
+    _loo_predict_request(loo_predict, predict_interval, y)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
         with open(filename, "w") as f:
@@ -984,10 +1234,11 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                                     return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
                                     xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval,
                                     waic=waic, loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation,
-                                    pred_seed=pred_seed)
+                                    pred_seed=pred_seed, loo_predict=loo_predict)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
                             return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
                             xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic,
-                            loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed)
+                            loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed,
+                            loo_predict=loo_predict)

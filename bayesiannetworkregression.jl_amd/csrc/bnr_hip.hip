@@ -177,9 +177,27 @@ struct pred_extra {
     unsigned long long seed;
     double *plo, *phi, *pit;
 };
+// the LOO predictive checks of a predict_rows call (ABI 11: k_psis_w, k_loo_moments, k_loo_quantile behind k_predict on every block; all device
+// pointers): the outputs of k_psis_w (never NULL), the moments (all three or none), the bounds (each nullable) with their probabilities and the
+// bracket's c (Phi(-c) < min(p_lo, 1 - p_hi) / 2)
+struct loow_out {
+    const int *tail_len;
+    int lds;
+    double *lpd, *elpd, *khat;
+    double *mean, *sd, *pit;
+    double *lower, *upper;
+    double p_lo, p_hi, c;
+};
 static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, int k_lo, int k_hi,
                         double *mean_d, double *lo_d, double *hi_d, double *lpd_d, double *pwaic_d, dev_tmp &tmp, const psis_out *ps = nullptr,
-                        const pred_extra *ex = nullptr);
+                        const pred_extra *ex = nullptr, const loow_out *lw = nullptr);
+// (defined at the very end of this file, behind every other kernel reference: see ensure_lds_attributes)
+static int loow_lds_attributes();
+static void launch_loow_inv_sd(hipStream_t st, const double *tau2, int S, double *isd);
+static void launch_loow_block(hipStream_t st, const loow_out &lw, const double *E, double *LW, int S, int mr, int i0, const double *yd, const double *tau2,
+                              const double *isd);
+static int psis_weights_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *log_weights, double *elpd,
+                               double *khat);
 static int psis_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *elpd, double *khat, double *lpd);
 static int ensure_lds_attributes(int device)
 {
@@ -2384,8 +2402,9 @@ int bnr_chains_loglik_stats(bnr_chain *const *chains, int32_t nchains, int32_t f
 }
 
 // loo 2.x's tail length M = ceil(min(0.2 S, 3 sqrt(S / r_eff))) of every row (r_eff NULL: 1), checked against BNR_PSIS_MAX_TAIL, and the
-// dynamic LDS of k_psis for the longest tail that is smoothed (M >= 5)
-static int psis_tail_lengths(int m, int nsamp, const double *r_eff, std::vector<int> &M, int &lds)
+// dynamic LDS of the longest tail that is smoothed (M >= 5), P = its length rounded up to a power of two: 16 bytes per entry for k_psis
+// (entry_bytes' default), 12 for k_psis_w; 8 KiB at least (the histogram of the radix select)
+static int psis_tail_lengths(int m, int nsamp, const double *r_eff, std::vector<int> &M, int &lds, int entry_bytes = 16)
 {
     M.assign(m, 0);
     int pmax = 0;
@@ -2403,7 +2422,7 @@ static int psis_tail_lengths(int m, int nsamp, const double *r_eff, std::vector<
             pmax = std::max(pmax, p);
         }
     }
-    lds = std::max(8192, 16 * pmax);
+    lds = std::max(8192, entry_bytes * pmax);
     return BNR_OK;
 }
 // PSIS-LOO of the chains' own training rows over rows first_row .. first_row+nsamp-1 of every chain listed (k_predict, then k_psis on every block
@@ -2463,6 +2482,79 @@ int bnr_psis_loo(int32_t device, int32_t m, int32_t nsamp, const double *loglik,
     HIPCHK(hipSetDevice(device));
     if ((rc = ensure_lds_attributes(device))) return rc;
     return psis_matrix(m, nsamp, loglik, M, lds, elpd_loo, pareto_k, lpd);
+}
+
+// LOO predictive checks (ABI 11) of the chains' own training rows over the pooled window: k_predict, then k_psis_w (the PSIS weights of the block),
+// k_loo_moments and k_loo_quantile on every block of rows.  Every output is nullable; lpd, elpd_loo and pareto_k always come from k_psis_w.
+static int loo_predict_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, const double *r_eff, double p_lo, double p_hi, double *lpd,
+                            double *elpd_loo, double *pareto_k, double *loo_mean, double *loo_sd, double *loo_pit, double *loo_lower, double *loo_upper)
+{
+    bnr_chain *c = cs[0];
+    const bnr_dev &d = c->d;
+    const bool bounds = loo_lower || loo_upper, moments = loo_mean || loo_sd || loo_pit;
+    double cc = 0.0;
+    if (bounds) {
+        if (!(p_lo > 0.0) || !(p_hi < 1.0) || !(p_lo < p_hi)) return fail(BNR_ERR_BAD_ARG, "need 0 < p_lo < p_hi < 1");
+        const double pm = 0.5 * std::min(p_lo, 1.0 - p_hi);
+        for (cc = 1.0; !(0.5 * std::erfc(cc * 0.70710678118654752440) < pm) && cc < 40.0; cc += 0.5) { }
+    }
+    std::vector<int> M;
+    int lds = 0, rc;
+    if ((rc = psis_tail_lengths(d.n, nc * nsamp, r_eff, M, lds, BNR_PSISW_ENTRY_BYTES))) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = loow_lds_attributes())) return rc;
+    hipStream_t st = c->x.stream;
+    dev_tmp tmp;
+    double *out = nullptr;
+    int *tl = nullptr;
+    const size_t n = (size_t)d.n;
+    if ((rc = pooled_quiesce(cs, nc))) return rc;
+    if ((rc = tmp.alloc(&out, 8 * n, st))) return rc;
+    if ((rc = tmp.alloc(&tl, n, st))) return rc;
+    HIPCHK(hipMemcpyAsync(tl, M.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
+    const loow_out lw{tl, lds, out, out + n, out + 2 * n, moments ? out + 3 * n : nullptr, moments ? out + 4 * n : nullptr, moments ? out + 5 * n : nullptr,
+                      loo_lower ? out + 6 * n : nullptr, loo_upper ? out + 7 * n : nullptr, p_lo, p_hi, cc};
+    if ((rc = predict_rows(cs, nc, first_row, nsamp, d.n, d.X, d.n_pad, d.y, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, tmp, nullptr, nullptr, &lw)))
+        return rc;
+    std::vector<double> host(8 * n);
+    hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("loo_predict: ") + hipGetErrorString(e));
+    if ((rc = check_launch("k_psis_w"))) return rc;
+    double *dst[8] = {lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper};
+    for (int k = 0; k < 8; ++k) if (dst[k]) memcpy(dst[k], host.data() + k * n, sizeof(double) * n);
+    return BNR_OK;
+}
+int bnr_chain_loo_predict(bnr_chain *c, int32_t first_row, int32_t nsamp, const double *r_eff, double p_lo, double p_hi, double *lpd, double *elpd_loo,
+                          double *pareto_k, double *loo_mean, double *loo_sd, double *loo_pit, double *loo_lower, double *loo_upper)
+{
+    if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > c->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    return loo_predict_call(&c, 1, first_row, nsamp, r_eff, p_lo, p_hi, lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper);
+}
+int bnr_chains_loo_predict(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, const double *r_eff, double p_lo, double p_hi,
+                           double *lpd, double *elpd_loo, double *pareto_k, double *loo_mean, double *loo_sd, double *loo_pit, double *loo_lower,
+                           double *loo_upper)
+{
+    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
+    return loo_predict_call(chains, nchains, first_row, nsamp, r_eff, p_lo, p_hi, lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper);
+}
+// the PSIS weights of a caller's m x nsamp log-likelihood matrix (host, row-major): the companion of bnr_psis_loo
+int bnr_psis_weights(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *log_weights, double *elpd_loo,
+                     double *pareto_k)
+{
+    if (!loglik || !log_weights) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (m < 1 || nsamp < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows and nsamp >= 1 draws");
+    std::vector<int> M;
+    int lds = 0, rc, ndev = 0;
+    if ((rc = psis_tail_lengths(m, nsamp, r_eff, M, lds, BNR_PSISW_ENTRY_BYTES))) return rc;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
+    HIPCHK(hipSetDevice(device));
+    if ((rc = ensure_lds_attributes(device))) return rc;
+    if ((rc = loow_lds_attributes())) return rc;
+    return psis_weights_matrix(m, nsamp, loglik, M, lds, log_weights, elpd_loo, pareto_k);
 }
 
 // Bulk effective sample size over all chains from the gathered messages (the estimator of Vehtari et al. 2021 as in
@@ -2722,18 +2814,20 @@ static void launch_late_backproj64(bnr_exec &x, int s, int flags, size_t lds64)
 // an output's MFMA tile position and K order -- and with them every result, bit for bit -- do not depend on the block size; the noise is keyed
 // by the row's index in the call.  With one chain and no extras: the launches of the single-chain entry points, unchanged.
 static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, int k_lo, int k_hi,
-                        double *mean_d, double *lo_d, double *hi_d, double *lpd_d, double *pwaic_d, dev_tmp &tmp, const psis_out *ps, const pred_extra *ex)
+                        double *mean_d, double *lo_d, double *hi_d, double *lpd_d, double *pwaic_d, dev_tmp &tmp, const psis_out *ps, const pred_extra *ex,
+                        const loow_out *lw)
 {
     bnr_chain *c = cs[0];
     const bnr_dev &d = c->d;
     hipStream_t st = c->x.stream;
     const long long S = (long long)nc * nsamp;
-    const size_t budget = (size_t)1 << 30;
+    const size_t budget = lw ? (size_t)1 << 29 : (size_t)1 << 30;          // (half the rows with the log weights beside E: E + LW stay near 1 GiB)
     long long blk = c->predict_block_rows > 0 ? c->predict_block_rows : (long long)(budget / ((size_t)S * sizeof(double))) / 32 * 32;
     blk = std::min<long long>(round_up((int)std::max<long long>(blk, 1), 32), round_up(m, 32));
-    double *E = nullptr, *tau2 = nullptr, *pmean = nullptr;
+    double *E = nullptr, *tau2 = nullptr, *pmean = nullptr, *LW = nullptr, *isd = nullptr;
     int rc;
     if ((rc = tmp.alloc(&E, (size_t)blk * (size_t)S, st))) return rc;
+    if (lw && (rc = tmp.alloc(&LW, (size_t)blk * (size_t)S, st))) return rc;
     if (yd || ex) {
         if ((rc = tmp.alloc(&tau2, (size_t)S, st))) return rc;
         for (int k = 0; k < nc; ++k)
@@ -2741,6 +2835,10 @@ static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, 
                                first_row - 1, nsamp, tau2 + (size_t)k * nsamp, S);
     }
     if (ex && ex->plo && (rc = tmp.alloc(&pmean, (size_t)m, st))) return rc;      // (k_summary also writes the mean of y~: not returned)
+    if (lw && (lw->lower || lw->upper)) {
+        if ((rc = tmp.alloc(&isd, (size_t)S, st))) return rc;
+        launch_loow_inv_sd(st, tau2, (int)S, isd);
+    }
     const int q16 = round_up(d.q, 16);
     for (int i0 = 0; i0 < m; i0 += (int)blk) {
         const int mr = std::min<int>((int)blk, m - i0);
@@ -2758,6 +2856,8 @@ static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, 
         if (yd && lpd_d)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pred_loglik<0>), dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, yd + i0, (const double *)tau2,
                                lpd_d + i0, pwaic_d + i0);
+        if (lw)                                        // the LOO predictive checks read E: before anything that overwrites it
+            launch_loow_block(st, *lw, E, LW, (int)S, mr, i0, yd, tau2, isd);
         if (ps)                                        // last: k_psis turns the block's E into l in place
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis<1>), dim3(mr), dim3(256), ps->lds, st, E, (int)S, yd + i0, (const double *)tau2, ps->tail_len + i0,
                                ps->lpd + i0, ps->elpd + i0, ps->khat + i0);
@@ -2806,6 +2906,70 @@ static int psis_matrix(int m, int nsamp, const double *loglik, const std::vector
         if (lpd) memcpy(lpd, host.data(), sizeof(double) * m);
         memcpy(elpd, host.data() + m, sizeof(double) * m);
         memcpy(khat, host.data() + 2 * (size_t)m, sizeof(double) * m);
+    }
+    return BNR_OK;
+}
+
+// ----------------------------------------------------------------------------------------- every reference to the kernels of the LOO predictive checks (ABI 11)
+// k_psis_w: the sorted tail, 12 bytes per entry for up to BNR_PSIS_MAX_TAIL entries (on the current device; cheap enough for once per call)
+static int loow_lds_attributes()
+{
+    const void *fns[] = {(const void *)&k_psis_w<0>, (const void *)&k_psis_w<1>};
+    for (const void *f : fns) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, BNR_PSISW_ENTRY_BYTES * BNR_PSIS_MAX_TAIL));
+    return BNR_OK;
+}
+static void launch_loow_inv_sd(hipStream_t st, const double *tau2, int S, double *isd)
+{ hipLaunchKernelGGL(HIP_KERNEL_NAME(k_inv_sd<0>), dim3((S + 255) / 256), dim3(256), 0, st, tau2, S, isd); }
+// a block of mr rows starting at row i0 of the call: the weights of the block into LW, then what reads them
+static void launch_loow_block(hipStream_t st, const loow_out &lw, const double *E, double *LW, int S, int mr, int i0, const double *yd, const double *tau2,
+                              const double *isd)
+{
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis_w<1>), dim3(mr), dim3(256), lw.lds, st, E, S, yd + i0, tau2, lw.tail_len + i0, LW, lw.lpd + i0, lw.elpd + i0,
+                       lw.khat + i0);
+    if (lw.mean)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_loo_moments<0>), dim3(mr), dim3(256), 0, st, E, (const double *)LW, S, yd + i0, tau2, lw.mean + i0, lw.sd + i0,
+                           lw.pit + i0);
+    if (lw.lower || lw.upper)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_loo_quantile<0>), dim3(mr, 2), dim3(256), 0, st, E, (const double *)LW, S, tau2, isd, lw.c, lw.p_lo, lw.p_hi,
+                           lw.lower ? lw.lower + i0 : nullptr, lw.upper ? lw.upper + i0 : nullptr);
+}
+// The device work of bnr_psis_weights on its own stream: the rows of the caller's matrix in blocks of about 512 MiB (l and the weights side by
+// side), k_psis_w<0> on every block, the block's weights copied back behind it.
+static int psis_weights_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *log_weights, double *elpd,
+                               double *khat)
+{
+    struct stream_guard {
+        hipStream_t s = nullptr;
+        ~stream_guard() { if (s) (void)hipStreamDestroy(s); }
+    } sg;
+    HIPCHK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
+    hipStream_t st = sg.s;
+    const size_t budget = (size_t)1 << 29;
+    const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, budget / ((size_t)nsamp * sizeof(double))));
+    int rc;
+    {
+        dev_tmp tmp;
+        double *Ld = nullptr, *Wd = nullptr, *out = nullptr;
+        int *tl = nullptr;
+        if ((rc = tmp.alloc(&Ld, (size_t)blk * nsamp, st))) return rc;
+        if ((rc = tmp.alloc(&Wd, (size_t)blk * nsamp, st))) return rc;
+        if ((rc = tmp.alloc(&out, (size_t)2 * m, st))) return rc;
+        if ((rc = tmp.alloc(&tl, (size_t)m, st))) return rc;
+        HIPCHK(hipMemcpyAsync(tl, tail_len.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
+        for (int i0 = 0; i0 < m; i0 += blk) {
+            const int mr = std::min(blk, m - i0);
+            HIPCHK(hipMemcpyAsync(Ld, loglik + (size_t)i0 * nsamp, sizeof(double) * (size_t)mr * nsamp, hipMemcpyHostToDevice, st));
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis_w<0>), dim3(mr), dim3(256), lds, st, (const double *)Ld, nsamp, (const double *)nullptr,
+                               (const double *)nullptr, (const int *)tl + i0, Wd, (double *)nullptr, out + i0, out + m + i0);
+            HIPCHK(hipMemcpyAsync(log_weights + (size_t)i0 * nsamp, Wd, sizeof(double) * (size_t)mr * nsamp, hipMemcpyDeviceToHost, st));
+        }
+        std::vector<double> host(2 * (size_t)m);
+        hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("psis_weights: ") + hipGetErrorString(e));
+        if ((rc = check_launch("k_psis_w"))) return rc;
+        if (elpd) memcpy(elpd, host.data(), sizeof(double) * m);
+        if (khat) memcpy(khat, host.data() + m, sizeof(double) * m);
     }
     return BNR_OK;
 }

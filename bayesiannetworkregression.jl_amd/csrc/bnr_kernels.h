@@ -4072,3 +4072,355 @@ __global__ __launch_bounds__(256) void k_pred_pit(const double *E, int nsamp, co
     for (int w = 128; w > 0; w >>= 1) { if (tid < w) ra[tid] += ra[tid + w]; __syncthreads(); }
     if (tid == 0) pit[i] = ra[0] / nsamp;
 }
+
+// ===================================================================================== LOO predictive checks (ABI 11; additions to the reference)
+// The PSIS weights themselves and, on top of them, the leave-one-out posterior predictive of every row: mean, standard deviation, PIT and the
+// quantiles of the mixture CDF.  All templates, referenced only from the very end of bnr_hip.hip (behind every kernel above in the code object).
+//
+// k_psis_w: k_psis with the per-draw weights kept.  One workgroup of 256 threads per row (blockIdx.x).  In: the row's eta (FROM_E = 1:
+// l_s = bnr_pred_ell(y_i, E_is, tau2_s)) or its l row (FROM_E = 0), read once and never written.  Out: LW + i nsamp, the NORMALISED log weights
+// lw_s - logsumexp_s lw_s (loo's weights(normalize = TRUE, log = TRUE)) after smoothing and truncation at 0; lpd (k_psis's, bit for bit),
+// elpd = log sum_s w_s exp(l_s) from the same weights, khat.  A row with a non-finite l: LW all NaN, elpd NaN, khat +inf.
+// l is written to LW in pass 1 and overwritten by the weights at the end (not recomputed from eta on every pass: a log and a division per
+// draw and pass against one 8-byte read that the pass needs in either form; it also makes the two instantiations one code path behind pass 1).
+// Passes over the row: 1 l -> LW, max, min, finiteness; 2-7 k_psis's exact radix select of K_c, the (M+1)-th largest 64-bit key of lw (pass 2 also
+// sums exp(l - max) for lpd); [7a-7c only when keys equal to K_c belong to the tail: radix select over the DRAW INDEX among the keys == K_c,
+// 11 + 11 + 10 bits, of s_c, the t-th largest such index]; 8 gather of the tail and the log-sum-exps of every other draw; 9 the weights.
+// Tail and ties: the tail is the M draws largest in the lexicographic order (lw, s) -- what a stable ascending argsort of lw picks -- i.e.
+// key > K_c, or key == K_c and s >= s_c; the composite key has no ties, so after the bitonic sort of (key, s) in LDS position j is one
+// definite draw and gets the j-th GPD quantile.  A tail entry is the key (8 bytes) and the draw index (4 bytes); its l is read back from
+// LW[s].  Dynamic LDS: max(8 KiB, 12 P) bytes, P = the smallest power of two >= the largest M of the launch: 96 KiB at M = BNR_PSIS_MAX_TAIL,
+// which with the 9.3 KiB of static LDS fits the CU's 160 KiB -- the longest tail is k_psis's, nothing more is refused.
+// The smoothed tail is scattered back to LW[s] behind a barrier; every sum is thread-strided and then a tree (running log-sum-exps as in
+// k_psis), the GPD grid has k_psis's fixed butterflies, the atomics are integer LDS atomics: results are bitwise independent of the grid,
+// of the block of rows and of the call.  Against k_psis, elpd and khat differ only in the order of tied terms and of the tail's sums.
+// 120 VGPRs, 99 SGPRs, 9 504 bytes of static LDS, no scratch (kernel-resource-usage, gfx950: 4 waves per SIMD); with the dynamic LDS -- 24 KiB
+// at the headline's pooled tail of 1 200 draws -- 4 workgroups per CU, one at the longest tail.
+#define BNR_PSISW_ENTRY_BYTES 12       // a tail entry of k_psis_w in LDS: the key (8) and the draw index (4); the host sizes the dynamic LDS with it
+__device__ __forceinline__ void bnr_hist_pick(const unsigned *hist, int nbins, unsigned want, int lane, unsigned *bin, unsigned *above, unsigned *cnt)
+{
+    // (wave 0) lane owns the bins [lane per, lane per + per); suffix sums over the lanes find the bin that holds the want-th largest entry
+    const int per = nbins / 64;
+    unsigned c = 0;
+    for (int b = 0; b < per; ++b) c += hist[lane * per + b];
+    unsigned suf = c;
+    for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_down(suf, o); if (lane + o < 64) suf += t; }
+    const unsigned long long ge = __ballot(suf >= want);
+    const int owner = 63 - __clzll((long long)ge);
+    if (lane == owner) {
+        unsigned acc = suf - c;
+        for (int b = per - 1; b >= 0; --b) {
+            const unsigned h = hist[lane * per + b];
+            if (acc + h >= want) { *bin = (unsigned)(lane * per + b); *above = acc; *cnt = h; break; }
+            acc += h;
+        }
+    }
+}
+template <int FROM_E>
+__global__ __launch_bounds__(256) void k_psis_w(const double *Lin, int nsamp, const double *y, const double *tau2, const int *tail_len, double *LW,
+                                                double *lpd, double *elpd, double *khat)
+{
+    extern __shared__ unsigned long long psisw_dyn[];
+    __shared__ double ra[256], rb[256], rc[256], rd[256], lth[BNR_PSIS_MAX_GRID];
+    __shared__ unsigned s_bin, s_above, s_cnt, s_pos;
+    __shared__ double s_theta, s_logz;
+    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const double *src = Lin + (size_t)i * nsamp;
+    double *l = LW + (size_t)i * nsamp;
+    const int M = tail_len[i];
+
+    // pass 1: l into LW, its max and min, finiteness
+    double mx = -INFINITY, mn = INFINITY;
+    int bad = 0;
+    for (int s = tid; s < nsamp; s += 256) {
+        const double v = FROM_E ? bnr_pred_ell(y[i], src[s], tau2[s]) : src[s];
+        l[s] = v;
+        mx = fmax(mx, v); mn = fmin(mn, v);
+        bad |= !isfinite(v);
+    }
+    ra[tid] = mx; rb[tid] = mn;
+    bad = __syncthreads_or(bad);
+    for (int w = 128; w > 0; w >>= 1) { if (tid < w) { ra[tid] = fmax(ra[tid], ra[tid + w]); rb[tid] = fmin(rb[tid], rb[tid + w]); } __syncthreads(); }
+    const double lmax = ra[0], rmax = -rb[0];          // max r = -min l
+    __syncthreads();
+    const bool select = !bad && M >= 5;
+
+    // passes 2-7: radix select of the (M+1)-th largest key of lw = -l - rmax; pass 2 also sums exp(l - lmax) for lpd
+    unsigned *hist = (unsigned *)psisw_dyn;
+    unsigned long long prefix = 0, mask = 0;
+    unsigned want = (unsigned)M + 1;
+    double se = 0.0;
+    for (int p = 0; p < 6; ++p) {
+        const int shift = p < 5 ? 53 - 11 * p : 0, nbins = p < 5 ? 2048 : 512;
+        if (select) {
+            for (int b = tid; b < nbins; b += 256) hist[b] = 0u;
+            __syncthreads();
+        }
+        for (int s = tid; s < nsamp; s += 256) {
+            const double v = l[s];
+            if (p == 0) se += exp(v - lmax);
+            if (select) {
+                const unsigned long long k = bnr_okey(-v - rmax);
+                if ((k & mask) == prefix) atomicAdd(&hist[(unsigned)(k >> shift) & (unsigned)(nbins - 1)], 1u);
+            }
+        }
+        if (!select) break;
+        __syncthreads();
+        if (wv == 0) bnr_hist_pick(hist, nbins, want, lane, &s_bin, &s_above, &s_cnt);
+        __syncthreads();
+        prefix |= (unsigned long long)s_bin << shift;
+        mask |= (unsigned long long)(nbins - 1) << shift;
+        want -= s_above;
+        __syncthreads();
+    }
+    // lpd: k_pred_loglik's tree
+    ra[tid] = se;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) { if (tid < w) ra[tid] += ra[tid + w]; __syncthreads(); }
+    if (tid == 0 && lpd) lpd[i] = lmax + log(ra[0] / nsamp);
+    __syncthreads();
+    if (bad) {
+        for (int s = tid; s < nsamp; s += 256) l[s] = NAN;
+        if (tid == 0) { if (elpd) elpd[i] = NAN; if (khat) khat[i] = INFINITY; }
+        return;
+    }
+
+    // passes 7a-7c: want - 1 of the keys == K_c belong to the tail: those of the largest draw index.  s_c = the (want - 1)-th largest
+    // draw index among them (no such pass without a tie at the cutoff: want == 1)
+    const unsigned long long Kc = select ? prefix : ~0ull;
+    unsigned sc = 0xFFFFFFFFu;
+    if (select && want > 1u) {
+        unsigned ipre = 0, imask = 0, iwant = want - 1u;
+        for (int p = 0; p < 3; ++p) {
+            const int shift = p == 0 ? 21 : p == 1 ? 10 : 0, nbins = p < 2 ? 2048 : 1024;
+            for (int b = tid; b < nbins; b += 256) hist[b] = 0u;
+            __syncthreads();
+            for (int s = tid; s < nsamp; s += 256) {
+                if (bnr_okey(-l[s] - rmax) == Kc && ((unsigned)s & imask) == ipre) atomicAdd(&hist[((unsigned)s >> shift) & (unsigned)(nbins - 1)], 1u);
+            }
+            __syncthreads();
+            if (wv == 0) bnr_hist_pick(hist, nbins, iwant, lane, &s_bin, &s_above, &s_cnt);
+            __syncthreads();
+            ipre |= s_bin << shift;
+            imask |= (unsigned)(nbins - 1) << shift;
+            iwant -= s_above;
+            __syncthreads();
+        }
+        sc = ipre;
+    }
+
+    // pass 8: the tail (key, draw) into LDS and the log-sum-exps of every other draw (K_c = all ones: no tail, every draw)
+    const int P = select ? (int)(1u << (32 - __clz(M - 1))) : 0;        // the smallest power of two >= M
+    unsigned long long *tk = psisw_dyn;
+    unsigned *ts = (unsigned *)(psisw_dyn + P);
+    if (tid == 0) s_pos = 0u;
+    __syncthreads();
+    double mA = -INFINITY, sA = 0.0, mB = -INFINITY, sB = 0.0;
+    for (int s = tid; s < nsamp; s += 256) {
+        const double v = l[s], lw = -v - rmax;
+        const unsigned long long k = bnr_okey(lw);
+        if (k > Kc || (k == Kc && (unsigned)s >= sc)) {
+            const unsigned pos = atomicAdd(&s_pos, 1u);
+            if (pos < (unsigned)M) { tk[pos] = k; ts[pos] = (unsigned)s; }
+        } else { bnr_lse_merge(mA, sA, lw + v, 1.0); bnr_lse_merge(mB, sB, lw, 1.0); }
+    }
+    double kh = INFINITY;
+    if (select) {
+        bool smooth = false;
+        double sigma = 0.0, ec = 0.0;
+        __syncthreads();
+        for (int j = (int)min(s_pos, (unsigned)M) + tid; j < P; j += 256) { tk[j] = ~0ull; ts[j] = 0xFFFFFFFFu; }     // (exactly M draws were gathered: j = M ..)
+        __syncthreads();
+        // bitonic sort of (key, draw) ascending; the padding ends behind the tail
+        for (int kk = 2; kk <= P; kk <<= 1)
+            for (int jj = kk >> 1; jj > 0; jj >>= 1) {
+                for (int t = tid; t < P / 2; t += 256) {
+                    const int a = (t / jj) * 2 * jj + (t % jj), b = a + jj;
+                    const unsigned long long ka = tk[a], kb = tk[b];
+                    const unsigned sa = ts[a], sb = ts[b];
+                    const bool gt = ka > kb || (ka == kb && sa > sb);
+                    if (gt == ((a & kk) == 0)) { tk[a] = kb; tk[b] = ka; ts[a] = sb; ts[b] = sa; }
+                }
+                __syncthreads();
+            }
+        const double cutoff = bnr_okey_inv(Kc);
+        const double lo = bnr_okey_inv(tk[0]), hi = bnr_okey_inv(tk[M - 1]);
+        if (!(fabs(hi - lo) < 2.220446049250313e-16 / 100)) {         // .Machine$double.eps / 100
+            // gpdfit on x_j = exp(lw_(j)) - exp(cutoff), ascending (k_psis's expressions and orders)
+            ec = exp(cutoff);
+            auto xv = [&](int j) { return exp(bnr_okey_inv(tk[j])) - ec; };
+            const double xN = xv(M - 1), xstar = xv((int)floor(M / 4.0 + 0.5) - 1);
+            const int mg = 30 + (int)floor(sqrt((double)M));
+            auto theta = [&](int j) { return 1.0 / xN + (1.0 - sqrt((double)mg / ((double)j + 0.5))) / 3.0 / xstar; };
+            for (int j = wv; j < mg; j += 4) {
+                const double a = -theta(j);
+                double acc = 0.0;
+                for (int t = lane; t < M; t += 64) acc += log1p(a * xv(t));
+                acc += __shfl_xor(acc, 32); acc += __shfl_xor(acc, 16); acc += __shfl_xor(acc, 8);
+                acc += __shfl_xor(acc, 4); acc += __shfl_xor(acc, 2); acc += __shfl_xor(acc, 1);
+                const double kj = acc / M;
+                if (lane == 0) lth[j] = M * (log(a / kj) - kj - 1.0);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                int jm = 0;
+                for (int j = 1; j < mg; ++j) if (lth[j] > lth[jm]) jm = j;
+                const double lm = lth[jm];
+                double sum = 0.0;
+                for (int j = 0; j < mg; ++j) if (j != jm) sum += exp(lth[j] - lm);
+                const double lse = lm + log1p(sum);
+                double th = 0.0;
+                for (int j = 0; j < mg; ++j) th += theta(j) * exp(lth[j] - lse);
+                s_theta = th;
+            }
+            __syncthreads();
+            const double th = s_theta;
+            double acc = 0.0;
+            for (int t = tid; t < M; t += 256) acc += log1p(-th * xv(t));
+            ra[tid] = acc;
+            __syncthreads();
+            for (int w = 128; w > 0; w >>= 1) { if (tid < w) ra[tid] += ra[tid + w]; __syncthreads(); }
+            const double k0 = ra[0] / M;
+            sigma = -k0 / th;
+            kh = k0 * M / (M + 10) + 10 * 0.5 / (M + 10);
+            if (isnan(kh)) kh = INFINITY;
+            smooth = isfinite(kh);
+        }
+        // the tail's log weights, smoothed (qgpd quantiles above the cutoff) or as they were, truncated at 0; kept in place of the key.
+        // The barrier ends every read of another thread's key (lo / hi above, the x_j of the fit): on the path without a fit there is none
+        // since the sort's, and the loop below overwrites tk[0] and tk[M - 1].  Behind it a thread touches only the entries j it owns.
+        __syncthreads();
+        for (int j = tid; j < M; j += 256) {
+            double lw;
+            if (smooth) {
+                const double pj = ((double)j + 0.5) / M;
+                const double qq = (isnan(sigma) || sigma <= 0.0) ? NAN : sigma * expm1(-kh * log1p(-pj)) / kh;
+                lw = log(qq + ec);
+            } else lw = bnr_okey_inv(tk[j]);
+            if (lw > 0.0) lw = 0.0;
+            if (ts[j] >= (unsigned)nsamp) continue;    // (never: the padding's index; keeps every access inside the row)
+            bnr_lse_merge(mA, sA, lw + l[ts[j]], 1.0);
+            bnr_lse_merge(mB, sB, lw, 1.0);
+            tk[j] = (unsigned long long)__double_as_longlong(lw);
+        }
+    }
+    __syncthreads();                                   // (every thread has read ra[0] above)
+    ra[tid] = mA; rb[tid] = sA; rc[tid] = mB; rd[tid] = sB;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) {
+            double m1 = ra[tid], s1 = rb[tid], m2 = rc[tid], s2 = rd[tid];
+            bnr_lse_merge(m1, s1, ra[tid + w], rb[tid + w]);
+            bnr_lse_merge(m2, s2, rc[tid + w], rd[tid + w]);
+            ra[tid] = m1; rb[tid] = s1; rc[tid] = m2; rd[tid] = s2;
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        const double lz = rc[0] + log(rd[0]);          // logsumexp_s lw_s
+        s_logz = lz;
+        if (elpd) elpd[i] = (ra[0] + log(rb[0])) - lz;
+        if (khat) khat[i] = kh;
+    }
+    __syncthreads();
+    // pass 9: the normalised log weights of the draws outside the tail over their l, then (behind a barrier: the pass reads the tail's l to
+    // tell its draws) the tail's, scattered from LDS
+    const double lz = s_logz;
+    for (int s = tid; s < nsamp; s += 256) {
+        const double lw = -l[s] - rmax;
+        const unsigned long long k = bnr_okey(lw);
+        if (!(k > Kc || (k == Kc && (unsigned)s >= sc))) l[s] = lw - lz;
+    }
+    __syncthreads();
+    if (select)
+        for (int j = tid; j < M; j += 256) if (ts[j] < (unsigned)nsamp) l[ts[j]] = __longlong_as_double((long long)tk[j]) - lz;
+}
+
+// k_inv_sd: isd_s = 1 / sqrt(tau2_s), once per pooled draw and call, for every evaluation of the mixture CDF in k_loo_quantile
+template <int LATE>
+__global__ __launch_bounds__(256) void k_inv_sd(const double *tau2, int S, double *isd)
+{
+    const int s = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (s < S) isd[s] = 1.0 / sqrt(tau2[s]);
+}
+
+// k_loo_moments: the moments of the LOO posterior predictive of row i, a mixture of N(eta_is, tau2_s) with the PSIS weights w_is = exp(LW_is):
+//   mean_i = sum_s w eta,  sd_i = sqrt(sum_s w (tau2 + eta^2) - mean_i^2),  pit_i = sum_s w Phi((y_i - eta) / sqrt(tau2))  (Phi as in k_pred_pit)
+// in one pass over (E, LW, tau2).  Layout of k_pred_pit: one workgroup of 256 threads per row, thread-strided partial sums, then a tree: bitwise
+// independent of the grid and the block of rows.  A refused row (LW NaN) gets NaN.  No random numbers, no dynamic LDS, no scratch; bound by
+// the exp and the erfc (some 10^2 f64 instructions per 16 bytes read), like k_pred_pit.  94 VGPRs, 6 KiB of LDS, no scratch.
+template <int LATE>
+__global__ __launch_bounds__(256) void k_loo_moments(const double *E, const double *LW, int nsamp, const double *y, const double *tau2, double *mean,
+                                                     double *sd, double *pit)
+{
+    __shared__ double ra[256], rb[256], rc[256];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    const double *e = E + (size_t)i * nsamp, *lw = LW + (size_t)i * nsamp;
+    const double yi = y[i];
+    double a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    for (int s = tid; s < nsamp; s += 256) {
+        const double w = exp(lw[s]), eta = e[s], t = tau2[s];
+        const double z = (yi - eta) / sqrt(t);
+        a1 += w * eta;
+        a2 += w * (t + eta * eta);
+        a3 += w * (0.5 * erfc(-z / BNR_SQRT2));
+    }
+    ra[tid] = a1; rb[tid] = a2; rc[tid] = a3;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) { if (tid < w) { ra[tid] += ra[tid + w]; rb[tid] += rb[tid + w]; rc[tid] += rc[tid + w]; } __syncthreads(); }
+    if (tid == 0) {
+        const double m = ra[0];
+        mean[i] = m; sd[i] = sqrt(rb[0] - m * m); pit[i] = rc[0];
+    }
+}
+
+// k_loo_quantile: the p-quantile of the mixture CDF F_i(t) = sum_s w_is Phi((t - eta_is) isd_s), Phi(z) = erfc(-z / sqrt 2) / 2, of row
+// blockIdx.x; blockIdx.y = 0: p_lo -> lower, 1: p_hi -> upper (a NULL output: nothing to do).  Bisection from the bracket
+// [min_s(eta_is - c sd_s), max_s(eta_is + c sd_s)], sd_s = sqrt(tau2_s), with the caller's c such that Phi(-c) < min(p_lo, 1 - p_hi) / 2, so that
+// F(lower end) < p < F(upper end) whatever the weights; F(mid) < p moves the lower end, anything else the upper one; stops when the bracket is no
+// wider than 2^-40 of the first one -- 40 halvings; BNR_LOOQ_MAX_IT caps the loop -- and returns the midpoint.  No sort, no random numbers.
+// Every F is summed in k_loo_moments's order (thread-strided, then a tree) and broadcast from LDS, so the whole workgroup takes the same branch
+// and the result is bitwise independent of the grid, the block of rows and the call.  A NaN F (a refused row) gives NaN.
+// Per evaluation and draw one exp (the weight) and one erfc; the reciprocal of sd is staged by k_inv_sd, -1 / sqrt 2 is a constant factor.
+// One workgroup per (row, bound): 2 x 40 evaluation passes per row over (E, LW), which stay in the L2 between passes.  90 VGPRs, 4 KiB of LDS,
+// no scratch.
+#define BNR_LOOQ_MAX_IT 64
+template <int LATE>
+__global__ __launch_bounds__(256) void k_loo_quantile(const double *E, const double *LW, int nsamp, const double *tau2, const double *isd, double c,
+                                                      double p_lo, double p_hi, double *lower, double *upper)
+{
+    __shared__ double ra[256], rb[256];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    double *out = blockIdx.y ? upper : lower;
+    if (!out) return;
+    const double p = blockIdx.y ? p_hi : p_lo;
+    const double *e = E + (size_t)i * nsamp, *lw = LW + (size_t)i * nsamp;
+    double mn = INFINITY, mx = -INFINITY;
+    for (int s = tid; s < nsamp; s += 256) {
+        const double eta = e[s], h = c * sqrt(tau2[s]);
+        mn = fmin(mn, eta - h); mx = fmax(mx, eta + h);
+    }
+    ra[tid] = mn; rb[tid] = mx;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) { if (tid < w) { ra[tid] = fmin(ra[tid], ra[tid + w]); rb[tid] = fmax(rb[tid], rb[tid + w]); } __syncthreads(); }
+    double lo = ra[0], hi = rb[0];
+    __syncthreads();
+    const double tol = (hi - lo) * 9.094947017729282e-13;             // 2^-40
+    bool nan = false;
+    for (int it = 0; it < BNR_LOOQ_MAX_IT && hi - lo > tol; ++it) {
+        const double mid = 0.5 * (lo + hi);
+        double acc = 0.0;
+        for (int s = tid; s < nsamp; s += 256) {
+            const double z = (mid - e[s]) * isd[s];
+            acc += exp(lw[s]) * (0.5 * erfc(z * -0.70710678118654752440));
+        }
+        ra[tid] = acc;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) { if (tid < w) ra[tid] += ra[tid + w]; __syncthreads(); }
+        const double F = ra[0];
+        __syncthreads();
+        if (F != F) { nan = true; break; }
+        if (F < p) lo = mid; else hi = mid;
+    }
+    if (tid == 0) out[i] = nan ? NAN : 0.5 * (lo + hi);
+}

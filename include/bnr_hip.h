@@ -28,12 +28,13 @@
 extern "C" {
 #endif
 
-#define BNR_ABI_VERSION 10  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
+#define BNR_ABI_VERSION 11  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
                                5: + bnr_chain_create_typed, bnr_chain_create_from_matrices, bnr_device_synchronize; 6: + bnr_comm_info;
                                7: + option "xi_weights", bnr_host_xi_weight; 8: + bnr_chain_predict, bnr_chain_predict_from_matrices,
                                bnr_chain_loglik_stats, option "predict_block_rows"; 9: + bnr_chain_loo, bnr_psis_loo;
                                10: + bnr_chains_summary, bnr_chains_predict, bnr_chains_predict_from_matrices, bnr_chains_loglik_stats, bnr_chains_loo,
-                               bnr_host_pred_noise, option "summary_block_cols" (all additive) */
+                               bnr_host_pred_noise, option "summary_block_cols"; 11: + bnr_chain_loo_predict, bnr_chains_loo_predict,
+                               bnr_psis_weights (all additive) */
 
 enum {
     BNR_OK = 0,
@@ -229,7 +230,7 @@ int bnr_psis_loo(int32_t device, int32_t m, int32_t nsamp, const double *loglik,
  *                        pred_seed itself (no chain id is added).  Host mirror: bnr_host_pred_noise.
  *       pit[m]           (needs y) the probability integral transform of y_i under the posterior predictive, Rao-Blackwellised (no draws):
  *                        (1/S) sum_s Phi((y_i - eta_is) / sqrt(tau2_s)), Phi(z) = erfc(-z / sqrt 2) / 2.  Uniform on (0, 1) over rows when the
- *                        predictive distribution is calibrated.  (LOO-PIT, weighted by the PSIS weights, is not computed.)
+ *                        predictive distribution is calibrated.  (In-sample for training rows; the leave-one-out PIT: bnr_chains_loo_predict.)
  *   bnr_chains_loglik_stats  = bnr_chain_loglik_stats over the pooled window; pit[n] (nullable): the PIT of the training responses.
  *   bnr_chains_loo           = bnr_chain_loo over the pooled window.
  * All work runs eagerly on chains[0]'s stream after the library has waited for the other chains' streams; no table, iteration counter, RNG
@@ -249,6 +250,39 @@ int bnr_chains_predict_from_matrices(bnr_chain *const *chains, int32_t nchains, 
 int bnr_chains_loglik_stats(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic, double *pit);
 int bnr_chains_loo(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd,
                    double *elpd_loo, double *pareto_k);
+
+/* LOO predictive checks (ABI 11) -- an ADDITION to the reference: the PSIS weights themselves and the leave-one-out posterior predictive of
+ * every training row over the pooled window of nchains >= 1 chains (draws and checks as bnr_chains_loo).  For row i and pooled draw s, with
+ * l_is = log N(y_i | eta_is, tau2_s) and lw_is the log weight of bnr_chain_loo after smoothing and truncation at 0:
+ *   w_is = exp(lw_is - logsumexp_s lw_is)                                   loo's weights(normalize = TRUE)
+ *   the tail = the M draws largest in the lexicographic order (lw, s) (what a stable ascending argsort of lw picks); position j of that
+ *       order gets the j-th quantile of the fitted generalized Pareto.  The composite key has no ties, so every w_is is well defined;
+ *       against bnr_chain_loo, whose tail order is (lw, l), elpd_loo and pareto_k can differ only by the order of tied terms.
+ *   lpd[i], elpd_loo[i], pareto_k[i]   as bnr_chains_loo (lpd bit for bit), elpd_loo[i] = log sum_s w_is exp(l_is) from the weights above
+ *   loo_mean[i]  = sum_s w_is eta_is
+ *   loo_sd[i]    = sqrt(sum_s w_is (tau2_s + eta_is^2) - loo_mean[i]^2): the sd of a NEW OBSERVATION of row i under the LOO predictive, a
+ *                  mixture moment (no random numbers)
+ *   loo_pit[i]   = sum_s w_is Phi((y_i - eta_is) / sqrt(tau2_s)), Phi(z) = erfc(-z / sqrt 2) / 2: the leave-one-out PIT
+ *   loo_lower[i], loo_upper[i] = the p_lo- and p_hi-quantile of the mixture CDF F_i(t) = sum_s w_is Phi((t - eta_is) / sqrt(tau2_s)), by
+ *                  bisection from [min_s(eta_is - c sd_s), max_s(eta_is + c sd_s)] (Phi(-c) < min(p_lo, 1 - p_hi) / 2) down to 2^-40 of that
+ *                  bracket; the midpoint is returned.  The Rao-Blackwellised counterpart of the PIT: no sort, and NOT loo's weighted sample
+ *                  quantile (.wquant).
+ * Every output is nullable (with only lpd / elpd_loo / pareto_k the call still runs the weights kernel).  A row with a non-finite l gets NaN in
+ * every output but lpd (as bnr_chains_loo computes it) and pareto_k (+inf).  p_lo, p_hi are read only when a bound is requested:
+ * BNR_ERR_BAD_ARG unless 0 < p_lo < p_hi < 1.  Otherwise the checks of bnr_chains_loo / bnr_chain_loo, the tail limit included: a tail entry
+ * is 12 bytes in LDS here (16 there), so the longest tail stays BNR_PSIS_MAX_TAIL (8192) and nothing more is refused.  Rows are processed in
+ * blocks of about 512 MiB of eta with the log weights beside them ("predict_block_rows" overrides); no result depends on the block, the grid
+ * or the call, bit for bit.  Nothing of any chain is written: tables, iteration counters, RNG and counters stay untouched.
+ * bnr_psis_weights: the companion of bnr_psis_loo for a caller's m x nsamp log-likelihood matrix (host, row-major): log_weights[m x nsamp]
+ *   (row-major, required) = log w_is; elpd_loo[m], pareto_k[m] nullable.  DESIGN.md section 8. */
+int bnr_chain_loo_predict(bnr_chain *chain, int32_t first_row, int32_t nsamp, const double *r_eff, double p_lo, double p_hi, double *lpd,
+                          double *elpd_loo, double *pareto_k, double *loo_mean, double *loo_sd, double *loo_pit, double *loo_lower,
+                          double *loo_upper);
+int bnr_chains_loo_predict(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, const double *r_eff, double p_lo,
+                           double p_hi, double *lpd, double *elpd_loo, double *pareto_k, double *loo_mean, double *loo_sd, double *loo_pit,
+                           double *loo_lower, double *loo_upper);
+int bnr_psis_weights(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *log_weights, double *elpd_loo,
+                     double *pareto_k);
 
 /* Effective sample size -- an ADDITION to the reference (which only has split-Rhat; north-star item "Rhat/ESS check").
  * bnr_chain_ess_stats: this chain's message over rows first_row .. first_row+nsamp-1: for both halves of the window (the

@@ -283,8 +283,12 @@ function pooled_loglik_stats(chains::Vector{Chain}, nburn, nsamp)
     lpd, pw, pit
 end
 
-# PSIS-LOO of the training rows over the pooled window (the tail length comes from the pooled draw count): (lpd, elpd_loo, pareto_k)
-function pooled_loo_stats(chains::Vector{Chain}, nburn, nsamp; r_eff=nothing)
+# PSIS-LOO of the training rows over the pooled window (the tail length comes from the pooled draw count): (lpd, elpd_loo, pareto_k).
+# NOTE: loo_predict=true CHANGES THE RETURN TYPE -- the call then returns pooled_loo_predict_stats's NamedTuple of 8 vectors (lpd, elpd_loo,
+# pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper; `interval` sets the two bounds) instead of the 3-tuple.  Code that wants one
+# type calls pooled_loo_predict_stats directly; the keyword is the switch that mirrors Fit(..., loo_predict=True) of the Python layer.
+function pooled_loo_stats(chains::Vector{Chain}, nburn, nsamp; r_eff=nothing, loo_predict=false, interval=95)
+    loo_predict && return pooled_loo_predict_stats(chains, nburn, nsamp; r_eff, interval)
     n = chains[1].n
     hs = Ptr{Cvoid}[c.h for c in chains]
     rv = r_eff === nothing ? Float64[] : (r_eff isa Number ? fill(Float64(r_eff), n) : Vector{Float64}(r_eff))
@@ -294,6 +298,56 @@ function pooled_loo_stats(chains::Vector{Chain}, nburn, nsamp; r_eff=nothing)
     GC.@preserve hs rv check(ccall((:bnr_chains_loo, LIB), Cint, (Ptr{Ptr{Cvoid}}, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
         hs, length(hs), nburn + 1, nsamp, rp, lpd, elpd, k))
     lpd, elpd, k
+end
+
+# ---- LOO predictive checks (bnr_chain(s)_loo_predict, bnr_psis_weights; additions to the reference): the leave-one-out posterior predictive
+# of every training row from the PSIS weights w over the pooled window -- loo_mean = sum w eta, loo_sd = the sd of a new observation,
+# loo_pit = sum w Phi((y - eta) / sqrt(tau2)), loo_lower / loo_upper = the (1 - interval/100)/2 and 1 - (1 - interval/100)/2 quantiles of the
+# mixture CDF (a bracketed root search on the device; not a weighted sample quantile) -- with lpd, elpd_loo and pareto_k of the same call.
+function loo_r_eff(r_eff, n)
+    rv = r_eff === nothing ? Float64[] : (r_eff isa Number ? fill(Float64(r_eff), n) : Vector{Float64}(r_eff))
+    r_eff === nothing || length(rv) == n || throw(ArgumentError("r_eff must be a number or have one entry per row"))
+    rv
+end
+function loo_probs(interval)
+    p_lo = (1 - interval / 100) / 2
+    0 < p_lo < 1 - p_lo < 1 || throw(ArgumentError("interval must be between 0 and 100"))
+    p_lo, 1 - p_lo
+end
+function pooled_loo_predict_stats(chains::Vector{Chain}, nburn, nsamp; r_eff=nothing, interval=95)
+    n = chains[1].n
+    hs = Ptr{Cvoid}[c.h for c in chains]
+    rv = loo_r_eff(r_eff, n)
+    rp = r_eff === nothing ? Ptr{Cdouble}(C_NULL) : pointer(rv)
+    p_lo, p_hi = loo_probs(interval)
+    lpd, elpd, k, m, sd, pit, lo, hi = (zeros(n) for _ in 1:8)
+    GC.@preserve hs rv check(ccall((:bnr_chains_loo_predict, LIB), Cint,
+        (Ptr{Ptr{Cvoid}}, Int32, Int32, Int32, Ptr{Cdouble}, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        hs, length(hs), nburn + 1, nsamp, rp, p_lo, p_hi, lpd, elpd, k, m, sd, pit, lo, hi))
+    (lpd = lpd, elpd_loo = elpd, pareto_k = k, loo_mean = m, loo_sd = sd, loo_pit = pit, loo_lower = lo, loo_upper = hi)
+end
+function loo_predict_stats(ch::Chain, nburn, nsamp; r_eff=nothing, interval=95)
+    n = ch.n
+    rv = loo_r_eff(r_eff, n)
+    rp = r_eff === nothing ? Ptr{Cdouble}(C_NULL) : pointer(rv)
+    p_lo, p_hi = loo_probs(interval)
+    lpd, elpd, k, m, sd, pit, lo, hi = (zeros(n) for _ in 1:8)
+    GC.@preserve rv check(ccall((:bnr_chain_loo_predict, LIB), Cint,
+        (Ptr{Cvoid}, Int32, Int32, Ptr{Cdouble}, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        ch.h, nburn + 1, nsamp, rp, p_lo, p_hi, lpd, elpd, k, m, sd, pit, lo, hi))
+    (lpd = lpd, elpd_loo = elpd, pareto_k = k, loo_mean = m, loo_sd = sd, loo_pit = pit, loo_lower = lo, loo_upper = hi)
+end
+# the normalised PSIS log weights of an m x S log-likelihood matrix (rows x draws): (log_weights m x S, elpd_loo, pareto_k).  The library
+# takes and returns row-major matrices: the transposes of Julia's
+function psis_weights(loglik::AbstractMatrix; r_eff=nothing, device=0)
+    m, S = size(loglik)
+    lt = Matrix{Float64}(transpose(loglik))                                      # S x m column-major = m x S row-major
+    rv = loo_r_eff(r_eff, m)
+    rp = r_eff === nothing ? Ptr{Cdouble}(C_NULL) : pointer(rv)
+    lw, elpd, k = zeros(S, m), zeros(m), zeros(m)
+    GC.@preserve rv check(ccall((:bnr_psis_weights, LIB), Cint, (Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        device, m, S, lt, rp, lw, elpd, k))
+    Matrix(transpose(lw)), elpd, k
 end
 
 # the noise of the predictive draws as the device draws it (host code, no GPU): ns x ni, element [s - s0 + 1, i - i0 + 1]
