@@ -11,6 +11,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -150,55 +151,50 @@ struct bnr_exec;
 static int late_kernels_lds_attributes(int bytes);
 static void launch_late_xpass_group2(bnr_exec &x, int s);
 static void launch_late_backproj64(bnr_exec &x, int s, int flags, size_t lds64);
-// device temporaries of one call, freed on every path (zeroed on the chain's stream, see dev_alloc)
+// device temporaries of one call, freed on every path (zeroed on the chain's stream, see dev_alloc; zero = false: a staging buffer that is
+// written whole before it is read)
 struct dev_tmp {
     std::vector<void *> p;
     ~dev_tmp() { for (void *q : p) (void)hipFree(q); }
     template <typename T>
-    int alloc(T **out, size_t count, hipStream_t st)
+    int alloc(T **out, size_t count, hipStream_t st, bool zero = true)
     {
         void *q = nullptr;
         HIPCHK(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
         p.push_back(q);
-        HIPCHK(hipMemsetAsync(q, 0, std::max<size_t>(count, 1) * sizeof(T), st));
+        if (zero) HIPCHK(hipMemsetAsync(q, 0, std::max<size_t>(count, 1) * sizeof(T), st));
         *out = (T *)q;
         return BNR_OK;
     }
 };
-// PSIS-LOO outputs of a predict_rows call (k_psis behind k_predict on every block): per-row tail lengths on the device, k_psis's dynamic LDS
-struct psis_out {
-    const int *tail_len;
-    int lds;
-    double *lpd, *elpd, *khat;
+// What a predict_rows call computes from a block's E behind k_predict, in the order of its launches; every pointer is a device pointer, and a
+// NULL one skips its stage
+struct pred_stages {
+    int k_lo = 0, k_hi = 0;                                        // k_summary: mean and the k_lo-th / k_hi-th smallest of every E column
+    double *mean = nullptr, *lower = nullptr, *upper = nullptr;
+    double *lpd = nullptr, *pwaic = nullptr;                       // k_pred_loglik (needs yd)
+    // PSIS (needs yd): the per-row tail lengths, the kernel's dynamic LDS, its outputs (never NULL).  keep_weights = false: k_psis, which
+    // overwrites E; true: k_psis_w and on its weights the LOO predictive checks (ABI 11): k_loo_moments (all three or none) and k_loo_quantile
+    // (each bound nullable) with its probabilities and the bracket's c (Phi(-c) < min(p_lo, 1 - p_hi) / 2)
+    const int *tail_len = nullptr;
+    int lds = 0;
+    bool keep_weights = false;
+    double *psis_lpd = nullptr, *elpd = nullptr, *khat = nullptr;
+    double *loo_mean = nullptr, *loo_sd = nullptr, *loo_pit = nullptr, *loo_lower = nullptr, *loo_upper = nullptr;
+    double p_lo = 0.0, p_hi = 0.0, c = 0.0;
+    double *pit = nullptr;                                         // k_pred_pit: the PIT of the observed responses (needs yd)
+    unsigned long long seed = 0;                                   // k_pred_noise with `seed`, then a second k_summary: the k_lo-th / k_hi-th
+    double *pred_lower = nullptr, *pred_upper = nullptr;           // smallest draw of a new observation (both or none; overwrites E)
 };
-// the extras of the pooled entry points (all device pointers, each nullable): the PIT of the observed responses, and the k_lo-th / k_hi-th smallest
-// draw of a new observation (k_pred_noise with `seed`, then a second k_summary)
-struct pred_extra {
-    unsigned long long seed;
-    double *plo, *phi, *pit;
-};
-// the LOO predictive checks of a predict_rows call (ABI 11: k_psis_w, k_loo_moments, k_loo_quantile behind k_predict on every block; all device
-// pointers): the outputs of k_psis_w (never NULL), the moments (all three or none), the bounds (each nullable) with their probabilities and the
-// bracket's c (Phi(-c) < min(p_lo, 1 - p_hi) / 2)
-struct loow_out {
-    const int *tail_len;
-    int lds;
-    double *lpd, *elpd, *khat;
-    double *mean, *sd, *pit;
-    double *lower, *upper;
-    double p_lo, p_hi, c;
-};
-static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, int k_lo, int k_hi,
-                        double *mean_d, double *lo_d, double *hi_d, double *lpd_d, double *pwaic_d, dev_tmp &tmp, const psis_out *ps = nullptr,
-                        const pred_extra *ex = nullptr, const loow_out *lw = nullptr);
+static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, const pred_stages &sg,
+                        dev_tmp &tmp);
 // (defined at the very end of this file, behind every other kernel reference: see ensure_lds_attributes)
 static int loow_lds_attributes();
 static void launch_loow_inv_sd(hipStream_t st, const double *tau2, int S, double *isd);
-static void launch_loow_block(hipStream_t st, const loow_out &lw, const double *E, double *LW, int S, int mr, int i0, const double *yd, const double *tau2,
+static void launch_loow_block(hipStream_t st, const pred_stages &sg, const double *E, double *LW, int S, int mr, int i0, const double *yd, const double *tau2,
                               const double *isd);
-static int psis_weights_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *log_weights, double *elpd,
-                               double *khat);
-static int psis_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *elpd, double *khat, double *lpd);
+static int psis_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *log_weights, double *lpd, double *elpd,
+                       double *khat);
 static int ensure_lds_attributes(int device)
 {
     static std::mutex mu;
@@ -224,6 +220,26 @@ static int exec_init(bnr_exec &x, int device, int nb, const bnr_dev *shape);
 static int check_launch(const char *what);
 static void exec_free(bnr_exec &x);
 static int sync_dev(bnr_chain *c);
+// The results of one call: k columns of m doubles on the device (zeroed), brought to the host in one copy.  fetch: the copy and the sync on st
+// (a failure is reported as "<call>: ..."), the launch check under the kernel's name, then column j into dst[j] where that is not NULL
+struct result_slab {
+    double *d = nullptr;
+    size_t m = 0;
+    int k = 0;
+    int alloc(dev_tmp &tmp, int cols, size_t rows, hipStream_t st) { k = cols; m = rows; return tmp.alloc(&d, (size_t)k * m, st); }
+    double *col(int j) const { return d + (size_t)j * m; }
+    int fetch(hipStream_t st, const char *call, const char *kernel, std::initializer_list<double *> dst) const
+    {
+        std::vector<double> host((size_t)k * m);
+        hipError_t e = hipMemcpyAsync(host.data(), d, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string(call) + ": " + hipGetErrorString(e));
+        if (int rc = check_launch(kernel)) return rc;
+        size_t j = 0;
+        for (double *p : dst) { if (p) memcpy(p, host.data() + j * m, sizeof(double) * m); ++j; }
+        return BNR_OK;
+    }
+};
 
 int bnr_abi_version(void) { return BNR_ABI_VERSION; }
 const char *bnr_last_error(void) { return g_err.c_str(); }
@@ -286,6 +302,24 @@ struct x_source {
     int dtype = BNR_F64;
 };
 static size_t dtype_size(int t) { return t == BNR_U8 ? 1 : (t == BNR_I32 || t == BNR_F32) ? 4 : 8; }
+// k_x_convert on `rows` rows of raw (on the device, host layout, element type dtype; mats: V x V matrices) into the f64 matrix Xd of leading
+// dimension ld; an integer type also fills the byte image X8 (nullable), not_bytes (nullable) is raised by an entry that is no byte
+extern "C++" template <typename T>
+static void launch_x_convert_as(const void *raw, bool mats, int rows, const bnr_dev &d, int ld, double *Xd, unsigned char *X8, int *not_bytes, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_x_convert<T>, dim3((rows + 63) / 64, std::min(d.q, 65535)), dim3(64), 0, st, (const T *)raw, mats, rows, d.V, d.q, ld, d.ek, d.el, Xd, X8,
+                       not_bytes);
+}
+static void launch_x_convert(int dtype, const void *raw, bool mats, int rows, const bnr_dev &d, int ld, double *Xd, unsigned char *X8, int *not_bytes, hipStream_t st)
+{
+    switch (dtype) {
+    case BNR_U8:  launch_x_convert_as<uint8_t>(raw, mats, rows, d, ld, Xd, X8, not_bytes, st); break;
+    case BNR_I32: launch_x_convert_as<int32_t>(raw, mats, rows, d, ld, Xd, X8, not_bytes, st); break;
+    case BNR_I64: launch_x_convert_as<int64_t>(raw, mats, rows, d, ld, Xd, X8, not_bytes, st); break;
+    case BNR_F32: launch_x_convert_as<float>(raw, mats, rows, d, ld, Xd, nullptr, not_bytes, st); break;
+    default:      launch_x_convert_as<double>(raw, mats, rows, d, ld, Xd, nullptr, not_bytes, st); break;
+    }
+}
 // raw (host layout, any element type) -> the padded f64 device matrix; the conversion runs on the device
 static int upload_x(bnr_chain *c, const x_source &src, double *Xd, unsigned char *X8, int *not_bytes_dev)
 {
@@ -306,14 +340,7 @@ static int upload_x(bnr_chain *c, const x_source &src, double *Xd, unsigned char
         }
     } else e = hipMemcpyAsync(raw, src.X, count * es, hipMemcpyHostToDevice, c->x.stream);
     if (e == hipSuccess) {
-        const dim3 grid((d.n + 63) / 64, std::min(d.q, 65535)), block(64);
-        switch (src.dtype) {
-        case BNR_U8:  hipLaunchKernelGGL(k_x_convert<uint8_t>, grid, block, 0, c->x.stream, (const uint8_t *)raw, src.mats != nullptr, d.n, d.V, d.q, d.n_pad, d.ek, d.el, Xd, X8, not_bytes_dev); break;
-        case BNR_I32: hipLaunchKernelGGL(k_x_convert<int32_t>, grid, block, 0, c->x.stream, (const int32_t *)raw, src.mats != nullptr, d.n, d.V, d.q, d.n_pad, d.ek, d.el, Xd, X8, not_bytes_dev); break;
-        case BNR_I64: hipLaunchKernelGGL(k_x_convert<int64_t>, grid, block, 0, c->x.stream, (const int64_t *)raw, src.mats != nullptr, d.n, d.V, d.q, d.n_pad, d.ek, d.el, Xd, X8, not_bytes_dev); break;
-        case BNR_F32: hipLaunchKernelGGL(k_x_convert<float>, grid, block, 0, c->x.stream, (const float *)raw, src.mats != nullptr, d.n, d.V, d.q, d.n_pad, d.ek, d.el, Xd, (unsigned char *)nullptr, not_bytes_dev); break;
-        default:      hipLaunchKernelGGL(k_x_convert<double>, grid, block, 0, c->x.stream, (const double *)raw, src.mats != nullptr, d.n, d.V, d.q, d.n_pad, d.ek, d.el, Xd, (unsigned char *)nullptr, not_bytes_dev); break;
-        }
+        launch_x_convert(src.dtype, raw, src.mats != nullptr, d.n, d, d.n_pad, Xd, X8, not_bytes_dev, c->x.stream);
         e = hipStreamSynchronize(c->x.stream);
     }
     (void)hipFree(raw);
@@ -2108,8 +2135,15 @@ int bnr_rhat(bnr_chain *const *chains, int32_t nchains_local, int32_t nchains_to
     return BNR_OK;
 }
 
-// The chains of a pooled call (bnr_chains_*): one device, equal n, V, R, none listed twice, none with a pending asynchronous run, the window
-// inside every table, the pooled draw count within int32
+// The state and row window of the chains of an analysis call: none with a pending asynchronous run, the window inside every table
+static int window_check(bnr_chain *const *cs, int nc, int first_row, int nsamp)
+{
+    for (int i = 0; i < nc; ++i) if (cs[i]->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+    for (int i = 0; i < nc; ++i)
+        if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > cs[i]->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    return BNR_OK;
+}
+// The chains of a pooled call (bnr_chains_*): one device, equal n, V, R, none listed twice, window_check, the pooled draw count within int32
 static int pooled_check(bnr_chain *const *cs, int nc, int first_row, int nsamp)
 {
     if (!cs) return fail(BNR_ERR_BAD_ARG, "NULL argument");
@@ -2121,9 +2155,7 @@ static int pooled_check(bnr_chain *const *cs, int nc, int first_row, int nsamp)
         if (cs[i]->device != cs[0]->device || a.n != b.n || a.V != b.V || a.R != b.R)
             return fail(BNR_ERR_BAD_ARG, "pooled chains must live on one device and have equal n, V, R");
     }
-    for (int i = 0; i < nc; ++i) if (cs[i]->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
-    for (int i = 0; i < nc; ++i)
-        if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > cs[i]->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    if (int rc = window_check(cs, nc, first_row, nsamp)) return rc;
     if ((long long)nc * nsamp > 0x7FFFFFFFll) return fail(BNR_ERR_BAD_ARG, "more than 2^31 - 1 pooled draws");
     return BNR_OK;
 }
@@ -2152,15 +2184,18 @@ static int summary_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t
     if (k_lo < 1 || k_lo > S || k_hi < 1 || k_hi > S)
         return fail(BNR_ERR_BAD_ARG, nc == 1 ? "order statistics must be between 1 and nsamp" : "order statistics must be between 1 and nchains * nsamp");
     HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->x.stream;
     int rc;
     if ((rc = pooled_quiesce(cs, nc))) return rc;
     const int np = d.q + d.V;
     const size_t budget = (size_t)1 << 30;
     long long blk = c->summary_block_cols > 0 ? c->summary_block_cols : (long long)(budget / ((size_t)S * sizeof(double)));
     blk = std::min<long long>(std::max<long long>(blk, 1), np);
-    double *buf = nullptr, *out = nullptr;
-    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (size_t)blk * (size_t)S));
-    if (hipMalloc((void **)&out, sizeof(double) * 3 * (size_t)np) != hipSuccess) { (void)hipFree(buf); return fail(BNR_ERR_HIP, "hipMalloc failed"); }
+    dev_tmp tmp;
+    double *buf = nullptr;
+    result_slab out;                                    // the mean, the lower and the upper statistic of the np = q + V parameters, gamma first
+    if ((rc = tmp.alloc(&buf, (size_t)blk * (size_t)S, st, false))) return rc;
+    if ((rc = out.alloc(tmp, 3, (size_t)np, st))) return rc;
     const dim3 block(32, 8);
     for (int p0 = 0; p0 < np; p0 += (int)blk) {
         const int pc = std::min<int>((int)blk, np - p0);
@@ -2170,32 +2205,28 @@ static int summary_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t
             const bnr_dev &dk = cs[k]->d;
             double *dst = buf + (size_t)k * nsamp;
             if (g1 > g0)
-                hipLaunchKernelGGL(k_fetch_cols, dim3((g1 - g0 + 31) / 32, (nsamp + 31) / 32), block, 0, c->x.stream, (const double *)dk.trace, dk.rowlen,
+                hipLaunchKernelGGL(k_fetch_cols, dim3((g1 - g0 + 31) / 32, (nsamp + 31) / 32), block, 0, st, (const double *)dk.trace, dk.rowlen,
                                    dk.o_gamma + g0, g1 - g0, first_row - 1, nsamp, dst, S);
             if (x1 > x0)
-                hipLaunchKernelGGL(k_fetch_cols, dim3((x1 - x0 + 31) / 32, (nsamp + 31) / 32), block, 0, c->x.stream, (const double *)dk.trace, dk.rowlen,
+                hipLaunchKernelGGL(k_fetch_cols, dim3((x1 - x0 + 31) / 32, (nsamp + 31) / 32), block, 0, st, (const double *)dk.trace, dk.rowlen,
                                    dk.o_xi + x0, x1 - x0, first_row - 1, nsamp, dst + (size_t)(g1 - g0) * (size_t)S, S);
         }
-        hipLaunchKernelGGL(k_summary, dim3(pc), dim3(256), 0, c->x.stream, (const double *)buf, (int)S, g1 - g0, k_lo, k_hi, out + p0, out + np + p0,
-                           out + 2 * (size_t)np + p0);
+        hipLaunchKernelGGL(k_summary, dim3(pc), dim3(256), 0, st, (const double *)buf, (int)S, g1 - g0, k_lo, k_hi, out.col(0) + p0, out.col(1) + p0,
+                           out.col(2) + p0);
     }
-    std::vector<double> host(3 * (size_t)np);
-    hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, c->x.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->x.stream);
-    (void)hipFree(buf); (void)hipFree(out);
-    if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("summary: ") + hipGetErrorString(e));
+    std::vector<double> host(3 * (size_t)np);           // (the callers' arrays hold q and V entries, not q + V)
+    if ((rc = out.fetch(st, "summary", "k_summary", {host.data(), host.data() + np, host.data() + 2 * (size_t)np}))) return rc;
     memcpy(mean_gamma, host.data(), sizeof(double) * d.q);
     memcpy(prob_xi, host.data() + d.q, sizeof(double) * d.V);
     memcpy(lower, host.data() + np, sizeof(double) * d.q);
     memcpy(upper, host.data() + 2 * (size_t)np, sizeof(double) * d.q);
-    return check_launch("k_summary");
+    return BNR_OK;
 }
 int bnr_chain_summary(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
                       double *mean_gamma, double *lower, double *upper, double *prob_xi)
 {
     if (!c || !mean_gamma || !lower || !upper || !prob_xi) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
-    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > c->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
     return summary_call(&c, 1, first_row, nsamp, k_lo, k_hi, mean_gamma, lower, upper, prob_xi);
 }
 int bnr_chains_summary(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
@@ -2216,20 +2247,19 @@ int bnr_chain_ess_stats(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t 
     if (first_row < 1 || nsamp < 8 || first_row + nsamp - 1 > d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table or nsamp < 8");
     if (max_lag < 2 || max_lag > nsamp / 2) return fail(BNR_ERR_BAD_ARG, "need 2 <= max_lag <= nsamp/2");
     HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->x.stream;
     const int np = d.q + d.V;
-    const size_t width = (size_t)2 * (2 + max_lag) * np;
-    double *buf = nullptr, *out = nullptr;
-    HIPCHK(hipMalloc((void **)&buf, sizeof(double) * (size_t)np * nsamp));
-    if (hipMalloc((void **)&out, sizeof(double) * width) != hipSuccess) { (void)hipFree(buf); return fail(BNR_ERR_HIP, "hipMalloc failed"); }
+    dev_tmp tmp;
+    double *buf = nullptr;
+    result_slab out;
+    int rc;
+    if ((rc = tmp.alloc(&buf, (size_t)np * nsamp, st, false))) return rc;
+    if ((rc = out.alloc(tmp, 1, (size_t)2 * (2 + max_lag) * np, st))) return rc;
     dim3 block(32, 8);
-    hipLaunchKernelGGL(k_fetch_cols, dim3((d.q + 31) / 32, (nsamp + 31) / 32), block, 0, c->x.stream, (const double *)d.trace, d.rowlen, d.o_gamma, d.q, first_row - 1, nsamp, buf, (long long)nsamp);
-    hipLaunchKernelGGL(k_fetch_cols, dim3((d.V + 31) / 32, (nsamp + 31) / 32), block, 0, c->x.stream, (const double *)d.trace, d.rowlen, d.o_xi, d.V, first_row - 1, nsamp, buf + (size_t)d.q * nsamp, (long long)nsamp);
-    hipLaunchKernelGGL(k_acov, dim3(np, 2), dim3(256), 0, c->x.stream, (const double *)buf, nsamp, np, max_lag, out);
-    hipError_t e = hipMemcpyAsync(stats, out, sizeof(double) * width, hipMemcpyDeviceToHost, c->x.stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(c->x.stream);
-    (void)hipFree(buf); (void)hipFree(out);
-    if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("ess_stats: ") + hipGetErrorString(e));
-    return check_launch("k_acov");
+    hipLaunchKernelGGL(k_fetch_cols, dim3((d.q + 31) / 32, (nsamp + 31) / 32), block, 0, st, (const double *)d.trace, d.rowlen, d.o_gamma, d.q, first_row - 1, nsamp, buf, (long long)nsamp);
+    hipLaunchKernelGGL(k_fetch_cols, dim3((d.V + 31) / 32, (nsamp + 31) / 32), block, 0, st, (const double *)d.trace, d.rowlen, d.o_xi, d.V, first_row - 1, nsamp, buf + (size_t)d.q * nsamp, (long long)nsamp);
+    hipLaunchKernelGGL(k_acov, dim3(np, 2), dim3(256), 0, st, (const double *)buf, nsamp, np, max_lag, out.d);
+    return out.fetch(st, "ess_stats", "k_acov", {stats});
 }
 
 // Posterior of the mean response mu + x . gamma of m new rows over rows first_row .. first_row+nsamp-1 of the chains listed (an addition to the
@@ -2251,12 +2281,12 @@ static int predict_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t
     hipStream_t st = c->x.stream;
     const int m_pad = round_up(m, 32), q16 = round_up(d.q, 16);
     dev_tmp tmp;
-    double *Xd = nullptr, *yd = nullptr, *out = nullptr;
+    double *Xd = nullptr, *yd = nullptr;
+    result_slab out;
     int rc;
     if ((rc = pooled_quiesce(cs, nc))) return rc;
     if ((rc = tmp.alloc(&Xd, (size_t)m_pad * q16, st))) return rc;             // zero rows m .. m_pad - 1 and columns q .. q16 - 1 (k_predict)
-    const bool extras = pred_lower || pit;
-    if ((rc = tmp.alloc(&out, (size_t)(extras ? 8 : 5) * m, st))) return rc;
+    if ((rc = out.alloc(tmp, pred_lower || pit ? 8 : 5, (size_t)m, st))) return rc;
     const size_t es = dtype_size(xs.dtype);
     if (!xs.mats && xs.dtype == BNR_F64) {
         HIPCHK(hipMemcpy2DAsync(Xd, (size_t)m_pad * sizeof(double), xs.X, (size_t)m * sizeof(double), (size_t)m * sizeof(double), d.q, hipMemcpyHostToDevice, st));
@@ -2267,50 +2297,27 @@ static int predict_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t
         if (xs.mats) {
             for (int i = 0; i < m; ++i) HIPCHK(hipMemcpyAsync(raw + (size_t)i * d.V * d.V * es, xs.mats[i], (size_t)d.V * d.V * es, hipMemcpyHostToDevice, st));
         } else HIPCHK(hipMemcpyAsync(raw, xs.X, count * es, hipMemcpyHostToDevice, st));
-        const dim3 grid((m + 63) / 64, std::min(d.q, 65535)), block(64);
-        const bool fm = xs.mats != nullptr;
-        switch (xs.dtype) {
-        case BNR_U8:  hipLaunchKernelGGL(k_x_convert<uint8_t>, grid, block, 0, st, (const uint8_t *)raw, fm, m, d.V, d.q, m_pad, d.ek, d.el, Xd, (unsigned char *)nullptr, (int *)nullptr); break;
-        case BNR_I32: hipLaunchKernelGGL(k_x_convert<int32_t>, grid, block, 0, st, (const int32_t *)raw, fm, m, d.V, d.q, m_pad, d.ek, d.el, Xd, (unsigned char *)nullptr, (int *)nullptr); break;
-        case BNR_I64: hipLaunchKernelGGL(k_x_convert<int64_t>, grid, block, 0, st, (const int64_t *)raw, fm, m, d.V, d.q, m_pad, d.ek, d.el, Xd, (unsigned char *)nullptr, (int *)nullptr); break;
-        case BNR_F32: hipLaunchKernelGGL(k_x_convert<float>, grid, block, 0, st, (const float *)raw, fm, m, d.V, d.q, m_pad, d.ek, d.el, Xd, (unsigned char *)nullptr, (int *)nullptr); break;
-        default:      hipLaunchKernelGGL(k_x_convert<double>, grid, block, 0, st, (const double *)raw, fm, m, d.V, d.q, m_pad, d.ek, d.el, Xd, (unsigned char *)nullptr, (int *)nullptr); break;
-        }
+        launch_x_convert(xs.dtype, raw, xs.mats != nullptr, m, d, m_pad, Xd, nullptr, nullptr, st);
     }
     if (y) {
         if ((rc = tmp.alloc(&yd, (size_t)m, st))) return rc;
         HIPCHK(hipMemcpyAsync(yd, y, sizeof(double) * m, hipMemcpyHostToDevice, st));
     }
-    const pred_extra ex{(unsigned long long)pred_seed, pred_lower ? out + 5 * (size_t)m : nullptr, pred_lower ? out + 6 * (size_t)m : nullptr,
-                        pit ? out + 7 * (size_t)m : nullptr};
-    if ((rc = predict_rows(cs, nc, first_row, nsamp, m, Xd, m_pad, yd, k_lo, k_hi, out, out + m, out + 2 * (size_t)m, y ? out + 3 * (size_t)m : nullptr,
-                           y ? out + 4 * (size_t)m : nullptr, tmp, nullptr, extras ? &ex : nullptr))) return rc;
-    std::vector<double> host((size_t)(extras ? 8 : 5) * m);
-    hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("predict: ") + hipGetErrorString(e));
-    if ((rc = check_launch("k_predict"))) return rc;
-    memcpy(mean, host.data(), sizeof(double) * m);
-    memcpy(lower, host.data() + m, sizeof(double) * m);
-    memcpy(upper, host.data() + 2 * (size_t)m, sizeof(double) * m);
-    if (y) {
-        memcpy(lpd, host.data() + 3 * (size_t)m, sizeof(double) * m);
-        memcpy(pwaic, host.data() + 4 * (size_t)m, sizeof(double) * m);
-    }
-    if (pred_lower) {
-        memcpy(pred_lower, host.data() + 5 * (size_t)m, sizeof(double) * m);
-        memcpy(pred_upper, host.data() + 6 * (size_t)m, sizeof(double) * m);
-    }
-    if (pit) memcpy(pit, host.data() + 7 * (size_t)m, sizeof(double) * m);
-    return BNR_OK;
+    pred_stages sg;
+    sg.k_lo = k_lo; sg.k_hi = k_hi;
+    sg.mean = out.col(0); sg.lower = out.col(1); sg.upper = out.col(2);
+    if (y) { sg.lpd = out.col(3); sg.pwaic = out.col(4); }
+    if (pred_lower) { sg.seed = pred_seed; sg.pred_lower = out.col(5); sg.pred_upper = out.col(6); }
+    if (pit) sg.pit = out.col(7);
+    if ((rc = predict_rows(cs, nc, first_row, nsamp, m, Xd, m_pad, yd, sg, tmp))) return rc;
+    return out.fetch(st, "predict", "k_predict", {mean, lower, upper, y ? lpd : nullptr, y ? pwaic : nullptr, pred_lower, pred_lower ? pred_upper : nullptr, pit});
 }
 // the checks of the single-chain entry points, in their order
 static int predict_one(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const x_source &xs, const double *y, int32_t k_lo, int32_t k_hi,
                        double *mean, double *lower, double *upper, double *lpd, double *pwaic)
 {
     if (!c || !mean || !lower || !upper || (!xs.X && !xs.mats) || (y && (!lpd || !pwaic))) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
-    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > c->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
     return predict_call(&c, 1, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic, 0, nullptr, nullptr, nullptr);
 }
 // ... and of the pooled ones: pred_lower and pred_upper come together; lpd / pwaic and pit need y
@@ -2361,37 +2368,51 @@ void bnr_host_pred_noise(uint64_t seed, uint32_t s0, uint32_t ns, uint32_t i0, u
     for (uint32_t i = 0; i < ni; ++i)
         for (uint32_t s = 0; s < ns; ++s) out[(size_t)i * ns + s] = bnr_normal(seed, s0 + s, SITE_PRED, i0 + i, 0u);
 }
-// pointwise lpd and WAIC penalty (and, pooled entry point only, the PIT) of the chains' own training rows: X (n_pad x q_pad, zero padded) and y
-// are on the device already
+// The calls on the chains' own training rows: X (n_pad x q_pad, zero padded) and y are on the device already.  analysis_call holds what they
+// share: the device, the quiesce, the result slab of k columns of n doubles and -- with_tails: for PSIS -- the tail lengths on the device
+struct analysis_call {
+    dev_tmp tmp;
+    result_slab out;
+    pred_stages sg;
+    hipStream_t st = nullptr;
+    int begin(bnr_chain *const *cs, int nc, int k, const std::vector<int> *tails, int lds)
+    {
+        bnr_chain *c = cs[0];
+        HIPCHK(hipSetDevice(c->device));
+        st = c->x.stream;
+        int rc;
+        if ((rc = pooled_quiesce(cs, nc))) return rc;
+        if ((rc = out.alloc(tmp, k, (size_t)c->d.n, st))) return rc;
+        if (tails) {
+            int *tl = nullptr;
+            if ((rc = tmp.alloc(&tl, (size_t)c->d.n, st))) return rc;
+            HIPCHK(hipMemcpyAsync(tl, tails->data(), sizeof(int) * c->d.n, hipMemcpyHostToDevice, st));
+            sg.tail_len = tl; sg.lds = lds;
+            sg.psis_lpd = out.col(0); sg.elpd = out.col(1); sg.khat = out.col(2);
+        }
+        return BNR_OK;
+    }
+    int run(bnr_chain *const *cs, int nc, int first_row, int nsamp)
+    {
+        const bnr_dev &d = cs[0]->d;
+        return predict_rows(cs, nc, first_row, nsamp, d.n, d.X, d.n_pad, d.y, sg, tmp);
+    }
+};
+// pointwise lpd and WAIC penalty (and, pooled entry point only, the PIT)
 static int loglik_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic, double *pit)
 {
-    bnr_chain *c = cs[0];
-    const bnr_dev &d = c->d;
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->x.stream;
-    dev_tmp tmp;
-    double *out = nullptr;
+    analysis_call a;
     int rc;
-    if ((rc = pooled_quiesce(cs, nc))) return rc;
-    if ((rc = tmp.alloc(&out, (size_t)(pit ? 3 : 2) * d.n, st))) return rc;
-    const pred_extra ex{0ull, nullptr, nullptr, pit ? out + 2 * (size_t)d.n : nullptr};
-    if ((rc = predict_rows(cs, nc, first_row, nsamp, d.n, d.X, d.n_pad, d.y, 0, 0, nullptr, nullptr, nullptr, out, out + d.n, tmp, nullptr, pit ? &ex : nullptr)))
-        return rc;
-    std::vector<double> host((size_t)(pit ? 3 : 2) * d.n);
-    hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("loglik_stats: ") + hipGetErrorString(e));
-    if ((rc = check_launch("k_pred_loglik"))) return rc;
-    memcpy(lpd, host.data(), sizeof(double) * d.n);
-    memcpy(pwaic, host.data() + d.n, sizeof(double) * d.n);
-    if (pit) memcpy(pit, host.data() + 2 * (size_t)d.n, sizeof(double) * d.n);
-    return BNR_OK;
+    if ((rc = a.begin(cs, nc, pit ? 3 : 2, nullptr, 0))) return rc;
+    a.sg.lpd = a.out.col(0); a.sg.pwaic = a.out.col(1);
+    if (pit) a.sg.pit = a.out.col(2);
+    if ((rc = a.run(cs, nc, first_row, nsamp))) return rc;
+    return a.out.fetch(a.st, "loglik_stats", "k_pred_loglik", {lpd, pwaic, pit});
 }
 int bnr_chain_loglik_stats(bnr_chain *c, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic)
 {
     if (!c || !lpd || !pwaic) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
-    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > c->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
     return loglik_call(&c, 1, first_row, nsamp, lpd, pwaic, nullptr);
 }
 int bnr_chains_loglik_stats(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic, double *pit)
@@ -2429,37 +2450,18 @@ static int psis_tail_lengths(int m, int nsamp, const double *r_eff, std::vector<
 // of rows); the tail length comes from the pooled draw count
 static int loo_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo, double *pareto_k)
 {
-    bnr_chain *c = cs[0];
-    const bnr_dev &d = c->d;
     std::vector<int> M;
     int lds = 0, rc;
-    if ((rc = psis_tail_lengths(d.n, nc * nsamp, r_eff, M, lds))) return rc;
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->x.stream;
-    dev_tmp tmp;
-    double *out = nullptr;
-    int *tl = nullptr;
-    if ((rc = pooled_quiesce(cs, nc))) return rc;
-    if ((rc = tmp.alloc(&out, (size_t)3 * d.n, st))) return rc;
-    if ((rc = tmp.alloc(&tl, (size_t)d.n, st))) return rc;
-    HIPCHK(hipMemcpyAsync(tl, M.data(), sizeof(int) * d.n, hipMemcpyHostToDevice, st));
-    const psis_out ps{tl, lds, out, out + d.n, out + 2 * (size_t)d.n};
-    if ((rc = predict_rows(cs, nc, first_row, nsamp, d.n, d.X, d.n_pad, d.y, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, tmp, &ps))) return rc;
-    std::vector<double> host(3 * (size_t)d.n);
-    hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("loo: ") + hipGetErrorString(e));
-    if ((rc = check_launch("k_psis"))) return rc;
-    if (lpd) memcpy(lpd, host.data(), sizeof(double) * d.n);
-    memcpy(elpd_loo, host.data() + d.n, sizeof(double) * d.n);
-    memcpy(pareto_k, host.data() + 2 * (size_t)d.n, sizeof(double) * d.n);
-    return BNR_OK;
+    if ((rc = psis_tail_lengths(cs[0]->d.n, nc * nsamp, r_eff, M, lds))) return rc;
+    analysis_call a;
+    if ((rc = a.begin(cs, nc, 3, &M, lds))) return rc;
+    if ((rc = a.run(cs, nc, first_row, nsamp))) return rc;
+    return a.out.fetch(a.st, "loo", "k_psis", {lpd, elpd_loo, pareto_k});
 }
 int bnr_chain_loo(bnr_chain *c, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo, double *pareto_k)
 {
     if (!c || !elpd_loo || !pareto_k) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
-    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > c->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
     return loo_call(&c, 1, first_row, nsamp, r_eff, lpd, elpd_loo, pareto_k);
 }
 int bnr_chains_loo(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo,
@@ -2469,28 +2471,12 @@ int bnr_chains_loo(bnr_chain *const *chains, int32_t nchains, int32_t first_row,
     if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
     return loo_call(chains, nchains, first_row, nsamp, r_eff, lpd, elpd_loo, pareto_k);
 }
-// the same PSIS on a caller's m x nsamp log-likelihood matrix (host, row-major)
-int bnr_psis_loo(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *elpd_loo, double *pareto_k, double *lpd)
-{
-    if (!loglik || !elpd_loo || !pareto_k) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (m < 1 || nsamp < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows and nsamp >= 1 draws");
-    std::vector<int> M;
-    int lds = 0, rc, ndev = 0;
-    if ((rc = psis_tail_lengths(m, nsamp, r_eff, M, lds))) return rc;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
-    HIPCHK(hipSetDevice(device));
-    if ((rc = ensure_lds_attributes(device))) return rc;
-    return psis_matrix(m, nsamp, loglik, M, lds, elpd_loo, pareto_k, lpd);
-}
 
 // LOO predictive checks (ABI 11) of the chains' own training rows over the pooled window: k_predict, then k_psis_w (the PSIS weights of the block),
 // k_loo_moments and k_loo_quantile on every block of rows.  Every output is nullable; lpd, elpd_loo and pareto_k always come from k_psis_w.
 static int loo_predict_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, const double *r_eff, double p_lo, double p_hi, double *lpd,
                             double *elpd_loo, double *pareto_k, double *loo_mean, double *loo_sd, double *loo_pit, double *loo_lower, double *loo_upper)
 {
-    bnr_chain *c = cs[0];
-    const bnr_dev &d = c->d;
     const bool bounds = loo_lower || loo_upper, moments = loo_mean || loo_sd || loo_pit;
     double cc = 0.0;
     if (bounds) {
@@ -2500,37 +2486,25 @@ static int loo_predict_call(bnr_chain *const *cs, int nc, int32_t first_row, int
     }
     std::vector<int> M;
     int lds = 0, rc;
-    if ((rc = psis_tail_lengths(d.n, nc * nsamp, r_eff, M, lds, BNR_PSISW_ENTRY_BYTES))) return rc;
-    HIPCHK(hipSetDevice(c->device));
+    if ((rc = psis_tail_lengths(cs[0]->d.n, nc * nsamp, r_eff, M, lds, BNR_PSISW_ENTRY_BYTES))) return rc;
+    HIPCHK(hipSetDevice(cs[0]->device));
     if ((rc = loow_lds_attributes())) return rc;
-    hipStream_t st = c->x.stream;
-    dev_tmp tmp;
-    double *out = nullptr;
-    int *tl = nullptr;
-    const size_t n = (size_t)d.n;
-    if ((rc = pooled_quiesce(cs, nc))) return rc;
-    if ((rc = tmp.alloc(&out, 8 * n, st))) return rc;
-    if ((rc = tmp.alloc(&tl, n, st))) return rc;
-    HIPCHK(hipMemcpyAsync(tl, M.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
-    const loow_out lw{tl, lds, out, out + n, out + 2 * n, moments ? out + 3 * n : nullptr, moments ? out + 4 * n : nullptr, moments ? out + 5 * n : nullptr,
-                      loo_lower ? out + 6 * n : nullptr, loo_upper ? out + 7 * n : nullptr, p_lo, p_hi, cc};
-    if ((rc = predict_rows(cs, nc, first_row, nsamp, d.n, d.X, d.n_pad, d.y, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, tmp, nullptr, nullptr, &lw)))
-        return rc;
-    std::vector<double> host(8 * n);
-    hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("loo_predict: ") + hipGetErrorString(e));
-    if ((rc = check_launch("k_psis_w"))) return rc;
-    double *dst[8] = {lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper};
-    for (int k = 0; k < 8; ++k) if (dst[k]) memcpy(dst[k], host.data() + k * n, sizeof(double) * n);
-    return BNR_OK;
+    analysis_call a;
+    if ((rc = a.begin(cs, nc, 8, &M, lds))) return rc;
+    pred_stages &sg = a.sg;
+    sg.keep_weights = true;
+    if (moments) { sg.loo_mean = a.out.col(3); sg.loo_sd = a.out.col(4); sg.loo_pit = a.out.col(5); }
+    if (loo_lower) sg.loo_lower = a.out.col(6);
+    if (loo_upper) sg.loo_upper = a.out.col(7);
+    sg.p_lo = p_lo; sg.p_hi = p_hi; sg.c = cc;
+    if ((rc = a.run(cs, nc, first_row, nsamp))) return rc;
+    return a.out.fetch(a.st, "loo_predict", "k_psis_w", {lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper});
 }
 int bnr_chain_loo_predict(bnr_chain *c, int32_t first_row, int32_t nsamp, const double *r_eff, double p_lo, double p_hi, double *lpd, double *elpd_loo,
                           double *pareto_k, double *loo_mean, double *loo_sd, double *loo_pit, double *loo_lower, double *loo_upper)
 {
     if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
-    if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > c->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
     return loo_predict_call(&c, 1, first_row, nsamp, r_eff, p_lo, p_hi, lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper);
 }
 int bnr_chains_loo_predict(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, const double *r_eff, double p_lo, double p_hi,
@@ -2540,21 +2514,33 @@ int bnr_chains_loo_predict(bnr_chain *const *chains, int32_t nchains, int32_t fi
     if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
     return loo_predict_call(chains, nchains, first_row, nsamp, r_eff, p_lo, p_hi, lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper);
 }
-// the PSIS weights of a caller's m x nsamp log-likelihood matrix (host, row-major): the companion of bnr_psis_loo
-int bnr_psis_weights(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *log_weights, double *elpd_loo,
+
+// PSIS on a caller's m x nsamp log-likelihood matrix (host, row-major): bnr_psis_loo (k_psis) and its companion bnr_psis_weights, which also
+// returns the weights (k_psis_w: log_weights != NULL).  The shared front: the checks in their order, the tail lengths, the device
+static int psis_call(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *log_weights, double *lpd, double *elpd_loo,
                      double *pareto_k)
 {
-    if (!loglik || !log_weights) return fail(BNR_ERR_BAD_ARG, "NULL argument");
     if (m < 1 || nsamp < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows and nsamp >= 1 draws");
     std::vector<int> M;
     int lds = 0, rc, ndev = 0;
-    if ((rc = psis_tail_lengths(m, nsamp, r_eff, M, lds, BNR_PSISW_ENTRY_BYTES))) return rc;
+    if ((rc = psis_tail_lengths(m, nsamp, r_eff, M, lds, log_weights ? BNR_PSISW_ENTRY_BYTES : 16))) return rc;
     HIPCHK(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
     HIPCHK(hipSetDevice(device));
     if ((rc = ensure_lds_attributes(device))) return rc;
-    if ((rc = loow_lds_attributes())) return rc;
-    return psis_weights_matrix(m, nsamp, loglik, M, lds, log_weights, elpd_loo, pareto_k);
+    if (log_weights && (rc = loow_lds_attributes())) return rc;
+    return psis_matrix(m, nsamp, loglik, M, lds, log_weights, lpd, elpd_loo, pareto_k);
+}
+int bnr_psis_loo(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *elpd_loo, double *pareto_k, double *lpd)
+{
+    if (!loglik || !elpd_loo || !pareto_k) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    return psis_call(device, m, nsamp, loglik, r_eff, nullptr, lpd, elpd_loo, pareto_k);
+}
+int bnr_psis_weights(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *log_weights, double *elpd_loo,
+                     double *pareto_k)
+{
+    if (!loglik || !log_weights) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    return psis_call(device, m, nsamp, loglik, r_eff, log_weights, nullptr, elpd_loo, pareto_k);
 }
 
 // Bulk effective sample size over all chains from the gathered messages (the estimator of Vehtari et al. 2021 as in
@@ -2808,34 +2794,35 @@ static void launch_late_backproj64(bnr_exec &x, int s, int flags, size_t lds64)
 
 // The device work of the prediction, log-likelihood and LOO calls, eagerly on the first chain's stream: the m rows of X (device, column-major,
 // leading dimension ldx, zero in columns q .. q16 - 1 and readable for whole 32-row tiles) in blocks of rows whose E buffer (rows x S doubles,
-// S = nc nsamp pooled draws: chain c's window in the columns c nsamp ..) stays near 1 GiB; per block one k_predict per chain, then k_summary
-// (mean, k_lo-th / k_hi-th smallest of every E column; skipped when mean_d is NULL), k_pred_loglik (when yd and lpd_d are given), k_pred_pit
-// (ex->pit), and last what overwrites E: k_pred_noise + a second k_summary (ex->plo / phi), or k_psis.  Blocks start at multiples of 32 rows, so
-// an output's MFMA tile position and K order -- and with them every result, bit for bit -- do not depend on the block size; the noise is keyed
-// by the row's index in the call.  With one chain and no extras: the launches of the single-chain entry points, unchanged.
-static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, int k_lo, int k_hi,
-                        double *mean_d, double *lo_d, double *hi_d, double *lpd_d, double *pwaic_d, dev_tmp &tmp, const psis_out *ps, const pred_extra *ex,
-                        const loow_out *lw)
+// S = nc nsamp pooled draws: chain c's window in the columns c nsamp ..) stays near 1 GiB; per block one k_predict per chain, then the stages
+// of sg that are wanted, in this order: k_summary (mean, k_lo-th / k_hi-th smallest of every E column), k_pred_loglik, the LOO predictive
+// checks (k_psis_w and what reads its weights), k_psis, k_pred_pit, and last what overwrites E: k_pred_noise + a second k_summary (no call asks
+// for that and k_psis, which overwrites E as well).  Blocks start at multiples of 32 rows, so an output's MFMA tile position and K order -- and
+// with them every result, bit for bit -- do not depend on the block size; the noise is keyed by the row's index in the call.  With one chain
+// and no extras: the launches of the single-chain entry points, unchanged.
+static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, const pred_stages &sg,
+                        dev_tmp &tmp)
 {
     bnr_chain *c = cs[0];
     const bnr_dev &d = c->d;
     hipStream_t st = c->x.stream;
     const long long S = (long long)nc * nsamp;
-    const size_t budget = lw ? (size_t)1 << 29 : (size_t)1 << 30;          // (half the rows with the log weights beside E: E + LW stay near 1 GiB)
+    const bool loow = sg.tail_len && sg.keep_weights, psis = sg.tail_len && !sg.keep_weights;
+    const size_t budget = loow ? (size_t)1 << 29 : (size_t)1 << 30;        // (half the rows with the log weights beside E: E + LW stay near 1 GiB)
     long long blk = c->predict_block_rows > 0 ? c->predict_block_rows : (long long)(budget / ((size_t)S * sizeof(double))) / 32 * 32;
     blk = std::min<long long>(round_up((int)std::max<long long>(blk, 1), 32), round_up(m, 32));
     double *E = nullptr, *tau2 = nullptr, *pmean = nullptr, *LW = nullptr, *isd = nullptr;
     int rc;
     if ((rc = tmp.alloc(&E, (size_t)blk * (size_t)S, st))) return rc;
-    if (lw && (rc = tmp.alloc(&LW, (size_t)blk * (size_t)S, st))) return rc;
-    if (yd || ex) {
+    if (loow && (rc = tmp.alloc(&LW, (size_t)blk * (size_t)S, st))) return rc;
+    if (yd || sg.pit || sg.pred_lower) {
         if ((rc = tmp.alloc(&tau2, (size_t)S, st))) return rc;
         for (int k = 0; k < nc; ++k)
             hipLaunchKernelGGL(k_fetch_cols, dim3(1, (nsamp + 31) / 32), dim3(32, 8), 0, st, (const double *)cs[k]->d.trace, cs[k]->d.rowlen, (int)ROW_TAU2, 1,
                                first_row - 1, nsamp, tau2 + (size_t)k * nsamp, S);
     }
-    if (ex && ex->plo && (rc = tmp.alloc(&pmean, (size_t)m, st))) return rc;      // (k_summary also writes the mean of y~: not returned)
-    if (lw && (lw->lower || lw->upper)) {
+    if (sg.pred_lower && (rc = tmp.alloc(&pmean, (size_t)m, st))) return rc;      // (k_summary also writes the mean of y~: not returned)
+    if (loow && (sg.loo_lower || sg.loo_upper)) {
         if ((rc = tmp.alloc(&isd, (size_t)S, st))) return rc;
         launch_loow_inv_sd(st, tau2, (int)S, isd);
     }
@@ -2851,63 +2838,25 @@ static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, 
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<1>), dim3((nsamp + 127) / 128, 1), dim3(256), 0, st, Xd + i0, ldx, q16,
                                    (const double *)dk.trace, dk.rowlen, dk.o_gamma, first_row - 1, nsamp, mr, E + (size_t)k * nsamp, S);
         }
-        if (mean_d)
-            hipLaunchKernelGGL(k_summary, dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, mr, k_lo, k_hi, mean_d + i0, lo_d + i0, hi_d + i0);
-        if (yd && lpd_d)
+        if (sg.mean)
+            hipLaunchKernelGGL(k_summary, dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, mr, sg.k_lo, sg.k_hi, sg.mean + i0, sg.lower + i0, sg.upper + i0);
+        if (yd && sg.lpd)
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pred_loglik<0>), dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, yd + i0, (const double *)tau2,
-                               lpd_d + i0, pwaic_d + i0);
-        if (lw)                                        // the LOO predictive checks read E: before anything that overwrites it
-            launch_loow_block(st, *lw, E, LW, (int)S, mr, i0, yd, tau2, isd);
-        if (ps)                                        // last: k_psis turns the block's E into l in place
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis<1>), dim3(mr), dim3(256), ps->lds, st, E, (int)S, yd + i0, (const double *)tau2, ps->tail_len + i0,
-                               ps->lpd + i0, ps->elpd + i0, ps->khat + i0);
-        if (ex && ex->pit)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pred_pit<0>), dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, yd + i0, (const double *)tau2, ex->pit + i0);
-        if (ex && ex->plo) {                           // last: the block's E becomes draws of new observations in place
+                               sg.lpd + i0, sg.pwaic + i0);
+        if (loow)                                      // the LOO predictive checks read E: before anything that overwrites it
+            launch_loow_block(st, sg, E, LW, (int)S, mr, i0, yd, tau2, isd);
+        if (psis)                                      // last: k_psis turns the block's E into l in place
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis<1>), dim3(mr), dim3(256), sg.lds, st, E, (int)S, yd + i0, (const double *)tau2, sg.tail_len + i0,
+                               sg.psis_lpd + i0, sg.elpd + i0, sg.khat + i0);
+        if (sg.pit)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pred_pit<0>), dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, yd + i0, (const double *)tau2, sg.pit + i0);
+        if (sg.pred_lower) {                           // last: the block's E becomes draws of new observations in place
             const int gx = (int)((S + 255) / 256), gy = std::max(1, std::min(mr, 8192 / gx));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pred_noise<0>), dim3(gx, gy), dim3(256), 0, st, E, S, (int)S, mr, i0, (const double *)tau2, ex->seed);
-            hipLaunchKernelGGL(k_summary, dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, mr, k_lo, k_hi, pmean + i0, ex->plo + i0, ex->phi + i0);
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pred_noise<0>), dim3(gx, gy), dim3(256), 0, st, E, S, (int)S, mr, i0, (const double *)tau2, sg.seed);
+            hipLaunchKernelGGL(k_summary, dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, mr, sg.k_lo, sg.k_hi, pmean + i0, sg.pred_lower + i0, sg.pred_upper + i0);
         }
     }
     return check_launch("k_predict");
-}
-
-// The device work of bnr_psis_loo on its own stream: the rows of the caller's matrix in blocks of about 1 GiB, k_psis<0> on every block.
-static int psis_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *elpd, double *khat, double *lpd)
-{
-    struct stream_guard {
-        hipStream_t s = nullptr;
-        ~stream_guard() { if (s) (void)hipStreamDestroy(s); }
-    } sg;
-    HIPCHK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
-    hipStream_t st = sg.s;
-    const size_t budget = (size_t)1 << 30;
-    const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, budget / ((size_t)nsamp * sizeof(double))));
-    int rc;
-    {
-        dev_tmp tmp;
-        double *Ld = nullptr, *out = nullptr;
-        int *tl = nullptr;
-        if ((rc = tmp.alloc(&Ld, (size_t)blk * nsamp, st))) return rc;
-        if ((rc = tmp.alloc(&out, (size_t)3 * m, st))) return rc;
-        if ((rc = tmp.alloc(&tl, (size_t)m, st))) return rc;
-        HIPCHK(hipMemcpyAsync(tl, tail_len.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
-        for (int i0 = 0; i0 < m; i0 += blk) {
-            const int mr = std::min(blk, m - i0);
-            HIPCHK(hipMemcpyAsync(Ld, loglik + (size_t)i0 * nsamp, sizeof(double) * (size_t)mr * nsamp, hipMemcpyHostToDevice, st));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis<0>), dim3(mr), dim3(256), lds, st, Ld, nsamp, (const double *)nullptr, (const double *)nullptr,
-                               (const int *)tl + i0, out + i0, out + m + i0, out + 2 * (size_t)m + i0);
-        }
-        std::vector<double> host(3 * (size_t)m);
-        hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("psis_loo: ") + hipGetErrorString(e));
-        if ((rc = check_launch("k_psis"))) return rc;
-        if (lpd) memcpy(lpd, host.data(), sizeof(double) * m);
-        memcpy(elpd, host.data() + m, sizeof(double) * m);
-        memcpy(khat, host.data() + 2 * (size_t)m, sizeof(double) * m);
-    }
-    return BNR_OK;
 }
 
 // ----------------------------------------------------------------------------------------- every reference to the kernels of the LOO predictive checks (ABI 11)
@@ -2921,56 +2870,53 @@ static int loow_lds_attributes()
 static void launch_loow_inv_sd(hipStream_t st, const double *tau2, int S, double *isd)
 { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_inv_sd<0>), dim3((S + 255) / 256), dim3(256), 0, st, tau2, S, isd); }
 // a block of mr rows starting at row i0 of the call: the weights of the block into LW, then what reads them
-static void launch_loow_block(hipStream_t st, const loow_out &lw, const double *E, double *LW, int S, int mr, int i0, const double *yd, const double *tau2,
+static void launch_loow_block(hipStream_t st, const pred_stages &sg, const double *E, double *LW, int S, int mr, int i0, const double *yd, const double *tau2,
                               const double *isd)
 {
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis_w<1>), dim3(mr), dim3(256), lw.lds, st, E, S, yd + i0, tau2, lw.tail_len + i0, LW, lw.lpd + i0, lw.elpd + i0,
-                       lw.khat + i0);
-    if (lw.mean)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_loo_moments<0>), dim3(mr), dim3(256), 0, st, E, (const double *)LW, S, yd + i0, tau2, lw.mean + i0, lw.sd + i0,
-                           lw.pit + i0);
-    if (lw.lower || lw.upper)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_loo_quantile<0>), dim3(mr, 2), dim3(256), 0, st, E, (const double *)LW, S, tau2, isd, lw.c, lw.p_lo, lw.p_hi,
-                           lw.lower ? lw.lower + i0 : nullptr, lw.upper ? lw.upper + i0 : nullptr);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis_w<1>), dim3(mr), dim3(256), sg.lds, st, E, S, yd + i0, tau2, sg.tail_len + i0, LW, sg.psis_lpd + i0, sg.elpd + i0,
+                       sg.khat + i0);
+    if (sg.loo_mean)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_loo_moments<0>), dim3(mr), dim3(256), 0, st, E, (const double *)LW, S, yd + i0, tau2, sg.loo_mean + i0, sg.loo_sd + i0,
+                           sg.loo_pit + i0);
+    if (sg.loo_lower || sg.loo_upper)
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_loo_quantile<0>), dim3(mr, 2), dim3(256), 0, st, E, (const double *)LW, S, tau2, isd, sg.c, sg.p_lo, sg.p_hi,
+                           sg.loo_lower ? sg.loo_lower + i0 : nullptr, sg.loo_upper ? sg.loo_upper + i0 : nullptr);
 }
-// The device work of bnr_psis_weights on its own stream: the rows of the caller's matrix in blocks of about 512 MiB (l and the weights side by
-// side), k_psis_w<0> on every block, the block's weights copied back behind it.
-static int psis_weights_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *log_weights, double *elpd,
-                               double *khat)
+// The device work of bnr_psis_loo and bnr_psis_weights on a stream of its own: the rows of the caller's matrix in blocks, k_psis<0> on every block
+// of about 1 GiB; with log_weights k_psis_w<0> on every block of about 512 MiB (l and the weights side by side), the block's weights copied back
+// behind it (and no lpd)
+static int psis_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *log_weights, double *lpd, double *elpd,
+                       double *khat)
 {
     struct stream_guard {
         hipStream_t s = nullptr;
         ~stream_guard() { if (s) (void)hipStreamDestroy(s); }
-    } sg;
-    HIPCHK(hipStreamCreateWithFlags(&sg.s, hipStreamNonBlocking));
-    hipStream_t st = sg.s;
-    const size_t budget = (size_t)1 << 29;
+    } guard;
+    HIPCHK(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
+    hipStream_t st = guard.s;
+    const size_t budget = log_weights ? (size_t)1 << 29 : (size_t)1 << 30;
     const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, budget / ((size_t)nsamp * sizeof(double))));
     int rc;
-    {
-        dev_tmp tmp;
-        double *Ld = nullptr, *Wd = nullptr, *out = nullptr;
-        int *tl = nullptr;
-        if ((rc = tmp.alloc(&Ld, (size_t)blk * nsamp, st))) return rc;
-        if ((rc = tmp.alloc(&Wd, (size_t)blk * nsamp, st))) return rc;
-        if ((rc = tmp.alloc(&out, (size_t)2 * m, st))) return rc;
-        if ((rc = tmp.alloc(&tl, (size_t)m, st))) return rc;
-        HIPCHK(hipMemcpyAsync(tl, tail_len.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
-        for (int i0 = 0; i0 < m; i0 += blk) {
-            const int mr = std::min(blk, m - i0);
-            HIPCHK(hipMemcpyAsync(Ld, loglik + (size_t)i0 * nsamp, sizeof(double) * (size_t)mr * nsamp, hipMemcpyHostToDevice, st));
+    dev_tmp tmp;                                        // (freed before the stream goes)
+    double *Ld = nullptr, *Wd = nullptr;
+    int *tl = nullptr;
+    result_slab out;
+    if ((rc = tmp.alloc(&Ld, (size_t)blk * nsamp, st))) return rc;
+    if (log_weights && (rc = tmp.alloc(&Wd, (size_t)blk * nsamp, st))) return rc;
+    if ((rc = out.alloc(tmp, 3, (size_t)m, st))) return rc;
+    if ((rc = tmp.alloc(&tl, (size_t)m, st))) return rc;
+    HIPCHK(hipMemcpyAsync(tl, tail_len.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
+    for (int i0 = 0; i0 < m; i0 += blk) {
+        const int mr = std::min(blk, m - i0);
+        HIPCHK(hipMemcpyAsync(Ld, loglik + (size_t)i0 * nsamp, sizeof(double) * (size_t)mr * nsamp, hipMemcpyHostToDevice, st));
+        if (log_weights) {
             hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis_w<0>), dim3(mr), dim3(256), lds, st, (const double *)Ld, nsamp, (const double *)nullptr,
-                               (const double *)nullptr, (const int *)tl + i0, Wd, (double *)nullptr, out + i0, out + m + i0);
+                               (const double *)nullptr, (const int *)tl + i0, Wd, (double *)nullptr, out.col(1) + i0, out.col(2) + i0);
             HIPCHK(hipMemcpyAsync(log_weights + (size_t)i0 * nsamp, Wd, sizeof(double) * (size_t)mr * nsamp, hipMemcpyDeviceToHost, st));
-        }
-        std::vector<double> host(2 * (size_t)m);
-        hipError_t e = hipMemcpyAsync(host.data(), out, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("psis_weights: ") + hipGetErrorString(e));
-        if ((rc = check_launch("k_psis_w"))) return rc;
-        if (elpd) memcpy(elpd, host.data(), sizeof(double) * m);
-        if (khat) memcpy(khat, host.data() + m, sizeof(double) * m);
+        } else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis<0>), dim3(mr), dim3(256), lds, st, Ld, nsamp, (const double *)nullptr, (const double *)nullptr,
+                               (const int *)tl + i0, out.col(0) + i0, out.col(1) + i0, out.col(2) + i0);
     }
-    return BNR_OK;
+    return out.fetch(st, log_weights ? "psis_weights" : "psis_loo", log_weights ? "k_psis_w" : "k_psis", {lpd, elpd, khat});
 }
 }

@@ -3786,18 +3786,18 @@ __global__ __launch_bounds__(256) void k_pred_loglik(const double *E, int nsamp,
 //   elpd_i = log sum_s exp(lw_s + l_s) - log sum_s exp(lw_s)
 //   khat_i = the fitted shape after the prior adjustment; +inf when there is no fit (M < 5, a constant tail, a NaN shape).
 // A row with a non-finite l gets elpd NaN, khat +inf.
-// One workgroup of 256 threads per row (blockIdx.x); L + i nsamp holds the row's E column (FROM_E = 1: l_s = bnr_pred_ell(y_i, E_is, tau2_s),
-// written back over E) or its l row (FROM_E = 0).  The row is streamed from L2 / HBM on every pass:
-//   1  l, its max and min, finiteness;  2  sum exp(l - max) (lpd) and the first digit histogram;  3-7  the other digit histograms: exact
-//   radix select of the (M+1)-th largest order-preserving 64-bit key of lw (11-bit digits, 6 passes, integer LDS atomics: exact);
-//   8  gather: keys above the cutoff key K_c into LDS, the max l over keys equal to K_c, the per-thread log-sum-exps of the rest.
-// Ties: the tail is every key > K_c plus (M - #{key > K_c}) copies of (K_c, l_c), l_c = max l over key == K_c; the other keys == K_c enter
-// the sums as a counted multiple of (K_c, l_c).  Tied ratios have tied l, so this is the tail any sort would pick; a tie created only by the
-// rounding of r - max r moves a result by an ulp of that l.  The tail is sorted by (key, key of l) with a bitonic sort in LDS.
+// Two kernels do this, k_psis (lpd, elpd, khat) and k_psis_w (the per-draw weights as well); what they share is the bnr_psis_* pieces below,
+// one source for both, and this contract.  One workgroup of 256 threads per row (blockIdx.x); FROM_E = 1: the row comes as its E column of
+// k_predict, l_s = bnr_pred_ell(y_i, E_is, tau2_s); FROM_E = 0: as its l row.  The row is streamed from L2 / HBM on every pass:
+//   1  l, its max and min, finiteness (bnr_psis_pass1);  2  sum exp(l - max) (lpd) and the first digit histogram;  3-7  the other digit
+//   histograms: exact radix select of K_c, the (M+1)-th largest order-preserving 64-bit key of lw (11-bit digits, 6 passes, integer LDS
+//   atomics: exact; bnr_psis_cutoff);  8  gather: the tail into LDS, the per-thread log-sum-exps of the rest.
+// The tail is sorted with a bitonic sort in LDS (P entries, P = the smallest power of two >= M, the padding behind the tail), fitted
+// (bnr_psis_gpd_fit) and its M terms, smoothed or as they were (bnr_psis_tail_lw), join the log-sum-exps (bnr_psis_lse_tree).  Which draws
+// with a key equal to K_c belong to the tail, what a tail entry carries beside its key, and what is written back are each kernel's own.
 // Every sum is in a fixed order (thread-strided partial sums, then a tree; the GPD grid: lane-strided partial sums, then a fixed butterfly of
-// the wave), so results are bitwise independent of the grid and of the block of rows.  Dynamic LDS: max(8 KiB, 16 P) bytes, P = the
-// smallest power of two >= the largest M of the launch; M <= BNR_PSIS_MAX_TAIL (the host refuses longer tails).
-// Both instantiations are referenced only from the end of bnr_hip.hip, so that they sit behind the sweep kernels in the code object.
+// the wave), so results are bitwise independent of the grid, of the block of rows and of the call.  Dynamic LDS: max(8 KiB, entry bytes x P)
+// for the largest M of the launch; M <= BNR_PSIS_MAX_TAIL (the host refuses longer tails).
 #define BNR_PSIS_MAX_TAIL 8192
 #define BNR_PSIS_MAX_GRID 128          // 30 + floor(sqrt(BNR_PSIS_MAX_TAIL)) = 120 grid points
 __device__ __forceinline__ unsigned long long bnr_okey(double v)
@@ -3816,40 +3816,76 @@ __device__ __forceinline__ void bnr_lse_merge(double &m, double &s, double m2, d
     else if (m2 > m) { s = s * exp(m - m2) + s2; m = m2; }
     else if (m2 > -INFINITY) s += s2 * exp(m2 - m);
 }
-template <int FROM_E>
-__global__ __launch_bounds__(256) void k_psis(double *L, int nsamp, const double *y, const double *tau2, const int *tail_len, double *lpd,
-                                              double *elpd, double *khat)
+// the static LDS of a PSIS workgroup: four reduction arrays, the GPD grid's log-likelihoods and the broadcast scalars
+struct bnr_psis_lds {
+    double ra[256], rb[256], rc[256], rd[256], lth[BNR_PSIS_MAX_GRID];
+    double theta;
+    unsigned bin, above, cnt, pos;
+};
+// the sum / the max of v over the 256 threads in k_pred_loglik's tree, through ra; every thread gets it.  No barrier behind the last read of ra[0]
+__device__ __forceinline__ double bnr_block_sum(double *ra, int tid, double v)
 {
-    extern __shared__ unsigned long long psis_dyn[];
-    __shared__ double ra[256], rb[256], rc[256], rd[256], lth[BNR_PSIS_MAX_GRID];
-    __shared__ unsigned s_bin, s_above, s_cnt, s_pos;
-    __shared__ double s_theta;
-    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    double *l = L + (size_t)i * nsamp;
-    const int M = tail_len[i];
-
-    // pass 1: l (written back over E), its max and min, finiteness
+    ra[tid] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) { if (tid < w) ra[tid] += ra[tid + w]; __syncthreads(); }
+    return ra[0];
+}
+__device__ __forceinline__ double bnr_block_max(double *ra, int tid, double v)
+{
+    ra[tid] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) { if (tid < w) ra[tid] = fmax(ra[tid], ra[tid + w]); __syncthreads(); }
+    return ra[0];
+}
+// (wave 0) the bin of a histogram that holds its want-th largest entry: lane owns the bins [lane per, lane per + per), suffix sums over the
+// lanes find the owner; *above = the entries in higher bins, *cnt = the bin's own
+__device__ __forceinline__ void bnr_hist_pick(const unsigned *hist, int nbins, unsigned want, int lane, unsigned *bin, unsigned *above, unsigned *cnt)
+{
+    const int per = nbins / 64;
+    unsigned c = 0;
+    for (int b = 0; b < per; ++b) c += hist[lane * per + b];
+    unsigned suf = c;
+    for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_down(suf, o); if (lane + o < 64) suf += t; }
+    const unsigned long long ge = __ballot(suf >= want);
+    const int owner = 63 - __clzll((long long)ge);
+    if (lane == owner) {
+        unsigned acc = suf - c;
+        for (int b = per - 1; b >= 0; --b) {
+            const unsigned h = hist[lane * per + b];
+            if (acc + h >= want) { *bin = (unsigned)(lane * per + b); *above = acc; *cnt = h; break; }
+            acc += h;
+        }
+    }
+}
+// pass 1: the row's l (from src; stored to dst when `store`), lmax = max l, rmax = max r = -min l; returns nonzero when an l is not finite
+template <int FROM_E>
+__device__ __forceinline__ int bnr_psis_pass1(const double *src, double *dst, bool store, int nsamp, const double *y, int i, const double *tau2,
+                                              bnr_psis_lds &sh, int tid, double &lmax, double &rmax)
+{
     double mx = -INFINITY, mn = INFINITY;
     int bad = 0;
     for (int s = tid; s < nsamp; s += 256) {
-        double v;
-        if (FROM_E) { v = bnr_pred_ell(y[i], l[s], tau2[s]); l[s] = v; }
-        else v = l[s];
+        const double v = FROM_E ? bnr_pred_ell(y[i], src[s], tau2[s]) : src[s];
+        if (store) dst[s] = v;
         mx = fmax(mx, v); mn = fmin(mn, v);
         bad |= !isfinite(v);
     }
-    ra[tid] = mx; rb[tid] = mn;
+    sh.ra[tid] = mx; sh.rb[tid] = mn;
     bad = __syncthreads_or(bad);
-    for (int w = 128; w > 0; w >>= 1) { if (tid < w) { ra[tid] = fmax(ra[tid], ra[tid + w]); rb[tid] = fmin(rb[tid], rb[tid + w]); } __syncthreads(); }
-    const double lmax = ra[0], rmax = -rb[0];          // max r = -min l
+    for (int w = 128; w > 0; w >>= 1) { if (tid < w) { sh.ra[tid] = fmax(sh.ra[tid], sh.ra[tid + w]); sh.rb[tid] = fmin(sh.rb[tid], sh.rb[tid + w]); } __syncthreads(); }
+    lmax = sh.ra[0]; rmax = -sh.rb[0];
     __syncthreads();
-    const bool select = !bad && M >= 5;
-
-    // passes 2-7: radix select of the (M+1)-th largest key of lw = -l - rmax; pass 2 also sums exp(l - lmax) for lpd
-    unsigned *hist = (unsigned *)psis_dyn;
+    return bad;
+}
+// passes 2-7: radix select of K_c, the (M+1)-th largest key of lw = -l - rmax (select: the row is finite and M >= 5; otherwise pass 2 alone and
+// K_c = all ones: no tail).  want - 1 of the cnt_eq keys == K_c rank above the cutoff, `above` keys are > K_c; se = this thread's part of
+// sum_s exp(l_s - lmax) (pass 2).  hist: 2048 unsigned of dynamic LDS
+__device__ __forceinline__ unsigned long long bnr_psis_cutoff(const double *l, int nsamp, bool select, int M, double lmax, double rmax, unsigned *hist,
+                                                              bnr_psis_lds &sh, int tid, unsigned &want, unsigned &above, unsigned &cnt_eq, double &se)
+{
     unsigned long long prefix = 0, mask = 0;
-    unsigned want = (unsigned)M + 1, above_all = 0, cnt_eq = 0;
-    double se = 0.0;
+    want = (unsigned)M + 1; above = 0; cnt_eq = 0;
+    se = 0.0;
     for (int p = 0; p < 6; ++p) {
         const int shift = p < 5 ? 53 - 11 * p : 0, nbins = p < 5 ? 2048 : 512;
         if (select) {
@@ -3866,66 +3902,144 @@ __global__ __launch_bounds__(256) void k_psis(double *L, int nsamp, const double
         }
         if (!select) break;
         __syncthreads();
-        if (wv == 0) {
-            // lane owns the bins [lane per, lane per + per); suffix sums over the lanes find the bin that holds the want-th largest key
-            const int per = nbins / 64;
-            unsigned c = 0;
-            for (int b = 0; b < per; ++b) c += hist[lane * per + b];
-            unsigned suf = c;
-            for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_down(suf, o); if (lane + o < 64) suf += t; }
-            const unsigned long long ge = __ballot(suf >= want);
-            const int owner = 63 - __clzll((long long)ge);
-            if (lane == owner) {
-                unsigned acc = suf - c;
-                for (int b = per - 1; b >= 0; --b) {
-                    const unsigned h = hist[lane * per + b];
-                    if (acc + h >= want) { s_bin = (unsigned)(lane * per + b); s_above = acc; s_cnt = h; break; }
-                    acc += h;
-                }
-            }
-        }
+        if ((tid >> 6) == 0) bnr_hist_pick(hist, nbins, want, tid & 63, &sh.bin, &sh.above, &sh.cnt);
         __syncthreads();
-        prefix |= (unsigned long long)s_bin << shift;
+        prefix |= (unsigned long long)sh.bin << shift;
         mask |= (unsigned long long)(nbins - 1) << shift;
-        above_all += s_above; want -= s_above; cnt_eq = s_cnt;
+        above += sh.above; want -= sh.above; cnt_eq = sh.cnt;
         __syncthreads();
     }
-    // lpd: k_pred_loglik's tree
-    ra[tid] = se;
+    return select ? prefix : ~0ull;
+}
+// the generalized Pareto fit of a tail; kh = +inf, smooth = false: no fit
+struct bnr_psis_fit {
+    double kh, sigma, ec;
+    bool smooth;
+};
+// gpdfit (Zhang & Stephens with loo's prior on k) on x_j = exp(lw_(j)) - exp(cutoff), lw_(j) = the sorted keys tk[0 .. M - 1], ascending;
+// a tail narrower than .Machine$double.eps / 100 is not fitted.  Reads other threads' keys up to its last barrier-free statement: the caller
+// puts a barrier before it overwrites one
+__device__ __forceinline__ bnr_psis_fit bnr_psis_gpd_fit(const unsigned long long *tk, int M, unsigned long long Kc, bnr_psis_lds &sh, int tid)
+{
+    const int lane = tid & 63, wv = tid >> 6;
+    bnr_psis_fit f{INFINITY, 0.0, 0.0, false};
+    const double cutoff = bnr_okey_inv(Kc);
+    const double lo = bnr_okey_inv(tk[0]), hi = bnr_okey_inv(tk[M - 1]);
+    if (fabs(hi - lo) < 2.220446049250313e-16 / 100) return f;
+    const double ec = exp(cutoff);
+    auto xv = [&](int j) { return exp(bnr_okey_inv(tk[j])) - ec; };
+    const double xN = xv(M - 1), xstar = xv((int)floor(M / 4.0 + 0.5) - 1);
+    const int mg = 30 + (int)floor(sqrt((double)M));
+    auto theta = [&](int j) { return 1.0 / xN + (1.0 - sqrt((double)mg / ((double)j + 0.5))) / 3.0 / xstar; };
+    for (int j = wv; j < mg; j += 4) {
+        const double a = -theta(j);
+        double acc = 0.0;
+        for (int t = lane; t < M; t += 64) acc += log1p(a * xv(t));
+        acc += __shfl_xor(acc, 32); acc += __shfl_xor(acc, 16); acc += __shfl_xor(acc, 8);
+        acc += __shfl_xor(acc, 4); acc += __shfl_xor(acc, 2); acc += __shfl_xor(acc, 1);
+        const double kj = acc / M;
+        if (lane == 0) sh.lth[j] = M * (log(a / kj) - kj - 1.0);
+    }
     __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) { if (tid < w) ra[tid] += ra[tid + w]; __syncthreads(); }
-    if (tid == 0 && lpd) lpd[i] = lmax + log(ra[0] / nsamp);
+    if (tid == 0) {
+        // weights exp(l_j - logSumExp(l)) with matrixStats' logSumExp (max + log1p of the sum over the other points)
+        int jm = 0;
+        for (int j = 1; j < mg; ++j) if (sh.lth[j] > sh.lth[jm]) jm = j;
+        const double lm = sh.lth[jm];
+        double sum = 0.0;
+        for (int j = 0; j < mg; ++j) if (j != jm) sum += exp(sh.lth[j] - lm);
+        const double lse = lm + log1p(sum);
+        double th = 0.0;
+        for (int j = 0; j < mg; ++j) th += theta(j) * exp(sh.lth[j] - lse);
+        sh.theta = th;
+    }
+    __syncthreads();
+    const double th = sh.theta;
+    double acc = 0.0;
+    for (int t = tid; t < M; t += 256) acc += log1p(-th * xv(t));
+    const double k0 = bnr_block_sum(sh.ra, tid, acc) / M;
+    f.ec = ec;
+    f.sigma = -k0 / th;
+    f.kh = k0 * M / (M + 10) + 10 * 0.5 / (M + 10);
+    if (isnan(f.kh)) f.kh = INFINITY;
+    f.smooth = isfinite(f.kh);
+    return f;
+}
+// the log weight of position j of the sorted tail: the j-th qgpd quantile above the cutoff, or the key as it was; truncated at 0
+__device__ __forceinline__ double bnr_psis_tail_lw(const bnr_psis_fit &f, const unsigned long long *tk, int j, int M)
+{
+    double lw;
+    if (f.smooth) {
+        const double pj = ((double)j + 0.5) / M;
+        const double qq = (isnan(f.sigma) || f.sigma <= 0.0) ? NAN : f.sigma * expm1(-f.kh * log1p(-pj)) / f.kh;
+        lw = log(qq + f.ec);
+    } else lw = bnr_okey_inv(tk[j]);
+    return lw > 0.0 ? 0.0 : lw;
+}
+// the threads' running log-sum-exps (mA, sA) and (mB, sB) merged in a tree: (ra[0], rb[0]) and (rc[0], rd[0]) hold the two totals
+__device__ __forceinline__ void bnr_psis_lse_tree(bnr_psis_lds &sh, int tid, double mA, double sA, double mB, double sB)
+{
+    __syncthreads();                                   // (every thread has read ra[0] of the sums before)
+    sh.ra[tid] = mA; sh.rb[tid] = sA; sh.rc[tid] = mB; sh.rd[tid] = sB;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if (tid < w) {
+            double m1 = sh.ra[tid], s1 = sh.rb[tid], m2 = sh.rc[tid], s2 = sh.rd[tid];
+            bnr_lse_merge(m1, s1, sh.ra[tid + w], sh.rb[tid + w]);
+            bnr_lse_merge(m2, s2, sh.rc[tid + w], sh.rd[tid + w]);
+            sh.ra[tid] = m1; sh.rb[tid] = s1; sh.rc[tid] = m2; sh.rd[tid] = s2;
+        }
+        __syncthreads();
+    }
+}
+
+// k_psis: lpd, elpd and khat of a row.  L + i nsamp holds the row; FROM_E = 1 writes l back over E in pass 1.  A tail entry is its key and its l
+// (16 bytes).  Ties: the tail is every key > K_c plus (M - #{key > K_c}) copies of (K_c, l_c), l_c = max l over key == K_c (found in pass 8); the
+// other keys == K_c enter the sums as a counted multiple of (K_c, l_c).  Tied ratios have tied l, so this is the tail any sort would pick; a tie
+// created only by the rounding of r - max r moves a result by an ulp of that l.  The tail is sorted by (key, key of l).
+// Both instantiations are referenced only from the end of bnr_hip.hip, so that they sit behind the sweep kernels in the code object.
+template <int FROM_E>
+__global__ __launch_bounds__(256) void k_psis(double *L, int nsamp, const double *y, const double *tau2, const int *tail_len, double *lpd,
+                                              double *elpd, double *khat)
+{
+    extern __shared__ unsigned long long psis_dyn[];
+    __shared__ bnr_psis_lds sh;
+    const int i = blockIdx.x, tid = threadIdx.x;
+    double *l = L + (size_t)i * nsamp;
+    const int M = tail_len[i];
+
+    double lmax, rmax, se;
+    const int bad = bnr_psis_pass1<FROM_E>(l, l, FROM_E != 0, nsamp, y, i, tau2, sh, tid, lmax, rmax);
+    const bool select = !bad && M >= 5;
+    unsigned want, above_all, cnt_eq;
+    const unsigned long long Kc = bnr_psis_cutoff(l, nsamp, select, M, lmax, rmax, (unsigned *)psis_dyn, sh, tid, want, above_all, cnt_eq, se);
+    se = bnr_block_sum(sh.ra, tid, se);
+    if (tid == 0 && lpd) lpd[i] = lmax + log(se / nsamp);
     __syncthreads();
     if (bad) {
         if (tid == 0) { elpd[i] = NAN; khat[i] = INFINITY; }
         return;
     }
 
-    // pass 8: the tail (keys > K_c) into LDS, l_c, and the log-sum-exps of every other draw (K_c = all ones: no tail, every draw)
-    const unsigned long long Kc = select ? prefix : ~0ull;
+    // pass 8: the tail (keys > K_c) into LDS, l_c, and the log-sum-exps of every other draw
     const int P = select ? (int)(1u << (32 - __clz(M - 1))) : 0;        // the smallest power of two >= M
     unsigned long long *tk = psis_dyn;
     double *tl = (double *)(psis_dyn + P);
-    if (tid == 0) s_pos = 0u;
+    if (tid == 0) sh.pos = 0u;
     __syncthreads();
     double mA = -INFINITY, sA = 0.0, mB = -INFINITY, sB = 0.0, lc = -INFINITY;
     for (int s = tid; s < nsamp; s += 256) {
         const double v = l[s], lw = -v - rmax;
         const unsigned long long k = bnr_okey(lw);
         if (k > Kc) {
-            const unsigned pos = atomicAdd(&s_pos, 1u);
+            const unsigned pos = atomicAdd(&sh.pos, 1u);
             if (pos < (unsigned)M) { tk[pos] = k; tl[pos] = v; }
         } else if (k == Kc) lc = fmax(lc, v);
         else { bnr_lse_merge(mA, sA, lw + v, 1.0); bnr_lse_merge(mB, sB, lw, 1.0); }
     }
-    double kh = INFINITY;
-    bool smooth = false;
-    double sigma = 0.0, ec = 0.0;
+    bnr_psis_fit f{INFINITY, 0.0, 0.0, false};
     if (select) {
-        ra[tid] = lc;
-        __syncthreads();
-        for (int w = 128; w > 0; w >>= 1) { if (tid < w) ra[tid] = fmax(ra[tid], ra[tid + w]); __syncthreads(); }
-        lc = ra[0];
+        lc = bnr_block_max(sh.ra, tid, lc);
         const int g = (int)above_all;                  // #{key > K_c}; M - g copies of (K_c, l_c) complete the tail
         for (int j = g + tid; j < P; j += 256) {
             if (j < M) { tk[j] = Kc; tl[j] = lc; }
@@ -3946,83 +4060,22 @@ __global__ __launch_bounds__(256) void k_psis(double *L, int nsamp, const double
                 }
                 __syncthreads();
             }
-        const double cutoff = bnr_okey_inv(Kc);
-        const double lo = bnr_okey_inv(tk[0]), hi = bnr_okey_inv(tk[M - 1]);
-        if (!(fabs(hi - lo) < 2.220446049250313e-16 / 100)) {         // .Machine$double.eps / 100
-            // gpdfit on x_j = exp(lw_(j)) - exp(cutoff), ascending
-            ec = exp(cutoff);
-            auto xv = [&](int j) { return exp(bnr_okey_inv(tk[j])) - ec; };
-            const double xN = xv(M - 1), xstar = xv((int)floor(M / 4.0 + 0.5) - 1);
-            const int mg = 30 + (int)floor(sqrt((double)M));
-            auto theta = [&](int j) { return 1.0 / xN + (1.0 - sqrt((double)mg / ((double)j + 0.5))) / 3.0 / xstar; };
-            for (int j = wv; j < mg; j += 4) {
-                const double a = -theta(j);
-                double acc = 0.0;
-                for (int t = lane; t < M; t += 64) acc += log1p(a * xv(t));
-                acc += __shfl_xor(acc, 32); acc += __shfl_xor(acc, 16); acc += __shfl_xor(acc, 8);
-                acc += __shfl_xor(acc, 4); acc += __shfl_xor(acc, 2); acc += __shfl_xor(acc, 1);
-                const double kj = acc / M;
-                if (lane == 0) lth[j] = M * (log(a / kj) - kj - 1.0);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                // weights exp(l_j - logSumExp(l)) with matrixStats' logSumExp (max + log1p of the sum over the other points)
-                int jm = 0;
-                for (int j = 1; j < mg; ++j) if (lth[j] > lth[jm]) jm = j;
-                const double lm = lth[jm];
-                double sum = 0.0;
-                for (int j = 0; j < mg; ++j) if (j != jm) sum += exp(lth[j] - lm);
-                const double lse = lm + log1p(sum);
-                double th = 0.0;
-                for (int j = 0; j < mg; ++j) th += theta(j) * exp(lth[j] - lse);
-                s_theta = th;
-            }
-            __syncthreads();
-            const double th = s_theta;
-            double acc = 0.0;
-            for (int t = tid; t < M; t += 256) acc += log1p(-th * xv(t));
-            ra[tid] = acc;
-            __syncthreads();
-            for (int w = 128; w > 0; w >>= 1) { if (tid < w) ra[tid] += ra[tid + w]; __syncthreads(); }
-            const double k0 = ra[0] / M;
-            sigma = -k0 / th;
-            kh = k0 * M / (M + 10) + 10 * 0.5 / (M + 10);
-            if (isnan(kh)) kh = INFINITY;
-            smooth = isfinite(kh);
-        }
-        // the tail's terms, smoothed (qgpd quantiles above the cutoff) or as they were, truncated at 0
+        f = bnr_psis_gpd_fit(tk, M, Kc, sh, tid);
         for (int j = tid; j < M; j += 256) {
-            double lw;
-            if (smooth) {
-                const double pj = ((double)j + 0.5) / M;
-                const double qq = (isnan(sigma) || sigma <= 0.0) ? NAN : sigma * expm1(-kh * log1p(-pj)) / kh;
-                lw = log(qq + ec);
-            } else lw = bnr_okey_inv(tk[j]);
-            if (lw > 0.0) lw = 0.0;
+            const double lw = bnr_psis_tail_lw(f, tk, j, M);
             bnr_lse_merge(mA, sA, lw + tl[j], 1.0);
             bnr_lse_merge(mB, sB, lw, 1.0);
         }
     }
-    __syncthreads();                                   // (every thread has read ra[0] above)
-    ra[tid] = mA; rb[tid] = sA; rc[tid] = mB; rd[tid] = sB;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) {
-            double m1 = ra[tid], s1 = rb[tid], m2 = rc[tid], s2 = rd[tid];
-            bnr_lse_merge(m1, s1, ra[tid + w], rb[tid + w]);
-            bnr_lse_merge(m2, s2, rc[tid + w], rd[tid + w]);
-            ra[tid] = m1; rb[tid] = s1; rc[tid] = m2; rd[tid] = s2;
-        }
-        __syncthreads();
-    }
+    bnr_psis_lse_tree(sh, tid, mA, sA, mB, sB);
     if (tid == 0) {
-        double m1 = ra[0], s1 = rb[0], m2 = rc[0], s2 = rd[0];
+        double m1 = sh.ra[0], s1 = sh.rb[0], m2 = sh.rc[0], s2 = sh.rd[0];
         if (select) {
             const double ne = (double)(cnt_eq - (want - 1)), lwc = bnr_okey_inv(Kc);   // the keys == K_c outside the tail
             if (ne > 0) { bnr_lse_merge(m1, s1, lwc + lc, ne); bnr_lse_merge(m2, s2, lwc, ne); }
         }
         elpd[i] = (m1 + log(s1)) - (m2 + log(s2));
-        khat[i] = kh;
+        khat[i] = f.kh;
     }
 }
 
@@ -4077,107 +4130,42 @@ __global__ __launch_bounds__(256) void k_pred_pit(const double *E, int nsamp, co
 // The PSIS weights themselves and, on top of them, the leave-one-out posterior predictive of every row: mean, standard deviation, PIT and the
 // quantiles of the mixture CDF.  All templates, referenced only from the very end of bnr_hip.hip (behind every kernel above in the code object).
 //
-// k_psis_w: k_psis with the per-draw weights kept.  One workgroup of 256 threads per row (blockIdx.x).  In: the row's eta (FROM_E = 1:
-// l_s = bnr_pred_ell(y_i, E_is, tau2_s)) or its l row (FROM_E = 0), read once and never written.  Out: LW + i nsamp, the NORMALISED log weights
-// lw_s - logsumexp_s lw_s (loo's weights(normalize = TRUE, log = TRUE)) after smoothing and truncation at 0; lpd (k_psis's, bit for bit),
-// elpd = log sum_s w_s exp(l_s) from the same weights, khat.  A row with a non-finite l: LW all NaN, elpd NaN, khat +inf.
+// k_psis_w: the PSIS of k_psis's header with the per-draw weights kept.  In: the row's eta (FROM_E = 1) or its l row (FROM_E = 0), read once and
+// never written.  Out: LW + i nsamp, the NORMALISED log weights lw_s - logsumexp_s lw_s (loo's weights(normalize = TRUE, log = TRUE)) after
+// smoothing and truncation at 0; lpd (the shared passes 1-2: k_psis's, bit for bit), elpd = log sum_s w_s exp(l_s) from the same weights, khat.
+// A row with a non-finite l: LW all NaN, elpd NaN, khat +inf.
 // l is written to LW in pass 1 and overwritten by the weights at the end (not recomputed from eta on every pass: a log and a division per
 // draw and pass against one 8-byte read that the pass needs in either form; it also makes the two instantiations one code path behind pass 1).
-// Passes over the row: 1 l -> LW, max, min, finiteness; 2-7 k_psis's exact radix select of K_c, the (M+1)-th largest 64-bit key of lw (pass 2 also
-// sums exp(l - max) for lpd); [7a-7c only when keys equal to K_c belong to the tail: radix select over the DRAW INDEX among the keys == K_c,
-// 11 + 11 + 10 bits, of s_c, the t-th largest such index]; 8 gather of the tail and the log-sum-exps of every other draw; 9 the weights.
+// Its own passes: [7a-7c only when keys equal to K_c belong to the tail: radix select over the DRAW INDEX among the keys == K_c, 11 + 11 + 10
+// bits, of s_c, the t-th largest such index]; 8 gathers (key, draw); 9 the weights.
 // Tail and ties: the tail is the M draws largest in the lexicographic order (lw, s) -- what a stable ascending argsort of lw picks -- i.e.
 // key > K_c, or key == K_c and s >= s_c; the composite key has no ties, so after the bitonic sort of (key, s) in LDS position j is one
 // definite draw and gets the j-th GPD quantile.  A tail entry is the key (8 bytes) and the draw index (4 bytes); its l is read back from
-// LW[s].  Dynamic LDS: max(8 KiB, 12 P) bytes, P = the smallest power of two >= the largest M of the launch: 96 KiB at M = BNR_PSIS_MAX_TAIL,
-// which with the 9.3 KiB of static LDS fits the CU's 160 KiB -- the longest tail is k_psis's, nothing more is refused.
-// The smoothed tail is scattered back to LW[s] behind a barrier; every sum is thread-strided and then a tree (running log-sum-exps as in
-// k_psis), the GPD grid has k_psis's fixed butterflies, the atomics are integer LDS atomics: results are bitwise independent of the grid,
-// of the block of rows and of the call.  Against k_psis, elpd and khat differ only in the order of tied terms and of the tail's sums.
-// 120 VGPRs, 99 SGPRs, 9 504 bytes of static LDS, no scratch (kernel-resource-usage, gfx950: 4 waves per SIMD); with the dynamic LDS -- 24 KiB
+// LW[s].  Dynamic LDS: 96 KiB at M = BNR_PSIS_MAX_TAIL, which with the static LDS fits the CU's 160 KiB -- the longest tail is k_psis's,
+// nothing more is refused.  The smoothed tail is scattered back to LW[s] behind a barrier.  Against k_psis, elpd and khat differ only in the
+// order of tied terms and of the tail's sums.
+// 120 VGPRs, 96 SGPRs, 9 504 bytes of static LDS, no scratch (kernel-resource-usage, gfx950: 4 waves per SIMD); with the dynamic LDS -- 24 KiB
 // at the headline's pooled tail of 1 200 draws -- 4 workgroups per CU, one at the longest tail.
 #define BNR_PSISW_ENTRY_BYTES 12       // a tail entry of k_psis_w in LDS: the key (8) and the draw index (4); the host sizes the dynamic LDS with it
-__device__ __forceinline__ void bnr_hist_pick(const unsigned *hist, int nbins, unsigned want, int lane, unsigned *bin, unsigned *above, unsigned *cnt)
-{
-    // (wave 0) lane owns the bins [lane per, lane per + per); suffix sums over the lanes find the bin that holds the want-th largest entry
-    const int per = nbins / 64;
-    unsigned c = 0;
-    for (int b = 0; b < per; ++b) c += hist[lane * per + b];
-    unsigned suf = c;
-    for (int o = 1; o < 64; o <<= 1) { const unsigned t = __shfl_down(suf, o); if (lane + o < 64) suf += t; }
-    const unsigned long long ge = __ballot(suf >= want);
-    const int owner = 63 - __clzll((long long)ge);
-    if (lane == owner) {
-        unsigned acc = suf - c;
-        for (int b = per - 1; b >= 0; --b) {
-            const unsigned h = hist[lane * per + b];
-            if (acc + h >= want) { *bin = (unsigned)(lane * per + b); *above = acc; *cnt = h; break; }
-            acc += h;
-        }
-    }
-}
 template <int FROM_E>
 __global__ __launch_bounds__(256) void k_psis_w(const double *Lin, int nsamp, const double *y, const double *tau2, const int *tail_len, double *LW,
                                                 double *lpd, double *elpd, double *khat)
 {
     extern __shared__ unsigned long long psisw_dyn[];
-    __shared__ double ra[256], rb[256], rc[256], rd[256], lth[BNR_PSIS_MAX_GRID];
-    __shared__ unsigned s_bin, s_above, s_cnt, s_pos;
-    __shared__ double s_theta, s_logz;
-    const int i = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const double *src = Lin + (size_t)i * nsamp;
+    __shared__ bnr_psis_lds sh;
+    __shared__ double s_logz;
+    const int i = blockIdx.x, tid = threadIdx.x;
     double *l = LW + (size_t)i * nsamp;
     const int M = tail_len[i];
 
-    // pass 1: l into LW, its max and min, finiteness
-    double mx = -INFINITY, mn = INFINITY;
-    int bad = 0;
-    for (int s = tid; s < nsamp; s += 256) {
-        const double v = FROM_E ? bnr_pred_ell(y[i], src[s], tau2[s]) : src[s];
-        l[s] = v;
-        mx = fmax(mx, v); mn = fmin(mn, v);
-        bad |= !isfinite(v);
-    }
-    ra[tid] = mx; rb[tid] = mn;
-    bad = __syncthreads_or(bad);
-    for (int w = 128; w > 0; w >>= 1) { if (tid < w) { ra[tid] = fmax(ra[tid], ra[tid + w]); rb[tid] = fmin(rb[tid], rb[tid + w]); } __syncthreads(); }
-    const double lmax = ra[0], rmax = -rb[0];          // max r = -min l
-    __syncthreads();
+    double lmax, rmax, se;
+    const int bad = bnr_psis_pass1<FROM_E>(Lin + (size_t)i * nsamp, l, true, nsamp, y, i, tau2, sh, tid, lmax, rmax);
     const bool select = !bad && M >= 5;
-
-    // passes 2-7: radix select of the (M+1)-th largest key of lw = -l - rmax; pass 2 also sums exp(l - lmax) for lpd
     unsigned *hist = (unsigned *)psisw_dyn;
-    unsigned long long prefix = 0, mask = 0;
-    unsigned want = (unsigned)M + 1;
-    double se = 0.0;
-    for (int p = 0; p < 6; ++p) {
-        const int shift = p < 5 ? 53 - 11 * p : 0, nbins = p < 5 ? 2048 : 512;
-        if (select) {
-            for (int b = tid; b < nbins; b += 256) hist[b] = 0u;
-            __syncthreads();
-        }
-        for (int s = tid; s < nsamp; s += 256) {
-            const double v = l[s];
-            if (p == 0) se += exp(v - lmax);
-            if (select) {
-                const unsigned long long k = bnr_okey(-v - rmax);
-                if ((k & mask) == prefix) atomicAdd(&hist[(unsigned)(k >> shift) & (unsigned)(nbins - 1)], 1u);
-            }
-        }
-        if (!select) break;
-        __syncthreads();
-        if (wv == 0) bnr_hist_pick(hist, nbins, want, lane, &s_bin, &s_above, &s_cnt);
-        __syncthreads();
-        prefix |= (unsigned long long)s_bin << shift;
-        mask |= (unsigned long long)(nbins - 1) << shift;
-        want -= s_above;
-        __syncthreads();
-    }
-    // lpd: k_pred_loglik's tree
-    ra[tid] = se;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) { if (tid < w) ra[tid] += ra[tid + w]; __syncthreads(); }
-    if (tid == 0 && lpd) lpd[i] = lmax + log(ra[0] / nsamp);
+    unsigned want, above_all, cnt_eq;
+    const unsigned long long Kc = bnr_psis_cutoff(l, nsamp, select, M, lmax, rmax, hist, sh, tid, want, above_all, cnt_eq, se);
+    se = bnr_block_sum(sh.ra, tid, se);
+    if (tid == 0 && lpd) lpd[i] = lmax + log(se / nsamp);
     __syncthreads();
     if (bad) {
         for (int s = tid; s < nsamp; s += 256) l[s] = NAN;
@@ -4187,7 +4175,6 @@ __global__ __launch_bounds__(256) void k_psis_w(const double *Lin, int nsamp, co
 
     // passes 7a-7c: want - 1 of the keys == K_c belong to the tail: those of the largest draw index.  s_c = the (want - 1)-th largest
     // draw index among them (no such pass without a tie at the cutoff: want == 1)
-    const unsigned long long Kc = select ? prefix : ~0ull;
     unsigned sc = 0xFFFFFFFFu;
     if (select && want > 1u) {
         unsigned ipre = 0, imask = 0, iwant = want - 1u;
@@ -4199,37 +4186,35 @@ __global__ __launch_bounds__(256) void k_psis_w(const double *Lin, int nsamp, co
                 if (bnr_okey(-l[s] - rmax) == Kc && ((unsigned)s & imask) == ipre) atomicAdd(&hist[((unsigned)s >> shift) & (unsigned)(nbins - 1)], 1u);
             }
             __syncthreads();
-            if (wv == 0) bnr_hist_pick(hist, nbins, iwant, lane, &s_bin, &s_above, &s_cnt);
+            if ((tid >> 6) == 0) bnr_hist_pick(hist, nbins, iwant, tid & 63, &sh.bin, &sh.above, &sh.cnt);
             __syncthreads();
-            ipre |= s_bin << shift;
+            ipre |= sh.bin << shift;
             imask |= (unsigned)(nbins - 1) << shift;
-            iwant -= s_above;
+            iwant -= sh.above;
             __syncthreads();
         }
         sc = ipre;
     }
 
-    // pass 8: the tail (key, draw) into LDS and the log-sum-exps of every other draw (K_c = all ones: no tail, every draw)
+    // pass 8: the tail (key, draw) into LDS and the log-sum-exps of every other draw
     const int P = select ? (int)(1u << (32 - __clz(M - 1))) : 0;        // the smallest power of two >= M
     unsigned long long *tk = psisw_dyn;
     unsigned *ts = (unsigned *)(psisw_dyn + P);
-    if (tid == 0) s_pos = 0u;
+    if (tid == 0) sh.pos = 0u;
     __syncthreads();
     double mA = -INFINITY, sA = 0.0, mB = -INFINITY, sB = 0.0;
     for (int s = tid; s < nsamp; s += 256) {
         const double v = l[s], lw = -v - rmax;
         const unsigned long long k = bnr_okey(lw);
         if (k > Kc || (k == Kc && (unsigned)s >= sc)) {
-            const unsigned pos = atomicAdd(&s_pos, 1u);
+            const unsigned pos = atomicAdd(&sh.pos, 1u);
             if (pos < (unsigned)M) { tk[pos] = k; ts[pos] = (unsigned)s; }
         } else { bnr_lse_merge(mA, sA, lw + v, 1.0); bnr_lse_merge(mB, sB, lw, 1.0); }
     }
     double kh = INFINITY;
     if (select) {
-        bool smooth = false;
-        double sigma = 0.0, ec = 0.0;
         __syncthreads();
-        for (int j = (int)min(s_pos, (unsigned)M) + tid; j < P; j += 256) { tk[j] = ~0ull; ts[j] = 0xFFFFFFFFu; }     // (exactly M draws were gathered: j = M ..)
+        for (int j = (int)min(sh.pos, (unsigned)M) + tid; j < P; j += 256) { tk[j] = ~0ull; ts[j] = 0xFFFFFFFFu; }     // (exactly M draws were gathered: j = M ..)
         __syncthreads();
         // bitonic sort of (key, draw) ascending; the padding ends behind the tail
         for (int kk = 2; kk <= P; kk <<= 1)
@@ -4243,83 +4228,25 @@ __global__ __launch_bounds__(256) void k_psis_w(const double *Lin, int nsamp, co
                 }
                 __syncthreads();
             }
-        const double cutoff = bnr_okey_inv(Kc);
-        const double lo = bnr_okey_inv(tk[0]), hi = bnr_okey_inv(tk[M - 1]);
-        if (!(fabs(hi - lo) < 2.220446049250313e-16 / 100)) {         // .Machine$double.eps / 100
-            // gpdfit on x_j = exp(lw_(j)) - exp(cutoff), ascending (k_psis's expressions and orders)
-            ec = exp(cutoff);
-            auto xv = [&](int j) { return exp(bnr_okey_inv(tk[j])) - ec; };
-            const double xN = xv(M - 1), xstar = xv((int)floor(M / 4.0 + 0.5) - 1);
-            const int mg = 30 + (int)floor(sqrt((double)M));
-            auto theta = [&](int j) { return 1.0 / xN + (1.0 - sqrt((double)mg / ((double)j + 0.5))) / 3.0 / xstar; };
-            for (int j = wv; j < mg; j += 4) {
-                const double a = -theta(j);
-                double acc = 0.0;
-                for (int t = lane; t < M; t += 64) acc += log1p(a * xv(t));
-                acc += __shfl_xor(acc, 32); acc += __shfl_xor(acc, 16); acc += __shfl_xor(acc, 8);
-                acc += __shfl_xor(acc, 4); acc += __shfl_xor(acc, 2); acc += __shfl_xor(acc, 1);
-                const double kj = acc / M;
-                if (lane == 0) lth[j] = M * (log(a / kj) - kj - 1.0);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int jm = 0;
-                for (int j = 1; j < mg; ++j) if (lth[j] > lth[jm]) jm = j;
-                const double lm = lth[jm];
-                double sum = 0.0;
-                for (int j = 0; j < mg; ++j) if (j != jm) sum += exp(lth[j] - lm);
-                const double lse = lm + log1p(sum);
-                double th = 0.0;
-                for (int j = 0; j < mg; ++j) th += theta(j) * exp(lth[j] - lse);
-                s_theta = th;
-            }
-            __syncthreads();
-            const double th = s_theta;
-            double acc = 0.0;
-            for (int t = tid; t < M; t += 256) acc += log1p(-th * xv(t));
-            ra[tid] = acc;
-            __syncthreads();
-            for (int w = 128; w > 0; w >>= 1) { if (tid < w) ra[tid] += ra[tid + w]; __syncthreads(); }
-            const double k0 = ra[0] / M;
-            sigma = -k0 / th;
-            kh = k0 * M / (M + 10) + 10 * 0.5 / (M + 10);
-            if (isnan(kh)) kh = INFINITY;
-            smooth = isfinite(kh);
-        }
-        // the tail's log weights, smoothed (qgpd quantiles above the cutoff) or as they were, truncated at 0; kept in place of the key.
-        // The barrier ends every read of another thread's key (lo / hi above, the x_j of the fit): on the path without a fit there is none
-        // since the sort's, and the loop below overwrites tk[0] and tk[M - 1].  Behind it a thread touches only the entries j it owns.
+        const bnr_psis_fit f = bnr_psis_gpd_fit(tk, M, Kc, sh, tid);
+        kh = f.kh;
+        // the tail's log weights, kept in place of the key.  The barrier ends every read of another thread's key (lo / hi and the x_j of the
+        // fit): on the path without a fit there is none since the sort's, and the loop below overwrites tk[0] and tk[M - 1].  Behind it a
+        // thread touches only the entries j it owns.
         __syncthreads();
         for (int j = tid; j < M; j += 256) {
-            double lw;
-            if (smooth) {
-                const double pj = ((double)j + 0.5) / M;
-                const double qq = (isnan(sigma) || sigma <= 0.0) ? NAN : sigma * expm1(-kh * log1p(-pj)) / kh;
-                lw = log(qq + ec);
-            } else lw = bnr_okey_inv(tk[j]);
-            if (lw > 0.0) lw = 0.0;
+            const double lw = bnr_psis_tail_lw(f, tk, j, M);
             if (ts[j] >= (unsigned)nsamp) continue;    // (never: the padding's index; keeps every access inside the row)
             bnr_lse_merge(mA, sA, lw + l[ts[j]], 1.0);
             bnr_lse_merge(mB, sB, lw, 1.0);
             tk[j] = (unsigned long long)__double_as_longlong(lw);
         }
     }
-    __syncthreads();                                   // (every thread has read ra[0] above)
-    ra[tid] = mA; rb[tid] = sA; rc[tid] = mB; rd[tid] = sB;
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if (tid < w) {
-            double m1 = ra[tid], s1 = rb[tid], m2 = rc[tid], s2 = rd[tid];
-            bnr_lse_merge(m1, s1, ra[tid + w], rb[tid + w]);
-            bnr_lse_merge(m2, s2, rc[tid + w], rd[tid + w]);
-            ra[tid] = m1; rb[tid] = s1; rc[tid] = m2; rd[tid] = s2;
-        }
-        __syncthreads();
-    }
+    bnr_psis_lse_tree(sh, tid, mA, sA, mB, sB);
     if (tid == 0) {
-        const double lz = rc[0] + log(rd[0]);          // logsumexp_s lw_s
+        const double lz = sh.rc[0] + log(sh.rd[0]);    // logsumexp_s lw_s
         s_logz = lz;
-        if (elpd) elpd[i] = (ra[0] + log(rb[0])) - lz;
+        if (elpd) elpd[i] = (sh.ra[0] + log(sh.rb[0])) - lz;
         if (khat) khat[i] = kh;
     }
     __syncthreads();
