@@ -44,37 +44,22 @@ struct bnr_exec {
     bnr_dev *cds = nullptr;                             // device array of nb structs
     const bnr_dev *shape = nullptr;                     // host struct of member 0 (sizes are equal for all members)
     hipStream_t stream = nullptr, stream2 = nullptr;   // stream2: the Gram branch of a sweep
-    hipStream_t stream3 = nullptr, stream4 = nullptr;  // pipelined schedule: the factorization beside the Gram; the sacrificial first branch
-    int pipeline = -1;                                  // -1: chosen by size / availability; 0: the factorization follows the Gram; 1: beside it
-    int gate_us = 3000;                                 // how long a gate of the factorization polls for the Gram's progress
-    unsigned *gctl = nullptr;                           // k_gram8p: queue heads and tickets
-    const unsigned *resv = nullptr;                     // reserved compute units (device table shared per device), nullptr: none
     std::vector<hipEvent_t> fj;                         // fork/join events
     size_t fj_next = 0;
     int overlap = 1;
-    int nop_fork = 0;                                   // (experiments) 1: an empty kernel is captured as the first forked branch of every sweep (needs stream4)
-    int resv_mask = 0x80;                               // k_gram8q: cu ids (inside a shader engine) it keeps off -- 0x80 = cu id 7 of every SE = 32 CUs
-    int crit_origin = 0;                                // 1: the critical chain (Gram, factorization, solve, back-projection) stays on the capture origin's queue and the scalar branch is the forked one; 2: the same with an empty kernel captured as the first fork
     int gram_variant = 0;                               // 0: chosen per launch; 8 / 16: k_gram8 / k_gram forced (tests, experiments)
     int fuse_reduce = -1;                               // -1 / 1: launch 0 of the one-panel factorization also sums the Gram's K-split partials (no k_gram_reduce launch); 0: separate pass
-    int group_backproj = 0;                             // 1: the same for the back-projection / GIG kernel (opt-in: bitwise equal, measured no faster -- the block is bound by the latency of the draws' arithmetic)
     int group_xpass = -1;                               // -1 / 1: a group whose members share X runs the X pass with one workgroup per chunk for all chains; 0: per chain
     bnr_plan_entry *gplan_pin = nullptr, *gplan_dev = nullptr;   // groups: the members' plans of a run call, staged for one copy
     int gplan_cap = 0;                                  // entries per member in there
-    int lin_debug = 0, lin_merge = 0;                   // lin_merge: one stream per part (its scalar branch in front of its Gram)
-    int lin = 0;                                        // >= 1: the linear schedule with that many phase-shifted parts (see capture_linear)
-    std::vector<hipStream_t> lstreams;                  // [2 p] critical chain, [2 p + 1] scalar branch of part p
-    unsigned long long *lflags = nullptr;               // the counters the streams meet through
-    struct lrung { int k, part, which; hipGraph_t graph; hipGraphExec_t gexec; };
-    std::vector<lrung> lladder;
     int wide_backproj = -1;                              // 1: k_backproj64 (64 edges per workgroup, one edge per lane of the drawing wave); -1: launches of many rounds (a group at large q)
     int split_sums = -1;                                 // 1: the back-projection's partial sums as a launch of their own in front of the scalar tail (off the critical chain)
-    int spw_cap = 1;                                    // super blocks per update workgroup of the factorization, at most (round 6: 1 -- with the pipelined panel sweep one block each is the shorter launch: 8 chains 369.4 against 372-374 us per sweep; rounds 3-5 packed up to 4 behind the single sweeping wave)
+    int spw_cap = 1;                                    // super blocks per update workgroup of the factorization, at most (round 6: 1 -- with the four-wave panel sweep (bnr_panel_sweep_pipe) one block each is the shorter launch: 8 chains 369.4 against 372-374 us per sweep; rounds 3-5 packed up to 4 behind the single sweeping wave)
     // Round 6: WHEN the scalar branch's kernels start is part of the schedule (profiles/round6_experiments_notes.txt A): inside the two-branch sweep they are ordered behind
     // points of the critical chain by events (graph edges), instead of starting whenever the dispatcher lets the second queue in.
     int tail_after = -2;                                // k_tail(s-1) waits for: -1 nothing (rounds 1-5), 0 the Gram of sweep s; -2: default by size (tail_after_default)
     int node_after = -2;                                // k_node(s) waits for factorization launch number node_after (0-based; -1 nothing); -2: default by size (node_after_default)
-    int factor_variant = -1;                            // -1: chosen by size; 0: right-looking k_chol_step (+ k_gram_reduce); 1: left-looking k_chol_ll
+    int factor_variant = -1;                            // -1: chosen by size; 0: right-looking k_chol_step (+ k_gram_reduce); 2 / 3: two panels per launch (k_chol_step2), 3 with the K = 128 trailing update
     int use_graph = 1, graph_k = 16;                     // (round 5: 16, was 8 -- between two graph launches the GPU idles ~30 us: 640 sweeps 382.2 -> 380.1 us each, 20 sweeps = 16 + 4 instead of 8 + 8 + 4)
     struct rung { int k; hipGraph_t graph; hipGraphExec_t gexec; };
     std::vector<rung> ladder;                           // captured graphs of graph_k, graph_k/2, ..., 1 sweeps: any batch is replayed
@@ -92,7 +77,6 @@ struct bnr_exec {
 // with bnr_chain_create_like, freed with the last of them
 struct bnr_inputs {
     std::vector<void *> bufs;
-    int gq_off[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};       // k_gram8p: queue x = gmapc[gq_off[x] .. gq_off[x + 1])
     ~bnr_inputs() { for (void *p : bufs) (void)hipFree(p); }
 };
 
@@ -467,13 +451,12 @@ static int chain_build(const bnr_chain *donor, int32_t n, int32_t V, int32_t R, 
         c->in = donor->in;
         c->x8_kept = donor->x8_kept;                     // the image belongs to the shared inputs: a chain made from a donor with byte_x = 0 can switch it on again
         c->xm_kept = donor->xm_kept;
-        d.X = donor->d.X; d.X8 = donor->d.X8; d.XM = donor->d.XM; d.y = donor->d.y; d.ek = donor->d.ek; d.el = donor->d.el; d.gmap = donor->d.gmap; d.gmapc = donor->d.gmapc;
+        d.X = donor->d.X; d.X8 = donor->d.X8; d.XM = donor->d.XM; d.y = donor->d.y; d.ek = donor->d.ek; d.el = donor->d.el; d.gmap = donor->d.gmap;
         d.xi_ref = donor->d.xi_ref;                      // a model option, not a path: the chains of one fit sample the same model
     } else {
         c->in = std::make_shared<bnr_inputs>();
         double *Xd = nullptr, *yd = nullptr;
-        int *ek = nullptr, *el = nullptr, *gm = nullptr, *gmc = nullptr;
-        int gq_off[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+        int *ek = nullptr, *el = nullptr, *gm = nullptr;
         auto in_alloc = [&](void **ptr, size_t bytes) -> int {
             HIPCHK(hipMalloc(ptr, std::max<size_t>(bytes, 8)));
             c->in->bufs.push_back(*ptr);
@@ -566,33 +549,8 @@ static int chain_build(const bnr_chain *donor, int32_t n, int32_t V, int32_t R, 
             }
             TRY(in_alloc((void **)&gm, sizeof(int) * ntask));
             HIPNOTE(hipMemcpy(gm, map.data(), ntask * sizeof(int), hipMemcpyHostToDevice));
-            // k_gram8p: eight queues, one per XCD, each in tile-COLUMN order (the factorization consumes G column by column): the
-            // XCD-aware assignment of the static map above -- XCD x works through the K slices ks = x mod 8 and the XCDs without a
-            // slice of their own take an equal share from the END of the others' lists (cascading instead -- an XCD that has run dry
-            // helping its neighbour, which then runs dry early and moves on -- was measured: 3.5 x the L2 misses, 225 instead of 49 MB fetched)
-            std::vector<int> mapc;
-            {
-                std::vector<std::vector<int>> qc(8), mine(8);
-                for (int tc = 0; tc < d.ntile; ++tc)
-                    for (int ti = tc; ti < d.ntile; ++ti)
-                        for (int ks = 0; ks < d.ksplit; ++ks) qc[ks % 8].push_back((ti * (ti + 1) / 2 + tc) | (ks << 16));
-                const int share = (ntask + 7) / 8;
-                std::vector<int> spill;                                   // what exceeds an XCD's share, taken from the end of its list
-                for (int x = 0; x < 8; ++x) {
-                    while ((int)qc[x].size() > share) { spill.push_back(qc[x].back()); qc[x].pop_back(); }
-                    mine[x] = qc[x];
-                }
-                std::sort(spill.begin(), spill.end(), [](int a, int b) { return (a & 0xFFFF) != (b & 0xFFFF) ? (a & 0xFFFF) < (b & 0xFFFF) : a < b; });
-                for (int x = 0; x < 8 && !spill.empty(); ++x)
-                    while ((int)mine[x].size() < share && !spill.empty()) { mine[x].push_back(spill.front()); spill.erase(spill.begin()); }
-                for (int x = 0; x < 8; ++x) { gq_off[x] = (int)mapc.size(); mapc.insert(mapc.end(), mine[x].begin(), mine[x].end()); }
-                gq_off[8] = (int)mapc.size();
-            }
-            TRY(in_alloc((void **)&gmc, sizeof(int) * ntask));
-            HIPNOTE(hipMemcpy(gmc, mapc.data(), ntask * sizeof(int), hipMemcpyHostToDevice));
         }
-        d.X = Xd; d.y = yd; d.ek = ek; d.el = el; d.gmap = gm; d.gmapc = gmc;
-        for (int x = 0; x < 9; ++x) c->in->gq_off[x] = gq_off[x];
+        d.X = Xd; d.y = yd; d.ek = ek; d.el = el; d.gmap = gm;
     }
     TRY(alloc_trace(c, tot_save, &d.trace));
     TRY(dev_alloc(c, &d.Wbuf, d.q_pad));
@@ -658,8 +616,6 @@ static void drop_graph(bnr_exec &x)
 {
     for (auto &r : x.ladder) { if (r.gexec) (void)hipGraphExecDestroy(r.gexec); if (r.graph) (void)hipGraphDestroy(r.graph); }
     x.ladder.clear();
-    for (auto &r : x.lladder) { if (r.gexec) (void)hipGraphExecDestroy(r.gexec); if (r.graph) (void)hipGraphDestroy(r.graph); }
-    x.lladder.clear();
 }
 static int exec_init(bnr_exec &x, int device, int nb, const bnr_dev *shape)
 {
@@ -680,14 +636,7 @@ static void exec_free(bnr_exec &x)
 {
     if (x.stream) { (void)hipStreamSynchronize(x.stream); }
     if (x.stream2) { (void)hipStreamSynchronize(x.stream2); }
-    if (x.stream3) { (void)hipStreamSynchronize(x.stream3); (void)hipStreamDestroy(x.stream3); }
-    if (x.stream4) { (void)hipStreamSynchronize(x.stream4); (void)hipStreamDestroy(x.stream4); }
-    for (hipStream_t st : x.lstreams) { (void)hipStreamSynchronize(st); }
-    if (x.gctl) (void)hipFree(x.gctl);
     drop_graph(x);
-    for (hipStream_t st : x.lstreams) (void)hipStreamDestroy(st);
-    x.lstreams.clear();
-    if (x.lflags) (void)hipFree(x.lflags);
     if (x.stream) (void)hipStreamDestroy(x.stream);
     if (x.stream2) (void)hipStreamDestroy(x.stream2);
     for (hipEvent_t e : x.fj) (void)hipEventDestroy(e);
@@ -803,42 +752,15 @@ static void launch_xpass(bnr_exec &x, int s, int which)
     }
     BNR_LAUNCH(k_xpass, dim3(round_up(x.shape->nblk_x, 8) * x.nb), dim3(256), 3 * x.shape->chunk_x * sizeof(double), x.stream, x, s, which, x.nb);
 }
-// Which factorization: right-looking (k_chol_step behind k_gram_reduce: the trailing update spread over the whole chip) unless the
-// caller asks for the left-looking one (k_chol_ll: no reduction pass, ceil(nbk/4) + nbk - 1 workgroups per chain and launch, can
-// run beside the Gram).  Same tables bit for bit.
-static bool left_looking(const bnr_exec &x)
-{
-    (void)x; return false;
-}
-// The sweep's schedule: pipelined (option "pipeline" = 1) = the factorization runs BESIDE the Gram (k_gram8p keeps off the reserved
-// CUs, k_chol_ll's gates follow its progress column by column); otherwise it follows the Gram on the same stream.
-static bool pipelined(const bnr_exec &x)
-{
-    if (!left_looking(x) || !x.overlap || x.shape->gram_kg != 2) return false;
-    return x.pipeline == 1;                                        // opt-in, experiments build only (notes round 3 B, round 4 B)
-}
+// Which factorization: right-looking, one panel per launch (k_chol_step) or two (k_chol_step2).  Same tables bit for bit.
 // two panels per launch with the K = 128 trailing update (variant 3) where the trailing update is bandwidth-bound: n_pad >= 1024
 // (n = 2000 one chain 424 -> 448 it/s, n = 1000 eight chains 5.49 -> 5.88 k it/s; at n = 500 it is a draw and the one-panel launches stay)
 static bool two_panel_default(const bnr_exec &x) { return x.shape->n_pad >= 1024; }
-// the data-flow factorization (k_chol_df: one launch, one chain per XCD, blocks resident in registers): n_pad <= 512, groups of up to 8
-// (opt-in, experiments build only: bitwise the same factor, measured slower -- profiles/round4_experiments_notes.txt, F)
-static bool dataflow(const bnr_exec &x)
-{
-    (void)x; return false;
-}
-// small problems (n_pad <= 128): the whole factorization in ONE launch of one workgroup per chain (k_chol_small): factor_variant 5
-// (experiments build only: bitwise equal, measured slower -- profiles/round4_experiments_notes.txt H)
-static bool small_factor(const bnr_exec &x)
-{
-    (void)x; return false;
-}
-// the one-panel right-looking factorization (k_chol_step) is the one that runs, and its first launch takes over k_gram_reduce's work
+static bool two_panel(const bnr_exec &x) { return x.factor_variant == 2 || x.factor_variant == 3 || (x.factor_variant < 0 && two_panel_default(x)); }
+// the first launch of the one-panel factorization takes over k_gram_reduce's work
 static bool reduce_in_chol(const bnr_exec &x)
 {
-    if (small_factor(x)) return true;                    // (k_chol_small sums the partial tiles at the first touch of every block: no reduction pass)
-    if (dataflow(x)) return true;                        // (k_chol_df sums the partial tiles at the first touch of every block: no reduction pass at all)
-    const bool one_panel = x.factor_variant == 0 || (x.factor_variant < 0 && !two_panel_default(x));
-    return one_panel && x.fuse_reduce != 0;
+    return !two_panel(x) && x.fuse_reduce != 0;
 }
 // the i8 Gram runs when every chain of the launch has the byte mask of a binary model matrix switched on (chain option "gram_i8")
 static bool gram_on_i8(const bnr_exec &x)
@@ -907,11 +829,8 @@ static void launch_gram(bnr_exec &x, int s, hipStream_t st, bool timed)
         }
     }
     if (timed) HIPNOTE(hipEventRecord(e1, st));
-    if (!left_looking(x) && !reduce_in_chol(x)) BNR_LAUNCH(k_gram_reduce, dim3(ntl, 8, x.nb), dim3(256), 0, st, x, s);
+    if (!reduce_in_chol(x)) BNR_LAUNCH(k_gram_reduce, dim3(ntl, 8, x.nb), dim3(256), 0, st, x, s);
 }
-static int build_qlist(bnr_exec &) { return BNR_OK; }
-static bool wants_qlist(const bnr_exec &x);
-static bool wants_qlist(const bnr_exec &) { return false; }
 static void launch_rhs(bnr_exec &x, int s) { BNR_LAUNCH(k_rhs, dim3(x.shape->n_pad / 64, 1, x.nb), dim3(256), 0, x.stream, x, s); }
 static void launch_chol(bnr_exec &x, int s, hipStream_t st, int rec_p = -1, hipEvent_t rec_ev = nullptr)
 {
@@ -919,7 +838,7 @@ static void launch_chol(bnr_exec &x, int s, hipStream_t st, int rec_p = -1, hipE
     int nlaunch = 0;
     // (after launch number rec_p of the factorization the event rec_ev is recorded: the scalar branch's k_node waits for it)
 #define BNR_CHOL_LAUNCHED() do { if (rec_ev && nlaunch == rec_p) HIPNOTE(hipEventRecord(rec_ev, st)); ++nlaunch; } while (0)
-    if (x.factor_variant == 2 || x.factor_variant == 3 || (x.factor_variant < 0 && two_panel_default(x))) {
+    if (two_panel(x)) {
         // two panels per launch (k_chol_step2): half the launches on the critical path, the same arithmetic; variant 3 (the choice for
         // large n): the whole trailing matrix is read and written at every other launch only, with K = 128
         const int ncu = x.ncu, lazy = x.factor_variant != 2;
@@ -979,7 +898,7 @@ static void launch_chol(bnr_exec &x, int s, hipStream_t st, int rec_p = -1, hipE
 static int chol_launches(const bnr_exec &x)
 {
     const int nbk = x.shape->n_pad / BNR_NB;
-    return (x.factor_variant == 2 || x.factor_variant == 3 || (x.factor_variant < 0 && two_panel_default(x))) ? nbk / 2 : nbk;
+    return two_panel(x) ? nbk / 2 : nbk;
 }
 // Ordering the scalar branch behind points of the critical chain pays where the factorization is the longer of the two chains behind the Gram by a margin (each
 // edge costs the waiting queue ~9 us in a replayed graph): measured per sweep, edges on / off (profiles/round6_experiments_notes.txt A) -- headline shape one chain
@@ -1031,9 +950,6 @@ static void launch_backproj(bnr_exec &x, int s, int flags)
 }
 static void launch_tail(bnr_exec &x, int s, int mask, int xg_src, unsigned wgs = 1)
 {
-#ifdef BNR_EXP_PAD
-    { static const int pad = getenv("BNR_EXP_TAIL_PAD_US") ? atoi(getenv("BNR_EXP_TAIL_PAD_US")) : 0; if (mask == 1023) xg_src |= pad << 8; }
-#endif
     const size_t rv = (size_t)x.shape->R * x.shape->V;
     const size_t lds_a = (mask & BNR_TAIL_EARLY) ? tail_a_bytes(x) : 0;       // Delta / M / inv(M) asked for here (hooks, a loaded row): bnr_tail_a's work matrices behind u
     if (rv <= BNR_TAIL_U_LDS) { BNR_LAUNCH(k_tail, dim3(wgs, 1, x.nb), dim3(BNR_TAIL_THREADS), rv * sizeof(double) + lds_a, x.stream, x, s, mask, xg_src); return; }
@@ -1078,9 +994,7 @@ static void launch_sweep(bnr_exec &x, int s, bool prev_tail)
     const bool timed = x.profiling != 0;
     const bool overlap = x.overlap != 0;
     hipStream_t sb = overlap ? x.stream2 : x.stream;
-    const bool pipe = pipelined(x);
-    hipEvent_t ej[3] = {nullptr, nullptr, nullptr};
-    (void)pipe;
+    hipEvent_t ej = nullptr;
     if (overlap) {
         hipEvent_t ef = next_event(x);
         HIPNOTE(hipEventRecord(ef, x.stream));
@@ -1090,7 +1004,7 @@ static void launch_sweep(bnr_exec &x, int s, bool prev_tail)
         if (tail_after(x) == 0 && prev_tail) { HIPNOTE(hipEventRecord(eg = next_event(x), x.stream2)); }
         if (node_after(x) >= 0) en = next_event(x);
         launch_chol(x, s, sb, node_after(x), en);
-        HIPNOTE(hipEventRecord(ej[0] = next_event(x), x.stream2));
+        HIPNOTE(hipEventRecord(ej = next_event(x), x.stream2));
         // the scalar branch is ordered behind points of the critical chain (see bnr_exec::tail_after / node_after)
         if (eg) HIPNOTE(hipStreamWaitEvent(x.stream, eg, 0));
         if (prev_tail) launch_full_tail(x, s - 1);
@@ -1100,7 +1014,7 @@ static void launch_sweep(bnr_exec &x, int s, bool prev_tail)
     launch_node(x, s, 3);
     launch_xpass(x, s, 3);
     launch_rhs(x, s);
-    if (overlap) { for (hipEvent_t e : ej) if (e) HIPNOTE(hipStreamWaitEvent(x.stream, e, 0)); }
+    if (overlap) { if (ej) HIPNOTE(hipStreamWaitEvent(x.stream, ej, 0)); }
     else { launch_gram(x, s, sb, timed); launch_chol(x, s, sb); }
     launch_solve(x);
     launch_backproj(x, s, split_sums(x) ? 3 : 7);
@@ -1138,7 +1052,6 @@ static int capture_sweeps(bnr_exec &x, int K, hipGraph_t *graph, hipGraphExec_t 
 // Built here, outside anybody's timed region.
 static int exec_prepare(bnr_exec &x)
 {
-    if (wants_qlist(x)) { int rq = build_qlist(x); if (rq) return rq; }
     if (!x.use_graph || x.profiling || x.graph_k <= 0 || !x.ladder.empty()) return BNR_OK;
     for (int k = x.graph_k; k >= 1; k /= 2) {
         bnr_exec::rung r{k, nullptr, nullptr};
@@ -1152,7 +1065,6 @@ static int exec_prepare(bnr_exec &x)
 static int launch_range(bnr_exec &x, int count)
 {
     int done = 0;
-    if (wants_qlist(x)) { int rq = build_qlist(x); if (rq) return rq; }
     if (x.use_graph && !x.profiling && x.graph_k > 0) {     // profiling records HIP events around k_gram: eager launches
         int rc = exec_prepare(x);
         if (rc) return rc;
@@ -1283,7 +1195,6 @@ static int run_exec(bnr_exec &x, int first_index, int count, int prog_freq, bnr_
 {
     int rc;
     hipLaunchKernelGGL(k_setbase, dim3(x.nb), dim3(1), 0, x.stream, (const bnr_dev *)x.cds, 1);
-    if (x.lflags) HIPCHK(hipMemsetAsync(x.lflags, 0, sizeof(unsigned long long) * 64, x.stream));
     x.t_gram_acc = 0; x.n_gram = 0; x.n_replayed = 0; x.n_eager = 0;
     hipEvent_t r0 = nullptr, r1 = nullptr;
     if (x.profiling) { HIPCHK(hipEventCreate(&r0)); HIPCHK(hipEventCreate(&r1)); HIPNOTE(hipEventRecord(r0, x.stream)); }
@@ -2694,7 +2605,7 @@ int bnr_chain_debug_time_gram(bnr_chain *c, int32_t reps, double *avg_us)
     HIPNOTE(hipEventRecord(e0, c->x.stream));
     for (int r = 0; r < reps; ++r) launch_gram_only(c);
     HIPNOTE(hipEventRecord(e1, c->x.stream));
-    HIPCHK(hipMemsetAsync(c->d.gprog, 0, sizeof(unsigned int) * (c->d.ntile + 1), c->x.stream));   // these launches were not consumed by a factorization
+    HIPCHK(hipMemsetAsync(c->d.gprog, 0, sizeof(unsigned int) * (c->d.ntile + 1), c->x.stream));   // (vestigial: nothing counts into gprog any more, so this zeroes zeros; it goes with the descriptor member)
     HIPCHK(hipMemsetAsync(c->d.counters + 9, 0, sizeof(long long), c->x.stream));      // ... nor by a solve: a flag k_sdigits raised is not a gamma update's failure
     HIPCHK(hipStreamSynchronize(c->x.stream));
     float ms = 0;

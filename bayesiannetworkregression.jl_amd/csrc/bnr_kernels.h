@@ -75,11 +75,12 @@ struct bnr_dev {
                                  // [9] the G + I factorization of the running gamma update failed (bnr_flag_gfail; counted once by k_solve_w)
     unsigned long long *dbg;     // in-kernel s_memtime stamps (diagnostics only; never read by any kernel)
     unsigned int *stamp;         // one word per k_gram_reduce workgroup: iteration id of the Gram it finished (checked by k_chol_step)
-    unsigned int *gprog;         // Gram progress: [tc] = finished (tile, K slice) tasks of tile column tc of the running sweep (read by
-                                 // k_chol_ll, zeroed by its last launch); [ntile] = task queue head of k_gram8p; [ntile + 1] = sticky "a gate timed out"
-    const int *gmapc;            // k_gram8p: task list in tile-COLUMN order (tile | ks << 16): the factorization consumes G column by column
-    unsigned int *dfctl;         // (experiments build only, else null) data-flow factorization (k_chol_df): [0] epoch (one more per Gram launch), [1] XCDs its workgroups ran on (bit mask),
-                                 // [32 + 32 q + block row] = epoch when block (block row, q) of the factor is in E
+    // Left from the factorization experiments of rounds 3-4 (tools/experiments/), read by no kernel: gprog = ntile + 4 words that k_gram_reduce and launch 0 of
+    // k_chol_step zero every sweep; gmapc, dfctl = always null.  They stay in the descriptor because taking them (and the two stores) out changes the register
+    // allocation of k_chol_step and k_gram_reduce (profiles/sweep_cleanup_codeobject.txt): that wants a timing of its own.
+    unsigned int *gprog;
+    const int *gmapc;
+    unsigned int *dfctl;
 };
 
 // How a sweep kernel finds its chain.  One chain: the struct travels by value in the kernel arguments (no dependent
@@ -141,8 +142,6 @@ struct bnr_few {
 // is one per failed gamma update whatever the family, the number of panels that see the bad pivot or the group the chain runs in.
 __device__ __forceinline__ void bnr_flag_gfail(const bnr_dev &cd) { atomicOr((unsigned long long *)&cd.counters[9], 1ull); }
 
-#define BNR_EXP_SKIP_SCALAR() 0
-#define BNR_EXP_SKIP_CHOL(p) 0
 enum { ROW_TAU2 = 0, ROW_THETA = 1, ROW_DELTA = 2, ROW_MU = 3 };
 enum { SC_RR = 0, SC_SIGQ = 1, SC_TAU = 2, SC_TAU2N = 3, SC_TAU2N_IT = 4, SC_I8SCALE = 8 };   // TAU2N: tau2 pre-drawn by k_tail for iteration id TAU2N_IT
 
@@ -302,10 +301,6 @@ __global__ __launch_bounds__(64) void k_node(const SRC chain_src, int s, int mod
     const bnr_plan_entry P = cd.plan[cd.pbase[0] + s];
     double *row = cd.trace + (size_t)P.row * cd.rowlen;
     const double *prev = cd.trace + (size_t)P.prev * cd.rowlen;
-    if (BNR_EXP_SKIP_SCALAR()) {
-        if (k == 0) { for (int i = lane; i < cd.o_gamma; i += 64) row[i] = prev[i]; if (lane == 0) cd.scal[SC_TAU] = sqrt(prev[ROW_TAU2]); }
-        return;
-    }
 #ifdef BNR_STAMPS
     if (lane == 0 && k < 256) {                           // diagnostics: when did this node's wave start / finish its sums / end, and on which XCD
         unsigned v; asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(v));
@@ -686,7 +681,6 @@ __global__ __launch_bounds__(256) void k_xpass(const SRC chain_src, int s, int w
     const int bid = (gr / nchains) * 8 + gx;
     const bnr_dev &cd = chain_src.at(gr % nchains);
     if (bid >= cd.nblk_x) return;
-    if (BNR_EXP_SKIP_SCALAR() && which == 3) return;
     BNR_TL_IN(cd, TL_XPASS, bid == 0);
     double *sW = sh, *sZ = sh + cd.chunk_x, *sG = sh + 2 * cd.chunk_x;
     const bnr_plan_entry P = cd.plan[cd.pbase[0] + s];
@@ -738,7 +732,6 @@ __global__ __launch_bounds__(256) void k_xpass(const SRC chain_src, int s, int w
 //   grid = nblk_x x ceil(n_pad / 256), 256 threads, dynamic LDS = 2 x 8 x chunk_x doubles.
 __global__ __launch_bounds__(256) void k_xpass_group(const bnr_many chain_src, int s, int nchains)
 {
-    if (BNR_EXP_SKIP_SCALAR()) return;
     extern __shared__ double sh[];
     const int wg = blockIdx.x;
     const bnr_dev &c0 = chain_src.at(0);                  // the geometry and the shared X, index maps
@@ -822,7 +815,7 @@ __device__ __forceinline__ double bnr_bufload_f64(__amdgpu_buffer_rsrc_t r, unsi
 }
 // A Gram workgroup has stored its partial tile: count it for the tile's column (the factorization checks the count before its
 // first read of the column).  k_gram / k_gram8 are consumed after the kernel boundary: one relaxed atomic, no fence.
-// Only the left-looking / pipelined factorization experiments of rounds 3-4 read the counts (tools/experiments/): the library does not
+// Only the factorization experiments of rounds 3-4 that ran beside the Gram read the counts (tools/experiments/): the library does not
 // count at all (round 3 did, on every launch: one agent-scope atomic per workgroup on 8 words per chain).
 __device__ __forceinline__ void bnr_gram_count(const bnr_dev &cd, int tj)
 {
@@ -848,10 +841,6 @@ __host__ __device__ inline long long bnr_gram_span_bytes(int n_pad, int kchunk, 
                                       // block of a diagonal tile (its two waves only stage: 5.6 % of the launch's MFMAs at ntile = 8; 8 chains 216.5 ->
                                       // 212.6 us per launch, 401.7 -> 396.6 us per sweep) and the upper 16 x 16 tile of a diagonal block (3 MFMAs per
                                       // k-step instead of 4 in the diagonal waves); zeros are written there, nobody reads them
-#endif
-
-#ifndef BNR_GRAM_EXP
-#define BNR_GRAM_EXP 0        // timing experiments only (tools/gram_experiments.sh): 1 no S scaling, 2 no global loads in the loop, 3 both
 #endif
 
 // LDS-staged K loop.  Per K-group (4 waves = 256 threads) and batch of 16 columns: the j-side panel X[j-rows, 16 cols] and
@@ -924,20 +913,16 @@ __device__ __forceinline__ void bnr_gram16_task(const bnr_gram_geom &cd, const d
     const int bstep = BNR_GRAM_KB * (int)ld * 8;                       // bytes per batch (scalar)
 #define BNR_GRAM_LOAD(BIDX)                                                                               \
     do {                                                                                                  \
-        const bool keep_ = (BNR_GRAM_EXP & 2) && (BIDX) > 1;                                              \
-        const int so_ = (keep_ ? 0 : (BIDX)) * bstep;                                                     \
-        if (!(BNR_GRAM_EXP & 1)) { sv0 = bnr_bufload_f64(rS, offS, (BIDX) * (BNR_GRAM_KB * 8)); sv1 = bnr_bufload_f64(rS, offS + 64u, (BIDX) * (BNR_GRAM_KB * 8)); } \
-        else { sv0 = 1.0; sv1 = 1.0; }                                                                    \
-        if (!keep_) {                                                                                     \
-            ri0 = bnr_bufload_d2(rX, offI, so_); ri1 = bnr_bufload_d2(rX, offI + off8, so_);              \
-            rj0 = bnr_bufload_d2(rX, offJ, so_); rj1 = bnr_bufload_d2(rX, offJ + off8, so_);              \
-        }                                                                                                 \
+        const int so_ = (BIDX) * bstep;                                                                   \
+        sv0 = bnr_bufload_f64(rS, offS, (BIDX) * (BNR_GRAM_KB * 8)); sv1 = bnr_bufload_f64(rS, offS + 64u, (BIDX) * (BNR_GRAM_KB * 8)); \
+        ri0 = bnr_bufload_d2(rX, offI, so_); ri1 = bnr_bufload_d2(rX, offI + off8, so_);                  \
+        rj0 = bnr_bufload_d2(rX, offJ, so_); rj1 = bnr_bufload_d2(rX, offJ + off8, so_);                  \
     } while (0)
 #define BNR_GRAM_STORE(BUF)                                                                               \
     do {                                                                                                  \
         double *nx_ = stg + (size_t)(BUF) * (2 * PANEL);                                                  \
-        *(bnr_d2 *)(nx_ + woff) = (BNR_GRAM_EXP & 1) ? ri0 : ri0 * sv0;                                   \
-        *(bnr_d2 *)(nx_ + 8 * BNR_GT + woff) = (BNR_GRAM_EXP & 1) ? ri1 : ri1 * sv1;                      \
+        *(bnr_d2 *)(nx_ + woff) = ri0 * sv0;                                                          \
+        *(bnr_d2 *)(nx_ + 8 * BNR_GT + woff) = ri1 * sv1;                                             \
         *(bnr_d2 *)(nx_ + PANEL + woff) = rj0;                                                            \
         *(bnr_d2 *)(nx_ + PANEL + 8 * BNR_GT + woff) = rj1;                                               \
     } while (0)
@@ -1435,8 +1420,8 @@ __global__ __launch_bounds__(256) void k_gram_reduce(const SRC chain_src, int s)
 //   role A (nbk + 2 panel workgroups): apply panel p-1's update to the blocks (p,p) and (rho,p) by f64 MFMA (operands
 //       loaded from L2 straight in fragment layout), then ONE wavefront sweeps the 64 x 32 register-resident panel
 //       [E_pp ; E_rho,p] column by column: pivot chain on scalars, rsqrt = v_rsq_f64 + one third-order step, rank-1 updates of
-//       the next two columns with v_readlane broadcasts, of the remaining columns one step later with LDS broadcast reads
-//       (software pipelined so that the LDS latency hides behind the next pivot's rsqrt chain).
+//       the next two columns with v_readlane broadcasts, of the remaining columns one step later with the previous column's
+//       multipliers, also by v_readlane (bnr_sweep16).
 //       Lanes 0-31 redo the diagonal block in every workgroup: no cross-workgroup hand-off inside a launch.
 //   role B (update workgroups): E[rho,j] -= L[rho,p-1] L[j,p-1]' for every block column j >= p+1, by f64 MFMA.
 // k_solve_gemv: a4 = Y w, then the n-vector bookkeeping for X gamma_new.
@@ -1489,16 +1474,11 @@ __device__ __forceinline__ bnr_d4 bnr_tile_update(const double *colrows, const d
 }
 
 // Register-resident sweep of 16 panel columns, lane = row (64 rows): column j's pivot sits in lane COFF + j.
-// Software pipelined: the next two columns are updated at once through v_readlane broadcasts, the remaining ones one step
-// later with LDS broadcast reads of the published column (sCol, double buffered), so that the LDS latency hides behind the
-// next pivot's rsqrt chain.  (Measured on gfx950: a ds_write is NOT ordered before later ds_reads of the same wave
-// without an s_waitcnt.)
-#ifndef BNR_SWEEP_RL
-#define BNR_SWEEP_RL 1
-#endif
+// The next two columns are updated at once through v_readlane broadcasts, the remaining ones one step later, their
+// multipliers taken from the previous column's register by v_readlane as well (no LDS round trip per pivot).
 #define BNR_L1S 80            // LDS column stride of the 64 x 16 half-panel handed to the MFMA update (conflict-free fragments)
 template <int COFF, bool PUB = false>
-__device__ __forceinline__ int bnr_sweep16(double (&a)[16], int lane, double (*sCol)[BNR_NB], double *pub = nullptr)
+__device__ __forceinline__ int bnr_sweep16(double (&a)[16], int lane, double *pub = nullptr)
 {
     int bad = 0;
     double lprev = 0.0;
@@ -1515,23 +1495,15 @@ __device__ __forceinline__ int bnr_sweep16(double (&a)[16], int lane, double (*s
         if (j + 1 < 16) { s1 = bnr_readlane(a[j + 1], COFF + j + 1); s2 = bnr_readlane(a[j], COFF + j + 1); }
         if (j + 2 < 16) s3 = bnr_readlane(a[j], COFF + j + 2);
         if (!(piv > 0.0)) bad = 1;                       // not positive definite: NaNs from here on, reported by the caller
-        // the reciprocal square root is started BEFORE the wait for the previous column's LDS write: the wave issues in
-        // order, so the v_rsq_f64 (quarter rate, long latency) runs while the LDS round trip completes
+        // the reciprocal square root is started first: the wave issues in order, so the v_rsq_f64 (quarter rate, long latency)
+        // runs while the broadcasts below are read
         double y = __builtin_amdgcn_rsq(piv);
-#if BNR_SWEEP_RL
         // the multipliers l_{k,j-1} of the lagged update come from the previous column's register by v_readlane (wave-uniform scalars):
         // no LDS write -> wait -> read round trip per pivot
         if (j >= 1) {
 #pragma unroll
             for (int k = j + 2; k < 16; ++k) tk[k] = bnr_readlane(lprev, COFF + k);
         }
-#else
-        if (j >= 1) {
-            asm volatile("s_waitcnt lgkmcnt(0)" :: "v"(y) : "memory");
-#pragma unroll
-            for (int k = j + 2; k < 16; ++k) tk[k] = sCol[(j - 1) & 1][COFF + k];
-        }
-#endif
         // v_rsq_f64 is good to 2^-24 (tools/rsq_precision.hip); ONE third-order step y (1 + e/2 + 3 e^2/8), e = 1 - x y^2,
         // gives 1.2 ulp -- what two Newton steps give -- in 5 instead of 8 operations and depth 4 instead of 6
         const double e = fma(-(piv * y), y, 1.0);
@@ -1543,24 +1515,17 @@ __device__ __forceinline__ int bnr_sweep16(double (&a)[16], int lane, double (*s
         if (PUB) pub[j * BNR_L1S + lane] = lj;             // the finished column goes to LDS at once (an LDS write costs the chain nothing) instead of 16 writes behind the sweep
         if (j + 1 < 16) a[j + 1] = fma(-lj, t1, a[j + 1]);
         if (j + 2 < 16) a[j + 2] = fma(-lj, s3 * rinv, a[j + 2]);
-#if !BNR_SWEEP_RL
-        if (lane < 32) sCol[j & 1][lane] = lj;
-#endif
         if (j >= 1) {
 #pragma unroll
             for (int k = j + 2; k < 16; ++k) a[k] = fma(-lprev, tk[k], a[k]);
         }
         lprev = lj;
     }
-#if !BNR_SWEEP_RL
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#endif
     return bad;
 }
 
 struct bnr_panel_lds {
     double sD[BNR_NB * BNR_LP], sB[BNR_NB * BNR_LP];
-    double sCol[2][BNR_NB];
     double sL1[16 * BNR_L1S];
 };
 // Sweep of the 64 x 32 panel [D ; B] by one workgroup of 256 threads: D = updated, unfactored diagonal block, B = own
@@ -1594,7 +1559,7 @@ __device__ __forceinline__ int bnr_panel_sweep(bnr_panel_lds &sh, const bnr_d4 &
 #pragma unroll
         for (int c = 0; c < 16; ++c) a1[c] = src[rr + BNR_LP * c];
         BNR_PH(2);
-        bad = bnr_sweep16<0, true>(a1, lane, sh.sCol, sh.sL1);
+        bad = bnr_sweep16<0, true>(a1, lane, sh.sL1);
         BNR_PH(3);
     }
     __syncthreads();
@@ -1624,7 +1589,7 @@ __device__ __forceinline__ int bnr_panel_sweep(bnr_panel_lds &sh, const bnr_d4 &
 #pragma unroll
         for (int c = 0; c < 16; ++c) a2[c] = src[rr + BNR_LP * (16 + c)];
         BNR_PH(6);
-        bad |= bnr_sweep16<16>(a2, lane, sh.sCol);
+        bad |= bnr_sweep16<16>(a2, lane);
         BNR_PH(7);
         // the swept own block goes to E straight from the sweeping wave's registers (lane = row: 32 coalesced 256-byte stores; the
         // LDS hand-back + barrier + store by all four waves cost ~1000 cycles at the end of every panel step); the factored
@@ -2103,7 +2068,6 @@ __global__ __launch_bounds__(256, 1) void k_chol_step(const SRC chain_src, int p
 #ifdef BNR_STAMPS
     const unsigned long long t_entry = __builtin_amdgcn_s_memtime();       // before anything is read, the kernel's arguments included
 #endif
-    if (BNR_EXP_SKIP_CHOL(p)) return;
     const bnr_dev &cd = chain_src.get_x();               // grid = (chains, workgroups): blockIdx.x = chain, blockIdx.y = workgroup
 #if BNR_PANEL_PIPE
     __shared__ bnr_panelp_lds sh;
@@ -2324,7 +2288,7 @@ __global__ __launch_bounds__(256, 1) void k_chol_step(const SRC chain_src, int p
     BNR_STAMP(3);
     BNR_STAMP(4);
 #ifdef BNR_STAMPS
-    if (lane == 0) atomicMax((unsigned long long *)&cd.dbg[p * 8 + 5], (unsigned long long)__builtin_amdgcn_s_memrealtime());      // (every wave: with the pipelined sweep wave 3 is the last one)
+    if (lane == 0) atomicMax((unsigned long long *)&cd.dbg[p * 8 + 5], (unsigned long long)__builtin_amdgcn_s_memrealtime());      // (every wave: with the four-wave sweep, bnr_panel_sweep_pipe, wave 3 is the last one)
     if (b == 0 && tid == 192 && p < 48) { cd.dbg[3900 + 2 * p] = __builtin_amdgcn_s_memrealtime(); cd.dbg[3901 + 2 * p] = __builtin_amdgcn_s_memtime(); }      // the LAST wave of panel workgroup 0 on both clocks (tools/stamps_steps.py: which clock do the panel steps run at?)
 #endif
 }
@@ -2344,7 +2308,7 @@ __global__ __launch_bounds__(256, 1) void k_chol_step(const SRC chain_src, int p
 //     previous launch's two panels, beside role A (look-ahead as before).
 struct bnr_panel2_lds {
     double sDaa[BNR_NB * BNR_LP], sDba[BNR_NB * BNR_LP], sDbb[BNR_NB * BNR_LP], sOa[BNR_NB * BNR_LP], sOb[BNR_NB * BNR_LP];
-    double sCol[2][2][BNR_NB];
+    double pad_[2][2][BNR_NB];          // unread (once the lagged multipliers of bnr_sweep16 travelled through it): kept so that sL1 and with it the ds offsets of k_chol_step2 stay where they are
     double sL1[2][16 * BNR_L1S];
 };
 // one half-sweep helper: registers <- LDS panel [D ; B] (lane = row), columns c0..c0+15
@@ -2540,7 +2504,7 @@ __global__ __launch_bounds__(256, 1) void k_chol_step2(const SRC chain_src, int 
     double *sBw = wave == 0 ? sh.sOa : sh.sDba;
     if (wave < 2) {
         bnr_panel_load16(a1, sh.sDaa, sBw, lane, 0);
-        bad = bnr_sweep16<0>(a1, lane, sh.sCol[wave]);
+        bad = bnr_sweep16<0>(a1, lane);
 #pragma unroll
         for (int c = 0; c < 16; ++c) sh.sL1[wave][c * BNR_L1S + lane] = a1[c];
     }
@@ -2555,7 +2519,7 @@ __global__ __launch_bounds__(256, 1) void k_chol_step2(const SRC chain_src, int 
     __syncthreads();
     if (wave < 2) {
         bnr_panel_load16(a2, sh.sDaa, sBw, lane, 16);
-        bad |= bnr_sweep16<16>(a2, lane, sh.sCol[wave]);
+        bad |= bnr_sweep16<16>(a2, lane);
         if (lane >= 32) {
 #pragma unroll
             for (int c = 0; c < 16; ++c) { sBw[rr + BNR_LP * c] = a1[c]; sBw[rr + BNR_LP * (16 + c)] = a2[c]; }
@@ -2572,7 +2536,7 @@ __global__ __launch_bounds__(256, 1) void k_chol_step2(const SRC chain_src, int 
     // 3. panel b: wave 0 on [Dbb ; Ob], the second half updated by all four waves
     if (wave == 0) {
         bnr_panel_load16(a1, sh.sDbb, sh.sOb, lane, 0);
-        bad |= bnr_sweep16<0>(a1, lane, sh.sCol[0]);
+        bad |= bnr_sweep16<0>(a1, lane);
 #pragma unroll
         for (int c = 0; c < 16; ++c) sh.sL1[0][c * BNR_L1S + lane] = a1[c];
     }
@@ -2581,7 +2545,7 @@ __global__ __launch_bounds__(256, 1) void k_chol_step2(const SRC chain_src, int 
     __syncthreads();
     if (wave == 0) {
         bnr_panel_load16(a2, sh.sDbb, sh.sOb, lane, 16);
-        bad |= bnr_sweep16<16>(a2, lane, sh.sCol[0]);
+        bad |= bnr_sweep16<16>(a2, lane);
         if (lane >= 32) {
 #pragma unroll
             for (int c = 0; c < 16; ++c) { sh.sOb[rr + BNR_LP * c] = a1[c]; sh.sOb[rr + BNR_LP * (16 + c)] = a2[c]; }
@@ -2607,7 +2571,6 @@ __global__ __launch_bounds__(256, 1) void k_chol_step2(const SRC chain_src, int 
 template <class SRC>
 __global__ __launch_bounds__(256) void k_rhs(const SRC chain_src, int s)
 {
-    if (BNR_EXP_SKIP_SCALAR()) return;
     const bnr_dev &cd = chain_src.get();
     __shared__ double sw[4][64], sa[4][64];
     const bnr_plan_entry P = cd.plan[cd.pbase[0] + s];
@@ -2934,7 +2897,6 @@ __global__ __launch_bounds__(BNR_TAIL_THREADS) void k_tail(const SRC chain_src, 
     __shared__ int sflag[2];
     const bnr_plan_entry P = cd.plan[cd.pbase[0] + s];
     if (P.wrap & 2) return;                      // placeholder entry in front of the first sweep of a run
-    if (BNR_EXP_SKIP_SCALAR() && mask == 1023) return;
     // (the row pointers are the same for the whole workgroup: pinned to scalar registers -- as vector values they lived through the whole
     // kernel, and the register allocator spilled them and the thread id around the inlined samplers: 32 bytes of scratch per lane in round 3)
     double *row = bnr_sgpr_global(cd.trace + (size_t)P.row * cd.rowlen);
@@ -3141,13 +3103,6 @@ __global__ __launch_bounds__(BNR_TAIL_THREADS) void k_tail(const SRC chain_src, 
     BNR_TSTAMP(6);
     if (gridDim.x == 2) BNR_TL_OUT(cd, TL_TAIL);
     if (cap) atomicAdd((unsigned long long *)&cd.counters[2], 1ull);
-#ifdef BNR_EXP_PAD
-    // timing experiment only (never in the shipped build): the kernel ends xg_src >> 8 microseconds later, to move the start of what follows it on the scalar branch
-    if ((xg_src >> 8) > 0 && tid == 0) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime(), dt = (unsigned long long)(xg_src >> 8) * 100ull;
-        while (__builtin_amdgcn_s_memrealtime() - t0 < dt) __builtin_amdgcn_s_sleep(8);
-    }
-#endif
 }
 
 // advances the plan base after a batch of sweeps (last node of the captured graph)
@@ -3474,7 +3429,6 @@ __device__ __forceinline__ void bnr_xg_dispatch(int nc, const XT *xp, size_t ld,
 template <int LATE>     // (a template only so that the kernel is emitted behind the others, with the instantiations: see the note above)
 __global__ __launch_bounds__(256) void k_xpass_group2(const bnr_many chain_src, int s, int nchains)
 {
-    if (BNR_EXP_SKIP_SCALAR()) return;
     extern __shared__ double sh[];
     const int wg = blockIdx.x;
     const bnr_dev &c0 = chain_src.at(0);                  // the geometry and the shared X, index maps

@@ -399,7 +399,8 @@ int bnr_debug_set_exp(int32_t device, int32_t flags);
  *               two rounds of workgroups keep k_backproj, whose draws have the shorter latency); 1: always; 0: never.  Bitwise the same tables.
  *   Experiments ("nop_fork", "pipeline", "gate_us", "linear", "linear_merge", "linear_debug", "group_backproj", "resv_mask", "crit_origin"; rounds 3-4,
  *               profiles/round*_experiments_notes.txt): all measured no faster, part of them polled device memory.  Removed from the tree in
- *               round 5 (tools/experiments/README.md): the library refuses them by name.
+ *               round 5 (tools/experiments/README.md): the library refuses them by name.  Their host scaffolding (streams, fields and
+ *               predicates of the sweep's issue path) is gone too; what is left of them in csrc/ is listed in DESIGN.md, section 3.
  *   "predict_block_rows" (chains only) rows per block of bnr_chain_predict / bnr_chain_loglik_stats, whose work buffer holds rows x nsamp
  *               doubles; rounded up to whole 32-row tiles.  0 (default): as many rows as fit in about 1 GiB.  The results are bitwise the same
  *               for every value.
