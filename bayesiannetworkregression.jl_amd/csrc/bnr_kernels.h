@@ -3283,8 +3283,13 @@ __global__ void k_rhat_stats(bnr_dev cd, int first, int nsamp, double *out)
 // `buf` holds the window transposed by k_fetch_cols: column p (gamma_0..gamma_{q-1}, then xi_0..xi_{V-1}) is contiguous,
 // nsamp doubles.  One workgroup of 256 threads per column.  Exact selection by MSD radix counting on the order-preserving
 // 64-bit image of the doubles: 6 passes (11,11,11,11,11,9 bits) of a 2048-bin LDS histogram per statistic.
+// The order is the one the reference's sort uses (Julia's isless) and numpy's: numbers by value (-Inf first, +Inf last; -0 below +0, which
+// compare equal), then every NaN, whatever its sign or payload.  All NaNs share the top key, so a rank that falls among them reports a NaN
+// (the one bnr_double_of makes of the top key), and the sign-bit NaNs x86 produces (inf - inf, 0 / 0) in a loaded table cannot sort below the
+// numbers as their bit image would.  NaN-free columns get the same keys as before.
 __device__ __forceinline__ unsigned long long bnr_key_of(double v)
 {
+    if (v != v) return ~0ull;
     unsigned long long u = (unsigned long long)__double_as_longlong(v);
     return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
 }
