@@ -85,6 +85,10 @@ _SIGS = {
     "bnr_chain_loo_predict": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp, C.c_double, C.c_double] + [_dp] * 8),
     "bnr_chains_loo_predict": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, _dp, C.c_double, C.c_double] + [_dp] * 8),
     "bnr_psis_weights": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp]),
+    "bnr_chain_rank_diag": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 6),
+    "bnr_chains_rank_diag": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 6),
+    "bnr_rank_normalize": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
+    "bnr_host_ndtri": (C.c_double, [C.c_double]),
     "bnr_comm_unique_id": (C.c_int, [C.POINTER(UniqueId)]),
     "bnr_comm_create_rccl": (C.c_int, [C.POINTER(UniqueId), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "bnr_comm_create_callback": (C.c_int, [C.c_int32, C.c_int32, ALLGATHER_CB, C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -261,6 +265,34 @@ def loo_probs(p_lo, p_hi):
 
 
 LOO_PREDICT_FIELDS = ("lpd", "elpd_loo", "pareto_k", "loo_mean", "loo_sd", "loo_pit", "loo_lower", "loo_upper")
+
+
+RANK_DIAG_FIELDS = ("rhat_bulk", "rhat_tail", "ess_bulk", "ess_tail", "ess_mean", "mcse_mean")
+
+
+def host_ndtri(p):
+    """Phi^-1 as the rank kernel evaluates it (bnr_host_ndtri: Wichura's AS 241, PPND16; no GPU), elementwise"""
+    f = lib().bnr_host_ndtri
+    a = np.asarray(p, dtype=np.float64)
+    return np.array([f(v) for v in a.reshape(-1).tolist()], dtype=np.float64).reshape(a.shape)
+
+
+def rank_normalize_raw(x, device=0, ranks=True, z=True):
+    """(ranks, z) of every row of an m x S matrix, each row ranked on its own, on the device (bnr_rank_normalize): average ranks (ties share the
+    mean of their positions) and z = Phi^-1((r - 3/8) / (S + 1/4)); the one not asked for is None"""
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("x must be an m x S matrix (rows x draws) with m, S >= 1")
+    if not (ranks or z):
+        raise ValueError("ask for the ranks, z or both")
+    m, S = a.shape
+    r = np.empty((m, S)) if ranks else None
+    zz = np.empty((m, S)) if z else None
+    L = lib()
+    if _foreign_hip:
+        raise BnrError(BNR_ERR_HIP, _foreign_hip)
+    check(L.bnr_rank_normalize(int(device), m, S, _ptr(a), _ptr(r), _ptr(zz)))
+    return r, zz
 
 
 X_DTYPES = {np.dtype(np.float64): 0, np.dtype(np.bool_): 1, np.dtype(np.uint8): 1, np.dtype(np.int32): 2, np.dtype(np.int64): 3,
@@ -490,6 +522,14 @@ class Chain:
         check(self.L.bnr_chain_ess_stats(self.h, first_row, nsamp, max_lag, _ptr(out)))
         return out
 
+    def rank_diag(self, first_row, nsamp, max_lag, fields=None):
+        """The rank-normalised diagnostics of this chain's window, on the device (bnr_chain_rank_diag): the tuple RANK_DIAG_FIELDS, each q + V
+        values (gamma first); an entry not named in `fields` is not requested and comes back as None"""
+        fields = RANK_DIAG_FIELDS if fields is None else fields
+        out = [np.empty(self.q + self.V) if f in fields else None for f in RANK_DIAG_FIELDS]
+        check(self.L.bnr_chain_rank_diag(self.h, int(first_row), int(nsamp), int(max_lag), *[_ptr(o) for o in out]))
+        return tuple(out)
+
     def counters(self):
         out = (C.c_int64 * 8)()
         check(self.L.bnr_chain_counters(self.h, out))
@@ -669,6 +709,16 @@ def pooled_loo_predict(chains, first_row, nsamp, r_eff=None, p_lo=0.025, p_hi=0.
     r = r_eff_array(r_eff, n)
     out = [np.empty(n) if f in fields else None for f in LOO_PREDICT_FIELDS]
     check(chains[0].L.bnr_chains_loo_predict(arr, len(chains), int(first_row), int(nsamp), _ptr(r), p_lo, p_hi, *[_ptr(o) for o in out]))
+    return tuple(out)
+
+
+def pooled_rank_diag(chains, first_row, nsamp, max_lag, fields=None):
+    """Chain.rank_diag over the pooled window of `chains` (bnr_chains_rank_diag): the tuple RANK_DIAG_FIELDS"""
+    chains, arr = _pooled(chains)
+    c0 = chains[0]
+    fields = RANK_DIAG_FIELDS if fields is None else fields
+    out = [np.empty(c0.q + c0.V) if f in fields else None for f in RANK_DIAG_FIELDS]
+    check(c0.L.bnr_chains_rank_diag(arr, len(chains), int(first_row), int(nsamp), int(max_lag), *[_ptr(o) for o in out]))
     return tuple(out)
 
 

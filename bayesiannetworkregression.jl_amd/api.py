@@ -17,7 +17,9 @@ Julia is not available in this image, so the thin host layer a Julia user would 
   Summary                gibbs.jl:1214-1250 -> Summary
   (additions)                               -> Predict / BNRPrediction (posterior of the mean response of new rows), WAIC, LOO / psis_loo;
                                                pooled chains, predictive intervals and PIT: device_*_pooled, _host_pooled_*;
-                                               LOO predictive checks: LOOPredict / LOOPredictive, psis_weights, device_loo_predict
+                                               LOO predictive checks: LOOPredict / LOOPredictive, psis_weights, device_loo_predict;
+                                               rank-normalised R-hat / ESS / MCSE: RankDiagnose / RankDiagnostics, rank_normalize,
+                                               device_rank_diagnostics, _host_rank_diagnostics
   lower_triangle / create_lower_tri / setup_X!  utils.jl:17-57, gibbs.jl:239-247
 
 All sampling runs on the GPU through libbnr_hip.so; this file holds only the schedule logic (chain fan-out,
@@ -94,6 +96,7 @@ class Results:
     waic: dict = None                # filled on request (waic=True): WAIC of the training rows from the GPU's pointwise numbers (see WAIC)
     loo: dict = None                 # filled on request (loo=True): PSIS-LOO of the training rows computed on the GPU (see LOO)
     loo_predictive: "LOOPredictive" = None   # filled on request (loo_predict=True): the LOO predictive checks of the training rows (see LOOPredict)
+    rank_diag: "RankDiagnostics" = None   # filled on request (rank_diagnostics=True): rank-normalised R-hat, bulk / tail ESS and MCSE over every chain (see RankDiagnose)
     stat_chains: int = None          # how many chains the device statistics above (summary_device, prediction, waic, loo, loo_predictive) cover: 1 (chain 1's window), or
                                      # every chain of the fit with pool_chains=True; None when the fit computed none
 
@@ -391,6 +394,185 @@ def LOO(results, X=None, y=None, x_transform=True, r_eff=None):
     xi = _new_rows(X, x_transform, results.state["gamma"].shape[1], y)
     ll = _host_loglik(results.state, _dense_rows(xi), y, results.burn_in, results.sampled)
     return _loo_from_pointwise(*_psis_host(ll, r_eff), results.sampled)
+
+
+# ------------------------------------------------------------------------------------------ rank-normalised convergence diagnostics (additions)
+# R-hat, bulk / tail effective sample size and MCSE of Vehtari, Gelman, Simpson, Carpenter, Buerkner (2021) as `posterior` 1.x computes them
+# (rhat, ess_bulk, ess_tail, ess_mean, mcse_mean), over the pooled window of the chains of one device (include/bnr_hip.h, ABI 12).  One
+# deviation: rhat = fmax(rhat_bulk, rhat_tail) is NaN only when both are -- binary xi columns often fold to a constant, and `posterior`'s max
+# would turn the whole answer into NA there.  ESS figures equal `posterior`'s whenever Geyer's sequence ends before max_lag.
+RANK_DIAG_FIELDS = _capi.RANK_DIAG_FIELDS
+
+
+@dataclass
+class RankDiagnostics:
+    """Per parameter, gamma (q) and xi (V) apart: rhat = fmax(rhat_bulk, rhat_tail), rhat_bulk (split-R-hat of the normal scores z of the
+    ranks), rhat_tail (the same for |x - median|), ess_bulk (on z), ess_tail (the smaller ESS of the 5 % and 95 % indicators), ess_mean (on x),
+    mcse_mean = sd / sqrt(ess_mean).  draws: the ranked split-chain draws 2 chains (nsamp // 2); max_lag: where Geyer's sequence is cut.
+    NaN throughout for a parameter with a non-finite draw or with all draws equal."""
+    rhat_gamma: np.ndarray
+    rhat_xi: np.ndarray
+    rhat_bulk_gamma: np.ndarray
+    rhat_bulk_xi: np.ndarray
+    rhat_tail_gamma: np.ndarray
+    rhat_tail_xi: np.ndarray
+    ess_bulk_gamma: np.ndarray
+    ess_bulk_xi: np.ndarray
+    ess_tail_gamma: np.ndarray
+    ess_tail_xi: np.ndarray
+    ess_mean_gamma: np.ndarray
+    ess_mean_xi: np.ndarray
+    mcse_mean_gamma: np.ndarray
+    mcse_mean_xi: np.ndarray
+    draws: int
+    chains: int
+    max_lag: int
+
+    def full(self, name):
+        """field `name` ("rhat", or one of RANK_DIAG_FIELDS) of all q + V parameters, gamma first"""
+        return np.concatenate([getattr(self, name + "_gamma"), getattr(self, name + "_xi")])
+
+
+def _rank_lag(nsamp, max_lag):
+    """the lag window of the rank diagnostics (default min(250, nsamp // 4), as ChainSet.ess) with the library's checks as ValueErrors"""
+    nsamp = int(nsamp)
+    max_lag = min(250, nsamp // 4) if max_lag is None else int(max_lag)
+    if nsamp < 8:
+        raise ValueError("the rank diagnostics need nsamp >= 8, not %d" % nsamp)
+    if not (2 <= max_lag <= nsamp // 2):
+        raise ValueError("need 2 <= max_lag <= nsamp // 2, not max_lag = %d with nsamp = %d" % (max_lag, nsamp))
+    return max_lag
+
+
+def _rank_diagnostics(q, fields, nchains, nsamp, max_lag):
+    """RankDiagnostics from the six arrays of q + V values in the order of RANK_DIAG_FIELDS"""
+    f = dict(zip(RANK_DIAG_FIELDS, fields))
+    f["rhat"] = np.fmax(f["rhat_bulk"], f["rhat_tail"])
+    kw = {}
+    for k, v in f.items():
+        kw[k + "_gamma"], kw[k + "_xi"] = v[:q].copy(), v[q:].copy()
+    return RankDiagnostics(draws=2 * nchains * (nsamp // 2), chains=nchains, max_lag=max_lag, **kw)
+
+
+def device_rank_diagnostics(chains, nburn, nsamp, max_lag=None):
+    """The rank-normalised diagnostics over the pooled windows nburn+1 .. nburn+nsamp of live chains, on the device (bnr_chains_rank_diag): only
+    6 (q + V) numbers leave the GPU's side of the call"""
+    chains = list(chains)
+    max_lag = _rank_lag(nsamp, max_lag)
+    out = _capi.pooled_rank_diag(chains, nburn + 1, nsamp, max_lag)
+    return _rank_diagnostics(chains[0].q, out, len(chains), nsamp, max_lag)
+
+
+def _average_ranks(x):
+    """average ranks (1-based; ties share the mean of their positions, -0 ties with +0) and the sorted values of a NaN-free vector"""
+    n = x.size
+    order = np.argsort(x, kind="stable")
+    xs = x[order]
+    head = np.ones(n, dtype=bool)
+    head[1:] = xs[1:] != xs[:-1]
+    starts = np.flatnonzero(head)
+    ends = np.append(starts[1:], n)
+    run = np.cumsum(head) - 1
+    r = np.empty(n)
+    r[order] = (starts[run] + ends[run] + 1) * 0.5
+    return r, xs
+
+
+def _z_scale(x):
+    """the normal scores of the ranks of a NaN-free vector, Phi^-1 by the library's own routine (one call per distinct rank)"""
+    r, xs = _average_ranks(x)
+    ur, inv = np.unique(r, return_inverse=True)
+    return _capi.host_ndtri((ur - 0.375) / (x.size + 0.25))[inv], xs
+
+
+def _split_message(series, L):
+    """k_acov's messages of series (m, h, P) -- m = 2 C split chains in the order chain 0 first half, chain 0 second half, chain 1 ... -- as
+    bnr_ess_from_stats takes them: (C, 2 (2 + L) P), per half the mean, the variance (ddof 1) and the autocovariances at lags 0 .. L-1 (1 / h)"""
+    m, h, P = series.shape
+    out = np.empty((m, 2 + L, P))
+    mean = series.mean(axis=1)
+    c = series - mean[:, None, :]
+    out[:, 0] = mean
+    for t in range(L):
+        out[:, 2 + t] = (c[:, :h - t] * c[:, t:]).sum(axis=1) / h
+    out[:, 1] = out[:, 2] * h / (h - 1)
+    return out.reshape(m // 2, 2 * (2 + L) * P)
+
+
+def _split_rhat(msg, C, L, P, h):
+    """sqrt(((h-1)/h W + B) / W) from the messages: W the mean of the 2 C variances, B the variance (ddof 1) of the 2 C means"""
+    st = msg.reshape(2 * C, 2 + L, P)
+    W = st[:, 1].mean(axis=0)
+    B = st[:, 0].var(axis=0, ddof=1)
+    with np.errstate(all="ignore"):
+        return np.sqrt(((h - 1.0) / h * W + B) / W)
+
+
+def _host_rank_diagnostics(tables, nburn, nsamp, max_lag=None):
+    """device_rank_diagnostics restated in numpy over the fetched tables of the same chains (Phi^-1 through _capi.host_ndtri, Geyer's sequence
+    through the library's host routine bnr_ess_from_stats): the fallback of users who hold the tables, and the yardstick of the GPU tests"""
+    tables = list(tables)
+    if not tables:
+        raise ValueError("need at least one table")
+    L = _rank_lag(nsamp, max_lag)
+    C, h = len(tables), nsamp // 2
+    q = tables[0]["gamma"].shape[1]
+    halves = []
+    for t in tables:
+        w = np.concatenate([t["gamma"][nburn:nburn + nsamp, :, 0], t["xi"][nburn:nburn + nsamp, :, 0]], axis=1)
+        halves += [w[:h], w[nsamp - h:]]
+    X = np.stack(halves)                                 # (2 C, h, q + V)
+    m, _, P = X.shape
+    n = m * h
+    flat = X.reshape(n, P)
+    ok = np.isfinite(flat).all(axis=0) & (flat != flat[0]).any(axis=0)
+    Z, F, I05, I95, XC = (np.zeros_like(flat) for _ in range(5))
+    fold_ok = np.zeros(P, dtype=bool)
+    k05, k95 = int(np.floor((n - 1) * 0.05)) + 1, int(np.floor((n - 1) * 0.95)) + 1
+    for p in np.flatnonzero(ok):
+        x = flat[:, p]
+        Z[:, p], xs = _z_scale(x)
+        I05[:, p], I95[:, p] = x <= xs[k05 - 1], x <= xs[k95 - 1]
+        XC[:, p] = x - (xs[n // 2 - 1] + xs[n // 2]) / 2.0            # x about its median: ess_mean and mcse_mean are shift-invariant, and
+        f = np.abs(XC[:, p])                                         # the split-chain means of a column like 1e8 + N(0, 1) keep their digits
+        fold_ok[p] = np.isfinite(f).all() and (f != f[0]).any()
+        if fold_ok[p]:
+            F[:, p] = _z_scale(f)[0]
+    shape = (m, h, P)
+    mz, m05, m95, mx = (_split_message(a.reshape(shape), L) for a in (Z, I05, I95, XC))
+    mf = _split_message(F.reshape(shape), 1)
+    nan = np.full(P, np.nan)
+    rhat_bulk = np.where(ok, _split_rhat(mz, C, L, P, h), nan)
+    rhat_tail = np.where(ok & fold_ok, _split_rhat(mf, C, 1, P, h), nan)
+    ess = [_capi.ess_from_stats(a, nsamp, L) for a in (mz, m05, m95, mx)]
+    ess_bulk = np.where(ok, ess[0], nan)
+    ess_tail = np.where(ok & ~np.isnan(ess[1]) & ~np.isnan(ess[2]), np.minimum(ess[1], ess[2]), nan)
+    ess_mean = np.where(ok, ess[3], nan)
+    sx = mx.reshape(m, 2 + L, P)
+    mm = sx[:, 0].mean(axis=0)
+    sd2 = ((h - 1.0) * sx[:, 1].sum(axis=0) + h * ((sx[:, 0] - mm) ** 2).sum(axis=0)) / (n - 1.0)
+    with np.errstate(all="ignore"):
+        mcse = np.where(ok, np.sqrt(sd2) / np.sqrt(ess_mean), nan)
+    return _rank_diagnostics(q, (rhat_bulk, rhat_tail, ess_bulk, ess_tail, ess_mean, mcse), C, nsamp, L)
+
+
+def rank_normalize(x, device=None):
+    """Average ranks and normal scores of every row of an m x S matrix (rows x draws), each row ranked on its own, on the GPU
+    (bnr_rank_normalize): dict with ranks (ties share the mean of their positions) and z = Phi^-1((ranks - 3/8) / (S + 1/4)).  +-Inf rank as
+    numbers; a row that holds a NaN is NaN everywhere.  A vector is taken as one row."""
+    a = np.asarray(x, dtype=np.float64)
+    r, z = _capi.rank_normalize_raw(a.reshape(1, -1) if a.ndim == 1 else a, 0 if device is None else int(device))
+    return dict(ranks=r.reshape(a.shape), z=z.reshape(a.shape))
+
+
+def RankDiagnose(results, max_lag=None):
+    """The rank-normalised diagnostics of a fit -> RankDiagnostics.  Uses the GPU's numbers when the fit carried them (rank_diagnostics=True:
+    every chain of the fit), otherwise restates them on the host over results.state (needs return_state=True; chain 1 alone)."""
+    if results.rank_diag is not None and (max_lag is None or int(max_lag) == results.rank_diag.max_lag):
+        return results.rank_diag
+    if results.state is None:
+        raise ValueError("RankDiagnose needs Fit(..., rank_diagnostics=True), or the state table (return_state=True)")
+    return _host_rank_diagnostics([results.state], results.burn_in, results.sampled, max_lag)
 
 
 # ------------------------------------------------------------------------------------------ pooled chains, predictive intervals, PIT (additions)
@@ -944,12 +1126,15 @@ def return_psrf_VOI(chainset, nburn, nsamp, fetch_state=True, summary_interval=N
 
 
 def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None, predict=None, waic=False, loo=False, loo_r_eff=None,
-            pool_chains=False, predict_observation=False, pred_seed=0, loo_predict=None):
+            pool_chains=False, predict_observation=False, pred_seed=0, loo_predict=None, rank_diag=False):
     """The Results a fit returns: chain 1's table (states[1], gibbs.jl:788) and/or its Summary statistics from the device; predict =
     (new rows, their y or None, interval), waic=True and loo=True add the prediction, WAIC and PSIS-LOO computed on the device over the
     same window.  pool_chains: those statistics over the pooled windows of all chains of the fit (one rank holds them all);
     predict_observation: the prediction through the pooled entry point (one chain unless pool_chains) with the predictive bounds and the PIT;
-    loo_predict = (training y, interval): the LOO predictive checks (Results.loo_predictive), and Results.loo from the same call."""
+    loo_predict = (training y, interval): the LOO predictive checks (Results.loo_predictive), and Results.loo from the same call.
+    rank_diag: the rank-normalised diagnostics over every chain of the fit (Results.rank_diag; ess_max_lag, where positive, is their lag window)."""
+    if rank_diag:
+        res.rank_diag = device_rank_diagnostics([chainset.chains[c] for c in chainset.ids], res.burn_in, res.sampled, ess_max_lag if ess_max_lag else None)
     if pool_chains or predict_observation:
         return _finish_pooled(chainset, res, return_state, summary_interval, ess_max_lag, predict, waic, loo, loo_r_eff, pool_chains,
                               predict_observation, pred_seed, loo_predict)
@@ -1020,6 +1205,17 @@ def _loo_predict_request(loo_predict, predict_interval, y):
     return np.asarray(y, dtype=np.float64).reshape(-1), predict_interval
 
 
+def _rank_diag_request(rank_diagnostics, nsamp=None, ess_max_lag=None):
+    """Fit's rank_diagnostics checked before any sampling: like pool_chains it needs every chain of the fit on this rank"""
+    if not rank_diagnostics:
+        return False
+    if _rank_world()[1] > 1:
+        raise ValueError("rank_diagnostics needs every chain of the fit on one rank: the chains are spread over %d torch.distributed ranks" % _rank_world()[1])
+    if nsamp is not None:
+        _rank_lag(nsamp, ess_max_lag if ess_max_lag else None)
+    return True
+
+
 def _pooled_request(pool_chains, predict_observation, predict_X):
     """Fit's pool_chains / predict_observation checked before any sampling"""
     if predict_observation and predict_X is None:
@@ -1066,7 +1262,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                      maxburn=50000, psrf_cutoff=1.2, x_transform=True, suppress_timer=False, num_chains=2, seed=None,
                      purge_burn=None, device=None, _keep=None, return_state=True, summary_interval=None, ess_max_lag=None,
                      xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
-                     pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False):
+                     pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False):
     """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
     xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
     xi_weights_code(xi_weights)
@@ -1078,6 +1274,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
     pred = _predict_request(predict_X, predict_y, predict_interval, x_transform, X_new)
     _pooled_request(pool_chains, predict_observation, predict_X)
     lp_req = _loo_predict_request(loo_predict, predict_interval, y)
+    rd_req = _rank_diag_request(rank_diagnostics, nsamp, ess_max_lag)
     _capi.r_eff_array(loo_r_eff, X_new.n)              # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
@@ -1121,7 +1318,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
     print("R = %s nu=%s nburn= %d nsamp = %d" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f\n" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
     res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff, pool_chains, predict_observation,
-                  seed_eff if pred_seed is None else pred_seed, lp_req)
+                  seed_eff if pred_seed is None else pred_seed, lp_req, rd_req)
     if _keep is None:
         cs.close()
     return res
@@ -1131,7 +1328,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                          maxgen=100000, psrf_cutoff=1.01, x_transform=True, suppress_timer=False, num_chains=2,
                          seed=None, purge_burn=None, device=None, return_state=True, summary_interval=None, ess_max_lag=None,
                          xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
-                         pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False):
+                         pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False):
     """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
     xi_weights_code(xi_weights)
     if nu == R:
@@ -1142,6 +1339,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
     pred = _predict_request(predict_X, predict_y, predict_interval, x_transform, X_new)
     _pooled_request(pool_chains, predict_observation, predict_X)
     lp_req = _loo_predict_request(loo_predict, predict_interval, y)
+    rd_req = _rank_diag_request(rank_diagnostics, nsamp, ess_max_lag)
     _capi.r_eff_array(loo_r_eff, X_new.n)              # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
@@ -1187,7 +1385,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
     print("\nR = %s nu=%s nburn= %d nsamp = %d\n" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.4f. Max PSRF Gamma: %.4f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
     res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff, pool_chains, predict_observation,
-                  seed_eff if pred_seed is None else pred_seed, lp_req)
+                  seed_eff if pred_seed is None else pred_seed, lp_req, rd_req)
     cs.close()
     return res
 
@@ -1196,7 +1394,7 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
         mingen=0, maxgen=0, psrf_cutoff=1.01, x_transform=True, suppress_timer=False, num_chains=2, seed=None,
         purge_burn=None, filename="parameters.log", device=None, return_state=True, summary_interval=None, ess_max_lag=None,
         xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
-        pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False):
+        pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False):
     """Fit! (gibbs.jl:725-751).  The `V` keyword is accepted and ignored, as in the reference.
     Extensions: summary_interval=95 computes Summary's statistics on the GPU (Results.summary_device);
     return_state=False then leaves the (large) state table on the device and frees it; ess_max_lag=0 (default lag
@@ -1212,10 +1410,13 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     pred_seed (default: the fit's seed).  loo_predict=True adds the LOO predictive checks of the training rows (Results.loo_predictive, see
     LOOPredict: PSIS-weighted mean, sd, PIT and a predict_interval% interval of every row, RMSE, R2, coverage); it implies loo (Results.loo comes
     from the same device call), honours pool_chains and loo_r_eff, and like pool_chains needs every chain of the fit on this rank.
+    rank_diagnostics=True adds the rank-normalised R-hat, bulk / tail ESS and MCSE over every chain of the fit, computed on the GPU from the
+    resident traces (Results.rank_diag, see RankDiagnose; ess_max_lag, where positive, is their lag window); every chain must live on this rank.
     parameters.log keeps the reference's lines only."""
     xi_weights_code(xi_weights)
     _pooled_request(pool_chains, predict_observation, predict_X)
     _loo_predict_request(loo_predict, predict_interval, y)
+    _rank_diag_request(rank_diagnostics)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
         with open(filename, "w") as f:
@@ -1234,11 +1435,11 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                                     return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
                                     xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval,
                                     waic=waic, loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation,
-                                    pred_seed=pred_seed, loo_predict=loo_predict)
+                                    pred_seed=pred_seed, loo_predict=loo_predict, rank_diagnostics=rank_diagnostics)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
                             return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
                             xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic,
                             loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed,
-                            loo_predict=loo_predict)
+                            loo_predict=loo_predict, rank_diagnostics=rank_diagnostics)

@@ -101,6 +101,7 @@ struct bnr_chain {
     long long cap_seen = 0;      // sampler-cap events already reported (the device counter is cumulative: a capped draw is reported by the call it happened in, once)
     int predict_block_rows = 0;  // tunable "predict_block_rows": rows per block of bnr_chain_predict / bnr_chain_loglik_stats (0: automatic)
     int summary_block_cols = 0;  // tunable "summary_block_cols": parameter columns per staging block of the Summary calls (0: automatic)
+    int rank_block_cols = 0;     // tunable "rank_block_cols": parameter columns per staging block of the rank-normalised diagnostics (0: automatic)
 };
 
 struct bnr_group {
@@ -179,6 +180,12 @@ static void launch_loow_block(hipStream_t st, const pred_stages &sg, const doubl
                               const double *isd);
 static int psis_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *log_weights, double *lpd, double *elpd,
                        double *khat);
+// the rank-normalised diagnostics (ABI 12): k_rank's two (key, index) buffers, one slice of ld entries per column; k_rank and k_fold are launched
+// from the end of this file, like the other late kernels
+struct rank_bufs { unsigned long long *keyA = nullptr, *keyB = nullptr; unsigned int *idxA = nullptr, *idxB = nullptr; };
+static void launch_rank(hipStream_t st, int cols, const double *buf, long long ld, int nsamp, int nch, int all, const rank_bufs &rb, int k05, int k95,
+                        double *ranks, double *z, double *ind05, double *ind95, double *med, int *flag);
+static void launch_fold(hipStream_t st, int cols, const double *buf, long long ld, const double *med, int absolute, double *out);
 static int ensure_lds_attributes(int device)
 {
     static std::mutex mu;
@@ -2173,6 +2180,206 @@ int bnr_chain_ess_stats(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t 
     return out.fetch(st, "ess_stats", "k_acov", {stats});
 }
 
+// Rank-normalised convergence diagnostics (ABI 12; Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021, as `posterior` 1.x computes them) of every
+// parameter p in [gamma(q) | xi(V)] over the pooled window of the chains listed.  The columns are staged as in summary_call ("rank_block_cols"
+// overrides the block of about 1 GiB of draws); per block: k_rank on the split-chain draws (z, the two tail indicators, the median, the flag),
+// k_acov -- unchanged: a pooled column is nc windows of nsamp side by side, i.e. pc nc columns of nsamp -- on z, the indicators and x - med
+// (k_fold: the moments of x are taken about the median), k_fold and a second k_rank and k_acov for the folded z.  Each series' message of the block (2 (2 + L) pc nc doubles; L = 1 where only R-hat is
+// wanted) is fetched and finished here: bnr_ess_from_stats as it stands, and split-R-hat = sqrt(((h-1)/h W + B) / W).  Work nobody asked for
+// is not run.  Conventions: a parameter with a non-finite draw, or with all draws equal, is NaN in every output; rhat_tail is NaN where the
+// folded draws are all equal; ess_tail is NaN where either indicator's ESS is.
+namespace {
+struct split_msg {                                       // k_acov's message of one series of a block, per chain in bnr_ess_from_stats' layout
+    std::vector<double> raw, st, ess;
+    int nc = 0, pc = 0, L = 0, h = 0;
+    double mean(int c, int half, int p) const { return st[((size_t)c * 2 + half) * (size_t)(2 + L) * pc + p]; }
+    double var(int c, int half, int p) const { return st[((size_t)c * 2 + half) * (size_t)(2 + L) * pc + pc + p]; }
+    void moments(int p, double &W, double &dev2) const  // the mean of the 2 nc variances; the sum of the squared deviations of the 2 nc means
+    {
+        const int m = 2 * nc;
+        double mm = 0.0;
+        W = 0.0;
+        for (int c = 0; c < nc; ++c) for (int k = 0; k < 2; ++k) { mm += mean(c, k, p); W += var(c, k, p); }
+        mm /= m; W /= m;
+        dev2 = 0.0;
+        for (int c = 0; c < nc; ++c) for (int k = 0; k < 2; ++k) dev2 += (mean(c, k, p) - mm) * (mean(c, k, p) - mm);
+    }
+    double rhat(int p) const
+    {
+        double W, dev2;
+        moments(p, W, dev2);
+        return sqrt(((double)(h - 1) / h * W + dev2 / (2 * nc - 1)) / W);
+    }
+};
+}
+static int rank_diag_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t max_lag, double *rhat_bulk, double *rhat_tail,
+                          double *ess_bulk, double *ess_tail, double *ess_mean, double *mcse_mean)
+{
+    if (!rhat_bulk && !rhat_tail && !ess_bulk && !ess_tail && !ess_mean && !mcse_mean) return fail(BNR_ERR_BAD_ARG, "no output requested");
+    if (nsamp < 8) return fail(BNR_ERR_BAD_ARG, "need nsamp >= 8");
+    if (max_lag < 2 || max_lag > nsamp / 2) return fail(BNR_ERR_BAD_ARG, "need 2 <= max_lag <= nsamp/2");
+    bnr_chain *c = cs[0];
+    const bnr_dev &d = c->d;
+    const long long S = (long long)nc * nsamp;
+    const int h = nsamp / 2, np = d.q + d.V;
+    const long long n = (long long)nc * 2 * h;          // the split-chain draws that are ranked
+    const int k05 = (int)floor((double)(n - 1) * 0.05) + 1, k95 = (int)floor((double)(n - 1) * 0.95) + 1;
+    const bool want_bulk = rhat_bulk || ess_bulk, want_mean = ess_mean || mcse_mean, want_et = ess_tail != nullptr, want_rt = rhat_tail != nullptr;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->x.stream;
+    int rc;
+    if ((rc = pooled_quiesce(cs, nc))) return rc;
+    const size_t budget = (size_t)1 << 30;
+    long long blk = c->rank_block_cols > 0 ? c->rank_block_cols : (long long)(budget / ((size_t)S * sizeof(double)));
+    blk = std::min<long long>(std::max<long long>(blk, 1), np);
+    const int Lmax = (ess_bulk || want_et || want_mean) ? max_lag : 1;
+    dev_tmp tmp;
+    double *X = nullptr, *Z = nullptr, *A = nullptr, *B = nullptr, *med = nullptr, *statd = nullptr;
+    int *flagd = nullptr;
+    rank_bufs rb;
+    const size_t cells = (size_t)blk * (size_t)S;
+    if ((rc = tmp.alloc(&X, cells, st, false))) return rc;
+    if ((want_bulk || want_rt) && (rc = tmp.alloc(&Z, cells, st, false))) return rc;
+    if ((want_et || want_rt || want_mean) && (rc = tmp.alloc(&A, cells, st, false))) return rc;
+    if (want_et && (rc = tmp.alloc(&B, cells, st, false))) return rc;
+    if ((rc = tmp.alloc(&rb.keyA, cells, st, false)) || (rc = tmp.alloc(&rb.keyB, cells, st, false)) || (rc = tmp.alloc(&rb.idxA, cells, st, false)) ||
+        (rc = tmp.alloc(&rb.idxB, cells, st, false)))
+        return rc;
+    if ((rc = tmp.alloc(&med, (size_t)blk, st)) || (rc = tmp.alloc(&flagd, 2 * (size_t)blk, st))) return rc;
+    if ((rc = tmp.alloc(&statd, (size_t)2 * (2 + Lmax) * (size_t)blk * nc, st, false))) return rc;
+    const double nanv = NAN;
+    std::vector<double> o_rb(np, nanv), o_rt(np, nanv), o_eb(np, nanv), o_et(np, nanv), o_em(np, nanv), o_mc(np, nanv);
+    std::vector<int> flags(2 * (size_t)blk);
+    split_msg sz, s05, s95, sx, sf;
+    const dim3 block(32, 8);
+    for (int p0 = 0; p0 < np; p0 += (int)blk) {
+        const int pc = std::min<int>((int)blk, np - p0);
+        const int g0 = std::min(p0, d.q), g1 = std::min(p0 + pc, d.q);
+        const int x0 = std::max(p0, d.q) - d.q, x1 = std::max(p0 + pc, d.q) - d.q;
+        for (int k = 0; k < nc; ++k) {
+            const bnr_dev &dk = cs[k]->d;
+            double *dst = X + (size_t)k * nsamp;
+            if (g1 > g0)
+                hipLaunchKernelGGL(k_fetch_cols, dim3((g1 - g0 + 31) / 32, (nsamp + 31) / 32), block, 0, st, (const double *)dk.trace, dk.rowlen,
+                                   dk.o_gamma + g0, g1 - g0, first_row - 1, nsamp, dst, S);
+            if (x1 > x0)
+                hipLaunchKernelGGL(k_fetch_cols, dim3((x1 - x0 + 31) / 32, (nsamp + 31) / 32), block, 0, st, (const double *)dk.trace, dk.rowlen,
+                                   dk.o_xi + x0, x1 - x0, first_row - 1, nsamp, dst + (size_t)(g1 - g0) * (size_t)S, S);
+        }
+        // one series: k_acov on the block's pc nc windows, its message fetched and laid out per chain; the ESS where lags were asked for
+        auto series = [&](const double *data, int L, split_msg &m) -> int {
+            const size_t cnt = (size_t)2 * (2 + L) * (size_t)pc * nc;
+            hipLaunchKernelGGL(k_acov, dim3(pc * nc, 2), dim3(256), 0, st, data, nsamp, pc * nc, L, statd);
+            m.raw.resize(cnt);
+            hipError_t e = hipMemcpyAsync(m.raw.data(), statd, sizeof(double) * cnt, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("rank_diag: ") + hipGetErrorString(e));
+            if (int r = check_launch("k_acov")) return r;
+            m.nc = nc; m.pc = pc; m.L = L; m.h = h;
+            m.st.resize(cnt);
+            for (int k = 0; k < 2; ++k) for (int j = 0; j < 2 + L; ++j) {
+                const double *src = m.raw.data() + ((size_t)k * (2 + L) + j) * (size_t)pc * nc;
+                for (int ch = 0; ch < nc; ++ch) {
+                    double *dst = m.st.data() + (((size_t)ch * 2 + k) * (2 + L) + j) * (size_t)pc;
+                    for (int p = 0; p < pc; ++p) dst[p] = src[(size_t)p * nc + ch];
+                }
+            }
+            m.ess.assign(pc, NAN);
+            if (L >= 2) return bnr_ess_from_stats(m.st.data(), nc, pc, nsamp, L, m.ess.data());
+            return BNR_OK;
+        };
+        launch_rank(st, pc, X, S, nsamp, nc, 0, rb, k05, k95, nullptr, want_bulk ? Z : nullptr, want_et ? A : nullptr, want_et ? B : nullptr, med, flagd);
+        if (want_bulk && (rc = series(Z, ess_bulk ? max_lag : 1, sz))) return rc;
+        if (want_et && ((rc = series(A, max_lag, s05)) || (rc = series(B, max_lag, s95)))) return rc;
+        if (want_mean) {                                     // on x - med: see k_fold
+            launch_fold(st, pc, X, S, med, 0, A);
+            if ((rc = series(A, max_lag, sx))) return rc;
+        }
+        if (want_rt) {
+            launch_fold(st, pc, X, S, med, 1, A);
+            launch_rank(st, pc, A, S, nsamp, nc, 0, rb, k05, k95, nullptr, Z, nullptr, nullptr, nullptr, flagd + blk);
+            if ((rc = series(Z, 1, sf))) return rc;
+        }
+        HIPCHK(hipMemcpyAsync(flags.data(), flagd, sizeof(int) * 2 * (size_t)blk, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if ((rc = check_launch("k_rank"))) return rc;
+        for (int p = 0; p < pc; ++p) {
+            if (flags[p]) continue;                          // a NaN, an Inf or all draws equal: NaN throughout
+            const int P = p0 + p;
+            if (want_bulk) { o_rb[P] = sz.rhat(p); o_eb[P] = sz.ess[p]; }
+            if (want_rt && !flags[(size_t)blk + p]) o_rt[P] = sf.rhat(p);
+            if (want_et) o_et[P] = (s05.ess[p] != s05.ess[p] || s95.ess[p] != s95.ess[p]) ? nanv : std::min(s05.ess[p], s95.ess[p]);
+            if (want_mean) {
+                double W, dev2;
+                sx.moments(p, W, dev2);
+                const double sd2 = ((double)(h - 1) * (W * 2 * nc) + (double)h * dev2) / (double)(n - 1);
+                o_em[P] = sx.ess[p];
+                o_mc[P] = sqrt(sd2) / sqrt(sx.ess[p]);
+            }
+        }
+    }
+    const struct { double *dst; const std::vector<double> *src; } outs[] = {{rhat_bulk, &o_rb}, {rhat_tail, &o_rt}, {ess_bulk, &o_eb},
+                                                                           {ess_tail, &o_et}, {ess_mean, &o_em}, {mcse_mean, &o_mc}};
+    for (const auto &o : outs) if (o.dst) memcpy(o.dst, o.src->data(), sizeof(double) * np);
+    return BNR_OK;
+}
+int bnr_chain_rank_diag(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t max_lag, double *rhat_bulk, double *rhat_tail, double *ess_bulk,
+                        double *ess_tail, double *ess_mean, double *mcse_mean)
+{
+    if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
+    return rank_diag_call(&c, 1, first_row, nsamp, max_lag, rhat_bulk, rhat_tail, ess_bulk, ess_tail, ess_mean, mcse_mean);
+}
+int bnr_chains_rank_diag(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t max_lag, double *rhat_bulk,
+                         double *rhat_tail, double *ess_bulk, double *ess_tail, double *ess_mean, double *mcse_mean)
+{
+    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
+    return rank_diag_call(chains, nchains, first_row, nsamp, max_lag, rhat_bulk, rhat_tail, ess_bulk, ess_tail, ess_mean, mcse_mean);
+}
+double bnr_host_ndtri(double p) { return bnr_ndtri(p); }
+
+// Average ranks and normal scores of every row of a caller's m x S matrix (host, row-major), each row on its own: the companion of
+// bnr_psis_loo / bnr_psis_weights, and k_rank's direct test.  On a stream of its own, the rows in blocks of about 256 MiB.
+int bnr_rank_normalize(int32_t device, int32_t m, int32_t S, const double *x, double *ranks, double *z)
+{
+    if (!x || (!ranks && !z)) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (m < 1 || S < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows and S >= 1 draws");
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
+    HIPCHK(hipSetDevice(device));
+    struct stream_guard {
+        hipStream_t s = nullptr;
+        ~stream_guard() { if (s) (void)hipStreamDestroy(s); }
+    } guard;
+    HIPCHK(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
+    hipStream_t st = guard.s;
+    const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, ((size_t)1 << 28) / ((size_t)S * sizeof(double))));
+    const size_t cells = (size_t)blk * (size_t)S;
+    int rc;
+    dev_tmp tmp;                                        // (freed before the stream goes)
+    double *Xd = nullptr, *Rd = nullptr, *Zd = nullptr;
+    int *flagd = nullptr;
+    rank_bufs rb;
+    if ((rc = tmp.alloc(&Xd, cells, st, false))) return rc;
+    if (ranks && (rc = tmp.alloc(&Rd, cells, st, false))) return rc;
+    if (z && (rc = tmp.alloc(&Zd, cells, st, false))) return rc;
+    if ((rc = tmp.alloc(&rb.keyA, cells, st, false)) || (rc = tmp.alloc(&rb.keyB, cells, st, false)) || (rc = tmp.alloc(&rb.idxA, cells, st, false)) ||
+        (rc = tmp.alloc(&rb.idxB, cells, st, false)) || (rc = tmp.alloc(&flagd, (size_t)blk, st)))
+        return rc;
+    for (int i0 = 0; i0 < m; i0 += blk) {
+        const int mr = std::min(blk, m - i0);
+        const size_t cnt = (size_t)mr * (size_t)S;
+        HIPCHK(hipMemcpyAsync(Xd, x + (size_t)i0 * S, sizeof(double) * cnt, hipMemcpyHostToDevice, st));
+        launch_rank(st, mr, Xd, S, S, 1, 1, rb, 1, 1, Rd, Zd, nullptr, nullptr, nullptr, flagd);
+        if (ranks) HIPCHK(hipMemcpyAsync(ranks + (size_t)i0 * S, Rd, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
+        if (z) HIPCHK(hipMemcpyAsync(z + (size_t)i0 * S, Zd, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
+    }
+    hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("rank_normalize: ") + hipGetErrorString(e));
+    return check_launch("k_rank");
+}
+
 // Posterior of the mean response mu + x . gamma of m new rows over rows first_row .. first_row+nsamp-1 of the chains listed (an addition to the
 // reference): X_pred goes to the device in its own element type and is converted there (k_x_convert with m rows), then predict_rows.
 // pred_lower / pred_upper / pit (host, nullable): the extras of the pooled entry points.
@@ -2671,6 +2878,12 @@ int bnr_chain_set_option(bnr_chain *c, const char *name, int64_t value)
         c->summary_block_cols = (int)value;
         return BNR_OK;
     }
+    if (!strcmp(name, "rank_block_cols")) {
+        // performance only: parameter columns per staging block of bnr_chain_rank_diag / bnr_chains_rank_diag (the first chain's setting counts)
+        if (value < 0 || value > (1 << 24)) return fail(BNR_ERR_BAD_ARG, "rank_block_cols must be between 0 (automatic) and 2^24");
+        c->rank_block_cols = (int)value;
+        return BNR_OK;
+    }
     if (!strcmp(name, "byte_x")) {
         // 0: the X passes read the f64 matrix also when a byte image exists; 1: back to the byte image (if the input had one)
         if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
@@ -2771,6 +2984,18 @@ static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, 
 }
 
 // ----------------------------------------------------------------------------------------- every reference to the kernels of the LOO predictive checks (ABI 11)
+// k_rank / k_fold (ABI 12): first referenced here, behind the kernels of the sweep and the late kernels above, in front of the kernels of ABI 11
+static void launch_rank(hipStream_t st, int cols, const double *buf, long long ld, int nsamp, int nch, int all, const rank_bufs &rb, int k05, int k95,
+                        double *ranks, double *z, double *ind05, double *ind95, double *med, int *flag)
+{
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rank<0>), dim3(cols), dim3(256), 0, st, buf, ld, nsamp, nch, all, rb.keyA, rb.keyB, rb.idxA, rb.idxB, k05, k95, ranks, z,
+                       ind05, ind95, med, flag);
+}
+static void launch_fold(hipStream_t st, int cols, const double *buf, long long ld, const double *med, int absolute, double *out)
+{
+    const int chunks = (int)((ld + 255) / 256);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fold<0>), dim3((unsigned)chunks * (unsigned)cols), dim3(256), 0, st, buf, ld, chunks, med, absolute, out);
+}
 // k_psis_w: the sorted tail, 12 bytes per entry for up to BNR_PSIS_MAX_TAIL entries (on the current device; cheap enough for once per call)
 static int loow_lds_attributes()
 {

@@ -4310,3 +4310,163 @@ __global__ __launch_bounds__(256) void k_loo_quantile(const double *E, const dou
     }
     if (tid == 0) out[i] = nan ? NAN : 0.5 * (lo + hi);
 }
+
+// ===================================================================================== k_rank / k_fold (ABI 12: rank-normalised diagnostics)
+// k_rank: the average ranks of the draws of one staged column (see k_summary: column p of `buf`, leading dimension ld), their normal scores
+// z = Phi^-1((r - 3/8) / (n + 1/4)) (bnr_ndtri), the two tail indicators, the median and a flag, one workgroup of 256 threads per column.
+// The column holds nch windows of nsamp draws side by side; all = 0 ranks only the split-chain draws (rows [0, h) and [nsamp - h, nsamp) of
+// every window, h = nsamp / 2: an odd window drops its middle row, as k_rhat_stats and k_acov do), all = 1 every draw.  n = nch x (nsamp or 2h).
+//   1. keys: the order-preserving 64-bit image of every draw (bnr_key_of, -0 folded onto +0 so that the two tie) and its position in the
+//      column (32 bits) go to keyA / idxA; the histograms of all eight 8-bit digits are counted in LDS on the way (integer LDS atomics: the
+//      counts do not depend on their order).
+//   2. LSD radix sort, 8 bits per pass, between the two (key, index) buffers in global memory; a pass whose digit is the same in every key
+//      (the exponent bytes of most columns, seven of eight bytes of a 0/1 column) is skipped.  A pass walks the source in tiles of 256 in
+//      order: a thread finds the lanes of its wave that hold its digit with eight ballots (its rank among them is a popcount), the waves'
+//      counts meet in LDS (wcnt), and the digit's running base makes the destination: stable, no global atomics.
+//   3. tie runs: one forward sweep over the sorted keys, a ballot per wave and a carry per tile, gives every position the start of its run
+//      (sa) and every run start the end of its run (ea: written by the head of the next run); both live in the key buffer the sort left free.
+//   4. results, scattered to the draws' own positions: rank = (start + end + 1) / 2 (1-based average of start + 1 .. end: an exact multiple
+//      of 1/2), z, the indicators I(x <= x_(k05)) and I(x <= x_(k95)) as 0.0 / 1.0 (a comparison of keys), med = (x_(n/2) + x_(n/2+1)) / 2,
+//      flag = 1 (a NaN) | 2 (an Inf) | 4 (all draws equal).  A column that holds a NaN gets NaN ranks and z.
+// Ranks are a pure function of the data: equal keys end up in one run whatever order the sort left their indices in, so every output is bitwise
+// independent of the grid, the block of columns and the call.  Every index stays below n <= ld: nothing is written outside the column's slices.
+// 128 VGPRs, 14.1 KiB of LDS, no scratch.
+template <int LATE>
+__global__ __launch_bounds__(256) void k_rank(const double *buf, long long ld, int nsamp, int nch, int all, unsigned long long *keyA,
+                                              unsigned long long *keyB, unsigned int *idxA, unsigned int *idxB, int k05, int k95, double *ranks,
+                                              double *z, double *ind05, double *ind95, double *med, int *flag)
+{
+    __shared__ unsigned int hist[8][256];
+    __shared__ unsigned int base[256], tmp[256];
+    __shared__ unsigned int wcnt[4][256];
+    __shared__ int s_skip[8], wlast[2][4], carry[2], s_flag;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const size_t c0 = (size_t)blockIdx.x * (size_t)ld;
+    const double *x = buf + c0;
+    const int hh = nsamp / 2, per = all ? nsamp : 2 * hh, gap = nsamp - per;
+    const int n = nch * per;
+    unsigned long long *src = keyA + c0, *dst = keyB + c0;
+    unsigned int *si = idxA + c0, *di = idxB + c0;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int b = 0; b < 8; ++b) hist[b][tid] = 0u;
+    for (int b = 0; b < 4; ++b) wcnt[b][tid] = 0u;
+    if (tid < 8) s_skip[tid] = 0;
+    if (tid == 0) { s_flag = 0; carry[0] = 0; carry[1] = 0; }
+    __syncthreads();
+    // 1. keys and digit histograms
+    int myflag = 0;
+    for (int t = tid; t < n; t += 256) {
+        const int c = t / per, u = t - c * per;
+        const unsigned int pos = (unsigned int)(c * nsamp + (u < hh ? u : u + gap));
+        double v = x[pos];
+        if (v != v) myflag |= 1;
+        else if (fabs(v) == INFINITY) myflag |= 2;
+        if (v == 0.0) v = 0.0;                                 // -0 ties with +0
+        const unsigned long long key = bnr_key_of(v);
+        src[t] = key; si[t] = pos;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) atomicAdd(&hist[b][(unsigned int)(key >> (8 * b)) & 255u], 1u);
+    }
+    if (myflag) atomicOr(&s_flag, myflag);
+    __syncthreads();
+    for (int b = 0; b < 8; ++b) if (hist[b][tid] == (unsigned int)n) s_skip[b] = 1;
+    __syncthreads();
+    // 2. the passes
+    for (int pass = 0; pass < 8; ++pass) {
+        if (s_skip[pass]) continue;                            // (uniform: read behind the barrier above, never written again)
+        const int shift = 8 * pass;
+        const unsigned int mine = hist[pass][tid];
+        tmp[tid] = mine;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {
+            const unsigned int a = tid >= off ? tmp[tid - off] : 0u;
+            __syncthreads();
+            tmp[tid] += a;
+            __syncthreads();
+        }
+        base[tid] = tmp[tid] - mine;
+        __syncthreads();
+        for (int t0 = 0; t0 < n; t0 += 256) {
+            const int t = t0 + tid;
+            const bool valid = t < n;
+            const unsigned long long key = valid ? src[t] : 0ull;
+            const unsigned int id = valid ? si[t] : 0u;
+            const unsigned int d = (unsigned int)(key >> shift) & 255u;
+            unsigned long long mask = __ballot(valid);
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const unsigned long long m = __ballot((d >> b) & 1u);
+                mask &= ((d >> b) & 1u) ? m : ~m;
+            }
+            const unsigned int lrank = (unsigned int)__popcll(mask & below), cnt = (unsigned int)__popcll(mask);
+            if (valid && lrank == 0u) wcnt[w][d] = cnt;
+            __syncthreads();
+            unsigned int pos = 0u;
+            if (valid) {
+                pos = base[d] + lrank;
+                for (int ww = 0; ww < w; ++ww) pos += wcnt[ww][d];
+            }
+            __syncthreads();
+            if (valid && lrank == 0u) { atomicAdd(&base[d], cnt); wcnt[w][d] = 0u; }
+            if (valid && pos < (unsigned int)n) { dst[pos] = key; di[pos] = id; }
+        }
+        __syncthreads();
+        unsigned long long *tk = src; src = dst; dst = tk;
+        unsigned int *ti = si; si = di; di = ti;
+    }
+    // 3. tie runs
+    unsigned int *sa = (unsigned int *)dst, *ea = sa + ld;
+    for (int t0 = 0, it = 0; t0 < n; t0 += 256, ++it) {
+        const int par = it & 1, t = t0 + tid;
+        const bool valid = t < n;
+        const bool head = valid && (t == 0 || src[t] != src[t - 1]);
+        const unsigned long long hm = __ballot(head);
+        if (lane == 0) wlast[par][w] = hm ? t0 + w * 64 + (63 - __clzll((long long)hm)) : -1;
+        __syncthreads();
+        int c = carry[par];
+        for (int ww = 0; ww < w; ++ww) if (wlast[par][ww] >= 0) c = wlast[par][ww];
+        const unsigned long long lo = hm & below, in = hm & (below | (1ull << lane));
+        const int sx = lo ? t0 + w * 64 + (63 - __clzll((long long)lo)) : c;        // the start of the run of position t - 1
+        const int s_in = in ? t0 + w * 64 + (63 - __clzll((long long)in)) : c;      // the start of the run of position t
+        if (valid) {
+            sa[t] = (unsigned int)s_in;
+            if (head && t > 0) ea[sx] = (unsigned int)t;
+            if (t == n - 1) ea[s_in] = (unsigned int)n;
+        }
+        if (tid == 255) carry[par ^ 1] = s_in;
+    }
+    __syncthreads();
+    // 4. results
+    const int fl = s_flag | (ea[0] == (unsigned int)n ? 4 : 0);
+    const bool nan = (fl & 1) != 0;
+    if (tid == 0) {
+        flag[blockIdx.x] = fl;
+        if (med) med[blockIdx.x] = n >= 2 ? (bnr_double_of(src[n / 2 - 1]) + bnr_double_of(src[n / 2])) / 2.0 : bnr_double_of(src[0]);
+    }
+    const unsigned long long q05 = ind05 ? src[k05 - 1] : 0ull, q95 = ind95 ? src[k95 - 1] : 0ull;
+    const double den = (double)n + 0.25;
+    for (int t = tid; t < n; t += 256) {
+        const unsigned int s = sa[t], e = ea[s];
+        const double r = (double)((unsigned long long)s + e + 1ull) * 0.5;
+        const size_t i = c0 + si[t];
+        if (ranks) ranks[i] = nan ? NAN : r;
+        if (z) z[i] = nan ? NAN : bnr_ndtri((r - 0.375) / den);
+        if (ind05) ind05[i] = src[t] <= q05 ? 1.0 : 0.0;
+        if (ind95) ind95[i] = src[t] <= q95 ? 1.0 : 0.0;
+    }
+}
+
+// k_fold: the draws of every staged column about the column's median, for k_rank's second run and for the moments of x; `chunks` workgroups
+// of 256 draws per column.  absolute = 1: the folded draws |x - med| of the tail R-hat; 0: x - med, on which ess_mean and mcse_mean are
+// computed -- both are invariant under the shift, and a column like 1e8 + N(0, 1) would otherwise lose eight digits of its split-chain means
+// (the between-chain variance B) to the rounding of k_acov's sums.
+template <int LATE>
+__global__ __launch_bounds__(256) void k_fold(const double *buf, long long ld, int chunks, const double *med, int absolute, double *out)
+{
+    const int col = (int)(blockIdx.x / (unsigned)chunks);
+    const long long i = (long long)(blockIdx.x % (unsigned)chunks) * 256 + threadIdx.x;
+    if (i >= ld) return;
+    const size_t o = (size_t)col * (size_t)ld + (size_t)i;
+    const double v = buf[o] - med[col];
+    out[o] = absolute ? fabs(v) : v;
+}

@@ -289,3 +289,37 @@ BNR_HD double bnr_xi_weight_ref(double lt, double lb, double Delta)
     const double w_top = (1.0 - Delta) * exp(lt), w_bot = Delta * exp(lb);
     return w_top / (w_bot + w_top);
 }
+
+// Phi^-1 for the rank-normalised diagnostics (k_rank) and bnr_host_ndtri: Wichura's algorithm AS 241, routine PPND16 (Appl. Statist. 37, 1988;
+// about 1e-16 relative): rational approximations in q = p - 1/2 for |q| <= 0.425 and in r = sqrt(-log(min(p, 1 - p))) in the tails.  Odd in q
+// by construction (Phi^-1(1/2) = 0 exactly; Phi^-1(p) = -Phi^-1(1 - p) bit for bit wherever 1 - p is exact); the library is built with
+// -ffp-contract=off, so host and device can differ only through the one log and the one sqrt of the tails.  p <= 0: -Inf, p >= 1: +Inf.
+BNR_HD double bnr_ndtri(double p)
+{
+    if (p != p) return p;
+    if (p <= 0.0) return -INFINITY;
+    if (p >= 1.0) return INFINITY;
+    const double q = p - 0.5;
+    if (fabs(q) <= 0.425) {
+        const double r = 0.180625 - q * q;
+        return q * (((((((r * 2509.0809287301226727 + 33430.575583588128105) * r + 67265.770927008700853) * r + 45921.953931549871457) * r
+                       + 13731.693765509461125) * r + 1971.5909503065514427) * r + 133.14166789178437745) * r + 3.387132872796366608)
+               / (((((((r * 5226.495278852545925 + 28729.085735721942674) * r + 39307.89580009271061) * r + 21213.794301586595867) * r
+                     + 5394.1960214247511077) * r + 687.1870074920579083) * r + 42.313330701600911252) * r + 1.0);
+    }
+    double r = sqrt(-log(q < 0.0 ? p : 1.0 - p)), val;
+    if (r <= 5.0) {
+        r -= 1.6;
+        val = (((((((r * 7.7454501427834140764e-4 + 0.0227238449892691845833) * r + 0.24178072517745061177) * r + 1.27045825245236838258) * r
+                  + 3.64784832476320460504) * r + 5.7694972214606914055) * r + 4.6303378461565452959) * r + 1.42343711074968357734)
+              / (((((((r * 1.05075007164441684324e-9 + 5.475938084995344946e-4) * r + 0.0151986665636164571966) * r + 0.14810397642748007459) * r
+                    + 0.68976733498510000455) * r + 1.6763848301838038494) * r + 2.05319162663775882187) * r + 1.0);
+    } else {
+        r -= 5.0;
+        val = (((((((r * 2.01033439929228813265e-7 + 2.71155556874348757815e-5) * r + 0.0012426609473880784386) * r + 0.026532189526576123093) * r
+                  + 0.29656057182850489123) * r + 1.7848265399172913358) * r + 5.4637849111641143699) * r + 6.6579046435011037772)
+              / (((((((r * 2.04426310338993978564e-15 + 1.4215117583164458887e-7) * r + 1.8463183175100546818e-5) * r + 7.868691311456132591e-4) * r
+                    + 0.0148753612908506148525) * r + 0.13692988092273580531) * r + 0.59983220655588793769) * r + 1.0);
+    }
+    return q < 0.0 ? -val : val;
+}

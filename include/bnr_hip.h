@@ -28,13 +28,14 @@
 extern "C" {
 #endif
 
-#define BNR_ABI_VERSION 11  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
+#define BNR_ABI_VERSION 12  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
                                5: + bnr_chain_create_typed, bnr_chain_create_from_matrices, bnr_device_synchronize; 6: + bnr_comm_info;
                                7: + option "xi_weights", bnr_host_xi_weight; 8: + bnr_chain_predict, bnr_chain_predict_from_matrices,
                                bnr_chain_loglik_stats, option "predict_block_rows"; 9: + bnr_chain_loo, bnr_psis_loo;
                                10: + bnr_chains_summary, bnr_chains_predict, bnr_chains_predict_from_matrices, bnr_chains_loglik_stats, bnr_chains_loo,
                                bnr_host_pred_noise, option "summary_block_cols"; 11: + bnr_chain_loo_predict, bnr_chains_loo_predict,
-                               bnr_psis_weights (all additive) */
+                               bnr_psis_weights; 12: + bnr_chain_rank_diag, bnr_chains_rank_diag, bnr_rank_normalize, bnr_host_ndtri,
+                               option "rank_block_cols" (all additive) */
 
 enum {
     BNR_OK = 0,
@@ -284,6 +285,29 @@ int bnr_chains_loo_predict(bnr_chain *const *chains, int32_t nchains, int32_t fi
 int bnr_psis_weights(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *log_weights, double *elpd_loo,
                      double *pareto_k);
 
+/* Rank-normalised convergence diagnostics (ABI 12) -- an ADDITION to the reference: the R-hat, bulk / tail effective sample sizes and Monte
+ * Carlo standard error of Vehtari, Gelman, Simpson, Carpenter, Buerkner (2021) as `posterior` 1.x computes them (rhat, ess_bulk, ess_tail,
+ * ess_mean, mcse_mean), for every parameter in [gamma(q) | xi(V)] over the pooled window (rows first_row .. first_row+nsamp-1 of every chain,
+ * in the order the chains are passed) of nchains >= 1 chains of one device.  Every window gives two split chains of h = nsamp / 2 rows
+ * (rows [0, h) and [nsamp - h, nsamp): an odd window drops its middle row); only these S' = 2 nchains h draws are ranked.
+ *   z = Phi^-1((r - 3/8) / (S' + 1/4)), r the average rank (ties share the mean of their positions; -0 ties with +0), Phi^-1: bnr_host_ndtri.
+ *   rhat_bulk = split-R-hat of z, sqrt(((h-1)/h W + B) / W); rhat_tail the same for the z of |x - median| (the median: mean of the two middle
+ *   order statistics).  The caller combines rhat = fmax(rhat_bulk, rhat_tail).
+ *   ess_bulk = bnr_ess_from_stats' estimator (truncated at max_lag) on z; ess_tail = the smaller of that estimator on I(x <= x_(k)),
+ *   k = floor((S'-1) prob) + 1, prob = 0.05 and 0.95 (NaN if either is); ess_mean the estimator on x; mcse_mean = sd / sqrt(ess_mean).
+ * Each output holds q + V doubles, gamma first, and may be NULL (not all): what is not asked for is not computed.  A parameter with a
+ * non-finite draw, or with all S' draws equal, is NaN in every output (not bnr_rhat's 1.0); rhat_tail is NaN where the folded draws are all
+ * equal.  Checks: those of bnr_chains_summary, nsamp >= 8, 2 <= max_lag <= nsamp / 2.  Runs eagerly on chains[0]'s stream; the columns are
+ * staged in blocks of about 1 GiB of draws (option "rank_block_cols" of chains[0] overrides); no result depends on the block, the grid or
+ * the call, bit for bit, and bnr_chain_rank_diag is the pooled call with one chain.  Nothing of any chain is written.
+ * bnr_rank_normalize: the average ranks and normal scores of every row of a caller's m x S matrix (host, row-major), each row on its own;
+ *   ranks[m x S], z[m x S] nullable (not both).  +-Inf rank as numbers; a row that holds a NaN gets NaN everywhere.  DESIGN.md section 8. */
+int bnr_chain_rank_diag(bnr_chain *chain, int32_t first_row, int32_t nsamp, int32_t max_lag, double *rhat_bulk, double *rhat_tail,
+                        double *ess_bulk, double *ess_tail, double *ess_mean, double *mcse_mean);
+int bnr_chains_rank_diag(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t max_lag, double *rhat_bulk,
+                         double *rhat_tail, double *ess_bulk, double *ess_tail, double *ess_mean, double *mcse_mean);
+int bnr_rank_normalize(int32_t device, int32_t m, int32_t S, const double *x, double *ranks, double *z);
+
 /* Effective sample size -- an ADDITION to the reference (which only has split-Rhat; north-star item "Rhat/ESS check").
  * bnr_chain_ess_stats: this chain's message over rows first_row .. first_row+nsamp-1: for both halves of the window (the
  *   halves of split-Rhat) the mean, the variance and the autocovariances at lags 0..max_lag-1 of gamma (q) then xi (V):
@@ -430,6 +454,8 @@ int32_t bnr_host_edge_index(int32_t V, int32_t l, int32_t k);   /* 0-based (l,k)
 /* the noise of bnr_chains_predict's predictive draws (the kernel's own function; no GPU needed): an ni x ns block, ROW-major,
  * out[(i - i0) * ns + (s - s0)] = bnr_host_normal(seed, s, 40 (SITE_PRED), i, 0) for rows i0 <= i < i0 + ni and pooled draws s0 <= s < s0 + ns */
 void bnr_host_pred_noise(uint64_t seed, uint32_t s0, uint32_t ns, uint32_t i0, uint32_t ni, double *out);
+/* Phi^-1 as k_rank evaluates it (Wichura's AS 241, PPND16); no GPU */
+double bnr_host_ndtri(double p);
 /* the node weight of option "xi_weights" = 1 (the kernel's own function): w = (1 - Delta) exp(lt) / (Delta exp(lb) + (1 - Delta) exp(lt)),
  * written literally (gibbs.jl:349-351), so 0, 1 and NaN arise where they arise in the reference */
 double bnr_host_xi_weight(double lt, double lb, double Delta);
