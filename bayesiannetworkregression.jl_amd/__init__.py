@@ -7,5 +7,6 @@ from ._capi import BnrError, Chain, Comm, Group, XInput, device_count, device_sy
 from .api import (BNRPrediction, BNRSummary, ChainSet, Fit, LOO, LOOPredict, LOOPredictive, Predict, Results, Summary, WAIC, create_lower_tri, device_predict,   # noqa: F401
                   device_summary, device_predict_pooled, device_summary_pooled, generate_samples, psis_loo, psis_weights, device_loo_predict,
                   generate_samples_dbl, initialize_and_run, lower_triangle, return_psrf_VOI, run, setup_X,
-                  allgather_stats, local_chain_ids, make_comm, shared_seed, RankDiagnose, RankDiagnostics, device_rank_diagnostics, rank_normalize)
+                  allgather_stats, local_chain_ids, make_comm, shared_seed, RankDiagnose, RankDiagnostics, device_rank_diagnostics, rank_normalize,
+                  EdgeSelect, EdgeSelection, device_edge_selection, hdi)
 from .synthetic import make_synthetic                             # noqa: F401

@@ -89,6 +89,9 @@ _SIGS = {
     "bnr_chains_rank_diag": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 6),
     "bnr_rank_normalize": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
     "bnr_host_ndtri": (C.c_double, [C.c_double]),
+    "bnr_chain_hdi": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp] + [_dp] * 5),
+    "bnr_chains_hdi": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp] + [_dp] * 5),
+    "bnr_hdi": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp] + [_dp] * 5),
     "bnr_comm_unique_id": (C.c_int, [C.POINTER(UniqueId)]),
     "bnr_comm_create_rccl": (C.c_int, [C.POINTER(UniqueId), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "bnr_comm_create_callback": (C.c_int, [C.c_int32, C.c_int32, ALLGATHER_CB, C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -293,6 +296,43 @@ def rank_normalize_raw(x, device=0, ranks=True, z=True):
         raise BnrError(BNR_ERR_HIP, _foreign_hip)
     check(L.bnr_rank_normalize(int(device), m, S, _ptr(a), _ptr(r), _ptr(zz)))
     return r, zz
+
+
+HDI_FIELDS = ("lower", "upper", "median", "p_pos", "p_neg")
+
+
+def hdi_probs(probs):
+    """the levels of an HDI call as a float64 vector (a scalar is one level); ValueError (before any library call) unless there are at most 8
+    and every one lies in (0, 1)"""
+    pr = np.ascontiguousarray(np.atleast_1d(np.asarray(probs, dtype=np.float64)).reshape(-1))
+    if pr.size > 8:
+        raise ValueError("at most 8 HDI levels in one call, not %d" % pr.size)
+    if not np.all((pr > 0.0) & (pr < 1.0)):
+        raise ValueError("every HDI level must lie in (0, 1), not %r" % (pr.tolist(),))
+    return pr
+
+
+def _hdi_outputs(pr, m, fields):
+    """the five output arrays of an HDI call over m columns: lower / upper (nprob, m), median / p_pos / p_neg (m,); None where not in `fields`"""
+    shapes = dict(lower=(pr.size, m), upper=(pr.size, m), median=(m,), p_pos=(m,), p_neg=(m,))
+    return [np.empty(shapes[f]) if f in fields else None for f in HDI_FIELDS]
+
+
+def hdi_raw(x, probs, device=0, fields=HDI_FIELDS):
+    """The tuple HDI_FIELDS of every row of an m x S matrix, each row on its own, on the device (bnr_hdi): lower / upper (nprob, m) -- the
+    highest-density interval of every level of `probs` --, the median, and the shares of draws above and below zero (m,); an entry not named
+    in `fields` is not requested and comes back as None"""
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("x must be an m x S matrix (rows x draws) with m, S >= 1")
+    pr = hdi_probs(probs)
+    m, S = a.shape
+    out = _hdi_outputs(pr, m, fields)
+    L = lib()
+    if _foreign_hip:
+        raise BnrError(BNR_ERR_HIP, _foreign_hip)
+    check(L.bnr_hdi(int(device), m, S, _ptr(a), pr.size, _ptr(pr), *[_ptr(o) for o in out]))
+    return tuple(out)
 
 
 X_DTYPES = {np.dtype(np.float64): 0, np.dtype(np.bool_): 1, np.dtype(np.uint8): 1, np.dtype(np.int32): 2, np.dtype(np.int64): 3,
@@ -530,6 +570,15 @@ class Chain:
         check(self.L.bnr_chain_rank_diag(self.h, int(first_row), int(nsamp), int(max_lag), *[_ptr(o) for o in out]))
         return tuple(out)
 
+    def hdi(self, first_row, nsamp, probs, fields=HDI_FIELDS):
+        """The highest-density intervals, medians and sign probabilities of this chain's window, on the device (bnr_chain_hdi): the tuple
+        HDI_FIELDS over the q + V parameters (gamma first), lower / upper one row per level of `probs`; an entry not named in `fields` is not
+        requested and comes back as None"""
+        pr = hdi_probs(probs)
+        out = _hdi_outputs(pr, self.q + self.V, fields)
+        check(self.L.bnr_chain_hdi(self.h, int(first_row), int(nsamp), pr.size, _ptr(pr), *[_ptr(o) for o in out]))
+        return tuple(out)
+
     def counters(self):
         out = (C.c_int64 * 8)()
         check(self.L.bnr_chain_counters(self.h, out))
@@ -719,6 +768,16 @@ def pooled_rank_diag(chains, first_row, nsamp, max_lag, fields=None):
     fields = RANK_DIAG_FIELDS if fields is None else fields
     out = [np.empty(c0.q + c0.V) if f in fields else None for f in RANK_DIAG_FIELDS]
     check(c0.L.bnr_chains_rank_diag(arr, len(chains), int(first_row), int(nsamp), int(max_lag), *[_ptr(o) for o in out]))
+    return tuple(out)
+
+
+def pooled_hdi(chains, first_row, nsamp, probs, fields=HDI_FIELDS):
+    """Chain.hdi over the pooled window of `chains` (bnr_chains_hdi): the tuple HDI_FIELDS"""
+    chains, arr = _pooled(chains)
+    c0 = chains[0]
+    pr = hdi_probs(probs)
+    out = _hdi_outputs(pr, c0.q + c0.V, fields)
+    check(c0.L.bnr_chains_hdi(arr, len(chains), int(first_row), int(nsamp), pr.size, _ptr(pr), *[_ptr(o) for o in out]))
     return tuple(out)
 
 

@@ -20,6 +20,8 @@ Julia is not available in this image, so the thin host layer a Julia user would 
                                                LOO predictive checks: LOOPredict / LOOPredictive, psis_weights, device_loo_predict;
                                                rank-normalised R-hat / ESS / MCSE: RankDiagnose / RankDiagnostics, rank_normalize,
                                                device_rank_diagnostics, _host_rank_diagnostics
+                                               highest-density intervals, sign probabilities, edge selection: EdgeSelect / EdgeSelection,
+                                               hdi, device_edge_selection, _host_hdi
   lower_triangle / create_lower_tri / setup_X!  utils.jl:17-57, gibbs.jl:239-247
 
 All sampling runs on the GPU through libbnr_hip.so; this file holds only the schedule logic (chain fan-out,
@@ -27,6 +29,7 @@ PSRF-driven top-ups), the table layout and the post-processing that the referenc
 Chains are placed one (or several) per GPU; with torch.distributed initialised, chains are sharded over ranks and
 the per-chain split-Rhat statistics are all-gathered (RCCL on GPUs, gloo on CPU tests).
 """
+import dataclasses
 import datetime
 import math
 import random
@@ -97,6 +100,7 @@ class Results:
     loo: dict = None                 # filled on request (loo=True): PSIS-LOO of the training rows computed on the GPU (see LOO)
     loo_predictive: "LOOPredictive" = None   # filled on request (loo_predict=True): the LOO predictive checks of the training rows (see LOOPredict)
     rank_diag: "RankDiagnostics" = None   # filled on request (rank_diagnostics=True): rank-normalised R-hat, bulk / tail ESS and MCSE over every chain (see RankDiagnose)
+    edge_selection: "EdgeSelection" = None   # filled on request (edge_selection=True): HDIs, sign probabilities and the selected edges over every chain (see EdgeSelect)
     stat_chains: int = None          # how many chains the device statistics above (summary_device, prediction, waic, loo, loo_predictive) cover: 1 (chain 1's window), or
                                      # every chain of the fit with pool_chains=True; None when the fit computed none
 
@@ -573,6 +577,165 @@ def RankDiagnose(results, max_lag=None):
     if results.state is None:
         raise ValueError("RankDiagnose needs Fit(..., rank_diagnostics=True), or the state table (return_state=True)")
     return _host_rank_diagnostics([results.state], results.burn_in, results.sampled, max_lag)
+
+
+# ------------------------------------------------------------------------------------------ highest-density intervals and edge selection (additions)
+# Per parameter over the pooled window of the chains of one device (include/bnr_hip.h, ABI 13): the highest-density interval of the sample as
+# ArviZ's hdi and R's HDInterval::hdi compute it (the shortest window of floor(prob n) + 1 consecutive order statistics, the first among equal
+# widths), the median, and the sign probabilities P(x > 0), P(x < 0) as exact shares of the draws.  From them the local false sign rate of every
+# edge, lfsr = 1 - max(p_pos, p_neg) (Stephens 2017), and the largest set of edges whose mean lfsr -- the expected share of wrongly signed
+# edges in the set -- stays within `fdr`.
+def _host_hdi(x, probs):
+    """bnr_hdi restated in numpy for the rows of an m x S matrix (a vector is one row): dict of lower / upper (nprob, m), median, p_pos, p_neg
+    (m,).  The device's conventions: -0 counts and is reported as +0; a row with a NaN is NaN throughout; a row with an infinite draw is NaN in
+    lower, upper and median.  The fallback over fetched tables and the yardstick of the GPU tests."""
+    a = np.asarray(x, dtype=np.float64)
+    a = a.reshape(1, -1) if a.ndim == 1 else a
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("x must be an m x S matrix (rows x draws) with m, S >= 1")
+    pr = _capi.hdi_probs(probs)
+    m, n = a.shape
+    lower, upper = np.full((pr.size, m), np.nan), np.full((pr.size, m), np.nan)
+    median, p_pos, p_neg = np.full(m, np.nan), np.full(m, np.nan), np.full(m, np.nan)
+    for i in range(m):
+        row = a[i]
+        if np.isnan(row).any():
+            continue
+        p_pos[i], p_neg[i] = np.count_nonzero(row > 0) / n, np.count_nonzero(row < 0) / n
+        if np.isinf(row).any():
+            continue
+        xs = np.sort(row + 0.0)                                      # (-0 + 0 = +0)
+        median[i] = (xs[n // 2 - 1] + xs[n // 2]) / 2.0 if n >= 2 else xs[0]
+        for k, prob in enumerate(pr):
+            w = min(int(np.floor(prob * n)), n - 1)
+            j = int(np.argmin(xs[w:] - xs[:n - w]))
+            lower[k, i], upper[k, i] = xs[j], xs[j + w]
+    return dict(lower=lower, upper=upper, median=median, p_pos=p_pos, p_neg=p_neg)
+
+
+def hdi(x, prob=0.95, device=None):
+    """Highest-density intervals of every row of an m x S matrix (rows x draws), each row on its own, on the GPU (bnr_hdi): dict with lower and
+    upper (the shortest interval holding floor(prob S) + 1 consecutive order statistics: ArviZ's hdi for a unimodal sample), median, p_pos and
+    p_neg (the shares of draws above and below zero).  prob: one level, or up to 8 -- lower / upper then get a leading axis of levels.  A row
+    with a NaN is NaN throughout; one with an infinite draw is NaN in lower, upper and median.  A vector is taken as one row."""
+    a = np.asarray(x, dtype=np.float64)
+    out = dict(zip(_capi.HDI_FIELDS, _capi.hdi_raw(a.reshape(1, -1) if a.ndim == 1 else a, prob, 0 if device is None else int(device))))
+    lead = () if np.ndim(prob) == 0 else (-1,)
+    tail = a.shape[:-1]
+    for k in ("lower", "upper"):
+        out[k] = out[k].reshape(lead + tail)
+    for k in ("median", "p_pos", "p_neg"):
+        out[k] = out[k].reshape(tail)
+    return out
+
+
+@dataclass
+class EdgeSelection:
+    """Per edge (q, in Summary's order): node1, node2, estimate (the posterior median), hdi_lower / hdi_upper (the hdi_prob highest-density
+    interval), p_pos / p_neg (the shares of draws above / below zero), lfsr = 1 - max(p_pos, p_neg) (the local false sign rate),
+    hdi_excludes_zero, selected (the largest set of edges whose mean lfsr is at most fdr).  Per node (V): xi_estimate, xi_hdi_lower,
+    xi_hdi_upper and prob_nodes (the share of draws with xi = 1).  expected_fsr: the mean lfsr of the selected edges (0 when none is); draws:
+    the pooled draws per parameter."""
+    node1: np.ndarray
+    node2: np.ndarray
+    estimate: np.ndarray
+    hdi_lower: np.ndarray
+    hdi_upper: np.ndarray
+    p_pos: np.ndarray
+    p_neg: np.ndarray
+    lfsr: np.ndarray
+    hdi_excludes_zero: np.ndarray
+    selected: np.ndarray
+    xi_estimate: np.ndarray
+    xi_hdi_lower: np.ndarray
+    xi_hdi_upper: np.ndarray
+    prob_nodes: np.ndarray
+    hdi_prob: float
+    fdr: float
+    n_selected: int
+    expected_fsr: float
+    chains: int
+    draws: int
+
+
+def _edge_levels(hdi_prob, fdr):
+    """(hdi_prob, fdr) as floats; ValueError unless 0 < hdi_prob < 1 and 0 <= fdr <= 1"""
+    hdi_prob, fdr = float(hdi_prob), float(fdr)
+    if not (0.0 < hdi_prob < 1.0):
+        raise ValueError("need 0 < hdi_prob < 1, not %r" % hdi_prob)
+    if not (0.0 <= fdr <= 1.0):
+        raise ValueError("need 0 <= fdr <= 1, not %r" % fdr)
+    return hdi_prob, fdr
+
+
+def _select_by_lfsr(lfsr, fdr):
+    """(selected, expected_fsr): the edges in the order of their lfsr (stable: ties by edge index), the longest prefix whose running mean of
+    lfsr is at most fdr; expected_fsr is that mean, 0.0 when nothing is selected.  An edge whose lfsr is NaN is never selected."""
+    lfsr = np.asarray(lfsr, dtype=np.float64)
+    sel = np.zeros(lfsr.size, dtype=bool)
+    cand = np.flatnonzero(~np.isnan(lfsr))
+    order = cand[np.argsort(lfsr[cand], kind="stable")]
+    if order.size == 0:
+        return sel, 0.0
+    run = np.cumsum(lfsr[order]) / np.arange(1, order.size + 1)
+    ok = np.flatnonzero(run <= fdr)
+    if ok.size == 0:
+        return sel, 0.0
+    k = int(ok[-1]) + 1                                              # (the running mean of a sorted vector never decreases: a prefix)
+    sel[order[:k]] = True
+    return sel, float(run[k - 1])
+
+
+def _edge_selection(q, fields, hdi_prob, fdr, nchains, draws):
+    """EdgeSelection from the five arrays of HDI_FIELDS over q + V parameters at one level"""
+    lower, upper, median, p_pos, p_neg = (np.asarray(f, dtype=np.float64).reshape(-1) for f in fields)
+    V = lower.size - q
+    node1 = np.concatenate([np.full(V - k + 1, k) for k in range(1, V + 1)])
+    node2 = np.concatenate([np.arange(k, V + 1) for k in range(1, V + 1)])
+    lfsr = 1.0 - np.maximum(p_pos[:q], p_neg[:q])                    # (NaN where the shares are)
+    selected, efsr = _select_by_lfsr(lfsr, fdr)
+    return EdgeSelection(node1=node1, node2=node2, estimate=median[:q].copy(), hdi_lower=lower[:q].copy(), hdi_upper=upper[:q].copy(),
+                         p_pos=p_pos[:q].copy(), p_neg=p_neg[:q].copy(), lfsr=lfsr, hdi_excludes_zero=(lower[:q] > 0) | (upper[:q] < 0),
+                         selected=selected, xi_estimate=median[q:].copy(), xi_hdi_lower=lower[q:].copy(), xi_hdi_upper=upper[q:].copy(),
+                         prob_nodes=p_pos[q:].copy(), hdi_prob=hdi_prob, fdr=fdr, n_selected=int(selected.sum()), expected_fsr=efsr,
+                         chains=nchains, draws=draws)
+
+
+def device_edge_selection(chains, nburn, nsamp, hdi_prob=0.95, fdr=0.05):
+    """The HDIs, sign probabilities and selected edges over the pooled windows nburn+1 .. nburn+nsamp of live chains, on the device
+    (bnr_chains_hdi): only 5 (q + V) numbers leave the GPU's side of the call"""
+    chains = list(chains)
+    hdi_prob, fdr = _edge_levels(hdi_prob, fdr)
+    out = _capi.pooled_hdi(chains, nburn + 1, nsamp, hdi_prob)
+    return _edge_selection(chains[0].q, out, hdi_prob, fdr, len(chains), len(chains) * int(nsamp))
+
+
+def _host_edge_selection(tables, nburn, nsamp, hdi_prob=0.95, fdr=0.05):
+    """device_edge_selection restated in numpy over the fetched tables of the same chains (_host_hdi on the pooled windows)"""
+    tables = list(tables)
+    if not tables:
+        raise ValueError("need at least one table")
+    hdi_prob, fdr = _edge_levels(hdi_prob, fdr)
+    q = tables[0]["gamma"].shape[1]
+    w = np.concatenate([np.concatenate([t["gamma"][nburn:nburn + nsamp, :, 0], t["xi"][nburn:nburn + nsamp, :, 0]], axis=1) for t in tables], axis=0)
+    h = _host_hdi(w.T, hdi_prob)
+    return _edge_selection(q, [h[f] for f in _capi.HDI_FIELDS], hdi_prob, fdr, len(tables), w.shape[0])
+
+
+def EdgeSelect(results, hdi_prob=None, fdr=None):
+    """The edge selection of a fit -> EdgeSelection.  Uses the GPU's numbers when the fit carried them (edge_selection=True: every chain of
+    the fit; another fdr re-applies the rule to them), otherwise restates them on the host over results.state (needs return_state=True; chain
+    1 alone; defaults hdi_prob = 0.95, fdr = 0.05)."""
+    es = results.edge_selection
+    if es is not None and (hdi_prob is None or float(hdi_prob) == es.hdi_prob):
+        if fdr is None or float(fdr) == es.fdr:
+            return es
+        _, fdr = _edge_levels(es.hdi_prob, fdr)
+        selected, efsr = _select_by_lfsr(es.lfsr, fdr)
+        return dataclasses.replace(es, fdr=fdr, selected=selected, n_selected=int(selected.sum()), expected_fsr=efsr)
+    if results.state is None:
+        raise ValueError("EdgeSelect needs Fit(..., edge_selection=True), or the state table (return_state=True)")
+    return _host_edge_selection([results.state], results.burn_in, results.sampled, 0.95 if hdi_prob is None else hdi_prob, 0.05 if fdr is None else fdr)
 
 
 # ------------------------------------------------------------------------------------------ pooled chains, predictive intervals, PIT (additions)
@@ -1126,13 +1289,16 @@ def return_psrf_VOI(chainset, nburn, nsamp, fetch_state=True, summary_interval=N
 
 
 def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None, predict=None, waic=False, loo=False, loo_r_eff=None,
-            pool_chains=False, predict_observation=False, pred_seed=0, loo_predict=None, rank_diag=False):
+            pool_chains=False, predict_observation=False, pred_seed=0, loo_predict=None, rank_diag=False, edge_sel=None):
     """The Results a fit returns: chain 1's table (states[1], gibbs.jl:788) and/or its Summary statistics from the device; predict =
     (new rows, their y or None, interval), waic=True and loo=True add the prediction, WAIC and PSIS-LOO computed on the device over the
     same window.  pool_chains: those statistics over the pooled windows of all chains of the fit (one rank holds them all);
     predict_observation: the prediction through the pooled entry point (one chain unless pool_chains) with the predictive bounds and the PIT;
     loo_predict = (training y, interval): the LOO predictive checks (Results.loo_predictive), and Results.loo from the same call.
-    rank_diag: the rank-normalised diagnostics over every chain of the fit (Results.rank_diag; ess_max_lag, where positive, is their lag window)."""
+    rank_diag: the rank-normalised diagnostics over every chain of the fit (Results.rank_diag; ess_max_lag, where positive, is their lag window).
+    edge_sel = (hdi_prob, fdr): the HDIs, sign probabilities and selected edges over every chain of the fit (Results.edge_selection)."""
+    if edge_sel is not None:
+        res.edge_selection = device_edge_selection([chainset.chains[c] for c in chainset.ids], res.burn_in, res.sampled, edge_sel[0], edge_sel[1])
     if rank_diag:
         res.rank_diag = device_rank_diagnostics([chainset.chains[c] for c in chainset.ids], res.burn_in, res.sampled, ess_max_lag if ess_max_lag else None)
     if pool_chains or predict_observation:
@@ -1216,6 +1382,16 @@ def _rank_diag_request(rank_diagnostics, nsamp=None, ess_max_lag=None):
     return True
 
 
+def _edge_selection_request(edge_selection, hdi_prob, fdr):
+    """Fit's edge_selection checked before any sampling: (hdi_prob, fdr) for _finish, or None.  Like rank_diagnostics it needs every chain of
+    the fit on this rank."""
+    if not edge_selection:
+        return None
+    if _rank_world()[1] > 1:
+        raise ValueError("edge_selection needs every chain of the fit on one rank: the chains are spread over %d torch.distributed ranks" % _rank_world()[1])
+    return _edge_levels(hdi_prob, fdr)
+
+
 def _pooled_request(pool_chains, predict_observation, predict_X):
     """Fit's pool_chains / predict_observation checked before any sampling"""
     if predict_observation and predict_X is None:
@@ -1262,7 +1438,8 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                      maxburn=50000, psrf_cutoff=1.2, x_transform=True, suppress_timer=False, num_chains=2, seed=None,
                      purge_burn=None, device=None, _keep=None, return_state=True, summary_interval=None, ess_max_lag=None,
                      xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
-                     pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False):
+                     pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
+                     hdi_prob=0.95, fdr=0.05):
     """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
     xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
     xi_weights_code(xi_weights)
@@ -1275,6 +1452,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
     _pooled_request(pool_chains, predict_observation, predict_X)
     lp_req = _loo_predict_request(loo_predict, predict_interval, y)
     rd_req = _rank_diag_request(rank_diagnostics, nsamp, ess_max_lag)
+    es_req = _edge_selection_request(edge_selection, hdi_prob, fdr)
     _capi.r_eff_array(loo_r_eff, X_new.n)              # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
@@ -1318,7 +1496,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
     print("R = %s nu=%s nburn= %d nsamp = %d" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f\n" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
     res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff, pool_chains, predict_observation,
-                  seed_eff if pred_seed is None else pred_seed, lp_req, rd_req)
+                  seed_eff if pred_seed is None else pred_seed, lp_req, rd_req, es_req)
     if _keep is None:
         cs.close()
     return res
@@ -1328,7 +1506,8 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                          maxgen=100000, psrf_cutoff=1.01, x_transform=True, suppress_timer=False, num_chains=2,
                          seed=None, purge_burn=None, device=None, return_state=True, summary_interval=None, ess_max_lag=None,
                          xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
-                         pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False):
+                         pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
+                         hdi_prob=0.95, fdr=0.05):
     """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
     xi_weights_code(xi_weights)
     if nu == R:
@@ -1340,6 +1519,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
     _pooled_request(pool_chains, predict_observation, predict_X)
     lp_req = _loo_predict_request(loo_predict, predict_interval, y)
     rd_req = _rank_diag_request(rank_diagnostics, nsamp, ess_max_lag)
+    es_req = _edge_selection_request(edge_selection, hdi_prob, fdr)
     _capi.r_eff_array(loo_r_eff, X_new.n)              # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
@@ -1385,7 +1565,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
     print("\nR = %s nu=%s nburn= %d nsamp = %d\n" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.4f. Max PSRF Gamma: %.4f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
     res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff, pool_chains, predict_observation,
-                  seed_eff if pred_seed is None else pred_seed, lp_req, rd_req)
+                  seed_eff if pred_seed is None else pred_seed, lp_req, rd_req, es_req)
     cs.close()
     return res
 
@@ -1394,7 +1574,8 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
         mingen=0, maxgen=0, psrf_cutoff=1.01, x_transform=True, suppress_timer=False, num_chains=2, seed=None,
         purge_burn=None, filename="parameters.log", device=None, return_state=True, summary_interval=None, ess_max_lag=None,
         xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
-        pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False):
+        pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
+        hdi_prob=0.95, fdr=0.05):
     """Fit! (gibbs.jl:725-751).  The `V` keyword is accepted and ignored, as in the reference.
     Extensions: summary_interval=95 computes Summary's statistics on the GPU (Results.summary_device);
     return_state=False then leaves the (large) state table on the device and frees it; ess_max_lag=0 (default lag
@@ -1412,11 +1593,15 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     from the same device call), honours pool_chains and loo_r_eff, and like pool_chains needs every chain of the fit on this rank.
     rank_diagnostics=True adds the rank-normalised R-hat, bulk / tail ESS and MCSE over every chain of the fit, computed on the GPU from the
     resident traces (Results.rank_diag, see RankDiagnose; ess_max_lag, where positive, is their lag window); every chain must live on this rank.
+    edge_selection=True adds the hdi_prob highest-density interval, the median and the sign probabilities of every edge coefficient and node
+    indicator, and the largest set of edges whose expected false sign rate stays within fdr, computed on the GPU from the resident traces over
+    every chain of the fit (Results.edge_selection, see EdgeSelect); every chain must live on this rank.
     parameters.log keeps the reference's lines only."""
     xi_weights_code(xi_weights)
     _pooled_request(pool_chains, predict_observation, predict_X)
     _loo_predict_request(loo_predict, predict_interval, y)
     _rank_diag_request(rank_diagnostics)
+    _edge_selection_request(edge_selection, hdi_prob, fdr)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
         with open(filename, "w") as f:
@@ -1435,11 +1620,12 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                                     return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
                                     xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval,
                                     waic=waic, loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation,
-                                    pred_seed=pred_seed, loo_predict=loo_predict, rank_diagnostics=rank_diagnostics)
+                                    pred_seed=pred_seed, loo_predict=loo_predict, rank_diagnostics=rank_diagnostics,
+                                    edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
                             return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
                             xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic,
                             loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed,
-                            loo_predict=loo_predict, rank_diagnostics=rank_diagnostics)
+                            loo_predict=loo_predict, rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr)

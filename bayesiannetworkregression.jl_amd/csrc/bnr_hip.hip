@@ -186,6 +186,10 @@ struct rank_bufs { unsigned long long *keyA = nullptr, *keyB = nullptr; unsigned
 static void launch_rank(hipStream_t st, int cols, const double *buf, long long ld, int nsamp, int nch, int all, const rank_bufs &rb, int k05, int k95,
                         double *ranks, double *z, double *ind05, double *ind95, double *med, int *flag);
 static void launch_fold(hipStream_t st, int cols, const double *buf, long long ld, const double *med, int absolute, double *out);
+// highest-density intervals and sign probabilities (ABI 13): k_hdi on `cols` staged columns of n draws with k_rank's key buffers (the index
+// buffers stay unused); launched from the end of this file, behind k_rank / k_fold
+static void launch_hdi(hipStream_t st, int cols, const double *buf, long long ld, int n, const rank_bufs &rb, int nprob, const bnr_hdi_levels &lv, double *lower,
+                       double *upper, long long lstride, double *med, double *p_pos, double *p_neg);
 static int ensure_lds_attributes(int device)
 {
     static std::mutex mu;
@@ -2088,6 +2092,27 @@ static int pooled_quiesce(bnr_chain *const *cs, int nc)
     return BNR_OK;
 }
 
+// Parameter columns p0 .. p0 + pc - 1 of [gamma(q) | xi(V)] over the pooled window, staged by k_fetch_cols: column p of `buf` holds S = nc nsamp
+// draws, chain k's window in rows k nsamp .. (k + 1) nsamp - 1 (one launch per chain and per kind of column)
+static void stage_cols(hipStream_t st, bnr_chain *const *cs, int nc, int first_row, int nsamp, int p0, int pc, double *buf)
+{
+    const bnr_dev &d = cs[0]->d;
+    const long long S = (long long)nc * nsamp;
+    const dim3 block(32, 8);
+    const int g0 = std::min(p0, d.q), g1 = std::min(p0 + pc, d.q);          // gamma columns g0 .. g1 - 1 first, then xi columns x0 .. x1 - 1
+    const int x0 = std::max(p0, d.q) - d.q, x1 = std::max(p0 + pc, d.q) - d.q;
+    for (int k = 0; k < nc; ++k) {
+        const bnr_dev &dk = cs[k]->d;
+        double *dst = buf + (size_t)k * nsamp;
+        if (g1 > g0)
+            hipLaunchKernelGGL(k_fetch_cols, dim3((g1 - g0 + 31) / 32, (nsamp + 31) / 32), block, 0, st, (const double *)dk.trace, dk.rowlen,
+                               dk.o_gamma + g0, g1 - g0, first_row - 1, nsamp, dst, S);
+        if (x1 > x0)
+            hipLaunchKernelGGL(k_fetch_cols, dim3((x1 - x0 + 31) / 32, (nsamp + 31) / 32), block, 0, st, (const double *)dk.trace, dk.rowlen,
+                               dk.o_xi + x0, x1 - x0, first_row - 1, nsamp, dst + (size_t)(g1 - g0) * (size_t)S, S);
+    }
+}
+
 // Summary(results) on the device (gibbs.jl:1214-1250): posterior mean and two order statistics of every gamma_e over rows
 // first_row .. first_row+nsamp-1 of every chain listed (pooled: S = nc nsamp draws, draw c nsamp + s = chain c's s-th window row), and the mean
 // of every xi_v.  3q + V doubles cross PCIe instead of the gamma traces.  The q + V parameter columns are staged (k_fetch_cols, one launch per
@@ -2114,23 +2139,11 @@ static int summary_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t
     result_slab out;                                    // the mean, the lower and the upper statistic of the np = q + V parameters, gamma first
     if ((rc = tmp.alloc(&buf, (size_t)blk * (size_t)S, st, false))) return rc;
     if ((rc = out.alloc(tmp, 3, (size_t)np, st))) return rc;
-    const dim3 block(32, 8);
     for (int p0 = 0; p0 < np; p0 += (int)blk) {
         const int pc = std::min<int>((int)blk, np - p0);
-        const int g0 = std::min(p0, d.q), g1 = std::min(p0 + pc, d.q);          // gamma columns g0 .. g1 - 1 first, then xi columns x0 .. x1 - 1
-        const int x0 = std::max(p0, d.q) - d.q, x1 = std::max(p0 + pc, d.q) - d.q;
-        for (int k = 0; k < nc; ++k) {
-            const bnr_dev &dk = cs[k]->d;
-            double *dst = buf + (size_t)k * nsamp;
-            if (g1 > g0)
-                hipLaunchKernelGGL(k_fetch_cols, dim3((g1 - g0 + 31) / 32, (nsamp + 31) / 32), block, 0, st, (const double *)dk.trace, dk.rowlen,
-                                   dk.o_gamma + g0, g1 - g0, first_row - 1, nsamp, dst, S);
-            if (x1 > x0)
-                hipLaunchKernelGGL(k_fetch_cols, dim3((x1 - x0 + 31) / 32, (nsamp + 31) / 32), block, 0, st, (const double *)dk.trace, dk.rowlen,
-                                   dk.o_xi + x0, x1 - x0, first_row - 1, nsamp, dst + (size_t)(g1 - g0) * (size_t)S, S);
-        }
-        hipLaunchKernelGGL(k_summary, dim3(pc), dim3(256), 0, st, (const double *)buf, (int)S, g1 - g0, k_lo, k_hi, out.col(0) + p0, out.col(1) + p0,
-                           out.col(2) + p0);
+        stage_cols(st, cs, nc, first_row, nsamp, p0, pc, buf);
+        hipLaunchKernelGGL(k_summary, dim3(pc), dim3(256), 0, st, (const double *)buf, (int)S, std::min(p0 + pc, d.q) - std::min(p0, d.q), k_lo, k_hi,
+                           out.col(0) + p0, out.col(1) + p0, out.col(2) + p0);
     }
     std::vector<double> host(3 * (size_t)np);           // (the callers' arrays hold q and V entries, not q + V)
     if ((rc = out.fetch(st, "summary", "k_summary", {host.data(), host.data() + np, host.data() + 2 * (size_t)np}))) return rc;
@@ -2251,21 +2264,9 @@ static int rank_diag_call(bnr_chain *const *cs, int nc, int32_t first_row, int32
     std::vector<double> o_rb(np, nanv), o_rt(np, nanv), o_eb(np, nanv), o_et(np, nanv), o_em(np, nanv), o_mc(np, nanv);
     std::vector<int> flags(2 * (size_t)blk);
     split_msg sz, s05, s95, sx, sf;
-    const dim3 block(32, 8);
     for (int p0 = 0; p0 < np; p0 += (int)blk) {
         const int pc = std::min<int>((int)blk, np - p0);
-        const int g0 = std::min(p0, d.q), g1 = std::min(p0 + pc, d.q);
-        const int x0 = std::max(p0, d.q) - d.q, x1 = std::max(p0 + pc, d.q) - d.q;
-        for (int k = 0; k < nc; ++k) {
-            const bnr_dev &dk = cs[k]->d;
-            double *dst = X + (size_t)k * nsamp;
-            if (g1 > g0)
-                hipLaunchKernelGGL(k_fetch_cols, dim3((g1 - g0 + 31) / 32, (nsamp + 31) / 32), block, 0, st, (const double *)dk.trace, dk.rowlen,
-                                   dk.o_gamma + g0, g1 - g0, first_row - 1, nsamp, dst, S);
-            if (x1 > x0)
-                hipLaunchKernelGGL(k_fetch_cols, dim3((x1 - x0 + 31) / 32, (nsamp + 31) / 32), block, 0, st, (const double *)dk.trace, dk.rowlen,
-                                   dk.o_xi + x0, x1 - x0, first_row - 1, nsamp, dst + (size_t)(g1 - g0) * (size_t)S, S);
-        }
+        stage_cols(st, cs, nc, first_row, nsamp, p0, pc, X);
         // one series: k_acov on the block's pc nc windows, its message fetched and laid out per chain; the ESS where lags were asked for
         auto series = [&](const double *data, int L, split_msg &m) -> int {
             const size_t cnt = (size_t)2 * (2 + L) * (size_t)pc * nc;
@@ -2378,6 +2379,134 @@ int bnr_rank_normalize(int32_t device, int32_t m, int32_t S, const double *x, do
     hipError_t e = hipStreamSynchronize(st);
     if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("rank_normalize: ") + hipGetErrorString(e));
     return check_launch("k_rank");
+}
+
+// Highest-density intervals, the median and the sign probabilities (ABI 13) of every parameter in [gamma(q) | xi(V)] over the pooled window of
+// the chains listed, or of every row of a caller's matrix: include/bnr_hip.h.  hdi_args: the checks that need no device, and the window length
+// w = floor(prob n) of every level (in double, as numpy does; at most n - 1).
+static int hdi_args(long long n, int32_t nprob, const double *probs, const double *lower, const double *upper, const double *median, const double *p_pos,
+                    const double *p_neg, bnr_hdi_levels &lv)
+{
+    if (!lower && !upper && !median && !p_pos && !p_neg) return fail(BNR_ERR_BAD_ARG, "no output requested");
+    if (!lower != !upper) return fail(BNR_ERR_BAD_ARG, "lower and upper come together");
+    if (nprob < 0 || nprob > 8) return fail(BNR_ERR_BAD_ARG, "need 0 <= nprob <= 8 levels");
+    if (nprob > 0 && !probs) return fail(BNR_ERR_BAD_ARG, "probs is NULL");
+    if (lower && nprob < 1) return fail(BNR_ERR_BAD_ARG, "lower and upper need nprob >= 1 levels");
+    for (int k = 0; k < 8; ++k) lv.w[k] = 0;
+    for (int k = 0; k < nprob; ++k) {
+        if (!(probs[k] > 0.0 && probs[k] < 1.0)) return fail(BNR_ERR_BAD_ARG, "every level must lie in (0, 1)");
+        lv.w[k] = (int)std::min<double>(floor(probs[k] * (double)n), (double)(n - 1));
+    }
+    return BNR_OK;
+}
+// the results of an hdi call on the device: nprob lower and nprob upper bounds, the median, p_pos and p_neg of np columns each
+struct hdi_slab {
+    double *d = nullptr;
+    size_t np = 0;
+    int nprob = 0;
+    int alloc(dev_tmp &tmp, int levels, size_t cols, hipStream_t st) { nprob = levels; np = cols; return tmp.alloc(&d, (size_t)(2 * nprob + 3) * np, st); }
+    double *lower() const { return d; }
+    double *upper() const { return d + (size_t)nprob * np; }
+    double *med() const { return d + (size_t)2 * nprob * np; }
+    double *p_pos() const { return med() + np; }
+    double *p_neg() const { return med() + 2 * np; }
+    int fetch(hipStream_t st, double *lo, double *up, double *median, double *pp, double *pn) const
+    {
+        std::vector<double> host((size_t)(2 * nprob + 3) * np);
+        hipError_t e = hipMemcpyAsync(host.data(), d, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("hdi: ") + hipGetErrorString(e));
+        if (int rc = check_launch("k_hdi")) return rc;
+        const double *h = host.data();
+        if (lo) memcpy(lo, h, sizeof(double) * nprob * np);
+        if (up) memcpy(up, h + (size_t)nprob * np, sizeof(double) * nprob * np);
+        h += (size_t)2 * nprob * np;
+        if (median) memcpy(median, h, sizeof(double) * np);
+        if (pp) memcpy(pp, h + np, sizeof(double) * np);
+        if (pn) memcpy(pn, h + 2 * np, sizeof(double) * np);
+        return BNR_OK;
+    }
+};
+static int hdi_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t nprob, const double *probs, double *lower, double *upper,
+                    double *median, double *p_pos, double *p_neg)
+{
+    bnr_chain *c = cs[0];
+    const bnr_dev &d = c->d;
+    const long long S = (long long)nc * nsamp;
+    bnr_hdi_levels lv;
+    int rc;
+    if ((rc = hdi_args(S, nprob, probs, lower, upper, median, p_pos, p_neg, lv))) return rc;
+    const int np = d.q + d.V, levels = lower ? nprob : 0;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->x.stream;
+    if ((rc = pooled_quiesce(cs, nc))) return rc;
+    const size_t budget = (size_t)1 << 30;
+    long long blk = c->rank_block_cols > 0 ? c->rank_block_cols : (long long)(budget / ((size_t)S * sizeof(double)));
+    blk = std::min<long long>(std::max<long long>(blk, 1), np);
+    dev_tmp tmp;
+    double *X = nullptr;
+    rank_bufs rb;
+    hdi_slab out;
+    const size_t cells = (size_t)blk * (size_t)S;
+    if ((rc = tmp.alloc(&X, cells, st, false)) || (rc = tmp.alloc(&rb.keyA, cells, st, false)) || (rc = tmp.alloc(&rb.keyB, cells, st, false))) return rc;
+    if ((rc = out.alloc(tmp, levels, (size_t)np, st))) return rc;
+    for (int p0 = 0; p0 < np; p0 += (int)blk) {
+        const int pc = std::min<int>((int)blk, np - p0);
+        stage_cols(st, cs, nc, first_row, nsamp, p0, pc, X);
+        launch_hdi(st, pc, X, S, (int)S, rb, levels, lv, levels ? out.lower() + p0 : nullptr, levels ? out.upper() + p0 : nullptr, np, out.med() + p0,
+                   out.p_pos() + p0, out.p_neg() + p0);
+    }
+    return out.fetch(st, lower, upper, median, p_pos, p_neg);
+}
+int bnr_chain_hdi(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t nprob, const double *probs, double *lower, double *upper, double *median,
+                  double *p_pos, double *p_neg)
+{
+    if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
+    return hdi_call(&c, 1, first_row, nsamp, nprob, probs, lower, upper, median, p_pos, p_neg);
+}
+int bnr_chains_hdi(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t nprob, const double *probs, double *lower,
+                   double *upper, double *median, double *p_pos, double *p_neg)
+{
+    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
+    return hdi_call(chains, nchains, first_row, nsamp, nprob, probs, lower, upper, median, p_pos, p_neg);
+}
+// k_hdi on every row of a caller's m x S matrix (host, row-major), each row on its own: k_hdi's direct test, as bnr_rank_normalize is k_rank's.
+// On a stream of its own, the rows in blocks of about 256 MiB.
+int bnr_hdi(int32_t device, int32_t m, int32_t S, const double *x, int32_t nprob, const double *probs, double *lower, double *upper, double *median,
+            double *p_pos, double *p_neg)
+{
+    if (!x) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (m < 1 || S < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows and S >= 1 draws");
+    bnr_hdi_levels lv;
+    int rc;
+    if ((rc = hdi_args(S, nprob, probs, lower, upper, median, p_pos, p_neg, lv))) return rc;
+    const int levels = lower ? nprob : 0;
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
+    HIPCHK(hipSetDevice(device));
+    struct stream_guard {
+        hipStream_t s = nullptr;
+        ~stream_guard() { if (s) (void)hipStreamDestroy(s); }
+    } guard;
+    HIPCHK(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
+    hipStream_t st = guard.s;
+    const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, ((size_t)1 << 28) / ((size_t)S * sizeof(double))));
+    const size_t cells = (size_t)blk * (size_t)S;
+    dev_tmp tmp;                                        // (freed before the stream goes)
+    double *Xd = nullptr;
+    rank_bufs rb;
+    hdi_slab out;
+    if ((rc = tmp.alloc(&Xd, cells, st, false)) || (rc = tmp.alloc(&rb.keyA, cells, st, false)) || (rc = tmp.alloc(&rb.keyB, cells, st, false))) return rc;
+    if ((rc = out.alloc(tmp, levels, (size_t)m, st))) return rc;
+    for (int i0 = 0; i0 < m; i0 += blk) {
+        const int mr = std::min(blk, m - i0);
+        HIPCHK(hipMemcpyAsync(Xd, x + (size_t)i0 * S, sizeof(double) * (size_t)mr * (size_t)S, hipMemcpyHostToDevice, st));
+        launch_hdi(st, mr, Xd, S, S, rb, levels, lv, levels ? out.lower() + i0 : nullptr, levels ? out.upper() + i0 : nullptr, m, out.med() + i0,
+                   out.p_pos() + i0, out.p_neg() + i0);
+    }
+    return out.fetch(st, lower, upper, median, p_pos, p_neg);
 }
 
 // Posterior of the mean response mu + x . gamma of m new rows over rows first_row .. first_row+nsamp-1 of the chains listed (an addition to the
@@ -2984,7 +3113,7 @@ static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, 
 }
 
 // ----------------------------------------------------------------------------------------- every reference to the kernels of the LOO predictive checks (ABI 11)
-// k_rank / k_fold (ABI 12): first referenced here, behind the kernels of the sweep and the late kernels above, in front of the kernels of ABI 11
+// k_rank / k_fold (ABI 12): first referenced here, behind the kernels of the sweep and the late kernels above, in front of k_hdi and the kernels of ABI 11
 static void launch_rank(hipStream_t st, int cols, const double *buf, long long ld, int nsamp, int nch, int all, const rank_bufs &rb, int k05, int k95,
                         double *ranks, double *z, double *ind05, double *ind95, double *med, int *flag)
 {
@@ -2995,6 +3124,12 @@ static void launch_fold(hipStream_t st, int cols, const double *buf, long long l
 {
     const int chunks = (int)((ld + 255) / 256);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fold<0>), dim3((unsigned)chunks * (unsigned)cols), dim3(256), 0, st, buf, ld, chunks, med, absolute, out);
+}
+// k_hdi (ABI 13): first referenced here, behind k_rank / k_fold and in front of the kernels of ABI 11
+static void launch_hdi(hipStream_t st, int cols, const double *buf, long long ld, int n, const rank_bufs &rb, int nprob, const bnr_hdi_levels &lv, double *lower,
+                       double *upper, long long lstride, double *med, double *p_pos, double *p_neg)
+{
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_hdi<0>), dim3(cols), dim3(256), 0, st, buf, ld, n, rb.keyA, rb.keyB, nprob, lv, lower, upper, lstride, med, p_pos, p_neg);
 }
 // k_psis_w: the sorted tail, 12 bytes per entry for up to BNR_PSIS_MAX_TAIL entries (on the current device; cheap enough for once per call)
 static int loow_lds_attributes()

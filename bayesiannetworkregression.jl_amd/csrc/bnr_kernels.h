@@ -4331,6 +4331,87 @@ __global__ __launch_bounds__(256) void k_loo_quantile(const double *E, const dou
 // Ranks are a pure function of the data: equal keys end up in one run whatever order the sort left their indices in, so every output is bitwise
 // independent of the grid, the block of columns and the call.  Every index stays below n <= ld: nothing is written outside the column's slices.
 // 128 VGPRs, 14.1 KiB of LDS, no scratch.
+// Phases 1 and 2 are shared with k_hdi (behind k_fold): IDX = true, the draw's position travels with its key (k_rank); false, keys only -- 8 + 8
+// bytes per draw and pass instead of 12 + 12, and the index buffers are never touched (k_hdi).  The LDS arrays are the caller's.
+template <bool IDX>
+__device__ __forceinline__ void bnr_sort_build_keys(const double *x, int n, int nsamp, int per, int hh, int gap, unsigned long long *src, unsigned int *si,
+                                                    unsigned int (&hist)[8][256], int (&s_skip)[8], int &s_flag)
+{
+    const int tid = threadIdx.x;
+    int myflag = 0;
+    for (int t = tid; t < n; t += 256) {
+        const int c = t / per, u = t - c * per;
+        const unsigned int pos = (unsigned int)(c * nsamp + (u < hh ? u : u + gap));
+        double v = x[pos];
+        if (v != v) myflag |= 1;
+        else if (fabs(v) == INFINITY) myflag |= 2;
+        if (v == 0.0) v = 0.0;                                 // -0 ties with +0
+        const unsigned long long key = bnr_key_of(v);
+        src[t] = key;
+        if constexpr (IDX) si[t] = pos;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) atomicAdd(&hist[b][(unsigned int)(key >> (8 * b)) & 255u], 1u);
+    }
+    if (myflag) atomicOr(&s_flag, myflag);
+    __syncthreads();
+    for (int b = 0; b < 8; ++b) if (hist[b][tid] == (unsigned int)n) s_skip[b] = 1;
+    __syncthreads();
+}
+// (on return src holds the sorted keys -- and si their positions -- and dst / di are free)
+template <bool IDX>
+__device__ __forceinline__ void bnr_sort_passes(int n, unsigned long long *&src, unsigned long long *&dst, unsigned int *&si, unsigned int *&di,
+                                                unsigned int (&hist)[8][256], unsigned int (&base)[256], unsigned int (&tmp)[256],
+                                                unsigned int (&wcnt)[4][256], int (&s_skip)[8])
+{
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    for (int pass = 0; pass < 8; ++pass) {
+        if (s_skip[pass]) continue;                            // (uniform: read behind the barrier above, never written again)
+        const int shift = 8 * pass;
+        const unsigned int mine = hist[pass][tid];
+        tmp[tid] = mine;
+        __syncthreads();
+        for (int off = 1; off < 256; off <<= 1) {
+            const unsigned int a = tid >= off ? tmp[tid - off] : 0u;
+            __syncthreads();
+            tmp[tid] += a;
+            __syncthreads();
+        }
+        base[tid] = tmp[tid] - mine;
+        __syncthreads();
+        for (int t0 = 0; t0 < n; t0 += 256) {
+            const int t = t0 + tid;
+            const bool valid = t < n;
+            const unsigned long long key = valid ? src[t] : 0ull;
+            unsigned int id = 0u;
+            if constexpr (IDX) id = valid ? si[t] : 0u;
+            const unsigned int d = (unsigned int)(key >> shift) & 255u;
+            unsigned long long mask = __ballot(valid);
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                const unsigned long long m = __ballot((d >> b) & 1u);
+                mask &= ((d >> b) & 1u) ? m : ~m;
+            }
+            const unsigned int lrank = (unsigned int)__popcll(mask & below), cnt = (unsigned int)__popcll(mask);
+            if (valid && lrank == 0u) wcnt[w][d] = cnt;
+            __syncthreads();
+            unsigned int pos = 0u;
+            if (valid) {
+                pos = base[d] + lrank;
+                for (int ww = 0; ww < w; ++ww) pos += wcnt[ww][d];
+            }
+            __syncthreads();
+            if (valid && lrank == 0u) { atomicAdd(&base[d], cnt); wcnt[w][d] = 0u; }
+            if (valid && pos < (unsigned int)n) {
+                dst[pos] = key;
+                if constexpr (IDX) di[pos] = id;
+            }
+        }
+        __syncthreads();
+        unsigned long long *tk = src; src = dst; dst = tk;
+        if constexpr (IDX) { unsigned int *ti = si; si = di; di = ti; }
+    }
+}
 template <int LATE>
 __global__ __launch_bounds__(256) void k_rank(const double *buf, long long ld, int nsamp, int nch, int all, unsigned long long *keyA,
                                               unsigned long long *keyB, unsigned int *idxA, unsigned int *idxB, int k05, int k95, double *ranks,
@@ -4354,66 +4435,9 @@ __global__ __launch_bounds__(256) void k_rank(const double *buf, long long ld, i
     if (tid == 0) { s_flag = 0; carry[0] = 0; carry[1] = 0; }
     __syncthreads();
     // 1. keys and digit histograms
-    int myflag = 0;
-    for (int t = tid; t < n; t += 256) {
-        const int c = t / per, u = t - c * per;
-        const unsigned int pos = (unsigned int)(c * nsamp + (u < hh ? u : u + gap));
-        double v = x[pos];
-        if (v != v) myflag |= 1;
-        else if (fabs(v) == INFINITY) myflag |= 2;
-        if (v == 0.0) v = 0.0;                                 // -0 ties with +0
-        const unsigned long long key = bnr_key_of(v);
-        src[t] = key; si[t] = pos;
-#pragma unroll
-        for (int b = 0; b < 8; ++b) atomicAdd(&hist[b][(unsigned int)(key >> (8 * b)) & 255u], 1u);
-    }
-    if (myflag) atomicOr(&s_flag, myflag);
-    __syncthreads();
-    for (int b = 0; b < 8; ++b) if (hist[b][tid] == (unsigned int)n) s_skip[b] = 1;
-    __syncthreads();
+    bnr_sort_build_keys<true>(x, n, nsamp, per, hh, gap, src, si, hist, s_skip, s_flag);
     // 2. the passes
-    for (int pass = 0; pass < 8; ++pass) {
-        if (s_skip[pass]) continue;                            // (uniform: read behind the barrier above, never written again)
-        const int shift = 8 * pass;
-        const unsigned int mine = hist[pass][tid];
-        tmp[tid] = mine;
-        __syncthreads();
-        for (int off = 1; off < 256; off <<= 1) {
-            const unsigned int a = tid >= off ? tmp[tid - off] : 0u;
-            __syncthreads();
-            tmp[tid] += a;
-            __syncthreads();
-        }
-        base[tid] = tmp[tid] - mine;
-        __syncthreads();
-        for (int t0 = 0; t0 < n; t0 += 256) {
-            const int t = t0 + tid;
-            const bool valid = t < n;
-            const unsigned long long key = valid ? src[t] : 0ull;
-            const unsigned int id = valid ? si[t] : 0u;
-            const unsigned int d = (unsigned int)(key >> shift) & 255u;
-            unsigned long long mask = __ballot(valid);
-#pragma unroll
-            for (int b = 0; b < 8; ++b) {
-                const unsigned long long m = __ballot((d >> b) & 1u);
-                mask &= ((d >> b) & 1u) ? m : ~m;
-            }
-            const unsigned int lrank = (unsigned int)__popcll(mask & below), cnt = (unsigned int)__popcll(mask);
-            if (valid && lrank == 0u) wcnt[w][d] = cnt;
-            __syncthreads();
-            unsigned int pos = 0u;
-            if (valid) {
-                pos = base[d] + lrank;
-                for (int ww = 0; ww < w; ++ww) pos += wcnt[ww][d];
-            }
-            __syncthreads();
-            if (valid && lrank == 0u) { atomicAdd(&base[d], cnt); wcnt[w][d] = 0u; }
-            if (valid && pos < (unsigned int)n) { dst[pos] = key; di[pos] = id; }
-        }
-        __syncthreads();
-        unsigned long long *tk = src; src = dst; dst = tk;
-        unsigned int *ti = si; si = di; di = ti;
-    }
+    bnr_sort_passes<true>(n, src, dst, si, di, hist, base, tmp, wcnt, s_skip);
     // 3. tie runs
     unsigned int *sa = (unsigned int *)dst, *ea = sa + ld;
     for (int t0 = 0, it = 0; t0 < n; t0 += 256, ++it) {
@@ -4469,4 +4493,94 @@ __global__ __launch_bounds__(256) void k_fold(const double *buf, long long ld, i
     const size_t o = (size_t)col * (size_t)ld + (size_t)i;
     const double v = buf[o] - med[col];
     out[o] = absolute ? fabs(v) : v;
+}
+
+// ===================================================================================== k_hdi (ABI 13: highest-density intervals, sign probabilities)
+// k_hdi: of one staged column of n draws (column blockIdx.x of `buf`, leading dimension ld >= n; every draw takes part), one workgroup of 256
+// threads per column: the shortest interval that holds w_k + 1 consecutive order statistics for each of nprob <= 8 window lengths w_k (the
+// highest-density interval of a sample: ArviZ's _hdi, R's HDInterval::hdi), the median as k_rank takes it, and the shares of draws above and
+// below zero.
+//   1., 2. k_rank's key image and sort, keys only (bnr_sort_build_keys<false>, bnr_sort_passes<false>).
+//   3. sign counts: two binary searches over the sorted keys for the key of +0.0 (-0 was folded onto it) give the number of keys below it and
+//      the number not above it: p_neg = below / n, p_pos = (n - not above) / n, integers over n.
+//   4. per level, over j = 0 .. n - w - 1 the width d_j = x_(j+w) - x_(j), one f64 subtraction of the decoded keys; every thread walks
+//      j = tid, tid + 256, ... and keeps the smallest (d_j, j) in lexicographic order, a fixed tree over the 256 threads merges them: the first
+//      minimum, whatever the grid or the order of arrival.  lower = x_(j*), upper = x_(j* + w), level k at offset k lstride of both.
+// A column that holds a NaN is NaN in every output and is not sorted; one that holds an Inf (and no NaN) is NaN in lower, upper and med, its
+// shares are counted.  A constant column skips every pass and gets lower = upper = the constant.  Every index stays below n <= ld: nothing is
+// written outside the column's slices of keyA / keyB, and every output is a pure function of the column's draws.  lower / upper NULL (both):
+// phase 4 is not run.
+struct bnr_hdi_levels { int w[8]; };
+template <int LATE>
+__global__ __launch_bounds__(256) void k_hdi(const double *buf, long long ld, int n, unsigned long long *keyA, unsigned long long *keyB, int nprob,
+                                             bnr_hdi_levels lv, double *lower, double *upper, long long lstride, double *med, double *p_pos, double *p_neg)
+{
+    __shared__ unsigned int hist[8][256];
+    __shared__ unsigned int base[256], tmp[256];
+    __shared__ unsigned int wcnt[4][256];
+    __shared__ double rd[256];
+    __shared__ int rj[256];
+    __shared__ int s_skip[8], s_flag;
+    const int tid = threadIdx.x;
+    const size_t c0 = (size_t)blockIdx.x * (size_t)ld;
+    unsigned long long *src = keyA + c0, *dst = keyB + c0;
+    unsigned int *si = nullptr, *di = nullptr;
+    for (int b = 0; b < 8; ++b) hist[b][tid] = 0u;
+    for (int b = 0; b < 4; ++b) wcnt[b][tid] = 0u;
+    if (tid < 8) s_skip[tid] = 0;
+    if (tid == 0) s_flag = 0;
+    __syncthreads();
+    bnr_sort_build_keys<false>(buf + c0, n, n, n, n / 2, 0, src, si, hist, s_skip, s_flag);
+    const int fl = s_flag;                                     // (uniform: behind the function's barriers)
+    if (fl & 1) {
+        if (tid == 0) { med[blockIdx.x] = NAN; p_pos[blockIdx.x] = NAN; p_neg[blockIdx.x] = NAN; }
+        if (lower && tid < nprob) { lower[(size_t)tid * lstride + blockIdx.x] = NAN; upper[(size_t)tid * lstride + blockIdx.x] = NAN; }
+        return;
+    }
+    bnr_sort_passes<false>(n, src, dst, si, di, hist, base, tmp, wcnt, s_skip);
+    // 3. sign counts and the median
+    if (tid == 0 || tid == 64) {
+        const unsigned long long zero = 0x8000000000000000ull;
+        int lo = 0, hi = n;                                    // tid 0: the first key >= zero; tid 64: the first key > zero
+        while (lo < hi) {
+            const int mid = lo + (hi - lo) / 2;
+            const unsigned long long k = src[mid];
+            if (tid == 0 ? k < zero : k <= zero) lo = mid + 1; else hi = mid;
+        }
+        if (tid == 0) p_neg[blockIdx.x] = (double)lo / (double)n;
+        else p_pos[blockIdx.x] = (double)(n - lo) / (double)n;
+    }
+    if (tid == 128)
+        med[blockIdx.x] = (fl & 2) ? NAN : n >= 2 ? (bnr_double_of(src[n / 2 - 1]) + bnr_double_of(src[n / 2])) / 2.0 : bnr_double_of(src[0]);
+    if (!lower) return;
+    if (fl & 2) {
+        if (tid < nprob) { lower[(size_t)tid * lstride + blockIdx.x] = NAN; upper[(size_t)tid * lstride + blockIdx.x] = NAN; }
+        return;
+    }
+    // 4. the shortest window of every level
+    for (int k = 0; k < nprob; ++k) {
+        const int w = lv.w[k], m = n - w;
+        double bd = INFINITY;
+        int bj = 0x7FFFFFFF;
+        for (int j = tid; j < m; j += 256) {
+            const double d = bnr_double_of(src[j + w]) - bnr_double_of(src[j]);
+            if (d < bd || bj == 0x7FFFFFFF) { bd = d; bj = j; }
+        }
+        rd[tid] = bd; rj[tid] = bj;
+        __syncthreads();
+        for (int s = 128; s > 0; s >>= 1) {
+            if (tid < s) {
+                const double od = rd[tid + s];
+                const int oj = rj[tid + s];
+                if (od < rd[tid] || (od == rd[tid] && oj < rj[tid])) { rd[tid] = od; rj[tid] = oj; }
+            }
+            __syncthreads();
+        }
+        if (tid == 0) {
+            const int j = rj[0];
+            lower[(size_t)k * lstride + blockIdx.x] = bnr_double_of(src[j]);
+            upper[(size_t)k * lstride + blockIdx.x] = bnr_double_of(src[j + w]);
+        }
+        __syncthreads();
+    }
 }

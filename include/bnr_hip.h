@@ -28,14 +28,14 @@
 extern "C" {
 #endif
 
-#define BNR_ABI_VERSION 12  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
+#define BNR_ABI_VERSION 13  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
                                5: + bnr_chain_create_typed, bnr_chain_create_from_matrices, bnr_device_synchronize; 6: + bnr_comm_info;
                                7: + option "xi_weights", bnr_host_xi_weight; 8: + bnr_chain_predict, bnr_chain_predict_from_matrices,
                                bnr_chain_loglik_stats, option "predict_block_rows"; 9: + bnr_chain_loo, bnr_psis_loo;
                                10: + bnr_chains_summary, bnr_chains_predict, bnr_chains_predict_from_matrices, bnr_chains_loglik_stats, bnr_chains_loo,
                                bnr_host_pred_noise, option "summary_block_cols"; 11: + bnr_chain_loo_predict, bnr_chains_loo_predict,
                                bnr_psis_weights; 12: + bnr_chain_rank_diag, bnr_chains_rank_diag, bnr_rank_normalize, bnr_host_ndtri,
-                               option "rank_block_cols" (all additive) */
+                               option "rank_block_cols"; 13: + bnr_chain_hdi, bnr_chains_hdi, bnr_hdi (all additive) */
 
 enum {
     BNR_OK = 0,
@@ -307,6 +307,31 @@ int bnr_chain_rank_diag(bnr_chain *chain, int32_t first_row, int32_t nsamp, int3
 int bnr_chains_rank_diag(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t max_lag, double *rhat_bulk,
                          double *rhat_tail, double *ess_bulk, double *ess_tail, double *ess_mean, double *mcse_mean);
 int bnr_rank_normalize(int32_t device, int32_t m, int32_t S, const double *x, double *ranks, double *z);
+
+/* Highest-density intervals, the median and the sign probabilities (ABI 13) -- an ADDITION to the reference -- of every parameter in
+ * [gamma(q) | xi(V)] over the pooled window of nchains >= 1 chains of one device: all S = nchains nsamp draws take part (no split halves).
+ *   For each of the nprob <= 8 levels probs[k] in (0, 1): w = floor(probs[k] S) (computed in double; at most S - 1), and among the windows
+ *   x_(j) .. x_(j+w), j = 0 .. S - w - 1, of the sorted draws the one of the smallest width x_(j+w) - x_(j) (one f64 subtraction), the smallest j
+ *   among equal widths: lower = x_(j), upper = x_(j+w).  This is the HDI of a sample as ArviZ (_hdi) and R's HDInterval::hdi compute it
+ *   (unimodal; first minimum).
+ *   median = the mean of the two middle order statistics x_(S/2) and x_(S/2+1) (1-based; S = 1: the draw), as bnr_chains_rank_diag takes it.
+ *   p_pos, p_neg = the shares of draws above and below zero (exact counts over S; -0 counts as zero); P(x = 0) = 1 - p_pos - p_neg.
+ * lower and upper hold nprob (q + V) doubles, level k at offset k (q + V), gamma first; median, p_pos and p_neg hold q + V doubles.  Every
+ * output may be NULL (not all of them); lower and upper come together, and without them nprob may be 0 and no window is searched.
+ * A parameter with a NaN draw is NaN in every output; one with an infinite draw (and no NaN) is NaN in lower, upper and median, and its shares
+ * are counted (+Inf above, -Inf below zero).  All draws equal: lower = upper = the draw.  -0 is reported as +0.
+ * Checks: those of bnr_chains_summary, 0 <= nprob <= 8, every level in (0, 1), lower and upper both or neither, nprob >= 1 with them.  Runs
+ * eagerly on chains[0]'s stream; the columns are staged in blocks of about 1 GiB of draws (option "rank_block_cols" of chains[0] overrides);
+ * no result depends on the block, the grid, the outputs requested or the call, bit for bit, and bnr_chain_hdi is the pooled call with one
+ * chain.  Nothing of any chain is written.
+ * bnr_hdi: the same for every row of a caller's m x S matrix (host, row-major), each row on its own; lower and upper hold nprob m doubles,
+ *   level k at offset k m.  DESIGN.md section 8. */
+int bnr_chain_hdi(bnr_chain *chain, int32_t first_row, int32_t nsamp, int32_t nprob, const double *probs, double *lower, double *upper,
+                  double *median, double *p_pos, double *p_neg);
+int bnr_chains_hdi(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t nprob, const double *probs, double *lower,
+                   double *upper, double *median, double *p_pos, double *p_neg);
+int bnr_hdi(int32_t device, int32_t m, int32_t S, const double *x, int32_t nprob, const double *probs, double *lower, double *upper, double *median,
+            double *p_pos, double *p_neg);
 
 /* Effective sample size -- an ADDITION to the reference (which only has split-Rhat; north-star item "Rhat/ESS check").
  * bnr_chain_ess_stats: this chain's message over rows first_row .. first_row+nsamp-1: for both halves of the window (the
