@@ -10,7 +10,7 @@ def build(force=False, verbose=False):
     if os.environ.get("BNR_HIP_LIB"):
         return LIB
     csrc = os.path.join(HERE, "csrc")
-    cmd = ["make", "-C", csrc] + (["-B"] if force else [])
+    cmd = ["make", "-j2", "-C", csrc] + (["-B"] if force else [])          # two translation units, side by side
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if verbose or r.returncode:
         print(r.stdout)

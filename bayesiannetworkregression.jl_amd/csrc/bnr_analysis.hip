@@ -1,0 +1,879 @@
+// bnr_analysis.hip -- the posterior analysis behind the C ABI (include/bnr_hip.h) over the kernels in bnr_analysis_kernels.h: Summary, rank-normalised
+// diagnostics, highest-density intervals, posterior prediction, log-likelihood statistics, PSIS-LOO and its predictive checks.  A translation unit and
+// so a gfx950 code object of its own: nothing added here can move a kernel of the sweep (bnr_hip.hip), whose speed depends on where its kernels lie.
+// k_fetch_cols, k_summary and k_acov stay with the sweep kernels and are launched through bnr_internal.h.
+#include "bnr_internal.h"
+#include "bnr_analysis_kernels.h"
+
+#include <cmath>
+
+// a stream of a call's own (the calls on a caller's matrix), destroyed on every path
+namespace {
+struct stream_guard {
+    hipStream_t s = nullptr;
+    ~stream_guard() { if (s) (void)hipStreamDestroy(s); }
+};
+}
+
+// The state and row window of the chains of an analysis call: none with a pending asynchronous run, the window inside every table
+static int window_check(bnr_chain *const *cs, int nc, int first_row, int nsamp)
+{
+    for (int i = 0; i < nc; ++i) if (cs[i]->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+    for (int i = 0; i < nc; ++i)
+        if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > cs[i]->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    return BNR_OK;
+}
+// The chains of a pooled call (bnr_chains_*): one device, equal n, V, R, none listed twice, window_check, the pooled draw count within int32
+static int pooled_check(bnr_chain *const *cs, int nc, int first_row, int nsamp)
+{
+    if (!cs) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (nc < 1) return fail(BNR_ERR_BAD_ARG, "need nchains >= 1");
+    for (int i = 0; i < nc; ++i) {
+        if (!cs[i]) return fail(BNR_ERR_BAD_ARG, "NULL chain");
+        for (int k = 0; k < i; ++k) if (cs[k] == cs[i]) return fail(BNR_ERR_BAD_ARG, "chain listed twice");
+        const bnr_dev &a = cs[0]->d, &b = cs[i]->d;
+        if (cs[i]->device != cs[0]->device || a.n != b.n || a.V != b.V || a.R != b.R)
+            return fail(BNR_ERR_BAD_ARG, "pooled chains must live on one device and have equal n, V, R");
+    }
+    if (int rc = window_check(cs, nc, first_row, nsamp)) return rc;
+    if ((long long)nc * nsamp > 0x7FFFFFFFll) return fail(BNR_ERR_BAD_ARG, "more than 2^31 - 1 pooled draws");
+    return BNR_OK;
+}
+// The pooled work runs on the first chain's stream and reads the other chains' tables: whatever their own streams (and their group's) still
+// hold -- a table load, the tail of a synchronous run -- is waited for here.  (One chain: nothing to order, as before.)
+static int pooled_quiesce(bnr_chain *const *cs, int nc)
+{
+    for (int i = 1; i < nc; ++i) {
+        HIPCHK(hipStreamSynchronize(cs[i]->x.stream));
+        if (cs[i]->group) HIPCHK(hipStreamSynchronize(cs[i]->group->x.stream));
+    }
+    return BNR_OK;
+}
+
+// Parameter columns p0 .. p0 + pc - 1 of [gamma(q) | xi(V)] over the pooled window, staged by k_fetch_cols: column p of `buf` holds S = nc nsamp
+// draws, chain k's window in rows k nsamp .. (k + 1) nsamp - 1 (one launch per chain and per kind of column)
+static void stage_cols(hipStream_t st, bnr_chain *const *cs, int nc, int first_row, int nsamp, int p0, int pc, double *buf)
+{
+    const bnr_dev &d = cs[0]->d;
+    const long long S = (long long)nc * nsamp;
+    const int g0 = std::min(p0, d.q), g1 = std::min(p0 + pc, d.q);          // gamma columns g0 .. g1 - 1 first, then xi columns x0 .. x1 - 1
+    const int x0 = std::max(p0, d.q) - d.q, x1 = std::max(p0 + pc, d.q) - d.q;
+    for (int k = 0; k < nc; ++k) {
+        const bnr_dev &dk = cs[k]->d;
+        double *dst = buf + (size_t)k * nsamp;
+        if (g1 > g0)
+            launch_fetch_cols(st, dk.trace, dk.rowlen, dk.o_gamma + g0, g1 - g0, first_row - 1, nsamp, dst, S);
+        if (x1 > x0)
+            launch_fetch_cols(st, dk.trace, dk.rowlen, dk.o_xi + x0, x1 - x0, first_row - 1, nsamp, dst + (size_t)(g1 - g0) * (size_t)S, S);
+    }
+}
+
+// Summary(results) on the device (gibbs.jl:1214-1250): posterior mean and two order statistics of every gamma_e over rows
+// first_row .. first_row+nsamp-1 of every chain listed (pooled: S = nc nsamp draws, draw c nsamp + s = chain c's s-th window row), and the mean
+// of every xi_v.  3q + V doubles cross PCIe instead of the gamma traces.  The q + V parameter columns are staged (k_fetch_cols, one launch per
+// chain into its nsamp rows of the S-row column) in blocks of columns that keep the staging buffer near 1 GiB ("summary_block_cols" overrides);
+// k_summary works on one column per workgroup, so the block size cannot change a result.
+static int summary_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
+                        double *mean_gamma, double *lower, double *upper, double *prob_xi)
+{
+    bnr_chain *c = cs[0];
+    const bnr_dev &d = c->d;
+    const long long S = (long long)nc * nsamp;
+    if (k_lo < 1 || k_lo > S || k_hi < 1 || k_hi > S)
+        return fail(BNR_ERR_BAD_ARG, nc == 1 ? "order statistics must be between 1 and nsamp" : "order statistics must be between 1 and nchains * nsamp");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->x.stream;
+    int rc;
+    if ((rc = pooled_quiesce(cs, nc))) return rc;
+    const int np = d.q + d.V;
+    const size_t budget = (size_t)1 << 30;
+    long long blk = c->summary_block_cols > 0 ? c->summary_block_cols : (long long)(budget / ((size_t)S * sizeof(double)));
+    blk = std::min<long long>(std::max<long long>(blk, 1), np);
+    dev_tmp tmp;
+    double *buf = nullptr;
+    result_slab out;                                    // the mean, the lower and the upper statistic of the np = q + V parameters, gamma first
+    if ((rc = tmp.alloc(&buf, (size_t)blk * (size_t)S, st, false))) return rc;
+    if ((rc = out.alloc(tmp, 3, (size_t)np, st))) return rc;
+    for (int p0 = 0; p0 < np; p0 += (int)blk) {
+        const int pc = std::min<int>((int)blk, np - p0);
+        stage_cols(st, cs, nc, first_row, nsamp, p0, pc, buf);
+        launch_summary(st, pc, buf, (int)S, std::min(p0 + pc, d.q) - std::min(p0, d.q), k_lo, k_hi, out.col(0) + p0, out.col(1) + p0, out.col(2) + p0);
+    }
+    std::vector<double> host(3 * (size_t)np);           // (the callers' arrays hold q and V entries, not q + V)
+    if ((rc = out.fetch(st, "summary", "k_summary", {host.data(), host.data() + np, host.data() + 2 * (size_t)np}))) return rc;
+    memcpy(mean_gamma, host.data(), sizeof(double) * d.q);
+    memcpy(prob_xi, host.data() + d.q, sizeof(double) * d.V);
+    memcpy(lower, host.data() + np, sizeof(double) * d.q);
+    memcpy(upper, host.data() + 2 * (size_t)np, sizeof(double) * d.q);
+    return BNR_OK;
+}
+int bnr_chain_summary(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
+                      double *mean_gamma, double *lower, double *upper, double *prob_xi)
+{
+    if (!c || !mean_gamma || !lower || !upper || !prob_xi) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
+    return summary_call(&c, 1, first_row, nsamp, k_lo, k_hi, mean_gamma, lower, upper, prob_xi);
+}
+int bnr_chains_summary(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
+                       double *mean_gamma, double *lower, double *upper, double *prob_xi)
+{
+    if (!chains || !mean_gamma || !lower || !upper || !prob_xi) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
+    return summary_call(chains, nchains, first_row, nsamp, k_lo, k_hi, mean_gamma, lower, upper, prob_xi);
+}
+
+// the rank-normalised diagnostics (ABI 12): k_rank's two (key, index) buffers, one slice of ld entries per column
+struct rank_bufs { unsigned long long *keyA = nullptr, *keyB = nullptr; unsigned int *idxA = nullptr, *idxB = nullptr; };
+static void launch_rank(hipStream_t st, int cols, const double *buf, long long ld, int nsamp, int nch, int all, const rank_bufs &rb, int k05, int k95,
+                        double *ranks, double *z, double *ind05, double *ind95, double *med, int *flag)
+{
+    hipLaunchKernelGGL(k_rank, dim3(cols), dim3(256), 0, st, buf, ld, nsamp, nch, all, rb.keyA, rb.keyB, rb.idxA, rb.idxB, k05, k95, ranks, z,
+                       ind05, ind95, med, flag);
+}
+static void launch_fold(hipStream_t st, int cols, const double *buf, long long ld, const double *med, int absolute, double *out)
+{
+    const int chunks = (int)((ld + 255) / 256);
+    hipLaunchKernelGGL(k_fold, dim3((unsigned)chunks * (unsigned)cols), dim3(256), 0, st, buf, ld, chunks, med, absolute, out);
+}
+// Rank-normalised convergence diagnostics (ABI 12; Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021, as `posterior` 1.x computes them) of every
+// parameter p in [gamma(q) | xi(V)] over the pooled window of the chains listed.  The columns are staged as in summary_call ("rank_block_cols"
+// overrides the block of about 1 GiB of draws); per block: k_rank on the split-chain draws (z, the two tail indicators, the median, the flag),
+// k_acov -- unchanged: a pooled column is nc windows of nsamp side by side, i.e. pc nc columns of nsamp -- on z, the indicators and x - med
+// (k_fold: the moments of x are taken about the median), k_fold and a second k_rank and k_acov for the folded z.  Each series' message of the block (2 (2 + L) pc nc doubles; L = 1 where only R-hat is
+// wanted) is fetched and finished here: bnr_ess_from_stats as it stands, and split-R-hat = sqrt(((h-1)/h W + B) / W).  Work nobody asked for
+// is not run.  Conventions: a parameter with a non-finite draw, or with all draws equal, is NaN in every output; rhat_tail is NaN where the
+// folded draws are all equal; ess_tail is NaN where either indicator's ESS is.
+namespace {
+struct split_msg {                                       // k_acov's message of one series of a block, per chain in bnr_ess_from_stats' layout
+    std::vector<double> raw, st, ess;
+    int nc = 0, pc = 0, L = 0, h = 0;
+    double mean(int c, int half, int p) const { return st[((size_t)c * 2 + half) * (size_t)(2 + L) * pc + p]; }
+    double var(int c, int half, int p) const { return st[((size_t)c * 2 + half) * (size_t)(2 + L) * pc + pc + p]; }
+    void moments(int p, double &W, double &dev2) const  // the mean of the 2 nc variances; the sum of the squared deviations of the 2 nc means
+    {
+        const int m = 2 * nc;
+        double mm = 0.0;
+        W = 0.0;
+        for (int c = 0; c < nc; ++c) for (int k = 0; k < 2; ++k) { mm += mean(c, k, p); W += var(c, k, p); }
+        mm /= m; W /= m;
+        dev2 = 0.0;
+        for (int c = 0; c < nc; ++c) for (int k = 0; k < 2; ++k) dev2 += (mean(c, k, p) - mm) * (mean(c, k, p) - mm);
+    }
+    double rhat(int p) const
+    {
+        double W, dev2;
+        moments(p, W, dev2);
+        return sqrt(((double)(h - 1) / h * W + dev2 / (2 * nc - 1)) / W);
+    }
+};
+}
+static int rank_diag_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t max_lag, double *rhat_bulk, double *rhat_tail,
+                          double *ess_bulk, double *ess_tail, double *ess_mean, double *mcse_mean)
+{
+    if (!rhat_bulk && !rhat_tail && !ess_bulk && !ess_tail && !ess_mean && !mcse_mean) return fail(BNR_ERR_BAD_ARG, "no output requested");
+    if (nsamp < 8) return fail(BNR_ERR_BAD_ARG, "need nsamp >= 8");
+    if (max_lag < 2 || max_lag > nsamp / 2) return fail(BNR_ERR_BAD_ARG, "need 2 <= max_lag <= nsamp/2");
+    bnr_chain *c = cs[0];
+    const bnr_dev &d = c->d;
+    const long long S = (long long)nc * nsamp;
+    const int h = nsamp / 2, np = d.q + d.V;
+    const long long n = (long long)nc * 2 * h;          // the split-chain draws that are ranked
+    const int k05 = (int)floor((double)(n - 1) * 0.05) + 1, k95 = (int)floor((double)(n - 1) * 0.95) + 1;
+    const bool want_bulk = rhat_bulk || ess_bulk, want_mean = ess_mean || mcse_mean, want_et = ess_tail != nullptr, want_rt = rhat_tail != nullptr;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->x.stream;
+    int rc;
+    if ((rc = pooled_quiesce(cs, nc))) return rc;
+    const size_t budget = (size_t)1 << 30;
+    long long blk = c->rank_block_cols > 0 ? c->rank_block_cols : (long long)(budget / ((size_t)S * sizeof(double)));
+    blk = std::min<long long>(std::max<long long>(blk, 1), np);
+    const int Lmax = (ess_bulk || want_et || want_mean) ? max_lag : 1;
+    dev_tmp tmp;
+    double *X = nullptr, *Z = nullptr, *A = nullptr, *B = nullptr, *med = nullptr, *statd = nullptr;
+    int *flagd = nullptr;
+    rank_bufs rb;
+    const size_t cells = (size_t)blk * (size_t)S;
+    if ((rc = tmp.alloc(&X, cells, st, false))) return rc;
+    if ((want_bulk || want_rt) && (rc = tmp.alloc(&Z, cells, st, false))) return rc;
+    if ((want_et || want_rt || want_mean) && (rc = tmp.alloc(&A, cells, st, false))) return rc;
+    if (want_et && (rc = tmp.alloc(&B, cells, st, false))) return rc;
+    if ((rc = tmp.alloc(&rb.keyA, cells, st, false)) || (rc = tmp.alloc(&rb.keyB, cells, st, false)) || (rc = tmp.alloc(&rb.idxA, cells, st, false)) ||
+        (rc = tmp.alloc(&rb.idxB, cells, st, false)))
+        return rc;
+    if ((rc = tmp.alloc(&med, (size_t)blk, st)) || (rc = tmp.alloc(&flagd, 2 * (size_t)blk, st))) return rc;
+    if ((rc = tmp.alloc(&statd, (size_t)2 * (2 + Lmax) * (size_t)blk * nc, st, false))) return rc;
+    const double nanv = NAN;
+    std::vector<double> o_rb(np, nanv), o_rt(np, nanv), o_eb(np, nanv), o_et(np, nanv), o_em(np, nanv), o_mc(np, nanv);
+    std::vector<int> flags(2 * (size_t)blk);
+    split_msg sz, s05, s95, sx, sf;
+    for (int p0 = 0; p0 < np; p0 += (int)blk) {
+        const int pc = std::min<int>((int)blk, np - p0);
+        stage_cols(st, cs, nc, first_row, nsamp, p0, pc, X);
+        // one series: k_acov on the block's pc nc windows, its message fetched and laid out per chain; the ESS where lags were asked for
+        auto series = [&](const double *data, int L, split_msg &m) -> int {
+            const size_t cnt = (size_t)2 * (2 + L) * (size_t)pc * nc;
+            launch_acov(st, data, nsamp, pc * nc, L, statd);
+            m.raw.resize(cnt);
+            hipError_t e = hipMemcpyAsync(m.raw.data(), statd, sizeof(double) * cnt, hipMemcpyDeviceToHost, st);
+            if (e == hipSuccess) e = hipStreamSynchronize(st);
+            if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("rank_diag: ") + hipGetErrorString(e));
+            if (int r = check_launch("k_acov")) return r;
+            m.nc = nc; m.pc = pc; m.L = L; m.h = h;
+            m.st.resize(cnt);
+            for (int k = 0; k < 2; ++k) for (int j = 0; j < 2 + L; ++j) {
+                const double *src = m.raw.data() + ((size_t)k * (2 + L) + j) * (size_t)pc * nc;
+                for (int ch = 0; ch < nc; ++ch) {
+                    double *dst = m.st.data() + (((size_t)ch * 2 + k) * (2 + L) + j) * (size_t)pc;
+                    for (int p = 0; p < pc; ++p) dst[p] = src[(size_t)p * nc + ch];
+                }
+            }
+            m.ess.assign(pc, NAN);
+            if (L >= 2) return bnr_ess_from_stats(m.st.data(), nc, pc, nsamp, L, m.ess.data());
+            return BNR_OK;
+        };
+        launch_rank(st, pc, X, S, nsamp, nc, 0, rb, k05, k95, nullptr, want_bulk ? Z : nullptr, want_et ? A : nullptr, want_et ? B : nullptr, med, flagd);
+        if (want_bulk && (rc = series(Z, ess_bulk ? max_lag : 1, sz))) return rc;
+        if (want_et && ((rc = series(A, max_lag, s05)) || (rc = series(B, max_lag, s95)))) return rc;
+        if (want_mean) {                                     // on x - med: see k_fold
+            launch_fold(st, pc, X, S, med, 0, A);
+            if ((rc = series(A, max_lag, sx))) return rc;
+        }
+        if (want_rt) {
+            launch_fold(st, pc, X, S, med, 1, A);
+            launch_rank(st, pc, A, S, nsamp, nc, 0, rb, k05, k95, nullptr, Z, nullptr, nullptr, nullptr, flagd + blk);
+            if ((rc = series(Z, 1, sf))) return rc;
+        }
+        HIPCHK(hipMemcpyAsync(flags.data(), flagd, sizeof(int) * 2 * (size_t)blk, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        if ((rc = check_launch("k_rank"))) return rc;
+        for (int p = 0; p < pc; ++p) {
+            if (flags[p]) continue;                          // a NaN, an Inf or all draws equal: NaN throughout
+            const int P = p0 + p;
+            if (want_bulk) { o_rb[P] = sz.rhat(p); o_eb[P] = sz.ess[p]; }
+            if (want_rt && !flags[(size_t)blk + p]) o_rt[P] = sf.rhat(p);
+            if (want_et) o_et[P] = (s05.ess[p] != s05.ess[p] || s95.ess[p] != s95.ess[p]) ? nanv : std::min(s05.ess[p], s95.ess[p]);
+            if (want_mean) {
+                double W, dev2;
+                sx.moments(p, W, dev2);
+                const double sd2 = ((double)(h - 1) * (W * 2 * nc) + (double)h * dev2) / (double)(n - 1);
+                o_em[P] = sx.ess[p];
+                o_mc[P] = sqrt(sd2) / sqrt(sx.ess[p]);
+            }
+        }
+    }
+    const struct { double *dst; const std::vector<double> *src; } outs[] = {{rhat_bulk, &o_rb}, {rhat_tail, &o_rt}, {ess_bulk, &o_eb},
+                                                                           {ess_tail, &o_et}, {ess_mean, &o_em}, {mcse_mean, &o_mc}};
+    for (const auto &o : outs) if (o.dst) memcpy(o.dst, o.src->data(), sizeof(double) * np);
+    return BNR_OK;
+}
+int bnr_chain_rank_diag(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t max_lag, double *rhat_bulk, double *rhat_tail, double *ess_bulk,
+                        double *ess_tail, double *ess_mean, double *mcse_mean)
+{
+    if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
+    return rank_diag_call(&c, 1, first_row, nsamp, max_lag, rhat_bulk, rhat_tail, ess_bulk, ess_tail, ess_mean, mcse_mean);
+}
+int bnr_chains_rank_diag(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t max_lag, double *rhat_bulk,
+                         double *rhat_tail, double *ess_bulk, double *ess_tail, double *ess_mean, double *mcse_mean)
+{
+    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
+    return rank_diag_call(chains, nchains, first_row, nsamp, max_lag, rhat_bulk, rhat_tail, ess_bulk, ess_tail, ess_mean, mcse_mean);
+}
+double bnr_host_ndtri(double p) { return bnr_ndtri(p); }
+
+// Average ranks and normal scores of every row of a caller's m x S matrix (host, row-major), each row on its own: the companion of
+// bnr_psis_loo / bnr_psis_weights, and k_rank's direct test.  On a stream of its own, the rows in blocks of about 256 MiB.
+int bnr_rank_normalize(int32_t device, int32_t m, int32_t S, const double *x, double *ranks, double *z)
+{
+    if (!x || (!ranks && !z)) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (m < 1 || S < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows and S >= 1 draws");
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
+    HIPCHK(hipSetDevice(device));
+    stream_guard guard;
+    HIPCHK(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
+    hipStream_t st = guard.s;
+    const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, ((size_t)1 << 28) / ((size_t)S * sizeof(double))));
+    const size_t cells = (size_t)blk * (size_t)S;
+    int rc;
+    dev_tmp tmp;                                        // (freed before the stream goes)
+    double *Xd = nullptr, *Rd = nullptr, *Zd = nullptr;
+    int *flagd = nullptr;
+    rank_bufs rb;
+    if ((rc = tmp.alloc(&Xd, cells, st, false))) return rc;
+    if (ranks && (rc = tmp.alloc(&Rd, cells, st, false))) return rc;
+    if (z && (rc = tmp.alloc(&Zd, cells, st, false))) return rc;
+    if ((rc = tmp.alloc(&rb.keyA, cells, st, false)) || (rc = tmp.alloc(&rb.keyB, cells, st, false)) || (rc = tmp.alloc(&rb.idxA, cells, st, false)) ||
+        (rc = tmp.alloc(&rb.idxB, cells, st, false)) || (rc = tmp.alloc(&flagd, (size_t)blk, st)))
+        return rc;
+    for (int i0 = 0; i0 < m; i0 += blk) {
+        const int mr = std::min(blk, m - i0);
+        const size_t cnt = (size_t)mr * (size_t)S;
+        HIPCHK(hipMemcpyAsync(Xd, x + (size_t)i0 * S, sizeof(double) * cnt, hipMemcpyHostToDevice, st));
+        launch_rank(st, mr, Xd, S, S, 1, 1, rb, 1, 1, Rd, Zd, nullptr, nullptr, nullptr, flagd);
+        if (ranks) HIPCHK(hipMemcpyAsync(ranks + (size_t)i0 * S, Rd, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
+        if (z) HIPCHK(hipMemcpyAsync(z + (size_t)i0 * S, Zd, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
+    }
+    hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("rank_normalize: ") + hipGetErrorString(e));
+    return check_launch("k_rank");
+}
+
+// highest-density intervals and sign probabilities (ABI 13): k_hdi on `cols` staged columns of n draws with k_rank's key buffers (the index
+// buffers stay unused)
+static void launch_hdi(hipStream_t st, int cols, const double *buf, long long ld, int n, const rank_bufs &rb, int nprob, const bnr_hdi_levels &lv, double *lower,
+                       double *upper, long long lstride, double *med, double *p_pos, double *p_neg)
+{
+    hipLaunchKernelGGL(k_hdi, dim3(cols), dim3(256), 0, st, buf, ld, n, rb.keyA, rb.keyB, nprob, lv, lower, upper, lstride, med, p_pos, p_neg);
+}
+// Highest-density intervals, the median and the sign probabilities (ABI 13) of every parameter in [gamma(q) | xi(V)] over the pooled window of
+// the chains listed, or of every row of a caller's matrix: include/bnr_hip.h.  hdi_args: the checks that need no device, and the window length
+// w = floor(prob n) of every level (in double, as numpy does; at most n - 1).
+static int hdi_args(long long n, int32_t nprob, const double *probs, const double *lower, const double *upper, const double *median, const double *p_pos,
+                    const double *p_neg, bnr_hdi_levels &lv)
+{
+    if (!lower && !upper && !median && !p_pos && !p_neg) return fail(BNR_ERR_BAD_ARG, "no output requested");
+    if (!lower != !upper) return fail(BNR_ERR_BAD_ARG, "lower and upper come together");
+    if (nprob < 0 || nprob > 8) return fail(BNR_ERR_BAD_ARG, "need 0 <= nprob <= 8 levels");
+    if (nprob > 0 && !probs) return fail(BNR_ERR_BAD_ARG, "probs is NULL");
+    if (lower && nprob < 1) return fail(BNR_ERR_BAD_ARG, "lower and upper need nprob >= 1 levels");
+    for (int k = 0; k < 8; ++k) lv.w[k] = 0;
+    for (int k = 0; k < nprob; ++k) {
+        if (!(probs[k] > 0.0 && probs[k] < 1.0)) return fail(BNR_ERR_BAD_ARG, "every level must lie in (0, 1)");
+        lv.w[k] = (int)std::min<double>(floor(probs[k] * (double)n), (double)(n - 1));
+    }
+    return BNR_OK;
+}
+// the results of an hdi call on the device: nprob lower and nprob upper bounds, the median, p_pos and p_neg of np columns each
+struct hdi_slab {
+    double *d = nullptr;
+    size_t np = 0;
+    int nprob = 0;
+    int alloc(dev_tmp &tmp, int levels, size_t cols, hipStream_t st) { nprob = levels; np = cols; return tmp.alloc(&d, (size_t)(2 * nprob + 3) * np, st); }
+    double *lower() const { return d; }
+    double *upper() const { return d + (size_t)nprob * np; }
+    double *med() const { return d + (size_t)2 * nprob * np; }
+    double *p_pos() const { return med() + np; }
+    double *p_neg() const { return med() + 2 * np; }
+    int fetch(hipStream_t st, double *lo, double *up, double *median, double *pp, double *pn) const
+    {
+        std::vector<double> host((size_t)(2 * nprob + 3) * np);
+        hipError_t e = hipMemcpyAsync(host.data(), d, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
+        if (e == hipSuccess) e = hipStreamSynchronize(st);
+        if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("hdi: ") + hipGetErrorString(e));
+        if (int rc = check_launch("k_hdi")) return rc;
+        const double *h = host.data();
+        if (lo) memcpy(lo, h, sizeof(double) * nprob * np);
+        if (up) memcpy(up, h + (size_t)nprob * np, sizeof(double) * nprob * np);
+        h += (size_t)2 * nprob * np;
+        if (median) memcpy(median, h, sizeof(double) * np);
+        if (pp) memcpy(pp, h + np, sizeof(double) * np);
+        if (pn) memcpy(pn, h + 2 * np, sizeof(double) * np);
+        return BNR_OK;
+    }
+};
+static int hdi_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t nprob, const double *probs, double *lower, double *upper,
+                    double *median, double *p_pos, double *p_neg)
+{
+    bnr_chain *c = cs[0];
+    const bnr_dev &d = c->d;
+    const long long S = (long long)nc * nsamp;
+    bnr_hdi_levels lv;
+    int rc;
+    if ((rc = hdi_args(S, nprob, probs, lower, upper, median, p_pos, p_neg, lv))) return rc;
+    const int np = d.q + d.V, levels = lower ? nprob : 0;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->x.stream;
+    if ((rc = pooled_quiesce(cs, nc))) return rc;
+    const size_t budget = (size_t)1 << 30;
+    long long blk = c->rank_block_cols > 0 ? c->rank_block_cols : (long long)(budget / ((size_t)S * sizeof(double)));
+    blk = std::min<long long>(std::max<long long>(blk, 1), np);
+    dev_tmp tmp;
+    double *X = nullptr;
+    rank_bufs rb;
+    hdi_slab out;
+    const size_t cells = (size_t)blk * (size_t)S;
+    if ((rc = tmp.alloc(&X, cells, st, false)) || (rc = tmp.alloc(&rb.keyA, cells, st, false)) || (rc = tmp.alloc(&rb.keyB, cells, st, false))) return rc;
+    if ((rc = out.alloc(tmp, levels, (size_t)np, st))) return rc;
+    for (int p0 = 0; p0 < np; p0 += (int)blk) {
+        const int pc = std::min<int>((int)blk, np - p0);
+        stage_cols(st, cs, nc, first_row, nsamp, p0, pc, X);
+        launch_hdi(st, pc, X, S, (int)S, rb, levels, lv, levels ? out.lower() + p0 : nullptr, levels ? out.upper() + p0 : nullptr, np, out.med() + p0,
+                   out.p_pos() + p0, out.p_neg() + p0);
+    }
+    return out.fetch(st, lower, upper, median, p_pos, p_neg);
+}
+int bnr_chain_hdi(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t nprob, const double *probs, double *lower, double *upper, double *median,
+                  double *p_pos, double *p_neg)
+{
+    if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
+    return hdi_call(&c, 1, first_row, nsamp, nprob, probs, lower, upper, median, p_pos, p_neg);
+}
+int bnr_chains_hdi(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t nprob, const double *probs, double *lower,
+                   double *upper, double *median, double *p_pos, double *p_neg)
+{
+    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
+    return hdi_call(chains, nchains, first_row, nsamp, nprob, probs, lower, upper, median, p_pos, p_neg);
+}
+// k_hdi on every row of a caller's m x S matrix (host, row-major), each row on its own: k_hdi's direct test, as bnr_rank_normalize is k_rank's.
+// On a stream of its own, the rows in blocks of about 256 MiB.
+int bnr_hdi(int32_t device, int32_t m, int32_t S, const double *x, int32_t nprob, const double *probs, double *lower, double *upper, double *median,
+            double *p_pos, double *p_neg)
+{
+    if (!x) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (m < 1 || S < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows and S >= 1 draws");
+    bnr_hdi_levels lv;
+    int rc;
+    if ((rc = hdi_args(S, nprob, probs, lower, upper, median, p_pos, p_neg, lv))) return rc;
+    const int levels = lower ? nprob : 0;
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
+    HIPCHK(hipSetDevice(device));
+    stream_guard guard;
+    HIPCHK(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
+    hipStream_t st = guard.s;
+    const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, ((size_t)1 << 28) / ((size_t)S * sizeof(double))));
+    const size_t cells = (size_t)blk * (size_t)S;
+    dev_tmp tmp;                                        // (freed before the stream goes)
+    double *Xd = nullptr;
+    rank_bufs rb;
+    hdi_slab out;
+    if ((rc = tmp.alloc(&Xd, cells, st, false)) || (rc = tmp.alloc(&rb.keyA, cells, st, false)) || (rc = tmp.alloc(&rb.keyB, cells, st, false))) return rc;
+    if ((rc = out.alloc(tmp, levels, (size_t)m, st))) return rc;
+    for (int i0 = 0; i0 < m; i0 += blk) {
+        const int mr = std::min(blk, m - i0);
+        HIPCHK(hipMemcpyAsync(Xd, x + (size_t)i0 * S, sizeof(double) * (size_t)mr * (size_t)S, hipMemcpyHostToDevice, st));
+        launch_hdi(st, mr, Xd, S, S, rb, levels, lv, levels ? out.lower() + i0 : nullptr, levels ? out.upper() + i0 : nullptr, m, out.med() + i0,
+                   out.p_pos() + i0, out.p_neg() + i0);
+    }
+    return out.fetch(st, lower, upper, median, p_pos, p_neg);
+}
+
+// What a predict_rows call computes from a block's E behind k_predict, in the order of its launches; every pointer is a device pointer, and a
+// NULL one skips its stage
+struct pred_stages {
+    int k_lo = 0, k_hi = 0;                                        // k_summary: mean and the k_lo-th / k_hi-th smallest of every E column
+    double *mean = nullptr, *lower = nullptr, *upper = nullptr;
+    double *lpd = nullptr, *pwaic = nullptr;                       // k_pred_loglik (needs yd)
+    // PSIS (needs yd): the per-row tail lengths, the kernel's dynamic LDS, its outputs (never NULL).  keep_weights = false: k_psis, which
+    // overwrites E; true: k_psis_w and on its weights the LOO predictive checks (ABI 11): k_loo_moments (all three or none) and k_loo_quantile
+    // (each bound nullable) with its probabilities and the bracket's c (Phi(-c) < min(p_lo, 1 - p_hi) / 2)
+    const int *tail_len = nullptr;
+    int lds = 0;
+    bool keep_weights = false;
+    double *psis_lpd = nullptr, *elpd = nullptr, *khat = nullptr;
+    double *loo_mean = nullptr, *loo_sd = nullptr, *loo_pit = nullptr, *loo_lower = nullptr, *loo_upper = nullptr;
+    double p_lo = 0.0, p_hi = 0.0, c = 0.0;
+    double *pit = nullptr;                                         // k_pred_pit: the PIT of the observed responses (needs yd)
+    unsigned long long seed = 0;                                   // k_pred_noise with `seed`, then a second k_summary: the k_lo-th / k_hi-th
+    double *pred_lower = nullptr, *pred_upper = nullptr;           // smallest draw of a new observation (both or none; overwrites E)
+};
+// k_psis: the sorted tail, 16 bytes per entry for up to BNR_PSIS_MAX_TAIL entries; k_psis_w: 12 bytes per entry.  On the current device, in front of the
+// first launch of either (cheap enough for once per call)
+static int psis_lds_attributes()
+{
+    const void *psis[] = {(const void *)&k_psis<0>, (const void *)&k_psis<1>};
+    for (const void *f : psis) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * BNR_PSIS_MAX_TAIL));
+    const void *psis_w[] = {(const void *)&k_psis_w<0>, (const void *)&k_psis_w<1>};
+    for (const void *f : psis_w) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, BNR_PSISW_ENTRY_BYTES * BNR_PSIS_MAX_TAIL));
+    return BNR_OK;
+}
+static void launch_loow_inv_sd(hipStream_t st, const double *tau2, int S, double *isd)
+{ hipLaunchKernelGGL(k_inv_sd, dim3((S + 255) / 256), dim3(256), 0, st, tau2, S, isd); }
+// a block of mr rows starting at row i0 of the call: the weights of the block into LW, then what reads them
+static void launch_loow_block(hipStream_t st, const pred_stages &sg, const double *E, double *LW, int S, int mr, int i0, const double *yd, const double *tau2,
+                              const double *isd)
+{
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis_w<1>), dim3(mr), dim3(256), sg.lds, st, E, S, yd + i0, tau2, sg.tail_len + i0, LW, sg.psis_lpd + i0, sg.elpd + i0,
+                       sg.khat + i0);
+    if (sg.loo_mean)
+        hipLaunchKernelGGL(k_loo_moments, dim3(mr), dim3(256), 0, st, E, (const double *)LW, S, yd + i0, tau2, sg.loo_mean + i0, sg.loo_sd + i0,
+                           sg.loo_pit + i0);
+    if (sg.loo_lower || sg.loo_upper)
+        hipLaunchKernelGGL(k_loo_quantile, dim3(mr, 2), dim3(256), 0, st, E, (const double *)LW, S, tau2, isd, sg.c, sg.p_lo, sg.p_hi,
+                           sg.loo_lower ? sg.loo_lower + i0 : nullptr, sg.loo_upper ? sg.loo_upper + i0 : nullptr);
+}
+// The device work of the prediction, log-likelihood and LOO calls, eagerly on the first chain's stream: the m rows of X (device, column-major,
+// leading dimension ldx, zero in columns q .. q16 - 1 and readable for whole 32-row tiles) in blocks of rows whose E buffer (rows x S doubles,
+// S = nc nsamp pooled draws: chain c's window in the columns c nsamp ..) stays near 1 GiB; per block one k_predict per chain, then the stages
+// of sg that are wanted, in this order: k_summary (mean, k_lo-th / k_hi-th smallest of every E column), k_pred_loglik, the LOO predictive
+// checks (k_psis_w and what reads its weights), k_psis, k_pred_pit, and last what overwrites E: k_pred_noise + a second k_summary (no call asks
+// for that and k_psis, which overwrites E as well).  Blocks start at multiples of 32 rows, so an output's MFMA tile position and K order -- and
+// with them every result, bit for bit -- do not depend on the block size; the noise is keyed by the row's index in the call.  With one chain
+// and no extras: the launches of the single-chain entry points, unchanged.
+static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, const pred_stages &sg,
+                        dev_tmp &tmp)
+{
+    bnr_chain *c = cs[0];
+    const bnr_dev &d = c->d;
+    hipStream_t st = c->x.stream;
+    const long long S = (long long)nc * nsamp;
+    const bool loow = sg.tail_len && sg.keep_weights, psis = sg.tail_len && !sg.keep_weights;
+    const size_t budget = loow ? (size_t)1 << 29 : (size_t)1 << 30;        // (half the rows with the log weights beside E: E + LW stay near 1 GiB)
+    long long blk = c->predict_block_rows > 0 ? c->predict_block_rows : (long long)(budget / ((size_t)S * sizeof(double))) / 32 * 32;
+    blk = std::min<long long>(round_up((int)std::max<long long>(blk, 1), 32), round_up(m, 32));
+    double *E = nullptr, *tau2 = nullptr, *pmean = nullptr, *LW = nullptr, *isd = nullptr;
+    int rc;
+    if ((rc = tmp.alloc(&E, (size_t)blk * (size_t)S, st))) return rc;
+    if (loow && (rc = tmp.alloc(&LW, (size_t)blk * (size_t)S, st))) return rc;
+    if (yd || sg.pit || sg.pred_lower) {
+        if ((rc = tmp.alloc(&tau2, (size_t)S, st))) return rc;
+        for (int k = 0; k < nc; ++k)
+            launch_fetch_cols(st, cs[k]->d.trace, cs[k]->d.rowlen, ROW_TAU2, 1, first_row - 1, nsamp, tau2 + (size_t)k * nsamp, S);
+    }
+    if (sg.pred_lower && (rc = tmp.alloc(&pmean, (size_t)m, st))) return rc;      // (k_summary also writes the mean of y~: not returned)
+    if (loow && (sg.loo_lower || sg.loo_upper)) {
+        if ((rc = tmp.alloc(&isd, (size_t)S, st))) return rc;
+        launch_loow_inv_sd(st, tau2, (int)S, isd);
+    }
+    const int q16 = round_up(d.q, 16);
+    for (int i0 = 0; i0 < m; i0 += (int)blk) {
+        const int mr = std::min<int>((int)blk, m - i0);
+        for (int k = 0; k < nc; ++k) {
+            const bnr_dev &dk = cs[k]->d;
+            if (mr > 16)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<2>), dim3((nsamp + 127) / 128, (mr + 31) / 32), dim3(256), 0, st, Xd + i0, ldx, q16,
+                                   (const double *)dk.trace, dk.rowlen, dk.o_gamma, first_row - 1, nsamp, mr, E + (size_t)k * nsamp, S);
+            else
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<1>), dim3((nsamp + 127) / 128, 1), dim3(256), 0, st, Xd + i0, ldx, q16,
+                                   (const double *)dk.trace, dk.rowlen, dk.o_gamma, first_row - 1, nsamp, mr, E + (size_t)k * nsamp, S);
+        }
+        if (sg.mean)
+            launch_summary(st, mr, E, (int)S, mr, sg.k_lo, sg.k_hi, sg.mean + i0, sg.lower + i0, sg.upper + i0);
+        if (yd && sg.lpd)
+            hipLaunchKernelGGL(k_pred_loglik, dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, yd + i0, (const double *)tau2,
+                               sg.lpd + i0, sg.pwaic + i0);
+        if (loow)                                      // the LOO predictive checks read E: before anything that overwrites it
+            launch_loow_block(st, sg, E, LW, (int)S, mr, i0, yd, tau2, isd);
+        if (psis)                                      // last: k_psis turns the block's E into l in place
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis<1>), dim3(mr), dim3(256), sg.lds, st, E, (int)S, yd + i0, (const double *)tau2, sg.tail_len + i0,
+                               sg.psis_lpd + i0, sg.elpd + i0, sg.khat + i0);
+        if (sg.pit)
+            hipLaunchKernelGGL(k_pred_pit, dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, yd + i0, (const double *)tau2, sg.pit + i0);
+        if (sg.pred_lower) {                           // last: the block's E becomes draws of new observations in place
+            const int gx = (int)((S + 255) / 256), gy = std::max(1, std::min(mr, 8192 / gx));
+            hipLaunchKernelGGL(k_pred_noise, dim3(gx, gy), dim3(256), 0, st, E, S, (int)S, mr, i0, (const double *)tau2, sg.seed);
+            launch_summary(st, mr, E, (int)S, mr, sg.k_lo, sg.k_hi, pmean + i0, sg.pred_lower + i0, sg.pred_upper + i0);
+        }
+    }
+    return check_launch("k_predict");
+}
+
+// Posterior of the mean response mu + x . gamma of m new rows over rows first_row .. first_row+nsamp-1 of the chains listed (an addition to the
+// reference): X_pred goes to the device in its own element type and is converted there (k_x_convert with m rows), then predict_rows.
+// pred_lower / pred_upper / pit (host, nullable): the extras of the pooled entry points.
+static int predict_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t m, const x_source &xs, const double *y, int32_t k_lo,
+                        int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic, uint64_t pred_seed, double *pred_lower,
+                        double *pred_upper, double *pit)
+{
+    bnr_chain *c = cs[0];
+    const bnr_dev &d = c->d;
+    const long long S = (long long)nc * nsamp;
+    if (k_lo < 1 || k_lo > S || k_hi < 1 || k_hi > S)
+        return fail(BNR_ERR_BAD_ARG, nc == 1 ? "order statistics must be between 1 and nsamp" : "order statistics must be between 1 and nchains * nsamp");
+    if (m < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows");
+    if (xs.dtype < BNR_F64 || xs.dtype > BNR_F32) return fail(BNR_ERR_BAD_ARG, "unknown element type of X");
+    if (xs.mats) for (int i = 0; i < m; ++i) if (!xs.mats[i]) return fail(BNR_ERR_BAD_ARG, "NULL adjacency matrix");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->x.stream;
+    const int m_pad = round_up(m, 32), q16 = round_up(d.q, 16);
+    dev_tmp tmp;
+    double *Xd = nullptr, *yd = nullptr;
+    result_slab out;
+    int rc;
+    if ((rc = pooled_quiesce(cs, nc))) return rc;
+    if ((rc = tmp.alloc(&Xd, (size_t)m_pad * q16, st))) return rc;             // zero rows m .. m_pad - 1 and columns q .. q16 - 1 (k_predict)
+    if ((rc = out.alloc(tmp, pred_lower || pit ? 8 : 5, (size_t)m, st))) return rc;
+    const size_t es = dtype_size(xs.dtype);
+    if (!xs.mats && xs.dtype == BNR_F64) {
+        HIPCHK(hipMemcpy2DAsync(Xd, (size_t)m_pad * sizeof(double), xs.X, (size_t)m * sizeof(double), (size_t)m * sizeof(double), d.q, hipMemcpyHostToDevice, st));
+    } else {
+        char *raw = nullptr;
+        const size_t count = xs.mats ? (size_t)m * d.V * d.V : (size_t)m * d.q;
+        if ((rc = tmp.alloc(&raw, count * es, st))) return rc;
+        if (xs.mats) {
+            for (int i = 0; i < m; ++i) HIPCHK(hipMemcpyAsync(raw + (size_t)i * d.V * d.V * es, xs.mats[i], (size_t)d.V * d.V * es, hipMemcpyHostToDevice, st));
+        } else HIPCHK(hipMemcpyAsync(raw, xs.X, count * es, hipMemcpyHostToDevice, st));
+        launch_x_convert(xs.dtype, raw, xs.mats != nullptr, m, d, m_pad, Xd, nullptr, nullptr, st);
+    }
+    if (y) {
+        if ((rc = tmp.alloc(&yd, (size_t)m, st))) return rc;
+        HIPCHK(hipMemcpyAsync(yd, y, sizeof(double) * m, hipMemcpyHostToDevice, st));
+    }
+    pred_stages sg;
+    sg.k_lo = k_lo; sg.k_hi = k_hi;
+    sg.mean = out.col(0); sg.lower = out.col(1); sg.upper = out.col(2);
+    if (y) { sg.lpd = out.col(3); sg.pwaic = out.col(4); }
+    if (pred_lower) { sg.seed = pred_seed; sg.pred_lower = out.col(5); sg.pred_upper = out.col(6); }
+    if (pit) sg.pit = out.col(7);
+    if ((rc = predict_rows(cs, nc, first_row, nsamp, m, Xd, m_pad, yd, sg, tmp))) return rc;
+    return out.fetch(st, "predict", "k_predict", {mean, lower, upper, y ? lpd : nullptr, y ? pwaic : nullptr, pred_lower, pred_lower ? pred_upper : nullptr, pit});
+}
+// the checks of the single-chain entry points, in their order
+static int predict_one(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const x_source &xs, const double *y, int32_t k_lo, int32_t k_hi,
+                       double *mean, double *lower, double *upper, double *lpd, double *pwaic)
+{
+    if (!c || !mean || !lower || !upper || (!xs.X && !xs.mats) || (y && (!lpd || !pwaic))) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
+    return predict_call(&c, 1, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic, 0, nullptr, nullptr, nullptr);
+}
+// ... and of the pooled ones: pred_lower and pred_upper come together; lpd / pwaic and pit need y
+static int predict_pooled(bnr_chain *const *cs, int32_t nc, int32_t first_row, int32_t nsamp, int32_t m, const x_source &xs, const double *y, int32_t k_lo,
+                          int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic, uint64_t pred_seed, double *pred_lower,
+                          double *pred_upper, double *pit)
+{
+    if (!cs || !mean || !lower || !upper || (!xs.X && !xs.mats) || (y && (!lpd || !pwaic)) || (!pred_lower != !pred_upper))
+        return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (pit && !y) return fail(BNR_ERR_BAD_ARG, "pit needs the observed responses y");
+    if (int rc = pooled_check(cs, nc, first_row, nsamp)) return rc;
+    return predict_call(cs, nc, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic, pred_seed, pred_lower, pred_upper, pit);
+}
+int bnr_chain_predict(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const void *X, int32_t x_dtype, const double *y,
+                      int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic)
+{
+    x_source xs;
+    xs.X = X; xs.dtype = x_dtype;
+    return predict_one(c, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic);
+}
+int bnr_chain_predict_from_matrices(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const void *const *A, int32_t x_dtype,
+                                    const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic)
+{
+    x_source xs;
+    xs.mats = A; xs.dtype = x_dtype;
+    return predict_one(c, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic);
+}
+int bnr_chains_predict(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t m, const void *X, int32_t x_dtype,
+                       const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic,
+                       uint64_t pred_seed, double *pred_lower, double *pred_upper, double *pit)
+{
+    x_source xs;
+    xs.X = X; xs.dtype = x_dtype;
+    return predict_pooled(chains, nchains, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic, pred_seed, pred_lower, pred_upper, pit);
+}
+int bnr_chains_predict_from_matrices(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t m, const void *const *A,
+                                     int32_t x_dtype, const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper,
+                                     double *lpd, double *pwaic, uint64_t pred_seed, double *pred_lower, double *pred_upper, double *pit)
+{
+    x_source xs;
+    xs.mats = A; xs.dtype = x_dtype;
+    return predict_pooled(chains, nchains, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic, pred_seed, pred_lower, pred_upper, pit);
+}
+// the element-by-element host mirror of k_pred_noise's draws: out[(i - i0) ns + (s - s0)] = bnr_normal(seed, s, SITE_PRED, i, 0)
+void bnr_host_pred_noise(uint64_t seed, uint32_t s0, uint32_t ns, uint32_t i0, uint32_t ni, double *out)
+{
+    if (!out) return;
+    for (uint32_t i = 0; i < ni; ++i)
+        for (uint32_t s = 0; s < ns; ++s) out[(size_t)i * ns + s] = bnr_normal(seed, s0 + s, SITE_PRED, i0 + i, 0u);
+}
+// The calls on the chains' own training rows: X (n_pad x q_pad, zero padded) and y are on the device already.  analysis_call holds what they
+// share: the device, the quiesce, the result slab of k columns of n doubles and -- with_tails: for PSIS -- the tail lengths on the device
+struct analysis_call {
+    dev_tmp tmp;
+    result_slab out;
+    pred_stages sg;
+    hipStream_t st = nullptr;
+    int begin(bnr_chain *const *cs, int nc, int k, const std::vector<int> *tails, int lds)
+    {
+        bnr_chain *c = cs[0];
+        HIPCHK(hipSetDevice(c->device));
+        st = c->x.stream;
+        int rc;
+        if ((rc = pooled_quiesce(cs, nc))) return rc;
+        if ((rc = out.alloc(tmp, k, (size_t)c->d.n, st))) return rc;
+        if (tails) {
+            int *tl = nullptr;
+            if ((rc = tmp.alloc(&tl, (size_t)c->d.n, st))) return rc;
+            HIPCHK(hipMemcpyAsync(tl, tails->data(), sizeof(int) * c->d.n, hipMemcpyHostToDevice, st));
+            sg.tail_len = tl; sg.lds = lds;
+            sg.psis_lpd = out.col(0); sg.elpd = out.col(1); sg.khat = out.col(2);
+        }
+        return BNR_OK;
+    }
+    int run(bnr_chain *const *cs, int nc, int first_row, int nsamp)
+    {
+        const bnr_dev &d = cs[0]->d;
+        return predict_rows(cs, nc, first_row, nsamp, d.n, d.X, d.n_pad, d.y, sg, tmp);
+    }
+};
+// pointwise lpd and WAIC penalty (and, pooled entry point only, the PIT)
+static int loglik_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic, double *pit)
+{
+    analysis_call a;
+    int rc;
+    if ((rc = a.begin(cs, nc, pit ? 3 : 2, nullptr, 0))) return rc;
+    a.sg.lpd = a.out.col(0); a.sg.pwaic = a.out.col(1);
+    if (pit) a.sg.pit = a.out.col(2);
+    if ((rc = a.run(cs, nc, first_row, nsamp))) return rc;
+    return a.out.fetch(a.st, "loglik_stats", "k_pred_loglik", {lpd, pwaic, pit});
+}
+int bnr_chain_loglik_stats(bnr_chain *c, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic)
+{
+    if (!c || !lpd || !pwaic) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
+    return loglik_call(&c, 1, first_row, nsamp, lpd, pwaic, nullptr);
+}
+int bnr_chains_loglik_stats(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic, double *pit)
+{
+    if (!chains || !lpd || !pwaic) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
+    return loglik_call(chains, nchains, first_row, nsamp, lpd, pwaic, pit);
+}
+
+// loo 2.x's tail length M = ceil(min(0.2 S, 3 sqrt(S / r_eff))) of every row (r_eff NULL: 1), checked against BNR_PSIS_MAX_TAIL, and the
+// dynamic LDS of the longest tail that is smoothed (M >= 5), P = its length rounded up to a power of two: 16 bytes per entry for k_psis
+// (entry_bytes' default), 12 for k_psis_w; 8 KiB at least (the histogram of the radix select)
+static int psis_tail_lengths(int m, int nsamp, const double *r_eff, std::vector<int> &M, int &lds, int entry_bytes = 16)
+{
+    M.assign(m, 0);
+    int pmax = 0;
+    for (int i = 0; i < m; ++i) {
+        const double r = r_eff ? r_eff[i] : 1.0;
+        if (!(r > 0.0) || !std::isfinite(r)) return fail(BNR_ERR_BAD_ARG, "r_eff must be positive and finite");
+        const double t = std::ceil(std::min(0.2 * nsamp, 3.0 * std::sqrt(nsamp / r)));
+        if (t > BNR_PSIS_MAX_TAIL)
+            return fail(BNR_ERR_BAD_ARG, "PSIS tail length " + std::to_string((long long)t) + " of row " + std::to_string(i + 1) + " exceeds the supported " +
+                                             std::to_string(BNR_PSIS_MAX_TAIL) + " (raise r_eff or shorten the window)");
+        M[i] = (int)t;
+        if (M[i] >= 5) {
+            int p = 8;
+            while (p < M[i]) p <<= 1;
+            pmax = std::max(pmax, p);
+        }
+    }
+    lds = std::max(8192, entry_bytes * pmax);
+    return BNR_OK;
+}
+// PSIS-LOO of the chains' own training rows over rows first_row .. first_row+nsamp-1 of every chain listed (k_predict, then k_psis on every block
+// of rows); the tail length comes from the pooled draw count
+static int loo_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo, double *pareto_k)
+{
+    std::vector<int> M;
+    int lds = 0, rc;
+    if ((rc = psis_tail_lengths(cs[0]->d.n, nc * nsamp, r_eff, M, lds))) return rc;
+    HIPCHK(hipSetDevice(cs[0]->device));
+    if ((rc = psis_lds_attributes())) return rc;
+    analysis_call a;
+    if ((rc = a.begin(cs, nc, 3, &M, lds))) return rc;
+    if ((rc = a.run(cs, nc, first_row, nsamp))) return rc;
+    return a.out.fetch(a.st, "loo", "k_psis", {lpd, elpd_loo, pareto_k});
+}
+int bnr_chain_loo(bnr_chain *c, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo, double *pareto_k)
+{
+    if (!c || !elpd_loo || !pareto_k) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
+    return loo_call(&c, 1, first_row, nsamp, r_eff, lpd, elpd_loo, pareto_k);
+}
+int bnr_chains_loo(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo,
+                   double *pareto_k)
+{
+    if (!chains || !elpd_loo || !pareto_k) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
+    return loo_call(chains, nchains, first_row, nsamp, r_eff, lpd, elpd_loo, pareto_k);
+}
+
+// LOO predictive checks (ABI 11) of the chains' own training rows over the pooled window: k_predict, then k_psis_w (the PSIS weights of the block),
+// k_loo_moments and k_loo_quantile on every block of rows.  Every output is nullable; lpd, elpd_loo and pareto_k always come from k_psis_w.
+static int loo_predict_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, const double *r_eff, double p_lo, double p_hi, double *lpd,
+                            double *elpd_loo, double *pareto_k, double *loo_mean, double *loo_sd, double *loo_pit, double *loo_lower, double *loo_upper)
+{
+    const bool bounds = loo_lower || loo_upper, moments = loo_mean || loo_sd || loo_pit;
+    double cc = 0.0;
+    if (bounds) {
+        if (!(p_lo > 0.0) || !(p_hi < 1.0) || !(p_lo < p_hi)) return fail(BNR_ERR_BAD_ARG, "need 0 < p_lo < p_hi < 1");
+        const double pm = 0.5 * std::min(p_lo, 1.0 - p_hi);
+        for (cc = 1.0; !(0.5 * std::erfc(cc * 0.70710678118654752440) < pm) && cc < 40.0; cc += 0.5) { }
+    }
+    std::vector<int> M;
+    int lds = 0, rc;
+    if ((rc = psis_tail_lengths(cs[0]->d.n, nc * nsamp, r_eff, M, lds, BNR_PSISW_ENTRY_BYTES))) return rc;
+    HIPCHK(hipSetDevice(cs[0]->device));
+    if ((rc = psis_lds_attributes())) return rc;
+    analysis_call a;
+    if ((rc = a.begin(cs, nc, 8, &M, lds))) return rc;
+    pred_stages &sg = a.sg;
+    sg.keep_weights = true;
+    if (moments) { sg.loo_mean = a.out.col(3); sg.loo_sd = a.out.col(4); sg.loo_pit = a.out.col(5); }
+    if (loo_lower) sg.loo_lower = a.out.col(6);
+    if (loo_upper) sg.loo_upper = a.out.col(7);
+    sg.p_lo = p_lo; sg.p_hi = p_hi; sg.c = cc;
+    if ((rc = a.run(cs, nc, first_row, nsamp))) return rc;
+    return a.out.fetch(a.st, "loo_predict", "k_psis_w", {lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper});
+}
+int bnr_chain_loo_predict(bnr_chain *c, int32_t first_row, int32_t nsamp, const double *r_eff, double p_lo, double p_hi, double *lpd, double *elpd_loo,
+                          double *pareto_k, double *loo_mean, double *loo_sd, double *loo_pit, double *loo_lower, double *loo_upper)
+{
+    if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
+    return loo_predict_call(&c, 1, first_row, nsamp, r_eff, p_lo, p_hi, lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper);
+}
+int bnr_chains_loo_predict(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, const double *r_eff, double p_lo, double p_hi,
+                           double *lpd, double *elpd_loo, double *pareto_k, double *loo_mean, double *loo_sd, double *loo_pit, double *loo_lower,
+                           double *loo_upper)
+{
+    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
+    return loo_predict_call(chains, nchains, first_row, nsamp, r_eff, p_lo, p_hi, lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper);
+}
+
+// The device work of bnr_psis_loo and bnr_psis_weights on a stream of its own: the rows of the caller's matrix in blocks, k_psis<0> on every block
+// of about 1 GiB; with log_weights k_psis_w<0> on every block of about 512 MiB (l and the weights side by side), the block's weights copied back
+// behind it (and no lpd)
+static int psis_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *log_weights, double *lpd, double *elpd,
+                       double *khat)
+{
+    stream_guard guard;
+    HIPCHK(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
+    hipStream_t st = guard.s;
+    const size_t budget = log_weights ? (size_t)1 << 29 : (size_t)1 << 30;
+    const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, budget / ((size_t)nsamp * sizeof(double))));
+    int rc;
+    dev_tmp tmp;                                        // (freed before the stream goes)
+    double *Ld = nullptr, *Wd = nullptr;
+    int *tl = nullptr;
+    result_slab out;
+    if ((rc = tmp.alloc(&Ld, (size_t)blk * nsamp, st))) return rc;
+    if (log_weights && (rc = tmp.alloc(&Wd, (size_t)blk * nsamp, st))) return rc;
+    if ((rc = out.alloc(tmp, 3, (size_t)m, st))) return rc;
+    if ((rc = tmp.alloc(&tl, (size_t)m, st))) return rc;
+    HIPCHK(hipMemcpyAsync(tl, tail_len.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
+    for (int i0 = 0; i0 < m; i0 += blk) {
+        const int mr = std::min(blk, m - i0);
+        HIPCHK(hipMemcpyAsync(Ld, loglik + (size_t)i0 * nsamp, sizeof(double) * (size_t)mr * nsamp, hipMemcpyHostToDevice, st));
+        if (log_weights) {
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis_w<0>), dim3(mr), dim3(256), lds, st, (const double *)Ld, nsamp, (const double *)nullptr,
+                               (const double *)nullptr, (const int *)tl + i0, Wd, (double *)nullptr, out.col(1) + i0, out.col(2) + i0);
+            HIPCHK(hipMemcpyAsync(log_weights + (size_t)i0 * nsamp, Wd, sizeof(double) * (size_t)mr * nsamp, hipMemcpyDeviceToHost, st));
+        } else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis<0>), dim3(mr), dim3(256), lds, st, Ld, nsamp, (const double *)nullptr, (const double *)nullptr,
+                               (const int *)tl + i0, out.col(0) + i0, out.col(1) + i0, out.col(2) + i0);
+    }
+    return out.fetch(st, log_weights ? "psis_weights" : "psis_loo", log_weights ? "k_psis_w" : "k_psis", {lpd, elpd, khat});
+}
+// PSIS on a caller's m x nsamp log-likelihood matrix (host, row-major): bnr_psis_loo (k_psis) and its companion bnr_psis_weights, which also
+// returns the weights (k_psis_w: log_weights != NULL).  The shared front: the checks in their order, the tail lengths, the device
+static int psis_call(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *log_weights, double *lpd, double *elpd_loo,
+                     double *pareto_k)
+{
+    if (m < 1 || nsamp < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows and nsamp >= 1 draws");
+    std::vector<int> M;
+    int lds = 0, rc, ndev = 0;
+    if ((rc = psis_tail_lengths(m, nsamp, r_eff, M, lds, log_weights ? BNR_PSISW_ENTRY_BYTES : 16))) return rc;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
+    HIPCHK(hipSetDevice(device));
+    if ((rc = psis_lds_attributes())) return rc;
+    return psis_matrix(m, nsamp, loglik, M, lds, log_weights, lpd, elpd_loo, pareto_k);
+}
+int bnr_psis_loo(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *elpd_loo, double *pareto_k, double *lpd)
+{
+    if (!loglik || !elpd_loo || !pareto_k) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    return psis_call(device, m, nsamp, loglik, r_eff, nullptr, lpd, elpd_loo, pareto_k);
+}
+int bnr_psis_weights(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *log_weights, double *elpd_loo,
+                     double *pareto_k)
+{
+    if (!loglik || !log_weights) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    return psis_call(device, m, nsamp, loglik, r_eff, log_weights, nullptr, elpd_loo, pareto_k);
+}

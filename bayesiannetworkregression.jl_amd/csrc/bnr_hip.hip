@@ -1,24 +1,18 @@
 // bnr_hip.hip -- C ABI (include/bnr_hip.h) over the gfx950 kernels in bnr_kernels.h.
 // Host side: chain allocation (own or shared device inputs), the run! loop with the purge ring (gibbs.jl:849-864) for one
 // chain or for a lockstep group of chains (one launch per kernel for all members), the test hooks that mirror the
-// reference's update_*! functions, table fetch/load, the split-Rhat / ESS messages, the device-side Summary and posterior prediction.
-#include "../../include/bnr_hip.h"
+// reference's update_*! functions, table fetch/load, the split-Rhat / ESS messages.  The posterior analysis is bnr_analysis.hip.
+#include "bnr_internal.h"
 #include "bnr_kernels.h"
 
 #include <dlfcn.h>
 
-#include <algorithm>
 #include <cmath>
 #include <cstdio>
-#include <cstring>
-#include <initializer_list>
-#include <memory>
 #include <mutex>
-#include <string>
-#include <vector>
 
 static thread_local std::string g_err;
-static int fail(int code, const std::string &msg) { g_err = msg; return code; }
+int fail(int code, const std::string &msg) { g_err = msg; return code; }
 // HIP calls inside the launch helpers (event records, stream waits): their first failure is kept and reported by the next
 // check_launch(), like a failed kernel launch
 static thread_local hipError_t g_noted = hipSuccess;
@@ -28,88 +22,6 @@ static thread_local const char *g_noted_what = nullptr;
         hipError_t _e = (expr);                                                                        \
         if (_e != hipSuccess && g_noted == hipSuccess) { g_noted = _e; g_noted_what = #expr; }         \
     } while (0)
-#define HIPCHK(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess)                                                                          \
-            return fail(BNR_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));               \
-    } while (0)
-
-// Where and how sweeps are issued: ONE chain, or a lockstep group of equally shaped chains whose kernels are launched
-// together (blockIdx.z = member).  Kernels read their chain's bnr_dev from the device array `cds`.
-struct bnr_exec {
-    int device = 0;
-    int ncu = 256;                                      // compute units of the device
-    int nb = 1;                                         // chains issued together
-    bnr_dev *cds = nullptr;                             // device array of nb structs
-    const bnr_dev *shape = nullptr;                     // host struct of member 0 (sizes are equal for all members)
-    hipStream_t stream = nullptr, stream2 = nullptr;   // stream2: the Gram branch of a sweep
-    std::vector<hipEvent_t> fj;                         // fork/join events
-    size_t fj_next = 0;
-    int overlap = 1;
-    int gram_variant = 0;                               // 0: chosen per launch; 8 / 16: k_gram8 / k_gram forced (tests, experiments)
-    int fuse_reduce = -1;                               // -1 / 1: launch 0 of the one-panel factorization also sums the Gram's K-split partials (no k_gram_reduce launch); 0: separate pass
-    int group_xpass = -1;                               // -1 / 1: a group whose members share X runs the X pass with one workgroup per chunk for all chains; 0: per chain
-    bnr_plan_entry *gplan_pin = nullptr, *gplan_dev = nullptr;   // groups: the members' plans of a run call, staged for one copy
-    int gplan_cap = 0;                                  // entries per member in there
-    int wide_backproj = -1;                              // 1: k_backproj64 (64 edges per workgroup, one edge per lane of the drawing wave); -1: launches of many rounds (a group at large q)
-    int split_sums = -1;                                 // 1: the back-projection's partial sums as a launch of their own in front of the scalar tail (off the critical chain)
-    int spw_cap = 1;                                    // super blocks per update workgroup of the factorization, at most (round 6: 1 -- with the four-wave panel sweep (bnr_panel_sweep_pipe) one block each is the shorter launch: 8 chains 369.4 against 372-374 us per sweep; rounds 3-5 packed up to 4 behind the single sweeping wave)
-    // Round 6: WHEN the scalar branch's kernels start is part of the schedule (profiles/round6_experiments_notes.txt A): inside the two-branch sweep they are ordered behind
-    // points of the critical chain by events (graph edges), instead of starting whenever the dispatcher lets the second queue in.
-    int tail_after = -2;                                // k_tail(s-1) waits for: -1 nothing (rounds 1-5), 0 the Gram of sweep s; -2: default by size (tail_after_default)
-    int node_after = -2;                                // k_node(s) waits for factorization launch number node_after (0-based; -1 nothing); -2: default by size (node_after_default)
-    int factor_variant = -1;                            // -1: chosen by size; 0: right-looking k_chol_step (+ k_gram_reduce); 2 / 3: two panels per launch (k_chol_step2), 3 with the K = 128 trailing update
-    int use_graph = 1, graph_k = 16;                     // (round 5: 16, was 8 -- between two graph launches the GPU idles ~30 us: 640 sweeps 382.2 -> 380.1 us each, 20 sweeps = 16 + 4 instead of 8 + 8 + 4)
-    struct rung { int k; hipGraph_t graph; hipGraphExec_t gexec; };
-    std::vector<rung> ladder;                           // captured graphs of graph_k, graph_k/2, ..., 1 sweeps: any batch is replayed
-    bnr_dev *cds_pin = nullptr;                         // pinned staging of the members' descriptors
-    long long *status_dev = nullptr, *status_pin = nullptr;   // nb x 16: the members' event counters, gathered once per run call
-    int64_t n_replayed = 0, n_eager = 0;                // sweeps issued by graph replay / eagerly since the last run call began
-    // profiling
-    int profiling = 0;
-    std::vector<hipEvent_t> ev;  // pairs around k_gram
-    double t_gram_us = 0, t_iter_us = 0, t_gram_acc = 0;
-    int64_t n_gram = 0, n_iter = 0;
-};
-
-// read-only device inputs of a fit (model matrix, response, edge maps, Gram task map): shared by the chains created
-// with bnr_chain_create_like, freed with the last of them
-struct bnr_inputs {
-    std::vector<void *> bufs;
-    ~bnr_inputs() { for (void *p : bufs) (void)hipFree(p); }
-};
-
-struct bnr_chain {
-    bnr_dev d{};
-    std::shared_ptr<bnr_inputs> in;
-    bnr_exec x;                  // issues this chain alone
-    int device = 0;
-    std::vector<void *> allocs;
-    bnr_plan_entry *plan_dev = nullptr, *plan_pin = nullptr;
-    int plan_cap = 0;
-    int64_t iter = 0;            // global iteration id of the last drawn row
-    int carried_row = -1;        // 0-based row whose (rr, sig_q) are in d.scal; -1 = invalid
-    int next_row = 0;            // 1-based j the next run call would write
-    bool pending = false;
-    long long *counters_host = nullptr;
-    int *pbase_dev = nullptr;
-    size_t trace_bytes = 0;
-    struct bnr_group *group = nullptr;   // lockstep group this chain belongs to (at most one)
-    const unsigned char *x8_kept = nullptr;   // the byte image of X (also while option "byte_x" is 0); nullptr: the input had none
-    const unsigned char *xm_kept = nullptr;   // the byte MASK of a 0/1 model matrix for the i8 Gram (also while option "gram_i8" is 0); nullptr: the input was not binary
-    long long cap_seen = 0;      // sampler-cap events already reported (the device counter is cumulative: a capped draw is reported by the call it happened in, once)
-    int predict_block_rows = 0;  // tunable "predict_block_rows": rows per block of bnr_chain_predict / bnr_chain_loglik_stats (0: automatic)
-    int summary_block_cols = 0;  // tunable "summary_block_cols": parameter columns per staging block of the Summary calls (0: automatic)
-    int rank_block_cols = 0;     // tunable "rank_block_cols": parameter columns per staging block of the rank-normalised diagnostics (0: automatic)
-};
-
-struct bnr_group {
-    std::vector<bnr_chain *> m;
-    bnr_exec x;                  // issues all members together
-};
-
-static int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
 template <typename T>
 static int dev_alloc(bnr_chain *c, T **p, size_t count, bool zero = true)
@@ -136,60 +48,6 @@ struct bnr_exec;
 static int late_kernels_lds_attributes(int bytes);
 static void launch_late_xpass_group2(bnr_exec &x, int s);
 static void launch_late_backproj64(bnr_exec &x, int s, int flags, size_t lds64);
-// device temporaries of one call, freed on every path (zeroed on the chain's stream, see dev_alloc; zero = false: a staging buffer that is
-// written whole before it is read)
-struct dev_tmp {
-    std::vector<void *> p;
-    ~dev_tmp() { for (void *q : p) (void)hipFree(q); }
-    template <typename T>
-    int alloc(T **out, size_t count, hipStream_t st, bool zero = true)
-    {
-        void *q = nullptr;
-        HIPCHK(hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)));
-        p.push_back(q);
-        if (zero) HIPCHK(hipMemsetAsync(q, 0, std::max<size_t>(count, 1) * sizeof(T), st));
-        *out = (T *)q;
-        return BNR_OK;
-    }
-};
-// What a predict_rows call computes from a block's E behind k_predict, in the order of its launches; every pointer is a device pointer, and a
-// NULL one skips its stage
-struct pred_stages {
-    int k_lo = 0, k_hi = 0;                                        // k_summary: mean and the k_lo-th / k_hi-th smallest of every E column
-    double *mean = nullptr, *lower = nullptr, *upper = nullptr;
-    double *lpd = nullptr, *pwaic = nullptr;                       // k_pred_loglik (needs yd)
-    // PSIS (needs yd): the per-row tail lengths, the kernel's dynamic LDS, its outputs (never NULL).  keep_weights = false: k_psis, which
-    // overwrites E; true: k_psis_w and on its weights the LOO predictive checks (ABI 11): k_loo_moments (all three or none) and k_loo_quantile
-    // (each bound nullable) with its probabilities and the bracket's c (Phi(-c) < min(p_lo, 1 - p_hi) / 2)
-    const int *tail_len = nullptr;
-    int lds = 0;
-    bool keep_weights = false;
-    double *psis_lpd = nullptr, *elpd = nullptr, *khat = nullptr;
-    double *loo_mean = nullptr, *loo_sd = nullptr, *loo_pit = nullptr, *loo_lower = nullptr, *loo_upper = nullptr;
-    double p_lo = 0.0, p_hi = 0.0, c = 0.0;
-    double *pit = nullptr;                                         // k_pred_pit: the PIT of the observed responses (needs yd)
-    unsigned long long seed = 0;                                   // k_pred_noise with `seed`, then a second k_summary: the k_lo-th / k_hi-th
-    double *pred_lower = nullptr, *pred_upper = nullptr;           // smallest draw of a new observation (both or none; overwrites E)
-};
-static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, const pred_stages &sg,
-                        dev_tmp &tmp);
-// (defined at the very end of this file, behind every other kernel reference: see ensure_lds_attributes)
-static int loow_lds_attributes();
-static void launch_loow_inv_sd(hipStream_t st, const double *tau2, int S, double *isd);
-static void launch_loow_block(hipStream_t st, const pred_stages &sg, const double *E, double *LW, int S, int mr, int i0, const double *yd, const double *tau2,
-                              const double *isd);
-static int psis_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *log_weights, double *lpd, double *elpd,
-                       double *khat);
-// the rank-normalised diagnostics (ABI 12): k_rank's two (key, index) buffers, one slice of ld entries per column; k_rank and k_fold are launched
-// from the end of this file, like the other late kernels
-struct rank_bufs { unsigned long long *keyA = nullptr, *keyB = nullptr; unsigned int *idxA = nullptr, *idxB = nullptr; };
-static void launch_rank(hipStream_t st, int cols, const double *buf, long long ld, int nsamp, int nch, int all, const rank_bufs &rb, int k05, int k95,
-                        double *ranks, double *z, double *ind05, double *ind95, double *med, int *flag);
-static void launch_fold(hipStream_t st, int cols, const double *buf, long long ld, const double *med, int absolute, double *out);
-// highest-density intervals and sign probabilities (ABI 13): k_hdi on `cols` staged columns of n draws with k_rank's key buffers (the index
-// buffers stay unused); launched from the end of this file, behind k_rank / k_fold
-static void launch_hdi(hipStream_t st, int cols, const double *buf, long long ld, int n, const rank_bufs &rb, int nprob, const bnr_hdi_levels &lv, double *lower,
-                       double *upper, long long lstride, double *med, double *p_pos, double *p_neg);
 static int ensure_lds_attributes(int device)
 {
     static std::mutex mu;
@@ -212,29 +70,8 @@ static int ensure_lds_attributes(int device)
 extern "C" {
 
 static int exec_init(bnr_exec &x, int device, int nb, const bnr_dev *shape);
-static int check_launch(const char *what);
 static void exec_free(bnr_exec &x);
 static int sync_dev(bnr_chain *c);
-// The results of one call: k columns of m doubles on the device (zeroed), brought to the host in one copy.  fetch: the copy and the sync on st
-// (a failure is reported as "<call>: ..."), the launch check under the kernel's name, then column j into dst[j] where that is not NULL
-struct result_slab {
-    double *d = nullptr;
-    size_t m = 0;
-    int k = 0;
-    int alloc(dev_tmp &tmp, int cols, size_t rows, hipStream_t st) { k = cols; m = rows; return tmp.alloc(&d, (size_t)k * m, st); }
-    double *col(int j) const { return d + (size_t)j * m; }
-    int fetch(hipStream_t st, const char *call, const char *kernel, std::initializer_list<double *> dst) const
-    {
-        std::vector<double> host((size_t)k * m);
-        hipError_t e = hipMemcpyAsync(host.data(), d, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string(call) + ": " + hipGetErrorString(e));
-        if (int rc = check_launch(kernel)) return rc;
-        size_t j = 0;
-        for (double *p : dst) { if (p) memcpy(p, host.data() + j * m, sizeof(double) * m); ++j; }
-        return BNR_OK;
-    }
-};
 
 int bnr_abi_version(void) { return BNR_ABI_VERSION; }
 const char *bnr_last_error(void) { return g_err.c_str(); }
@@ -288,15 +125,7 @@ static int alloc_trace(bnr_chain *c, int tot, double **out)
     return BNR_OK;
 }
 
-// Where the model matrix comes from: the n x q matrix X_new of generate_samples! (gibbs.jl:917-918) in one of the element types
-// the reference accepts (Matrix{eltype(T)}: Bool, Int, Float64 ...), or the vector of n adjacency matrices itself, vectorised on
-// the device (setup_X!, gibbs.jl:239-247: row i = lower_triangle(X[i]), utils.jl:40-57).
-struct x_source {
-    const void *X = nullptr;               // n x q column-major (mats == nullptr)
-    const void *const *mats = nullptr;     // n pointers to V x V column-major matrices
-    int dtype = BNR_F64;
-};
-static size_t dtype_size(int t) { return t == BNR_U8 ? 1 : (t == BNR_I32 || t == BNR_F32) ? 4 : 8; }
+extern "C++" size_t dtype_size(int t) { return t == BNR_U8 ? 1 : (t == BNR_I32 || t == BNR_F32) ? 4 : 8; }
 // k_x_convert on `rows` rows of raw (on the device, host layout, element type dtype; mats: V x V matrices) into the f64 matrix Xd of leading
 // dimension ld; an integer type also fills the byte image X8 (nullable), not_bytes (nullable) is raised by an entry that is no byte
 extern "C++" template <typename T>
@@ -305,7 +134,7 @@ static void launch_x_convert_as(const void *raw, bool mats, int rows, const bnr_
     hipLaunchKernelGGL(k_x_convert<T>, dim3((rows + 63) / 64, std::min(d.q, 65535)), dim3(64), 0, st, (const T *)raw, mats, rows, d.V, d.q, ld, d.ek, d.el, Xd, X8,
                        not_bytes);
 }
-static void launch_x_convert(int dtype, const void *raw, bool mats, int rows, const bnr_dev &d, int ld, double *Xd, unsigned char *X8, int *not_bytes, hipStream_t st)
+extern "C++" void launch_x_convert(int dtype, const void *raw, bool mats, int rows, const bnr_dev &d, int ld, double *Xd, unsigned char *X8, int *not_bytes, hipStream_t st)
 {
     switch (dtype) {
     case BNR_U8:  launch_x_convert_as<uint8_t>(raw, mats, rows, d, ld, Xd, X8, not_bytes, st); break;
@@ -718,7 +547,7 @@ static int upload_plan(bnr_chain *c, int count, hipStream_t st = nullptr)
     HIPCHK(hipMemsetAsync(c->pbase_dev, 0, sizeof(int), st));
     return BNR_OK;
 }
-static int check_launch(const char *what)
+extern "C++" int check_launch(const char *what)
 {
     hipError_t e = hipGetLastError();
     if (g_noted != hipSuccess) {
@@ -1694,6 +1523,14 @@ int bnr_chain_set_iter(bnr_chain *c, int64_t iter)
     return BNR_OK;
 }
 
+// k_fetch_cols, k_summary, k_acov for both translation units (bnr_internal.h)
+extern "C++" void launch_fetch_cols(hipStream_t st, const double *trace, int rowlen, int off, int ncols, int first, int nrows, double *out, long long ldo)
+{ hipLaunchKernelGGL(k_fetch_cols, dim3((ncols + 31) / 32, (nrows + 31) / 32), dim3(32, 8), 0, st, trace, rowlen, off, ncols, first, nrows, out, ldo); }
+extern "C++" void launch_summary(hipStream_t st, int cols, const double *buf, int nsamp, int q, int k_lo, int k_hi, double *mean, double *lo, double *hi)
+{ hipLaunchKernelGGL(k_summary, dim3(cols), dim3(256), 0, st, buf, nsamp, q, k_lo, k_hi, mean, lo, hi); }
+extern "C++" void launch_acov(hipStream_t st, const double *buf, int nsamp, int np, int L, double *out)
+{ hipLaunchKernelGGL(k_acov, dim3(np, 2), dim3(256), 0, st, buf, nsamp, np, L, out); }
+
 // ------------------------------------------------------------------------------------------ table I/O
 struct col_desc { int off, ncols; };
 static void col_layout(const bnr_dev &d, col_desc out[11])
@@ -1725,17 +1562,16 @@ static int table_io(bnr_chain *c, bool fetch, int first_row, int last_row, int h
         if (!cols[k]) continue;
         for (int c0 = 0; c0 < cdsc[k].ncols && !rc; c0 += cols_per) {
             int nc = std::min(cols_per, cdsc[k].ncols - c0);
-            dim3 grid((nc + 31) / 32, (nrows + 31) / 32), block(32, 8);
             double *hbase = cols[k] + (size_t)(first_row - 1 + host_off) + (size_t)host_tot * c0;
             hipError_t e;
             if (fetch) {
-                hipLaunchKernelGGL(k_fetch_cols, grid, block, 0, c->x.stream, (const double *)d.trace, d.rowlen, cdsc[k].off + c0, nc, first_row - 1, nrows, stage, (long long)nrows);
+                launch_fetch_cols(c->x.stream, d.trace, d.rowlen, cdsc[k].off + c0, nc, first_row - 1, nrows, stage, nrows);
                 e = hipMemcpy2DAsync(hbase, (size_t)host_tot * sizeof(double), stage, (size_t)nrows * sizeof(double),
                                      (size_t)nrows * sizeof(double), nc, hipMemcpyDeviceToHost, c->x.stream);
             } else {
                 e = hipMemcpy2DAsync(stage, (size_t)nrows * sizeof(double), hbase, (size_t)host_tot * sizeof(double),
                                      (size_t)nrows * sizeof(double), nc, hipMemcpyHostToDevice, c->x.stream);
-                hipLaunchKernelGGL(k_load_cols, grid, block, 0, c->x.stream, d.trace, d.rowlen, cdsc[k].off + c0, nc, first_row - 1, nrows, (const double *)stage);
+                hipLaunchKernelGGL(k_load_cols, dim3((nc + 31) / 32, (nrows + 31) / 32), dim3(32, 8), 0, c->x.stream, d.trace, d.rowlen, cdsc[k].off + c0, nc, first_row - 1, nrows, (const double *)stage);
             }
             if (e != hipSuccess) rc = fail(BNR_ERR_HIP, std::string("table copy: ") + hipGetErrorString(e));
             if (!rc && hipStreamSynchronize(c->x.stream) != hipSuccess) rc = fail(BNR_ERR_HIP, "table copy sync failed");
@@ -2057,117 +1893,6 @@ int bnr_rhat(bnr_chain *const *chains, int32_t nchains_local, int32_t nchains_to
     return BNR_OK;
 }
 
-// The state and row window of the chains of an analysis call: none with a pending asynchronous run, the window inside every table
-static int window_check(bnr_chain *const *cs, int nc, int first_row, int nsamp)
-{
-    for (int i = 0; i < nc; ++i) if (cs[i]->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
-    for (int i = 0; i < nc; ++i)
-        if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > cs[i]->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
-    return BNR_OK;
-}
-// The chains of a pooled call (bnr_chains_*): one device, equal n, V, R, none listed twice, window_check, the pooled draw count within int32
-static int pooled_check(bnr_chain *const *cs, int nc, int first_row, int nsamp)
-{
-    if (!cs) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (nc < 1) return fail(BNR_ERR_BAD_ARG, "need nchains >= 1");
-    for (int i = 0; i < nc; ++i) {
-        if (!cs[i]) return fail(BNR_ERR_BAD_ARG, "NULL chain");
-        for (int k = 0; k < i; ++k) if (cs[k] == cs[i]) return fail(BNR_ERR_BAD_ARG, "chain listed twice");
-        const bnr_dev &a = cs[0]->d, &b = cs[i]->d;
-        if (cs[i]->device != cs[0]->device || a.n != b.n || a.V != b.V || a.R != b.R)
-            return fail(BNR_ERR_BAD_ARG, "pooled chains must live on one device and have equal n, V, R");
-    }
-    if (int rc = window_check(cs, nc, first_row, nsamp)) return rc;
-    if ((long long)nc * nsamp > 0x7FFFFFFFll) return fail(BNR_ERR_BAD_ARG, "more than 2^31 - 1 pooled draws");
-    return BNR_OK;
-}
-// The pooled work runs on the first chain's stream and reads the other chains' tables: whatever their own streams (and their group's) still
-// hold -- a table load, the tail of a synchronous run -- is waited for here.  (One chain: nothing to order, as before.)
-static int pooled_quiesce(bnr_chain *const *cs, int nc)
-{
-    for (int i = 1; i < nc; ++i) {
-        HIPCHK(hipStreamSynchronize(cs[i]->x.stream));
-        if (cs[i]->group) HIPCHK(hipStreamSynchronize(cs[i]->group->x.stream));
-    }
-    return BNR_OK;
-}
-
-// Parameter columns p0 .. p0 + pc - 1 of [gamma(q) | xi(V)] over the pooled window, staged by k_fetch_cols: column p of `buf` holds S = nc nsamp
-// draws, chain k's window in rows k nsamp .. (k + 1) nsamp - 1 (one launch per chain and per kind of column)
-static void stage_cols(hipStream_t st, bnr_chain *const *cs, int nc, int first_row, int nsamp, int p0, int pc, double *buf)
-{
-    const bnr_dev &d = cs[0]->d;
-    const long long S = (long long)nc * nsamp;
-    const dim3 block(32, 8);
-    const int g0 = std::min(p0, d.q), g1 = std::min(p0 + pc, d.q);          // gamma columns g0 .. g1 - 1 first, then xi columns x0 .. x1 - 1
-    const int x0 = std::max(p0, d.q) - d.q, x1 = std::max(p0 + pc, d.q) - d.q;
-    for (int k = 0; k < nc; ++k) {
-        const bnr_dev &dk = cs[k]->d;
-        double *dst = buf + (size_t)k * nsamp;
-        if (g1 > g0)
-            hipLaunchKernelGGL(k_fetch_cols, dim3((g1 - g0 + 31) / 32, (nsamp + 31) / 32), block, 0, st, (const double *)dk.trace, dk.rowlen,
-                               dk.o_gamma + g0, g1 - g0, first_row - 1, nsamp, dst, S);
-        if (x1 > x0)
-            hipLaunchKernelGGL(k_fetch_cols, dim3((x1 - x0 + 31) / 32, (nsamp + 31) / 32), block, 0, st, (const double *)dk.trace, dk.rowlen,
-                               dk.o_xi + x0, x1 - x0, first_row - 1, nsamp, dst + (size_t)(g1 - g0) * (size_t)S, S);
-    }
-}
-
-// Summary(results) on the device (gibbs.jl:1214-1250): posterior mean and two order statistics of every gamma_e over rows
-// first_row .. first_row+nsamp-1 of every chain listed (pooled: S = nc nsamp draws, draw c nsamp + s = chain c's s-th window row), and the mean
-// of every xi_v.  3q + V doubles cross PCIe instead of the gamma traces.  The q + V parameter columns are staged (k_fetch_cols, one launch per
-// chain into its nsamp rows of the S-row column) in blocks of columns that keep the staging buffer near 1 GiB ("summary_block_cols" overrides);
-// k_summary works on one column per workgroup, so the block size cannot change a result.
-static int summary_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
-                        double *mean_gamma, double *lower, double *upper, double *prob_xi)
-{
-    bnr_chain *c = cs[0];
-    const bnr_dev &d = c->d;
-    const long long S = (long long)nc * nsamp;
-    if (k_lo < 1 || k_lo > S || k_hi < 1 || k_hi > S)
-        return fail(BNR_ERR_BAD_ARG, nc == 1 ? "order statistics must be between 1 and nsamp" : "order statistics must be between 1 and nchains * nsamp");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->x.stream;
-    int rc;
-    if ((rc = pooled_quiesce(cs, nc))) return rc;
-    const int np = d.q + d.V;
-    const size_t budget = (size_t)1 << 30;
-    long long blk = c->summary_block_cols > 0 ? c->summary_block_cols : (long long)(budget / ((size_t)S * sizeof(double)));
-    blk = std::min<long long>(std::max<long long>(blk, 1), np);
-    dev_tmp tmp;
-    double *buf = nullptr;
-    result_slab out;                                    // the mean, the lower and the upper statistic of the np = q + V parameters, gamma first
-    if ((rc = tmp.alloc(&buf, (size_t)blk * (size_t)S, st, false))) return rc;
-    if ((rc = out.alloc(tmp, 3, (size_t)np, st))) return rc;
-    for (int p0 = 0; p0 < np; p0 += (int)blk) {
-        const int pc = std::min<int>((int)blk, np - p0);
-        stage_cols(st, cs, nc, first_row, nsamp, p0, pc, buf);
-        hipLaunchKernelGGL(k_summary, dim3(pc), dim3(256), 0, st, (const double *)buf, (int)S, std::min(p0 + pc, d.q) - std::min(p0, d.q), k_lo, k_hi,
-                           out.col(0) + p0, out.col(1) + p0, out.col(2) + p0);
-    }
-    std::vector<double> host(3 * (size_t)np);           // (the callers' arrays hold q and V entries, not q + V)
-    if ((rc = out.fetch(st, "summary", "k_summary", {host.data(), host.data() + np, host.data() + 2 * (size_t)np}))) return rc;
-    memcpy(mean_gamma, host.data(), sizeof(double) * d.q);
-    memcpy(prob_xi, host.data() + d.q, sizeof(double) * d.V);
-    memcpy(lower, host.data() + np, sizeof(double) * d.q);
-    memcpy(upper, host.data() + 2 * (size_t)np, sizeof(double) * d.q);
-    return BNR_OK;
-}
-int bnr_chain_summary(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
-                      double *mean_gamma, double *lower, double *upper, double *prob_xi)
-{
-    if (!c || !mean_gamma || !lower || !upper || !prob_xi) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
-    return summary_call(&c, 1, first_row, nsamp, k_lo, k_hi, mean_gamma, lower, upper, prob_xi);
-}
-int bnr_chains_summary(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
-                       double *mean_gamma, double *lower, double *upper, double *prob_xi)
-{
-    if (!chains || !mean_gamma || !lower || !upper || !prob_xi) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
-    return summary_call(chains, nchains, first_row, nsamp, k_lo, k_hi, mean_gamma, lower, upper, prob_xi);
-}
-
 // Effective sample size (an addition: the reference only has split-Rhat).  Per-chain message: for both halves of the window
 // the mean, variance and the autocovariances at lags 0..max_lag-1 of gamma (q) and xi (V): 2 (2 + max_lag) (q + V) doubles.
 int bnr_chain_ess_stats(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t max_lag, double *stats)
@@ -2186,608 +1911,10 @@ int bnr_chain_ess_stats(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t 
     int rc;
     if ((rc = tmp.alloc(&buf, (size_t)np * nsamp, st, false))) return rc;
     if ((rc = out.alloc(tmp, 1, (size_t)2 * (2 + max_lag) * np, st))) return rc;
-    dim3 block(32, 8);
-    hipLaunchKernelGGL(k_fetch_cols, dim3((d.q + 31) / 32, (nsamp + 31) / 32), block, 0, st, (const double *)d.trace, d.rowlen, d.o_gamma, d.q, first_row - 1, nsamp, buf, (long long)nsamp);
-    hipLaunchKernelGGL(k_fetch_cols, dim3((d.V + 31) / 32, (nsamp + 31) / 32), block, 0, st, (const double *)d.trace, d.rowlen, d.o_xi, d.V, first_row - 1, nsamp, buf + (size_t)d.q * nsamp, (long long)nsamp);
-    hipLaunchKernelGGL(k_acov, dim3(np, 2), dim3(256), 0, st, (const double *)buf, nsamp, np, max_lag, out.d);
+    launch_fetch_cols(st, d.trace, d.rowlen, d.o_gamma, d.q, first_row - 1, nsamp, buf, nsamp);
+    launch_fetch_cols(st, d.trace, d.rowlen, d.o_xi, d.V, first_row - 1, nsamp, buf + (size_t)d.q * nsamp, nsamp);
+    launch_acov(st, buf, nsamp, np, max_lag, out.d);
     return out.fetch(st, "ess_stats", "k_acov", {stats});
-}
-
-// Rank-normalised convergence diagnostics (ABI 12; Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021, as `posterior` 1.x computes them) of every
-// parameter p in [gamma(q) | xi(V)] over the pooled window of the chains listed.  The columns are staged as in summary_call ("rank_block_cols"
-// overrides the block of about 1 GiB of draws); per block: k_rank on the split-chain draws (z, the two tail indicators, the median, the flag),
-// k_acov -- unchanged: a pooled column is nc windows of nsamp side by side, i.e. pc nc columns of nsamp -- on z, the indicators and x - med
-// (k_fold: the moments of x are taken about the median), k_fold and a second k_rank and k_acov for the folded z.  Each series' message of the block (2 (2 + L) pc nc doubles; L = 1 where only R-hat is
-// wanted) is fetched and finished here: bnr_ess_from_stats as it stands, and split-R-hat = sqrt(((h-1)/h W + B) / W).  Work nobody asked for
-// is not run.  Conventions: a parameter with a non-finite draw, or with all draws equal, is NaN in every output; rhat_tail is NaN where the
-// folded draws are all equal; ess_tail is NaN where either indicator's ESS is.
-namespace {
-struct split_msg {                                       // k_acov's message of one series of a block, per chain in bnr_ess_from_stats' layout
-    std::vector<double> raw, st, ess;
-    int nc = 0, pc = 0, L = 0, h = 0;
-    double mean(int c, int half, int p) const { return st[((size_t)c * 2 + half) * (size_t)(2 + L) * pc + p]; }
-    double var(int c, int half, int p) const { return st[((size_t)c * 2 + half) * (size_t)(2 + L) * pc + pc + p]; }
-    void moments(int p, double &W, double &dev2) const  // the mean of the 2 nc variances; the sum of the squared deviations of the 2 nc means
-    {
-        const int m = 2 * nc;
-        double mm = 0.0;
-        W = 0.0;
-        for (int c = 0; c < nc; ++c) for (int k = 0; k < 2; ++k) { mm += mean(c, k, p); W += var(c, k, p); }
-        mm /= m; W /= m;
-        dev2 = 0.0;
-        for (int c = 0; c < nc; ++c) for (int k = 0; k < 2; ++k) dev2 += (mean(c, k, p) - mm) * (mean(c, k, p) - mm);
-    }
-    double rhat(int p) const
-    {
-        double W, dev2;
-        moments(p, W, dev2);
-        return sqrt(((double)(h - 1) / h * W + dev2 / (2 * nc - 1)) / W);
-    }
-};
-}
-static int rank_diag_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t max_lag, double *rhat_bulk, double *rhat_tail,
-                          double *ess_bulk, double *ess_tail, double *ess_mean, double *mcse_mean)
-{
-    if (!rhat_bulk && !rhat_tail && !ess_bulk && !ess_tail && !ess_mean && !mcse_mean) return fail(BNR_ERR_BAD_ARG, "no output requested");
-    if (nsamp < 8) return fail(BNR_ERR_BAD_ARG, "need nsamp >= 8");
-    if (max_lag < 2 || max_lag > nsamp / 2) return fail(BNR_ERR_BAD_ARG, "need 2 <= max_lag <= nsamp/2");
-    bnr_chain *c = cs[0];
-    const bnr_dev &d = c->d;
-    const long long S = (long long)nc * nsamp;
-    const int h = nsamp / 2, np = d.q + d.V;
-    const long long n = (long long)nc * 2 * h;          // the split-chain draws that are ranked
-    const int k05 = (int)floor((double)(n - 1) * 0.05) + 1, k95 = (int)floor((double)(n - 1) * 0.95) + 1;
-    const bool want_bulk = rhat_bulk || ess_bulk, want_mean = ess_mean || mcse_mean, want_et = ess_tail != nullptr, want_rt = rhat_tail != nullptr;
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->x.stream;
-    int rc;
-    if ((rc = pooled_quiesce(cs, nc))) return rc;
-    const size_t budget = (size_t)1 << 30;
-    long long blk = c->rank_block_cols > 0 ? c->rank_block_cols : (long long)(budget / ((size_t)S * sizeof(double)));
-    blk = std::min<long long>(std::max<long long>(blk, 1), np);
-    const int Lmax = (ess_bulk || want_et || want_mean) ? max_lag : 1;
-    dev_tmp tmp;
-    double *X = nullptr, *Z = nullptr, *A = nullptr, *B = nullptr, *med = nullptr, *statd = nullptr;
-    int *flagd = nullptr;
-    rank_bufs rb;
-    const size_t cells = (size_t)blk * (size_t)S;
-    if ((rc = tmp.alloc(&X, cells, st, false))) return rc;
-    if ((want_bulk || want_rt) && (rc = tmp.alloc(&Z, cells, st, false))) return rc;
-    if ((want_et || want_rt || want_mean) && (rc = tmp.alloc(&A, cells, st, false))) return rc;
-    if (want_et && (rc = tmp.alloc(&B, cells, st, false))) return rc;
-    if ((rc = tmp.alloc(&rb.keyA, cells, st, false)) || (rc = tmp.alloc(&rb.keyB, cells, st, false)) || (rc = tmp.alloc(&rb.idxA, cells, st, false)) ||
-        (rc = tmp.alloc(&rb.idxB, cells, st, false)))
-        return rc;
-    if ((rc = tmp.alloc(&med, (size_t)blk, st)) || (rc = tmp.alloc(&flagd, 2 * (size_t)blk, st))) return rc;
-    if ((rc = tmp.alloc(&statd, (size_t)2 * (2 + Lmax) * (size_t)blk * nc, st, false))) return rc;
-    const double nanv = NAN;
-    std::vector<double> o_rb(np, nanv), o_rt(np, nanv), o_eb(np, nanv), o_et(np, nanv), o_em(np, nanv), o_mc(np, nanv);
-    std::vector<int> flags(2 * (size_t)blk);
-    split_msg sz, s05, s95, sx, sf;
-    for (int p0 = 0; p0 < np; p0 += (int)blk) {
-        const int pc = std::min<int>((int)blk, np - p0);
-        stage_cols(st, cs, nc, first_row, nsamp, p0, pc, X);
-        // one series: k_acov on the block's pc nc windows, its message fetched and laid out per chain; the ESS where lags were asked for
-        auto series = [&](const double *data, int L, split_msg &m) -> int {
-            const size_t cnt = (size_t)2 * (2 + L) * (size_t)pc * nc;
-            hipLaunchKernelGGL(k_acov, dim3(pc * nc, 2), dim3(256), 0, st, data, nsamp, pc * nc, L, statd);
-            m.raw.resize(cnt);
-            hipError_t e = hipMemcpyAsync(m.raw.data(), statd, sizeof(double) * cnt, hipMemcpyDeviceToHost, st);
-            if (e == hipSuccess) e = hipStreamSynchronize(st);
-            if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("rank_diag: ") + hipGetErrorString(e));
-            if (int r = check_launch("k_acov")) return r;
-            m.nc = nc; m.pc = pc; m.L = L; m.h = h;
-            m.st.resize(cnt);
-            for (int k = 0; k < 2; ++k) for (int j = 0; j < 2 + L; ++j) {
-                const double *src = m.raw.data() + ((size_t)k * (2 + L) + j) * (size_t)pc * nc;
-                for (int ch = 0; ch < nc; ++ch) {
-                    double *dst = m.st.data() + (((size_t)ch * 2 + k) * (2 + L) + j) * (size_t)pc;
-                    for (int p = 0; p < pc; ++p) dst[p] = src[(size_t)p * nc + ch];
-                }
-            }
-            m.ess.assign(pc, NAN);
-            if (L >= 2) return bnr_ess_from_stats(m.st.data(), nc, pc, nsamp, L, m.ess.data());
-            return BNR_OK;
-        };
-        launch_rank(st, pc, X, S, nsamp, nc, 0, rb, k05, k95, nullptr, want_bulk ? Z : nullptr, want_et ? A : nullptr, want_et ? B : nullptr, med, flagd);
-        if (want_bulk && (rc = series(Z, ess_bulk ? max_lag : 1, sz))) return rc;
-        if (want_et && ((rc = series(A, max_lag, s05)) || (rc = series(B, max_lag, s95)))) return rc;
-        if (want_mean) {                                     // on x - med: see k_fold
-            launch_fold(st, pc, X, S, med, 0, A);
-            if ((rc = series(A, max_lag, sx))) return rc;
-        }
-        if (want_rt) {
-            launch_fold(st, pc, X, S, med, 1, A);
-            launch_rank(st, pc, A, S, nsamp, nc, 0, rb, k05, k95, nullptr, Z, nullptr, nullptr, nullptr, flagd + blk);
-            if ((rc = series(Z, 1, sf))) return rc;
-        }
-        HIPCHK(hipMemcpyAsync(flags.data(), flagd, sizeof(int) * 2 * (size_t)blk, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if ((rc = check_launch("k_rank"))) return rc;
-        for (int p = 0; p < pc; ++p) {
-            if (flags[p]) continue;                          // a NaN, an Inf or all draws equal: NaN throughout
-            const int P = p0 + p;
-            if (want_bulk) { o_rb[P] = sz.rhat(p); o_eb[P] = sz.ess[p]; }
-            if (want_rt && !flags[(size_t)blk + p]) o_rt[P] = sf.rhat(p);
-            if (want_et) o_et[P] = (s05.ess[p] != s05.ess[p] || s95.ess[p] != s95.ess[p]) ? nanv : std::min(s05.ess[p], s95.ess[p]);
-            if (want_mean) {
-                double W, dev2;
-                sx.moments(p, W, dev2);
-                const double sd2 = ((double)(h - 1) * (W * 2 * nc) + (double)h * dev2) / (double)(n - 1);
-                o_em[P] = sx.ess[p];
-                o_mc[P] = sqrt(sd2) / sqrt(sx.ess[p]);
-            }
-        }
-    }
-    const struct { double *dst; const std::vector<double> *src; } outs[] = {{rhat_bulk, &o_rb}, {rhat_tail, &o_rt}, {ess_bulk, &o_eb},
-                                                                           {ess_tail, &o_et}, {ess_mean, &o_em}, {mcse_mean, &o_mc}};
-    for (const auto &o : outs) if (o.dst) memcpy(o.dst, o.src->data(), sizeof(double) * np);
-    return BNR_OK;
-}
-int bnr_chain_rank_diag(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t max_lag, double *rhat_bulk, double *rhat_tail, double *ess_bulk,
-                        double *ess_tail, double *ess_mean, double *mcse_mean)
-{
-    if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
-    return rank_diag_call(&c, 1, first_row, nsamp, max_lag, rhat_bulk, rhat_tail, ess_bulk, ess_tail, ess_mean, mcse_mean);
-}
-int bnr_chains_rank_diag(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t max_lag, double *rhat_bulk,
-                         double *rhat_tail, double *ess_bulk, double *ess_tail, double *ess_mean, double *mcse_mean)
-{
-    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
-    return rank_diag_call(chains, nchains, first_row, nsamp, max_lag, rhat_bulk, rhat_tail, ess_bulk, ess_tail, ess_mean, mcse_mean);
-}
-double bnr_host_ndtri(double p) { return bnr_ndtri(p); }
-
-// Average ranks and normal scores of every row of a caller's m x S matrix (host, row-major), each row on its own: the companion of
-// bnr_psis_loo / bnr_psis_weights, and k_rank's direct test.  On a stream of its own, the rows in blocks of about 256 MiB.
-int bnr_rank_normalize(int32_t device, int32_t m, int32_t S, const double *x, double *ranks, double *z)
-{
-    if (!x || (!ranks && !z)) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (m < 1 || S < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows and S >= 1 draws");
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
-    HIPCHK(hipSetDevice(device));
-    struct stream_guard {
-        hipStream_t s = nullptr;
-        ~stream_guard() { if (s) (void)hipStreamDestroy(s); }
-    } guard;
-    HIPCHK(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
-    hipStream_t st = guard.s;
-    const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, ((size_t)1 << 28) / ((size_t)S * sizeof(double))));
-    const size_t cells = (size_t)blk * (size_t)S;
-    int rc;
-    dev_tmp tmp;                                        // (freed before the stream goes)
-    double *Xd = nullptr, *Rd = nullptr, *Zd = nullptr;
-    int *flagd = nullptr;
-    rank_bufs rb;
-    if ((rc = tmp.alloc(&Xd, cells, st, false))) return rc;
-    if (ranks && (rc = tmp.alloc(&Rd, cells, st, false))) return rc;
-    if (z && (rc = tmp.alloc(&Zd, cells, st, false))) return rc;
-    if ((rc = tmp.alloc(&rb.keyA, cells, st, false)) || (rc = tmp.alloc(&rb.keyB, cells, st, false)) || (rc = tmp.alloc(&rb.idxA, cells, st, false)) ||
-        (rc = tmp.alloc(&rb.idxB, cells, st, false)) || (rc = tmp.alloc(&flagd, (size_t)blk, st)))
-        return rc;
-    for (int i0 = 0; i0 < m; i0 += blk) {
-        const int mr = std::min(blk, m - i0);
-        const size_t cnt = (size_t)mr * (size_t)S;
-        HIPCHK(hipMemcpyAsync(Xd, x + (size_t)i0 * S, sizeof(double) * cnt, hipMemcpyHostToDevice, st));
-        launch_rank(st, mr, Xd, S, S, 1, 1, rb, 1, 1, Rd, Zd, nullptr, nullptr, nullptr, flagd);
-        if (ranks) HIPCHK(hipMemcpyAsync(ranks + (size_t)i0 * S, Rd, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
-        if (z) HIPCHK(hipMemcpyAsync(z + (size_t)i0 * S, Zd, sizeof(double) * cnt, hipMemcpyDeviceToHost, st));
-    }
-    hipError_t e = hipStreamSynchronize(st);
-    if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("rank_normalize: ") + hipGetErrorString(e));
-    return check_launch("k_rank");
-}
-
-// Highest-density intervals, the median and the sign probabilities (ABI 13) of every parameter in [gamma(q) | xi(V)] over the pooled window of
-// the chains listed, or of every row of a caller's matrix: include/bnr_hip.h.  hdi_args: the checks that need no device, and the window length
-// w = floor(prob n) of every level (in double, as numpy does; at most n - 1).
-static int hdi_args(long long n, int32_t nprob, const double *probs, const double *lower, const double *upper, const double *median, const double *p_pos,
-                    const double *p_neg, bnr_hdi_levels &lv)
-{
-    if (!lower && !upper && !median && !p_pos && !p_neg) return fail(BNR_ERR_BAD_ARG, "no output requested");
-    if (!lower != !upper) return fail(BNR_ERR_BAD_ARG, "lower and upper come together");
-    if (nprob < 0 || nprob > 8) return fail(BNR_ERR_BAD_ARG, "need 0 <= nprob <= 8 levels");
-    if (nprob > 0 && !probs) return fail(BNR_ERR_BAD_ARG, "probs is NULL");
-    if (lower && nprob < 1) return fail(BNR_ERR_BAD_ARG, "lower and upper need nprob >= 1 levels");
-    for (int k = 0; k < 8; ++k) lv.w[k] = 0;
-    for (int k = 0; k < nprob; ++k) {
-        if (!(probs[k] > 0.0 && probs[k] < 1.0)) return fail(BNR_ERR_BAD_ARG, "every level must lie in (0, 1)");
-        lv.w[k] = (int)std::min<double>(floor(probs[k] * (double)n), (double)(n - 1));
-    }
-    return BNR_OK;
-}
-// the results of an hdi call on the device: nprob lower and nprob upper bounds, the median, p_pos and p_neg of np columns each
-struct hdi_slab {
-    double *d = nullptr;
-    size_t np = 0;
-    int nprob = 0;
-    int alloc(dev_tmp &tmp, int levels, size_t cols, hipStream_t st) { nprob = levels; np = cols; return tmp.alloc(&d, (size_t)(2 * nprob + 3) * np, st); }
-    double *lower() const { return d; }
-    double *upper() const { return d + (size_t)nprob * np; }
-    double *med() const { return d + (size_t)2 * nprob * np; }
-    double *p_pos() const { return med() + np; }
-    double *p_neg() const { return med() + 2 * np; }
-    int fetch(hipStream_t st, double *lo, double *up, double *median, double *pp, double *pn) const
-    {
-        std::vector<double> host((size_t)(2 * nprob + 3) * np);
-        hipError_t e = hipMemcpyAsync(host.data(), d, sizeof(double) * host.size(), hipMemcpyDeviceToHost, st);
-        if (e == hipSuccess) e = hipStreamSynchronize(st);
-        if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("hdi: ") + hipGetErrorString(e));
-        if (int rc = check_launch("k_hdi")) return rc;
-        const double *h = host.data();
-        if (lo) memcpy(lo, h, sizeof(double) * nprob * np);
-        if (up) memcpy(up, h + (size_t)nprob * np, sizeof(double) * nprob * np);
-        h += (size_t)2 * nprob * np;
-        if (median) memcpy(median, h, sizeof(double) * np);
-        if (pp) memcpy(pp, h + np, sizeof(double) * np);
-        if (pn) memcpy(pn, h + 2 * np, sizeof(double) * np);
-        return BNR_OK;
-    }
-};
-static int hdi_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t nprob, const double *probs, double *lower, double *upper,
-                    double *median, double *p_pos, double *p_neg)
-{
-    bnr_chain *c = cs[0];
-    const bnr_dev &d = c->d;
-    const long long S = (long long)nc * nsamp;
-    bnr_hdi_levels lv;
-    int rc;
-    if ((rc = hdi_args(S, nprob, probs, lower, upper, median, p_pos, p_neg, lv))) return rc;
-    const int np = d.q + d.V, levels = lower ? nprob : 0;
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->x.stream;
-    if ((rc = pooled_quiesce(cs, nc))) return rc;
-    const size_t budget = (size_t)1 << 30;
-    long long blk = c->rank_block_cols > 0 ? c->rank_block_cols : (long long)(budget / ((size_t)S * sizeof(double)));
-    blk = std::min<long long>(std::max<long long>(blk, 1), np);
-    dev_tmp tmp;
-    double *X = nullptr;
-    rank_bufs rb;
-    hdi_slab out;
-    const size_t cells = (size_t)blk * (size_t)S;
-    if ((rc = tmp.alloc(&X, cells, st, false)) || (rc = tmp.alloc(&rb.keyA, cells, st, false)) || (rc = tmp.alloc(&rb.keyB, cells, st, false))) return rc;
-    if ((rc = out.alloc(tmp, levels, (size_t)np, st))) return rc;
-    for (int p0 = 0; p0 < np; p0 += (int)blk) {
-        const int pc = std::min<int>((int)blk, np - p0);
-        stage_cols(st, cs, nc, first_row, nsamp, p0, pc, X);
-        launch_hdi(st, pc, X, S, (int)S, rb, levels, lv, levels ? out.lower() + p0 : nullptr, levels ? out.upper() + p0 : nullptr, np, out.med() + p0,
-                   out.p_pos() + p0, out.p_neg() + p0);
-    }
-    return out.fetch(st, lower, upper, median, p_pos, p_neg);
-}
-int bnr_chain_hdi(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t nprob, const double *probs, double *lower, double *upper, double *median,
-                  double *p_pos, double *p_neg)
-{
-    if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
-    return hdi_call(&c, 1, first_row, nsamp, nprob, probs, lower, upper, median, p_pos, p_neg);
-}
-int bnr_chains_hdi(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t nprob, const double *probs, double *lower,
-                   double *upper, double *median, double *p_pos, double *p_neg)
-{
-    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
-    return hdi_call(chains, nchains, first_row, nsamp, nprob, probs, lower, upper, median, p_pos, p_neg);
-}
-// k_hdi on every row of a caller's m x S matrix (host, row-major), each row on its own: k_hdi's direct test, as bnr_rank_normalize is k_rank's.
-// On a stream of its own, the rows in blocks of about 256 MiB.
-int bnr_hdi(int32_t device, int32_t m, int32_t S, const double *x, int32_t nprob, const double *probs, double *lower, double *upper, double *median,
-            double *p_pos, double *p_neg)
-{
-    if (!x) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (m < 1 || S < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows and S >= 1 draws");
-    bnr_hdi_levels lv;
-    int rc;
-    if ((rc = hdi_args(S, nprob, probs, lower, upper, median, p_pos, p_neg, lv))) return rc;
-    const int levels = lower ? nprob : 0;
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
-    HIPCHK(hipSetDevice(device));
-    struct stream_guard {
-        hipStream_t s = nullptr;
-        ~stream_guard() { if (s) (void)hipStreamDestroy(s); }
-    } guard;
-    HIPCHK(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
-    hipStream_t st = guard.s;
-    const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, ((size_t)1 << 28) / ((size_t)S * sizeof(double))));
-    const size_t cells = (size_t)blk * (size_t)S;
-    dev_tmp tmp;                                        // (freed before the stream goes)
-    double *Xd = nullptr;
-    rank_bufs rb;
-    hdi_slab out;
-    if ((rc = tmp.alloc(&Xd, cells, st, false)) || (rc = tmp.alloc(&rb.keyA, cells, st, false)) || (rc = tmp.alloc(&rb.keyB, cells, st, false))) return rc;
-    if ((rc = out.alloc(tmp, levels, (size_t)m, st))) return rc;
-    for (int i0 = 0; i0 < m; i0 += blk) {
-        const int mr = std::min(blk, m - i0);
-        HIPCHK(hipMemcpyAsync(Xd, x + (size_t)i0 * S, sizeof(double) * (size_t)mr * (size_t)S, hipMemcpyHostToDevice, st));
-        launch_hdi(st, mr, Xd, S, S, rb, levels, lv, levels ? out.lower() + i0 : nullptr, levels ? out.upper() + i0 : nullptr, m, out.med() + i0,
-                   out.p_pos() + i0, out.p_neg() + i0);
-    }
-    return out.fetch(st, lower, upper, median, p_pos, p_neg);
-}
-
-// Posterior of the mean response mu + x . gamma of m new rows over rows first_row .. first_row+nsamp-1 of the chains listed (an addition to the
-// reference): X_pred goes to the device in its own element type and is converted there (k_x_convert with m rows), then predict_rows.
-// pred_lower / pred_upper / pit (host, nullable): the extras of the pooled entry points.
-static int predict_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t m, const x_source &xs, const double *y, int32_t k_lo,
-                        int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic, uint64_t pred_seed, double *pred_lower,
-                        double *pred_upper, double *pit)
-{
-    bnr_chain *c = cs[0];
-    const bnr_dev &d = c->d;
-    const long long S = (long long)nc * nsamp;
-    if (k_lo < 1 || k_lo > S || k_hi < 1 || k_hi > S)
-        return fail(BNR_ERR_BAD_ARG, nc == 1 ? "order statistics must be between 1 and nsamp" : "order statistics must be between 1 and nchains * nsamp");
-    if (m < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows");
-    if (xs.dtype < BNR_F64 || xs.dtype > BNR_F32) return fail(BNR_ERR_BAD_ARG, "unknown element type of X");
-    if (xs.mats) for (int i = 0; i < m; ++i) if (!xs.mats[i]) return fail(BNR_ERR_BAD_ARG, "NULL adjacency matrix");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->x.stream;
-    const int m_pad = round_up(m, 32), q16 = round_up(d.q, 16);
-    dev_tmp tmp;
-    double *Xd = nullptr, *yd = nullptr;
-    result_slab out;
-    int rc;
-    if ((rc = pooled_quiesce(cs, nc))) return rc;
-    if ((rc = tmp.alloc(&Xd, (size_t)m_pad * q16, st))) return rc;             // zero rows m .. m_pad - 1 and columns q .. q16 - 1 (k_predict)
-    if ((rc = out.alloc(tmp, pred_lower || pit ? 8 : 5, (size_t)m, st))) return rc;
-    const size_t es = dtype_size(xs.dtype);
-    if (!xs.mats && xs.dtype == BNR_F64) {
-        HIPCHK(hipMemcpy2DAsync(Xd, (size_t)m_pad * sizeof(double), xs.X, (size_t)m * sizeof(double), (size_t)m * sizeof(double), d.q, hipMemcpyHostToDevice, st));
-    } else {
-        char *raw = nullptr;
-        const size_t count = xs.mats ? (size_t)m * d.V * d.V : (size_t)m * d.q;
-        if ((rc = tmp.alloc(&raw, count * es, st))) return rc;
-        if (xs.mats) {
-            for (int i = 0; i < m; ++i) HIPCHK(hipMemcpyAsync(raw + (size_t)i * d.V * d.V * es, xs.mats[i], (size_t)d.V * d.V * es, hipMemcpyHostToDevice, st));
-        } else HIPCHK(hipMemcpyAsync(raw, xs.X, count * es, hipMemcpyHostToDevice, st));
-        launch_x_convert(xs.dtype, raw, xs.mats != nullptr, m, d, m_pad, Xd, nullptr, nullptr, st);
-    }
-    if (y) {
-        if ((rc = tmp.alloc(&yd, (size_t)m, st))) return rc;
-        HIPCHK(hipMemcpyAsync(yd, y, sizeof(double) * m, hipMemcpyHostToDevice, st));
-    }
-    pred_stages sg;
-    sg.k_lo = k_lo; sg.k_hi = k_hi;
-    sg.mean = out.col(0); sg.lower = out.col(1); sg.upper = out.col(2);
-    if (y) { sg.lpd = out.col(3); sg.pwaic = out.col(4); }
-    if (pred_lower) { sg.seed = pred_seed; sg.pred_lower = out.col(5); sg.pred_upper = out.col(6); }
-    if (pit) sg.pit = out.col(7);
-    if ((rc = predict_rows(cs, nc, first_row, nsamp, m, Xd, m_pad, yd, sg, tmp))) return rc;
-    return out.fetch(st, "predict", "k_predict", {mean, lower, upper, y ? lpd : nullptr, y ? pwaic : nullptr, pred_lower, pred_lower ? pred_upper : nullptr, pit});
-}
-// the checks of the single-chain entry points, in their order
-static int predict_one(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const x_source &xs, const double *y, int32_t k_lo, int32_t k_hi,
-                       double *mean, double *lower, double *upper, double *lpd, double *pwaic)
-{
-    if (!c || !mean || !lower || !upper || (!xs.X && !xs.mats) || (y && (!lpd || !pwaic))) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
-    return predict_call(&c, 1, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic, 0, nullptr, nullptr, nullptr);
-}
-// ... and of the pooled ones: pred_lower and pred_upper come together; lpd / pwaic and pit need y
-static int predict_pooled(bnr_chain *const *cs, int32_t nc, int32_t first_row, int32_t nsamp, int32_t m, const x_source &xs, const double *y, int32_t k_lo,
-                          int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic, uint64_t pred_seed, double *pred_lower,
-                          double *pred_upper, double *pit)
-{
-    if (!cs || !mean || !lower || !upper || (!xs.X && !xs.mats) || (y && (!lpd || !pwaic)) || (!pred_lower != !pred_upper))
-        return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (pit && !y) return fail(BNR_ERR_BAD_ARG, "pit needs the observed responses y");
-    if (int rc = pooled_check(cs, nc, first_row, nsamp)) return rc;
-    return predict_call(cs, nc, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic, pred_seed, pred_lower, pred_upper, pit);
-}
-int bnr_chain_predict(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const void *X, int32_t x_dtype, const double *y,
-                      int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic)
-{
-    x_source xs;
-    xs.X = X; xs.dtype = x_dtype;
-    return predict_one(c, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic);
-}
-int bnr_chain_predict_from_matrices(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const void *const *A, int32_t x_dtype,
-                                    const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic)
-{
-    x_source xs;
-    xs.mats = A; xs.dtype = x_dtype;
-    return predict_one(c, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic);
-}
-int bnr_chains_predict(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t m, const void *X, int32_t x_dtype,
-                       const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic,
-                       uint64_t pred_seed, double *pred_lower, double *pred_upper, double *pit)
-{
-    x_source xs;
-    xs.X = X; xs.dtype = x_dtype;
-    return predict_pooled(chains, nchains, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic, pred_seed, pred_lower, pred_upper, pit);
-}
-int bnr_chains_predict_from_matrices(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t m, const void *const *A,
-                                     int32_t x_dtype, const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper,
-                                     double *lpd, double *pwaic, uint64_t pred_seed, double *pred_lower, double *pred_upper, double *pit)
-{
-    x_source xs;
-    xs.mats = A; xs.dtype = x_dtype;
-    return predict_pooled(chains, nchains, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic, pred_seed, pred_lower, pred_upper, pit);
-}
-// the element-by-element host mirror of k_pred_noise's draws: out[(i - i0) ns + (s - s0)] = bnr_normal(seed, s, SITE_PRED, i, 0)
-void bnr_host_pred_noise(uint64_t seed, uint32_t s0, uint32_t ns, uint32_t i0, uint32_t ni, double *out)
-{
-    if (!out) return;
-    for (uint32_t i = 0; i < ni; ++i)
-        for (uint32_t s = 0; s < ns; ++s) out[(size_t)i * ns + s] = bnr_normal(seed, s0 + s, SITE_PRED, i0 + i, 0u);
-}
-// The calls on the chains' own training rows: X (n_pad x q_pad, zero padded) and y are on the device already.  analysis_call holds what they
-// share: the device, the quiesce, the result slab of k columns of n doubles and -- with_tails: for PSIS -- the tail lengths on the device
-struct analysis_call {
-    dev_tmp tmp;
-    result_slab out;
-    pred_stages sg;
-    hipStream_t st = nullptr;
-    int begin(bnr_chain *const *cs, int nc, int k, const std::vector<int> *tails, int lds)
-    {
-        bnr_chain *c = cs[0];
-        HIPCHK(hipSetDevice(c->device));
-        st = c->x.stream;
-        int rc;
-        if ((rc = pooled_quiesce(cs, nc))) return rc;
-        if ((rc = out.alloc(tmp, k, (size_t)c->d.n, st))) return rc;
-        if (tails) {
-            int *tl = nullptr;
-            if ((rc = tmp.alloc(&tl, (size_t)c->d.n, st))) return rc;
-            HIPCHK(hipMemcpyAsync(tl, tails->data(), sizeof(int) * c->d.n, hipMemcpyHostToDevice, st));
-            sg.tail_len = tl; sg.lds = lds;
-            sg.psis_lpd = out.col(0); sg.elpd = out.col(1); sg.khat = out.col(2);
-        }
-        return BNR_OK;
-    }
-    int run(bnr_chain *const *cs, int nc, int first_row, int nsamp)
-    {
-        const bnr_dev &d = cs[0]->d;
-        return predict_rows(cs, nc, first_row, nsamp, d.n, d.X, d.n_pad, d.y, sg, tmp);
-    }
-};
-// pointwise lpd and WAIC penalty (and, pooled entry point only, the PIT)
-static int loglik_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic, double *pit)
-{
-    analysis_call a;
-    int rc;
-    if ((rc = a.begin(cs, nc, pit ? 3 : 2, nullptr, 0))) return rc;
-    a.sg.lpd = a.out.col(0); a.sg.pwaic = a.out.col(1);
-    if (pit) a.sg.pit = a.out.col(2);
-    if ((rc = a.run(cs, nc, first_row, nsamp))) return rc;
-    return a.out.fetch(a.st, "loglik_stats", "k_pred_loglik", {lpd, pwaic, pit});
-}
-int bnr_chain_loglik_stats(bnr_chain *c, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic)
-{
-    if (!c || !lpd || !pwaic) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
-    return loglik_call(&c, 1, first_row, nsamp, lpd, pwaic, nullptr);
-}
-int bnr_chains_loglik_stats(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic, double *pit)
-{
-    if (!chains || !lpd || !pwaic) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
-    return loglik_call(chains, nchains, first_row, nsamp, lpd, pwaic, pit);
-}
-
-// loo 2.x's tail length M = ceil(min(0.2 S, 3 sqrt(S / r_eff))) of every row (r_eff NULL: 1), checked against BNR_PSIS_MAX_TAIL, and the
-// dynamic LDS of the longest tail that is smoothed (M >= 5), P = its length rounded up to a power of two: 16 bytes per entry for k_psis
-// (entry_bytes' default), 12 for k_psis_w; 8 KiB at least (the histogram of the radix select)
-static int psis_tail_lengths(int m, int nsamp, const double *r_eff, std::vector<int> &M, int &lds, int entry_bytes = 16)
-{
-    M.assign(m, 0);
-    int pmax = 0;
-    for (int i = 0; i < m; ++i) {
-        const double r = r_eff ? r_eff[i] : 1.0;
-        if (!(r > 0.0) || !std::isfinite(r)) return fail(BNR_ERR_BAD_ARG, "r_eff must be positive and finite");
-        const double t = std::ceil(std::min(0.2 * nsamp, 3.0 * std::sqrt(nsamp / r)));
-        if (t > BNR_PSIS_MAX_TAIL)
-            return fail(BNR_ERR_BAD_ARG, "PSIS tail length " + std::to_string((long long)t) + " of row " + std::to_string(i + 1) + " exceeds the supported " +
-                                             std::to_string(BNR_PSIS_MAX_TAIL) + " (raise r_eff or shorten the window)");
-        M[i] = (int)t;
-        if (M[i] >= 5) {
-            int p = 8;
-            while (p < M[i]) p <<= 1;
-            pmax = std::max(pmax, p);
-        }
-    }
-    lds = std::max(8192, entry_bytes * pmax);
-    return BNR_OK;
-}
-// PSIS-LOO of the chains' own training rows over rows first_row .. first_row+nsamp-1 of every chain listed (k_predict, then k_psis on every block
-// of rows); the tail length comes from the pooled draw count
-static int loo_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo, double *pareto_k)
-{
-    std::vector<int> M;
-    int lds = 0, rc;
-    if ((rc = psis_tail_lengths(cs[0]->d.n, nc * nsamp, r_eff, M, lds))) return rc;
-    analysis_call a;
-    if ((rc = a.begin(cs, nc, 3, &M, lds))) return rc;
-    if ((rc = a.run(cs, nc, first_row, nsamp))) return rc;
-    return a.out.fetch(a.st, "loo", "k_psis", {lpd, elpd_loo, pareto_k});
-}
-int bnr_chain_loo(bnr_chain *c, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo, double *pareto_k)
-{
-    if (!c || !elpd_loo || !pareto_k) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
-    return loo_call(&c, 1, first_row, nsamp, r_eff, lpd, elpd_loo, pareto_k);
-}
-int bnr_chains_loo(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo,
-                   double *pareto_k)
-{
-    if (!chains || !elpd_loo || !pareto_k) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
-    return loo_call(chains, nchains, first_row, nsamp, r_eff, lpd, elpd_loo, pareto_k);
-}
-
-// LOO predictive checks (ABI 11) of the chains' own training rows over the pooled window: k_predict, then k_psis_w (the PSIS weights of the block),
-// k_loo_moments and k_loo_quantile on every block of rows.  Every output is nullable; lpd, elpd_loo and pareto_k always come from k_psis_w.
-static int loo_predict_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, const double *r_eff, double p_lo, double p_hi, double *lpd,
-                            double *elpd_loo, double *pareto_k, double *loo_mean, double *loo_sd, double *loo_pit, double *loo_lower, double *loo_upper)
-{
-    const bool bounds = loo_lower || loo_upper, moments = loo_mean || loo_sd || loo_pit;
-    double cc = 0.0;
-    if (bounds) {
-        if (!(p_lo > 0.0) || !(p_hi < 1.0) || !(p_lo < p_hi)) return fail(BNR_ERR_BAD_ARG, "need 0 < p_lo < p_hi < 1");
-        const double pm = 0.5 * std::min(p_lo, 1.0 - p_hi);
-        for (cc = 1.0; !(0.5 * std::erfc(cc * 0.70710678118654752440) < pm) && cc < 40.0; cc += 0.5) { }
-    }
-    std::vector<int> M;
-    int lds = 0, rc;
-    if ((rc = psis_tail_lengths(cs[0]->d.n, nc * nsamp, r_eff, M, lds, BNR_PSISW_ENTRY_BYTES))) return rc;
-    HIPCHK(hipSetDevice(cs[0]->device));
-    if ((rc = loow_lds_attributes())) return rc;
-    analysis_call a;
-    if ((rc = a.begin(cs, nc, 8, &M, lds))) return rc;
-    pred_stages &sg = a.sg;
-    sg.keep_weights = true;
-    if (moments) { sg.loo_mean = a.out.col(3); sg.loo_sd = a.out.col(4); sg.loo_pit = a.out.col(5); }
-    if (loo_lower) sg.loo_lower = a.out.col(6);
-    if (loo_upper) sg.loo_upper = a.out.col(7);
-    sg.p_lo = p_lo; sg.p_hi = p_hi; sg.c = cc;
-    if ((rc = a.run(cs, nc, first_row, nsamp))) return rc;
-    return a.out.fetch(a.st, "loo_predict", "k_psis_w", {lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper});
-}
-int bnr_chain_loo_predict(bnr_chain *c, int32_t first_row, int32_t nsamp, const double *r_eff, double p_lo, double p_hi, double *lpd, double *elpd_loo,
-                          double *pareto_k, double *loo_mean, double *loo_sd, double *loo_pit, double *loo_lower, double *loo_upper)
-{
-    if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
-    return loo_predict_call(&c, 1, first_row, nsamp, r_eff, p_lo, p_hi, lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper);
-}
-int bnr_chains_loo_predict(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, const double *r_eff, double p_lo, double p_hi,
-                           double *lpd, double *elpd_loo, double *pareto_k, double *loo_mean, double *loo_sd, double *loo_pit, double *loo_lower,
-                           double *loo_upper)
-{
-    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
-    return loo_predict_call(chains, nchains, first_row, nsamp, r_eff, p_lo, p_hi, lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper);
-}
-
-// PSIS on a caller's m x nsamp log-likelihood matrix (host, row-major): bnr_psis_loo (k_psis) and its companion bnr_psis_weights, which also
-// returns the weights (k_psis_w: log_weights != NULL).  The shared front: the checks in their order, the tail lengths, the device
-static int psis_call(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *log_weights, double *lpd, double *elpd_loo,
-                     double *pareto_k)
-{
-    if (m < 1 || nsamp < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows and nsamp >= 1 draws");
-    std::vector<int> M;
-    int lds = 0, rc, ndev = 0;
-    if ((rc = psis_tail_lengths(m, nsamp, r_eff, M, lds, log_weights ? BNR_PSISW_ENTRY_BYTES : 16))) return rc;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
-    HIPCHK(hipSetDevice(device));
-    if ((rc = ensure_lds_attributes(device))) return rc;
-    if (log_weights && (rc = loow_lds_attributes())) return rc;
-    return psis_matrix(m, nsamp, loglik, M, lds, log_weights, lpd, elpd_loo, pareto_k);
-}
-int bnr_psis_loo(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *elpd_loo, double *pareto_k, double *lpd)
-{
-    if (!loglik || !elpd_loo || !pareto_k) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    return psis_call(device, m, nsamp, loglik, r_eff, nullptr, lpd, elpd_loo, pareto_k);
-}
-int bnr_psis_weights(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *log_weights, double *elpd_loo,
-                     double *pareto_k)
-{
-    if (!loglik || !log_weights) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    return psis_call(device, m, nsamp, loglik, r_eff, log_weights, nullptr, elpd_loo, pareto_k);
 }
 
 // Bulk effective sample size over all chains from the gathered messages (the estimator of Vehtari et al. 2021 as in
@@ -3035,159 +2162,11 @@ static int late_kernels_lds_attributes(int bytes)
     // k_tail outside a sweep (hooks, a loaded row): u (up to BNR_TAIL_U_LDS doubles) and the R x R work matrices of update_M! side by side
     const void *tails[] = {(const void *)&k_tail<bnr_one>, (const void *)&k_tail<bnr_many>, (const void *)&k_tail<bnr_one, false>, (const void *)&k_tail<bnr_many, false>};
     for (const void *f : tails) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-    // k_psis: the sorted tail, 16 bytes per entry for up to BNR_PSIS_MAX_TAIL entries
-    const void *psis[] = {(const void *)&k_psis<0>, (const void *)&k_psis<1>};
-    for (const void *f : psis) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 16 * BNR_PSIS_MAX_TAIL));
-    return BNR_OK;                                       // (k_pred_noise / k_pred_pit use no dynamic LDS: first referenced in predict_rows below, behind k_psis)
+    return BNR_OK;
 }
 static void launch_late_xpass_group2(bnr_exec &x, int s)
 { hipLaunchKernelGGL(HIP_KERNEL_NAME(k_xpass_group2<0>), dim3(x.shape->nblk_x * ((x.shape->n_pad + 255) / 256)), dim3(256), 16 * x.shape->chunk_x * sizeof(double), x.stream, bnr_many{x.cds}, s, x.nb); }
 static void launch_late_backproj64(bnr_exec &x, int s, int flags, size_t lds64)
 { BNR_LAUNCH(k_backproj64, dim3(round_up((x.shape->nblk_bp + 1) / 2, 8) * x.nb), dim3(256), lds64, x.stream, x, s, flags, x.nb); }
 
-// The device work of the prediction, log-likelihood and LOO calls, eagerly on the first chain's stream: the m rows of X (device, column-major,
-// leading dimension ldx, zero in columns q .. q16 - 1 and readable for whole 32-row tiles) in blocks of rows whose E buffer (rows x S doubles,
-// S = nc nsamp pooled draws: chain c's window in the columns c nsamp ..) stays near 1 GiB; per block one k_predict per chain, then the stages
-// of sg that are wanted, in this order: k_summary (mean, k_lo-th / k_hi-th smallest of every E column), k_pred_loglik, the LOO predictive
-// checks (k_psis_w and what reads its weights), k_psis, k_pred_pit, and last what overwrites E: k_pred_noise + a second k_summary (no call asks
-// for that and k_psis, which overwrites E as well).  Blocks start at multiples of 32 rows, so an output's MFMA tile position and K order -- and
-// with them every result, bit for bit -- do not depend on the block size; the noise is keyed by the row's index in the call.  With one chain
-// and no extras: the launches of the single-chain entry points, unchanged.
-static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, int m, const double *Xd, int ldx, const double *yd, const pred_stages &sg,
-                        dev_tmp &tmp)
-{
-    bnr_chain *c = cs[0];
-    const bnr_dev &d = c->d;
-    hipStream_t st = c->x.stream;
-    const long long S = (long long)nc * nsamp;
-    const bool loow = sg.tail_len && sg.keep_weights, psis = sg.tail_len && !sg.keep_weights;
-    const size_t budget = loow ? (size_t)1 << 29 : (size_t)1 << 30;        // (half the rows with the log weights beside E: E + LW stay near 1 GiB)
-    long long blk = c->predict_block_rows > 0 ? c->predict_block_rows : (long long)(budget / ((size_t)S * sizeof(double))) / 32 * 32;
-    blk = std::min<long long>(round_up((int)std::max<long long>(blk, 1), 32), round_up(m, 32));
-    double *E = nullptr, *tau2 = nullptr, *pmean = nullptr, *LW = nullptr, *isd = nullptr;
-    int rc;
-    if ((rc = tmp.alloc(&E, (size_t)blk * (size_t)S, st))) return rc;
-    if (loow && (rc = tmp.alloc(&LW, (size_t)blk * (size_t)S, st))) return rc;
-    if (yd || sg.pit || sg.pred_lower) {
-        if ((rc = tmp.alloc(&tau2, (size_t)S, st))) return rc;
-        for (int k = 0; k < nc; ++k)
-            hipLaunchKernelGGL(k_fetch_cols, dim3(1, (nsamp + 31) / 32), dim3(32, 8), 0, st, (const double *)cs[k]->d.trace, cs[k]->d.rowlen, (int)ROW_TAU2, 1,
-                               first_row - 1, nsamp, tau2 + (size_t)k * nsamp, S);
-    }
-    if (sg.pred_lower && (rc = tmp.alloc(&pmean, (size_t)m, st))) return rc;      // (k_summary also writes the mean of y~: not returned)
-    if (loow && (sg.loo_lower || sg.loo_upper)) {
-        if ((rc = tmp.alloc(&isd, (size_t)S, st))) return rc;
-        launch_loow_inv_sd(st, tau2, (int)S, isd);
-    }
-    const int q16 = round_up(d.q, 16);
-    for (int i0 = 0; i0 < m; i0 += (int)blk) {
-        const int mr = std::min<int>((int)blk, m - i0);
-        for (int k = 0; k < nc; ++k) {
-            const bnr_dev &dk = cs[k]->d;
-            if (mr > 16)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<2>), dim3((nsamp + 127) / 128, (mr + 31) / 32), dim3(256), 0, st, Xd + i0, ldx, q16,
-                                   (const double *)dk.trace, dk.rowlen, dk.o_gamma, first_row - 1, nsamp, mr, E + (size_t)k * nsamp, S);
-            else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<1>), dim3((nsamp + 127) / 128, 1), dim3(256), 0, st, Xd + i0, ldx, q16,
-                                   (const double *)dk.trace, dk.rowlen, dk.o_gamma, first_row - 1, nsamp, mr, E + (size_t)k * nsamp, S);
-        }
-        if (sg.mean)
-            hipLaunchKernelGGL(k_summary, dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, mr, sg.k_lo, sg.k_hi, sg.mean + i0, sg.lower + i0, sg.upper + i0);
-        if (yd && sg.lpd)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pred_loglik<0>), dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, yd + i0, (const double *)tau2,
-                               sg.lpd + i0, sg.pwaic + i0);
-        if (loow)                                      // the LOO predictive checks read E: before anything that overwrites it
-            launch_loow_block(st, sg, E, LW, (int)S, mr, i0, yd, tau2, isd);
-        if (psis)                                      // last: k_psis turns the block's E into l in place
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis<1>), dim3(mr), dim3(256), sg.lds, st, E, (int)S, yd + i0, (const double *)tau2, sg.tail_len + i0,
-                               sg.psis_lpd + i0, sg.elpd + i0, sg.khat + i0);
-        if (sg.pit)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pred_pit<0>), dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, yd + i0, (const double *)tau2, sg.pit + i0);
-        if (sg.pred_lower) {                           // last: the block's E becomes draws of new observations in place
-            const int gx = (int)((S + 255) / 256), gy = std::max(1, std::min(mr, 8192 / gx));
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_pred_noise<0>), dim3(gx, gy), dim3(256), 0, st, E, S, (int)S, mr, i0, (const double *)tau2, sg.seed);
-            hipLaunchKernelGGL(k_summary, dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, mr, sg.k_lo, sg.k_hi, pmean + i0, sg.pred_lower + i0, sg.pred_upper + i0);
-        }
-    }
-    return check_launch("k_predict");
-}
-
-// ----------------------------------------------------------------------------------------- every reference to the kernels of the LOO predictive checks (ABI 11)
-// k_rank / k_fold (ABI 12): first referenced here, behind the kernels of the sweep and the late kernels above, in front of k_hdi and the kernels of ABI 11
-static void launch_rank(hipStream_t st, int cols, const double *buf, long long ld, int nsamp, int nch, int all, const rank_bufs &rb, int k05, int k95,
-                        double *ranks, double *z, double *ind05, double *ind95, double *med, int *flag)
-{
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rank<0>), dim3(cols), dim3(256), 0, st, buf, ld, nsamp, nch, all, rb.keyA, rb.keyB, rb.idxA, rb.idxB, k05, k95, ranks, z,
-                       ind05, ind95, med, flag);
-}
-static void launch_fold(hipStream_t st, int cols, const double *buf, long long ld, const double *med, int absolute, double *out)
-{
-    const int chunks = (int)((ld + 255) / 256);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_fold<0>), dim3((unsigned)chunks * (unsigned)cols), dim3(256), 0, st, buf, ld, chunks, med, absolute, out);
-}
-// k_hdi (ABI 13): first referenced here, behind k_rank / k_fold and in front of the kernels of ABI 11
-static void launch_hdi(hipStream_t st, int cols, const double *buf, long long ld, int n, const rank_bufs &rb, int nprob, const bnr_hdi_levels &lv, double *lower,
-                       double *upper, long long lstride, double *med, double *p_pos, double *p_neg)
-{
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_hdi<0>), dim3(cols), dim3(256), 0, st, buf, ld, n, rb.keyA, rb.keyB, nprob, lv, lower, upper, lstride, med, p_pos, p_neg);
-}
-// k_psis_w: the sorted tail, 12 bytes per entry for up to BNR_PSIS_MAX_TAIL entries (on the current device; cheap enough for once per call)
-static int loow_lds_attributes()
-{
-    const void *fns[] = {(const void *)&k_psis_w<0>, (const void *)&k_psis_w<1>};
-    for (const void *f : fns) HIPCHK(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, BNR_PSISW_ENTRY_BYTES * BNR_PSIS_MAX_TAIL));
-    return BNR_OK;
-}
-static void launch_loow_inv_sd(hipStream_t st, const double *tau2, int S, double *isd)
-{ hipLaunchKernelGGL(HIP_KERNEL_NAME(k_inv_sd<0>), dim3((S + 255) / 256), dim3(256), 0, st, tau2, S, isd); }
-// a block of mr rows starting at row i0 of the call: the weights of the block into LW, then what reads them
-static void launch_loow_block(hipStream_t st, const pred_stages &sg, const double *E, double *LW, int S, int mr, int i0, const double *yd, const double *tau2,
-                              const double *isd)
-{
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis_w<1>), dim3(mr), dim3(256), sg.lds, st, E, S, yd + i0, tau2, sg.tail_len + i0, LW, sg.psis_lpd + i0, sg.elpd + i0,
-                       sg.khat + i0);
-    if (sg.loo_mean)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_loo_moments<0>), dim3(mr), dim3(256), 0, st, E, (const double *)LW, S, yd + i0, tau2, sg.loo_mean + i0, sg.loo_sd + i0,
-                           sg.loo_pit + i0);
-    if (sg.loo_lower || sg.loo_upper)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_loo_quantile<0>), dim3(mr, 2), dim3(256), 0, st, E, (const double *)LW, S, tau2, isd, sg.c, sg.p_lo, sg.p_hi,
-                           sg.loo_lower ? sg.loo_lower + i0 : nullptr, sg.loo_upper ? sg.loo_upper + i0 : nullptr);
-}
-// The device work of bnr_psis_loo and bnr_psis_weights on a stream of its own: the rows of the caller's matrix in blocks, k_psis<0> on every block
-// of about 1 GiB; with log_weights k_psis_w<0> on every block of about 512 MiB (l and the weights side by side), the block's weights copied back
-// behind it (and no lpd)
-static int psis_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *log_weights, double *lpd, double *elpd,
-                       double *khat)
-{
-    struct stream_guard {
-        hipStream_t s = nullptr;
-        ~stream_guard() { if (s) (void)hipStreamDestroy(s); }
-    } guard;
-    HIPCHK(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
-    hipStream_t st = guard.s;
-    const size_t budget = log_weights ? (size_t)1 << 29 : (size_t)1 << 30;
-    const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, budget / ((size_t)nsamp * sizeof(double))));
-    int rc;
-    dev_tmp tmp;                                        // (freed before the stream goes)
-    double *Ld = nullptr, *Wd = nullptr;
-    int *tl = nullptr;
-    result_slab out;
-    if ((rc = tmp.alloc(&Ld, (size_t)blk * nsamp, st))) return rc;
-    if (log_weights && (rc = tmp.alloc(&Wd, (size_t)blk * nsamp, st))) return rc;
-    if ((rc = out.alloc(tmp, 3, (size_t)m, st))) return rc;
-    if ((rc = tmp.alloc(&tl, (size_t)m, st))) return rc;
-    HIPCHK(hipMemcpyAsync(tl, tail_len.data(), sizeof(int) * m, hipMemcpyHostToDevice, st));
-    for (int i0 = 0; i0 < m; i0 += blk) {
-        const int mr = std::min(blk, m - i0);
-        HIPCHK(hipMemcpyAsync(Ld, loglik + (size_t)i0 * nsamp, sizeof(double) * (size_t)mr * nsamp, hipMemcpyHostToDevice, st));
-        if (log_weights) {
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis_w<0>), dim3(mr), dim3(256), lds, st, (const double *)Ld, nsamp, (const double *)nullptr,
-                               (const double *)nullptr, (const int *)tl + i0, Wd, (double *)nullptr, out.col(1) + i0, out.col(2) + i0);
-            HIPCHK(hipMemcpyAsync(log_weights + (size_t)i0 * nsamp, Wd, sizeof(double) * (size_t)mr * nsamp, hipMemcpyDeviceToHost, st));
-        } else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(k_psis<0>), dim3(mr), dim3(256), lds, st, Ld, nsamp, (const double *)nullptr, (const double *)nullptr,
-                               (const int *)tl + i0, out.col(0) + i0, out.col(1) + i0, out.col(2) + i0);
-    }
-    return out.fetch(st, log_weights ? "psis_weights" : "psis_loo", log_weights ? "k_psis_w" : "k_psis", {lpd, elpd, khat});
-}
 }

@@ -4,12 +4,12 @@ library's argument checks that precede its first HIP call, Fit's refusals before
 import ctypes as C
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import bnr_amd
+import code_objects as co
 import hdi_cases as hc
 import hdi_ref as hr
 import rank_diag_cases as rc
@@ -198,27 +198,13 @@ def test_fit_refuses_an_edge_selection_it_cannot_compute_before_sampling(monkeyp
     assert not made                                                          # no chain was created
 
 
-def test_k_hdi_sits_behind_k_rank_and_in_front_of_the_abi_11_kernels(tmp_path):
-    """k_hdi is referenced only from the end of bnr_hip.hip, behind k_rank / k_fold: in the gfx950 code object it comes behind them (and so
-    behind every kernel of the sweep) and in front of the kernels of ABI 11, which stay last"""
-    llvm = "/opt/rocm/lib/llvm/bin"
-    lib = os.path.join(ROOT, "bayesiannetworkregression.jl_amd", "libbnr_hip.so")
-    assert os.path.exists(lib), "libbnr_hip.so has not been built"
-    if not os.path.exists(os.path.join(llvm, "clang-offload-bundler")):
+def test_k_hdi_and_k_rank_sit_outside_the_code_object_of_the_sweep(tmp_path):
+    """k_hdi, k_rank and k_fold are compiled in csrc/bnr_analysis.hip: they are in the analysis code object and not in the sweep's"""
+    assert os.path.exists(co.LIB), "libbnr_hip.so has not been built"
+    if not co.have_tools():
         pytest.skip("no ROCm LLVM tools here")
-    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "co.o")
-    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat], check=True)
-    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + co,
-                    "--unbundle"], check=True)
-    out = subprocess.run([os.path.join(llvm, "llvm-readelf"), "-sW", co], check=True, stdout=subprocess.PIPE, text=True).stdout
-    names = subprocess.run(["c++filt"], input=out, check=True, stdout=subprocess.PIPE, text=True).stdout
-    addr = {}
-    for line in names.splitlines():
-        m = re.match(r"\s*\d+:\s+([0-9a-f]+)\s+\d+\s+FUNC\s+\S+\s+\S+\s+\S+\s+(?:void )?(k_\w+(?:<[^>]*>)?)", line)
-        if m:
-            addr[m.group(2)] = int(m.group(1), 16)
-    hdi = [v for k, v in addr.items() if k.startswith("k_hdi<")]
-    rank = [v for k, v in addr.items() if k.startswith(("k_rank<", "k_fold<"))]
-    abi11 = [v for k, v in addr.items() if k.startswith(("k_psis_w", "k_loo_moments", "k_loo_quantile", "k_inv_sd"))]
-    assert len(hdi) == 1 and len(rank) == 2 and len(abi11) == 5, sorted(addr)
-    assert max(rank) < hdi[0] < min(abi11)
+    sweep, analysis = co.sweep_and_analysis(tmp_path)
+    hdi = [k for k in analysis if k.startswith("k_hdi")]
+    rank = [k for k in analysis if k.startswith(("k_rank", "k_fold"))]
+    assert len(hdi) == 1 and len(rank) == 2 and set(hdi + rank) <= co.ANALYSIS, sorted(analysis)
+    assert not [k for k in sweep if k.startswith(("k_hdi", "k_rank", "k_fold"))]

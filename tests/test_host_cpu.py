@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import bnr_amd
+import code_objects as co
 from golden_data import load_golden
 from oracle import bnr_oracle as bo
 
@@ -399,21 +400,13 @@ def test_a_capped_draw_does_not_abort_a_fit():
 def test_late_kernels_sit_behind_the_sweep_kernels_in_the_code_object(tmp_path):
     """Round 5, notes Y: a chain alone runs 1.5 % slower when kernels added later sit in the middle of the code object (every kernel of the sweep 1.4-2.9 % slower at
     unchanged source).  The instantiations are emitted in the order of their first reference in bnr_hip.hip, so every reference to k_xpass_group2, k_backproj64 and
-    k_tail<.., false> lives at the end of that file: in the gfx950 code object of the built library they must come behind every kernel of the sweep."""
-    llvm = "/opt/rocm/lib/llvm/bin"
-    lib = os.path.join(ROOT, "bayesiannetworkregression.jl_amd", "libbnr_hip.so")
-    if not (os.path.exists(os.path.join(llvm, "clang-offload-bundler")) and os.path.exists(lib)):
+    k_tail<.., false> lives at the end of that file: in the sweep's gfx950 code object they must come behind every kernel of the sweep.  The posterior analysis cannot
+    get in there at all: it is a translation unit, and so a code object, of its own."""
+    if not (co.have_tools() and os.path.exists(co.LIB)):
         pytest.skip("no ROCm LLVM tools / no built library here")
-    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "co.o")
-    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat], check=True)
-    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + co, "--unbundle"], check=True)
-    out = subprocess.run([os.path.join(llvm, "llvm-readelf"), "-sW", co], check=True, stdout=subprocess.PIPE, text=True).stdout
-    names = subprocess.run(["c++filt"], input=out, check=True, stdout=subprocess.PIPE, text=True).stdout
-    addr = {}
-    for line in names.splitlines():
-        m = re.match(r"\s*\d+:\s+([0-9a-f]+)\s+\d+\s+FUNC\s+\S+\s+\S+\s+\S+\s+(?:void )?(k_\w+(?:<[^>]*>)?)", line)
-        if m:
-            addr[m.group(2)] = int(m.group(1), 16)
+    swept, _ = co.sweep_and_analysis(tmp_path)              # (asserts that the library holds exactly two gfx950 code objects)
+    assert not co.ANALYSIS & set(swept), sorted(co.ANALYSIS & set(swept))
+    addr = {k: v[0] for k, v in swept.items()}
     late = {k: v for k, v in addr.items() if k.startswith(("k_xpass_group2", "k_backproj64")) or (k.startswith("k_tail<") and "false" in k)}
     sweep = {k: v for k, v in addr.items() if k not in late and k.startswith(("k_chol_step", "k_gram", "k_solve", "k_rhs", "k_xpass", "k_backproj", "k_node", "k_tail", "k_sdigits"))}
     assert len(late) >= 5 and len(sweep) >= 20, (sorted(late), len(sweep))

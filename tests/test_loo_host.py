@@ -4,12 +4,12 @@ argument checks that run before any GPU call, the ABI version, the Julia shim's 
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import bnr_amd
+import code_objects as co
 from bnr_amd import _capi
 from bnr_amd.api import Results, _gpdfit, _loo_from_pointwise, _psis_host, _tail_length
 
@@ -319,26 +319,10 @@ def test_julia_shim_computes_loo_through_the_new_symbol():
     assert re.search(r"ccall\(\(:bnr_chain_loo, LIB\)", src)
 
 
-def test_psis_kernels_sit_behind_the_sweep_kernels_in_the_code_object(tmp_path):
-    """as test_host_cpu.py's check of the round-5 late kernels: k_psis is referenced only from the end of bnr_hip.hip, so both of its
-    instantiations come behind every kernel of the sweep in the gfx950 code object"""
-    llvm = "/opt/rocm/lib/llvm/bin"
-    lib = os.path.join(ROOT, "bayesiannetworkregression.jl_amd", "libbnr_hip.so")
-    assert os.path.exists(os.path.join(llvm, "clang-offload-bundler")) and os.path.exists(lib)
-    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "co.o")
-    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat], check=True)
-    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat,
-                    "--output=" + co, "--unbundle"], check=True)
-    out = subprocess.run([os.path.join(llvm, "llvm-readelf"), "-sW", co], check=True, stdout=subprocess.PIPE, text=True).stdout
-    names = subprocess.run(["c++filt"], input=out, check=True, stdout=subprocess.PIPE, text=True).stdout
-    addr = {}
-    for line in names.splitlines():
-        m = re.match(r"\s*\d+:\s+([0-9a-f]+)\s+\d+\s+FUNC\s+\S+\s+\S+\s+\S+\s+(?:void )?(k_\w+(?:<[^>]*>)?)", line)
-        if m:
-            addr[m.group(2)] = int(m.group(1), 16)
-    psis = {k: v for k, v in addr.items() if k.startswith("k_psis<")}
-    sweep = {k: v for k, v in addr.items() if k.startswith(("k_chol_step", "k_gram", "k_solve", "k_rhs", "k_xpass", "k_backproj", "k_node", "k_tail",
-                                                             "k_sdigits")) and not k.startswith(("k_xpass_group2", "k_backproj64"))
-             and not (k.startswith("k_tail<") and "false" in k)}
-    assert len(psis) == 2 and len(sweep) >= 20, (sorted(psis), len(sweep))
-    assert min(psis.values()) > max(sweep.values())
+def test_psis_kernels_sit_outside_the_code_object_of_the_sweep(tmp_path):
+    """k_psis is compiled in csrc/bnr_analysis.hip: both of its instantiations are in the analysis code object and not in the sweep's"""
+    assert co.have_tools() and os.path.exists(co.LIB)
+    sweep, analysis = co.sweep_and_analysis(tmp_path)
+    psis = [k for k in analysis if k.startswith("k_psis<")]
+    assert len(psis) == 2 and set(psis) <= co.ANALYSIS, sorted(analysis)
+    assert not [k for k in sweep if k.startswith("k_psis")]

@@ -5,12 +5,12 @@ statistical sanity check of "leaving one row out" on the golden fixture with the
 import math
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
 
 import bnr_amd
+import code_objects as co
 from bnr_amd import _capi, api
 from bnr_amd.api import (_host_eta, _host_loo_predict, _loo_bracket_c, _loo_predict_rows, _loo_predictive, _mixture_cdf, _mixture_quantile, _psis_host,
                          _psis_row, _psis_weights_host, _psis_weights_row, _tail_length)
@@ -248,28 +248,16 @@ def test_julia_shim_has_the_new_names():
     assert re.search(r"ccall\(\(:bnr_chains_loo_predict", src) and re.search(r"ccall\(\(:bnr_psis_weights", src)
 
 
-def test_new_kernels_sit_behind_every_other_kernel_in_the_code_object(tmp_path):
-    """the kernels of ABI 11 are referenced only from the very end of bnr_hip.hip: in the gfx950 code object they come behind every older kernel"""
-    llvm = "/opt/rocm/lib/llvm/bin"
-    lib = os.path.join(ROOT, "bayesiannetworkregression.jl_amd", "libbnr_hip.so")
-    assert os.path.exists(lib), "libbnr_hip.so has not been built"            # (a failed build is a failure here, not a skip)
-    if not os.path.exists(os.path.join(llvm, "clang-offload-bundler")):
+def test_loo_predict_kernels_sit_outside_the_code_object_of_the_sweep(tmp_path):
+    """the kernels of ABI 11 are compiled in csrc/bnr_analysis.hip: all five are in the analysis code object and none in the sweep's"""
+    assert os.path.exists(co.LIB), "libbnr_hip.so has not been built"         # (a failed build is a failure here, not a skip)
+    if not co.have_tools():
         pytest.skip("no ROCm LLVM tools here")
-    fat, co = str(tmp_path / "fat.bin"), str(tmp_path / "co.o")
-    subprocess.run(["objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib, fat], check=True)
-    subprocess.run([os.path.join(llvm, "clang-offload-bundler"), "--type=o", "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + fat, "--output=" + co,
-                    "--unbundle"], check=True)
-    out = subprocess.run([os.path.join(llvm, "llvm-readelf"), "-sW", co], check=True, stdout=subprocess.PIPE, text=True).stdout
-    names = subprocess.run(["c++filt"], input=out, check=True, stdout=subprocess.PIPE, text=True).stdout
-    addr = {}
-    for line in names.splitlines():
-        m = re.match(r"\s*\d+:\s+([0-9a-f]+)\s+\d+\s+FUNC\s+\S+\s+\S+\s+\S+\s+(?:void )?(k_\w+(?:<[^>]*>)?)", line)
-        if m:
-            addr[m.group(2)] = int(m.group(1), 16)
-    new = {k: v for k, v in addr.items() if k.startswith(("k_psis_w", "k_loo_moments", "k_loo_quantile", "k_inv_sd"))}
-    old = {k: v for k, v in addr.items() if k not in new}
-    assert len(new) == 5 and len(old) >= 60, (sorted(new), len(old))
-    assert min(new.values()) > max(old.values())
+    names = ("k_psis_w", "k_loo_moments", "k_loo_quantile", "k_inv_sd")
+    sweep, analysis = co.sweep_and_analysis(tmp_path)
+    new = [k for k in analysis if k.startswith(names)]
+    assert len(new) == 5 and set(new) <= co.ANALYSIS, sorted(analysis)
+    assert not [k for k in sweep if k.startswith(names)]
 
 
 def test_leaving_one_row_out_on_the_golden_fixture():

@@ -2,15 +2,18 @@
 """Register / scratch / LDS use of every kernel: tools/kres.py [extra hipcc flags]  (cross-compiles on the CPU, no GPU needed)"""
 import re, subprocess, sys, os
 here = os.path.dirname(os.path.abspath(__file__))
-src = os.path.join(here, "..", "bayesiannetworkregression.jl_amd", "csrc", "bnr_hip.hip")
-cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-mllvm", "-amdgpu-mfma-vgpr-form",
-       "-Rpass-analysis=kernel-resource-usage", "-shared", "-o", "/tmp/kres.so", src] + sys.argv[1:]
-r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
-if r.returncode:
-    print(r.stderr[-3000:]); sys.exit(1)
+csrc = os.path.join(here, "..", "bayesiannetworkregression.jl_amd", "csrc")
+remarks = []
+for unit in ("bnr_hip.hip", "bnr_analysis.hip"):           # the library's two translation units (code objects): the sweep, the posterior analysis
+    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function", "-mllvm", "-amdgpu-mfma-vgpr-form",
+           "-Rpass-analysis=kernel-resource-usage", "-c", "-o", "/tmp/kres.o", os.path.join(csrc, unit)] + sys.argv[1:]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+    if r.returncode:
+        print(r.stderr[-3000:]); sys.exit(1)
+    remarks += r.stderr.splitlines()
 cur = {}
 rows = []
-for line in r.stderr.splitlines():
+for line in remarks:
     m = re.search(r"remark: [^ ]* *(Function Name|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]|SGPRs): (.*?) \[-Rpass", line)
     if not m:
         m2 = re.search(r"(Function Name|    VGPRs|    ScratchSize \[bytes/lane\]|    Occupancy \[waves/SIMD\]|    LDS Size \[bytes/block\]|    SGPRs): (\S+)", line)
