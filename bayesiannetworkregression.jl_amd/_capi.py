@@ -116,6 +116,7 @@ _SIGS = {
     "bnr_host_normal": (C.c_double, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]),
     "bnr_host_gamma": (C.c_double, [C.c_uint64, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32]),
     "bnr_host_gig": (C.c_double, [C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_uint32]),
+    "bnr_host_gig_attempts": (C.c_int32, [C.c_uint64, C.c_double, C.c_double, C.c_double, C.c_uint32, C.c_uint32]),
     "bnr_host_edge_index": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32]),
     "bnr_host_xi_weight": (C.c_double, [C.c_double, C.c_double, C.c_double]),
     "bnr_host_pred_noise": (None, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _dp]),

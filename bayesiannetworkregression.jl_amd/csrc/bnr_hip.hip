@@ -107,6 +107,18 @@ double bnr_host_gamma(uint64_t seed, double shape, uint32_t it, uint32_t site, u
 { int cap = 0; return bnr_gamma(seed, shape, it, site, elem, &cap); }
 double bnr_host_gig(uint64_t seed, double lambda, double chi, double psi, uint32_t it, uint32_t elem)
 { int cap = 0; return bnr_gig(seed, lambda, chi, psi, it, elem, &cap); }
+int32_t bnr_host_gig_attempts(uint64_t seed, double lambda, double chi, double psi, uint32_t it, uint32_t elem)
+{
+    // bnr_gig's own loop, reporting the accepted attempt instead of its value
+    bnr_gig_ctx c;
+    bnr_gig_setup(c, lambda, chi, psi);
+    if (c.kind != 2 && c.kind != 3) return -1;
+    for (uint32_t k = 0; k < BNR_MAX_ATTEMPTS; ++k) {
+        double out;
+        if (bnr_gig_try(c, seed, it, elem, k, out)) return (int32_t)k;
+    }
+    return (int32_t)BNR_MAX_ATTEMPTS;
+}
 int32_t bnr_host_edge_index(int32_t V, int32_t l, int32_t k)
 { return l >= k ? bnr_edge_index(V, l, k) : bnr_edge_index(V, k, l); }
 double bnr_host_xi_weight(double lt, double lb, double Delta)
@@ -775,10 +787,18 @@ static void launch_solve(bnr_exec &x)
 static void launch_backproj(bnr_exec &x, int s, int flags)
 {
     {
-        // many rounds of workgroups (a lockstep group at large q): only the instructions per edge count -- one edge per lane of the drawing wave (k_backproj64)
+        // k_backproj64 (64 edges per workgroup, one sampler per drawing wave, packed retries): a lockstep group with more chunks than CUs, and a chain alone from 8 chunks per CU on.
+        // Measured, us per sweep, k_backproj / k_backproj64, two interleaved repeats each (profiles/backproj_packed_retry.txt; chunks = chains x chunks of 32 edges):
+        //   n=500 V=100 R=7  x 16 (2 528 chunks)  644.2 / 629.5      x 8 (1 264)  365.7 / 360.4      x 4 (632)  252.8 / 253.2 (equal: inside the repeat spread)
+        //                    x 3 (474)  235.4 / 233.0                x 2 (316)  208.8 / 206.2        alone (158)  172.4 / 174.6 (loses: latency-bound, keeps k_backproj)
+        //   n=500 V=300 R=10 x 8 (11 288)  1 970.9 / 1 915.8          x 2 (2 822)  621.0 / 608.3
+        //   n=200 V=50 R=5   x 8 (320)  121.1 / 119.6                x 2 (80)  105.4 / 106.5 (loses)  n=500 V=40 R=4 x 8 (208)  206.0 / 207.1 (loses)
+        // The group's threshold rests on these few points: the nearest pair is 208 chunks (loses 1.1) and 316 / 320 (win 2.6 / 1.5), 632 is a tie; "more chunks than CUs" lies between
+        // and is not a fitted optimum.  A chain alone between 158 and 2 048 chunks was not re-measured: it keeps the earlier rule.
         const size_t lds64 = ((size_t)x.shape->n_pad + 64 + (size_t)x.shape->R * 65 + (size_t)(3 * x.shape->R + 1) * 65) * sizeof(double);
-        const bool many_rounds = (size_t)x.nb * x.shape->nblk_bp >= (size_t)8 * x.ncu;       // (measured: 2 528 chunks -1.3 %, 2 822 -1.3 %, 5 644 -2.4 %, 11 288 -3 %; 1 411 equal; 1 264 +0.4 %; a chain alone at the headline shape +4 %)
-        if ((flags & 3) == 3 && lds64 <= 124 * 1024 && (x.wide_backproj == 1 || (x.wide_backproj < 0 && many_rounds))) {
+        const size_t chunks = (size_t)x.nb * x.shape->nblk_bp;
+        const bool many_rounds = x.nb > 1 ? chunks > (size_t)x.ncu : chunks >= (size_t)8 * x.ncu;
+        if ((flags & 3) == 3 && lds64 + BNR_BP64_STATIC_LDS <= 124 * 1024 && (x.wide_backproj == 1 || (x.wide_backproj < 0 && many_rounds))) {
             launch_late_backproj64(x, s, flags, lds64);
             return;
         }

@@ -38,7 +38,7 @@ struct bnr_exec {
     int group_xpass = -1;                               // -1 / 1: a group whose members share X runs the X pass with one workgroup per chunk for all chains; 0: per chain
     bnr_plan_entry *gplan_pin = nullptr, *gplan_dev = nullptr;   // groups: the members' plans of a run call, staged for one copy
     int gplan_cap = 0;                                  // entries per member in there
-    int wide_backproj = -1;                              // 1: k_backproj64 (64 edges per workgroup, one edge per lane of the drawing wave); -1: launches of many rounds (a group at large q)
+    int wide_backproj = -1;                              // 1: k_backproj64 (64 edges per workgroup, one sampler per drawing wave, packed retries); -1: a group with more chunks than CUs, a chain alone at large q (launch_backproj)
     int split_sums = -1;                                 // 1: the back-projection's partial sums as a launch of their own in front of the scalar tail (off the critical chain)
     int spw_cap = 1;                                    // super blocks per update workgroup of the factorization, at most (round 6: 1 -- with the four-wave panel sweep (bnr_panel_sweep_pipe) one block each is the shorter launch: 8 chains 369.4 against 372-374 us per sweep; rounds 3-5 packed up to 4 behind the single sweeping wave)
     // Round 6: WHEN the scalar branch's kernels start is part of the schedule (profiles/round6_experiments_notes.txt A): inside the two-branch sweep they are ordered behind

@@ -3355,15 +3355,90 @@ __global__ __launch_bounds__(256) void k_xpass_group2(const bnr_many chain_src, 
     }
 }
 
+// ------------------------------------------------------------------------------------- the draws of k_backproj64
+// One rejection sampler (KIND 2: ratio of uniforms, 3: concave envelope) for the edges of one wave, one edge per lane (`mine`: this lane's edge is of that kind).  Every such lane
+// runs bnr_gig_setup and attempt 0 of its edge.  The lanes whose attempt 0 is rejected are compacted (ballot + prefix count) into a list of open edges, and the fields of their
+// bnr_gig_ctx that bnr_gig_try reads go to LDS (copied, not recomputed).  In every further round the wave's 64 lanes are dealt over the m open edges, A = the largest power of
+// two <= 64 / m (at most 16) attempts each: lane l evaluates attempt base + l mod A of open edge l / A.  bnr_gig_try is a pure function of (ctx, seed, it, elem, k) and every open
+// edge has been refused the attempts below `base`, so the lowest accepted index of a round is the first accepted attempt of bnr_gig's loop -- the same draw bit for bit, in ~2
+// rounds of one instruction stream instead of as many dependent attempts as the unluckiest of 64 edges needs.  Bounded by BNR_MAX_ATTEMPTS with bnr_gig's fallback.
+// Wave-level synchronisation only (sc / sres / sopen belong to this wave).
+#define BNR_BP_NF 11                                      // staged fields per edge: the larger of the two sets below
+#define BNR_BP64_STATIC_LDS ((2 * BNR_BP_NF * 64 + 3 * 64) * sizeof(double) + 2 * 64 * sizeof(int))     // k_backproj64's static arrays (the staging of both drawing waves)
+template <int KIND>
+__device__ __forceinline__ void bnr_bp_stage(double (*sc)[64], int slot, const bnr_gig_ctx &c)
+{
+    sc[0][slot] = c.alpha; sc[1][slot] = c.xm;
+    if (KIND == 2) { sc[2][slot] = c.ulo; sc[3][slot] = c.uhi; sc[4][slot] = c.xoff; sc[5][slot] = c.t; sc[6][slot] = c.s; sc[7][slot] = c.nc; }
+    else { sc[2][slot] = c.omega; sc[3][slot] = c.Atot; sc[4][slot] = c.A0; sc[5][slot] = c.A1; sc[6][slot] = c.x0; sc[7][slot] = c.k0; sc[8][slot] = c.k1; sc[9][slot] = c.k2; sc[10][slot] = c.x0l; }
+}
+template <int KIND>
+__device__ __forceinline__ void bnr_bp_unstage(bnr_gig_ctx &c, const double (*sc)[64], int slot, double lambda)
+{
+    c.kind = KIND; c.lambda_old = lambda; c.lambda = lambda < 0.0 ? -lambda : lambda; c.half = (c.lambda == 0.5) ? 1 : 0;       // what bnr_gig_setup stores for this lambda
+    c.alpha = sc[0][slot]; c.xm = sc[1][slot];
+    if (KIND == 2) { c.ulo = sc[2][slot]; c.uhi = sc[3][slot]; c.xoff = sc[4][slot]; c.t = sc[5][slot]; c.s = sc[6][slot]; c.nc = sc[7][slot]; }
+    else { c.omega = sc[2][slot]; c.Atot = sc[3][slot]; c.A0 = sc[4][slot]; c.A1 = sc[5][slot]; c.x0 = sc[6][slot]; c.k0 = sc[7][slot]; c.k1 = sc[8][slot]; c.k2 = sc[9][slot]; c.x0l = sc[10][slot]; }
+}
+template <int KIND>
+__device__ __forceinline__ double bnr_bp_draw(bool mine, double chi, double psi, uint64_t seed, uint32_t it, int e0, int lane, double (*sc)[64], double *sres, int *sopen, int *cap)
+{
+    double Snew = 1.0;
+    bool open = false;
+    bnr_gig_ctx c;
+    if (mine) {
+        bnr_gig_setup(c, 0.5, chi, psi);
+        c.kind = KIND;                                    // (bnr_gig_kind said so: bnr_gig_try's other sampler drops out)
+        double out;
+        if (bnr_gig_try(c, seed, it, (uint32_t)(e0 + lane), 0u, out)) Snew = out; else open = true;
+    }
+    const unsigned long long om = __ballot(open), below = (1ull << lane) - 1ull;
+    int m = __popcll(om);                                 // open edges (the same number in every lane)
+    if (m == 0) return Snew;
+    if (open) { bnr_bp_stage<KIND>(sc, lane, c); sopen[__popcll(om & below)] = lane; }
+    bnr_wsync();
+    uint32_t base = 1u;
+    while (m > 0 && base < BNR_MAX_ATTEMPTS) {
+        const int lg = m <= 4 ? 4 : (m <= 8 ? 3 : (m <= 16 ? 2 : (m <= 32 ? 1 : 0))), A = 1 << lg;
+        const int j = lane >> lg, a = lane & (A - 1);
+        const uint32_t k = base + (uint32_t)a;
+        const bool has = j < m;
+        const int src = has ? sopen[j] : 0;
+        if (has) bnr_bp_unstage<KIND>(c, sc, src, 0.5);   // (a lane without an edge reads no staging slot: slot 0 may never have been written)
+        double out = 0.0;
+        const bool ok = has && k < BNR_MAX_ATTEMPTS && bnr_gig_try(c, seed, it, (uint32_t)(e0 + src), k, out);
+        const unsigned grp = (unsigned)(__ballot(ok) >> (j << lg)) & ((1u << A) - 1u);        // the accepted attempts of this lane's edge
+        if (ok && a == __ffs(grp) - 1) sres[src] = out;                                        // the lowest accepted attempt wins
+        const bool still = has && a == 0 && grp == 0u;
+        const unsigned long long sm = __ballot(still);
+        bnr_wsync();                                      // every lane has read its entry of the list before the list is rewritten
+        if (still) sopen[__popcll(sm & below)] = src;
+        m = __popcll(sm);
+        base += (uint32_t)A;
+        bnr_wsync();
+    }
+    if (m > 0) {                                          // attempt cap, as bnr_gig
+        if (lane < m) {
+            const int src = sopen[lane];
+            bnr_bp_unstage<KIND>(c, sc, src, 0.5);
+            if (cap) *cap = 1;
+            sres[src] = c.alpha * c.xm;
+        }
+        bnr_wsync();
+    }
+    if (open) Snew = sres[lane];
+    return Snew;
+}
+
 // ===================================================================================== k_backproj64
-// The back-projection for launches of MANY rounds of workgroups (a lockstep group at large q: 8 chains at BASELINE configs[4] are 11 288 chunks of 32 edges, 15 rounds of
-// 768 resident workgroups): there only the number of instructions per edge counts, and k_backproj's drawing wave spends its 64 lanes on 32 edges (two speculative attempts per
-// edge and round) -- one GIG setup and one pass of the 3R + 1 terms per 32 edges.  Here a workgroup owns 64 consecutive edges (two chunks of the Psum table) and its drawing
-// wave holds one edge per lane: one setup and one pass of the terms per 64 edges, the attempts of an edge one after the other (bnr_gig's own loop, no exchange through LDS).
-// About as many attempt rounds per 64 edges (the slowest of 64 lanes against twice the slowest of 32 with two attempts each), ~25 % fewer instructions per edge
-// (profiles/round5_cfg5_roofline.txt: the launch is bound by that arithmetic).  Per edge the same arithmetic as k_backproj: the same per-lane row sums and wave reduction (gamma),
-// the first accepted attempt of bnr_gig (S), the same terms summed per chunk of 32 edges in the same order (Psum) -- bitwise the same tables.
-// Launches of one or two rounds (the headline group, a chain alone) keep k_backproj: there the draw's latency counts, and it is shorter with 32 edges per wave.
+// The back-projection of a lockstep group and of launches of many rounds of workgroups: there the launch is bound by the vector instructions of the GIG draws, and k_backproj's
+// drawing wave spends its 64 lanes on 32 edges (a speculative second attempt per edge and round that is thrown away whenever the first is accepted, one GIG setup and one pass
+// of the 3R + 1 terms per 32 edges, both rejection samplers back to back in one wave).  Here a workgroup owns 64 consecutive edges (two chunks of the Psum table) and two of
+// its waves draw, one sampler each and one edge per lane: the setup and attempt 0 of every edge once, then only the refused edges' further attempts, packed over the wave's
+// lanes (bnr_bp_draw above: at the headline state 31 % of the first attempts are refused and a workgroup needs 1-2 packed rounds, against the 3.6 dependent attempts of the
+// unluckiest of 64 edges).  The terms are spread over the four waves by factor, the sums over the block's threads.
+// Per edge the same arithmetic as k_backproj: the same per-lane row sums and wave reduction (gamma), the first accepted attempt of bnr_gig (S), the same terms summed per chunk
+// of 32 edges in the same order (Psum) -- bitwise the same tables.  A chain alone at moderate q keeps k_backproj (latency-bound: four drawing waves per 32 edges are shorter).
 // flags bit 2 -> partial sums; gamma and S always.  grid = round_up(ceil(nblk_bp / 2), 8) x chains.
 template <class SRC>
 __global__ __launch_bounds__(256) void k_backproj64(const SRC chain_src, int s, int flags, int nchains)
@@ -3412,28 +3487,50 @@ __global__ __launch_bounds__(256) void k_backproj64(const SRC chain_src, int s, 
         if (lane == 0) { sdot[t] = acc0; if (t2 < ne) sdot[t2] = acc1; if (t3 < ne) sdot[t3] = acc2; if (t4 < ne) sdot[t4] = acc3; }
     }
     __syncthreads();
-    if (wave != (pid & 3)) return;                         // the drawing wave rotates with the workgroup (the drawing waves that share a CU sit on different SIMDs)
+    // update_D! (gibbs.jl:454-458).  Two waves draw, one rejection sampler each (bnr_bp_draw above): wave w2 the workgroup's ratio-of-uniforms edges (kind 2 of bnr_gig_setup) and
+    // the draws without a loop of their own (kinds 0, 1, 4), wave w3 its concave-envelope edges (kind 3) -- bnr_gig_kind decides, as in k_backproj.  The two rotate with the
+    // workgroup and sit two waves apart: on different SIMDs, and the drawing waves of the workgroups that share a CU spread over all four.  All four waves stay to the last
+    // barrier of the block (no block-wide barrier is asked of a block one of whose waves has left) and share the terms and the sums behind it.
+    __shared__ double s_ctx[2][BNR_BP_NF][64];
+    __shared__ double s_res[2][64], s_S[64];
+    __shared__ int s_open[2][64];
+    const int w2 = pid & 3, w3 = (pid + 2) & 3;
     const int e = e0 + lane;
     const bool act = lane < ne;
-    int cap = 0;
-    double gam = 0.0, W = 0.0, Snew = 1.0;
+    double gam = 0.0, W = 0.0;
     if (act) {
         W = cd.Wbuf[e];
         const double Sp = prev[cd.o_S + e];
         gam = tau * (cd.sz[e] + Sp * sdot[lane]) + W;
-        row[cd.o_gamma + e] = gam;
-        const double g = gam - W, chi = (g * g) / tau2;
-        Snew = bnr_gig(cd.seed, 0.5, chi, psi, P.it, (uint32_t)e, &cap);     // update_D! (gibbs.jl:454-458): the reference's own loop, one edge per lane
-        row[cd.o_S + e] = Snew;
+        if (wave == w2) row[cd.o_gamma + e] = gam;
     }
-    if (cap) atomicAdd((unsigned long long *)&cd.counters[2], 1ull);
+    if (wave == w2 || wave == w3) {
+        int cap = 0;
+        const double g = gam - W, chi = (g * g) / tau2;
+        const int kind = act ? bnr_gig_kind(0.5, chi, psi) : -1;
+        if (wave == w2) {
+            double Snew = bnr_bp_draw<2>(kind == 2, chi, psi, cd.seed, P.it, e0, lane, s_ctx[0], s_res[0], s_open[0], &cap);
+            if (act && kind != 2 && kind != 3) {
+                bnr_gig_ctx gc;
+                bnr_gig_setup(gc, 0.5, chi, psi);
+                Snew = bnr_gig_degenerate(gc, cd.seed, chi, psi, P.it, (uint32_t)e, &cap);
+            }
+            if (kind != 3) { s_S[lane] = Snew; if (act) row[cd.o_S + e] = Snew; }
+        } else {
+            const double Snew = bnr_bp_draw<3>(kind == 3, chi, psi, cd.seed, P.it, e0, lane, s_ctx[1], s_res[1], s_open[1], &cap);
+            if (kind == 3) { s_S[lane] = Snew; row[cd.o_S + e] = Snew; }
+        }
+        if (cap) atomicAdd((unsigned long long *)&cd.counters[2], 1ull);
+    }
     if (!(flags & 4)) return;
-    // the partial sums of update_theta! / update_Lambda! (gibbs.jl:476, 603-605): every lane its edge's terms, then lanes 0-31 sum the first chunk's and lanes 32-63 the second
-    // chunk's terms over their 32 edges in k_backproj's order
+    __syncthreads();                                       // every edge's S is in s_S
+    // the partial sums of update_theta! / update_Lambda! (gibbs.jl:476, 603-605): every lane its edge's terms -- wave w those of the factors w, w + 4, ... --, then one thread per
+    // chunk and term sums the term over the chunk's 32 edges in k_backproj's order
+    const double Snew = s_S[lane];
     const double sd = sqrt(tau2 * Snew), lsd = log(sd) + 0.5 * log(2.0 * BNR_PI);
     const double *lamp = prev + cd.o_lam;
-    st[lane] = act ? Snew : 0.0;
-    for (int r = 0; r < R; ++r) {
+    if (wave == w2) st[lane] = act ? Snew : 0.0;
+    for (int r = wave; r < R; r += 4) {
         const double dr = sdr[r * 65 + lane], lr = lamp[r];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -3442,15 +3539,14 @@ __global__ __launch_bounds__(256) void k_backproj64(const SRC chain_src, int s, 
             st[(1 + 3 * r + c) * 65 + lane] = act ? (-0.5 * zz * zz - lsd) : 0.0;
         }
     }
-    bnr_wsync();
-    const int half = lane >> 5, chunk = 2 * pid + half;
-    if (chunk < cd.nblk_bp) {
-        double *ps = cd.Psum + (size_t)chunk * nterm;
-        for (int j = lane & 31; j < nterm; j += 32) {
+    __syncthreads();
+    for (int idx = tid; idx < 2 * nterm; idx += 256) {
+        const int half = idx >= nterm ? 1 : 0, j = idx - half * nterm, chunk = 2 * pid + half;
+        if (chunk < cd.nblk_bp) {
             double acc = 0.0;
 #pragma unroll 8
             for (int e2 = 0; e2 < 32; ++e2) acc += st[j * 65 + 32 * half + e2];
-            ps[j] = acc;
+            cd.Psum[(size_t)chunk * nterm + j] = acc;
         }
     }
 }

@@ -28,14 +28,15 @@
 extern "C" {
 #endif
 
-#define BNR_ABI_VERSION 13  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
+#define BNR_ABI_VERSION 14  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
                                5: + bnr_chain_create_typed, bnr_chain_create_from_matrices, bnr_device_synchronize; 6: + bnr_comm_info;
                                7: + option "xi_weights", bnr_host_xi_weight; 8: + bnr_chain_predict, bnr_chain_predict_from_matrices,
                                bnr_chain_loglik_stats, option "predict_block_rows"; 9: + bnr_chain_loo, bnr_psis_loo;
                                10: + bnr_chains_summary, bnr_chains_predict, bnr_chains_predict_from_matrices, bnr_chains_loglik_stats, bnr_chains_loo,
                                bnr_host_pred_noise, option "summary_block_cols"; 11: + bnr_chain_loo_predict, bnr_chains_loo_predict,
                                bnr_psis_weights; 12: + bnr_chain_rank_diag, bnr_chains_rank_diag, bnr_rank_normalize, bnr_host_ndtri,
-                               option "rank_block_cols"; 13: + bnr_chain_hdi, bnr_chains_hdi, bnr_hdi (all additive) */
+                               option "rank_block_cols"; 13: + bnr_chain_hdi, bnr_chains_hdi, bnr_hdi;
+                               14: + bnr_host_gig_attempts (all additive) */
 
 enum {
     BNR_OK = 0,
@@ -443,9 +444,10 @@ int bnr_debug_set_exp(int32_t device, int32_t flags);
  *               dispatcher lets it (rounds 1-5).  "node_after" p >= 0: k_node waits for launch number p of the factorization; -1: follows k_tail at once.  -2 (default):
  *               chosen from a size model -- ordered where the factorization is the longer chain by a margin (n = 500, V = 100; n = 2000), free-running for small n or
  *               large q.  Graph edges between the two branches; the tables do not depend on them.
- *   "wide_backproj" -1 (default): launches of the back-projection with 8 x CUs or more chunks of 32 edges (a lockstep group at large q) run k_backproj64 --
- *               a workgroup owns 64 edges, its drawing wave one edge per lane and the reference's own attempt loop (fewer instructions per edge; launches of one or
- *               two rounds of workgroups keep k_backproj, whose draws have the shorter latency); 1: always; 0: never.  Bitwise the same tables.
+ *   "wide_backproj" -1 (default): a lockstep group whose back-projection has more chunks of 32 edges than the GPU has CUs, and a chain alone with 8 x CUs or more,
+ *               run k_backproj64 -- a workgroup owns 64 edges, two of its waves draw (one rejection sampler each, one edge per lane: attempt 0 of every edge, then the
+ *               refused edges' further attempts packed over the wave; fewer instructions per edge); smaller launches keep k_backproj, whose draws have the shorter
+ *               latency; 1: always; 0: never.  Bitwise the same tables.
  *   Experiments ("nop_fork", "pipeline", "gate_us", "linear", "linear_merge", "linear_debug", "group_backproj", "resv_mask", "crit_origin"; rounds 3-4,
  *               profiles/round*_experiments_notes.txt): all measured no faster, part of them polled device memory.  Removed from the tree in
  *               round 5 (tools/experiments/README.md): the library refuses them by name.  Their host scaffolding (streams, fields and
@@ -475,6 +477,9 @@ void bnr_host_uniform2(uint64_t seed, uint32_t it, uint32_t site, uint32_t elem,
 double bnr_host_normal(uint64_t seed, uint32_t it, uint32_t site, uint32_t elem, uint32_t att);
 double bnr_host_gamma(uint64_t seed, double shape, uint32_t it, uint32_t site, uint32_t elem);
 double bnr_host_gig(uint64_t seed, double lambda, double chi, double psi, uint32_t it, uint32_t elem);
+/* the index of the rejection attempt that bnr_host_gig's draw accepts (the same loop): -1 for the draws without a rejection loop of their own
+ * (chi ~ 0, psi ~ 0, invalid parameters), BNR_MAX_ATTEMPTS (100000) when the attempt cap is hit */
+int32_t bnr_host_gig_attempts(uint64_t seed, double lambda, double chi, double psi, uint32_t it, uint32_t elem);
 int32_t bnr_host_edge_index(int32_t V, int32_t l, int32_t k);   /* 0-based (l,k) -> 0-based e; utils.jl:50-55 */
 /* the noise of bnr_chains_predict's predictive draws (the kernel's own function; no GPU needed): an ni x ns block, ROW-major,
  * out[(i - i0) * ns + (s - s0)] = bnr_host_normal(seed, s, 40 (SITE_PRED), i, 0) for rows i0 <= i < i0 + ni and pooled draws s0 <= s < s0 + ns */
