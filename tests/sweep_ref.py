@@ -55,6 +55,12 @@ class Variates:
         self.L.bnr_host_uniform2(self.seed, it, site, elem, att, out)
         return out[0]
 
+    def uniform2(self, it, site, elem, att=0):
+        """both halves of the counter's draw: the pair (ru, rv) of one rejection attempt"""
+        out = (self._C.c_double * 2)()
+        self.L.bnr_host_uniform2(self.seed, it, site, elem, att, out)
+        return out[0], out[1]
+
     def normal(self, it, site, elem, att=0):
         return self.L.bnr_host_normal(self.seed, it, site, elem, att)
 
@@ -151,13 +157,13 @@ def edge_nodes(V):
     return np.array(el), np.array(ek)
 
 
-def compute_W(u, lam, el, ek):
-    """W_e = sum_r lam_r u_rl u_rk in long double, and the device's error bound of its own sum (gamma_(2R+1) sum |terms|)"""
+def compute_W(u, lam, el, ek, m=None):
+    """W_e = sum_r lam_r u_rl u_rk in long double, and the device's error bound of its own sum (gamma_m sum |terms|, m = 2R+1 unless given)"""
     U = np.asarray(u, dtype=LD)
     lam = np.asarray(lam, dtype=LD).ravel()
     terms = U[:, el] * lam[:, None] * U[:, ek]
     R = U.shape[0]
-    return terms.sum(axis=0), gamma_m(2 * R + 1) * absm(terms).sum(axis=0)
+    return terms.sum(axis=0), gamma_m(2 * R + 1 if m is None else m) * absm(terms).sum(axis=0)
 
 
 # ------------------------------------------------------------------------------------------------------------------ node update

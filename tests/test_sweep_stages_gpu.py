@@ -1,6 +1,7 @@
 """GPU tests of the node, tau2, M, inv(M), theta, mu, Delta, Lambda and pi stages against the extended-precision references of
 tests/sweep_ref.py (run with -m gpu on an MI355X): every entry within its a-priori bound of the device's float64 error, every xi / lambda
 decision equal to the exact one unless the uniform lies within the bound of its boundary (those are counted, and must stay few).
+In whole sweeps the S stage (update_D!, tests/gig_ref.py) is checked the same way, from k_backproj and -- wide_backproj = 1 -- k_backproj64.
 
 Crafted rows (Chain.load) run one hook at a time on the lone-chain instantiation; short runs and gibbs_step check whole sweeps stage by stage
 (inv(M) of the scalar tail, the pre-drawn tau2, the two-workgroup tail), alone and as the middle member of a lockstep group of three.
@@ -9,8 +10,10 @@ import numpy as np
 import pytest
 
 import bnr_amd
+import gig_ref as gr
 import sweep_ref as sr
 from oracle import bnr_oracle as bo
+from test_backproj_packed_retry_gpu import _draw_inputs, _kinds
 
 pytestmark = pytest.mark.gpu
 IT = 2
@@ -46,16 +49,21 @@ def _nodes(V, rng):
 
 
 class Skips:
-    def __init__(self):
-        self.n, self.skipped = 0, 0
+    """decisions too close to call, counted per group of stages: the xi / lambda decisions together, the edges of the S stage on their own (q
+    edges per row would otherwise widen what the few xi / lambda decisions may skip)"""
 
-    def add(self, n, s):
-        self.n += n
-        self.skipped += s
+    def __init__(self):
+        self.count = {}
+
+    def add(self, n, s, group="decisions"):
+        c = self.count.setdefault(group, [0, 0])
+        c[0] += n
+        c[1] += s
 
     def check(self, what):
-        print("%s: %d of %d decisions too close to call" % (what, self.skipped, self.n))
-        assert self.skipped <= max(1, SKIP_FRACTION * self.n), (what, self.skipped, self.n)
+        for group, (n, skipped) in self.count.items():
+            print("%s: %d of %d %s too close to call" % (what, skipped, n, group))
+            assert skipped <= (max(1, SKIP_FRACTION * n) if group == "decisions" else SKIP_FRACTION * n), (what, group, skipped, n)
 
 
 # ------------------------------------------------------------------------------------------------------------------ crafted rows, one hook each
@@ -198,6 +206,12 @@ def _sweep_rows(g, X, y, R, V, nu, var, rows, skips):
         assert np.array_equal(lam[rob], g["lam"][j].ravel()[rob]), (j, lam, g["lam"][j].ravel())
         skips.add(R, int(np.sum(~rob)))
         _note("pi (sweep)", sr.check(g["pi"][j], *sr.pi_ref(c, 1.01, var, it)))
+        # update_D!: row j's S from row j's gamma, u, tau2 and row j - 1's lambda and theta
+        worst, skipped, bad = gr.check_S(c["S"], gr.S_ref(p, c, V, var, it))
+        assert bad == 0, ("S", j, bad)
+        skips.add(c["S"].size, skipped, "edges of S")
+        for k, v in worst.items():
+            _note(k + " (sweep)", v)
 
 
 @pytest.mark.parametrize("n,V,R", [(40, 8, 3), (70, 19, 21), (30, 12, 7)])
@@ -243,5 +257,54 @@ def test_middle_member_of_a_group_matches_the_references(gpu):
         _sweep_rows(chains[m].fetch(), X, y, R, V, nu, sr.Variates(bnr_amd.lib(), 300 + m + 1), range(1, tot), skips)
     skips.check("group")
     grp.close()
+    for c in chains:
+        c.close()
+
+
+@pytest.mark.parametrize("ids", [(1,), (1, 2, 3)])
+def test_sweeps_of_k_backproj64_match_the_references(gpu, ids):
+    """wide_backproj = 1: a sweep's back-projection (flags 3 or 7) is k_backproj64 -- reachable no other way --, for a chain alone and for a lockstep group of three
+    (its middle member is `mid`).  Rows 2 ... 4, then one more sweep from a theta loaded into row 4 that puts omega = 0.2 at the median of mid's first 64 edges of
+    row 5: both drawing waves of its first workgroup have work (gamma, tau2 and u of row 5 do not depend on row 4's theta, so a probe chain gives chi)."""
+    n, V, R, seed, rows, nu = 60, 14, 5, 300, 4, 10
+    tot = rows + 1
+    # launch_backproj keeps k_backproj where k_backproj64's LDS (a4 | 64 dots | u products R x 65 | terms (3R + 1) x 65, and the 13 312 bytes of
+    # BNR_BP64_STATIC_LDS) passes 124 KB, and no counter tells which kernel ran: here n_pad = 64, (64 + 64 + 325 + 1040) x 8 + 13 312 = 25 256 bytes
+    assert (-(-n // 64) * 64 + 64 + 65 * R + 65 * (3 * R + 1)) * 8 + (2 * 11 * 64 + 3 * 64) * 8 + 2 * 64 * 4 <= 124 * 1024
+    X, y, _ = bnr_amd.make_synthetic(n, V, R, seed=21)
+    chains = [bnr_amd.Chain(X, y, R, tot, seed, ids[0], device=0)]
+    chains += [bnr_amd.Chain.like(chains[0], seed, c, tot) for c in ids[1:]]
+    mid = len(ids) // 2
+    probe = bnr_amd.Chain.like(chains[0], seed, ids[mid], tot)
+    probe.init_prior()
+    assert probe.run(2, tot, tot) == tot + 1
+    chi, _ = _draw_inputs(probe.fetch(), tot - 1, V)
+    probe.close()
+    theta = 0.04 / np.median(chi[:64])
+    for c in chains:
+        c.init_prior()
+    runner = bnr_amd.Group(chains) if len(chains) > 1 else chains[0]
+    runner.set_option("wide_backproj", 1)
+    assert runner.run(2, rows, rows) == rows + 1
+    skips = Skips()
+    checked = sorted({mid, len(ids) - 1})
+    for m, c in enumerate(chains):
+        t = c.fetch()
+        if m in checked:
+            _sweep_rows(t, X, y, R, V, nu, sr.Variates(bnr_amd.lib(), seed + ids[m]), range(1, rows), skips)
+        t["theta"][rows - 1] = theta
+        c.load(t, rows, rows)
+    assert runner.run(tot, tot, tot) == tot + 1
+    for m in checked:
+        g = chains[m].fetch()
+        _sweep_rows(g, X, y, R, V, nu, sr.Variates(bnr_amd.lib(), seed + ids[m]), [tot - 1], skips)
+        assert chains[m].counters()["chol_fail"] == 0 and chains[m].counters()["sampler_cap"] == 0
+        if m == mid:
+            chi, psi = _draw_inputs(g, tot - 1, V)
+            kinds = _kinds(chi, psi)[:64]
+            assert psi == theta and min((kinds == 2).sum(), (kinds == 3).sum()) >= 8, np.bincount(kinds)
+    skips.check("k_backproj64, %d chain(s)" % len(ids))
+    if len(chains) > 1:
+        runner.close()
     for c in chains:
         c.close()
