@@ -92,6 +92,9 @@ _SIGS = {
     "bnr_chain_hdi": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp] + [_dp] * 5),
     "bnr_chains_hdi": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp] + [_dp] * 5),
     "bnr_hdi": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp] + [_dp] * 5),
+    "bnr_chain_inclusion": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 6),
+    "bnr_chains_inclusion": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 6),
+    "bnr_inclusion": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32] + [_dp] * 6),
     "bnr_comm_unique_id": (C.c_int, [C.POINTER(UniqueId)]),
     "bnr_comm_create_rccl": (C.c_int, [C.POINTER(UniqueId), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "bnr_comm_create_callback": (C.c_int, [C.c_int32, C.c_int32, ALLGATHER_CB, C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -334,6 +337,55 @@ def hdi_raw(x, probs, device=0, fields=HDI_FIELDS):
         raise BnrError(BNR_ERR_HIP, _foreign_hip)
     check(L.bnr_hdi(int(device), m, S, _ptr(a), pr.size, _ptr(pr), *[_ptr(o) for o in out]))
     return tuple(out)
+
+
+INCL_FIELDS = ("prob", "joint", "size_pmf", "n_distinct", "top_sets", "top_count")
+
+
+def _incl_outputs(B, ntop, fields):
+    """(ntop, the six output arrays of an inclusion call over B indicators): prob (B,), joint (B, B), size_pmf (B + 1,), n_distinct (1,) int64,
+    top_sets (ntop, W) uint64 with W = ceil(B / 64), top_count (ntop,) int64; None where not in `fields`.  ValueError (before any library
+    call) for a field that does not exist, for no field at all, for ntop outside 0 .. 256 and for top_sets without top_count, the reverse,
+    or either with ntop = 0"""
+    fields = tuple(fields)
+    ntop = int(ntop)
+    unknown = [f for f in fields if f not in INCL_FIELDS]
+    if unknown or not fields:
+        raise ValueError("fields must name at least one of %r, not %r" % (INCL_FIELDS, fields))
+    if not 0 <= ntop <= 256:
+        raise ValueError("need 0 <= ntop <= 256, not %d" % ntop)
+    if ("top_sets" in fields) != ("top_count" in fields):
+        raise ValueError("top_sets and top_count come together")
+    if "top_sets" in fields and ntop < 1:
+        raise ValueError("top_sets and top_count need ntop >= 1")
+    W = (B + 63) // 64
+    make = dict(prob=lambda: np.empty(B), joint=lambda: np.empty((B, B)), size_pmf=lambda: np.empty(B + 1), n_distinct=lambda: np.zeros(1, dtype=np.int64),
+                top_sets=lambda: np.zeros((ntop, W), dtype=np.uint64), top_count=lambda: np.zeros(ntop, dtype=np.int64))
+    return ntop, [make[f]() if f in fields else None for f in INCL_FIELDS]
+
+
+def _incl_result(out):
+    """the outputs of an inclusion call as they are returned: n_distinct as an int"""
+    return tuple(int(o[0]) if f == "n_distinct" and o is not None else o for f, o in zip(INCL_FIELDS, out))
+
+
+def inclusion_raw(z, ntop, device=0, fields=INCL_FIELDS):
+    """The tuple INCL_FIELDS of an S x B matrix of indicators (rows = draws; an entry != 0 is 1), on the device (bnr_inclusion): the marginal
+    shares prob (B,), the co-inclusion shares joint (B, B), the distribution size_pmf (B + 1,) of the number of indicators that are 1 in a draw,
+    the number n_distinct of distinct rows, and the ntop most frequent rows as top_sets (ntop, W) -- bit k % 64 of word k // 64 is indicator k
+    -- with their counts top_count, most frequent first, ties by the row as an integer; an entry not named in `fields` is not requested and
+    comes back as None"""
+    a = np.asarray(z)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("z must be an S x B matrix (draws x indicators) with S, B >= 1")
+    a = np.ascontiguousarray(a != 0, dtype=np.uint8)
+    S, B = a.shape
+    ntop, out = _incl_outputs(B, ntop, fields)
+    L = lib()
+    if _foreign_hip:
+        raise BnrError(BNR_ERR_HIP, _foreign_hip)
+    check(L.bnr_inclusion(int(device), S, B, _ptr(a), ntop, *[_ptr(o) for o in out]))
+    return _incl_result(out)
 
 
 X_DTYPES = {np.dtype(np.float64): 0, np.dtype(np.bool_): 1, np.dtype(np.uint8): 1, np.dtype(np.int32): 2, np.dtype(np.int64): 3,
@@ -580,6 +632,14 @@ class Chain:
         check(self.L.bnr_chain_hdi(self.h, int(first_row), int(nsamp), pr.size, _ptr(pr), *[_ptr(o) for o in out]))
         return tuple(out)
 
+    def inclusion(self, first_row, nsamp, which, ntop, fields=INCL_FIELDS):
+        """The joint posterior of this chain's indicators over its window, on the device (bnr_chain_inclusion): the tuple INCL_FIELDS of the V
+        node indicators xi (which = 0) or of the R dimensions lambda != 0 (which = 1), see inclusion_raw; an entry not named in `fields` is
+        not requested and comes back as None"""
+        ntop, out = _incl_outputs(self.R if which == 1 else self.V, ntop, fields)
+        check(self.L.bnr_chain_inclusion(self.h, int(first_row), int(nsamp), int(which), ntop, *[_ptr(o) for o in out]))
+        return _incl_result(out)
+
     def counters(self):
         out = (C.c_int64 * 8)()
         check(self.L.bnr_chain_counters(self.h, out))
@@ -780,6 +840,15 @@ def pooled_hdi(chains, first_row, nsamp, probs, fields=HDI_FIELDS):
     out = _hdi_outputs(pr, c0.q + c0.V, fields)
     check(c0.L.bnr_chains_hdi(arr, len(chains), int(first_row), int(nsamp), pr.size, _ptr(pr), *[_ptr(o) for o in out]))
     return tuple(out)
+
+
+def pooled_inclusion(chains, first_row, nsamp, which, ntop, fields=INCL_FIELDS):
+    """Chain.inclusion over the pooled window of `chains` (bnr_chains_inclusion): the tuple INCL_FIELDS"""
+    chains, arr = _pooled(chains)
+    c0 = chains[0]
+    ntop, out = _incl_outputs(c0.R if which == 1 else c0.V, ntop, fields)
+    check(c0.L.bnr_chains_inclusion(arr, len(chains), int(first_row), int(nsamp), int(which), ntop, *[_ptr(o) for o in out]))
+    return _incl_result(out)
 
 
 class Comm:

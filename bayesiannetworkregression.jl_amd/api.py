@@ -22,6 +22,8 @@ Julia is not available in this image, so the thin host layer a Julia user would 
                                                device_rank_diagnostics, _host_rank_diagnostics
                                                highest-density intervals, sign probabilities, edge selection: EdgeSelect / EdgeSelection,
                                                hdi, device_edge_selection, _host_hdi
+                                               joint posterior of the node indicators: NodeSets, inclusion, device_node_sets,
+                                               _host_node_sets, _host_inclusion
   lower_triangle / create_lower_tri / setup_X!  utils.jl:17-57, gibbs.jl:239-247
 
 All sampling runs on the GPU through libbnr_hip.so; this file holds only the schedule logic (chain fan-out,
@@ -101,6 +103,7 @@ class Results:
     loo_predictive: "LOOPredictive" = None   # filled on request (loo_predict=True): the LOO predictive checks of the training rows (see LOOPredict)
     rank_diag: "RankDiagnostics" = None   # filled on request (rank_diagnostics=True): rank-normalised R-hat, bulk / tail ESS and MCSE over every chain (see RankDiagnose)
     edge_selection: "EdgeSelection" = None   # filled on request (edge_selection=True): HDIs, sign probabilities and the selected edges over every chain (see EdgeSelect)
+    node_sets: "NodeSets" = None     # filled on request (node_sets=True): co-inclusion, model size, the most probable node sets and the active dimensions over every chain (see NodeSets)
     stat_chains: int = None          # how many chains the device statistics above (summary_device, prediction, waic, loo, loo_predictive) cover: 1 (chain 1's window), or
                                      # every chain of the fit with pool_chains=True; None when the fit computed none
 
@@ -738,6 +741,144 @@ def EdgeSelect(results, hdi_prob=None, fdr=None):
     return _host_edge_selection([results.state], results.burn_in, results.sampled, 0.95 if hdi_prob is None else hdi_prob, 0.05 if fdr is None else fdr)
 
 
+# ------------------------------------------------------------------------------------------ joint posterior of the node indicators (additions)
+# Over the pooled window of the chains of one device (include/bnr_hip.h, ABI 15), of the S x B matrix of indicators z (xi_v != 0 per node, or
+# lambda_r != 0 per latent dimension): the marginal and pairwise inclusion shares, the distribution of the number of included indicators, the
+# number of distinct rows and the most frequent ones.  Every number is an integer count, divided once by S; the indicator is x != 0, so -0 is
+# excluded and a NaN counts as included.
+def _host_inclusion(z, ntop):
+    """bnr_inclusion restated in numpy for an S x B matrix (rows = draws; an entry != 0 is 1): dict of _capi.INCL_FIELDS -- prob (B,), joint
+    (B, B), size_pmf (B + 1,), n_distinct, top_sets (ntop, W) uint64 words (bit k % 64 of word k // 64 is indicator k) and top_count (ntop,),
+    most frequent first, ties by the row as an integer; zeros behind the n_distinct-th.  The fallback over fetched tables and the yardstick of
+    the GPU tests."""
+    a = np.asarray(z)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("z must be an S x B matrix (draws x indicators) with S, B >= 1")
+    ntop = int(ntop)
+    if not 0 <= ntop <= 256:
+        raise ValueError("need 0 <= ntop <= 256, not %d" % ntop)
+    b = a != 0
+    S, B = b.shape
+    W = (B + 63) // 64
+    zi = b.astype(np.int64)
+    padded = np.zeros((S, 64 * W), dtype=np.uint8)
+    padded[:, :B] = b
+    words = np.packbits(padded, axis=1, bitorder="little").view("<u8").astype(np.uint64).reshape(S, W)
+    uniq, counts = np.unique(words[:, ::-1], axis=0, return_counts=True)   # most significant word first: ascending as integers
+    order = np.argsort(-counts, kind="stable")[:ntop]
+    top_sets, top_count = np.zeros((ntop, W), dtype=np.uint64), np.zeros(ntop, dtype=np.int64)
+    top_sets[:order.size] = uniq[order][:, ::-1]
+    top_count[:order.size] = counts[order]
+    return dict(prob=zi.sum(axis=0) / float(S), joint=(zi.T @ zi) / float(S), size_pmf=np.bincount(zi.sum(axis=1), minlength=B + 1) / float(S),
+                n_distinct=int(uniq.shape[0]), top_sets=top_sets, top_count=top_count)
+
+
+def inclusion(z, ntop=10, device=None):
+    """The joint summary of any S x B matrix of 0/1 indicators (rows = draws), on the GPU (bnr_inclusion): dict with prob (B,), joint (B, B),
+    size_pmf (B + 1,), n_distinct, and the ntop most frequent rows as top_sets (ntop, W) uint64 words -- bit k % 64 of word k // 64 is
+    indicator k -- with their counts top_count (zeros behind the n_distinct-th).  ntop = 0: no rows are returned."""
+    fields = _capi.INCL_FIELDS if int(ntop) else _capi.INCL_FIELDS[:4]
+    out = dict(zip(_capi.INCL_FIELDS, _capi.inclusion_raw(z, ntop, 0 if device is None else int(device), fields=fields)))
+    return {k: v for k, v in out.items() if v is not None}
+
+
+def _set_members(words, B):
+    """the 1-based indices (as the reference numbers nodes) of the bits set in the W words of a pattern"""
+    w = np.asarray(words, dtype=np.uint64).reshape(-1)
+    k = np.arange(B)
+    return (np.flatnonzero((w[k // 64] >> (k % 64).astype(np.uint64)) & np.uint64(1)) + 1).astype(np.int64)
+
+
+_NODE_SETS_FIELDS = ("prob_nodes", "co_inclusion", "size_pmf", "size_mean", "size_mode", "n_distinct", "top_sets", "top_prob", "map_model",
+                     "median_model", "prob_active", "dim_pmf", "dim_mean", "chains", "draws")
+
+
+class NodeSets:
+    """The joint posterior of the node indicators of a fit.  Per node (V): prob_nodes (the share of draws with xi_v = 1), co_inclusion (V x V:
+    the share of draws that select both nodes; its diagonal is prob_nodes).  size_pmf (V + 1: the distribution of the number of selected
+    nodes), size_mean, size_mode.  n_distinct: the number of distinct node sets among the draws; top_sets: the most frequent ones, each an
+    array of 1-based node indices (as the reference numbers nodes), most probable first, ties by the set as an integer with node 1 the lowest
+    bit; top_prob: their shares of the draws; map_model = top_sets[0]; median_model: the nodes with prob_nodes > 0.5.  Per latent dimension
+    (R): prob_active (the share of draws with lambda_r != 0), dim_pmf (R + 1: the distribution of the number of active dimensions, the
+    "effective dimensionality"), dim_mean.  chains, draws: what was pooled.
+
+    NodeSets(results, top_sets=None) is the accessor of a fit: the GPU's numbers when the fit carried them (node_sets=True: every chain of the
+    fit; asking for more top sets than the fit kept is a ValueError, never another population), otherwise restated on the host over
+    results.state (needs return_state=True; chain 1 alone; top_sets defaults to 10).  Without a Results, NodeSets(**fields) builds the record
+    itself from exactly the fields above."""
+
+    def __new__(cls, results=None, top_sets=None, **fields):
+        if results is not None:
+            return _node_sets_of(results, top_sets)
+        return object.__new__(cls)
+
+    def __init__(self, results=None, top_sets=None, **fields):
+        if results is not None:                                          # (the accessor: __new__ returned a finished object)
+            return
+        fields["top_sets"] = top_sets                                    # (without a Results the keyword is the field of that name)
+        if set(fields) != set(_NODE_SETS_FIELDS) or top_sets is None:
+            raise TypeError("NodeSets takes a Results, or exactly the fields %r" % (_NODE_SETS_FIELDS,))
+        self.__dict__.update(fields)
+
+    def __repr__(self):
+        return "NodeSets(chains=%d, draws=%d, n_distinct=%d, size_mean=%.3f, map_model=%s)" % (self.chains, self.draws, self.n_distinct, self.size_mean,
+                                                                                               self.map_model.tolist())
+
+
+def _node_sets_ntop(ntop):
+    """the number of node sets a NodeSets reports: an int in 1 .. 256 (ValueError otherwise)"""
+    if isinstance(ntop, bool) or int(ntop) != ntop or not 1 <= int(ntop) <= 256:
+        raise ValueError("top_sets must be an integer between 1 and 256, not %r" % (ntop,))
+    return int(ntop)
+
+
+def _node_sets(xi, lam, nchains, draws):
+    """NodeSets from the INCL_FIELDS of the node indicators (all six) and of the dimensions (prob, size_pmf)"""
+    prob, joint, size_pmf, n_distinct, words, count = xi
+    V = prob.size
+    keep = min(int(n_distinct), count.size)
+    tops = [_set_members(words[j], V) for j in range(keep)]
+    return NodeSets(prob_nodes=prob, co_inclusion=joint, size_pmf=size_pmf, size_mean=float(np.arange(V + 1) @ size_pmf), size_mode=int(np.argmax(size_pmf)),
+                    n_distinct=int(n_distinct), top_sets=tops, top_prob=count[:keep] / float(draws), map_model=tops[0],
+                    median_model=(np.flatnonzero(prob > 0.5) + 1).astype(np.int64), prob_active=lam[0], dim_pmf=lam[2],
+                    dim_mean=float(np.arange(lam[2].size) @ lam[2]), chains=nchains, draws=draws)
+
+
+def device_node_sets(chains, nburn, nsamp, ntop=10):
+    """The joint posterior of the node indicators and the active dimensions over the pooled windows nburn+1 .. nburn+nsamp of live chains, on
+    the device (bnr_chains_inclusion, once for xi and once for lambda): V^2 + 2 V + R + ... numbers leave the GPU's side, not the traces"""
+    chains = list(chains)
+    ntop = _node_sets_ntop(ntop)
+    xi = _capi.pooled_inclusion(chains, nburn + 1, nsamp, 0, ntop)
+    lam = _capi.pooled_inclusion(chains, nburn + 1, nsamp, 1, 0, fields=("prob", "size_pmf"))
+    return _node_sets(xi, lam, len(chains), len(chains) * int(nsamp))
+
+
+def _host_node_sets(tables, nburn, nsamp, ntop=10):
+    """device_node_sets restated in numpy over the fetched tables of the same chains (_host_inclusion on the pooled windows)"""
+    tables = list(tables)
+    if not tables:
+        raise ValueError("need at least one table")
+    ntop = _node_sets_ntop(ntop)
+    zx = np.concatenate([t["xi"][nburn:nburn + nsamp, :, 0] for t in tables], axis=0)
+    xi = _host_inclusion(zx, ntop)
+    lam = _host_inclusion(np.concatenate([t["lam"][nburn:nburn + nsamp, :, 0] for t in tables], axis=0), 0)
+    return _node_sets([xi[f] for f in _capi.INCL_FIELDS], [lam[f] for f in _capi.INCL_FIELDS], len(tables), zx.shape[0])
+
+
+def _node_sets_of(results, top_sets=None):
+    """NodeSets(results, top_sets): see NodeSets"""
+    ns = results.node_sets
+    if ns is not None:                                                   # what the fit carried, never another population in its place
+        if top_sets is not None and _node_sets_ntop(top_sets) > len(ns.top_sets) and len(ns.top_sets) < ns.n_distinct:
+            raise ValueError("top_sets=%d, but the fit kept its %d most probable node sets of %d: refit with Fit(..., node_sets=True, top_sets=%d)"
+                             % (int(top_sets), len(ns.top_sets), ns.n_distinct, int(top_sets)))
+        return ns
+    if results.state is None:
+        raise ValueError("NodeSets needs Fit(..., node_sets=True), or the state table (return_state=True)")
+    return _host_node_sets([results.state], results.burn_in, results.sampled, 10 if top_sets is None else top_sets)
+
+
 # ------------------------------------------------------------------------------------------ pooled chains, predictive intervals, PIT (additions)
 # Statistics over the POOLED window of several chains of a fit (include/bnr_hip.h, bnr_chains_*): draw c nsamp + s is the s-th window row of the
 # c-th chain.  The device_* functions take live Chain objects; the _host_pooled_* restatements take the fetched tables of the same chains: the
@@ -1289,14 +1430,17 @@ def return_psrf_VOI(chainset, nburn, nsamp, fetch_state=True, summary_interval=N
 
 
 def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None, predict=None, waic=False, loo=False, loo_r_eff=None,
-            pool_chains=False, predict_observation=False, pred_seed=0, loo_predict=None, rank_diag=False, edge_sel=None):
+            pool_chains=False, predict_observation=False, pred_seed=0, loo_predict=None, rank_diag=False, edge_sel=None, node_sets=None):
     """The Results a fit returns: chain 1's table (states[1], gibbs.jl:788) and/or its Summary statistics from the device; predict =
     (new rows, their y or None, interval), waic=True and loo=True add the prediction, WAIC and PSIS-LOO computed on the device over the
     same window.  pool_chains: those statistics over the pooled windows of all chains of the fit (one rank holds them all);
     predict_observation: the prediction through the pooled entry point (one chain unless pool_chains) with the predictive bounds and the PIT;
     loo_predict = (training y, interval): the LOO predictive checks (Results.loo_predictive), and Results.loo from the same call.
     rank_diag: the rank-normalised diagnostics over every chain of the fit (Results.rank_diag; ess_max_lag, where positive, is their lag window).
-    edge_sel = (hdi_prob, fdr): the HDIs, sign probabilities and selected edges over every chain of the fit (Results.edge_selection)."""
+    edge_sel = (hdi_prob, fdr): the HDIs, sign probabilities and selected edges over every chain of the fit (Results.edge_selection).
+    node_sets = the number of top node sets: the joint posterior of the node indicators over every chain of the fit (Results.node_sets)."""
+    if node_sets is not None:
+        res.node_sets = device_node_sets([chainset.chains[c] for c in chainset.ids], res.burn_in, res.sampled, node_sets)
     if edge_sel is not None:
         res.edge_selection = device_edge_selection([chainset.chains[c] for c in chainset.ids], res.burn_in, res.sampled, edge_sel[0], edge_sel[1])
     if rank_diag:
@@ -1392,6 +1536,16 @@ def _edge_selection_request(edge_selection, hdi_prob, fdr):
     return _edge_levels(hdi_prob, fdr)
 
 
+def _node_sets_request(node_sets, top_sets):
+    """Fit's node_sets checked before any sampling: the number of top node sets for _finish, or None.  Like edge_selection it needs every chain
+    of the fit on this rank."""
+    if not node_sets:
+        return None
+    if _rank_world()[1] > 1:
+        raise ValueError("node_sets needs every chain of the fit on one rank: the chains are spread over %d torch.distributed ranks" % _rank_world()[1])
+    return _node_sets_ntop(top_sets)
+
+
 def _pooled_request(pool_chains, predict_observation, predict_X):
     """Fit's pool_chains / predict_observation checked before any sampling"""
     if predict_observation and predict_X is None:
@@ -1439,7 +1593,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                      purge_burn=None, device=None, _keep=None, return_state=True, summary_interval=None, ess_max_lag=None,
                      xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
                      pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
-                     hdi_prob=0.95, fdr=0.05):
+                     hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10):
     """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
     xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
     xi_weights_code(xi_weights)
@@ -1453,6 +1607,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
     lp_req = _loo_predict_request(loo_predict, predict_interval, y)
     rd_req = _rank_diag_request(rank_diagnostics, nsamp, ess_max_lag)
     es_req = _edge_selection_request(edge_selection, hdi_prob, fdr)
+    ns_req = _node_sets_request(node_sets, top_sets)
     _capi.r_eff_array(loo_r_eff, X_new.n)              # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
@@ -1496,7 +1651,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
     print("R = %s nu=%s nburn= %d nsamp = %d" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f\n" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
     res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff, pool_chains, predict_observation,
-                  seed_eff if pred_seed is None else pred_seed, lp_req, rd_req, es_req)
+                  seed_eff if pred_seed is None else pred_seed, lp_req, rd_req, es_req, ns_req)
     if _keep is None:
         cs.close()
     return res
@@ -1507,7 +1662,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                          seed=None, purge_burn=None, device=None, return_state=True, summary_interval=None, ess_max_lag=None,
                          xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
                          pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
-                         hdi_prob=0.95, fdr=0.05):
+                         hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10):
     """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
     xi_weights_code(xi_weights)
     if nu == R:
@@ -1520,6 +1675,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
     lp_req = _loo_predict_request(loo_predict, predict_interval, y)
     rd_req = _rank_diag_request(rank_diagnostics, nsamp, ess_max_lag)
     es_req = _edge_selection_request(edge_selection, hdi_prob, fdr)
+    ns_req = _node_sets_request(node_sets, top_sets)
     _capi.r_eff_array(loo_r_eff, X_new.n)              # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
@@ -1565,7 +1721,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
     print("\nR = %s nu=%s nburn= %d nsamp = %d\n" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.4f. Max PSRF Gamma: %.4f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
     res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff, pool_chains, predict_observation,
-                  seed_eff if pred_seed is None else pred_seed, lp_req, rd_req, es_req)
+                  seed_eff if pred_seed is None else pred_seed, lp_req, rd_req, es_req, ns_req)
     cs.close()
     return res
 
@@ -1575,7 +1731,7 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
         purge_burn=None, filename="parameters.log", device=None, return_state=True, summary_interval=None, ess_max_lag=None,
         xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
         pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
-        hdi_prob=0.95, fdr=0.05):
+        hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10):
     """Fit! (gibbs.jl:725-751).  The `V` keyword is accepted and ignored, as in the reference.
     Extensions: summary_interval=95 computes Summary's statistics on the GPU (Results.summary_device);
     return_state=False then leaves the (large) state table on the device and frees it; ess_max_lag=0 (default lag
@@ -1596,12 +1752,16 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     edge_selection=True adds the hdi_prob highest-density interval, the median and the sign probabilities of every edge coefficient and node
     indicator, and the largest set of edges whose expected false sign rate stays within fdr, computed on the GPU from the resident traces over
     every chain of the fit (Results.edge_selection, see EdgeSelect); every chain must live on this rank.
+    node_sets=True adds the joint posterior of the node indicators: the co-inclusion matrix, the distribution of the number of selected nodes,
+    the top_sets most probable node sets (the first is the MAP model) and the distribution of the number of active latent dimensions, computed
+    on the GPU from the resident traces over every chain of the fit (Results.node_sets, see NodeSets); every chain must live on this rank.
     parameters.log keeps the reference's lines only."""
     xi_weights_code(xi_weights)
     _pooled_request(pool_chains, predict_observation, predict_X)
     _loo_predict_request(loo_predict, predict_interval, y)
     _rank_diag_request(rank_diagnostics)
     _edge_selection_request(edge_selection, hdi_prob, fdr)
+    _node_sets_request(node_sets, top_sets)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
         with open(filename, "w") as f:
@@ -1621,11 +1781,13 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                                     xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval,
                                     waic=waic, loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation,
                                     pred_seed=pred_seed, loo_predict=loo_predict, rank_diagnostics=rank_diagnostics,
-                                    edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr)
+                                    edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr,
+                                    node_sets=node_sets, top_sets=top_sets)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
                             return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
                             xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic,
                             loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed,
-                            loo_predict=loo_predict, rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr)
+                            loo_predict=loo_predict, rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr,
+                            node_sets=node_sets, top_sets=top_sets)

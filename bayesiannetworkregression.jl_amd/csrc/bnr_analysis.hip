@@ -452,6 +452,129 @@ int bnr_hdi(int32_t device, int32_t m, int32_t S, const double *x, int32_t nprob
     return out.fetch(st, lower, upper, median, p_pos, p_neg);
 }
 
+// The joint posterior of the indicators (ABI 15): include/bnr_hip.h.  The six outputs of a call, and the checks that need no device
+#define BNR_INCL_MAX_B 4096                              // k_incl_pack's counters: 4 (2 B + 1) bytes of LDS
+namespace {
+struct incl_out {
+    double *prob, *joint, *size_pmf;
+    int64_t *n_distinct;
+    uint64_t *top_sets;
+    int64_t *top_count;
+};
+}
+static int incl_args(int32_t B, int32_t ntop, const incl_out &o)
+{
+    if (!o.prob && !o.joint && !o.size_pmf && !o.n_distinct && !o.top_sets && !o.top_count) return fail(BNR_ERR_BAD_ARG, "no output requested");
+    if (!o.top_sets != !o.top_count) return fail(BNR_ERR_BAD_ARG, "top_sets and top_count come together");
+    if (ntop < 0 || ntop > 256) return fail(BNR_ERR_BAD_ARG, "need 0 <= ntop <= 256");
+    if (o.top_sets && ntop < 1) return fail(BNR_ERR_BAD_ARG, "top_sets and top_count need ntop >= 1");
+    if (B > BNR_INCL_MAX_B) return fail(BNR_ERR_BAD_ARG, "more than 4096 indicators");
+    return BNR_OK;
+}
+// The device work on S draws of B indicators, on st: k_incl_pack (from the chains' windows `srcd`, or from the bytes `zb`), k_incl_joint where
+// the joint counts are wanted, k_incl_group where the distinct patterns are; then the counts come to the host and are divided by S once.
+static int incl_run(hipStream_t st, dev_tmp &tmp, const bnr_incl_src *srcd, int nsamp, const unsigned char *zb, long long S_, int B, int32_t ntop,
+                    const incl_out &o)
+{
+    const int S = (int)S_, W = (B + 63) / 64, CW = (int)((S_ + 63) / 64);
+    const bool group = o.n_distinct || o.top_sets;
+    const int nt = o.top_sets ? ntop : 0;
+    unsigned long long *pat = nullptr, *col = nullptr, *keyA = nullptr, *keyB = nullptr, *topd = nullptr;
+    unsigned int *marg = nullptr, *size = nullptr, *cnt = nullptr, *idxA = nullptr, *idxB = nullptr;
+    long long *ndd = nullptr;                            // n_distinct, then the nt counts
+    int rc;
+    if ((rc = tmp.alloc(&marg, (size_t)B, st)) || (rc = tmp.alloc(&size, (size_t)B + 1, st))) return rc;
+    if (o.joint && ((rc = tmp.alloc(&col, (size_t)B * CW, st, false)) || (rc = tmp.alloc(&cnt, (size_t)B * B, st)))) return rc;
+    if (group) {
+        if ((rc = tmp.alloc(&pat, (size_t)S * W, st, false)) || (rc = tmp.alloc(&keyA, (size_t)S, st, false)) || (rc = tmp.alloc(&keyB, (size_t)S, st, false)) ||
+            (rc = tmp.alloc(&idxA, (size_t)S, st, false)) || (rc = tmp.alloc(&idxB, (size_t)S, st, false)) || (rc = tmp.alloc(&ndd, (size_t)1 + nt, st)) ||
+            (rc = tmp.alloc(&topd, (size_t)nt * W, st)))
+            return rc;
+    }
+    hipLaunchKernelGGL(k_incl_pack, dim3(std::min((CW + 3) / 4, 1024)), dim3(256), sizeof(unsigned int) * (2 * (size_t)B + 1), st, srcd, nsamp, zb, S, B, W, CW,
+                       pat, col, marg, size);
+    if (o.joint) {
+        const int np = (B + 31) / 32;
+        hipLaunchKernelGGL(k_incl_joint, dim3(np * (np + 1) / 2, std::min((CW + 63) / 64, 16)), dim3(256), 0, st, (const unsigned long long *)col, B, CW, cnt);
+    }
+    if (group)
+        hipLaunchKernelGGL(k_incl_group, dim3(1), dim3(256), 0, st, (const unsigned long long *)pat, S, W, keyA, keyB, idxA, idxB, nt, ndd, topd, ndd + 1);
+    std::vector<unsigned int> hm(B), hs((size_t)B + 1), hc(o.joint ? (size_t)B * B : 0);
+    std::vector<long long> hn((size_t)1 + nt);
+    HIPCHK(hipMemcpyAsync(hm.data(), marg, sizeof(unsigned int) * hm.size(), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(hs.data(), size, sizeof(unsigned int) * hs.size(), hipMemcpyDeviceToHost, st));
+    if (o.joint) HIPCHK(hipMemcpyAsync(hc.data(), cnt, sizeof(unsigned int) * hc.size(), hipMemcpyDeviceToHost, st));
+    if (group) HIPCHK(hipMemcpyAsync(hn.data(), ndd, sizeof(long long) * hn.size(), hipMemcpyDeviceToHost, st));
+    if (nt) HIPCHK(hipMemcpyAsync(o.top_sets, topd, sizeof(uint64_t) * (size_t)nt * W, hipMemcpyDeviceToHost, st));
+    hipError_t e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("inclusion: ") + hipGetErrorString(e));
+    if ((rc = check_launch("k_incl_pack"))) return rc;
+    const double den = (double)S;
+    if (o.prob) for (int k = 0; k < B; ++k) o.prob[k] = (double)hm[k] / den;
+    if (o.size_pmf) for (int m = 0; m <= B; ++m) o.size_pmf[m] = (double)hs[m] / den;
+    if (o.joint) for (size_t i = 0; i < hc.size(); ++i) o.joint[i] = (double)hc[i] / den;
+    if (o.n_distinct) *o.n_distinct = hn[0];
+    if (nt) for (int j = 0; j < nt; ++j) o.top_count[j] = hn[1 + j];
+    return BNR_OK;
+}
+static int incl_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t which, int32_t ntop, const incl_out &o)
+{
+    if (which != 0 && which != 1) return fail(BNR_ERR_BAD_ARG, "which must be 0 (the node indicators xi) or 1 (the dimensions lambda)");
+    int rc;
+    bnr_chain *c = cs[0];
+    if ((rc = incl_args(which ? c->d.R : c->d.V, ntop, o))) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->x.stream;
+    if ((rc = pooled_quiesce(cs, nc))) return rc;
+    std::vector<bnr_incl_src> src(nc);
+    for (int k = 0; k < nc; ++k) {
+        const bnr_dev &dk = cs[k]->d;
+        src[k].base = dk.trace + (size_t)(first_row - 1) * dk.rowlen + (which ? dk.o_lam : dk.o_xi);
+        src[k].stride = dk.rowlen;
+    }
+    dev_tmp tmp;
+    bnr_incl_src *srcd = nullptr;
+    if ((rc = tmp.alloc(&srcd, (size_t)nc, st, false))) return rc;
+    HIPCHK(hipMemcpyAsync(srcd, src.data(), sizeof(bnr_incl_src) * nc, hipMemcpyHostToDevice, st));
+    return incl_run(st, tmp, srcd, nsamp, nullptr, (long long)nc * nsamp, which ? c->d.R : c->d.V, ntop, o);
+}
+int bnr_chain_inclusion(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t which, int32_t ntop, double *prob, double *joint, double *size_pmf,
+                        int64_t *n_distinct, uint64_t *top_sets, int64_t *top_count)
+{
+    if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
+    return incl_call(&c, 1, first_row, nsamp, which, ntop, incl_out{prob, joint, size_pmf, n_distinct, top_sets, top_count});
+}
+int bnr_chains_inclusion(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t which, int32_t ntop, double *prob,
+                         double *joint, double *size_pmf, int64_t *n_distinct, uint64_t *top_sets, int64_t *top_count)
+{
+    if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
+    return incl_call(chains, nchains, first_row, nsamp, which, ntop, incl_out{prob, joint, size_pmf, n_distinct, top_sets, top_count});
+}
+// the same on a caller's S x B matrix of bytes (host, row-major; != 0 is 1): the kernels' direct test, and the summary of any 0/1 trace.  On a
+// stream of its own.
+int bnr_inclusion(int32_t device, int32_t S, int32_t B, const uint8_t *z, int32_t ntop, double *prob, double *joint, double *size_pmf,
+                  int64_t *n_distinct, uint64_t *top_sets, int64_t *top_count)
+{
+    if (!z) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (S < 1 || B < 1) return fail(BNR_ERR_BAD_ARG, "need S >= 1 draws and B >= 1 indicators");
+    const incl_out o{prob, joint, size_pmf, n_distinct, top_sets, top_count};
+    int rc;
+    if ((rc = incl_args(B, ntop, o))) return rc;
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
+    HIPCHK(hipSetDevice(device));
+    stream_guard guard;
+    HIPCHK(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
+    hipStream_t st = guard.s;
+    dev_tmp tmp;                                        // (freed before the stream goes)
+    unsigned char *zd = nullptr;
+    if ((rc = tmp.alloc(&zd, (size_t)S * (size_t)B, st, false))) return rc;
+    HIPCHK(hipMemcpyAsync(zd, z, (size_t)S * (size_t)B, hipMemcpyHostToDevice, st));
+    return incl_run(st, tmp, nullptr, S, zd, S, B, ntop, o);
+}
+
 // What a predict_rows call computes from a block's E behind k_predict, in the order of its launches; every pointer is a device pointer, and a
 // NULL one skips its stage
 struct pred_stages {

@@ -944,3 +944,204 @@ __global__ __launch_bounds__(256) void k_hdi(const double *buf, long long ld, in
         __syncthreads();
     }
 }
+
+// ===================================================================================== k_incl_* (ABI 15: the joint posterior of the indicators)
+// Of an S x B matrix of 0/1 indicators z (B = V: xi_v != 0; B = R: lambda_r != 0; or a caller's bytes): the marginal and pairwise inclusion
+// counts, the histogram of the number of included indicators, and the distinct rows ("patterns") with their counts.  Every result is an
+// integer count; the integer atomics that collect them commute, so every output is bitwise independent of the grid and the call.  The
+// indicator is the IEEE comparison x != 0: -0 is zero, a NaN counts as included.
+//
+// k_incl_pack: the bit images of z.  A wave owns 64 draws (draw tile dt) and walks the W = ceil(B / 64) words of their patterns: for each of
+// the 64 draws one coalesced read of 64 indicators (lane = indicator; 512 bytes of a trace row read in place, or 64 bytes of the caller's
+// matrix; eight rows in flight), whose ballot is the draw's pattern word -- kept by lane i for draw i and stored to pat[S][W] --, while every lane ORs its own bit
+// into the bit-column word of its indicator over these 64 draws, stored to col[B][CW], CW = ceil(S / 64).  Rows past S and indicators past B
+// are 0 bits.  The popcounts of the column words are the marginal counts, the popcount of a draw's W words its size: both meet in LDS
+// (2 B + 1 counters, dynamic) and leave the workgroup as one global atomic per non-zero counter.  The grid strides over the draw tiles.
+// A chain's window: base = the first row's first indicator, stride = doubles between rows; pooled draw s lies in src[s / nsamp].
+// 32 VGPRs, 4 (2 B + 1) bytes of LDS, no scratch.
+struct bnr_incl_src { const double *base; long long stride; };
+__global__ __launch_bounds__(256) void k_incl_pack(const bnr_incl_src *src, int nsamp, const unsigned char *zb, int S, int B, int W, int CW,
+                                                   unsigned long long *pat, unsigned long long *col, unsigned int *marg, unsigned int *size)
+{
+    extern __shared__ unsigned int incl_cnt[];                 // [0, B]: the sizes; [B + 1, 2 B]: the marginal counts
+    unsigned int *lsize = incl_cnt, *lmarg = incl_cnt + B + 1;
+    const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    for (int t = tid; t < 2 * B + 1; t += 256) incl_cnt[t] = 0u;
+    __syncthreads();
+    for (int dt = blockIdx.x * 4 + w; dt < CW; dt += gridDim.x * 4) {
+        const int s0 = dt * 64, ns = min(64, S - s0);
+        const int c0 = zb ? 0 : s0 / nsamp, r0 = zb ? 0 : s0 - c0 * nsamp;
+        int npop = 0;
+        for (int wj = 0; wj < W; ++wj) {
+            const int k = wj * 64 + lane;
+            const bool in = k < B;
+            unsigned long long mine = 0ull, cw = 0ull;
+            for (int i0 = 0; i0 < ns; i0 += 8) {               // eight rows in flight, then their ballots
+                bool bit[8];
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const int i = i0 + j;
+                    bit[j] = false;
+                    if (in && i < ns) {
+                        if (zb) bit[j] = zb[(size_t)(s0 + i) * (size_t)B + k] != 0;
+                        else {
+                            int c = c0, r = r0 + i;
+                            while (r >= nsamp) { r -= nsamp; ++c; }            // (the next chain's window)
+                            bit[j] = src[c].base[(long long)r * src[c].stride + k] != 0.0;
+                        }
+                    }
+                }
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const unsigned long long m = __ballot(bit[j]);
+                    if (lane == i0 + j) mine = m;
+                    cw |= (unsigned long long)bit[j] << (i0 + j);
+                }
+            }
+            if (pat && lane < ns) pat[(size_t)(s0 + lane) * W + wj] = mine;
+            if (in) {
+                if (col) col[(size_t)k * CW + dt] = cw;
+                if (cw) atomicAdd(&lmarg[k], (unsigned int)__popcll(cw));
+            }
+            npop += __popcll(mine);
+        }
+        if (lane < ns) atomicAdd(&lsize[npop], 1u);
+    }
+    __syncthreads();
+    for (int t = tid; t < 2 * B + 1; t += 256) {
+        const unsigned int v = incl_cnt[t];
+        if (v) atomicAdd(t <= B ? &size[t] : &marg[t - B - 1], v);
+    }
+}
+
+// k_incl_joint: count[k][l] = sum over w of popcount(col_k[w] & col_l[w]), one 64-bit AND + popcount for 64 draws.  A workgroup takes a pair
+// (I, J <= I) of panels of 32 columns (blockIdx.x) and strides over chunks of 64 column words (blockIdx.y): both panels of a chunk go to LDS,
+// word-major and padded, so every col word is read from memory ceil(B / 32) + 1 times; a thread holds column kk = tid % 32 of panel I against
+// four columns of panel J in registers over all its chunks and adds them to the full symmetric matrix at the end, with integer atomics: the
+// pair (k, l) and, for I != J, its mirror (l, k); a diagonal pair of panels computes both halves itself.  Far below the cost of k_incl_pack
+// (V = 300, S = 400 000: 2.8e8 word operations), hence no MFMA path.  58 VGPRs, 33 KiB of LDS, no scratch.
+__global__ __launch_bounds__(256) void k_incl_joint(const unsigned long long *col, int B, int CW, unsigned int *count)
+{
+    __shared__ unsigned long long pa[64][33], pb[64][33];
+    const int tid = threadIdx.x, kk = tid & 31, l0 = (tid >> 5) * 4;
+    int I = 0, rest = blockIdx.x;
+    while (rest > I) { rest -= I + 1; ++I; }                   // blockIdx.x = I (I + 1) / 2 + J
+    const int J = rest, nchunks = (CW + 63) / 64;
+    unsigned int acc[4] = {0u, 0u, 0u, 0u};
+    for (int ch = blockIdx.y; ch < nchunks; ch += gridDim.y) {
+        const int w0 = ch * 64;
+        for (int e = tid; e < 32 * 64; e += 256) {
+            const int cidx = e >> 6, x = e & 63, ka = I * 32 + cidx, kb = J * 32 + cidx;
+            const bool wi = w0 + x < CW;
+            pa[x][cidx] = wi && ka < B ? col[(size_t)ka * CW + w0 + x] : 0ull;
+            pb[x][cidx] = wi && kb < B ? col[(size_t)kb * CW + w0 + x] : 0ull;
+        }
+        __syncthreads();
+        for (int x = 0; x < 64; ++x) {
+            const unsigned long long a = pa[x][kk];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] += (unsigned int)__popcll(a & pb[x][l0 + j]);
+        }
+        __syncthreads();
+    }
+    const int k = I * 32 + kk;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int l = J * 32 + l0 + j;
+        if (k < B && l < B && acc[j]) {
+            atomicAdd(&count[(size_t)k * B + l], acc[j]);
+            if (I != J) atomicAdd(&count[(size_t)l * B + k], acc[j]);
+        }
+    }
+}
+
+// k_incl_group: the distinct patterns among the S draws and their counts, exactly (no hashing), in one workgroup of 256 threads with k_rank's
+// sort (bnr_sort_passes and its LDS arrays, unchanged).
+//   1. LSD radix sort of the draw indices over the W pattern words, word 0 (the least significant) first: per word the keys pat[si[t]][w] are
+//      gathered in the current order with their eight digit histograms (a word that is the same in every draw skips all its passes), then
+//      bnr_sort_passes<true>.  Stable, so the draws end up ascending in the pattern as an integer.
+//   2. run heads: position t starts a run where any of the W words differs from position t - 1; the heads are compacted in order (a ballot per
+//      wave, a carry per tile of 256) into the free index buffer.  n_distinct = the number of heads, a run's length = the next head - its own.
+//   3. the ntop most frequent (ntop > 0): a keys-only sort (bnr_sort_passes<false>) of ((2^32 - 1 - count) << 32) | head position: count
+//      descending, ties by position, i.e. by pattern ascending.  The first min(ntop, n_distinct) give top_count and -- through si -- the W
+//      words of top_sets; the entries behind them stay the zeros they were allocated as.
+// Every index stays below S: si is a permutation of 0 .. S - 1 and head positions are positions of it.  keyA / keyB / idxA / idxB hold S
+// entries each.  37 VGPRs, 14.1 KiB of LDS, no scratch.
+__global__ __launch_bounds__(256) void k_incl_group(const unsigned long long *pat, int S, int W, unsigned long long *keyA, unsigned long long *keyB,
+                                                    unsigned int *idxA, unsigned int *idxB, int ntop, long long *n_distinct,
+                                                    unsigned long long *top_sets, long long *top_count)
+{
+    __shared__ unsigned int hist[8][256];
+    __shared__ unsigned int base[256], tmp[256];
+    __shared__ unsigned int wcnt[4][256];
+    __shared__ int s_skip[8], wheads[4];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    unsigned long long *src = keyA, *dst = keyB;
+    unsigned int *si = idxA, *di = idxB;
+    for (int b = 0; b < 4; ++b) wcnt[b][tid] = 0u;
+    for (int t = tid; t < S; t += 256) si[t] = (unsigned int)t;
+    // 1. the draws in the order of their patterns
+    for (int wd = 0; wd < W; ++wd) {
+        for (int b = 0; b < 8; ++b) hist[b][tid] = 0u;
+        if (tid < 8) s_skip[tid] = 0;
+        __syncthreads();
+        for (int t = tid; t < S; t += 256) {
+            const unsigned long long key = pat[(size_t)si[t] * W + wd];
+            src[t] = key;
+#pragma unroll
+            for (int b = 0; b < 8; ++b) atomicAdd(&hist[b][(unsigned int)(key >> (8 * b)) & 255u], 1u);
+        }
+        __syncthreads();
+        for (int b = 0; b < 8; ++b) if (hist[b][tid] == (unsigned int)S) s_skip[b] = 1;
+        __syncthreads();
+        bnr_sort_passes<true>(S, src, dst, si, di, hist, base, tmp, wcnt, s_skip);
+        __syncthreads();
+    }
+    // 2. run heads, compacted into di
+    int nd = 0;                                                // (the heads so far: the same in every thread)
+    for (int t0 = 0; t0 < S; t0 += 256) {
+        const int t = t0 + tid;
+        bool head = false;
+        if (t < S) {
+            head = t == 0;
+            if (t > 0) {
+                const unsigned long long *a = pat + (size_t)si[t] * W, *b = pat + (size_t)si[t - 1] * W;
+                for (int wd = 0; wd < W; ++wd) head = head || a[wd] != b[wd];
+            }
+        }
+        const unsigned long long hm = __ballot(head);
+        if (lane == 0) wheads[w] = __popcll(hm);
+        __syncthreads();
+        int at = nd;
+        for (int ww = 0; ww < w; ++ww) at += wheads[ww];
+        if (head) di[at + __popcll(hm & below)] = (unsigned int)t;
+        nd += wheads[0] + wheads[1] + wheads[2] + wheads[3];
+        __syncthreads();
+    }
+    if (tid == 0) *n_distinct = nd;
+    if (ntop < 1) return;
+    // 3. the most frequent patterns
+    for (int b = 0; b < 8; ++b) hist[b][tid] = 0u;
+    if (tid < 8) s_skip[tid] = 0;
+    __syncthreads();
+    for (int j = tid; j < nd; j += 256) {
+        const unsigned int at = di[j], cnt = (j + 1 < nd ? di[j + 1] : (unsigned int)S) - at;
+        const unsigned long long key = ((unsigned long long)(0xFFFFFFFFu - cnt) << 32) | at;
+        src[j] = key;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) atomicAdd(&hist[b][(unsigned int)(key >> (8 * b)) & 255u], 1u);
+    }
+    __syncthreads();
+    for (int b = 0; b < 8; ++b) if (hist[b][tid] == (unsigned int)nd) s_skip[b] = 1;
+    __syncthreads();
+    unsigned int *none_a = nullptr, *none_b = nullptr;
+    bnr_sort_passes<false>(nd, src, dst, none_a, none_b, hist, base, tmp, wcnt, s_skip);
+    __syncthreads();
+    for (int j = tid; j < min(ntop, nd); j += 256) {
+        const unsigned long long key = src[j];
+        top_count[j] = (long long)(0xFFFFFFFFu - (unsigned int)(key >> 32));
+        const unsigned long long *a = pat + (size_t)si[(unsigned int)key] * W;
+        for (int wd = 0; wd < W; ++wd) top_sets[(size_t)j * W + wd] = a[wd];
+    }
+}

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BNR_ABI_VERSION 14  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
+#define BNR_ABI_VERSION 15  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
                                5: + bnr_chain_create_typed, bnr_chain_create_from_matrices, bnr_device_synchronize; 6: + bnr_comm_info;
                                7: + option "xi_weights", bnr_host_xi_weight; 8: + bnr_chain_predict, bnr_chain_predict_from_matrices,
                                bnr_chain_loglik_stats, option "predict_block_rows"; 9: + bnr_chain_loo, bnr_psis_loo;
@@ -36,7 +36,8 @@ extern "C" {
                                bnr_host_pred_noise, option "summary_block_cols"; 11: + bnr_chain_loo_predict, bnr_chains_loo_predict,
                                bnr_psis_weights; 12: + bnr_chain_rank_diag, bnr_chains_rank_diag, bnr_rank_normalize, bnr_host_ndtri,
                                option "rank_block_cols"; 13: + bnr_chain_hdi, bnr_chains_hdi, bnr_hdi;
-                               14: + bnr_host_gig_attempts (all additive) */
+                               14: + bnr_host_gig_attempts; 15: + bnr_chain_inclusion, bnr_chains_inclusion,
+                               bnr_inclusion (all additive) */
 
 enum {
     BNR_OK = 0,
@@ -333,6 +334,32 @@ int bnr_chains_hdi(bnr_chain *const *chains, int32_t nchains, int32_t first_row,
                    double *upper, double *median, double *p_pos, double *p_neg);
 int bnr_hdi(int32_t device, int32_t m, int32_t S, const double *x, int32_t nprob, const double *probs, double *lower, double *upper, double *median,
             double *p_pos, double *p_neg);
+
+/* The joint posterior of the indicators (ABI 15) -- an ADDITION to the reference: which nodes are selected together, how many, and which node
+ * sets are the most probable, over the pooled window of nchains >= 1 chains of one device (S = nchains nsamp draws, chain by chain in the
+ * order passed, as for bnr_chains_hdi).  One call works on the S x B matrix z of 0/1 indicators:
+ *   which = 0: B = V, z_sv = (xi_v of draw s != 0), the node indicators;  which = 1: B = R, z_sr = (lambda_r of draw s != 0), the latent
+ *   dimensions in use.  The indicator is the IEEE comparison x != 0.0: -0 is zero, and a NaN counts as included.
+ *   The pattern of a draw is the integer P_s = sum_k z_sk 2^k, stored as W = ceil(B / 64) little-endian 64-bit words: bit k mod 64 of word
+ *   k div 64 is indicator k, the unused high bits are 0.
+ *   prob[B]           = #{s : z_sk} / S, the marginal inclusion probabilities (bit for bit bnr_chains_summary's prob_xi for which = 0);
+ *   joint[B x B]      = #{s : z_sk and z_sl} / S at joint[k B + l], the full symmetric co-inclusion matrix; its diagonal equals prob;
+ *   size_pmf[B + 1]   = #{s : popcount(P_s) = m} / S, m = 0 .. B: the distribution of the number of included indicators;
+ *   n_distinct        = the number of distinct patterns among the S draws;
+ *   top_sets[ntop W], top_count[ntop]: the ntop most frequent distinct patterns and their counts, by count descending, ties by the pattern
+ *   as an integer ascending; entries past n_distinct are all-zero words with count 0.
+ * Every output is an exact integer count, divided once by (double)S where a double is returned.  Every output may be NULL (not all of them):
+ * what is not asked for is not computed; top_sets and top_count come together and need ntop >= 1.
+ * Checks: those of bnr_chains_summary, which in {0, 1}, 0 <= ntop <= 256, top_sets and top_count both or neither, at most 4096 indicators.
+ * Runs eagerly on chains[0]'s stream and reads the trace rows in place; no result depends on the grid, the outputs requested or the call, bit
+ * for bit, and bnr_chain_inclusion is the pooled call with one chain.  Nothing of any chain is written.
+ * bnr_inclusion: the same for a caller's S x B matrix of bytes (host, row-major; a byte != 0 is 1), S >= 1, B >= 1.  DESIGN.md section 8. */
+int bnr_chain_inclusion(bnr_chain *chain, int32_t first_row, int32_t nsamp, int32_t which, int32_t ntop, double *prob, double *joint,
+                        double *size_pmf, int64_t *n_distinct, uint64_t *top_sets, int64_t *top_count);
+int bnr_chains_inclusion(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t which, int32_t ntop, double *prob,
+                         double *joint, double *size_pmf, int64_t *n_distinct, uint64_t *top_sets, int64_t *top_count);
+int bnr_inclusion(int32_t device, int32_t S, int32_t B, const uint8_t *z, int32_t ntop, double *prob, double *joint, double *size_pmf,
+                  int64_t *n_distinct, uint64_t *top_sets, int64_t *top_count);
 
 /* Effective sample size -- an ADDITION to the reference (which only has split-Rhat; north-star item "Rhat/ESS check").
  * bnr_chain_ess_stats: this chain's message over rows first_row .. first_row+nsamp-1: for both halves of the window (the
