@@ -8,5 +8,6 @@ from .api import (BNRPrediction, BNRSummary, ChainSet, Fit, LOO, LOOPredict, LOO
                   device_summary, device_predict_pooled, device_summary_pooled, generate_samples, psis_loo, psis_weights, device_loo_predict,
                   generate_samples_dbl, initialize_and_run, lower_triangle, return_psrf_VOI, run, setup_X,
                   allgather_stats, local_chain_ids, make_comm, shared_seed, RankDiagnose, RankDiagnostics, device_rank_diagnostics, rank_normalize,
-                  EdgeSelect, EdgeSelection, device_edge_selection, hdi, NodeSets, device_node_sets, inclusion)
+                  EdgeSelect, EdgeSelection, device_edge_selection, hdi, NodeSets, device_node_sets, inclusion,
+                  Stacking, ChainStacking, stacking_weights, wquantile, device_stack_chains, device_summary_stacked, device_predict_stacked)
 from .synthetic import make_synthetic                             # noqa: F401

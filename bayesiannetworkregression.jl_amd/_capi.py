@@ -95,6 +95,14 @@ _SIGS = {
     "bnr_chain_inclusion": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 6),
     "bnr_chains_inclusion": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 6),
     "bnr_inclusion": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32] + [_dp] * 6),
+    "bnr_stacking_weights": (C.c_int, [C.c_int32, C.c_int32, _dp, C.c_int32, C.c_double, _dp, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(C.c_int32)]),
+    "bnr_chains_stack": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_double, _dp, _dp, _dp, _dp,
+                                   C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
+    "bnr_chains_wsummary": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
+    "bnr_chains_wpredict": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, C.c_int32]
+                            + [_dp] * 4 + [C.c_uint64] + [_dp] * 2),
+    "bnr_wquantile": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp]),
     "bnr_comm_unique_id": (C.c_int, [C.POINTER(UniqueId)]),
     "bnr_comm_create_rccl": (C.c_int, [C.POINTER(UniqueId), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "bnr_comm_create_callback": (C.c_int, [C.c_int32, C.c_int32, ALLGATHER_CB, C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -849,6 +857,96 @@ def pooled_inclusion(chains, first_row, nsamp, which, ntop, fields=INCL_FIELDS):
     ntop, out = _incl_outputs(c0.R if which == 1 else c0.V, ntop, fields)
     check(c0.L.bnr_chains_inclusion(arr, len(chains), int(first_row), int(nsamp), int(which), ntop, *[_ptr(o) for o in out]))
     return _incl_result(out)
+
+
+# ------------------------------------------------------------------------------------------ chain stacking (ABI 16)
+STACK_MAX_CHAINS = 32
+WQUANTILE_FIELDS = ("mean", "lower", "upper")
+
+
+def stacking_weights_raw(lpd, max_iter=100000, gap_tol=1e-9):
+    """(weights, objective, gap, iterations) of bnr_stacking_weights for an n x K matrix of pointwise predictive log densities (no GPU)"""
+    a = np.ascontiguousarray(lpd, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError("lpd must be an n x K matrix (rows x chains)")
+    n, K = a.shape
+    w = np.empty(max(K, 1))
+    f, g, it = C.c_double(0.0), C.c_double(0.0), C.c_int32(0)
+    check(lib().bnr_stacking_weights(n, K, _ptr(a), int(max_iter), float(gap_tol), _ptr(w), C.byref(f), C.byref(g), C.byref(it)))
+    return w[:K], f.value, g.value, it.value
+
+
+def stack_weights_array(weights, K):
+    """chain weights as K float64 values (the library checks them)"""
+    w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if w.shape != (K,):
+        raise ValueError("need one weight per chain (%d), not %d" % (K, w.size))
+    return w
+
+
+def wquantile_raw(x, weights, nchains, k_lo, k_hi, device=0, fields=WQUANTILE_FIELDS):
+    """(mean, lower, upper) of every row of an m x (K nsamp) matrix under chain weights, on the device (bnr_wquantile): chain k's draws in
+    columns k nsamp .. (k + 1) nsamp - 1; an entry not named in `fields` is not requested and comes back as None"""
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    K = int(nchains)
+    if a.ndim != 2 or a.shape[0] < 1 or K < 1 or a.shape[1] < K or a.shape[1] % K:
+        raise ValueError("x must be an m x (nchains * nsamp) matrix with m, nsamp >= 1")
+    w = stack_weights_array(weights, K)
+    m, S = a.shape
+    out = [np.empty(m) if f in fields else None for f in WQUANTILE_FIELDS]
+    L = lib()
+    if _foreign_hip:
+        raise BnrError(BNR_ERR_HIP, _foreign_hip)
+    check(L.bnr_wquantile(int(device), m, K, S // K, _ptr(a), _ptr(w), int(k_lo), int(k_hi), *[_ptr(o) for o in out]))
+    return tuple(out)
+
+
+def chains_stack(chains, first_row, nsamp, r_eff=None, max_iter=100000, gap_tol=1e-9):
+    """(weights, elpd_chain K x n, pareto_k_chain K x n, elpd_stack n, gap, iterations): per-chain PSIS-LOO and the stacking weights
+    (bnr_chains_stack)"""
+    chains, arr = _pooled(chains)
+    n, K = chains[0].n, len(chains)
+    r = r_eff_array(r_eff, n)
+    w, el, kh, es = np.empty(K), np.empty((K, n)), np.empty((K, n)), np.empty(n)
+    g, it = C.c_double(0.0), C.c_int32(0)
+    check(chains[0].L.bnr_chains_stack(arr, K, int(first_row), int(nsamp), _ptr(r), int(max_iter), float(gap_tol), _ptr(w), _ptr(el), _ptr(kh), _ptr(es),
+                                       C.byref(g), C.byref(it)))
+    return w, el, kh, es, g.value, it.value
+
+
+def stacked_summary(chains, weights, first_row, nsamp, k_lo, k_hi):
+    """pooled_summary under chain weights (bnr_chains_wsummary)"""
+    chains, arr = _pooled(chains)
+    c0 = chains[0]
+    w = stack_weights_array(weights, len(chains))
+    mean, lo, hi, pxi = np.empty(c0.q), np.empty(c0.q), np.empty(c0.q), np.empty(c0.V)
+    check(c0.L.bnr_chains_wsummary(arr, len(chains), _ptr(w), int(first_row), int(nsamp), int(k_lo), int(k_hi), _ptr(mean), _ptr(lo), _ptr(hi), _ptr(pxi)))
+    return mean, lo, hi, pxi
+
+
+def stacked_predict(chains, weights, X, first_row, nsamp, k_lo, k_hi, y=None, x_transform=False, pred_seed=None):
+    """pooled_predict under chain weights for a model matrix (bnr_chains_wpredict): (mean, lower, upper, lpd, pred_lower, pred_upper) per row"""
+    chains, arr = _pooled(chains)
+    c0 = chains[0]
+    w = stack_weights_array(weights, len(chains))
+    xi = X if isinstance(X, XInput) else XInput(X, x_transform)
+    if xi.from_matrices:
+        raise ValueError("the stacked prediction takes a model matrix (n x q), not adjacency matrices")
+    if xi.q != c0.q:
+        raise ValueError("the new rows have %d edge columns, the chain %d" % (xi.q, c0.q))
+    m = xi.n
+    yf = None
+    if y is not None:
+        yf = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        if yf.shape != (m,):
+            raise ValueError("y must have one entry per new row (%d), not %d" % (m, yf.size))
+    mean, lo, hi = np.empty(m), np.empty(m), np.empty(m)
+    lpd = np.empty(m) if yf is not None else None
+    plo, phi = (np.empty(m), np.empty(m)) if pred_seed is not None else (None, None)
+    check(c0.L.bnr_chains_wpredict(arr, len(chains), _ptr(w), int(first_row), int(nsamp), m, _ptr(xi.data), xi.dtype_code, _ptr(yf), int(k_lo), int(k_hi),
+                                   _ptr(mean), _ptr(lo), _ptr(hi), _ptr(lpd), C.c_uint64((0 if pred_seed is None else int(pred_seed)) & (2**64 - 1)),
+                                   _ptr(plo), _ptr(phi)))
+    return mean, lo, hi, lpd, plo, phi
 
 
 class Comm:

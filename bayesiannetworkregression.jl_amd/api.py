@@ -24,6 +24,8 @@ Julia is not available in this image, so the thin host layer a Julia user would 
                                                hdi, device_edge_selection, _host_hdi
                                                joint posterior of the node indicators: NodeSets, inclusion, device_node_sets,
                                                _host_node_sets, _host_inclusion
+                                               chain stacking for chains that do not mix: Stacking / ChainStacking, stacking_weights,
+                                               wquantile, device_stack_chains, device_summary_stacked, device_predict_stacked, _host_*
   lower_triangle / create_lower_tri / setup_X!  utils.jl:17-57, gibbs.jl:239-247
 
 All sampling runs on the GPU through libbnr_hip.so; this file holds only the schedule logic (chain fan-out,
@@ -104,6 +106,7 @@ class Results:
     rank_diag: "RankDiagnostics" = None   # filled on request (rank_diagnostics=True): rank-normalised R-hat, bulk / tail ESS and MCSE over every chain (see RankDiagnose)
     edge_selection: "EdgeSelection" = None   # filled on request (edge_selection=True): HDIs, sign probabilities and the selected edges over every chain (see EdgeSelect)
     node_sets: "NodeSets" = None     # filled on request (node_sets=True): co-inclusion, model size, the most probable node sets and the active dimensions over every chain (see NodeSets)
+    stacking: "ChainStacking" = None   # filled on request (stack_chains=True): every chain's own PSIS-LOO, the stacking weights of the chains and the summaries under them (see Stacking)
     stat_chains: int = None          # how many chains the device statistics above (summary_device, prediction, waic, loo, loo_predictive) cover: 1 (chain 1's window), or
                                      # every chain of the fit with pool_chains=True; None when the fit computed none
 
@@ -1205,6 +1208,338 @@ def LOOPredict(results, X=None, y=None, x_transform=True, r_eff=None, interval=N
     return _host_loo_predict([results.state], X, y, results.burn_in, results.sampled, 95 if interval is None else interval, x_transform, r_eff)
 
 
+# ------------------------------------------------------------------------------------------ chain stacking (an addition to the reference)
+# Posterior statistics of chains that do not mix (Yao, Vehtari & Gelman 2022, "Stacking for non-mixing Bayesian computations", JMLR 23;
+# include/bnr_hip.h, ABI 16; DESIGN.md section 8, "Chain stacking"): every chain's own PSIS-LOO pointwise predictive density, the chain weights
+# on the simplex that maximise the leave-one-out log score of the mixture, and the summaries and predictions under those weights.  The _host_*
+# functions restate the definitions in numpy over fetched tables: the fallback of Stacking and the yardstick of the tests.
+STACK_MAX_CHAINS = _capi.STACK_MAX_CHAINS
+
+
+@dataclass
+class ChainStacking:
+    """weights: the stacking weight of every chain (they sum to 1); elpd_chain: every chain's own PSIS-LOO elpd (K totals), elpd_chain_i /
+    pareto_k: its pointwise values and Pareto k-hat (K x n), n_high_k: per chain the rows whose k-hat is above khat_threshold; elpd_stack: the
+    leave-one-out log score of the weighted mixture summed over the rows used, elpd_stack_i pointwise (NaN for a row whose elpd is not finite in
+    some chain: those rows are left out, n_used counts the rest), se = sqrt(n_used Var_i(elpd_stack_i)); elpd_uniform: the same score with
+    every weight 1 / K (what pooling the chains amounts to); gap: the bound max_k g_k - 1 on the distance of the weights' objective from the
+    optimum (per row), iterations: the updates the solver applied; summary: device_summary's dict under the weights, prediction: a BNRPrediction
+    under the weights (where requested)."""
+    weights: np.ndarray
+    elpd_chain: np.ndarray
+    elpd_chain_i: np.ndarray
+    pareto_k: np.ndarray
+    n_high_k: np.ndarray
+    elpd_stack: float
+    se: float
+    elpd_uniform: float
+    gap: float
+    iterations: int
+    elpd_stack_i: np.ndarray = None
+    n_used: int = None
+    khat_threshold: float = None
+    chains: int = None
+    draws: int = None
+    summary: dict = None
+    prediction: BNRPrediction = None
+
+
+def _stack_solver_args(max_iter, gap_tol):
+    max_iter, gap_tol = int(max_iter), float(gap_tol)
+    if max_iter < 1:
+        raise ValueError("max_iter must be >= 1")
+    if not (math.isfinite(gap_tol) and gap_tol > 0):
+        raise ValueError("gap_tol must be positive and finite")
+    return max_iter, gap_tol
+
+
+def stacking_weights(lpd, max_iter=100000, gap_tol=1e-9):
+    """The stacking weights of K chains (or models) from the n x K matrix of their pointwise predictive log densities (bnr_stacking_weights;
+    host code, no GPU): dict with weights, objective = (1/n) sum_i log sum_k w_k exp(lpd_ik), gap (objective is within gap of the optimum)
+    and iterations."""
+    max_iter, gap_tol = _stack_solver_args(max_iter, gap_tol)
+    w, f, g, it = _capi.stacking_weights_raw(lpd, max_iter, gap_tol)
+    return dict(weights=w, objective=f, gap=g, iterations=it)
+
+
+def _host_stacking_weights(lpd, max_iter=100000, gap_tol=1e-9, dtype=np.float64):
+    """bnr_stacking_weights restated in numpy (in `dtype`: the tests run it in long double): the dict of stacking_weights"""
+    a = np.ascontiguousarray(lpd, dtype=dtype)
+    if a.ndim != 2 or a.shape[0] < 1 or not 1 <= a.shape[1] <= STACK_MAX_CHAINS:
+        raise ValueError("lpd must be an n x K matrix with n >= 1 and 1 <= K <= %d" % STACK_MAX_CHAINS)
+    if np.isnan(a).any() or (a == np.inf).any() or (a.max(axis=1) == -np.inf).any():
+        raise ValueError("lpd must hold no NaN, no +Inf and no row that is -Inf in every chain")
+    max_iter, gap_tol = _stack_solver_args(max_iter, gap_tol)
+    n, K = a.shape
+    mx = a.max(axis=1)
+    p = np.exp(a - mx[:, None])
+    w = np.full(K, dtype(1) / dtype(K), dtype=dtype)
+    it = 0
+    while True:
+        d = p @ w
+        g = (p / d[:, None]).sum(axis=0) / n
+        gap = g.max() - 1
+        if gap <= gap_tol or it == max_iter:
+            break
+        w = w * g
+        w = w / w.sum()
+        it += 1
+    return dict(weights=w, objective=(mx + np.log(d)).sum() / n, gap=gap, iterations=it)
+
+
+def _order_key(x):
+    """the order of the summaries as 64-bit keys (bnr_key_of): numbers by value with -0 below +0, every NaN on top"""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    u = x.view(np.uint64)
+    top = np.uint64(1) << np.uint64(63)
+    return np.where(np.isnan(x), ~np.uint64(0), np.where(u & top != 0, ~u, u | top))
+
+
+def _order_key_inv(k):
+    top = np.uint64(1) << np.uint64(63)
+    k = np.ascontiguousarray(k, dtype=np.uint64)
+    return np.where(k & top != 0, k & ~top, ~k).view(np.float64)
+
+
+def _strided_mean(x):
+    """the mean along the last axis as the summary kernels add it: 256 strided partial sums, an 8-level tree, one division"""
+    x = np.asarray(x, dtype=np.float64)
+    n = x.shape[-1]
+    red = np.zeros(x.shape[:-1] + (256,))
+    with np.errstate(all="ignore"):
+        for i0 in range(0, n, 256):
+            blk = x[..., i0:i0 + 256]
+            red[..., :blk.shape[-1]] = red[..., :blk.shape[-1]] + blk
+        w = 128
+        while w > 0:
+            red[..., :w] = red[..., :w] + red[..., w:2 * w]
+            w //= 2
+        return red[..., 0] / n
+
+
+def _wquantile_args(x, weights, nchains):
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    a = a[None, :] if a.ndim == 1 else a
+    K = int(nchains)
+    if a.ndim != 2 or a.shape[0] < 1 or not 1 <= K <= STACK_MAX_CHAINS or a.shape[1] < K or a.shape[1] % K:
+        raise ValueError("x must be an m x (nchains * nsamp) matrix with m, nsamp >= 1 and 1 <= nchains <= %d" % STACK_MAX_CHAINS)
+    w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+    if w.shape != (K,):
+        raise ValueError("need one weight per chain (%d), not %d" % (K, w.size))
+    if not (np.all(np.isfinite(w)) and np.all(w >= 0) and np.any(w > 0)):
+        raise ValueError("weights must be finite and >= 0, one of them > 0")
+    tot = 0.0
+    for v in w:
+        tot = tot + v
+    if not abs(tot - 1.0) <= 1e-9:
+        raise ValueError("weights must sum to 1 (within 1e-9), not %r" % tot)
+    return a, w, K
+
+
+def _host_wquantile(x, weights, nchains, k_lo, k_hi):
+    """bnr_wquantile restated in numpy for the rows of an m x (K nsamp) matrix (chain k's draws in columns k nsamp ..): dict of mean, lower,
+    upper (m,).  mean = sum_k w_k m_k (k ascending from 0.0); the statistic of rank r: T = r / K, W(x) = sum_k w_k #{draws of chain k with key
+    <= key(x)} (k ascending from 0.0), the draw of the smallest key with W >= T, else the largest draw of the chains with w_k > 0; a row with
+    a NaN is NaN throughout."""
+    a, w, K = _wquantile_args(x, weights, nchains)
+    m, S = a.shape
+    ns = S // K
+    for r in (k_lo, k_hi):
+        if not 1 <= int(r) <= S:
+            raise ValueError("order statistics must be between 1 and nchains * nsamp")
+    seg = a.reshape(m, K, ns)
+    with np.errstate(all="ignore"):
+        mk = _strided_mean(seg)
+        mean = np.zeros(m)
+        for k in range(K):
+            mean = mean + w[k] * mk[:, k]
+    bad = np.isnan(a).any(axis=1)
+    mean = np.where(bad, np.nan, mean)
+    key = _order_key(a)
+    order = np.argsort(key, axis=1, kind="stable")
+    skey = np.take_along_axis(key, order, axis=1)
+    chain = order // ns
+    last = np.ones((m, S), dtype=bool)                               # the last position of every run of equal keys
+    last[:, :-1] = skey[:, 1:] != skey[:, :-1]
+    pos = np.where(last, np.arange(S)[None, :], S)
+    run_end = np.minimum.accumulate(pos[:, ::-1], axis=1)[:, ::-1]   # ... for every position
+    W = np.zeros((m, S))
+    for k in range(K):
+        c = np.take_along_axis(np.cumsum(chain == k, axis=1), run_end, axis=1)
+        W = W + w[k] * c.astype(np.float64)
+    pk = _order_key(np.where((w > 0)[None, :, None], seg, -np.inf).reshape(m, S)).max(axis=1)     # the largest key of the chains with w_k > 0
+    out = {}
+    for name, r in (("lower", k_lo), ("upper", k_hi)):
+        T = np.float64(int(r)) / np.float64(K)
+        hit = W >= T
+        first = np.argmax(hit, axis=1)
+        kk = np.where(hit.any(axis=1), skey[np.arange(m), first], pk)
+        out[name] = np.where(bad, np.nan, _order_key_inv(kk))
+    return dict(mean=mean, lower=out["lower"], upper=out["upper"])
+
+
+def wquantile(x, weights, nchains, interval=95, device=None):
+    """The weighted mean and the interval% order statistics of every row of an m x (nchains nsamp) matrix (rows x draws, chain k's draws in
+    columns k nsamp .. (k + 1) nsamp - 1) under chain weights, on the GPU (bnr_wquantile): dict with mean, lower, upper (m,) and interval"""
+    a, w, K = _wquantile_args(x, weights, nchains)
+    lw, hi = _summary_ranks(a.shape[1], interval)
+    mean, lo, up = _capi.wquantile_raw(a, w, K, lw, hi, 0 if device is None else int(device))
+    return dict(mean=mean, lower=lo, upper=up, interval=interval)
+
+
+def _weighted_lse(v, w):
+    """log sum_{k: w_k > 0} w_k exp(v_k) along axis 0, the largest such v_k taken out, k ascending"""
+    v, w = np.asarray(v, dtype=np.float64), np.asarray(w, dtype=np.float64)
+    pos = w > 0
+    with np.errstate(all="ignore"):
+        M = np.max(v[pos], axis=0)
+        s = np.zeros(v.shape[1:])
+        for k in np.flatnonzero(pos):
+            s = s + w[k] * np.exp(v[k] - M)
+        return M + np.log(s)
+
+
+def _stacking(weights, el, kh, gap, iterations, nsamp):
+    """ChainStacking from the weights and the per-chain pointwise numbers (K x n)"""
+    w, el, kh = np.asarray(weights, dtype=np.float64), np.asarray(el, dtype=np.float64), np.asarray(kh, dtype=np.float64)
+    K = el.shape[0]
+    used = np.isfinite(el).all(axis=0)
+    es = np.full(el.shape[1], np.nan)
+    eu = np.full(el.shape[1], np.nan)
+    if used.any():
+        es[used] = _weighted_lse(el[:, used], w)
+        eu[used] = _weighted_lse(el[:, used], np.full(K, 1.0 / K))
+    thr = -math.inf if nsamp == 1 else min(1.0 - 1.0 / math.log10(nsamp), 0.7)
+    nu = int(used.sum())
+    return ChainStacking(weights=w, elpd_chain=el.sum(axis=1), elpd_chain_i=el, pareto_k=kh, n_high_k=(kh > thr).sum(axis=1),
+                         elpd_stack=float(np.sum(es[used])), se=float(math.sqrt(nu * np.var(es[used]))) if nu else math.nan,
+                         elpd_uniform=float(np.sum(eu[used])), gap=float(gap), iterations=int(iterations), elpd_stack_i=es, n_used=nu,
+                         khat_threshold=thr, chains=K, draws=K * int(nsamp))
+
+
+def device_stack_chains(chains, nburn, nsamp, r_eff=None, max_iter=100000, gap_tol=1e-9):
+    """Every chain's own PSIS-LOO over rows nburn+1 .. nburn+nsamp and the stacking weights of the chains, on the GPU (bnr_chains_stack)
+    -> ChainStacking"""
+    chains = list(chains)
+    max_iter, gap_tol = _stack_solver_args(max_iter, gap_tol)
+    w, el, kh, _es, gap, it = _capi.chains_stack(chains, nburn + 1, nsamp, r_eff, max_iter, gap_tol)
+    return _stacking(w, el, kh, gap, it, nsamp)
+
+
+def _host_stack_chains(tables, X, y, nburn, nsamp, x_transform=False, r_eff=None, max_iter=100000, gap_tol=1e-9):
+    """device_stack_chains restated in numpy over the fetched tables of the same chains and the training X, y: _psis_host per chain, then
+    _host_stacking_weights over the rows that are finite in every chain"""
+    tables = list(tables)
+    if not 1 <= len(tables) <= STACK_MAX_CHAINS:
+        raise ValueError("need between 1 and %d tables" % STACK_MAX_CHAINS)
+    Xd = _dense_rows(_new_rows(X, x_transform, tables[0]["gamma"].shape[1], y))
+    el, kh = [], []
+    for t in tables:
+        _lpd, e, k = _psis_host(_host_loglik(t, Xd, y, nburn, nsamp), r_eff)
+        el.append(e)
+        kh.append(k)
+    el, kh = np.array(el), np.array(kh)
+    used = np.isfinite(el).all(axis=0)
+    K = len(tables)
+    if used.any():
+        r = _host_stacking_weights(el[:, used].T, max_iter, gap_tol)
+        w, gap, it = r["weights"], r["gap"], r["iterations"]
+    else:
+        w, gap, it = np.full(K, 1.0 / K), math.nan, 0
+    return _stacking(w, el, kh, gap, it, nsamp)
+
+
+def device_summary_stacked(chains, weights, nburn, nsamp, interval=95):
+    """device_summary_pooled under chain weights (bnr_chains_wsummary): the same ranks of the K nsamp pooled draws, read off the weighted
+    distribution"""
+    chains = list(chains)
+    lw, hi = _summary_ranks(nsamp * len(chains), interval)
+    mean, lo, up, pxi = _capi.stacked_summary(chains, weights, nburn + 1, nsamp, lw, hi)
+    return dict(interval=interval, estimate=mean, lower_bound=lo, upper_bound=up, probability=pxi, weights=np.array(weights, dtype=np.float64))
+
+
+def _host_summary_stacked(tables, weights, nburn, nsamp, interval=95):
+    """device_summary_stacked from the fetched tables (_host_wquantile on the windows side by side)"""
+    tables = list(tables)
+    K = len(tables)
+    lw, hi = _summary_ranks(nsamp * K, interval)
+    q = tables[0]["gamma"].shape[1]
+    cols = np.concatenate([np.concatenate([t["gamma"][nburn:nburn + nsamp, :, 0], t["xi"][nburn:nburn + nsamp, :, 0]], axis=1) for t in tables], axis=0)
+    h = _host_wquantile(cols.T, weights, K, lw, hi)
+    return dict(interval=interval, estimate=h["mean"][:q], lower_bound=h["lower"][:q], upper_bound=h["upper"][:q], probability=h["mean"][q:],
+                weights=np.array(weights, dtype=np.float64))
+
+
+def _stacked_rows(X_new, x_transform, q, y_new):
+    """the new rows of a stacked prediction as a model matrix (the entry point takes no adjacency matrices: they are vectorised here)"""
+    xi = _new_rows(X_new, x_transform, q, y_new)
+    return XInput(_dense_rows(xi), False) if xi.from_matrices else xi
+
+
+def device_predict_stacked(chains, weights, nburn, nsamp, X_new, y_new=None, interval=95, pred_seed=0, predict_observation=True, x_transform=False):
+    """device_predict_pooled under chain weights (bnr_chains_wpredict): the weighted mean and order statistics of the mean response, with y_new
+    the lpd of the weighted mixture of the chains' predictive densities, with predict_observation the predictive bounds (the noise of
+    device_predict_pooled); no PIT"""
+    chains = list(chains)
+    if not chains:
+        raise ValueError("need at least one chain")
+    xi = _stacked_rows(X_new, x_transform, chains[0].q, y_new)
+    S = nsamp * len(chains)
+    lw, hi = _summary_ranks(S, interval)
+    mean, lo, up, lpd, plo, phi = _capi.stacked_predict(chains, weights, xi, nburn + 1, nsamp, lw, hi, y=y_new,
+                                                        pred_seed=pred_seed if predict_observation else None)
+    return _prediction(mean, lo, up, interval, lpd, None, plo, phi, None, S)
+
+
+def _host_predict_stacked(tables, weights, X_new, y_new=None, nburn=0, nsamp=None, interval=95, x_transform=False, pred_seed=None, eta=None):
+    """device_predict_stacked from the fetched tables.  eta: the m x (K nsamp) matrix of mean responses to work on instead of the float64
+    product of the tables (the tests pass the device's own, or an exact one)."""
+    tables = list(tables)
+    K = len(tables)
+    xi = _stacked_rows(X_new, x_transform, tables[0]["gamma"].shape[1], y_new)
+    S = nsamp * K
+    lw, hi = _summary_ranks(S, interval)
+    X = _dense_rows(xi)
+    if eta is None:
+        eta = np.concatenate([_host_eta(t, X, nburn, nsamp) for t in tables], axis=1)
+    h = _host_wquantile(eta, weights, K, lw, hi)
+    lpd = None
+    if y_new is not None:
+        lpd = _weighted_lse(np.array([_host_pointwise(t, X, y_new, nburn, nsamp)[0] for t in tables]), weights)
+    plo = phi = None
+    if pred_seed is not None:
+        tau2 = np.concatenate([t["tau2"][nburn:nburn + nsamp, 0, 0] for t in tables])
+        hp = _host_wquantile(eta + np.sqrt(tau2)[None, :] * _capi.host_pred_noise(pred_seed, 0, S, 0, xi.n), weights, K, lw, hi)
+        plo, phi = hp["lower"], hp["upper"]
+    return _prediction(h["mean"], h["lower"], h["upper"], interval, lpd, None, plo, phi, None, S)
+
+
+def Stacking(results, X=None, y=None, x_transform=True, tables=None, r_eff=None):
+    """The chain stacking of a fit -> ChainStacking.  Uses the GPU's numbers when the fit carried them (stack_chains=True); otherwise restates
+    them on the host (_host_stack_chains) over the fetched tables of the chains -- `tables`, or results.state where that is a list of tables --
+    with the training X, y passed in."""
+    if results.stacking is not None and r_eff is None:
+        return results.stacking
+    if tables is None and isinstance(results.state, (list, tuple)):
+        tables = results.state
+    if tables is None or len(tables) < 2 or X is None or y is None:
+        raise ValueError("Stacking needs Fit(..., stack_chains=True), or the state tables of at least two chains together with the training X and y")
+    return _host_stack_chains(tables, X, y, results.burn_in, results.sampled, x_transform, r_eff)
+
+
+def _stack_request(stack_chains, num_chains):
+    """Fit's stack_chains checked before any sampling: at least two chains, and like pool_chains every chain of the fit on this rank"""
+    if not stack_chains:
+        return False
+    if int(num_chains) < 2:
+        raise ValueError("stack_chains needs num_chains >= 2: one chain has nothing to be weighted against")
+    if int(num_chains) > STACK_MAX_CHAINS:
+        raise ValueError("stack_chains takes at most %d chains" % STACK_MAX_CHAINS)
+    if _rank_world()[1] > 1:
+        raise ValueError("stack_chains needs every chain of the fit on one rank: the chains are spread over %d torch.distributed ranks" % _rank_world()[1])
+    return True
+
+
 # ------------------------------------------------------------------------------------------ chain placement
 def _dist():
     """torch.distributed if THE CALLER has imported and initialised it, else None.  Never imports torch itself: a process group can only
@@ -1430,7 +1765,8 @@ def return_psrf_VOI(chainset, nburn, nsamp, fetch_state=True, summary_interval=N
 
 
 def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None, predict=None, waic=False, loo=False, loo_r_eff=None,
-            pool_chains=False, predict_observation=False, pred_seed=0, loo_predict=None, rank_diag=False, edge_sel=None, node_sets=None):
+            pool_chains=False, predict_observation=False, pred_seed=0, loo_predict=None, rank_diag=False, edge_sel=None, node_sets=None,
+            stack=False):
     """The Results a fit returns: chain 1's table (states[1], gibbs.jl:788) and/or its Summary statistics from the device; predict =
     (new rows, their y or None, interval), waic=True and loo=True add the prediction, WAIC and PSIS-LOO computed on the device over the
     same window.  pool_chains: those statistics over the pooled windows of all chains of the fit (one rank holds them all);
@@ -1438,7 +1774,18 @@ def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None, pre
     loo_predict = (training y, interval): the LOO predictive checks (Results.loo_predictive), and Results.loo from the same call.
     rank_diag: the rank-normalised diagnostics over every chain of the fit (Results.rank_diag; ess_max_lag, where positive, is their lag window).
     edge_sel = (hdi_prob, fdr): the HDIs, sign probabilities and selected edges over every chain of the fit (Results.edge_selection).
-    node_sets = the number of top node sets: the joint posterior of the node indicators over every chain of the fit (Results.node_sets)."""
+    node_sets = the number of top node sets: the joint posterior of the node indicators over every chain of the fit (Results.node_sets).
+    stack: the chain stacking over every chain of the fit (Results.stacking), with summary_interval its summary and with predict its
+    prediction under the weights; what pool_chains or the default return is not changed by it."""
+    if stack:
+        chains = [chainset.chains[c] for c in chainset.ids]
+        st = device_stack_chains(chains, res.burn_in, res.sampled, loo_r_eff)
+        if summary_interval is not None:
+            st.summary = device_summary_stacked(chains, st.weights, res.burn_in, res.sampled, summary_interval)
+        if predict is not None:
+            st.prediction = device_predict_stacked(chains, st.weights, res.burn_in, res.sampled, predict[0], predict[1], predict[2], pred_seed,
+                                                   predict_observation=predict_observation)
+        res.stacking = st
     if node_sets is not None:
         res.node_sets = device_node_sets([chainset.chains[c] for c in chainset.ids], res.burn_in, res.sampled, node_sets)
     if edge_sel is not None:
@@ -1593,7 +1940,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                      purge_burn=None, device=None, _keep=None, return_state=True, summary_interval=None, ess_max_lag=None,
                      xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
                      pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
-                     hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10):
+                     hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False):
     """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
     xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
     xi_weights_code(xi_weights)
@@ -1608,6 +1955,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
     rd_req = _rank_diag_request(rank_diagnostics, nsamp, ess_max_lag)
     es_req = _edge_selection_request(edge_selection, hdi_prob, fdr)
     ns_req = _node_sets_request(node_sets, top_sets)
+    sk_req = _stack_request(stack_chains, num_chains)
     _capi.r_eff_array(loo_r_eff, X_new.n)              # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
@@ -1651,7 +1999,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
     print("R = %s nu=%s nburn= %d nsamp = %d" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f\n" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
     res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff, pool_chains, predict_observation,
-                  seed_eff if pred_seed is None else pred_seed, lp_req, rd_req, es_req, ns_req)
+                  seed_eff if pred_seed is None else pred_seed, lp_req, rd_req, es_req, ns_req, sk_req)
     if _keep is None:
         cs.close()
     return res
@@ -1662,7 +2010,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                          seed=None, purge_burn=None, device=None, return_state=True, summary_interval=None, ess_max_lag=None,
                          xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
                          pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
-                         hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10):
+                         hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False):
     """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
     xi_weights_code(xi_weights)
     if nu == R:
@@ -1676,6 +2024,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
     rd_req = _rank_diag_request(rank_diagnostics, nsamp, ess_max_lag)
     es_req = _edge_selection_request(edge_selection, hdi_prob, fdr)
     ns_req = _node_sets_request(node_sets, top_sets)
+    sk_req = _stack_request(stack_chains, num_chains)
     _capi.r_eff_array(loo_r_eff, X_new.n)              # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
@@ -1721,7 +2070,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
     print("\nR = %s nu=%s nburn= %d nsamp = %d\n" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.4f. Max PSRF Gamma: %.4f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
     res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff, pool_chains, predict_observation,
-                  seed_eff if pred_seed is None else pred_seed, lp_req, rd_req, es_req, ns_req)
+                  seed_eff if pred_seed is None else pred_seed, lp_req, rd_req, es_req, ns_req, sk_req)
     cs.close()
     return res
 
@@ -1731,7 +2080,7 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
         purge_burn=None, filename="parameters.log", device=None, return_state=True, summary_interval=None, ess_max_lag=None,
         xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
         pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
-        hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10):
+        hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False):
     """Fit! (gibbs.jl:725-751).  The `V` keyword is accepted and ignored, as in the reference.
     Extensions: summary_interval=95 computes Summary's statistics on the GPU (Results.summary_device);
     return_state=False then leaves the (large) state table on the device and frees it; ess_max_lag=0 (default lag
@@ -1755,6 +2104,10 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     node_sets=True adds the joint posterior of the node indicators: the co-inclusion matrix, the distribution of the number of selected nodes,
     the top_sets most probable node sets (the first is the MAP model) and the distribution of the number of active latent dimensions, computed
     on the GPU from the resident traces over every chain of the fit (Results.node_sets, see NodeSets); every chain must live on this rank.
+    stack_chains=True (num_chains >= 2, every chain on this rank) adds the chain stacking of Yao, Vehtari & Gelman (2022) for chains that do
+    not mix: every chain's own PSIS-LOO, the chain weights that maximise the leave-one-out log score of the mixture, and -- with
+    summary_interval / predict_X -- the Summary statistics and the prediction under those weights (Results.stacking, see Stacking); what
+    pool_chains or the default return is unchanged.
     parameters.log keeps the reference's lines only."""
     xi_weights_code(xi_weights)
     _pooled_request(pool_chains, predict_observation, predict_X)
@@ -1762,6 +2115,7 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     _rank_diag_request(rank_diagnostics)
     _edge_selection_request(edge_selection, hdi_prob, fdr)
     _node_sets_request(node_sets, top_sets)
+    _stack_request(stack_chains, num_chains)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
         with open(filename, "w") as f:
@@ -1782,7 +2136,7 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                                     waic=waic, loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation,
                                     pred_seed=pred_seed, loo_predict=loo_predict, rank_diagnostics=rank_diagnostics,
                                     edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr,
-                                    node_sets=node_sets, top_sets=top_sets)
+                                    node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
@@ -1790,4 +2144,4 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                             xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic,
                             loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed,
                             loo_predict=loo_predict, rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr,
-                            node_sets=node_sets, top_sets=top_sets)
+                            node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains)

@@ -1,7 +1,7 @@
 // bnr_analysis.hip -- the posterior analysis behind the C ABI (include/bnr_hip.h) over the kernels in bnr_analysis_kernels.h: Summary, rank-normalised
 // diagnostics, highest-density intervals, posterior prediction, log-likelihood statistics, PSIS-LOO and its predictive checks.  A translation unit and
 // so a gfx950 code object of its own: nothing added here can move a kernel of the sweep (bnr_hip.hip), whose speed depends on where its kernels lie.
-// k_fetch_cols, k_summary and k_acov stay with the sweep kernels and are launched through bnr_internal.h.
+// k_fetch_cols, k_summary, k_acov and k_wsummary (k_summary's companion of ABI 16) stay with the sweep kernels and are launched through bnr_internal.h.
 #include "bnr_internal.h"
 #include "bnr_analysis_kernels.h"
 
@@ -593,6 +593,8 @@ struct pred_stages {
     double *pit = nullptr;                                         // k_pred_pit: the PIT of the observed responses (needs yd)
     unsigned long long seed = 0;                                   // k_pred_noise with `seed`, then a second k_summary: the k_lo-th / k_hi-th
     double *pred_lower = nullptr, *pred_upper = nullptr;           // smallest draw of a new observation (both or none; overwrites E)
+    // chain stacking (ABI 16): with wt both summaries are k_wsummary under these chain weights (the ranks k_lo / k_hi over K)
+    const bnr_wsum_weights *wt = nullptr;
 };
 // k_psis: the sorted tail, 16 bytes per entry for up to BNR_PSIS_MAX_TAIL entries; k_psis_w: 12 bytes per entry.  On the current device, in front of the
 // first launch of either (cheap enough for once per call)
@@ -664,7 +666,9 @@ static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, 
                 hipLaunchKernelGGL(HIP_KERNEL_NAME(k_predict<1>), dim3((nsamp + 127) / 128, 1), dim3(256), 0, st, Xd + i0, ldx, q16,
                                    (const double *)dk.trace, dk.rowlen, dk.o_gamma, first_row - 1, nsamp, mr, E + (size_t)k * nsamp, S);
         }
-        if (sg.mean)
+        if (sg.mean && sg.wt)
+            launch_wsummary(st, mr, E, S, nsamp, nc, *sg.wt, mr, sg.k_lo, sg.k_hi, sg.mean + i0, sg.lower + i0, sg.upper + i0);
+        else if (sg.mean)
             launch_summary(st, mr, E, (int)S, mr, sg.k_lo, sg.k_hi, sg.mean + i0, sg.lower + i0, sg.upper + i0);
         if (yd && sg.lpd)
             hipLaunchKernelGGL(k_pred_loglik, dim3(mr), dim3(256), 0, st, (const double *)E, (int)S, yd + i0, (const double *)tau2,
@@ -679,7 +683,8 @@ static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, 
         if (sg.pred_lower) {                           // last: the block's E becomes draws of new observations in place
             const int gx = (int)((S + 255) / 256), gy = std::max(1, std::min(mr, 8192 / gx));
             hipLaunchKernelGGL(k_pred_noise, dim3(gx, gy), dim3(256), 0, st, E, S, (int)S, mr, i0, (const double *)tau2, sg.seed);
-            launch_summary(st, mr, E, (int)S, mr, sg.k_lo, sg.k_hi, pmean + i0, sg.pred_lower + i0, sg.pred_upper + i0);
+            if (sg.wt) launch_wsummary(st, mr, E, S, nsamp, nc, *sg.wt, mr, sg.k_lo, sg.k_hi, pmean + i0, sg.pred_lower + i0, sg.pred_upper + i0);
+            else launch_summary(st, mr, E, (int)S, mr, sg.k_lo, sg.k_hi, pmean + i0, sg.pred_lower + i0, sg.pred_upper + i0);
         }
     }
     return check_launch("k_predict");
@@ -999,4 +1004,267 @@ int bnr_psis_weights(int32_t device, int32_t m, int32_t nsamp, const double *log
 {
     if (!loglik || !log_weights) return fail(BNR_ERR_BAD_ARG, "NULL argument");
     return psis_call(device, m, nsamp, loglik, r_eff, log_weights, nullptr, elpd_loo, pareto_k);
+}
+
+// ------------------------------------------------------------------------------------------ chain stacking (ABI 16): include/bnr_hip.h
+// The stacking weights of K chains from their pointwise predictive log densities (Yao, Vehtari & Gelman 2022): the maximiser over the simplex of
+// f(w) = (1 / n) sum_i log sum_k w_k exp(lpd_ik), by the multiplicative (EM) fixed point w <- w o g, g_k = (1 / n) sum_i p_ik / sum_j w_j p_ij,
+// p_ik = exp(lpd_ik - max_k lpd_ik), from w = 1 / K; after every update w is divided by its sum (1 up to rounding: sum_k w_k g_k = 1), so
+// that round-off does not accumulate over thousands of updates.  f is concave, so max_k g_k - 1 bounds f(w*) - f(w) whatever produced w: the
+// iteration stops when it is <= gap_tol or after max_iter updates.  Pure host code; every sum in index order.
+int bnr_stacking_weights(int32_t n, int32_t K, const double *lpd, int32_t max_iter, double gap_tol, double *weights, double *objective, double *gap,
+                         int32_t *iters)
+{
+    if (!lpd || !weights) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (n < 1) return fail(BNR_ERR_BAD_ARG, "need n >= 1 rows");
+    if (K < 1 || K > BNR_STACK_MAX_CHAINS) return fail(BNR_ERR_BAD_ARG, "need 1 <= K <= 32 chains");
+    if (max_iter < 1) return fail(BNR_ERR_BAD_ARG, "need max_iter >= 1");
+    if (!std::isfinite(gap_tol) || !(gap_tol > 0.0)) return fail(BNR_ERR_BAD_ARG, "gap_tol must be positive and finite");
+    std::vector<double> p((size_t)n * K), rmax(n), g(K), w(K, 1.0 / K);
+    for (int i = 0; i < n; ++i) {
+        double mx = -INFINITY;
+        for (int k = 0; k < K; ++k) {
+            const double v = lpd[(size_t)i * K + k];
+            if (v != v || v == INFINITY) return fail(BNR_ERR_BAD_ARG, "lpd holds a NaN or +Inf");
+            mx = std::max(mx, v);
+        }
+        if (mx == -INFINITY) return fail(BNR_ERR_BAD_ARG, "row " + std::to_string(i + 1) + " of lpd is -Inf for every chain");
+        rmax[i] = mx;
+        for (int k = 0; k < K; ++k) p[(size_t)i * K + k] = exp(lpd[(size_t)i * K + k] - mx);
+    }
+    int it = 0;
+    double gp = 0.0, f = 0.0;
+    for (;;) {
+        for (int k = 0; k < K; ++k) g[k] = 0.0;
+        f = 0.0;
+        for (int i = 0; i < n; ++i) {
+            const double *pi = p.data() + (size_t)i * K;
+            double d = 0.0;
+            for (int k = 0; k < K; ++k) d += w[k] * pi[k];
+            for (int k = 0; k < K; ++k) g[k] += pi[k] / d;
+            f += rmax[i] + log(d);
+        }
+        gp = -INFINITY;
+        for (int k = 0; k < K; ++k) { g[k] /= n; gp = std::max(gp, g[k]); }
+        gp -= 1.0;
+        if (gp <= gap_tol || it == max_iter) break;
+        double s = 0.0;
+        for (int k = 0; k < K; ++k) { w[k] *= g[k]; s += w[k]; }
+        for (int k = 0; k < K; ++k) w[k] /= s;
+        ++it;
+    }
+    memcpy(weights, w.data(), sizeof(double) * K);
+    if (objective) *objective = f / n;
+    if (gap) *gap = gp;
+    if (iters) *iters = it;
+    return BNR_OK;
+}
+
+// the weights of a weighted call, checked and packed for k_wsummary: finite, >= 0, one > 0, |sum - 1| <= 1e-9; used as given
+static int wsum_pack(const double *weights, int K, bnr_wsum_weights &wt)
+{
+    if (K < 1 || K > BNR_STACK_MAX_CHAINS) return fail(BNR_ERR_BAD_ARG, "need 1 <= nchains <= 32 for a weighted call");
+    double s = 0.0;
+    bool any = false;
+    for (int k = 0; k < BNR_STACK_MAX_CHAINS; ++k) wt.w[k] = 0.0;
+    for (int k = 0; k < K; ++k) {
+        if (!std::isfinite(weights[k]) || weights[k] < 0.0) return fail(BNR_ERR_BAD_ARG, "weights must be finite and >= 0");
+        any = any || weights[k] > 0.0;
+        s += weights[k];
+        wt.w[k] = weights[k];
+    }
+    if (!any) return fail(BNR_ERR_BAD_ARG, "at least one weight must be > 0");
+    if (!(fabs(s - 1.0) <= 1e-9)) return fail(BNR_ERR_BAD_ARG, "weights must sum to 1 (within 1e-9)");
+    return BNR_OK;
+}
+// log sum_{k: w_k > 0} w_k exp(v_k) with the largest such v_k taken out, k ascending (v: stride ldv)
+static double wlse(const double *v, size_t ldv, const double *w, int K)
+{
+    double M = -INFINITY;
+    for (int k = 0; k < K; ++k) if (w[k] > 0.0) M = std::max(M, v[k * ldv]);
+    double s = 0.0;
+    for (int k = 0; k < K; ++k) if (w[k] > 0.0) s += w[k] * exp(v[k * ldv] - M);
+    return M + log(s);
+}
+
+// bnr_chains_summary under chain weights: the same staging blocks ("summary_block_cols"), k_wsummary instead of k_summary
+int bnr_chains_wsummary(bnr_chain *const *chains, int32_t nchains, const double *weights, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
+                        double *mean_gamma, double *lower, double *upper, double *prob_xi)
+{
+    if (!chains || !weights || !mean_gamma || !lower || !upper || !prob_xi) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    int rc;
+    bnr_wsum_weights wt;
+    if ((rc = wsum_pack(weights, nchains, wt))) return rc;
+    if ((rc = pooled_check(chains, nchains, first_row, nsamp))) return rc;
+    bnr_chain *c = chains[0];
+    const bnr_dev &d = c->d;
+    const long long S = (long long)nchains * nsamp;
+    if (k_lo < 1 || k_lo > S || k_hi < 1 || k_hi > S) return fail(BNR_ERR_BAD_ARG, "order statistics must be between 1 and nchains * nsamp");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->x.stream;
+    if ((rc = pooled_quiesce(chains, nchains))) return rc;
+    const int np = d.q + d.V;
+    const size_t budget = (size_t)1 << 30;
+    long long blk = c->summary_block_cols > 0 ? c->summary_block_cols : (long long)(budget / ((size_t)S * sizeof(double)));
+    blk = std::min<long long>(std::max<long long>(blk, 1), np);
+    dev_tmp tmp;
+    double *buf = nullptr;
+    result_slab out;
+    if ((rc = tmp.alloc(&buf, (size_t)blk * (size_t)S, st, false))) return rc;
+    if ((rc = out.alloc(tmp, 3, (size_t)np, st))) return rc;
+    for (int p0 = 0; p0 < np; p0 += (int)blk) {
+        const int pc = std::min<int>((int)blk, np - p0);
+        stage_cols(st, chains, nchains, first_row, nsamp, p0, pc, buf);
+        launch_wsummary(st, pc, buf, S, nsamp, nchains, wt, std::min(p0 + pc, d.q) - std::min(p0, d.q), k_lo, k_hi, out.col(0) + p0, out.col(1) + p0,
+                        out.col(2) + p0);
+    }
+    std::vector<double> host(3 * (size_t)np);
+    if ((rc = out.fetch(st, "wsummary", "k_wsummary", {host.data(), host.data() + np, host.data() + 2 * (size_t)np}))) return rc;
+    memcpy(mean_gamma, host.data(), sizeof(double) * d.q);
+    memcpy(prob_xi, host.data() + d.q, sizeof(double) * d.V);
+    memcpy(lower, host.data() + np, sizeof(double) * d.q);
+    memcpy(upper, host.data() + 2 * (size_t)np, sizeof(double) * d.q);
+    return BNR_OK;
+}
+
+// k_wsummary on every row of a caller's m x (K nsamp) matrix (host, row-major), each row on its own: the kernel's direct test, as bnr_hdi is
+// k_hdi's.  On a stream of its own, the rows in blocks of about 256 MiB.
+int bnr_wquantile(int32_t device, int32_t m, int32_t K, int32_t nsamp, const double *x, const double *weights, int32_t k_lo, int32_t k_hi, double *mean,
+                  double *lower, double *upper)
+{
+    if (!x || !weights) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (!mean && !lower && !upper) return fail(BNR_ERR_BAD_ARG, "no output requested");
+    if (!lower != !upper) return fail(BNR_ERR_BAD_ARG, "lower and upper come together");
+    if (m < 1 || nsamp < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows and nsamp >= 1 draws per chain");
+    bnr_wsum_weights wt;
+    int rc;
+    if ((rc = wsum_pack(weights, K, wt))) return rc;
+    const long long S = (long long)K * nsamp;
+    if (S > 0x7FFFFFFFll) return fail(BNR_ERR_BAD_ARG, "more than 2^31 - 1 pooled draws");
+    if (lower && (k_lo < 1 || k_lo > S || k_hi < 1 || k_hi > S)) return fail(BNR_ERR_BAD_ARG, "order statistics must be between 1 and K * nsamp");
+    int ndev = 0;
+    HIPCHK(hipGetDeviceCount(&ndev));
+    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
+    HIPCHK(hipSetDevice(device));
+    stream_guard guard;
+    HIPCHK(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
+    hipStream_t st = guard.s;
+    const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, ((size_t)1 << 28) / ((size_t)S * sizeof(double))));
+    dev_tmp tmp;                                        // (freed before the stream goes)
+    double *Xd = nullptr;
+    result_slab out;
+    if ((rc = tmp.alloc(&Xd, (size_t)blk * (size_t)S, st, false))) return rc;
+    if ((rc = out.alloc(tmp, 3, (size_t)m, st))) return rc;
+    for (int i0 = 0; i0 < m; i0 += blk) {
+        const int mr = std::min(blk, m - i0);
+        HIPCHK(hipMemcpyAsync(Xd, x + (size_t)i0 * S, sizeof(double) * (size_t)mr * (size_t)S, hipMemcpyHostToDevice, st));
+        launch_wsummary(st, mr, Xd, S, nsamp, K, wt, mr, lower ? k_lo : 1, lower ? k_hi : 1, mean ? out.col(0) + i0 : nullptr,
+                        lower ? out.col(1) + i0 : nullptr, lower ? out.col(2) + i0 : nullptr);
+    }
+    return out.fetch(st, "wquantile", "k_wsummary", {mean, lower, upper});
+}
+
+// Per-chain PSIS-LOO and the stacking weights in one call: row k of elpd_chain / pareto_k_chain is bnr_chain_loo of chains[k] (the existing path,
+// chain by chain: the tail length comes from nsamp), the weights are bnr_stacking_weights of the rows that are finite in every chain
+int bnr_chains_stack(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, const double *r_eff, int32_t max_iter, double gap_tol,
+                     double *weights, double *elpd_chain, double *pareto_k_chain, double *elpd_stack, double *gap, int32_t *iters)
+{
+    if (!chains || !weights) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    int rc;
+    if (nchains > BNR_STACK_MAX_CHAINS) return fail(BNR_ERR_BAD_ARG, "need nchains <= 32");
+    if ((rc = pooled_check(chains, nchains, first_row, nsamp))) return rc;
+    if (max_iter < 1) return fail(BNR_ERR_BAD_ARG, "need max_iter >= 1");
+    if (!std::isfinite(gap_tol) || !(gap_tol > 0.0)) return fail(BNR_ERR_BAD_ARG, "gap_tol must be positive and finite");
+    const int K = nchains, n = chains[0]->d.n;
+    HIPCHK(hipSetDevice(chains[0]->device));
+    if ((rc = pooled_quiesce(chains, nchains))) return rc;            // (as every pooled call: what the other chains' streams still hold)
+    std::vector<double> el((size_t)K * n), kh((size_t)K * n);
+    for (int k = 0; k < K; ++k) {
+        bnr_chain *ck = chains[k];
+        if ((rc = loo_call(&ck, 1, first_row, nsamp, r_eff, nullptr, el.data() + (size_t)k * n, kh.data() + (size_t)k * n))) return rc;
+    }
+    std::vector<double> lp;
+    std::vector<char> used(n, 1);
+    for (int i = 0; i < n; ++i) {
+        for (int k = 0; k < K; ++k) if (!std::isfinite(el[(size_t)k * n + i])) used[i] = 0;
+        if (used[i]) for (int k = 0; k < K; ++k) lp.push_back(el[(size_t)k * n + i]);
+    }
+    const int nu = (int)(lp.size() / K);
+    double gp = NAN;
+    int32_t it = 0;
+    if (nu < 1) for (int k = 0; k < K; ++k) weights[k] = 1.0 / K;
+    else if ((rc = bnr_stacking_weights(nu, K, lp.data(), max_iter, gap_tol, weights, nullptr, &gp, &it))) return rc;
+    if (elpd_chain) memcpy(elpd_chain, el.data(), sizeof(double) * el.size());
+    if (pareto_k_chain) memcpy(pareto_k_chain, kh.data(), sizeof(double) * kh.size());
+    if (elpd_stack) for (int i = 0; i < n; ++i) elpd_stack[i] = used[i] ? wlse(el.data() + i, (size_t)n, weights, K) : NAN;
+    if (gap) *gap = gp;
+    if (iters) *iters = it;
+    return BNR_OK;
+}
+
+// bnr_chains_predict for a model matrix under chain weights: k_wsummary over the eta columns of the pooled k_predict (and over the columns
+// after k_pred_noise); every chain's own lpd from the single-chain launches, combined here
+int bnr_chains_wpredict(bnr_chain *const *chains, int32_t nchains, const double *weights, int32_t first_row, int32_t nsamp, int32_t m, const void *X,
+                        int32_t x_dtype, const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd,
+                        uint64_t pred_seed, double *pred_lower, double *pred_upper)
+{
+    if (!chains || !weights || !X || !mean || !lower || !upper || (y && !lpd) || (!pred_lower != !pred_upper)) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    int rc;
+    bnr_wsum_weights wt;
+    if ((rc = wsum_pack(weights, nchains, wt))) return rc;
+    if ((rc = pooled_check(chains, nchains, first_row, nsamp))) return rc;
+    bnr_chain *c = chains[0];
+    const bnr_dev &d = c->d;
+    const long long S = (long long)nchains * nsamp;
+    if (k_lo < 1 || k_lo > S || k_hi < 1 || k_hi > S) return fail(BNR_ERR_BAD_ARG, "order statistics must be between 1 and nchains * nsamp");
+    if (m < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows");
+    if (x_dtype < BNR_F64 || x_dtype > BNR_F32) return fail(BNR_ERR_BAD_ARG, "unknown element type of X");
+    HIPCHK(hipSetDevice(c->device));
+    hipStream_t st = c->x.stream;
+    const int m_pad = round_up(m, 32), q16 = round_up(d.q, 16);
+    dev_tmp tmp;
+    double *Xd = nullptr, *yd = nullptr;
+    result_slab out, lc;
+    if ((rc = pooled_quiesce(chains, nchains))) return rc;
+    if ((rc = tmp.alloc(&Xd, (size_t)m_pad * q16, st))) return rc;             // zero rows m .. m_pad - 1 and columns q .. q16 - 1 (k_predict)
+    if ((rc = out.alloc(tmp, 5, (size_t)m, st))) return rc;
+    if (x_dtype == BNR_F64) {
+        HIPCHK(hipMemcpy2DAsync(Xd, (size_t)m_pad * sizeof(double), X, (size_t)m * sizeof(double), (size_t)m * sizeof(double), d.q, hipMemcpyHostToDevice, st));
+    } else {
+        char *raw = nullptr;
+        const size_t bytes = (size_t)m * d.q * dtype_size(x_dtype);
+        if ((rc = tmp.alloc(&raw, bytes, st))) return rc;
+        HIPCHK(hipMemcpyAsync(raw, X, bytes, hipMemcpyHostToDevice, st));
+        launch_x_convert(x_dtype, raw, false, m, d, m_pad, Xd, nullptr, nullptr, st);
+    }
+    pred_stages sg;
+    sg.k_lo = k_lo; sg.k_hi = k_hi;
+    sg.wt = &wt;
+    sg.mean = out.col(0); sg.lower = out.col(1); sg.upper = out.col(2);
+    if (y) {
+        if ((rc = tmp.alloc(&yd, (size_t)m, st))) return rc;
+        HIPCHK(hipMemcpyAsync(yd, y, sizeof(double) * m, hipMemcpyHostToDevice, st));
+        if ((rc = lc.alloc(tmp, nchains + 1, (size_t)m, st))) return rc;        // every chain's lpd; the last column takes the pwaic nobody reads
+        // every chain's own lpd: bnr_chain_predict's launches over that chain alone, on its stream (the inputs are complete first), so column k
+        // is its lpd bit for bit; the work buffers of a chain go before the next one's come
+        HIPCHK(hipStreamSynchronize(st));
+        for (int k = 0; k < nchains; ++k) {
+            bnr_chain *ck = chains[k];
+            dev_tmp tk;
+            pred_stages sk;
+            sk.lpd = lc.col(k); sk.pwaic = lc.col(nchains);
+            if ((rc = predict_rows(&ck, 1, first_row, nsamp, m, Xd, m_pad, yd, sk, tk))) return rc;
+            HIPCHK(hipStreamSynchronize(ck->x.stream));
+        }
+    }
+    if (pred_lower) { sg.seed = pred_seed; sg.pred_lower = out.col(3); sg.pred_upper = out.col(4); }
+    if ((rc = predict_rows(chains, nchains, first_row, nsamp, m, Xd, m_pad, nullptr, sg, tmp))) return rc;
+    std::vector<double> hl;
+    if (y) {
+        hl.resize((size_t)nchains * m);
+        HIPCHK(hipMemcpyAsync(hl.data(), lc.d, sizeof(double) * hl.size(), hipMemcpyDeviceToHost, st));
+    }
+    if ((rc = out.fetch(st, "wpredict", "k_wsummary", {mean, lower, upper, pred_lower, pred_lower ? pred_upper : nullptr}))) return rc;
+    if (y) for (int i = 0; i < m; ++i) lpd[i] = wlse(hl.data() + i, (size_t)m, weights, nchains);
+    return BNR_OK;
 }

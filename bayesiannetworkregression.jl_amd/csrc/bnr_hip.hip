@@ -1543,7 +1543,7 @@ int bnr_chain_set_iter(bnr_chain *c, int64_t iter)
     return BNR_OK;
 }
 
-// k_fetch_cols, k_summary, k_acov for both translation units (bnr_internal.h)
+// k_fetch_cols, k_summary, k_acov for both translation units (bnr_internal.h; k_wsummary's launcher is the last function of this file)
 extern "C++" void launch_fetch_cols(hipStream_t st, const double *trace, int rowlen, int off, int ncols, int first, int nrows, double *out, long long ldo)
 { hipLaunchKernelGGL(k_fetch_cols, dim3((ncols + 31) / 32, (nrows + 31) / 32), dim3(32, 8), 0, st, trace, rowlen, off, ncols, first, nrows, out, ldo); }
 extern "C++" void launch_summary(hipStream_t st, int cols, const double *buf, int nsamp, int q, int k_lo, int k_hi, double *mean, double *lo, double *hi)
@@ -2189,4 +2189,13 @@ static void launch_late_xpass_group2(bnr_exec &x, int s)
 static void launch_late_backproj64(bnr_exec &x, int s, int flags, size_t lds64)
 { BNR_LAUNCH(k_backproj64, dim3(round_up((x.shape->nblk_bp + 1) / 2, 8) * x.nb), dim3(256), lds64, x.stream, x, s, flags, x.nb); }
 
+}
+
+// k_wsummary for bnr_analysis.hip (bnr_internal.h).  Last in the file: the kernel's two instances are emitted here, behind every kernel of the sweep
+extern "C++" void launch_wsummary(hipStream_t st, int cols, const double *buf, long long ld, int nsamp, int K, const bnr_wsum_weights &wt, int q, int k_lo, int k_hi,
+                                  double *mean, double *lo, double *hi)
+{
+    const double T_lo = (double)k_lo / (double)K, T_hi = (double)k_hi / (double)K;
+    if (K <= 8) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wsummary<10>), dim3(cols), dim3(256), 0, st, buf, ld, nsamp, K, wt, q, T_lo, T_hi, mean, lo, hi);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_wsummary<8>), dim3(cols), dim3(256), 0, st, buf, ld, nsamp, K, wt, q, T_lo, T_hi, mean, lo, hi);
 }

@@ -149,10 +149,15 @@ size_t dtype_size(int t);
 // dimension ld; an integer type also fills the byte image X8 (nullable), not_bytes (nullable) is raised by an entry that is no byte
 void launch_x_convert(int dtype, const void *raw, bool mats, int rows, const bnr_dev &d, int ld, double *Xd, unsigned char *X8, int *not_bytes, hipStream_t st);
 
-// k_fetch_cols, k_summary and k_acov live among the sweep kernels (table I/O and bnr_chain_ess_stats use them too): bnr_analysis.hip launches them through
+// k_fetch_cols, k_summary, k_acov and k_wsummary live among the sweep kernels (table I/O and bnr_chain_ess_stats use them too): bnr_analysis.hip launches them through
 // these.  fetch_cols: rows first .. first + nrows - 1 (0-based) of the trace columns off .. off + ncols - 1 into out, column-major with leading dimension ldo;
 // summary: one workgroup per column of buf (the first q of them get the order statistics); acov: np series of nsamp draws, both halves, L lags
 void launch_fetch_cols(hipStream_t st, const double *trace, int rowlen, int off, int ncols, int first, int nrows, double *out, long long ldo);
 void launch_summary(hipStream_t st, int cols, const double *buf, int nsamp, int q, int k_lo, int k_hi, double *mean, double *lo, double *hi);
 void launch_acov(hipStream_t st, const double *buf, int nsamp, int np, int L, double *out);
+// k_wsummary (chain stacking, ABI 16) lives beside k_summary: `cols` staged columns of leading dimension ld, each K segments of nsamp draws, under the
+// chain weights wt (by value); the first q columns get the statistics of the pooled ranks k_lo, k_hi (T = rank / K); mean, lo / hi may be NULL
+struct bnr_wsum_weights { double w[BNR_STACK_MAX_CHAINS]; };
+void launch_wsummary(hipStream_t st, int cols, const double *buf, long long ld, int nsamp, int K, const bnr_wsum_weights &wt, int q, int k_lo, int k_hi,
+                     double *mean, double *lo, double *hi);
 #pragma GCC visibility pop

@@ -21,7 +21,7 @@
 // Every sweep kernel exists for ONE chain (descriptor by value: bnr_one) and for a lockstep group of chains (device array
 // of descriptors indexed by the grid's chain coordinate: bnr_many); the arithmetic of a chain is the same in both.
 // Outside the sweep: k_init_prior (initialize_variables!), k_fetch_cols / k_load_cols (Table layout), k_rhat_stats
-// (split-Rhat message), k_summary (Summary statistics), k_acov (ESS message).  The kernels of the posterior analysis (prediction, PSIS-LOO,
+// (split-Rhat message), k_summary (Summary statistics), k_acov (ESS message), k_wsummary (k_summary under chain weights, ABI 16; last in this file).  The kernels of the posterior analysis (prediction, PSIS-LOO,
 // rank-normalised diagnostics, HDI) are a code object of their own: bnr_analysis_kernels.h.
 //   k_x_mask, k_sdigits, k_gram_i8   the Gram of a binary (0/1) model matrix on the i8 matrix pipe (round 5)
 // The measured experiments of rounds 3-4 (persistent / resident Gram kernels, left-looking and data-flow factorizations, gates, ...) are not
@@ -3606,5 +3606,131 @@ __global__ __launch_bounds__(1024) void k_sdigits(const SRC chain_src, int s)
             carry = b >= 128u ? 1u : 0u;
             cd.Sdig[(size_t)l * cd.kslab + idx] = (unsigned char)(b & 255u);
         }
+    }
+}
+
+// ===================================================================================== k_wsummary (chain stacking, ABI 16; an addition to the reference)
+// Outside the sweep, with k_summary whose companion it is; behind every kernel of the sweep, so that none of them moves.
+// k_wsummary: the mean and two order statistics of one staged column (see k_summary: column p of `buf`, leading dimension ld) under chain
+// weights w_0 .. w_{K-1} (Yao, Vehtari & Gelman 2022): the column holds K segments of nsamp draws, chain k's in rows k nsamp ..
+//   mean = sum_k w_k m_k, k ascending from 0.0, m_k = the mean of segment k in k_summary's order (256 thread-strided partial sums, the tree,
+//          one division by nsamp): bit for bit bnr_chain_summary's mean of chain k;
+//   the statistic of T (= (double)r / (double)K for a pooled rank r, divided on the host) = the draw x with the smallest bnr_key_of key for
+//          which W(x) = sum_k w_k (double)c_k(x) >= T, c_k(x) = #{draws of chain k with key <= key(x)}; every product and every addition
+//          rounded on its own (-ffp-contract=off), k ascending from 0.0.  Where W never reaches T (round-off at r = K nsamp): the largest draw
+//          among the chains with w_k > 0.
+// W is non-decreasing in the key also in floating point (each term is a monotone function of an integer count, and a rounded addition is
+// monotone), so an MSD radix descent finds the draw exactly: per pass one integer histogram per chain in LDS (K x 2^bits counters; integer
+// atomics only, nothing depends on their order), turned into per-chain inclusive prefix counts by one wave per chain (lane-owned runs, a
+// shuffle scan), then every bin's W from `below_k` (the chain's draws under the current prefix) + its prefix count, and the first bin with
+// W >= T by an integer atomicMin.  Digits: 10 bits for K <= 8 (7 passes: 6 x 10 + 4), 8 bits above (8 passes); 8192 counters = 32 KiB either
+// way.  A column with a NaN draw is NaN in every output.  Columns p >= q get the mean only; mean, lo / hi (a pair) may be NULL.
+// The digit width is the template parameter (the launcher picks it from K); a template also so that its code is emitted where it is
+// instantiated, behind the sweep's kernels at the end of bnr_hip.hip.  One workgroup of 256 threads per column; results do not depend on the grid.  K <= BNR_STACK_MAX_CHAINS (include/bnr_hip.h); the weights by value (bnr_wsum_weights, bnr_internal.h).
+template <int BITS>
+__global__ __launch_bounds__(256) void k_wsummary(const double *buf, long long ld, int nsamp, int K, bnr_wsum_weights wt, int q, double T_lo, double T_hi,
+                                                  double *mean, double *lo, double *hi)
+{
+    __shared__ unsigned int hist[8192];
+    __shared__ double red[256];
+    __shared__ double sw[BNR_STACK_MAX_CHAINS];
+    __shared__ unsigned int below[BNR_STACK_MAX_CHAINS];
+    __shared__ unsigned long long s_prefix, s_max;
+    __shared__ int s_bin;
+    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const double *col = buf + (size_t)p * (size_t)ld;
+    if (tid < K) sw[tid] = wt.w[tid];
+    // the means of the segments, each in k_summary's order, and their weighted sum; a NaN anywhere
+    double wm = 0.0;
+    int bad = 0;
+    for (int k = 0; k < K; ++k) {
+        const double *seg = col + (size_t)k * nsamp;
+        double acc = 0.0;
+        for (int i = tid; i < nsamp; i += 256) { const double v = seg[i]; bad |= v != v; acc += v; }
+        __syncthreads();
+        red[tid] = acc;
+        __syncthreads();
+        for (int w = 128; w > 0; w >>= 1) { if (tid < w) red[tid] += red[tid + w]; __syncthreads(); }
+        wm = wm + sw[k] * (red[0] / nsamp);
+    }
+    bad = __syncthreads_or(bad);
+    if (tid == 0 && mean) mean[p] = bad ? NAN : wm;
+    if (p >= q || !lo) return;
+    if (bad) {
+        if (tid == 0) { lo[p] = NAN; hi[p] = NAN; }
+        return;
+    }
+    constexpr int bits0 = BITS;                          // 10 for K <= 8, 8 above: K 2^BITS <= 8192 counters
+    for (int stat = 0; stat < 2; ++stat) {
+        const double T = stat == 0 ? T_lo : T_hi;
+        double wall = 0.0;                                   // W of the largest draw
+        for (int k = 0; k < K; ++k) wall = wall + sw[k] * (double)nsamp;
+        if (!(wall >= T)) {                                  // never reached: the largest draw among the chains with w_k > 0
+            if (tid == 0) s_max = 0ull;
+            __syncthreads();
+            unsigned long long mx = 0ull;
+            for (int k = 0; k < K; ++k) {
+                if (!(sw[k] > 0.0)) continue;
+                const double *seg = col + (size_t)k * nsamp;
+                for (int i = tid; i < nsamp; i += 256) { const unsigned long long key = bnr_key_of(seg[i]); mx = key > mx ? key : mx; }
+            }
+            atomicMax(&s_max, mx);
+            __syncthreads();
+            if (tid == 0) (stat == 0 ? lo : hi)[p] = bnr_double_of(s_max);
+            __syncthreads();
+            continue;
+        }
+        if (tid == 0) s_prefix = 0ull;
+        if (tid < K) below[tid] = 0u;
+        __syncthreads();
+        int shift = 64;
+        while (shift > 0) {
+            const int bits = shift < bits0 ? shift : bits0, nb = 1 << bits;
+            const unsigned long long himask = shift >= 64 ? 0ull : (~0ull << shift);
+            shift -= bits;
+            const unsigned long long prefix = s_prefix;
+            for (int b = tid; b < K * nb; b += 256) hist[b] = 0u;
+            if (tid == 0) s_bin = nb;
+            __syncthreads();
+            for (int k = 0; k < K; ++k) {
+                const double *seg = col + (size_t)k * nsamp;
+                unsigned int *h = hist + k * nb;
+                for (int i = tid; i < nsamp; i += 256) {
+                    const unsigned long long key = bnr_key_of(seg[i]);
+                    if ((key & himask) == prefix) atomicAdd(&h[(unsigned int)(key >> shift) & (unsigned int)(nb - 1)], 1u);
+                }
+            }
+            __syncthreads();
+            // per chain the inclusive prefix counts over the bins: wave wv takes the chains wv, wv + 4, ..; a lane owns `per` consecutive bins
+            const int per = (nb + 63) / 64;
+            for (int k = wv; k < K; k += 4) {
+                unsigned int *h = hist + k * nb;
+                const int b0 = lane * per, b1 = min(nb, b0 + per);
+                unsigned int run = 0u;
+                for (int b = b0; b < b1; ++b) run += h[b];
+                unsigned int incl = run;
+                for (int off = 1; off < 64; off <<= 1) {
+                    const unsigned int v = __shfl_up(incl, off, 64);
+                    if (lane >= off) incl += v;
+                }
+                unsigned int c = incl - run;
+                for (int b = b0; b < b1; ++b) { c += h[b]; h[b] = c; }
+            }
+            __syncthreads();
+            // the first bin whose W reaches T
+            for (int b = tid; b < nb; b += 256) {
+                double W = 0.0;
+                for (int k = 0; k < K; ++k) W = W + sw[k] * (double)(below[k] + hist[k * nb + b]);
+                if (W >= T) { atomicMin(&s_bin, b); break; }    // (W is non-decreasing in b: this thread's later bins reach T as well)
+            }
+            __syncthreads();
+            const int bin = s_bin < nb ? s_bin : nb - 1;         // (always < nb: the last bin's W is the W that reached T one level up)
+            __syncthreads();
+            if (tid < K && bin > 0) below[tid] += hist[tid * nb + bin - 1];
+            if (tid == 0) s_prefix = prefix | ((unsigned long long)bin << shift);
+            __syncthreads();
+        }
+        if (tid == 0) (stat == 0 ? lo : hi)[p] = bnr_double_of(s_prefix);
+        __syncthreads();
     }
 }

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BNR_ABI_VERSION 15  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
+#define BNR_ABI_VERSION 16  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
                                5: + bnr_chain_create_typed, bnr_chain_create_from_matrices, bnr_device_synchronize; 6: + bnr_comm_info;
                                7: + option "xi_weights", bnr_host_xi_weight; 8: + bnr_chain_predict, bnr_chain_predict_from_matrices,
                                bnr_chain_loglik_stats, option "predict_block_rows"; 9: + bnr_chain_loo, bnr_psis_loo;
@@ -37,7 +37,8 @@ extern "C" {
                                bnr_psis_weights; 12: + bnr_chain_rank_diag, bnr_chains_rank_diag, bnr_rank_normalize, bnr_host_ndtri,
                                option "rank_block_cols"; 13: + bnr_chain_hdi, bnr_chains_hdi, bnr_hdi;
                                14: + bnr_host_gig_attempts; 15: + bnr_chain_inclusion, bnr_chains_inclusion,
-                               bnr_inclusion (all additive) */
+                               bnr_inclusion; 16: + bnr_stacking_weights, bnr_chains_stack, bnr_chains_wsummary, bnr_chains_wpredict,
+                               bnr_wquantile (all additive) */
 
 enum {
     BNR_OK = 0,
@@ -360,6 +361,52 @@ int bnr_chains_inclusion(bnr_chain *const *chains, int32_t nchains, int32_t firs
                          double *joint, double *size_pmf, int64_t *n_distinct, uint64_t *top_sets, int64_t *top_count);
 int bnr_inclusion(int32_t device, int32_t S, int32_t B, const uint8_t *z, int32_t ntop, double *prob, double *joint, double *size_pmf,
                   int64_t *n_distinct, uint64_t *top_sets, int64_t *top_count);
+
+/* Chain stacking (ABI 16) -- an ADDITION to the reference: posterior statistics of chains that do not mix, under chain weights chosen by
+ * leave-one-out predictive performance (Yao, Vehtari & Gelman 2022, "Stacking for non-mixing Bayesian computations", JMLR 23).
+ * bnr_stacking_weights (host code, no GPU): the weights on the simplex that maximise f(w) = (1 / n) sum_i log sum_k w_k exp(lpd_ik) for the
+ *   n x K matrix lpd (row-major) of pointwise predictive log densities, by the multiplicative (EM) fixed point: p_ik = exp(lpd_ik - max_k lpd_ik),
+ *   w = 1 / K, then g_k = (1 / n) sum_i p_ik / sum_j w_j p_ij and w <- w o g (divided by its sum, which is 1 up to rounding).  f is concave and
+ *   sum_k w_k g_k = 1, so f(w*) - f(w) <= max_k g_k - 1 for every w* of the simplex: the iteration stops when that bound is <= gap_tol, or
+ *   after max_iter updates (no error: the caller reads *gap).  *gap = the last max_k g_k - 1 (that of the weights returned), *objective = f(w)
+ *   with the row maxima added back, *iters = the updates applied (objective, gap, iters nullable).  Every sum runs in index order.
+ *   BNR_ERR_BAD_ARG: n < 1, K < 1 or K > BNR_STACK_MAX_CHAINS, a NaN or +Inf entry, a row that is -Inf in every chain, max_iter < 1, gap_tol not
+ *   finite or <= 0.
+ * bnr_chains_stack: row k of elpd_chain / pareto_k_chain (K x n, nullable) is bit for bit what bnr_chain_loo(chains[k], first_row, nsamp, r_eff)
+ *   returns (the tail length comes from nsamp, not from K nsamp); weights[K] = bnr_stacking_weights of the transposed elpd_chain over the rows
+ *   that are finite in every chain; elpd_stack[n] (nullable): elpd_stack_i = M_i + log sum_{k: w_k > 0} w_k exp(elpd_ki - M_i), M_i the largest
+ *   elpd_ki among the chains with w_k > 0, k ascending; NaN for a row left out.  No row left: every weight 1 / K, *gap NaN, *iters 0.
+ *   Checks: those of bnr_chains_loo, nchains <= BNR_STACK_MAX_CHAINS, max_iter and gap_tol as above.  The K LOO passes run one after the other,
+ *   each on its chain's stream, behind the wait every pooled call makes for the other chains' streams.  Nothing of any chain is written.
+ * The weighted statistics work on columns of S = K nsamp draws, chain k's window in rows k nsamp .. (k + 1) nsamp - 1 (kernel k_wsummary); every
+ *   sum below runs k ascending from 0.0, every product and addition rounded on its own:
+ *   mean = sum_k w_k m_k, m_k the mean of chain k's draws exactly as bnr_chain_summary computes it;
+ *   the order statistic of a rank r in 1 .. S (the ranks bnr_chains_summary takes): with T = (double)r / (double)K and
+ *   W(x) = sum_k w_k (double)#{draws of chain k whose key is <= the key of x} -- the key is the order of bnr_chains_summary: numbers by value,
+ *   -0 below +0 -- the draw with the smallest key for which W(x) >= T; where no draw reaches T (round-off near r = S) the largest draw among
+ *   the chains with w_k > 0.  With K a power of two and w_k = 1 / K this is bnr_chains_summary's order statistic bit for bit; with w = e_k it
+ *   is chain k's ceil(T)-th smallest draw.  A column holding a NaN draw is NaN in every output; +-Inf are ordered as numbers.
+ *   Weights: finite, >= 0, at least one > 0, |sum_k w_k - 1| <= 1e-9 (BNR_ERR_BAD_ARG otherwise); used as given, not renormalised.
+ * bnr_chains_wsummary: bnr_chains_summary under the weights (same staging blocks, option "summary_block_cols", same checks, nchains <=
+ *   BNR_STACK_MAX_CHAINS; bitwise independent of the block); prob_xi = the weighted mean of every xi column.
+ * bnr_chains_wpredict: bnr_chains_predict for a model matrix under the weights: mean / lower / upper from the eta columns of the pooled
+ *   prediction; lpd[i] (needs y) = M + log sum_{k: w_k > 0} w_k exp(lpd_ki - M), lpd_ki = bit for bit bnr_chain_predict's lpd of chain k, M the
+ *   largest of them among the chains with w_k > 0; pred_lower / pred_upper (both or neither): the same order statistics of the columns after
+ *   bnr_chains_predict's noise with pred_seed (bnr_host_pred_noise).  Rows in blocks ("predict_block_rows"); no result depends on the block.
+ * bnr_wquantile: the kernel on the rows of a caller's m x (K nsamp) matrix (host, row-major), each row on its own, on a stream of its own;
+ *   lower and upper are nullable as a pair, mean is nullable, not all three.  DESIGN.md section 8. */
+#define BNR_STACK_MAX_CHAINS 32
+int bnr_stacking_weights(int32_t n, int32_t K, const double *lpd, int32_t max_iter, double gap_tol, double *weights, double *objective, double *gap,
+                         int32_t *iters);
+int bnr_chains_stack(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, const double *r_eff, int32_t max_iter, double gap_tol,
+                     double *weights, double *elpd_chain, double *pareto_k_chain, double *elpd_stack, double *gap, int32_t *iters);
+int bnr_chains_wsummary(bnr_chain *const *chains, int32_t nchains, const double *weights, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
+                        double *mean_gamma, double *lower, double *upper, double *prob_xi);
+int bnr_chains_wpredict(bnr_chain *const *chains, int32_t nchains, const double *weights, int32_t first_row, int32_t nsamp, int32_t m, const void *X,
+                        int32_t x_dtype, const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd,
+                        uint64_t pred_seed, double *pred_lower, double *pred_upper);
+int bnr_wquantile(int32_t device, int32_t m, int32_t K, int32_t nsamp, const double *x, const double *weights, int32_t k_lo, int32_t k_hi, double *mean,
+                  double *lower, double *upper);
 
 /* Effective sample size -- an ADDITION to the reference (which only has split-Rhat; north-star item "Rhat/ESS check").
  * bnr_chain_ess_stats: this chain's message over rows first_row .. first_row+nsamp-1: for both halves of the window (the

@@ -350,6 +350,69 @@ function psis_weights(loglik::AbstractMatrix; r_eff=nothing, device=0)
     Matrix(transpose(lw)), elpd, k
 end
 
+# ---- chain stacking (ABI 16; bnr_stacking_weights, bnr_chains_stack, bnr_chains_wsummary, bnr_chains_wpredict; additions to the reference):
+# posterior statistics of chains that do not mix under chain weights chosen by leave-one-out predictive performance (Yao, Vehtari & Gelman
+# 2022).  stacking_weights: host code on an n x K matrix of pointwise predictive log densities -> (weights, objective, gap, iterations).
+function stacking_weights(lpd::AbstractMatrix; max_iter=100000, gap_tol=1e-9)
+    n, K = size(lpd)
+    lt = Matrix{Float64}(transpose(lpd))                                         # K x n column-major = n x K row-major
+    w = zeros(K)
+    f, g, it = Ref{Cdouble}(0.0), Ref{Cdouble}(0.0), Ref{Int32}(0)
+    check(ccall((:bnr_stacking_weights, LIB), Cint, (Int32, Int32, Ptr{Cdouble}, Int32, Cdouble, Ptr{Cdouble}, Ref{Cdouble}, Ref{Cdouble}, Ref{Int32}),
+        n, K, lt, max_iter, gap_tol, w, f, g, it))
+    (weights = w, objective = f[], gap = g[], iterations = Int(it[]))
+end
+# every chain's own PSIS-LOO over rows nburn+1 .. nburn+nsamp and the stacking weights of the chains: elpd_chain / pareto_k are n x K (column
+# k = chains[k]: what loo_stats returns for it), elpd_stack the pointwise leave-one-out log score of the weighted mixture (NaN for a row that
+# is not finite in some chain: those rows are left out)
+function chains_stack(chains::Vector{Chain}, nburn, nsamp; r_eff=nothing, max_iter=100000, gap_tol=1e-9)
+    n, K = chains[1].n, length(chains)
+    hs = Ptr{Cvoid}[c.h for c in chains]
+    rv = loo_r_eff(r_eff, n)
+    rp = r_eff === nothing ? Ptr{Cdouble}(C_NULL) : pointer(rv)
+    w, el, kh, es = zeros(K), zeros(n, K), zeros(n, K), zeros(n)
+    g, it = Ref{Cdouble}(0.0), Ref{Int32}(0)
+    GC.@preserve hs rv check(ccall((:bnr_chains_stack, LIB), Cint,
+        (Ptr{Ptr{Cvoid}}, Int32, Int32, Int32, Ptr{Cdouble}, Int32, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ref{Cdouble}, Ref{Int32}),
+        hs, K, nburn + 1, nsamp, rp, max_iter, gap_tol, w, el, kh, es, g, it))
+    (weights = w, elpd_chain = el, pareto_k = kh, elpd_stack = es, gap = g[], iterations = Int(it[]))
+end
+# pooled_summary_stats under chain weights: the same ranks of the pooled draws, read off the weighted distribution
+function chains_wsummary(chains::Vector{Chain}, weights, nburn, nsamp; interval=95)
+    ch = chains[1]
+    length(weights) == length(chains) || throw(ArgumentError("need one weight per chain"))
+    klo, khi = pooled_ranks(length(chains) * nsamp, interval)
+    hs = Ptr{Cvoid}[c.h for c in chains]
+    wv = Vector{Float64}(weights)
+    m, lo, hi, p = zeros(ch.q), zeros(ch.q), zeros(ch.q), zeros(ch.V)
+    GC.@preserve hs check(ccall((:bnr_chains_wsummary, LIB), Cint,
+        (Ptr{Ptr{Cvoid}}, Int32, Ptr{Cdouble}, Int32, Int32, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        hs, length(hs), wv, nburn + 1, nsamp, klo, khi, m, lo, hi, p))
+    m, lo, hi, p
+end
+# pooled_predict_stats under chain weights for an n x q model matrix: (mean, lower, upper, lpd, pred_lower, pred_upper); no PIT
+function chains_wpredict(chains::Vector{Chain}, weights, nburn, nsamp, Xnew::AbstractMatrix; y=nothing, interval=95, predict_observation=true, pred_seed=0)
+    ch = chains[1]
+    length(weights) == length(chains) || throw(ArgumentError("need one weight per chain"))
+    klo, khi = pooled_ranks(length(chains) * nsamp, interval)
+    hs = Ptr{Cvoid}[c.h for c in chains]
+    wv = Vector{Float64}(weights)
+    m = size(Xnew, 1)
+    y === nothing || length(y) == m || throw(ArgumentError("y must have one entry per new row"))
+    yv = y === nothing ? Float64[] : Vector{Float64}(y)
+    yp = y === nothing ? Ptr{Cdouble}(C_NULL) : pointer(yv)
+    mean, lo, hi, lpd, plo, phi = zeros(m), zeros(m), zeros(m), zeros(m), zeros(m), zeros(m)
+    plop = predict_observation ? pointer(plo) : Ptr{Cdouble}(C_NULL)
+    phip = predict_observation ? pointer(phi) : Ptr{Cdouble}(C_NULL)
+    T = dtype_code(eltype(Xnew)) >= 0 ? eltype(Xnew) : Float64
+    Xm = Matrix{T}(Xnew)
+    size(Xm, 2) == ch.q || throw(ArgumentError("X must have q = V(V+1)/2 columns"))
+    GC.@preserve hs Xm yv plo phi check(ccall((:bnr_chains_wpredict, LIB), Cint,
+        (Ptr{Ptr{Cvoid}}, Int32, Ptr{Cdouble}, Int32, Int32, Int32, Ptr{Cvoid}, Int32, Ptr{Cdouble}, Int32, Int32, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, UInt64, Ptr{Cdouble}, Ptr{Cdouble}),
+        hs, length(hs), wv, nburn + 1, nsamp, m, Xm, dtype_code(T), yp, klo, khi, mean, lo, hi, lpd, UInt64(pred_seed), plop, phip))
+    (mean, lo, hi, y === nothing ? nothing : lpd, predict_observation ? plo : nothing, predict_observation ? phi : nothing)
+end
+
 # the noise of the predictive draws as the device draws it (host code, no GPU): ns x ni, element [s - s0 + 1, i - i0 + 1]
 function pred_noise(seed, s0, ns, i0, ni)
     out = zeros(ns, ni)
