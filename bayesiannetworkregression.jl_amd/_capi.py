@@ -184,6 +184,14 @@ def lib():
     return _lib
 
 
+def _device_lib():
+    """lib() for the calls that open a device: refused where the library is bound to a foreign HIP runtime (see lib())"""
+    L = lib()
+    if _foreign_hip:
+        raise BnrError(BNR_ERR_HIP, _foreign_hip)
+    return L
+
+
 def check(code):
     if code != BNR_OK:
         raise BnrError(code, lib().bnr_last_error().decode())
@@ -240,34 +248,32 @@ def r_eff_array(r_eff, m):
     return r
 
 
+def _matrix(x, name):
+    """a caller's m x S matrix (rows x draws) as contiguous float64; ValueError (before any library call) unless it is one with m, S >= 1"""
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
+        raise ValueError("%s must be an m x S matrix (rows x draws) with m, S >= 1" % name)
+    return a
+
+
 def psis_loo_raw(loglik, r_eff=None, device=0):
     """(lpd, elpd_loo, pareto_k) of every row of an m x S log-likelihood matrix, PSIS on the device (bnr_psis_loo)"""
-    ll = np.ascontiguousarray(loglik, dtype=np.float64)
-    if ll.ndim != 2 or ll.shape[0] < 1 or ll.shape[1] < 1:
-        raise ValueError("loglik must be an m x S matrix (rows x draws) with m, S >= 1")
+    ll = _matrix(loglik, "loglik")
     m, S = ll.shape
     r = r_eff_array(r_eff, m)
     lpd, elpd, k = np.empty(m), np.empty(m), np.empty(m)
-    L = lib()
-    if _foreign_hip:
-        raise BnrError(BNR_ERR_HIP, _foreign_hip)
-    check(L.bnr_psis_loo(int(device), m, S, _ptr(ll), _ptr(r), _ptr(elpd), _ptr(k), _ptr(lpd)))
+    check(_device_lib().bnr_psis_loo(int(device), m, S, _ptr(ll), _ptr(r), _ptr(elpd), _ptr(k), _ptr(lpd)))
     return lpd, elpd, k
 
 
 def psis_weights_raw(loglik, r_eff=None, device=0):
     """(log_weights m x S, elpd_loo, pareto_k): the normalised PSIS log weights of every row of an m x S log-likelihood matrix, on the device
     (bnr_psis_weights); a row with a non-finite entry gets NaN weights"""
-    ll = np.ascontiguousarray(loglik, dtype=np.float64)
-    if ll.ndim != 2 or ll.shape[0] < 1 or ll.shape[1] < 1:
-        raise ValueError("loglik must be an m x S matrix (rows x draws) with m, S >= 1")
+    ll = _matrix(loglik, "loglik")
     m, S = ll.shape
     r = r_eff_array(r_eff, m)
     lw, elpd, k = np.empty((m, S)), np.empty(m), np.empty(m)
-    L = lib()
-    if _foreign_hip:
-        raise BnrError(BNR_ERR_HIP, _foreign_hip)
-    check(L.bnr_psis_weights(int(device), m, S, _ptr(ll), _ptr(r), _ptr(lw), _ptr(elpd), _ptr(k)))
+    check(_device_lib().bnr_psis_weights(int(device), m, S, _ptr(ll), _ptr(r), _ptr(lw), _ptr(elpd), _ptr(k)))
     return lw, elpd, k
 
 
@@ -295,18 +301,13 @@ def host_ndtri(p):
 def rank_normalize_raw(x, device=0, ranks=True, z=True):
     """(ranks, z) of every row of an m x S matrix, each row ranked on its own, on the device (bnr_rank_normalize): average ranks (ties share the
     mean of their positions) and z = Phi^-1((r - 3/8) / (S + 1/4)); the one not asked for is None"""
-    a = np.ascontiguousarray(x, dtype=np.float64)
-    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
-        raise ValueError("x must be an m x S matrix (rows x draws) with m, S >= 1")
+    a = _matrix(x, "x")
     if not (ranks or z):
         raise ValueError("ask for the ranks, z or both")
     m, S = a.shape
     r = np.empty((m, S)) if ranks else None
     zz = np.empty((m, S)) if z else None
-    L = lib()
-    if _foreign_hip:
-        raise BnrError(BNR_ERR_HIP, _foreign_hip)
-    check(L.bnr_rank_normalize(int(device), m, S, _ptr(a), _ptr(r), _ptr(zz)))
+    check(_device_lib().bnr_rank_normalize(int(device), m, S, _ptr(a), _ptr(r), _ptr(zz)))
     return r, zz
 
 
@@ -334,16 +335,11 @@ def hdi_raw(x, probs, device=0, fields=HDI_FIELDS):
     """The tuple HDI_FIELDS of every row of an m x S matrix, each row on its own, on the device (bnr_hdi): lower / upper (nprob, m) -- the
     highest-density interval of every level of `probs` --, the median, and the shares of draws above and below zero (m,); an entry not named
     in `fields` is not requested and comes back as None"""
-    a = np.ascontiguousarray(x, dtype=np.float64)
-    if a.ndim != 2 or a.shape[0] < 1 or a.shape[1] < 1:
-        raise ValueError("x must be an m x S matrix (rows x draws) with m, S >= 1")
+    a = _matrix(x, "x")
     pr = hdi_probs(probs)
     m, S = a.shape
     out = _hdi_outputs(pr, m, fields)
-    L = lib()
-    if _foreign_hip:
-        raise BnrError(BNR_ERR_HIP, _foreign_hip)
-    check(L.bnr_hdi(int(device), m, S, _ptr(a), pr.size, _ptr(pr), *[_ptr(o) for o in out]))
+    check(_device_lib().bnr_hdi(int(device), m, S, _ptr(a), pr.size, _ptr(pr), *[_ptr(o) for o in out]))
     return tuple(out)
 
 
@@ -389,10 +385,7 @@ def inclusion_raw(z, ntop, device=0, fields=INCL_FIELDS):
     a = np.ascontiguousarray(a != 0, dtype=np.uint8)
     S, B = a.shape
     ntop, out = _incl_outputs(B, ntop, fields)
-    L = lib()
-    if _foreign_hip:
-        raise BnrError(BNR_ERR_HIP, _foreign_hip)
-    check(L.bnr_inclusion(int(device), S, B, _ptr(a), ntop, *[_ptr(o) for o in out]))
+    check(_device_lib().bnr_inclusion(int(device), S, B, _ptr(a), ntop, *[_ptr(o) for o in out]))
     return _incl_result(out)
 
 
@@ -442,6 +435,94 @@ def xi_weights_code(xi_weights):
     return XI_WEIGHTS[xi_weights]
 
 
+# ------------------------------------------------------------------------------------------ the analysis calls, each written once
+# fn: the name of the library function of one chain (bnr_chain_*) or of a list of chains (bnr_chains_*), looked up on c0.L behind the checks
+# that need no library; head: its leading handle arguments, (chain.h,) or (array of handles, their number) -- and then the weights of a
+# stacked call; c0: the (first) chain, for the sizes.  Chain.<call> and pooled_<call> / stacked_<call> below are their callers.
+def _summary(fn, head, c0, first_row, nsamp, k_lo, k_hi):
+    mean, lo, hi, pxi = np.empty(c0.q), np.empty(c0.q), np.empty(c0.q), np.empty(c0.V)
+    check(getattr(c0.L, fn)(*head, int(first_row), int(nsamp), int(k_lo), int(k_hi), _ptr(mean), _ptr(lo), _ptr(hi), _ptr(pxi)))
+    return mean, lo, hi, pxi
+
+
+def _predict(form, fn, fn_matrices, head, c0, X, first_row, nsamp, k_lo, k_hi, y, x_transform, pred_seed=None, pit=False):
+    """(mean, lower, upper, lpd, pwaic, pred_lower, pred_upper, pit), None what was not asked for.  form: "chain" (no pred_seed and pit
+    arguments), "pooled", or "stacked" (no pwaic and pit arguments, and no fn_matrices)"""
+    xi = X if isinstance(X, XInput) else XInput(X, x_transform)
+    if xi.from_matrices and fn_matrices is None:
+        raise ValueError("the stacked prediction takes a model matrix (n x q), not adjacency matrices")
+    if xi.q != c0.q:
+        raise ValueError("the new rows have %d edge columns, the chain %d" % (xi.q, c0.q))
+    m = xi.n
+    yf = None
+    if y is not None:
+        yf = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+        if yf.shape != (m,):
+            raise ValueError("y must have one entry per new row (%d), not %d" % (m, yf.size))
+    if pit and yf is None:
+        raise ValueError("the PIT needs the observed responses y")
+    mean, lo, hi = np.empty(m), np.empty(m), np.empty(m)
+    lpd = np.empty(m) if yf is not None else None
+    pw = np.empty(m) if yf is not None and form != "stacked" else None
+    plo, phi = (np.empty(m), np.empty(m)) if pred_seed is not None else (None, None)
+    pt = np.empty(m) if pit else None
+    tail = [_ptr(yf), int(k_lo), int(k_hi), _ptr(mean), _ptr(lo), _ptr(hi), _ptr(lpd)]
+    if form != "stacked":
+        tail.append(_ptr(pw))
+    if form != "chain":
+        tail += [C.c_uint64((0 if pred_seed is None else int(pred_seed)) & (2**64 - 1)), _ptr(plo), _ptr(phi)]
+    if form == "pooled":
+        tail.append(_ptr(pt))
+    if xi.from_matrices:
+        ptrs = (C.c_void_p * m)(*[a.ctypes.data for a in xi.data])
+        check(getattr(c0.L, fn_matrices)(*head, int(first_row), int(nsamp), m, ptrs, xi.dtype_code, *tail))
+    else:
+        check(getattr(c0.L, fn)(*head, int(first_row), int(nsamp), m, _ptr(xi.data), xi.dtype_code, *tail))
+    return mean, lo, hi, lpd, pw, plo, phi, pt
+
+
+def _loglik_stats(fn, head, c0, first_row, nsamp, pit=None):
+    """(lpd, pwaic, pit or None); pit=None: fn takes no such argument (bnr_chain_loglik_stats)"""
+    lpd, pw = np.empty(c0.n), np.empty(c0.n)
+    pt = np.empty(c0.n) if pit else None
+    check(getattr(c0.L, fn)(*head, int(first_row), int(nsamp), _ptr(lpd), _ptr(pw), *(() if pit is None else (_ptr(pt),))))
+    return lpd, pw, pt
+
+
+def _loo(fn, head, c0, first_row, nsamp, r_eff):
+    r = r_eff_array(r_eff, c0.n)
+    lpd, elpd, k = np.empty(c0.n), np.empty(c0.n), np.empty(c0.n)
+    check(getattr(c0.L, fn)(*head, int(first_row), int(nsamp), _ptr(r), _ptr(lpd), _ptr(elpd), _ptr(k)))
+    return lpd, elpd, k
+
+
+def _loo_predict(fn, head, c0, first_row, nsamp, r_eff, p_lo, p_hi, fields):
+    r = r_eff_array(r_eff, c0.n)
+    out = [np.empty(c0.n) if f in fields else None for f in LOO_PREDICT_FIELDS]
+    check(getattr(c0.L, fn)(*head, int(first_row), int(nsamp), _ptr(r), p_lo, p_hi, *[_ptr(o) for o in out]))
+    return tuple(out)
+
+
+def _rank_diag(fn, head, c0, first_row, nsamp, max_lag, fields):
+    fields = RANK_DIAG_FIELDS if fields is None else fields
+    out = [np.empty(c0.q + c0.V) if f in fields else None for f in RANK_DIAG_FIELDS]
+    check(getattr(c0.L, fn)(*head, int(first_row), int(nsamp), int(max_lag), *[_ptr(o) for o in out]))
+    return tuple(out)
+
+
+def _hdi(fn, head, c0, first_row, nsamp, probs, fields):
+    pr = hdi_probs(probs)
+    out = _hdi_outputs(pr, c0.q + c0.V, fields)
+    check(getattr(c0.L, fn)(*head, int(first_row), int(nsamp), pr.size, _ptr(pr), *[_ptr(o) for o in out]))
+    return tuple(out)
+
+
+def _inclusion(fn, head, c0, first_row, nsamp, which, ntop, fields):
+    ntop, out = _incl_outputs(c0.R if which == 1 else c0.V, ntop, fields)
+    check(getattr(c0.L, fn)(*head, int(first_row), int(nsamp), int(which), ntop, *[_ptr(o) for o in out]))
+    return _incl_result(out)
+
+
 class Chain:
     """One Gibbs chain resident on one GPU (handle of include/bnr_hip.h).  xi_weights: "log" (default) or "reference" (model
     option "xi_weights": the reference's node weights with their under/overflow, see include/bnr_hip.h)."""
@@ -457,10 +538,8 @@ class Chain:
         self.n, self.q, self.V, self.R, self.tot = n, q, V, int(R), int(tot_save)
         self.h = C.c_void_p()
         hy = Hyper(eta, zeta, iota, aDelta, bDelta, float(nu))
-        self.L = lib()
-        if _foreign_hip:
-            raise BnrError(BNR_ERR_HIP, _foreign_hip)
-        common = (_ptr(yf), C.byref(hy), C.c_uint64(int(seed) & (2**64 - 1)), int(chain_id), int(device), int(tot_save), C.byref(self.h))
+        self.L = _device_lib()
+        common =(_ptr(yf), C.byref(hy), C.c_uint64(int(seed) & (2**64 - 1)), int(chain_id), int(device), int(tot_save), C.byref(self.h))
         if xi.from_matrices:
             ptrs = (C.c_void_p * n)(*[m.ctypes.data for m in xi.data])
             check(self.L.bnr_chain_create_from_matrices(n, V, int(R), ptrs, xi.dtype_code, *common))
@@ -568,55 +647,28 @@ class Chain:
 
     def summary(self, first_row, nsamp, k_lo, k_hi):
         """(mean gamma, k_lo-th smallest, k_hi-th smallest per edge, mean xi per node) over the row window, on the device."""
-        mean, lo, hi, pxi = np.empty(self.q), np.empty(self.q), np.empty(self.q), np.empty(self.V)
-        check(self.L.bnr_chain_summary(self.h, first_row, nsamp, k_lo, k_hi, _ptr(mean), _ptr(lo), _ptr(hi), _ptr(pxi)))
-        return mean, lo, hi, pxi
+        return _summary("bnr_chain_summary", (self.h,), self, first_row, nsamp, k_lo, k_hi)
 
     def predict(self, X, first_row, nsamp, k_lo, k_hi, y=None, x_transform=False):
         """Posterior of the mean response mu + x.gamma of new rows over the row window, on the device (bnr_chain_predict): (mean, k_lo-th
         smallest, k_hi-th smallest, lpd, pwaic) per row; lpd / pwaic are None without y.  X as for Chain(): an m x q matrix in its own element
         type, or (x_transform=True) a list of m V x V matrices."""
-        xi = X if isinstance(X, XInput) else XInput(X, x_transform)
-        if xi.q != self.q:
-            raise ValueError("the new rows have %d edge columns, the chain %d" % (xi.q, self.q))
-        m = xi.n
-        yf = None
-        if y is not None:
-            yf = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-            if yf.shape != (m,):
-                raise ValueError("y must have one entry per new row (%d), not %d" % (m, yf.size))
-        mean, lo, hi = np.empty(m), np.empty(m), np.empty(m)
-        lpd, pw = (np.empty(m), np.empty(m)) if yf is not None else (None, None)
-        tail = (_ptr(yf), int(k_lo), int(k_hi), _ptr(mean), _ptr(lo), _ptr(hi), _ptr(lpd), _ptr(pw))
-        if xi.from_matrices:
-            ptrs = (C.c_void_p * m)(*[a.ctypes.data for a in xi.data])
-            check(self.L.bnr_chain_predict_from_matrices(self.h, int(first_row), int(nsamp), m, ptrs, xi.dtype_code, *tail))
-        else:
-            check(self.L.bnr_chain_predict(self.h, int(first_row), int(nsamp), m, _ptr(xi.data), xi.dtype_code, *tail))
-        return mean, lo, hi, lpd, pw
+        return _predict("chain", "bnr_chain_predict", "bnr_chain_predict_from_matrices", (self.h,), self, X, first_row, nsamp, k_lo, k_hi, y,
+                        x_transform)[:5]
 
     def loglik_stats(self, first_row, nsamp):
         """(lpd, pwaic) of the chain's own training rows over the row window, on the device (bnr_chain_loglik_stats)."""
-        lpd, pw = np.empty(self.n), np.empty(self.n)
-        check(self.L.bnr_chain_loglik_stats(self.h, int(first_row), int(nsamp), _ptr(lpd), _ptr(pw)))
-        return lpd, pw
+        return _loglik_stats("bnr_chain_loglik_stats", (self.h,), self, first_row, nsamp)[:2]
 
     def loo(self, first_row, nsamp, r_eff=None):
         """(lpd, elpd_loo, pareto_k) of the chain's own training rows over the row window: PSIS-LOO on the device (bnr_chain_loo).
         r_eff: None (1), a scalar, or one relative efficiency per training row."""
-        r = r_eff_array(r_eff, self.n)
-        lpd, elpd, k = np.empty(self.n), np.empty(self.n), np.empty(self.n)
-        check(self.L.bnr_chain_loo(self.h, int(first_row), int(nsamp), _ptr(r), _ptr(lpd), _ptr(elpd), _ptr(k)))
-        return lpd, elpd, k
+        return _loo("bnr_chain_loo", (self.h,), self, first_row, nsamp, r_eff)
 
     def loo_predict(self, first_row, nsamp, r_eff=None, p_lo=0.025, p_hi=0.975):
         """The LOO predictive checks of the chain's own training rows over the row window, on the device (bnr_chain_loo_predict): the tuple
         LOO_PREDICT_FIELDS = (lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper), one entry per row each."""
-        p_lo, p_hi = loo_probs(p_lo, p_hi)
-        r = r_eff_array(r_eff, self.n)
-        out = [np.empty(self.n) for _ in LOO_PREDICT_FIELDS]
-        check(self.L.bnr_chain_loo_predict(self.h, int(first_row), int(nsamp), _ptr(r), p_lo, p_hi, *[_ptr(o) for o in out]))
-        return tuple(out)
+        return _loo_predict("bnr_chain_loo_predict", (self.h,), self, first_row, nsamp, r_eff, *loo_probs(p_lo, p_hi), LOO_PREDICT_FIELDS)
 
     def ess_stats(self, first_row, nsamp, max_lag):
         out = np.empty(2 * (2 + max_lag) * (self.q + self.V))
@@ -626,27 +678,19 @@ class Chain:
     def rank_diag(self, first_row, nsamp, max_lag, fields=None):
         """The rank-normalised diagnostics of this chain's window, on the device (bnr_chain_rank_diag): the tuple RANK_DIAG_FIELDS, each q + V
         values (gamma first); an entry not named in `fields` is not requested and comes back as None"""
-        fields = RANK_DIAG_FIELDS if fields is None else fields
-        out = [np.empty(self.q + self.V) if f in fields else None for f in RANK_DIAG_FIELDS]
-        check(self.L.bnr_chain_rank_diag(self.h, int(first_row), int(nsamp), int(max_lag), *[_ptr(o) for o in out]))
-        return tuple(out)
+        return _rank_diag("bnr_chain_rank_diag", (self.h,), self, first_row, nsamp, max_lag, fields)
 
     def hdi(self, first_row, nsamp, probs, fields=HDI_FIELDS):
         """The highest-density intervals, medians and sign probabilities of this chain's window, on the device (bnr_chain_hdi): the tuple
         HDI_FIELDS over the q + V parameters (gamma first), lower / upper one row per level of `probs`; an entry not named in `fields` is not
         requested and comes back as None"""
-        pr = hdi_probs(probs)
-        out = _hdi_outputs(pr, self.q + self.V, fields)
-        check(self.L.bnr_chain_hdi(self.h, int(first_row), int(nsamp), pr.size, _ptr(pr), *[_ptr(o) for o in out]))
-        return tuple(out)
+        return _hdi("bnr_chain_hdi", (self.h,), self, first_row, nsamp, probs, fields)
 
     def inclusion(self, first_row, nsamp, which, ntop, fields=INCL_FIELDS):
         """The joint posterior of this chain's indicators over its window, on the device (bnr_chain_inclusion): the tuple INCL_FIELDS of the V
         node indicators xi (which = 0) or of the R dimensions lambda != 0 (which = 1), see inclusion_raw; an entry not named in `fields` is
         not requested and comes back as None"""
-        ntop, out = _incl_outputs(self.R if which == 1 else self.V, ntop, fields)
-        check(self.L.bnr_chain_inclusion(self.h, int(first_row), int(nsamp), int(which), ntop, *[_ptr(o) for o in out]))
-        return _incl_result(out)
+        return _inclusion("bnr_chain_inclusion", (self.h,), self, first_row, nsamp, which, ntop, fields)
 
     def counters(self):
         out = (C.c_int64 * 8)()
@@ -743,11 +787,11 @@ class Group:
 
 # ------------------------------------------------------------------------------------------ pooled chains (bnr_chains_* of include/bnr_hip.h)
 def _pooled(chains):
-    """(list of the chains, their handles as a C array): the chains of one fit on one device whose windows are pooled, in this order"""
+    """(the first chain, (the handles as a C array, their number)): the chains of one fit on one device whose windows are pooled, in this order"""
     chains = list(chains)
     if not chains:
         raise ValueError("need at least one chain")
-    return chains, (C.c_void_p * len(chains))(*[ch.h for ch in chains])
+    return chains[0], ((C.c_void_p * len(chains))(*[ch.h for ch in chains]), len(chains))
 
 
 def host_pred_noise(seed, s0, ns, i0, ni):
@@ -760,103 +804,55 @@ def host_pred_noise(seed, s0, ns, i0, ni):
 
 def pooled_summary(chains, first_row, nsamp, k_lo, k_hi):
     """Chain.summary over the pooled window of `chains` (bnr_chains_summary); ranks in 1 .. len(chains) * nsamp"""
-    chains, arr = _pooled(chains)
-    c0 = chains[0]
-    mean, lo, hi, pxi = np.empty(c0.q), np.empty(c0.q), np.empty(c0.q), np.empty(c0.V)
-    check(c0.L.bnr_chains_summary(arr, len(chains), int(first_row), int(nsamp), int(k_lo), int(k_hi), _ptr(mean), _ptr(lo), _ptr(hi), _ptr(pxi)))
-    return mean, lo, hi, pxi
+    c0, head = _pooled(chains)
+    return _summary("bnr_chains_summary", head, c0, first_row, nsamp, k_lo, k_hi)
 
 
 def pooled_predict(chains, X, first_row, nsamp, k_lo, k_hi, y=None, x_transform=False, pred_seed=None, pit=False):
     """Chain.predict over the pooled window of `chains` (bnr_chains_predict / _from_matrices): (mean, lower, upper, lpd, pwaic, pred_lower,
     pred_upper, pit) per row.  pred_seed given: the k_lo-th / k_hi-th smallest draw of a new observation (None otherwise); pit=True (needs y):
     the PIT of the observed responses."""
-    chains, arr = _pooled(chains)
-    c0 = chains[0]
-    xi = X if isinstance(X, XInput) else XInput(X, x_transform)
-    if xi.q != c0.q:
-        raise ValueError("the new rows have %d edge columns, the chain %d" % (xi.q, c0.q))
-    m = xi.n
-    yf = None
-    if y is not None:
-        yf = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-        if yf.shape != (m,):
-            raise ValueError("y must have one entry per new row (%d), not %d" % (m, yf.size))
-    if pit and yf is None:
-        raise ValueError("the PIT needs the observed responses y")
-    mean, lo, hi = np.empty(m), np.empty(m), np.empty(m)
-    lpd, pw = (np.empty(m), np.empty(m)) if yf is not None else (None, None)
-    plo, phi = (np.empty(m), np.empty(m)) if pred_seed is not None else (None, None)
-    pt = np.empty(m) if pit else None
-    tail = (_ptr(yf), int(k_lo), int(k_hi), _ptr(mean), _ptr(lo), _ptr(hi), _ptr(lpd), _ptr(pw),
-            C.c_uint64((0 if pred_seed is None else int(pred_seed)) & (2**64 - 1)), _ptr(plo), _ptr(phi), _ptr(pt))
-    if xi.from_matrices:
-        ptrs = (C.c_void_p * m)(*[a.ctypes.data for a in xi.data])
-        check(c0.L.bnr_chains_predict_from_matrices(arr, len(chains), int(first_row), int(nsamp), m, ptrs, xi.dtype_code, *tail))
-    else:
-        check(c0.L.bnr_chains_predict(arr, len(chains), int(first_row), int(nsamp), m, _ptr(xi.data), xi.dtype_code, *tail))
-    return mean, lo, hi, lpd, pw, plo, phi, pt
+    c0, head = _pooled(chains)
+    return _predict("pooled", "bnr_chains_predict", "bnr_chains_predict_from_matrices", head, c0, X, first_row, nsamp, k_lo, k_hi, y, x_transform,
+                    pred_seed, pit)
 
 
 def pooled_loglik_stats(chains, first_row, nsamp, pit=False):
     """(lpd, pwaic, pit or None) of the training rows over the pooled window of `chains` (bnr_chains_loglik_stats)"""
-    chains, arr = _pooled(chains)
-    n = chains[0].n
-    lpd, pw = np.empty(n), np.empty(n)
-    pt = np.empty(n) if pit else None
-    check(chains[0].L.bnr_chains_loglik_stats(arr, len(chains), int(first_row), int(nsamp), _ptr(lpd), _ptr(pw), _ptr(pt)))
-    return lpd, pw, pt
+    c0, head = _pooled(chains)
+    return _loglik_stats("bnr_chains_loglik_stats", head, c0, first_row, nsamp, bool(pit))
 
 
 def pooled_loo(chains, first_row, nsamp, r_eff=None):
     """(lpd, elpd_loo, pareto_k) of the training rows over the pooled window of `chains`: PSIS-LOO on the device (bnr_chains_loo)"""
-    chains, arr = _pooled(chains)
-    n = chains[0].n
-    r = r_eff_array(r_eff, n)
-    lpd, elpd, k = np.empty(n), np.empty(n), np.empty(n)
-    check(chains[0].L.bnr_chains_loo(arr, len(chains), int(first_row), int(nsamp), _ptr(r), _ptr(lpd), _ptr(elpd), _ptr(k)))
-    return lpd, elpd, k
+    c0, head = _pooled(chains)
+    return _loo("bnr_chains_loo", head, c0, first_row, nsamp, r_eff)
 
 
 def pooled_loo_predict(chains, first_row, nsamp, r_eff=None, p_lo=0.025, p_hi=0.975, fields=LOO_PREDICT_FIELDS):
     """Chain.loo_predict over the pooled window of `chains` (bnr_chains_loo_predict): the tuple LOO_PREDICT_FIELDS; an entry not named in
     `fields` is not requested from the library and comes back as None"""
     p_lo, p_hi = loo_probs(p_lo, p_hi)
-    chains, arr = _pooled(chains)
-    n = chains[0].n
-    r = r_eff_array(r_eff, n)
-    out = [np.empty(n) if f in fields else None for f in LOO_PREDICT_FIELDS]
-    check(chains[0].L.bnr_chains_loo_predict(arr, len(chains), int(first_row), int(nsamp), _ptr(r), p_lo, p_hi, *[_ptr(o) for o in out]))
-    return tuple(out)
+    c0, head = _pooled(chains)
+    return _loo_predict("bnr_chains_loo_predict", head, c0, first_row, nsamp, r_eff, p_lo, p_hi, fields)
 
 
 def pooled_rank_diag(chains, first_row, nsamp, max_lag, fields=None):
     """Chain.rank_diag over the pooled window of `chains` (bnr_chains_rank_diag): the tuple RANK_DIAG_FIELDS"""
-    chains, arr = _pooled(chains)
-    c0 = chains[0]
-    fields = RANK_DIAG_FIELDS if fields is None else fields
-    out = [np.empty(c0.q + c0.V) if f in fields else None for f in RANK_DIAG_FIELDS]
-    check(c0.L.bnr_chains_rank_diag(arr, len(chains), int(first_row), int(nsamp), int(max_lag), *[_ptr(o) for o in out]))
-    return tuple(out)
+    c0, head = _pooled(chains)
+    return _rank_diag("bnr_chains_rank_diag", head, c0, first_row, nsamp, max_lag, fields)
 
 
 def pooled_hdi(chains, first_row, nsamp, probs, fields=HDI_FIELDS):
     """Chain.hdi over the pooled window of `chains` (bnr_chains_hdi): the tuple HDI_FIELDS"""
-    chains, arr = _pooled(chains)
-    c0 = chains[0]
-    pr = hdi_probs(probs)
-    out = _hdi_outputs(pr, c0.q + c0.V, fields)
-    check(c0.L.bnr_chains_hdi(arr, len(chains), int(first_row), int(nsamp), pr.size, _ptr(pr), *[_ptr(o) for o in out]))
-    return tuple(out)
+    c0, head = _pooled(chains)
+    return _hdi("bnr_chains_hdi", head, c0, first_row, nsamp, probs, fields)
 
 
 def pooled_inclusion(chains, first_row, nsamp, which, ntop, fields=INCL_FIELDS):
     """Chain.inclusion over the pooled window of `chains` (bnr_chains_inclusion): the tuple INCL_FIELDS"""
-    chains, arr = _pooled(chains)
-    c0 = chains[0]
-    ntop, out = _incl_outputs(c0.R if which == 1 else c0.V, ntop, fields)
-    check(c0.L.bnr_chains_inclusion(arr, len(chains), int(first_row), int(nsamp), int(which), ntop, *[_ptr(o) for o in out]))
-    return _incl_result(out)
+    c0, head = _pooled(chains)
+    return _inclusion("bnr_chains_inclusion", head, c0, first_row, nsamp, which, ntop, fields)
 
 
 # ------------------------------------------------------------------------------------------ chain stacking (ABI 16)
@@ -894,59 +890,36 @@ def wquantile_raw(x, weights, nchains, k_lo, k_hi, device=0, fields=WQUANTILE_FI
     w = stack_weights_array(weights, K)
     m, S = a.shape
     out = [np.empty(m) if f in fields else None for f in WQUANTILE_FIELDS]
-    L = lib()
-    if _foreign_hip:
-        raise BnrError(BNR_ERR_HIP, _foreign_hip)
-    check(L.bnr_wquantile(int(device), m, K, S // K, _ptr(a), _ptr(w), int(k_lo), int(k_hi), *[_ptr(o) for o in out]))
+    check(_device_lib().bnr_wquantile(int(device), m, K, S // K, _ptr(a), _ptr(w), int(k_lo), int(k_hi), *[_ptr(o) for o in out]))
     return tuple(out)
 
 
 def chains_stack(chains, first_row, nsamp, r_eff=None, max_iter=100000, gap_tol=1e-9):
     """(weights, elpd_chain K x n, pareto_k_chain K x n, elpd_stack n, gap, iterations): per-chain PSIS-LOO and the stacking weights
     (bnr_chains_stack)"""
-    chains, arr = _pooled(chains)
-    n, K = chains[0].n, len(chains)
+    c0, (arr, K) = _pooled(chains)
+    n = c0.n
     r = r_eff_array(r_eff, n)
     w, el, kh, es = np.empty(K), np.empty((K, n)), np.empty((K, n)), np.empty(n)
     g, it = C.c_double(0.0), C.c_int32(0)
-    check(chains[0].L.bnr_chains_stack(arr, K, int(first_row), int(nsamp), _ptr(r), int(max_iter), float(gap_tol), _ptr(w), _ptr(el), _ptr(kh), _ptr(es),
-                                       C.byref(g), C.byref(it)))
+    check(c0.L.bnr_chains_stack(arr, K, int(first_row), int(nsamp), _ptr(r), int(max_iter), float(gap_tol), _ptr(w), _ptr(el), _ptr(kh), _ptr(es),
+                                C.byref(g), C.byref(it)))
     return w, el, kh, es, g.value, it.value
 
 
 def stacked_summary(chains, weights, first_row, nsamp, k_lo, k_hi):
     """pooled_summary under chain weights (bnr_chains_wsummary)"""
-    chains, arr = _pooled(chains)
-    c0 = chains[0]
-    w = stack_weights_array(weights, len(chains))
-    mean, lo, hi, pxi = np.empty(c0.q), np.empty(c0.q), np.empty(c0.q), np.empty(c0.V)
-    check(c0.L.bnr_chains_wsummary(arr, len(chains), _ptr(w), int(first_row), int(nsamp), int(k_lo), int(k_hi), _ptr(mean), _ptr(lo), _ptr(hi), _ptr(pxi)))
-    return mean, lo, hi, pxi
+    c0, head = _pooled(chains)
+    w = stack_weights_array(weights, head[1])
+    return _summary("bnr_chains_wsummary", head + (_ptr(w),), c0, first_row, nsamp, k_lo, k_hi)
 
 
 def stacked_predict(chains, weights, X, first_row, nsamp, k_lo, k_hi, y=None, x_transform=False, pred_seed=None):
     """pooled_predict under chain weights for a model matrix (bnr_chains_wpredict): (mean, lower, upper, lpd, pred_lower, pred_upper) per row"""
-    chains, arr = _pooled(chains)
-    c0 = chains[0]
-    w = stack_weights_array(weights, len(chains))
-    xi = X if isinstance(X, XInput) else XInput(X, x_transform)
-    if xi.from_matrices:
-        raise ValueError("the stacked prediction takes a model matrix (n x q), not adjacency matrices")
-    if xi.q != c0.q:
-        raise ValueError("the new rows have %d edge columns, the chain %d" % (xi.q, c0.q))
-    m = xi.n
-    yf = None
-    if y is not None:
-        yf = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-        if yf.shape != (m,):
-            raise ValueError("y must have one entry per new row (%d), not %d" % (m, yf.size))
-    mean, lo, hi = np.empty(m), np.empty(m), np.empty(m)
-    lpd = np.empty(m) if yf is not None else None
-    plo, phi = (np.empty(m), np.empty(m)) if pred_seed is not None else (None, None)
-    check(c0.L.bnr_chains_wpredict(arr, len(chains), _ptr(w), int(first_row), int(nsamp), m, _ptr(xi.data), xi.dtype_code, _ptr(yf), int(k_lo), int(k_hi),
-                                   _ptr(mean), _ptr(lo), _ptr(hi), _ptr(lpd), C.c_uint64((0 if pred_seed is None else int(pred_seed)) & (2**64 - 1)),
-                                   _ptr(plo), _ptr(phi)))
-    return mean, lo, hi, lpd, plo, phi
+    c0, head = _pooled(chains)
+    w = stack_weights_array(weights, head[1])
+    r = _predict("stacked", "bnr_chains_wpredict", None, head + (_ptr(w),), c0, X, first_row, nsamp, k_lo, k_hi, y, x_transform, pred_seed)
+    return r[:4] + r[5:7]
 
 
 class Comm:

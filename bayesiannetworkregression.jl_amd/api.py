@@ -1527,19 +1527,6 @@ def Stacking(results, X=None, y=None, x_transform=True, tables=None, r_eff=None)
     return _host_stack_chains(tables, X, y, results.burn_in, results.sampled, x_transform, r_eff)
 
 
-def _stack_request(stack_chains, num_chains):
-    """Fit's stack_chains checked before any sampling: at least two chains, and like pool_chains every chain of the fit on this rank"""
-    if not stack_chains:
-        return False
-    if int(num_chains) < 2:
-        raise ValueError("stack_chains needs num_chains >= 2: one chain has nothing to be weighted against")
-    if int(num_chains) > STACK_MAX_CHAINS:
-        raise ValueError("stack_chains takes at most %d chains" % STACK_MAX_CHAINS)
-    if _rank_world()[1] > 1:
-        raise ValueError("stack_chains needs every chain of the fit on one rank: the chains are spread over %d torch.distributed ranks" % _rank_world()[1])
-    return True
-
-
 # ------------------------------------------------------------------------------------------ chain placement
 def _dist():
     """torch.distributed if THE CALLER has imported and initialised it, else None.  Never imports torch itself: a process group can only
@@ -1764,151 +1751,136 @@ def return_psrf_VOI(chainset, nburn, nsamp, fetch_state=True, summary_interval=N
     return Results(state, rx, rg, nburn, nsamp, dev)
 
 
-def _finish(chainset, res, return_state, summary_interval, ess_max_lag=None, predict=None, waic=False, loo=False, loo_r_eff=None,
-            pool_chains=False, predict_observation=False, pred_seed=0, loo_predict=None, rank_diag=False, edge_sel=None, node_sets=None,
-            stack=False):
-    """The Results a fit returns: chain 1's table (states[1], gibbs.jl:788) and/or its Summary statistics from the device; predict =
-    (new rows, their y or None, interval), waic=True and loo=True add the prediction, WAIC and PSIS-LOO computed on the device over the
-    same window.  pool_chains: those statistics over the pooled windows of all chains of the fit (one rank holds them all);
-    predict_observation: the prediction through the pooled entry point (one chain unless pool_chains) with the predictive bounds and the PIT;
-    loo_predict = (training y, interval): the LOO predictive checks (Results.loo_predictive), and Results.loo from the same call.
+@dataclass(frozen=True)
+class _Requests:
+    """What a fit computes behind the sampling, as _fit_requests checked it and _finish takes it"""
+    return_state: bool
+    summary_interval: float          # the credible level of the Summary statistics from the device, or None
+    ess_max_lag: int                 # None: no ESS; 0: the default lag window
+    predict: tuple                   # (new rows, their y or None, interval), or None
+    waic: bool
+    loo: bool
+    loo_r_eff: object
+    pool_chains: bool
+    predict_observation: bool
+    pred_seed: int                   # None: the fit's seed
+    loo_predict: tuple               # (training y, interval), or None
+    rank_diag: bool
+    edge_sel: tuple                  # (hdi_prob, fdr), or None
+    node_sets: int                   # the number of top node sets, or None
+    stack: bool
+
+
+def _one_rank(option):
+    """the refusal of an option that reads every chain of the fit where the chains are spread over several ranks"""
+    if _rank_world()[1] > 1:
+        raise ValueError("%s needs every chain of the fit on one rank: the chains are spread over %d torch.distributed ranks" % (option, _rank_world()[1]))
+
+
+def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, return_state=True, summary_interval=None, ess_max_lag=None, predict_X=None,
+                  predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None, pool_chains=False, predict_observation=False,
+                  pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False, hdi_prob=0.95, fdr=0.05, node_sets=False,
+                  top_sets=10, stack_chains=False):
+    """The options of a fit (Fit's keywords) checked before any sampling, in this order -> _Requests.  Fit itself calls it ahead of
+    parameters.log for the refusals alone, without X_new and nsamp: what needs them -- the new rows, the lag window of the rank diagnostics,
+    r_eff -- is then left to generate_samples / generate_samples_dbl."""
+    pred = None
+    if X_new is not None:
+        if predict_X is None and predict_y is not None:
+            raise ValueError("predict_y needs predict_X")
+        if predict_X is not None:
+            pred = (_new_rows(predict_X, x_transform, X_new.q, predict_y),
+                    None if predict_y is None else np.asarray(predict_y, dtype=np.float64).reshape(-1), predict_interval)
+    if predict_observation and predict_X is None:
+        raise ValueError("predict_observation needs predict_X")
+    if pool_chains:
+        _one_rank("pool_chains")
+    lp = None
+    if loo_predict:
+        _one_rank("loo_predict")
+        _loo_interval_probs(predict_interval)
+        lp = (np.asarray(y, dtype=np.float64).reshape(-1), predict_interval)
+    if rank_diagnostics:
+        _one_rank("rank_diagnostics")
+        if nsamp is not None:
+            _rank_lag(nsamp, ess_max_lag if ess_max_lag else None)
+    es = ntop = None
+    if edge_selection:
+        _one_rank("edge_selection")
+        es = _edge_levels(hdi_prob, fdr)
+    if node_sets:
+        _one_rank("node_sets")
+        ntop = _node_sets_ntop(top_sets)
+    if stack_chains:
+        if int(num_chains) < 2:
+            raise ValueError("stack_chains needs num_chains >= 2: one chain has nothing to be weighted against")
+        if int(num_chains) > STACK_MAX_CHAINS:
+            raise ValueError("stack_chains takes at most %d chains" % STACK_MAX_CHAINS)
+        _one_rank("stack_chains")
+    if X_new is not None:
+        _capi.r_eff_array(loo_r_eff, X_new.n)
+    return _Requests(return_state, summary_interval, ess_max_lag, pred, bool(waic), bool(loo), loo_r_eff, bool(pool_chains), bool(predict_observation),
+                     pred_seed, lp, bool(rank_diagnostics), es, ntop, bool(stack_chains))
+
+
+def _finish(chainset, res, req, seed):
+    """The Results a fit returns, from its checked requests (_Requests; seed: the fit's, which keys the predictive noise unless pred_seed does).
+    By default chain 1's table (states[1], gibbs.jl:788) and/or its Summary statistics, the prediction, WAIC and PSIS-LOO from the device over
+    chain 1's window, through the single-chain calls.  pool_chains: those statistics over the pooled windows of all chains of the fit (one rank
+    holds them all); predict_observation: through the pooled calls as well (over chain 1 alone unless pool_chains), which add the predictive
+    bounds and the PITs.  loo_predict: the LOO predictive checks (Results.loo_predictive), and Results.loo from the same call.
     rank_diag: the rank-normalised diagnostics over every chain of the fit (Results.rank_diag; ess_max_lag, where positive, is their lag window).
-    edge_sel = (hdi_prob, fdr): the HDIs, sign probabilities and selected edges over every chain of the fit (Results.edge_selection).
-    node_sets = the number of top node sets: the joint posterior of the node indicators over every chain of the fit (Results.node_sets).
+    edge_sel: the HDIs, sign probabilities and selected edges over every chain of the fit (Results.edge_selection).
+    node_sets: the joint posterior of the node indicators over every chain of the fit (Results.node_sets).
     stack: the chain stacking over every chain of the fit (Results.stacking), with summary_interval its summary and with predict its
     prediction under the weights; what pool_chains or the default return is not changed by it."""
-    if stack:
-        chains = [chainset.chains[c] for c in chainset.ids]
-        st = device_stack_chains(chains, res.burn_in, res.sampled, loo_r_eff)
-        if summary_interval is not None:
-            st.summary = device_summary_stacked(chains, st.weights, res.burn_in, res.sampled, summary_interval)
-        if predict is not None:
-            st.prediction = device_predict_stacked(chains, st.weights, res.burn_in, res.sampled, predict[0], predict[1], predict[2], pred_seed,
-                                                   predict_observation=predict_observation)
+    nb, ns = res.burn_in, res.sampled
+    every = [chainset.chains[c] for c in chainset.ids]
+    pred_seed = seed if req.pred_seed is None else req.pred_seed
+    if req.stack:
+        st = device_stack_chains(every, nb, ns, req.loo_r_eff)
+        if req.summary_interval is not None:
+            st.summary = device_summary_stacked(every, st.weights, nb, ns, req.summary_interval)
+        if req.predict is not None:
+            st.prediction = device_predict_stacked(every, st.weights, nb, ns, *req.predict, pred_seed, predict_observation=req.predict_observation)
         res.stacking = st
-    if node_sets is not None:
-        res.node_sets = device_node_sets([chainset.chains[c] for c in chainset.ids], res.burn_in, res.sampled, node_sets)
-    if edge_sel is not None:
-        res.edge_selection = device_edge_selection([chainset.chains[c] for c in chainset.ids], res.burn_in, res.sampled, edge_sel[0], edge_sel[1])
-    if rank_diag:
-        res.rank_diag = device_rank_diagnostics([chainset.chains[c] for c in chainset.ids], res.burn_in, res.sampled, ess_max_lag if ess_max_lag else None)
-    if pool_chains or predict_observation:
-        return _finish_pooled(chainset, res, return_state, summary_interval, ess_max_lag, predict, waic, loo, loo_r_eff, pool_chains,
-                              predict_observation, pred_seed, loo_predict)
-    if ess_max_lag is not None:                       # collective over ranks, like the PSRF
-        res.essgamma, res.essxi = chainset.ess(res.burn_in + 1, res.sampled, ess_max_lag if ess_max_lag > 0 else None)
-    if 1 in chainset.chains:
-        ch = chainset.chains[1]
-        if return_state:
-            res.state = new_table(ch.tot, ch.V, ch.R, dead=True)
-            ch.fetch(1, ch.tot, res.state)
-        if summary_interval is not None:
-            res.summary_device = device_summary(ch, res.burn_in, res.sampled, summary_interval)
-        if predict is not None:
-            res.prediction = device_predict(ch, res.burn_in, res.sampled, predict[0], predict[1], predict[2])
-        if waic:
-            res.waic = _waic_from_pointwise(*ch.loglik_stats(res.burn_in + 1, res.sampled))
-        if loo_predict is not None:                   # (implies loo: both from one call)
-            lp = device_loo_predict([ch], loo_predict[0], res.burn_in, res.sampled, loo_predict[1], loo_r_eff)
-            res.loo_predictive = lp
-            res.loo = _loo_from_pointwise(lp.lpd_i, lp.elpd_loo_i, lp.pareto_k, res.sampled)
-        elif loo:
-            res.loo = _loo_from_pointwise(*ch.loo(res.burn_in + 1, res.sampled, loo_r_eff), res.sampled)
-        if summary_interval is not None or predict is not None or waic or loo or loo_predict is not None:
-            res.stat_chains = 1
-    return res
-
-
-def _finish_pooled(chainset, res, return_state, summary_interval, ess_max_lag, predict, waic, loo, loo_r_eff, pool_chains, predict_observation,
-                   pred_seed, loo_predict=None):
-    """_finish through the pooled entry points: over every chain of the fit (pool_chains), or over chain 1 alone with the predictive extras"""
-    if ess_max_lag is not None:
-        res.essgamma, res.essxi = chainset.ess(res.burn_in + 1, res.sampled, ess_max_lag if ess_max_lag > 0 else None)
+    if req.node_sets is not None:
+        res.node_sets = device_node_sets(every, nb, ns, req.node_sets)
+    if req.edge_sel is not None:
+        res.edge_selection = device_edge_selection(every, nb, ns, *req.edge_sel)
+    if req.rank_diag:
+        res.rank_diag = device_rank_diagnostics(every, nb, ns, req.ess_max_lag if req.ess_max_lag else None)
+    if req.ess_max_lag is not None:                   # collective over ranks, like the PSRF
+        res.essgamma, res.essxi = chainset.ess(nb + 1, ns, req.ess_max_lag if req.ess_max_lag > 0 else None)
     if 1 not in chainset.chains:
         return res
     ch = chainset.chains[1]
-    chains = [chainset.chains[c] for c in chainset.ids] if pool_chains else [ch]
-    nb, ns = res.burn_in, res.sampled
+    pooled = req.pool_chains or req.predict_observation        # through the pooled calls: over every chain, or over chain 1 with their extras
+    chains = every if req.pool_chains else [ch]
     S = ns * len(chains)
-    if return_state:
+    if req.return_state:
         res.state = new_table(ch.tot, ch.V, ch.R, dead=True)
         ch.fetch(1, ch.tot, res.state)
-    if summary_interval is not None:
-        res.summary_device = device_summary_pooled(chains, nb, ns, summary_interval)
-    if predict is not None:
-        res.prediction = device_predict_pooled(chains, nb, ns, predict[0], predict[1], predict[2], pred_seed, predict_observation=predict_observation)
-    if waic:
+    if req.summary_interval is not None:
+        res.summary_device = (device_summary_pooled(chains, nb, ns, req.summary_interval) if pooled
+                              else device_summary(ch, nb, ns, req.summary_interval))
+    if req.predict is not None:
+        res.prediction = (device_predict_pooled(chains, nb, ns, *req.predict, pred_seed, predict_observation=req.predict_observation) if pooled
+                          else device_predict(ch, nb, ns, *req.predict))
+    if req.waic and pooled:
         lpd, pw, pit = _capi.pooled_loglik_stats(chains, nb + 1, ns, pit=True)
         res.waic = dict(_waic_from_pointwise(lpd, pw), pit_i=pit)
-    if loo_predict is not None:                       # (implies loo: both from one call)
-        lp = device_loo_predict(chains, loo_predict[0], nb, ns, loo_predict[1], loo_r_eff)
+    elif req.waic:
+        res.waic = _waic_from_pointwise(*ch.loglik_stats(nb + 1, ns))
+    if req.loo_predict is not None:                   # (implies loo: both from one call)
+        lp = device_loo_predict(chains, req.loo_predict[0], nb, ns, req.loo_predict[1], req.loo_r_eff)
         res.loo_predictive = lp
         res.loo = _loo_from_pointwise(lp.lpd_i, lp.elpd_loo_i, lp.pareto_k, S)
-    elif loo:
-        res.loo = _loo_from_pointwise(*_capi.pooled_loo(chains, nb + 1, ns, loo_r_eff), S)
-    if summary_interval is not None or predict is not None or waic or loo or loo_predict is not None:
+    elif req.loo:
+        res.loo = _loo_from_pointwise(*(_capi.pooled_loo(chains, nb + 1, ns, req.loo_r_eff) if pooled else ch.loo(nb + 1, ns, req.loo_r_eff)), S)
+    if req.summary_interval is not None or req.predict is not None or req.waic or req.loo or req.loo_predict is not None:
         res.stat_chains = len(chains)
     return res
-
-
-def _loo_predict_request(loo_predict, predict_interval, y):
-    """Fit's loo_predict checked before any sampling: (training y, interval) for _finish, or None.  Refused where pool_chains is: the chains
-    of the fit spread over several ranks."""
-    if not loo_predict:
-        return None
-    if _rank_world()[1] > 1:
-        raise ValueError("loo_predict needs every chain of the fit on one rank: the chains are spread over %d torch.distributed ranks" % _rank_world()[1])
-    _loo_interval_probs(predict_interval)
-    return np.asarray(y, dtype=np.float64).reshape(-1), predict_interval
-
-
-def _rank_diag_request(rank_diagnostics, nsamp=None, ess_max_lag=None):
-    """Fit's rank_diagnostics checked before any sampling: like pool_chains it needs every chain of the fit on this rank"""
-    if not rank_diagnostics:
-        return False
-    if _rank_world()[1] > 1:
-        raise ValueError("rank_diagnostics needs every chain of the fit on one rank: the chains are spread over %d torch.distributed ranks" % _rank_world()[1])
-    if nsamp is not None:
-        _rank_lag(nsamp, ess_max_lag if ess_max_lag else None)
-    return True
-
-
-def _edge_selection_request(edge_selection, hdi_prob, fdr):
-    """Fit's edge_selection checked before any sampling: (hdi_prob, fdr) for _finish, or None.  Like rank_diagnostics it needs every chain of
-    the fit on this rank."""
-    if not edge_selection:
-        return None
-    if _rank_world()[1] > 1:
-        raise ValueError("edge_selection needs every chain of the fit on one rank: the chains are spread over %d torch.distributed ranks" % _rank_world()[1])
-    return _edge_levels(hdi_prob, fdr)
-
-
-def _node_sets_request(node_sets, top_sets):
-    """Fit's node_sets checked before any sampling: the number of top node sets for _finish, or None.  Like edge_selection it needs every chain
-    of the fit on this rank."""
-    if not node_sets:
-        return None
-    if _rank_world()[1] > 1:
-        raise ValueError("node_sets needs every chain of the fit on one rank: the chains are spread over %d torch.distributed ranks" % _rank_world()[1])
-    return _node_sets_ntop(top_sets)
-
-
-def _pooled_request(pool_chains, predict_observation, predict_X):
-    """Fit's pool_chains / predict_observation checked before any sampling"""
-    if predict_observation and predict_X is None:
-        raise ValueError("predict_observation needs predict_X")
-    if pool_chains and _rank_world()[1] > 1:
-        raise ValueError("pool_chains needs every chain of the fit on one rank: the chains are spread over %d torch.distributed ranks" % _rank_world()[1])
-
-
-def _predict_request(predict_X, predict_y, predict_interval, x_transform, X_new):
-    """Fit's predict_X / predict_y checked before any sampling: (new rows, y, interval) for _finish, or None"""
-    if predict_X is None:
-        if predict_y is not None:
-            raise ValueError("predict_y needs predict_X")
-        return None
-    xi = _new_rows(predict_X, x_transform, X_new.q, predict_y)
-    return xi, None if predict_y is None else np.asarray(predict_y, dtype=np.float64).reshape(-1), predict_interval
 
 
 class _Progress:
@@ -1949,14 +1921,11 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
     elif nu == R:
         print("Warning: ν==R may give poor accuracy. Consider increasing ν")
     X_new = XInput(X, x_transform)                 # X_new of gibbs.jl:907-918: element type kept, setup_X! runs on the device
-    pred = _predict_request(predict_X, predict_y, predict_interval, x_transform, X_new)
-    _pooled_request(pool_chains, predict_observation, predict_X)
-    lp_req = _loo_predict_request(loo_predict, predict_interval, y)
-    rd_req = _rank_diag_request(rank_diagnostics, nsamp, ess_max_lag)
-    es_req = _edge_selection_request(edge_selection, hdi_prob, fdr)
-    ns_req = _node_sets_request(node_sets, top_sets)
-    sk_req = _stack_request(stack_chains, num_chains)
-    _capi.r_eff_array(loo_r_eff, X_new.n)              # (checked before any sampling)
+    req = _fit_requests(y, num_chains, X_new, nsamp, x_transform, return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
+                        predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic, loo=loo, loo_r_eff=loo_r_eff,
+                        pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed, loo_predict=loo_predict,
+                        rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets,
+                        top_sets=top_sets, stack_chains=stack_chains)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -1998,8 +1967,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
         print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()), file=sys.stderr)
     print("R = %s nu=%s nburn= %d nsamp = %d" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f\n" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
-    res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff, pool_chains, predict_observation,
-                  seed_eff if pred_seed is None else pred_seed, lp_req, rd_req, es_req, ns_req, sk_req)
+    res = _finish(cs, res, req, seed_eff)
     if _keep is None:
         cs.close()
     return res
@@ -2018,14 +1986,11 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
     nburn = _julia_round(mingen / 2)
     nsamp = mingen - nburn
     X_new = XInput(X, x_transform)
-    pred = _predict_request(predict_X, predict_y, predict_interval, x_transform, X_new)
-    _pooled_request(pool_chains, predict_observation, predict_X)
-    lp_req = _loo_predict_request(loo_predict, predict_interval, y)
-    rd_req = _rank_diag_request(rank_diagnostics, nsamp, ess_max_lag)
-    es_req = _edge_selection_request(edge_selection, hdi_prob, fdr)
-    ns_req = _node_sets_request(node_sets, top_sets)
-    sk_req = _stack_request(stack_chains, num_chains)
-    _capi.r_eff_array(loo_r_eff, X_new.n)              # (checked before any sampling)
+    req = _fit_requests(y, num_chains, X_new, nsamp, x_transform, return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
+                        predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic, loo=loo, loo_r_eff=loo_r_eff,
+                        pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed, loo_predict=loo_predict,
+                        rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets,
+                        top_sets=top_sets, stack_chains=stack_chains)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -2069,8 +2034,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
         print("%d samples generated. Max PSRF XI: %.3f. Max PSRF Gamma: %.3f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()), file=sys.stderr)
     print("\nR = %s nu=%s nburn= %d nsamp = %d\n" % (R, nu, nburn, nsamp))
     print("%d samples generated. Max PSRF XI: %.4f. Max PSRF Gamma: %.4f" % (tot_generated, res.rhatxi.max(), res.rhatgamma.max()))
-    res = _finish(cs, res, return_state, summary_interval, ess_max_lag, pred, waic, loo, loo_r_eff, pool_chains, predict_observation,
-                  seed_eff if pred_seed is None else pred_seed, lp_req, rd_req, es_req, ns_req, sk_req)
+    res = _finish(cs, res, req, seed_eff)
     cs.close()
     return res
 
@@ -2110,12 +2074,9 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     pool_chains or the default return is unchanged.
     parameters.log keeps the reference's lines only."""
     xi_weights_code(xi_weights)
-    _pooled_request(pool_chains, predict_observation, predict_X)
-    _loo_predict_request(loo_predict, predict_interval, y)
-    _rank_diag_request(rank_diagnostics)
-    _edge_selection_request(edge_selection, hdi_prob, fdr)
-    _node_sets_request(node_sets, top_sets)
-    _stack_request(stack_chains, num_chains)
+    _fit_requests(y, num_chains, predict_X=predict_X, predict_interval=predict_interval, pool_chains=pool_chains,
+                  predict_observation=predict_observation, loo_predict=loo_predict, rank_diagnostics=rank_diagnostics,
+                  edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
         with open(filename, "w") as f:

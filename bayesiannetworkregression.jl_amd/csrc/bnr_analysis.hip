@@ -7,23 +7,37 @@
 
 #include <cmath>
 
-// a stream of a call's own (the calls on a caller's matrix), destroyed on every path
+// a stream of a call's own (the calls on a caller's matrix), destroyed on every path.  open: the device checked against the device count and made
+// current, then the stream on it
 namespace {
 struct stream_guard {
     hipStream_t s = nullptr;
     ~stream_guard() { if (s) (void)hipStreamDestroy(s); }
+    int open(int device)
+    {
+        int ndev = 0;
+        HIPCHK(hipGetDeviceCount(&ndev));
+        if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
+        HIPCHK(hipSetDevice(device));
+        HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        return BNR_OK;
+    }
 };
 }
-
-// The state and row window of the chains of an analysis call: none with a pending asynchronous run, the window inside every table
-static int window_check(bnr_chain *const *cs, int nc, int first_row, int nsamp)
+// Rows of a caller's matrix per block: about `budget` bytes of rows of `len` doubles, between 1 and m
+static int block_rows(size_t budget, long long len, int m)
 {
-    for (int i = 0; i < nc; ++i) if (cs[i]->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
-    for (int i = 0; i < nc; ++i)
-        if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > cs[i]->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
-    return BNR_OK;
+    return (int)std::min<size_t>((size_t)m, std::max<size_t>(1, budget / ((size_t)len * sizeof(double))));
 }
-// The chains of a pooled call (bnr_chains_*): one device, equal n, V, R, none listed twice, window_check, the pooled draw count within int32
+// Parameter columns per staging block: about 1 GiB of columns of S draws, or the chain's override (`set` > 0), between 1 and np
+static int block_cols(long long S, int set, int np)
+{
+    const long long blk = set > 0 ? set : (long long)(((size_t)1 << 30) / ((size_t)S * sizeof(double)));
+    return (int)std::min<long long>(std::max<long long>(blk, 1), np);
+}
+
+// The chains of an analysis call (the single-chain entry points pass theirs as a list of one): one device, equal n, V, R, none listed twice,
+// none with a pending asynchronous run, the row window inside every table, the pooled draw count within int32
 static int pooled_check(bnr_chain *const *cs, int nc, int first_row, int nsamp)
 {
     if (!cs) return fail(BNR_ERR_BAD_ARG, "NULL argument");
@@ -35,7 +49,9 @@ static int pooled_check(bnr_chain *const *cs, int nc, int first_row, int nsamp)
         if (cs[i]->device != cs[0]->device || a.n != b.n || a.V != b.V || a.R != b.R)
             return fail(BNR_ERR_BAD_ARG, "pooled chains must live on one device and have equal n, V, R");
     }
-    if (int rc = window_check(cs, nc, first_row, nsamp)) return rc;
+    for (int i = 0; i < nc; ++i) if (cs[i]->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");
+    for (int i = 0; i < nc; ++i)
+        if (first_row < 1 || nsamp < 1 || first_row + nsamp - 1 > cs[i]->d.tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
     if ((long long)nc * nsamp > 0x7FFFFFFFll) return fail(BNR_ERR_BAD_ARG, "more than 2^31 - 1 pooled draws");
     return BNR_OK;
 }
@@ -72,54 +88,55 @@ static void stage_cols(hipStream_t st, bnr_chain *const *cs, int nc, int first_r
 // first_row .. first_row+nsamp-1 of every chain listed (pooled: S = nc nsamp draws, draw c nsamp + s = chain c's s-th window row), and the mean
 // of every xi_v.  3q + V doubles cross PCIe instead of the gamma traces.  The q + V parameter columns are staged (k_fetch_cols, one launch per
 // chain into its nsamp rows of the S-row column) in blocks of columns that keep the staging buffer near 1 GiB ("summary_block_cols" overrides);
-// k_summary works on one column per workgroup, so the block size cannot change a result.
-static int summary_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
+// k_summary works on one column per workgroup, so the block size cannot change a result.  With wt (chain stacking, ABI 16: bnr_chains_wsummary)
+// the same staging blocks, k_wsummary under these chain weights instead of k_summary.
+static int summary_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi, const bnr_wsum_weights *wt,
                         double *mean_gamma, double *lower, double *upper, double *prob_xi)
 {
     bnr_chain *c = cs[0];
     const bnr_dev &d = c->d;
     const long long S = (long long)nc * nsamp;
     if (k_lo < 1 || k_lo > S || k_hi < 1 || k_hi > S)
-        return fail(BNR_ERR_BAD_ARG, nc == 1 ? "order statistics must be between 1 and nsamp" : "order statistics must be between 1 and nchains * nsamp");
+        return fail(BNR_ERR_BAD_ARG, nc == 1 && !wt ? "order statistics must be between 1 and nsamp" : "order statistics must be between 1 and nchains * nsamp");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->x.stream;
     int rc;
     if ((rc = pooled_quiesce(cs, nc))) return rc;
-    const int np = d.q + d.V;
-    const size_t budget = (size_t)1 << 30;
-    long long blk = c->summary_block_cols > 0 ? c->summary_block_cols : (long long)(budget / ((size_t)S * sizeof(double)));
-    blk = std::min<long long>(std::max<long long>(blk, 1), np);
+    const int np = d.q + d.V, blk = block_cols(S, c->summary_block_cols, np);
     dev_tmp tmp;
     double *buf = nullptr;
     result_slab out;                                    // the mean, the lower and the upper statistic of the np = q + V parameters, gamma first
     if ((rc = tmp.alloc(&buf, (size_t)blk * (size_t)S, st, false))) return rc;
     if ((rc = out.alloc(tmp, 3, (size_t)np, st))) return rc;
-    for (int p0 = 0; p0 < np; p0 += (int)blk) {
-        const int pc = std::min<int>((int)blk, np - p0);
+    for (int p0 = 0; p0 < np; p0 += blk) {
+        const int pc = std::min(blk, np - p0), gc = std::min(p0 + pc, d.q) - std::min(p0, d.q);
         stage_cols(st, cs, nc, first_row, nsamp, p0, pc, buf);
-        launch_summary(st, pc, buf, (int)S, std::min(p0 + pc, d.q) - std::min(p0, d.q), k_lo, k_hi, out.col(0) + p0, out.col(1) + p0, out.col(2) + p0);
+        if (wt) launch_wsummary(st, pc, buf, S, nsamp, nc, *wt, gc, k_lo, k_hi, out.col(0) + p0, out.col(1) + p0, out.col(2) + p0);
+        else launch_summary(st, pc, buf, (int)S, gc, k_lo, k_hi, out.col(0) + p0, out.col(1) + p0, out.col(2) + p0);
     }
     std::vector<double> host(3 * (size_t)np);           // (the callers' arrays hold q and V entries, not q + V)
-    if ((rc = out.fetch(st, "summary", "k_summary", {host.data(), host.data() + np, host.data() + 2 * (size_t)np}))) return rc;
+    if ((rc = out.fetch(st, wt ? "wsummary" : "summary", wt ? "k_wsummary" : "k_summary", {host.data(), host.data() + np, host.data() + 2 * (size_t)np})))
+        return rc;
     memcpy(mean_gamma, host.data(), sizeof(double) * d.q);
     memcpy(prob_xi, host.data() + d.q, sizeof(double) * d.V);
     memcpy(lower, host.data() + np, sizeof(double) * d.q);
     memcpy(upper, host.data() + 2 * (size_t)np, sizeof(double) * d.q);
     return BNR_OK;
 }
+// (here and below a single-chain entry point is its pooled twin on a list of one: of pooled_check's conditions only the pending run and the row
+// window can fail there, and the order-statistic message names nsamp)
 int bnr_chain_summary(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
                       double *mean_gamma, double *lower, double *upper, double *prob_xi)
 {
-    if (!c || !mean_gamma || !lower || !upper || !prob_xi) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
-    return summary_call(&c, 1, first_row, nsamp, k_lo, k_hi, mean_gamma, lower, upper, prob_xi);
+    if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    return bnr_chains_summary(&c, 1, first_row, nsamp, k_lo, k_hi, mean_gamma, lower, upper, prob_xi);
 }
 int bnr_chains_summary(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
                        double *mean_gamma, double *lower, double *upper, double *prob_xi)
 {
     if (!chains || !mean_gamma || !lower || !upper || !prob_xi) return fail(BNR_ERR_BAD_ARG, "NULL argument");
     if (int rc = pooled_check(chains, nchains, first_row, nsamp)) return rc;
-    return summary_call(chains, nchains, first_row, nsamp, k_lo, k_hi, mean_gamma, lower, upper, prob_xi);
+    return summary_call(chains, nchains, first_row, nsamp, k_lo, k_hi, nullptr, mean_gamma, lower, upper, prob_xi);
 }
 
 // the rank-normalised diagnostics (ABI 12): k_rank's two (key, index) buffers, one slice of ld entries per column
@@ -184,9 +201,7 @@ static int rank_diag_call(bnr_chain *const *cs, int nc, int32_t first_row, int32
     hipStream_t st = c->x.stream;
     int rc;
     if ((rc = pooled_quiesce(cs, nc))) return rc;
-    const size_t budget = (size_t)1 << 30;
-    long long blk = c->rank_block_cols > 0 ? c->rank_block_cols : (long long)(budget / ((size_t)S * sizeof(double)));
-    blk = std::min<long long>(std::max<long long>(blk, 1), np);
+    const int blk = block_cols(S, c->rank_block_cols, np);
     const int Lmax = (ess_bulk || want_et || want_mean) ? max_lag : 1;
     dev_tmp tmp;
     double *X = nullptr, *Z = nullptr, *A = nullptr, *B = nullptr, *med = nullptr, *statd = nullptr;
@@ -206,8 +221,8 @@ static int rank_diag_call(bnr_chain *const *cs, int nc, int32_t first_row, int32
     std::vector<double> o_rb(np, nanv), o_rt(np, nanv), o_eb(np, nanv), o_et(np, nanv), o_em(np, nanv), o_mc(np, nanv);
     std::vector<int> flags(2 * (size_t)blk);
     split_msg sz, s05, s95, sx, sf;
-    for (int p0 = 0; p0 < np; p0 += (int)blk) {
-        const int pc = std::min<int>((int)blk, np - p0);
+    for (int p0 = 0; p0 < np; p0 += blk) {
+        const int pc = std::min(blk, np - p0);
         stage_cols(st, cs, nc, first_row, nsamp, p0, pc, X);
         // one series: k_acov on the block's pc nc windows, its message fetched and laid out per chain; the ESS where lags were asked for
         auto series = [&](const double *data, int L, split_msg &m) -> int {
@@ -270,8 +285,7 @@ int bnr_chain_rank_diag(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t 
                         double *ess_tail, double *ess_mean, double *mcse_mean)
 {
     if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
-    return rank_diag_call(&c, 1, first_row, nsamp, max_lag, rhat_bulk, rhat_tail, ess_bulk, ess_tail, ess_mean, mcse_mean);
+    return bnr_chains_rank_diag(&c, 1, first_row, nsamp, max_lag, rhat_bulk, rhat_tail, ess_bulk, ess_tail, ess_mean, mcse_mean);
 }
 int bnr_chains_rank_diag(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t max_lag, double *rhat_bulk,
                          double *rhat_tail, double *ess_bulk, double *ess_tail, double *ess_mean, double *mcse_mean)
@@ -287,16 +301,12 @@ int bnr_rank_normalize(int32_t device, int32_t m, int32_t S, const double *x, do
 {
     if (!x || (!ranks && !z)) return fail(BNR_ERR_BAD_ARG, "NULL argument");
     if (m < 1 || S < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows and S >= 1 draws");
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
-    HIPCHK(hipSetDevice(device));
-    stream_guard guard;
-    HIPCHK(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
-    hipStream_t st = guard.s;
-    const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, ((size_t)1 << 28) / ((size_t)S * sizeof(double))));
-    const size_t cells = (size_t)blk * (size_t)S;
     int rc;
+    stream_guard guard;
+    if ((rc = guard.open(device))) return rc;
+    hipStream_t st = guard.s;
+    const int blk = block_rows((size_t)1 << 28, S, m);
+    const size_t cells = (size_t)blk * (size_t)S;
     dev_tmp tmp;                                        // (freed before the stream goes)
     double *Xd = nullptr, *Rd = nullptr, *Zd = nullptr;
     int *flagd = nullptr;
@@ -386,9 +396,7 @@ static int hdi_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsa
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->x.stream;
     if ((rc = pooled_quiesce(cs, nc))) return rc;
-    const size_t budget = (size_t)1 << 30;
-    long long blk = c->rank_block_cols > 0 ? c->rank_block_cols : (long long)(budget / ((size_t)S * sizeof(double)));
-    blk = std::min<long long>(std::max<long long>(blk, 1), np);
+    const int blk = block_cols(S, c->rank_block_cols, np);
     dev_tmp tmp;
     double *X = nullptr;
     rank_bufs rb;
@@ -396,8 +404,8 @@ static int hdi_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsa
     const size_t cells = (size_t)blk * (size_t)S;
     if ((rc = tmp.alloc(&X, cells, st, false)) || (rc = tmp.alloc(&rb.keyA, cells, st, false)) || (rc = tmp.alloc(&rb.keyB, cells, st, false))) return rc;
     if ((rc = out.alloc(tmp, levels, (size_t)np, st))) return rc;
-    for (int p0 = 0; p0 < np; p0 += (int)blk) {
-        const int pc = std::min<int>((int)blk, np - p0);
+    for (int p0 = 0; p0 < np; p0 += blk) {
+        const int pc = std::min(blk, np - p0);
         stage_cols(st, cs, nc, first_row, nsamp, p0, pc, X);
         launch_hdi(st, pc, X, S, (int)S, rb, levels, lv, levels ? out.lower() + p0 : nullptr, levels ? out.upper() + p0 : nullptr, np, out.med() + p0,
                    out.p_pos() + p0, out.p_neg() + p0);
@@ -408,8 +416,7 @@ int bnr_chain_hdi(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t nprob,
                   double *p_pos, double *p_neg)
 {
     if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
-    return hdi_call(&c, 1, first_row, nsamp, nprob, probs, lower, upper, median, p_pos, p_neg);
+    return bnr_chains_hdi(&c, 1, first_row, nsamp, nprob, probs, lower, upper, median, p_pos, p_neg);
 }
 int bnr_chains_hdi(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t nprob, const double *probs, double *lower,
                    double *upper, double *median, double *p_pos, double *p_neg)
@@ -428,14 +435,10 @@ int bnr_hdi(int32_t device, int32_t m, int32_t S, const double *x, int32_t nprob
     int rc;
     if ((rc = hdi_args(S, nprob, probs, lower, upper, median, p_pos, p_neg, lv))) return rc;
     const int levels = lower ? nprob : 0;
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
-    HIPCHK(hipSetDevice(device));
     stream_guard guard;
-    HIPCHK(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
+    if ((rc = guard.open(device))) return rc;
     hipStream_t st = guard.s;
-    const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, ((size_t)1 << 28) / ((size_t)S * sizeof(double))));
+    const int blk = block_rows((size_t)1 << 28, S, m);
     const size_t cells = (size_t)blk * (size_t)S;
     dev_tmp tmp;                                        // (freed before the stream goes)
     double *Xd = nullptr;
@@ -542,8 +545,7 @@ int bnr_chain_inclusion(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t 
                         int64_t *n_distinct, uint64_t *top_sets, int64_t *top_count)
 {
     if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
-    return incl_call(&c, 1, first_row, nsamp, which, ntop, incl_out{prob, joint, size_pmf, n_distinct, top_sets, top_count});
+    return bnr_chains_inclusion(&c, 1, first_row, nsamp, which, ntop, prob, joint, size_pmf, n_distinct, top_sets, top_count);
 }
 int bnr_chains_inclusion(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t which, int32_t ntop, double *prob,
                          double *joint, double *size_pmf, int64_t *n_distinct, uint64_t *top_sets, int64_t *top_count)
@@ -561,12 +563,8 @@ int bnr_inclusion(int32_t device, int32_t S, int32_t B, const uint8_t *z, int32_
     const incl_out o{prob, joint, size_pmf, n_distinct, top_sets, top_count};
     int rc;
     if ((rc = incl_args(B, ntop, o))) return rc;
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
-    HIPCHK(hipSetDevice(device));
     stream_guard guard;
-    HIPCHK(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
+    if ((rc = guard.open(device))) return rc;
     hipStream_t st = guard.s;
     dev_tmp tmp;                                        // (freed before the stream goes)
     unsigned char *zd = nullptr;
@@ -690,31 +688,24 @@ static int predict_rows(bnr_chain *const *cs, int nc, int first_row, int nsamp, 
     return check_launch("k_predict");
 }
 
-// Posterior of the mean response mu + x . gamma of m new rows over rows first_row .. first_row+nsamp-1 of the chains listed (an addition to the
-// reference): X_pred goes to the device in its own element type and is converted there (k_x_convert with m rows), then predict_rows.
-// pred_lower / pred_upper / pit (host, nullable): the extras of the pooled entry points.
-static int predict_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t m, const x_source &xs, const double *y, int32_t k_lo,
-                        int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic, uint64_t pred_seed, double *pred_lower,
-                        double *pred_upper, double *pit)
+// The m new rows of a prediction call onto the first chain's device and stream, behind the checks of m, the element type and the matrices and
+// behind the quiesce: X_pred goes to the device in its own element type and is converted there (k_x_convert with m rows; a float64 model matrix
+// is copied straight in) into Xd, m_pad = round_up(m, 32) rows by round_up(q, 16) columns, and y (nullable) into yd
+static int stage_new_rows(bnr_chain *const *cs, int nc, int m, const x_source &xs, const double *y, dev_tmp &tmp, double **Xd_out, double **yd_out)
 {
     bnr_chain *c = cs[0];
     const bnr_dev &d = c->d;
-    const long long S = (long long)nc * nsamp;
-    if (k_lo < 1 || k_lo > S || k_hi < 1 || k_hi > S)
-        return fail(BNR_ERR_BAD_ARG, nc == 1 ? "order statistics must be between 1 and nsamp" : "order statistics must be between 1 and nchains * nsamp");
     if (m < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows");
     if (xs.dtype < BNR_F64 || xs.dtype > BNR_F32) return fail(BNR_ERR_BAD_ARG, "unknown element type of X");
     if (xs.mats) for (int i = 0; i < m; ++i) if (!xs.mats[i]) return fail(BNR_ERR_BAD_ARG, "NULL adjacency matrix");
     HIPCHK(hipSetDevice(c->device));
     hipStream_t st = c->x.stream;
     const int m_pad = round_up(m, 32), q16 = round_up(d.q, 16);
-    dev_tmp tmp;
-    double *Xd = nullptr, *yd = nullptr;
-    result_slab out;
+    double *Xd = nullptr;
     int rc;
     if ((rc = pooled_quiesce(cs, nc))) return rc;
     if ((rc = tmp.alloc(&Xd, (size_t)m_pad * q16, st))) return rc;             // zero rows m .. m_pad - 1 and columns q .. q16 - 1 (k_predict)
-    if ((rc = out.alloc(tmp, pred_lower || pit ? 8 : 5, (size_t)m, st))) return rc;
+    *Xd_out = Xd;
     const size_t es = dtype_size(xs.dtype);
     if (!xs.mats && xs.dtype == BNR_F64) {
         HIPCHK(hipMemcpy2DAsync(Xd, (size_t)m_pad * sizeof(double), xs.X, (size_t)m * sizeof(double), (size_t)m * sizeof(double), d.q, hipMemcpyHostToDevice, st));
@@ -728,27 +719,37 @@ static int predict_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t
         launch_x_convert(xs.dtype, raw, xs.mats != nullptr, m, d, m_pad, Xd, nullptr, nullptr, st);
     }
     if (y) {
-        if ((rc = tmp.alloc(&yd, (size_t)m, st))) return rc;
-        HIPCHK(hipMemcpyAsync(yd, y, sizeof(double) * m, hipMemcpyHostToDevice, st));
+        if ((rc = tmp.alloc(yd_out, (size_t)m, st))) return rc;
+        HIPCHK(hipMemcpyAsync(*yd_out, y, sizeof(double) * m, hipMemcpyHostToDevice, st));
     }
+    return BNR_OK;
+}
+// Posterior of the mean response mu + x . gamma of m new rows over rows first_row .. first_row+nsamp-1 of the chains listed (an addition to the
+// reference): stage_new_rows, then predict_rows.  pred_lower / pred_upper / pit (host, nullable): the extras of the pooled entry points.
+static int predict_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsamp, int32_t m, const x_source &xs, const double *y, int32_t k_lo,
+                        int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic, uint64_t pred_seed, double *pred_lower,
+                        double *pred_upper, double *pit)
+{
+    const long long S = (long long)nc * nsamp;
+    if (k_lo < 1 || k_lo > S || k_hi < 1 || k_hi > S)
+        return fail(BNR_ERR_BAD_ARG, nc == 1 ? "order statistics must be between 1 and nsamp" : "order statistics must be between 1 and nchains * nsamp");
+    dev_tmp tmp;
+    double *Xd = nullptr, *yd = nullptr;
+    result_slab out;
+    int rc;
+    if ((rc = stage_new_rows(cs, nc, m, xs, y, tmp, &Xd, &yd))) return rc;
+    hipStream_t st = cs[0]->x.stream;
+    if ((rc = out.alloc(tmp, pred_lower || pit ? 8 : 5, (size_t)m, st))) return rc;
     pred_stages sg;
     sg.k_lo = k_lo; sg.k_hi = k_hi;
     sg.mean = out.col(0); sg.lower = out.col(1); sg.upper = out.col(2);
     if (y) { sg.lpd = out.col(3); sg.pwaic = out.col(4); }
     if (pred_lower) { sg.seed = pred_seed; sg.pred_lower = out.col(5); sg.pred_upper = out.col(6); }
     if (pit) sg.pit = out.col(7);
-    if ((rc = predict_rows(cs, nc, first_row, nsamp, m, Xd, m_pad, yd, sg, tmp))) return rc;
+    if ((rc = predict_rows(cs, nc, first_row, nsamp, m, Xd, round_up(m, 32), yd, sg, tmp))) return rc;
     return out.fetch(st, "predict", "k_predict", {mean, lower, upper, y ? lpd : nullptr, y ? pwaic : nullptr, pred_lower, pred_lower ? pred_upper : nullptr, pit});
 }
-// the checks of the single-chain entry points, in their order
-static int predict_one(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const x_source &xs, const double *y, int32_t k_lo, int32_t k_hi,
-                       double *mean, double *lower, double *upper, double *lpd, double *pwaic)
-{
-    if (!c || !mean || !lower || !upper || (!xs.X && !xs.mats) || (y && (!lpd || !pwaic))) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
-    return predict_call(&c, 1, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic, 0, nullptr, nullptr, nullptr);
-}
-// ... and of the pooled ones: pred_lower and pred_upper come together; lpd / pwaic and pit need y
+// the checks of the entry points, in their order: pred_lower and pred_upper come together; lpd / pwaic and pit need y
 static int predict_pooled(bnr_chain *const *cs, int32_t nc, int32_t first_row, int32_t nsamp, int32_t m, const x_source &xs, const double *y, int32_t k_lo,
                           int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic, uint64_t pred_seed, double *pred_lower,
                           double *pred_upper, double *pit)
@@ -762,16 +763,15 @@ static int predict_pooled(bnr_chain *const *cs, int32_t nc, int32_t first_row, i
 int bnr_chain_predict(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const void *X, int32_t x_dtype, const double *y,
                       int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic)
 {
-    x_source xs;
-    xs.X = X; xs.dtype = x_dtype;
-    return predict_one(c, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic);
+    if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    return bnr_chains_predict(&c, 1, first_row, nsamp, m, X, x_dtype, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic, 0, nullptr, nullptr, nullptr);
 }
 int bnr_chain_predict_from_matrices(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t m, const void *const *A, int32_t x_dtype,
                                     const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic)
 {
-    x_source xs;
-    xs.mats = A; xs.dtype = x_dtype;
-    return predict_one(c, first_row, nsamp, m, xs, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic);
+    if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    return bnr_chains_predict_from_matrices(&c, 1, first_row, nsamp, m, A, x_dtype, y, k_lo, k_hi, mean, lower, upper, lpd, pwaic, 0, nullptr, nullptr,
+                                            nullptr);
 }
 int bnr_chains_predict(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, int32_t m, const void *X, int32_t x_dtype,
                        const double *y, int32_t k_lo, int32_t k_hi, double *mean, double *lower, double *upper, double *lpd, double *pwaic,
@@ -839,9 +839,8 @@ static int loglik_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t 
 }
 int bnr_chain_loglik_stats(bnr_chain *c, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic)
 {
-    if (!c || !lpd || !pwaic) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
-    return loglik_call(&c, 1, first_row, nsamp, lpd, pwaic, nullptr);
+    if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    return bnr_chains_loglik_stats(&c, 1, first_row, nsamp, lpd, pwaic, nullptr);
 }
 int bnr_chains_loglik_stats(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, double *lpd, double *pwaic, double *pit)
 {
@@ -890,9 +889,8 @@ static int loo_call(bnr_chain *const *cs, int nc, int32_t first_row, int32_t nsa
 }
 int bnr_chain_loo(bnr_chain *c, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo, double *pareto_k)
 {
-    if (!c || !elpd_loo || !pareto_k) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
-    return loo_call(&c, 1, first_row, nsamp, r_eff, lpd, elpd_loo, pareto_k);
+    if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    return bnr_chains_loo(&c, 1, first_row, nsamp, r_eff, lpd, elpd_loo, pareto_k);
 }
 int bnr_chains_loo(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, const double *r_eff, double *lpd, double *elpd_loo,
                    double *pareto_k)
@@ -934,8 +932,7 @@ int bnr_chain_loo_predict(bnr_chain *c, int32_t first_row, int32_t nsamp, const 
                           double *pareto_k, double *loo_mean, double *loo_sd, double *loo_pit, double *loo_lower, double *loo_upper)
 {
     if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (int rc = window_check(&c, 1, first_row, nsamp)) return rc;
-    return loo_predict_call(&c, 1, first_row, nsamp, r_eff, p_lo, p_hi, lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper);
+    return bnr_chains_loo_predict(&c, 1, first_row, nsamp, r_eff, p_lo, p_hi, lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper);
 }
 int bnr_chains_loo_predict(bnr_chain *const *chains, int32_t nchains, int32_t first_row, int32_t nsamp, const double *r_eff, double p_lo, double p_hi,
                            double *lpd, double *elpd_loo, double *pareto_k, double *loo_mean, double *loo_sd, double *loo_pit, double *loo_lower,
@@ -945,17 +942,13 @@ int bnr_chains_loo_predict(bnr_chain *const *chains, int32_t nchains, int32_t fi
     return loo_predict_call(chains, nchains, first_row, nsamp, r_eff, p_lo, p_hi, lpd, elpd_loo, pareto_k, loo_mean, loo_sd, loo_pit, loo_lower, loo_upper);
 }
 
-// The device work of bnr_psis_loo and bnr_psis_weights on a stream of its own: the rows of the caller's matrix in blocks, k_psis<0> on every block
+// The device work of bnr_psis_loo and bnr_psis_weights on the call's stream st: the rows of the caller's matrix in blocks, k_psis<0> on every block
 // of about 1 GiB; with log_weights k_psis_w<0> on every block of about 512 MiB (l and the weights side by side), the block's weights copied back
 // behind it (and no lpd)
-static int psis_matrix(int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *log_weights, double *lpd, double *elpd,
-                       double *khat)
+static int psis_matrix(hipStream_t st, int m, int nsamp, const double *loglik, const std::vector<int> &tail_len, int lds, double *log_weights, double *lpd,
+                       double *elpd, double *khat)
 {
-    stream_guard guard;
-    HIPCHK(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
-    hipStream_t st = guard.s;
-    const size_t budget = log_weights ? (size_t)1 << 29 : (size_t)1 << 30;
-    const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, budget / ((size_t)nsamp * sizeof(double))));
+    const int blk = block_rows(log_weights ? (size_t)1 << 29 : (size_t)1 << 30, nsamp, m);
     int rc;
     dev_tmp tmp;                                        // (freed before the stream goes)
     double *Ld = nullptr, *Wd = nullptr;
@@ -986,13 +979,12 @@ static int psis_call(int32_t device, int32_t m, int32_t nsamp, const double *log
 {
     if (m < 1 || nsamp < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows and nsamp >= 1 draws");
     std::vector<int> M;
-    int lds = 0, rc, ndev = 0;
+    int lds = 0, rc;
     if ((rc = psis_tail_lengths(m, nsamp, r_eff, M, lds, log_weights ? BNR_PSISW_ENTRY_BYTES : 16))) return rc;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
-    HIPCHK(hipSetDevice(device));
+    stream_guard guard;
+    if ((rc = guard.open(device))) return rc;
     if ((rc = psis_lds_attributes())) return rc;
-    return psis_matrix(m, nsamp, loglik, M, lds, log_weights, lpd, elpd_loo, pareto_k);
+    return psis_matrix(guard.s, m, nsamp, loglik, M, lds, log_weights, lpd, elpd_loo, pareto_k);
 }
 int bnr_psis_loo(int32_t device, int32_t m, int32_t nsamp, const double *loglik, const double *r_eff, double *elpd_loo, double *pareto_k, double *lpd)
 {
@@ -1087,7 +1079,7 @@ static double wlse(const double *v, size_t ldv, const double *w, int K)
     return M + log(s);
 }
 
-// bnr_chains_summary under chain weights: the same staging blocks ("summary_block_cols"), k_wsummary instead of k_summary
+// bnr_chains_summary under chain weights: summary_call with the packed weights
 int bnr_chains_wsummary(bnr_chain *const *chains, int32_t nchains, const double *weights, int32_t first_row, int32_t nsamp, int32_t k_lo, int32_t k_hi,
                         double *mean_gamma, double *lower, double *upper, double *prob_xi)
 {
@@ -1096,35 +1088,7 @@ int bnr_chains_wsummary(bnr_chain *const *chains, int32_t nchains, const double 
     bnr_wsum_weights wt;
     if ((rc = wsum_pack(weights, nchains, wt))) return rc;
     if ((rc = pooled_check(chains, nchains, first_row, nsamp))) return rc;
-    bnr_chain *c = chains[0];
-    const bnr_dev &d = c->d;
-    const long long S = (long long)nchains * nsamp;
-    if (k_lo < 1 || k_lo > S || k_hi < 1 || k_hi > S) return fail(BNR_ERR_BAD_ARG, "order statistics must be between 1 and nchains * nsamp");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->x.stream;
-    if ((rc = pooled_quiesce(chains, nchains))) return rc;
-    const int np = d.q + d.V;
-    const size_t budget = (size_t)1 << 30;
-    long long blk = c->summary_block_cols > 0 ? c->summary_block_cols : (long long)(budget / ((size_t)S * sizeof(double)));
-    blk = std::min<long long>(std::max<long long>(blk, 1), np);
-    dev_tmp tmp;
-    double *buf = nullptr;
-    result_slab out;
-    if ((rc = tmp.alloc(&buf, (size_t)blk * (size_t)S, st, false))) return rc;
-    if ((rc = out.alloc(tmp, 3, (size_t)np, st))) return rc;
-    for (int p0 = 0; p0 < np; p0 += (int)blk) {
-        const int pc = std::min<int>((int)blk, np - p0);
-        stage_cols(st, chains, nchains, first_row, nsamp, p0, pc, buf);
-        launch_wsummary(st, pc, buf, S, nsamp, nchains, wt, std::min(p0 + pc, d.q) - std::min(p0, d.q), k_lo, k_hi, out.col(0) + p0, out.col(1) + p0,
-                        out.col(2) + p0);
-    }
-    std::vector<double> host(3 * (size_t)np);
-    if ((rc = out.fetch(st, "wsummary", "k_wsummary", {host.data(), host.data() + np, host.data() + 2 * (size_t)np}))) return rc;
-    memcpy(mean_gamma, host.data(), sizeof(double) * d.q);
-    memcpy(prob_xi, host.data() + d.q, sizeof(double) * d.V);
-    memcpy(lower, host.data() + np, sizeof(double) * d.q);
-    memcpy(upper, host.data() + 2 * (size_t)np, sizeof(double) * d.q);
-    return BNR_OK;
+    return summary_call(chains, nchains, first_row, nsamp, k_lo, k_hi, &wt, mean_gamma, lower, upper, prob_xi);
 }
 
 // k_wsummary on every row of a caller's m x (K nsamp) matrix (host, row-major), each row on its own: the kernel's direct test, as bnr_hdi is
@@ -1142,14 +1106,10 @@ int bnr_wquantile(int32_t device, int32_t m, int32_t K, int32_t nsamp, const dou
     const long long S = (long long)K * nsamp;
     if (S > 0x7FFFFFFFll) return fail(BNR_ERR_BAD_ARG, "more than 2^31 - 1 pooled draws");
     if (lower && (k_lo < 1 || k_lo > S || k_hi < 1 || k_hi > S)) return fail(BNR_ERR_BAD_ARG, "order statistics must be between 1 and K * nsamp");
-    int ndev = 0;
-    HIPCHK(hipGetDeviceCount(&ndev));
-    if (device < 0 || device >= ndev) return fail(BNR_ERR_BAD_ARG, "no such device");
-    HIPCHK(hipSetDevice(device));
     stream_guard guard;
-    HIPCHK(hipStreamCreateWithFlags(&guard.s, hipStreamNonBlocking));
+    if ((rc = guard.open(device))) return rc;
     hipStream_t st = guard.s;
-    const int blk = (int)std::min<size_t>((size_t)m, std::max<size_t>(1, ((size_t)1 << 28) / ((size_t)S * sizeof(double))));
+    const int blk = block_rows((size_t)1 << 28, S, m);
     dev_tmp tmp;                                        // (freed before the stream goes)
     double *Xd = nullptr;
     result_slab out;
@@ -1213,37 +1173,22 @@ int bnr_chains_wpredict(bnr_chain *const *chains, int32_t nchains, const double 
     bnr_wsum_weights wt;
     if ((rc = wsum_pack(weights, nchains, wt))) return rc;
     if ((rc = pooled_check(chains, nchains, first_row, nsamp))) return rc;
-    bnr_chain *c = chains[0];
-    const bnr_dev &d = c->d;
     const long long S = (long long)nchains * nsamp;
     if (k_lo < 1 || k_lo > S || k_hi < 1 || k_hi > S) return fail(BNR_ERR_BAD_ARG, "order statistics must be between 1 and nchains * nsamp");
-    if (m < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 rows");
-    if (x_dtype < BNR_F64 || x_dtype > BNR_F32) return fail(BNR_ERR_BAD_ARG, "unknown element type of X");
-    HIPCHK(hipSetDevice(c->device));
-    hipStream_t st = c->x.stream;
-    const int m_pad = round_up(m, 32), q16 = round_up(d.q, 16);
+    x_source xs;
+    xs.X = X; xs.dtype = x_dtype;
     dev_tmp tmp;
     double *Xd = nullptr, *yd = nullptr;
     result_slab out, lc;
-    if ((rc = pooled_quiesce(chains, nchains))) return rc;
-    if ((rc = tmp.alloc(&Xd, (size_t)m_pad * q16, st))) return rc;             // zero rows m .. m_pad - 1 and columns q .. q16 - 1 (k_predict)
+    if ((rc = stage_new_rows(chains, nchains, m, xs, y, tmp, &Xd, &yd))) return rc;
+    hipStream_t st = chains[0]->x.stream;
+    const int m_pad = round_up(m, 32);
     if ((rc = out.alloc(tmp, 5, (size_t)m, st))) return rc;
-    if (x_dtype == BNR_F64) {
-        HIPCHK(hipMemcpy2DAsync(Xd, (size_t)m_pad * sizeof(double), X, (size_t)m * sizeof(double), (size_t)m * sizeof(double), d.q, hipMemcpyHostToDevice, st));
-    } else {
-        char *raw = nullptr;
-        const size_t bytes = (size_t)m * d.q * dtype_size(x_dtype);
-        if ((rc = tmp.alloc(&raw, bytes, st))) return rc;
-        HIPCHK(hipMemcpyAsync(raw, X, bytes, hipMemcpyHostToDevice, st));
-        launch_x_convert(x_dtype, raw, false, m, d, m_pad, Xd, nullptr, nullptr, st);
-    }
     pred_stages sg;
     sg.k_lo = k_lo; sg.k_hi = k_hi;
     sg.wt = &wt;
     sg.mean = out.col(0); sg.lower = out.col(1); sg.upper = out.col(2);
     if (y) {
-        if ((rc = tmp.alloc(&yd, (size_t)m, st))) return rc;
-        HIPCHK(hipMemcpyAsync(yd, y, sizeof(double) * m, hipMemcpyHostToDevice, st));
         if ((rc = lc.alloc(tmp, nchains + 1, (size_t)m, st))) return rc;        // every chain's lpd; the last column takes the pwaic nobody reads
         // every chain's own lpd: bnr_chain_predict's launches over that chain alone, on its stream (the inputs are complete first), so column k
         // is its lpd bit for bit; the work buffers of a chain go before the next one's come

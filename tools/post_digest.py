@@ -1,5 +1,7 @@
-"""SHA-256 of what the posterior-analysis entry points return on a few fixed inputs (the PSIS matrix calls on crafted rows; summary, predict in every
-input format, loglik_stats, loo, loo_predict and ess_stats on a 3-chain group and on a lone chain, with the default block sizes and with small ones):
+"""SHA-256 of what the posterior-analysis entry points return on a few fixed inputs (the PSIS, rank, HDI, inclusion and weighted-quantile matrix
+calls on crafted and seeded rows; summary, predict in every input format, loglik_stats, loo, loo_predict, rank_diag, hdi, inclusion and ess_stats
+on a 3-chain group and on a lone chain, the chain stacking and the summaries under its weights on the group, with the default block sizes and
+with small ones):
 run it with two builds of the library (BNR_HIP_LIB) and diff the output to see whether a change to that layer is bitwise neutral.  The companion of
 table_digest.py, which does the same for the sampled tables."""
 import sys, os, hashlib
@@ -15,7 +17,7 @@ NB, NS = 100, 300
 def digest(arrays):
     h = hashlib.sha256()
     for a in arrays:
-        h.update(b"-" if a is None else np.ascontiguousarray(a, dtype=np.float64).tobytes())
+        h.update(b"-" if a is None else np.ascontiguousarray(a).tobytes())          # (float64 throughout, but for the counts and sets of inclusion)
     return h.hexdigest()[:16]
 
 
@@ -56,6 +58,28 @@ def matrix_cases():
     psis_case("S=50000 M=8192", ll, S * 9.0 / 8192.0 ** 2 * 1.0001)
 
 
+def seeded_matrix_cases():
+    """the rank, HDI, inclusion and weighted-quantile calls on a caller's matrix: a few seeded rows each, ties and a NaN row among them"""
+    rng = np.random.default_rng(SEED + 5)
+    for S in (2, 7, 256, 1000):
+        x = np.array([rng.standard_normal(S), np.round(rng.standard_normal(S), 1), np.full(S, 1.5), np.abs(rng.standard_normal(S)) - 0.2,
+                      np.where(np.arange(S) == S // 2, np.nan, rng.standard_normal(S))])
+        show("rank_normalize S=%d" % S, _capi.rank_normalize_raw(x, DEV))
+        show("hdi S=%d" % S, _capi.hdi_raw(x, (0.5, 0.95), DEV))
+        show("hdi S=%d, no level" % S, _capi.hdi_raw(x, (), DEV, fields=("median", "p_pos", "p_neg")))
+    for S, B in ((3, 2), (77, 5), (1000, 70)):
+        z = rng.random((S, B)) < np.linspace(0.1, 0.9, B)[None, :]
+        show("inclusion S=%d B=%d" % (S, B), _capi.inclusion_raw(z, 4, DEV))
+        show("inclusion S=%d B=%d, marginals" % (S, B), _capi.inclusion_raw(z, 0, DEV, fields=("prob", "size_pmf")))
+    for K, ns in ((1, 9), (3, 50), (4, 333)):
+        x = np.array([rng.standard_normal(K * ns), np.round(rng.standard_normal(K * ns), 1), np.full(K * ns, -2.0)])
+        w = rng.random(K)
+        w[K // 2] = 0.0 if K > 1 else 1.0
+        w /= w.sum()
+        show("wquantile K=%d nsamp=%d" % (K, ns), _capi.wquantile_raw(x, w, K, 3, K * ns - 2, DEV))
+        show("wquantile K=%d nsamp=%d, mean" % (K, ns), _capi.wquantile_raw(x, w, K, 1, 1, DEV, fields=("mean",)))
+
+
 def chain_cases(label, chains, Xn, yn):
     """every analysis call on `chains`: the pooled entry points for a list of chains, the single-chain ones for a lone chain"""
     lone = chains[0] if len(chains) == 1 else None
@@ -72,6 +96,10 @@ def chain_cases(label, chains, Xn, yn):
         show("%s loglik_stats" % label, lone.loglik_stats(NB + 1, NS))
         show("%s loo" % label, lone.loo(NB + 1, NS, 0.7))
         show("%s loo_predict" % label, lone.loo_predict(NB + 1, NS, 0.7))
+        show("%s rank_diag" % label, lone.rank_diag(NB + 1, NS, 40))
+        show("%s hdi" % label, lone.hdi(NB + 1, NS, (0.5, 0.95)))
+        for which in (0, 1):
+            show("%s inclusion %d" % (label, which), lone.inclusion(NB + 1, NS, which, 5))
     else:
         show("%s summary" % label, _capi.pooled_summary(chains, NB + 1, NS, k_lo, k_hi))
     # (the pooled entry points also for the lone chain: its predictive bounds and PITs)
@@ -80,12 +108,25 @@ def chain_cases(label, chains, Xn, yn):
     show("%s pooled loglik_stats" % label, _capi.pooled_loglik_stats(chains, NB + 1, NS, pit=True))
     show("%s pooled loo" % label, _capi.pooled_loo(chains, NB + 1, NS, 0.7))
     show("%s pooled loo_predict" % label, _capi.pooled_loo_predict(chains, NB + 1, NS, 0.7))
+    show("%s pooled rank_diag" % label, _capi.pooled_rank_diag(chains, NB + 1, NS, 40))
+    show("%s pooled rank_diag, two fields" % label, _capi.pooled_rank_diag(chains, NB + 1, NS, 40, ("rhat_tail", "mcse_mean")))
+    show("%s pooled hdi" % label, _capi.pooled_hdi(chains, NB + 1, NS, (0.5, 0.95)))
+    for which in (0, 1):
+        show("%s pooled inclusion %d" % (label, which), _capi.pooled_inclusion(chains, NB + 1, NS, which, 5))
+    if not lone:                                                # the chain stacking, and the summaries under its weights and under given ones
+        st = _capi.chains_stack(chains, NB + 1, NS, 0.7)
+        show("%s chains_stack" % label, st)
+        for wl, w in (("stack", st[0]), ("given", np.array([0.5, 0.0, 0.5]))):
+            show("%s stacked_summary %s" % (label, wl), _capi.stacked_summary(chains, w, NB + 1, NS, k_lo, k_hi))
+            for name, X, xt in formats[:4]:
+                show("%s stacked_predict %s %s" % (label, wl, name), _capi.stacked_predict(chains, w, X, NB + 1, NS, k_lo, k_hi, y=yn, pred_seed=PS))
     for k, ch in enumerate(chains):
         show("%s ess_stats chain %d" % (label, k + 1), [ch.ess_stats(NB + 1, NS, 20)])
 
 
 def main():
     matrix_cases()
+    seeded_matrix_cases()
     X, y, _ = bnr_amd.make_synthetic(60, 12, 3, seed=SEED)                         # the trio of the pooled tests and a lone chain
     trio = [bnr_amd.Chain(X, y, 3, 400, SEED, 1, device=DEV)]
     trio += [bnr_amd.Chain.like(trio[0], SEED, c) for c in (2, 3)]
@@ -96,11 +137,12 @@ def main():
     grp.run(2, 400, 400)
     lone.run(2, 400, 400)
     Xn, yn, _ = bnr_amd.make_synthetic(37, 12, 3, seed=SEED + 1)
-    for rows, cols in ((0, 0), (32, 7)):
+    for rows, cols, rcols in ((0, 0, 0), (32, 7, 5)):
         for ch in (trio[0], lone):
             ch.set_option("predict_block_rows", rows)
             ch.set_option("summary_block_cols", cols)
-        tag = "blocks %d/%d" % (rows, cols)
+            ch.set_option("rank_block_cols", rcols)
+        tag = "blocks %d/%d/%d" % (rows, cols, rcols)
         chain_cases("trio %s" % tag, trio, Xn, yn)
         chain_cases("lone %s" % tag, [lone], Xn, yn)
     grp.close()
