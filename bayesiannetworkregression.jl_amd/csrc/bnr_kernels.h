@@ -12,7 +12,7 @@
 //   k_node      update_tau2! (scalar draw from carried sums) + update_u_xi! (one wave per node, log-space weights)
 //   k_xpass     W = lowtri(u' L u), sz = sqrt(S) z1, partial GEMVs X W and X sz          (reads X once)
 //   k_gram / k_gram8   X diag(S) X' by v_mfma_f64_16x16x4_f64, split-K partial tiles; lower triangle only, and of a diagonal tile only
-//               what lies on or below the diagonal at block / MFMA-tile granularity (BNR_GRAM_SKIP_DEAD)    (reads X once)
+//               what lies on or below the diagonal at block / MFMA-tile granularity    (reads X once)
 //   k_chol_step x n_pad/32   E = [G + I ; I] -> [L ; L^-T]  (right-looking blocked Cholesky, one launch per panel; launch 0 also sums the
 //               split-K partials; k_gram_reduce / k_chol_step2 for the two-panel variant of large n)
 //   k_rhs, k_solve_w, k_solve_a4   a4 = (G+I)^-1 (a1 - a3) = Y (Y' b); X gamma_new from n-vectors (no third pass over X)
@@ -732,12 +732,6 @@ __host__ __device__ inline long long bnr_gram_span_bytes(int n_pad, int kchunk, 
 {
     return ((long long)(kchunk / kg) + BNR_GRAM_PREFETCH_COLS + 16) * (long long)n_pad * 8;
 }
-#ifndef BNR_GRAM_SKIP_DEAD
-#define BNR_GRAM_SKIP_DEAD 1          // 1: what lies above the diagonal is not computed where whole waves or whole MFMAs can be left out: the upper 32 x 32
-                                      // block of a diagonal tile (its two waves only stage: 5.6 % of the launch's MFMAs at ntile = 8; 8 chains 216.5 ->
-                                      // 212.6 us per launch, 401.7 -> 396.6 us per sweep) and the upper 16 x 16 tile of a diagonal block (3 MFMAs per
-                                      // k-step instead of 4 in the diagonal waves); zeros are written there, nobody reads them
-#endif
 
 // LDS-staged K loop.  Per K-group (4 waves = 256 threads) and batch of 16 columns: the j-side panel X[j-rows, 16 cols] and
 // the S-scaled i-side panel travel global -> registers (16-byte loads, issued one whole batch ahead) -> LDS image
@@ -752,30 +746,15 @@ __host__ __device__ inline long long bnr_gram_span_bytes(int n_pad, int kchunk, 
 // Grid (1-D) = round_up(tasks, 8) x chains.  Workgroup id -> XCD label id % 8 (round-robin dispatch), and within one
 // XCD's sequence the chains of a lockstep group are innermost: the 8 (or C) workgroups that need the same panels of X
 // (same tile, same K slice, different S) run next to each other on the same XCD and share them through its L2.
-// a partial-tile element goes to memory either as a plain store (consumed after the kernel boundary) or written through to the
-// agent's coherence point (sc1), for a consumer that runs beside this kernel on another XCD
-template <bool WT>
-__device__ __forceinline__ void bnr_gstore(double *p, double v)
-{
-    if (WT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    else *p = v;
-}
-#define BNR_G8P_WPC 2          // persistent Gram workgroups per CU: two (4 waves per SIMD, up to 128 VGPRs).  Three would need the task loop in 80
-                              // VGPRs: the body alone takes 74, the loop's live state spills, and the spill code moved 63 KB of scratch per
-                              // task = 128 MB per 8-chain launch, twice the partial tiles (3.5 x the L2 misses, +40 % on the launch)
+// a partial-tile element goes to memory as a plain store (consumed after the kernel boundary).  The stores stay behind this helper: with
+// "out[idx] = ..." written out in the task bodies the compiler schedules all six Gram kernels differently (profiles/kernel_variants_cleanup.txt)
+__device__ __forceinline__ void bnr_gstore(double *p, double v) { *p = v; }
 // what a Gram task needs besides the chain's S row and its partial-tile buffer: equal for all members of a lockstep group
 struct bnr_gram_geom { const double *X; int n_pad, q_pad, ksplit, q, ntile; };
 __device__ __forceinline__ bnr_gram_geom bnr_geom_of(const bnr_dev &cd) { return bnr_gram_geom{cd.X, cd.n_pad, cd.q_pad, cd.ksplit, cd.q, cd.ntile}; }
-// s_setprio takes an immediate: a wave-uniform level 0..2
-__device__ __forceinline__ void bnr_setprio3(int level)
-{
-    if (level == 0) __builtin_amdgcn_s_setprio(0);
-    else if (level == 1) __builtin_amdgcn_s_setprio(1);
-    else __builtin_amdgcn_s_setprio(2);
-}
 // one (tile t = (ti, tj), K slice ks) task of the Gram with 16-column batches: KG x 256 threads, sred = KG x 32 KiB of LDS
-template <int KG, bool WT>
-__device__ __forceinline__ void bnr_gram16_task(const bnr_gram_geom &cd, const double *Sp, double *Gpart, int t, int ti, int tj, int ks, double *sred, int rot = -1)
+template <int KG>
+__device__ __forceinline__ void bnr_gram16_task(const bnr_gram_geom &cd, const double *Sp, double *Gpart, int t, int ti, int tj, int ks, double *sred)
 {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int kg = wave >> 2, wi = (wave >> 1) & 1, wj = wave & 1;
@@ -784,7 +763,6 @@ __device__ __forceinline__ void bnr_gram16_task(const bnr_gram_geom &cd, const d
     const int eb = ks * kchunk + kg * ksub;
     const int nfull = ksub / BNR_GRAM_KB;             // whole batches; ksub % 16 == 8 leaves one half batch
     const bool half = (ksub % BNR_GRAM_KB) != 0;
-    const int nbatch = nfull + (half ? 1 : 0);
     const size_t ld = cd.n_pad;
     const int li = lane & 15, lk = lane >> 4;
     // staging: this thread moves rows (2 rp, 2 rp + 1) of columns c and c + 8 of both panels.  Addresses = wave-uniform base
@@ -841,9 +819,11 @@ __device__ __forceinline__ void bnr_gram16_task(const bnr_gram_geom &cd, const d
     BNR_GRAM_STORE(0);
     BNR_GRAM_LOAD(1);
     __syncthreads();
-    if (BNR_GRAM_SKIP_DEAD && ti == tj && wi == 0 && wj == 1) {
+    if (ti == tj && wi == 0 && wj == 1) {
         // the 32 x 32 block above the diagonal of a diagonal tile is read by nobody (k_gram_reduce copies it into the strictly upper
         // part of E, which the factorization never touches): its two waves only take part in the staging and leave zeros
+        // (measured against computing it: 5.6 % of the launch's MFMAs at ntile = 8; 8 chains 216.5 -> 212.6 us per launch, 401.7 -> 396.6 us
+        // per sweep, together with the 3 instead of 4 MFMAs per k-step of the diagonal waves below)
         int b = 0;
         for (; b + 1 < nfull; b += 2) {
             BNR_GRAM_STORE(1); BNR_GRAM_LOAD(b + 2); __syncthreads();
@@ -851,7 +831,7 @@ __device__ __forceinline__ void bnr_gram16_task(const bnr_gram_geom &cd, const d
         }
         if (b < nfull) { BNR_GRAM_STORE(1); BNR_GRAM_LOAD(b + 2); __syncthreads(); }
         if (half) __syncthreads();
-    } else if (BNR_GRAM_SKIP_DEAD && ti == tj && wi == wj) {
+    } else if (ti == tj && wi == wj) {
         // a diagonal 32 x 32 block: its upper 16 x 16 tile (c10: columns 16.., rows ..15) is read by nobody either -- three MFMAs per k-step
         // (two batches per trip, the buffer parity a literal: LDS addresses are "lane base + immediate", no address VALU in the loop)
 #define BNR_GRAM_BATCH_L(B, PAR, DIAG)                                                                    \
@@ -875,8 +855,6 @@ __device__ __forceinline__ void bnr_gram16_task(const bnr_gram_geom &cd, const d
     if (b < nfull) BNR_GRAM_BATCH_L(b, 0, false);
     if (half) { if (nfull & 1) BNR_GRAM_COMPUTE(1, 0, 2, false); else BNR_GRAM_COMPUTE(0, 0, 2, false); __syncthreads(); }
     }
-    (void)rot;
-    (void)nbatch;
     // tile element (i,j) lives at [j*64 + i]; this lane: j = wj*32 + jt*16 + (lane>>4) + 4 r, i = wi*32 + it*16 + (lane&15)
     double *mine = sred + (size_t)kg * (BNR_GT * BNR_GT);
     const int jb = wj * 32 + (lane >> 4), ib = wi * 32 + (lane & 15);
@@ -891,8 +869,8 @@ __device__ __forceinline__ void bnr_gram16_task(const bnr_gram_geom &cd, const d
     double *out = Gpart + ((size_t)ks * (cd.ntile * (cd.ntile + 1) / 2) + t) * (BNR_GT * BNR_GT);
 #pragma unroll
     for (int idx = threadIdx.x; idx < BNR_GT * BNR_GT; idx += KG * 256) {
-        if (KG == 4) bnr_gstore<WT>(out + idx, (sred[idx] + sred[BNR_GT * BNR_GT + idx]) + (sred[2 * BNR_GT * BNR_GT + idx] + sred[3 * BNR_GT * BNR_GT + idx]));
-        else bnr_gstore<WT>(out + idx, sred[idx] + sred[BNR_GT * BNR_GT + idx]);
+        if (KG == 4) bnr_gstore(out + idx, (sred[idx] + sred[BNR_GT * BNR_GT + idx]) + (sred[2 * BNR_GT * BNR_GT + idx] + sred[3 * BNR_GT * BNR_GT + idx]));
+        else bnr_gstore(out + idx, sred[idx] + sred[BNR_GT * BNR_GT + idx]);
     }
 }
 template <class SRC, int KG>
@@ -912,7 +890,7 @@ __global__ __launch_bounds__(KG * 256, 4 / KG) void k_gram(const SRC chain_src, 
     while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
     int tj = t - ti * (ti + 1) / 2;
     BNR_TL_IN(cd, TL_GRAM, gslot == 0);
-    bnr_gram16_task<KG, false>(bnr_geom_of(cd), Sp, cd.Gpart, t, ti, tj, ks, sred);
+    bnr_gram16_task<KG>(bnr_geom_of(cd), Sp, cd.Gpart, t, ti, tj, ks, sred);
     bnr_gram_count(cd, tj);
     BNR_TL_OUT(cd, TL_GRAM);
 }
@@ -928,15 +906,11 @@ __global__ __launch_bounds__(KG * 256, 4 / KG) void k_gram(const SRC chain_src, 
 // of LDS instead of two (K-group 1 parks its tile, K-group 0 adds its registers and stores).  Eight waves per SIMD (64 VGPRs through
 // buffer descriptors) brought nothing more (profiles/round2_experiments_notes.txt D).
 // one (tile t = (ti, tj), K slice ks) task of the Gram with 8-column batches: 512 threads, sred = 32 KiB of LDS.
-// ROT >= 0 (persistent kernel): the workgroup's issue priority rotates through BNR_G8P_WPC levels every 16 batches, phase = ROT = its age
-// rank on the CU.  The arbiter serves equal priorities oldest-first, and a persistent workgroup never gets older relative to its
-// two neighbours: without the rotation the eldest runs a task in 61 us, the second in 100, the youngest in 175, and the launch
-// ends with the youngest ones' half-done tasks on an otherwise idle chip.
-template <bool WT>
-__device__ __forceinline__ void bnr_gram8_task(const bnr_gram_geom &cd, const double *Sp, double *Gpart, int t, int ti, int tj, int ks, double *sred, int rot = -1, int tid = -1, int rotmod = BNR_G8P_WPC, unsigned long long *clk = nullptr)
+// clk: where the stamps build records both clocks around the K loop (nullptr: nowhere)
+__device__ __forceinline__ void bnr_gram8_task(const bnr_gram_geom &cd, const double *Sp, double *Gpart, int t, int ti, int tj, int ks, double *sred, unsigned long long *clk = nullptr)
 {
     constexpr int KG = 2, KB = 8;
-    if (tid < 0) tid = threadIdx.x;
+    const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
     const int kg = wave >> 2, wi = (wave >> 1) & 1, wj = wave & 1;
     const int kchunk = cd.q_pad / cd.ksplit;          // multiple of 8 KG (host guarantees)
@@ -999,15 +973,7 @@ __device__ __forceinline__ void bnr_gram8_task(const bnr_gram_geom &cd, const do
     // both clocks around the K loop: shader cycles / 100 MHz ticks = the clock the PRODUCT kernel's loop runs at (tools/stamps_gram_clock.py)
     if (clk && tid == 0) { clk[0] = __builtin_amdgcn_s_memtime(); clk[1] = __builtin_amdgcn_s_memrealtime(); }
 #endif
-#define BNR_G8_BATCH_(B, DIAG)                                                                \
-    do {                                                                                      \
-        BNR_G8_COMPUTE((B) & 1, 0, DIAG);                                                     \
-        BNR_G8_STORE(((B) + 1) & 1);               /* batch b+1; its buffer was released by the last barrier */ \
-        BNR_G8_LOAD((B) + 2);                                                                 \
-        BNR_G8_COMPUTE((B) & 1, 1, DIAG);                                                     \
-        __syncthreads();                                                                      \
-    } while (0)
-#define BNR_G8_BATCH(B) BNR_G8_BATCH_(B, false)
+    // first k-step of batch b, then the staging of batch b + 1 (its buffer was released by the last barrier), then the second k-step;
     // two batches per trip with the buffer parity a literal: every LDS address is "lane base + immediate"
 #define BNR_G8_BATCH_L(B, PAR, DIAG)                                                          \
     do {                                                                                      \
@@ -1017,7 +983,7 @@ __device__ __forceinline__ void bnr_gram8_task(const bnr_gram_geom &cd, const do
         BNR_G8_COMPUTE(PAR, 1, DIAG);                                                         \
         __syncthreads();                                                                      \
     } while (0)
-    if (BNR_GRAM_SKIP_DEAD && ti == tj && wi == 0 && wj == 1) {
+    if (ti == tj && wi == 0 && wj == 1) {
         // dead block of a diagonal tile (see bnr_gram16_task): staging and barriers only, zeros out
         int b = 0;
         for (; b + 1 < nbatch; b += 2) {
@@ -1025,24 +991,15 @@ __device__ __forceinline__ void bnr_gram8_task(const bnr_gram_geom &cd, const do
             BNR_G8_STORE(0); BNR_G8_LOAD(b + 3); __syncthreads();
         }
         if (b < nbatch) { BNR_G8_STORE(1); BNR_G8_LOAD(b + 2); __syncthreads(); }
-    } else if (BNR_GRAM_SKIP_DEAD && ti == tj && wi == wj) {
+    } else if (ti == tj && wi == wj) {
         // a diagonal 32 x 32 block: three MFMAs per k-step (see bnr_gram16_task)
         int b = 0;
         for (; b + 1 < nbatch; b += 2) { BNR_G8_BATCH_L(b, 0, true); BNR_G8_BATCH_L(b + 1, 1, true); }
         if (b < nbatch) BNR_G8_BATCH_L(b, 0, true);
-    } else if (rot < 0) {
+    } else {
         int b = 0;
         for (; b + 1 < nbatch; b += 2) { BNR_G8_BATCH_L(b, 0, false); BNR_G8_BATCH_L(b + 1, 1, false); }
         if (b < nbatch) BNR_G8_BATCH_L(b, 0, false);
-    } else {
-        // the same loop in chunks of 16 batches with the priority rotation between the chunks (kept out of the inner loop: a
-        // branch in there changes how the compiler interleaves the MFMAs with the LDS reads)
-        int b = 0;
-        for (int ch = 0; b < nbatch; ++ch) {
-            bnr_setprio3((rot + ch) % rotmod);
-            const int be = b + 16 < nbatch ? b + 16 : nbatch;
-            for (; b < be; ++b) BNR_G8_BATCH(b);
-        }
     }
 #ifdef BNR_STAMPS
     if (clk && tid == 0) { clk[2] = __builtin_amdgcn_s_memtime(); clk[3] = __builtin_amdgcn_s_memrealtime(); }
@@ -1063,10 +1020,10 @@ __device__ __forceinline__ void bnr_gram8_task(const bnr_gram_geom &cd, const do
         double *out = Gpart + ((size_t)ks * (cd.ntile * (cd.ntile + 1) / 2) + t) * (BNR_GT * BNR_GT);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            bnr_gstore<WT>(out + (jb + 4 * r) * BNR_GT + ib, c00[r] + sred[(jb + 4 * r) * BNR_GT + ib]);
-            bnr_gstore<WT>(out + (jb + 4 * r) * BNR_GT + ib + 16, c01[r] + sred[(jb + 4 * r) * BNR_GT + ib + 16]);
-            bnr_gstore<WT>(out + (jb + 16 + 4 * r) * BNR_GT + ib, c10[r] + sred[(jb + 16 + 4 * r) * BNR_GT + ib]);
-            bnr_gstore<WT>(out + (jb + 16 + 4 * r) * BNR_GT + ib + 16, c11[r] + sred[(jb + 16 + 4 * r) * BNR_GT + ib + 16]);
+            bnr_gstore(out + (jb + 4 * r) * BNR_GT + ib, c00[r] + sred[(jb + 4 * r) * BNR_GT + ib]);
+            bnr_gstore(out + (jb + 4 * r) * BNR_GT + ib + 16, c01[r] + sred[(jb + 4 * r) * BNR_GT + ib + 16]);
+            bnr_gstore(out + (jb + 16 + 4 * r) * BNR_GT + ib, c10[r] + sred[(jb + 16 + 4 * r) * BNR_GT + ib]);
+            bnr_gstore(out + (jb + 16 + 4 * r) * BNR_GT + ib + 16, c11[r] + sred[(jb + 16 + 4 * r) * BNR_GT + ib + 16]);
         }
     }
 }
@@ -1087,9 +1044,9 @@ __global__ __launch_bounds__(512, 6) void k_gram8(const SRC chain_src, int s, in
     int tj = t - ti * (ti + 1) / 2;
     BNR_TL_IN(cd, TL_GRAM, gslot == 0);
 #ifdef BNR_STAMPS
-    bnr_gram8_task<false>(bnr_geom_of(cd), Sp, cd.Gpart, t, ti, tj, ks, sred, -1, -1, BNR_G8P_WPC, gslot < 256 ? cd.dbg + 2048 + 4 * gslot : nullptr);
+    bnr_gram8_task(bnr_geom_of(cd), Sp, cd.Gpart, t, ti, tj, ks, sred, gslot < 256 ? cd.dbg + 2048 + 4 * gslot : nullptr);
 #else
-    bnr_gram8_task<false>(bnr_geom_of(cd), Sp, cd.Gpart, t, ti, tj, ks, sred);
+    bnr_gram8_task(bnr_geom_of(cd), Sp, cd.Gpart, t, ti, tj, ks, sred);
 #endif
     bnr_gram_count(cd, tj);
     BNR_TL_OUT(cd, TL_GRAM);
@@ -1313,13 +1270,15 @@ __global__ __launch_bounds__(256) void k_gram_reduce(const SRC chain_src, int s)
 // (G + I) a4 = b,  b = a1 - a3  (gibbs.jl:434; the reference's generic `\` is an LU solve of this SPD system).
 // Right-looking blocked Cholesky of E, NB = 32, ONE launch per panel with lookahead 1 (k_chol_step(p), p = 0..nbk-1).
 // Every block row of E (matrix rows, identity rows, the b block) runs the same code:
-//   role A (nbk + 2 panel workgroups): apply panel p-1's update to the blocks (p,p) and (rho,p) by f64 MFMA (operands
-//       loaded from L2 straight in fragment layout), then ONE wavefront sweeps the 64 x 32 register-resident panel
-//       [E_pp ; E_rho,p] column by column: pivot chain on scalars, rsqrt = v_rsq_f64 + one third-order step, rank-1 updates of
-//       the next two columns with v_readlane broadcasts, of the remaining columns one step later with the previous column's
-//       multipliers, also by v_readlane (bnr_sweep16).
+//   role A (nbk + 1 panel workgroups): apply panel p-1's update to the blocks (p,p) and (rho,p) by f64 MFMA -- the two blocks of
+//       panel p-1 it needs are fetched once per workgroup, cooperatively, into LDS and the fragments come from there --, then the
+//       workgroup's FOUR waves sweep the 64 x 32 register-resident panel [E_pp ; E_rho,p] as a pipeline, eight columns each
+//       (bnr_panel_sweep_pipe): a wave first applies the columns that the waves in front publish in LDS, its multipliers
+//       taken by DPP row broadcast out of one LDS read per column, then walks its own eight pivots (bnr_sweepN: pivot chain on
+//       scalars, rsqrt = v_rsq_f64 + one third-order step, rank-1 updates by v_readlane broadcasts) and publishes each column.
 //       Lanes 0-31 redo the diagonal block in every workgroup: no cross-workgroup hand-off inside a launch.
 //   role B (update workgroups): E[rho,j] -= L[rho,p-1] L[j,p-1]' for every block column j >= p+1, by f64 MFMA.
+// k_chol_step2 (two panels per launch, large n) keeps the sweep of ONE wave per panel, 16 columns at a time (bnr_sweep16 = bnr_sweepN<16>).
 // k_solve_gemv: a4 = Y w, then the n-vector bookkeeping for X gamma_new.
 __device__ __forceinline__ double bnr_readlane(double v, int srclane)
 {
@@ -1329,15 +1288,6 @@ __device__ __forceinline__ double bnr_readlane(double v, int srclane)
     return __hiloint2double(hi, lo);
 }
 #define BNR_LP (BNR_NB + 1)
-#ifndef BNR_PIPE_DPP
-#define BNR_PIPE_DPP 1       // 1: the consuming waves of the panel pipeline take a column's multipliers by DPP row broadcast out of ONE LDS read (round 6, second half); 0: lane-uniform 16-byte LDS reads
-#endif
-#ifndef BNR_PANEL_COOP_FETCH
-#define BNR_PANEL_COOP_FETCH 1   // 1: a panel workgroup fetches the two blocks of panel p - 1 once, through LDS (round 6); 0: every wave its own fragments from memory
-#endif
-#ifndef BNR_PANEL_PIPE
-#define BNR_PANEL_PIPE 1      // 1: the panel sweep as a pipeline of the workgroup's four waves (round 6, bnr_panel_sweep_pipe); 0: one sweeping wave (rounds 1-5)
-#endif
 __host__ __device__ inline int bnr_chol_npanel(int nbk, int p) { (void)p; return nbk + 1; }
 __host__ __device__ inline int bnr_chol_ntile(int nbk, int p)
 {
@@ -1369,12 +1319,35 @@ __device__ __forceinline__ bnr_d4 bnr_tile_update(const double *colrows, const d
     return c;
 }
 
-// Register-resident sweep of 16 panel columns, lane = row (64 rows): column j's pivot sits in lane COFF + j.
-// The next two columns are updated at once through v_readlane broadcasts, the remaining ones one step later, their
-// multipliers taken from the previous column's register by v_readlane as well (no LDS round trip per pivot).
-#define BNR_L1S 80            // LDS column stride of the 64 x 16 half-panel handed to the MFMA update (conflict-free fragments)
-template <int COFF, bool PUB = false>
-__device__ __forceinline__ int bnr_sweep16(double (&a)[16], int lane, double *pub = nullptr)
+#define BNR_L1S 80            // LDS column stride of the 64 x 16 half-panel handed to the MFMA update of k_chol_step2 (conflict-free fragments)
+// ----------------------------------------------------------------------------------------- round 6: the panel sweep as a pipeline of the four waves
+// One wave walking all 32 pivots with all the rank-1 updates of the columns to their right (rounds 1-5) left three of the workgroup's four SIMDs idle: 45 instructions
+// per pivot at one issue per 4 cycles, 2 x 3 000 cycles, + 1 200 for an MFMA update between the two 16-column halves.  Here every wave owns
+// EIGHT of the 32 columns (lane = row: lanes 0..31 the diagonal block, 32..63 the own block) and the waves form a pipeline over the columns:
+//   wave w first applies the finished columns 0 .. 8w-1 to its own eight as they show up in LDS (sL: one 64-row column per pivot, published by the wave that owns
+//   it the moment it is scaled), two columns per trip, the next trip's four LDS reads in flight; then it walks its own eight pivots (bnr_sweepN<8>: the pivot chain on
+//   wave-uniform scalars, the rank-1 updates reach at most seven columns to the right) and publishes each column.
+// The pivot chain runs through the four waves in turn; what a wave's predecessors publish while they are the chain is applied by the waves behind, off the chain.
+// Nothing is ordered by barriers: a column that is not there yet shows as a NaN with a payload no arithmetic produces (sL is filled with it before the panel is
+// staged), every lane checks its own row and a wave vote says "all 64 rows there" -- which is the whole column, multipliers included.  The polls are bounded: a
+// column that never shows up (it cannot, short of a fault) ends the wait after BNR_PIPE_SPINS polls and reports the panel as failed.
+// Per element the updates arrive in column order except for the swap inside bnr_sweepN (k-2 before k-3): deterministic, independent of timing; NOT the summation
+// order of the one-wave sweep's MFMA mid update, so the factor differs from the round-5 build's in the last bits (the parity bar is rtol 1e-6 against the CPU restatement of the reference, tests/).
+#define BNR_PIPE_SPINS (1 << 16)
+#define BNR_PIPE_SENT_HI 0x7FF8DEAD
+__device__ __forceinline__ double bnr_canon_nan(double v) { return v == v ? v : __hiloint2double(0x7FF80000, 0); }
+struct alignas(16) bnr_panelp_lds {
+    double sD[BNR_NB * BNR_LP], sB[BNR_NB * BNR_LP];
+    double sL[BNR_NB][64];
+};
+__device__ __forceinline__ unsigned bnr_lds_addr(const void *p) { return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const void *)p; }
+// Register-resident sweep of N panel columns, lane = row (64 rows): column j's pivot sits in lane COFF + j.  The next two columns are updated at once through
+// v_readlane broadcasts, the remaining ones one step later, their multipliers taken from the previous column's register by v_readlane as well (no LDS round trip
+// per pivot).  PUB: 0 nothing, 2 every finished column goes to pub_addr + 512 j bytes (LDS, lane = row)
+struct bnr_no_hook { __device__ __forceinline__ void operator()() const {} };
+// (hook: called once, behind the issue of the first pivot's v_rsq_f64 -- multiply-adds of the wave's columns 2 .. N - 1 that are still pending run in that shadow)
+template <int N, int COFF, int PUB, class HOOK = bnr_no_hook>
+__device__ __forceinline__ int bnr_sweepN(double (&a)[N], int lane, unsigned pub_addr, HOOK hook = HOOK())
 {
     int bad = 0;
     double lprev = 0.0;
@@ -1382,23 +1355,24 @@ __device__ __forceinline__ int bnr_sweep16(double (&a)[16], int lane, double *pu
     // wave-uniform scalars: with s1 = a[j+1] and s2 = a[j] at row j+1 (read by v_readlane BEFORE column j is scaled, i.e.
     // off the chain), l_{j+1,j} = s2 rinv and the next pivot is fma(-l, l, s1) -- exactly the operations the vector
     // update performs on that lane, so the results are bitwise those of the plain column sweep, but the chain per pivot is
-    // rsq + 2 Newton steps + 2 operations instead of also scaling the column, broadcasting it and updating the next one.
+    // rsq + one third-order step + 2 operations instead of also scaling the column, broadcasting it and updating the next one.
     double piv = bnr_readlane(a[0], COFF);
 #pragma unroll
-    for (int j = 0; j < 16; ++j) {
-        double tk[16];
+    for (int j = 0; j < N; ++j) {
+        double tk[N];
         double s1 = 0.0, s2 = 0.0, s3 = 0.0;
-        if (j + 1 < 16) { s1 = bnr_readlane(a[j + 1], COFF + j + 1); s2 = bnr_readlane(a[j], COFF + j + 1); }
-        if (j + 2 < 16) s3 = bnr_readlane(a[j], COFF + j + 2);
+        if (j + 1 < N) { s1 = bnr_readlane(a[j + 1], COFF + j + 1); s2 = bnr_readlane(a[j], COFF + j + 1); }
+        if (j + 2 < N) s3 = bnr_readlane(a[j], COFF + j + 2);
         if (!(piv > 0.0)) bad = 1;                       // not positive definite: NaNs from here on, reported by the caller
         // the reciprocal square root is started first: the wave issues in order, so the v_rsq_f64 (quarter rate, long latency)
         // runs while the broadcasts below are read
         double y = __builtin_amdgcn_rsq(piv);
+        if (j == 0) hook();
         // the multipliers l_{k,j-1} of the lagged update come from the previous column's register by v_readlane (wave-uniform scalars):
         // no LDS write -> wait -> read round trip per pivot
         if (j >= 1) {
 #pragma unroll
-            for (int k = j + 2; k < 16; ++k) tk[k] = bnr_readlane(lprev, COFF + k);
+            for (int k = j + 2; k < N; ++k) tk[k] = bnr_readlane(lprev, COFF + k);
         }
         // v_rsq_f64 is good to 2^-24 (tools/rsq_precision.hip); ONE third-order step y (1 + e/2 + 3 e^2/8), e = 1 - x y^2,
         // gives 1.2 ulp -- what two Newton steps give -- in 5 instead of 8 operations and depth 4 instead of 6
@@ -1408,181 +1382,9 @@ __device__ __forceinline__ int bnr_sweep16(double (&a)[16], int lane, double *pu
         piv = fma(-t1, t1, s1);                          // next pivot
         double lj = a[j] * rinv;
         a[j] = lj;
-        if (PUB) pub[j * BNR_L1S + lane] = lj;             // the finished column goes to LDS at once (an LDS write costs the chain nothing) instead of 16 writes behind the sweep
-        if (j + 1 < 16) a[j + 1] = fma(-lj, t1, a[j + 1]);
-        if (j + 2 < 16) a[j + 2] = fma(-lj, s3 * rinv, a[j + 2]);
-        if (j >= 1) {
-#pragma unroll
-            for (int k = j + 2; k < 16; ++k) a[k] = fma(-lprev, tk[k], a[k]);
-        }
-        lprev = lj;
-    }
-    return bad;
-}
-
-struct bnr_panel_lds {
-    double sD[BNR_NB * BNR_LP], sB[BNR_NB * BNR_LP];
-    double sL1[16 * BNR_L1S];
-};
-// Sweep of the 64 x 32 panel [D ; B] by one workgroup of 256 threads: D = updated, unfactored diagonal block, B = own
-// block, both handed over as the MFMA accumulator fragments (mt, nt) of the four waves.  On return sh.sB holds
-// B L_D^-T (column-major, stride BNR_LP); the factored diagonal block is not produced.  Returns (wave 0 only) 1 if a
-// pivot was not positive.
-// Two halves of 16 columns (lane = row: lanes 0..31 rows of the diagonal block, lanes 32..63 rows of the own block);
-// between them the second half is updated with the first by f64 MFMA on all four waves:
-//   A[:, 16:32] -= L[:, 0:16] L[16:32, 0:16]'
-__device__ __forceinline__ int bnr_panel_sweep(bnr_panel_lds &sh, const bnr_d4 &cD, const bnr_d4 &cB, int tid, double *dst, size_t ld, unsigned long long *ph = nullptr)
-{
-#ifdef BNR_STAMPS
-#define BNR_PH(i) do { if (ph && tid == 0) ph[i] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define BNR_PH(i) do { } while (0)
-#endif
-    BNR_PH(0);
-    const int wave = tid >> 6, lane = tid & 63, mt = wave >> 1, nt = wave & 1, ln = lane & 15, lq = lane >> 4;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        sh.sD[(nt * 16 + ln) + BNR_LP * (mt * 16 + lq + 4 * r)] = cD[r];
-        sh.sB[(nt * 16 + ln) + BNR_LP * (mt * 16 + lq + 4 * r)] = cB[r];
-    }
-    __syncthreads();
-    BNR_PH(1);
-    const int rr = lane & 31;
-    double a1[16], a2[16];
-    int bad = 0;
-    if (wave == 0) {
-        const double *src = (lane < 32) ? sh.sD : sh.sB;
-#pragma unroll
-        for (int c = 0; c < 16; ++c) a1[c] = src[rr + BNR_LP * c];
-        BNR_PH(2);
-        bad = bnr_sweep16<0, true>(a1, lane, sh.sL1);
-        BNR_PH(3);
-    }
-    __syncthreads();
-    BNR_PH(4);
-    {
-        // wave w owns rows 16 w .. 16 w + 15 of the 64-row panel
-        double *sx = (wave < 2) ? sh.sD : sh.sB;
-        const int rowb = (wave & 1) * 16;
-        bnr_d4 c;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) c[r] = sx[(rowb + ln) + BNR_LP * (16 + lq + 4 * r)];
-        double av[4], bv[4];                                                   // all eight fragments in flight before the chain of four dependent MFMAs
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            av[ks] = sh.sL1[(4 * ks + lq) * BNR_L1S + 16 + ln];               // column side: rows 16..31 of the diagonal part
-            bv[ks] = sh.sL1[(4 * ks + lq) * BNR_L1S + 16 * wave + ln];        // row side
-        }
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) c = __builtin_amdgcn_mfma_f64_16x16x4f64(-av[ks], bv[ks], c, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) sx[(rowb + ln) + BNR_LP * (16 + lq + 4 * r)] = c[r];
-    }
-    __syncthreads();
-    BNR_PH(5);
-    if (wave == 0) {
-        const double *src = (lane < 32) ? sh.sD : sh.sB;
-#pragma unroll
-        for (int c = 0; c < 16; ++c) a2[c] = src[rr + BNR_LP * (16 + c)];
-        BNR_PH(6);
-        bad |= bnr_sweep16<16>(a2, lane);
-        BNR_PH(7);
-        // the swept own block goes to E straight from the sweeping wave's registers (lane = row: 32 coalesced 256-byte stores; the
-        // LDS hand-back + barrier + store by all four waves cost ~1000 cycles at the end of every panel step); the factored
-        // diagonal block is not needed by anybody later
-        if (dst && lane >= 32) {
-#pragma unroll
-            for (int c = 0; c < 16; ++c) { dst[(size_t)rr + ld * (size_t)c] = a1[c]; dst[(size_t)rr + ld * (size_t)(16 + c)] = a2[c]; }
-        }
-    }
-    return bad;
-}
-// ----------------------------------------------------------------------------------------- round 6: the panel sweep as a pipeline of the four waves
-// bnr_panel_sweep above leaves three of the workgroup's four SIMDs idle while ONE wave walks the 32 pivots with all the rank-1 updates of the columns to their
-// right (45 instructions per pivot at one issue per 4 cycles: 2 x 3 000 cycles, + 1 200 for the MFMA update between the two 16-column halves).  Here every wave owns
-// EIGHT of the 32 columns (lane = row as before: lanes 0..31 the diagonal block, 32..63 the own block) and the waves form a pipeline over the columns:
-//   wave w first applies the finished columns 0 .. 8w-1 to its own eight as they show up in LDS (sL: one 64-row column per pivot, published by the wave that owns
-//   it the moment it is scaled), two columns per trip, ten LDS reads in flight; then it walks its own eight pivots (bnr_sweepN<8>: the pivot chain on wave-uniform
-//   scalars as before, the rank-1 updates now reach at most seven columns to the right) and publishes each column.
-// The pivot chain runs through the four waves in turn; what a wave's predecessors publish while they are the chain is applied by the waves behind, off the chain.
-// Nothing is ordered by barriers: a column that is not there yet shows as a NaN with a payload no arithmetic produces (sL is filled with it before the panel is
-// staged), every lane checks its own row and a wave vote says "all 64 rows there" -- which is the whole column, multipliers included.  The polls are bounded: a
-// column that never shows up (it cannot, short of a fault) ends the wait after BNR_PIPE_SPINS polls and reports the panel as failed.
-// Per element the updates arrive in column order except for the swap inside bnr_sweepN (k-2 before k-3): deterministic, independent of timing; NOT the summation
-// order of bnr_panel_sweep's MFMA mid update, so the factor differs from the round-5 build's in the last bits (the parity bar is rtol 1e-6 against the CPU restatement of the reference, tests/).
-#define BNR_PIPE_SPINS (1 << 16)
-#ifndef BNR_PIPE_TIE
-#define BNR_PIPE_TIE 0      // 1: the publishing store tied to the block's last column instead of the next pivot (measured slower: one chain 172-174 against 168 us per sweep)
-#endif
-#ifndef BNR_PIPE_LATEPUB
-#define BNR_PIPE_LATEPUB 0      // 1: column j - 1 published behind the issue of pivot j's v_rsq_f64 (off the chain, but ~40 cycles later): tools/pipe_lab.hip 7 000 cycles per panel against 6 650
-#endif
-#ifndef BNR_PIPE_FASTHAND
-#define BNR_PIPE_FASTHAND 1
-#endif
-#ifndef BNR_PIPE_HEAVY
-#define BNR_PIPE_HEAVY 0    // 1: a starved wave polls with all ten reads instead of one (one chain 169.5 against 168.0 us per sweep)
-#endif
-#define BNR_PIPE_SENT_HI 0x7FF8DEAD
-__device__ __forceinline__ double bnr_canon_nan(double v) { return v == v ? v : __hiloint2double(0x7FF80000, 0); }
-struct alignas(16) bnr_panelp_lds {
-    double sD[BNR_NB * BNR_LP], sB[BNR_NB * BNR_LP];
-    double sL[BNR_NB][64];
-#ifdef BNR_STAMPS_FINE
-    unsigned long long st[4][24];          // per wave: [0..11] when a trip's pair of columns was there, [12..19] when an own column was published, [20] polls
-#endif
-};
-__device__ __forceinline__ unsigned bnr_lds_addr(const void *p) { return (unsigned)(unsigned long long)(__attribute__((address_space(3))) const void *)p; }
-// sweep of N panel columns held one row per lane: column j's pivot sits in lane COFF + j.  PUB: 0 nothing, 2 every finished column goes to pub + 512 j bytes (LDS, lane = row)
-struct bnr_no_hook { __device__ __forceinline__ void operator()() const {} };
-// (hook: called once, behind the issue of the first pivot's v_rsq_f64 -- multiply-adds of the wave's columns 2 .. N - 1 that are still pending run in that shadow)
-template <int N, int COFF, int PUB, class HOOK = bnr_no_hook>
-__device__ __forceinline__ int bnr_sweepN(double (&a)[N], int lane, unsigned pub_addr, unsigned long long *pst = nullptr, HOOK hook = HOOK())
-{
-    int bad = 0;
-    double lprev = 0.0;
-    double piv = bnr_readlane(a[0], COFF);
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        double tk[N];
-        double s1 = 0.0, s2 = 0.0, s3 = 0.0;
-        if (j + 1 < N) { s1 = bnr_readlane(a[j + 1], COFF + j + 1); s2 = bnr_readlane(a[j], COFF + j + 1); }
-        if (j + 2 < N) s3 = bnr_readlane(a[j], COFF + j + 2);
-        if (!(piv > 0.0)) bad = 1;
-        double y = __builtin_amdgcn_rsq(piv);
-        if (j == 0) hook();
-#if BNR_PIPE_LATEPUB
-        // column j - 1 goes to LDS here, right behind the issue of this pivot's v_rsq_f64 and named as its consumer: the store's issue slot sits inside the rsq's latency
-        // instead of between "next pivot known" and "its rsq issued" (measured: a publishing wave walks its pivots at ~155 cycles each, one that publishes nothing at ~118)
-        if (PUB == 2 && j >= 1) asm volatile("ds_write_b64 %1, %2 offset:%3" : "+v"(y) : "v"(pub_addr), "v"(lprev), "n"(512 * (j >= 1 ? j - 1 : 0)) : "memory");
-#endif
-        if (j >= 1) {
-#pragma unroll
-            for (int k = j + 2; k < N; ++k) tk[k] = bnr_readlane(lprev, COFF + k);
-        }
-        const double e = fma(-(piv * y), y, 1.0);
-        const double rinv = fma(y * e, fma(0.375, e, 0.5), y);
-        const double t1 = s2 * rinv;
-        piv = fma(-t1, t1, s1);
-        double lj = a[j] * rinv;
-        a[j] = lj;
-#if BNR_PIPE_LATEPUB
-        if (PUB == 2 && j == N - 1) asm volatile("ds_write_b64 %0, %1 offset:%2" :: "v"(pub_addr), "v"(lj), "n"(512 * j) : "memory");
-#endif
-        // (the store names a register of the sweep as an in/out operand: without such a tie the scheduler walks the whole pivot chain first and sinks all N stores behind
-        // it -- the waves behind would see the columns only when this wave is done.  The last column of the block is the register: every pivot's lagged update touches it,
-        // so the stores stay one per pivot and in order, but off the rsq chain; the next pivot itself for the last columns, which have no such update left)
-#ifdef BNR_LAB_NOPUB          // (tools/pipe_lab.hip, timing only: the sweep without its publishing stores)
-        if (false) {
-#else
-        if (PUB == 2 && !BNR_PIPE_LATEPUB) {
-#endif
-            if (BNR_PIPE_TIE && j + 3 < N) asm volatile("ds_write_b64 %1, %2 offset:%3" : "+v"(a[N - 1]) : "v"(pub_addr), "v"(lj), "n"(512 * j) : "memory");
-            else asm volatile("ds_write_b64 %1, %2 offset:%3" : "+v"(piv) : "v"(pub_addr), "v"(lj), "n"(512 * j) : "memory");
-        }
-#ifdef BNR_STAMPS_FINE
-        if (pst && lane == 0) pst[j] = __builtin_amdgcn_s_memtime();
-#endif
+        // (the publishing store names the next pivot as an in/out operand: without such a tie the scheduler walks the whole pivot chain first and sinks all N stores
+        // behind it -- the waves behind would see the columns only when this wave is done)
+        if (PUB == 2) asm volatile("ds_write_b64 %1, %2 offset:%3" : "+v"(piv) : "v"(pub_addr), "v"(lj), "n"(512 * j) : "memory");
         if (j + 1 < N) a[j + 1] = fma(-lj, t1, a[j + 1]);
         if (j + 2 < N) a[j + 2] = fma(-lj, s3 * rinv, a[j + 2]);
         if (j >= 1) {
@@ -1593,9 +1395,9 @@ __device__ __forceinline__ int bnr_sweepN(double (&a)[N], int lane, unsigned pub
     }
     return bad;
 }
-#ifdef BNR_LAB_STAMPS
-__shared__ unsigned long long bnr_lab_stamp[8];
-#endif
+// the one-wave sweep of 16 columns that k_chol_step2 keeps: nothing published
+template <int COFF>
+__device__ __forceinline__ int bnr_sweep16(double (&a)[16], int lane) { return bnr_sweepN<16, COFF, 0>(a, lane, 0u); }
 template <int W>
 __device__ __forceinline__ int bnr_pipe_wave(bnr_panelp_lds &sh, int lane, double *dst, size_t ld, unsigned long long *ph = nullptr)
 {
@@ -1611,72 +1413,21 @@ __device__ __forceinline__ int bnr_pipe_wave(bnr_panelp_lds &sh, int lane, doubl
 #pragma unroll
     for (int c = 0; c < 8; ++c) a[c] = src[rr + BNR_LP * (C0 + c)];
     int bad = 0;
-    // the columns of the waves in front, two per trip: this lane's row of both columns (ds_read_b64) and their eight multipliers each -- rows C0 .. C0 + 7 of the
-    // column, the same address in every lane: four ds_read_b128 -- ; the ten reads of the NEXT trip are in flight under this trip's sixteen multiply-adds.  A wave that
-    // has caught up with the publishing wave polls with ONE read (its row of the later column) and fetches the other nine when that shows up.
-    // (multipliers by v_readlane out of the column's register instead: 16 + 16 v_readlane_b32 per column pair made a trip 420-500 cycles -- the waves behind fell a whole
-    // block of columns behind the chain and every hand-over waited 1 300 cycles for them, profiles/round6_experiments_notes.txt B)
-    unsigned vcol = bnr_lds_addr(&sh.sL[0][lane]), vmul = bnr_lds_addr(&sh.sL[0][C0]);
-    double c0 = 0.0, c1 = 0.0, n0 = 0.0, n1 = 0.0;
-    bnr_d2 m[8], mn[8];
-    (void)vmul; (void)c0; (void)c1; (void)n0; (void)n1; (void)m; (void)mn;          // (the lane-uniform path's registers; unused with BNR_PIPE_DPP)
-    // (OFF: byte offset of the column pair relative to the running addresses vcol / vmul)
-#define BNR_PIPE_READ10(X0, X1, M, OFF)                                                                                                                      \
-    asm volatile("ds_read_b64 %0, %10 offset:%12\n\tds_read_b64 %1, %10 offset:%13\n\t"                                                                      \
-                 "ds_read_b128 %2, %11 offset:%12\n\tds_read_b128 %3, %11 offset:%14\n\tds_read_b128 %4, %11 offset:%15\n\tds_read_b128 %5, %11 offset:%16\n\t" \
-                 "ds_read_b128 %6, %11 offset:%13\n\tds_read_b128 %7, %11 offset:%17\n\tds_read_b128 %8, %11 offset:%18\n\tds_read_b128 %9, %11 offset:%19"      \
-                 : "=&v"(X0), "=&v"(X1), "=&v"(M[0]), "=&v"(M[1]), "=&v"(M[2]), "=&v"(M[3]), "=&v"(M[4]), "=&v"(M[5]), "=&v"(M[6]), "=&v"(M[7])              \
-                 : "v"(vcol), "v"(vmul), "n"(OFF), "n"((OFF) + 512), "n"((OFF) + 16), "n"((OFF) + 32), "n"((OFF) + 48),                                      \
-                   "n"((OFF) + 528), "n"((OFF) + 544), "n"((OFF) + 560) : "memory");                                                                         \
-    /* (and an empty statement that names the accumulators: the multiply-adds that follow in the source stay behind the reads) */                            \
-    asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]))
-    // (the wait names the trip's accumulators as operands too: the multiply-adds of the trip before stay in front of it, under the reads in flight)
-#define BNR_PIPE_WAIT10(X0, X1, M) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(X0), "+v"(X1), "+v"(M[0]), "+v"(M[1]), "+v"(M[2]), "+v"(M[3]), "+v"(M[4]), "+v"(M[5]), "+v"(M[6]), "+v"(M[7]), \
-                                                "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]) :: "memory")
-#define BNR_PIPE_POLL1(X1, OFF) asm volatile("ds_read_b64 %0, %1 offset:%2\n\ts_waitcnt lgkmcnt(0)" : "=&v"(X1) : "v"(vcol), "n"((OFF) + 512) : "memory")
+    // The columns of the waves in front, two per trip: this lane's row of both columns and their eight multipliers each -- rows C0 .. C0 + 7 of the column.  The
+    // multipliers reach the lanes by DPP: one ds_read_b64 per column puts them into lanes 0 .. 7 of every row of 16 lanes (lane q of a row reads row C0 + (q & 7): eight
+    // distinct addresses in 64 bytes, conflict-free), and the multiply-add takes its multiplier as "lane n of my row" (v_fmac_f64 with the DPP control row_newbcast:n,
+    // the one DPP mode of 64-bit operands).  The four reads of the NEXT trip are in flight under this trip's sixteen multiply-adds.
+    // What lost against it (profiles/round6_experiments_notes.txt):
+    //   lane-uniform ds_read_b128 of the multipliers (the same address in every lane): 9 KiB through the LDS pipe per column pair instead of 2 KiB -- a lane-uniform
+    //   read costs its full 1 KiB pass -- and 32 VGPRs of multipliers instead of 4; bitwise the same values (same products, same fused multiply-adds in the same order);
+    //   multipliers by v_readlane out of the column's register: 16 + 16 v_readlane_b32 per column pair made a trip 420-500 cycles -- the waves behind fell a whole block of
+    //   columns behind the chain and every hand-over waited 1 300 cycles for them.
 #define BNR_PIPE_HERE(X0, X1) __all(__double2hiint(X0) != BNR_PIPE_SENT_HI && __double2hiint(X1) != BNR_PIPE_SENT_HI)
-    // one trip: the pair at OFF is in flight into (X0, X1, M); wait, poll if it is not there yet, start the next pair's reads into (Y0, Y1, MY), apply
-#define BNR_PIPE_TRIP(X0, X1, M, OFF, Y0, Y1, MY, MORE)                                                                  \
-    do {                                                                                                                \
-        BNR_PIPE_WAIT10(X0, X1, M);                                                                                     \
-        if (!BNR_PIPE_HERE(X0, X1)) {                                                                                   \
-            int spins = 0;                                                                                              \
-            if (BNR_PIPE_HEAVY) {                                                                                       \
-            do {                                     /* (every poll is the ten reads: one LDS round trip between a publication and its use, not two) */ \
-                ++npoll;                                                                                                \
-                if (++spins > BNR_PIPE_SPINS) { bad = 1; break; }                                                       \
-                BNR_PIPE_READ10(X0, X1, M, OFF);                                                                        \
-                BNR_PIPE_WAIT10(X0, X1, M);                                                                             \
-            } while (!BNR_PIPE_HERE(X0, X1));                                                                           \
-            } else {                                                                                                    \
-            do {                                                                                                        \
-                ++npoll;                                                                                                \
-                if (++spins > BNR_PIPE_SPINS) { bad = 1; break; }                                                       \
-                BNR_PIPE_POLL1(X1, OFF);                                                                                \
-            } while (!__all(__double2hiint(X1) != BNR_PIPE_SENT_HI));                                                   \
-            BNR_PIPE_READ10(X0, X1, M, OFF);                                                                            \
-            BNR_PIPE_WAIT10(X0, X1, M);                                                                                 \
-            }                                                                                                           \
-        }                                                                                                               \
-        BNR_PIPE_TSTAMP();                                                                                              \
-        if (MORE) BNR_PIPE_READ10(Y0, Y1, MY, (OFF) + 1024);                                                            \
-        _Pragma("unroll") for (int c = 0; c < 8; ++c) a[c] = fma(-(X0), M[c >> 1][c & 1], a[c]);                         \
-        _Pragma("unroll") for (int c = 0; c < 8; ++c) a[c] = fma(-(X1), M[4 + (c >> 1)][c & 1], a[c]);                   \
-    } while (0)
-    int ntrip = 0, npoll = 0;
-#ifdef BNR_STAMPS_FINE     // (per-trip and per-pivot stamps perturb what they measure -- s_memtime returns through the LGKM counter --: a build of their own, -DBNR_STAMPS -DBNR_STAMPS_FINE)
-#define BNR_PIPE_TSTAMP() do { if (lane == 0) sh.st[W][ntrip] = __builtin_amdgcn_s_memtime(); ++ntrip; } while (0)
-#else
-#define BNR_PIPE_TSTAMP() do { } while (0)
-#endif
-#if BNR_PIPE_DPP
-    // The eight multipliers of a column -- its rows C0 .. C0 + 7 -- reach the lanes by DPP, not by lane-uniform LDS reads: one ds_read_b64 per column puts them into lanes
-    // 0 .. 7 of every row of 16 lanes (lane q of a row reads row C0 + (q & 7): eight distinct addresses in 64 bytes, conflict-free), and the multiply-add takes its multiplier
-    // as "lane n of my row" (v_fmac_f64 with the DPP control row_newbcast:n, the one DPP mode of 64-bit operands): per column pair four ds_read_b64 = 2 KiB through the LDS
-    // pipe instead of two ds_read_b64 + eight lane-uniform ds_read_b128 = 9 KiB (a lane-uniform read costs its full 1 KiB pass), and 4 VGPRs of multipliers instead of 32.
-    // Same products (-m x = -x m), same fused multiply-adds in the same order per element: bitwise the values of the other path.
-    unsigned vc = vcol, vm = bnr_lds_addr(&sh.sL[0][C0 + (lane & 7)]);
+    // (OFF: byte offset of the column pair relative to the running addresses vc / vm)
+    unsigned vc = bnr_lds_addr(&sh.sL[0][lane]), vm = bnr_lds_addr(&sh.sL[0][C0 + (lane & 7)]);
     double x0 = 0.0, x1 = 0.0, m0 = 0.0, m1 = 0.0, y0 = 0.0, y1 = 0.0, q0 = 0.0, q1 = 0.0;
+    // (the reads are followed by an empty statement that names the accumulators: the multiply-adds that follow in the source stay behind the reads; the wait names
+    // them too: the multiply-adds of the trip before stay in front of it, under the reads in flight)
 #define BNR_DPP_READ4(X0, X1, M0, M1, OFF)                                                                                                                   \
     do { asm volatile("ds_read_b64 %0, %4 offset:%6\n\tds_read_b64 %1, %4 offset:%7\n\tds_read_b64 %2, %5 offset:%6\n\tds_read_b64 %3, %5 offset:%7"          \
                  : "=&v"(X0), "=&v"(X1), "=&v"(M0), "=&v"(M1) : "v"(vc), "v"(vm), "n"(OFF), "n"((OFF) + 512) : "memory");                                    \
@@ -1729,98 +1480,9 @@ __device__ __forceinline__ int bnr_pipe_wave(bnr_panelp_lds &sh, int lane, doubl
         }
         BNR_DPP_FMA(0, q0, y0); BNR_DPP_FMA(0, q1, y1); BNR_DPP_FMA(1, q0, y0); BNR_DPP_FMA(1, q1, y1);
     }
-#define BNR_DPP_PENDING() do { if (W > 0) BNR_DPP_APPLY(2, y0, y1, q0, q1); } while (0)
-#elif BNR_PIPE_FASTHAND
-    // The LAST pair of columns is the hand-over of the pivot chain to this wave: what starts this wave's first pivot is its own columns 0 and 1 only.  So the last pair is
-    // not fetched like the others (one poll round trip for "is it there", then a second one for the ten reads): the poll itself reads this lane's row of both columns and the
-    // multiplier pair of the own columns 0, 1 of each (four reads), the moment they are there columns 0, 1 are brought up to date and the pivot chain can start; the other six
-    // multiplier reads and their twelve multiply-adds follow beside its first pivot.
-#define BNR_PIPE_READ4(X0, X1, MA, MB, OFF)                                                                                                                  \
-    do { asm volatile("ds_read_b64 %0, %4 offset:%6\n\tds_read_b64 %1, %4 offset:%7\n\tds_read_b128 %2, %5 offset:%6\n\tds_read_b128 %3, %5 offset:%7"       \
-                 : "=&v"(X0), "=&v"(X1), "=&v"(MA), "=&v"(MB) : "v"(vcol), "v"(vmul), "n"(OFF), "n"((OFF) + 512) : "memory");                                \
-         asm volatile("" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7])); } while (0)
-#define BNR_PIPE_WAIT4(X0, X1, MA, MB) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(X0), "+v"(X1), "+v"(MA), "+v"(MB), "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]) :: "memory")
-#define BNR_PIPE_READ6(M, OFF)                                                                                                                               \
-    asm volatile("ds_read_b128 %0, %6 offset:%7\n\tds_read_b128 %1, %6 offset:%8\n\tds_read_b128 %2, %6 offset:%9\n\t"                                       \
-                 "ds_read_b128 %3, %6 offset:%10\n\tds_read_b128 %4, %6 offset:%11\n\tds_read_b128 %5, %6 offset:%12"                                        \
-                 : "=&v"(M[1]), "=&v"(M[2]), "=&v"(M[3]), "=&v"(M[5]), "=&v"(M[6]), "=&v"(M[7])                                                              \
-                 : "v"(vmul), "n"((OFF) + 16), "n"((OFF) + 32), "n"((OFF) + 48), "n"((OFF) + 528), "n"((OFF) + 544), "n"((OFF) + 560) : "memory")
-#define BNR_PIPE_WAIT6(M) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(M[1]), "+v"(M[2]), "+v"(M[3]), "+v"(M[5]), "+v"(M[6]), "+v"(M[7]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]) :: "memory")
-    if (W > 0) {
-        // C0 / 2 trips: all but the last through the rolled two-trip loop (an even number of them) and, when their number is odd, one trip more in front of the last
-        constexpr int NT = C0 / 2, NLOOP = ((NT - 1) / 2) * 2;          // NT = 4, 8, 12: NLOOP = 2, 6, 10, then one plain trip, then the hand-over trip
-        BNR_PIPE_READ10(c0, c1, m, 0);
-#pragma unroll 1
-        for (int j = 0; j < 2 * NLOOP; j += 4) {
-            BNR_PIPE_TRIP(c0, c1, m, 0, n0, n1, mn, true);
-            BNR_PIPE_TRIP(n0, n1, mn, 1024, c0, c1, m, true);
-            vcol += 2048; vmul += 2048;
-        }
-        // trip NT - 2 (its pair is in flight in the first register set); the hand-over pair's four reads go out under its multiply-adds
-        BNR_PIPE_WAIT10(c0, c1, m);
-        if (!BNR_PIPE_HERE(c0, c1)) {
-            int spins = 0;
-            do {
-                if (++spins > BNR_PIPE_SPINS) { bad = 1; break; }
-                BNR_PIPE_POLL1(c1, 0);
-            } while (!__all(__double2hiint(c1) != BNR_PIPE_SENT_HI));
-            BNR_PIPE_READ10(c0, c1, m, 0);
-            BNR_PIPE_WAIT10(c0, c1, m);
-        }
-        BNR_PIPE_READ4(n0, n1, mn[0], mn[4], 1024);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) a[c] = fma(-c0, m[c >> 1][c & 1], a[c]);
-#pragma unroll
-        for (int c = 0; c < 8; ++c) a[c] = fma(-c1, m[4 + (c >> 1)][c & 1], a[c]);
-        // the hand-over trip
-        BNR_PIPE_WAIT4(n0, n1, mn[0], mn[4]);
-        if (!BNR_PIPE_HERE(n0, n1)) {
-            int spins = 0;
-            do {
-                if (++spins > BNR_PIPE_SPINS) { bad = 1; break; }
-                BNR_PIPE_READ4(n0, n1, mn[0], mn[4], 1024);
-                BNR_PIPE_WAIT4(n0, n1, mn[0], mn[4]);
-            } while (!BNR_PIPE_HERE(n0, n1));
-        }
-        BNR_PIPE_READ6(mn, 1024);
-        a[0] = fma(-n0, mn[0][0], a[0]); a[1] = fma(-n0, mn[0][1], a[1]);
-        a[0] = fma(-n1, mn[4][0], a[0]); a[1] = fma(-n1, mn[4][1], a[1]);
-        BNR_PIPE_WAIT6(mn);
-#pragma unroll
-        for (int c = 2; c < 8; ++c) a[c] = fma(-n0, mn[c >> 1][c & 1], a[c]);
-#pragma unroll
-        for (int c = 2; c < 8; ++c) a[c] = fma(-n1, mn[4 + (c >> 1)][c & 1], a[c]);
-    }
-#else
-    if (W > 0) {
-        BNR_PIPE_READ10(c0, c1, m, 0);
-#pragma unroll 1
-        for (int j = 0; j < C0; j += 4) {                   // two trips per turn: the two register sets take turns without copies (C0 is a multiple of 8)
-            BNR_PIPE_TRIP(c0, c1, m, 0, n0, n1, mn, true);
-            BNR_PIPE_TRIP(n0, n1, mn, 1024, c0, c1, m, j + 4 < C0);
-            vcol += 2048; vmul += 2048;
-        }
-    }
-#endif
-#ifdef BNR_LAB_STAMPS          // (tools/pipe_lab.hip: when this wave's own pivots start and end, two stamps per wave)
-    if (lane == 0) bnr_lab_stamp[2 * W] = __builtin_amdgcn_s_memtime();
-#endif
     if (W == 1) BNR_PPH(3);
     if (W == 3) BNR_PPH(6);
-#if BNR_PIPE_DPP
-    bad |= bnr_sweepN<8, C0, (W < 3 ? 2 : 0)>(a, lane, bnr_lds_addr(&sh.sL[C0][lane]), nullptr, [&]() { BNR_DPP_PENDING(); });
-#elif defined(BNR_STAMPS_FINE)
-    bad |= bnr_sweepN<8, C0, (W < 3 ? 2 : 0)>(a, lane, bnr_lds_addr(&sh.sL[C0][lane]), &sh.st[W][12]);
-#else
-    bad |= bnr_sweepN<8, C0, (W < 3 ? 2 : 0)>(a, lane, bnr_lds_addr(&sh.sL[C0][lane]));
-#endif
-#ifdef BNR_STAMPS_FINE
-    if (ph && lane == 0) { sh.st[W][20] = (unsigned long long)npoll; for (int i = 0; i < 24; ++i) ph[1024 + 24 * W + i] = sh.st[W][i]; }
-#endif
-    (void)ntrip; (void)npoll;
-#ifdef BNR_LAB_STAMPS
-    if (lane == 0) bnr_lab_stamp[2 * W + 1] = __builtin_amdgcn_s_memtime();
-#endif
+    bad |= bnr_sweepN<8, C0, (W < 3 ? 2 : 0)>(a, lane, bnr_lds_addr(&sh.sL[C0][lane]), [&]() { if (W > 0) BNR_DPP_APPLY(2, y0, y1, q0, q1); });
     if (W == 0) BNR_PPH(2);
     if (W == 1) BNR_PPH(4);
     if (W == 2) BNR_PPH(5);
@@ -1831,8 +1493,10 @@ __device__ __forceinline__ int bnr_pipe_wave(bnr_panelp_lds &sh, int lane, doubl
     }
     return bad;
 }
-// same contract as bnr_panel_sweep (D, B as the MFMA accumulator fragments of the four waves; the swept own block goes to dst); returns 1 in the waves that met
-// a non-positive pivot (any wave may)
+// Sweep of the 64 x 32 panel [D ; B] by one workgroup of 256 threads: D = updated, unfactored diagonal block, B = own block, both handed over as the MFMA
+// accumulator fragments (mt, nt) of the four waves.  The swept own block B L_D^-T goes to dst (E, leading dimension ld) straight from the sweeping waves' registers
+// (lane = row: coalesced 256-byte stores); the factored diagonal block is not produced -- nobody needs it later.  Returns 1 in the waves that met a non-positive
+// pivot (any wave may)
 __device__ __forceinline__ int bnr_panel_sweep_pipe(bnr_panelp_lds &sh, const bnr_d4 &cD, const bnr_d4 &cB, int tid, double *dst, size_t ld, unsigned long long *ph = nullptr)
 {
     const int wave = tid >> 6, lane = tid & 63, mt = wave >> 1, nt = wave & 1, ln = lane & 15, lq = lane >> 4;
@@ -1856,9 +1520,6 @@ __device__ __forceinline__ int bnr_panel_sweep_pipe(bnr_panelp_lds &sh, const bn
 #ifdef BNR_STAMPS
     if (ph && tid == 0) ph[1] = __builtin_amdgcn_s_memtime();
 #endif
-#ifdef BNR_LAB_W0_ONLY       // (tools/pipe_lab.hip, timing only: what the first wave's eight pivots cost with nobody reading beside it)
-    if (wave != 0) return 0;
-#endif
     if (wave == 0) return bnr_pipe_wave<0>(sh, lane, dst, ld, ph);
     if (wave == 1) return bnr_pipe_wave<1>(sh, lane, dst, ld, ph);
     if (wave == 2) return bnr_pipe_wave<2>(sh, lane, dst, ld, ph);
@@ -1869,15 +1530,9 @@ __device__ __forceinline__ int bnr_panel_sweep_pipe(bnr_panelp_lds &sh, const bn
 // element in k_gram_reduce's order (ks ascending from 0.0, then + 1 on the diagonal).  The loop runs over the K slices with
 // all elements of a lane in flight per slice (the partial tiles come from HBM: one element at a time would cost ksplit x 16
 // dependent round trips).
-// fresh: the partial tiles were written while this kernel was already running (factorization beside the Gram), possibly through
-// another XCD's L2: read them past the own L2 (sc1 loads) -- an acquire fence instead would invalidate the whole L2 of this XCD,
-// once per wave, under everybody who works from it (measured: +30 us on every gated launch).
-__device__ __forceinline__ double bnr_ld_fresh(const double *p, bool fresh)
-{
-    return fresh ? __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : *p;
-}
-template <int NT, int KUSEL = 0>
-__device__ __forceinline__ void bnr_gsum_frag(const bnr_dev &cd, int rho, int c, int at0, int bt0, int ln, int lq, bnr_d4 (&out)[NT][NT], bool fresh)
+// (both callers pass NT = 1; written out for one tile the same sums compile to other instructions in k_chol_step, profiles/kernel_variants_cleanup.txt)
+template <int NT>
+__device__ __forceinline__ void bnr_gsum_frag(const bnr_dev &cd, int rho, int c, int at0, int bt0, int ln, int lq, bnr_d4 (&out)[NT][NT])
 {
     const int ti = rho >> 1, tj = c >> 1, ntl = cd.ntile * (cd.ntile + 1) / 2;
     const size_t tsz = BNR_GT * BNR_GT, plane = (size_t)ntl * tsz;
@@ -1888,7 +1543,7 @@ __device__ __forceinline__ void bnr_gsum_frag(const bnr_dev &cd, int rho, int c,
         for (int bt = 0; bt < NT; ++bt) out[at][bt] = bnr_d4{0.0, 0.0, 0.0, 0.0};
     // KU slices per round, all in flight; a slice past the last one is read again from the last plane and enters as + 0.0, which
     // changes nothing (the running sum is never -0.0)
-    constexpr int KU = KUSEL ? KUSEL : (NT == 1 ? 8 : 4);   // (KUSEL: fewer slices in flight where registers are short: the same sums, slice by slice)
+    constexpr int KU = NT == 1 ? 8 : 4;
     const int klast = cd.ksplit - 1;
     for (int ks0 = 0; ks0 < cd.ksplit; ks0 += KU) {
         bnr_d4 v[KU][NT][NT];
@@ -1900,18 +1555,16 @@ __device__ __forceinline__ void bnr_gsum_frag(const bnr_dev &cd, int rho, int c,
 #pragma unroll
                 for (int bt = 0; bt < NT; ++bt)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) v[u][at][bt][r] = bnr_ld_fresh(src + po + (size_t)(16 * at + 4 * r) * BNR_GT + 16 * bt, fresh);
+                    for (int r = 0; r < 4; ++r) v[u][at][bt][r] = *(src + po + (size_t)(16 * at + 4 * r) * BNR_GT + 16 * bt);
         }
 #pragma unroll
         for (int u = 0; u < KU; ++u) {
-            const double keep = (ks0 + u <= klast) ? 1.0 : 0.0;
 #pragma unroll
             for (int at = 0; at < NT; ++at)
 #pragma unroll
                 for (int bt = 0; bt < NT; ++bt)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) out[at][bt][r] += (ks0 + u <= klast) ? v[u][at][bt][r] : 0.0;
-            (void)keep;
         }
     }
     if (rho == c) {
@@ -1965,15 +1618,9 @@ __global__ __launch_bounds__(256, 1) void k_chol_step(const SRC chain_src, int p
     const unsigned long long t_entry = __builtin_amdgcn_s_memtime();       // before anything is read, the kernel's arguments included
 #endif
     const bnr_dev &cd = chain_src.get_x();               // grid = (chains, workgroups): blockIdx.x = chain, blockIdx.y = workgroup
-#if BNR_PANEL_PIPE
     __shared__ bnr_panelp_lds sh;
-#else
-    __shared__ bnr_panel_lds sh;
-#endif
-#if BNR_PANEL_COOP_FETCH
-    static_assert(BNR_PANEL_PIPE && sizeof(sh.sL) == 2 * BNR_NB * BNR_NB * sizeof(double), "the two fetched blocks of panel p - 1 live where the sweep's published columns will be");
+    static_assert(sizeof(sh.sL) == 2 * BNR_NB * BNR_NB * sizeof(double), "the two fetched blocks of panel p - 1 live where the sweep's published columns will be");
     double (*sPO)[BNR_NB * BNR_NB] = (double (*)[BNR_NB * BNR_NB])&sh.sL[0][0];   // (no LDS of their own: the update workgroups of the launch carry the same static allocation)
-#endif
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nbk = cd.n_pad / BNR_NB;
     const size_t ld = bnr_ldE(cd.n_pad);
     const int npanel = bnr_chol_npanel(nbk, p);
@@ -2106,9 +1753,9 @@ __global__ __launch_bounds__(256, 1) void k_chol_step(const SRC chain_src, int p
     if (p == 0 && fuse0) {
         // first touch of column block 0: the K-slice partials summed here (k_gram_reduce's order), the identity block row generated
         bnr_d4 t1[1][1];
-        bnr_gsum_frag<1>(cd, 0, 0, mt, nt, ln, lq, t1, false);
+        bnr_gsum_frag<1>(cd, 0, 0, mt, nt, ln, lq, t1);
         cD = t1[0][0];
-        if (rho < nbk) { bnr_gsum_frag<1>(cd, rho, 0, mt, nt, ln, lq, t1, false); cB = t1[0][0]; }
+        if (rho < nbk) { bnr_gsum_frag<1>(cd, rho, 0, mt, nt, ln, lq, t1); cB = t1[0][0]; }
         else {
 #pragma unroll
             for (int r = 0; r < 4; ++r) cB[r] = (nt * 16 + ln == mt * 16 + lq + 4 * r) ? 1.0 : 0.0;
@@ -2121,7 +1768,6 @@ __global__ __launch_bounds__(256, 1) void k_chol_step(const SRC chain_src, int p
 #ifdef BNR_STAMPS           // (wave 0 of panel workgroup 0: entry of the kernel | its loads are back | its MFMAs are done -- words 3800 + 4 p of the debug buffer, tools/stamps_steps.py)
         if (b == 0 && tid == 0 && p < 24) cd.dbg[3800 + 4 * p] = t_entry;
 #endif
-#if BNR_PANEL_COOP_FETCH
         if (p > 0) {
             // The K = 32 update of both blocks with panel p - 1: the two 32 x 32 blocks of that panel it needs -- P = L[p, p-1] and O = L[own, p-1] -- are fetched ONCE per
             // workgroup, 16 bytes per lane and whole columns per quarter wave, into LDS; the MFMA fragments come from there.  (Fragments straight from memory: every wave
@@ -2154,33 +1800,17 @@ __global__ __launch_bounds__(256, 1) void k_chol_step(const SRC chain_src, int p
             { double chk = cD[3] + cB[3]; asm volatile("" :: "v"(chk)); if (b == 0 && tid == 0 && p < 24) cd.dbg[3800 + 4 * p + 2] = __builtin_amdgcn_s_memtime(); }
 #endif
         }
-#else
-        if (p > 0) {
-            const double *colrows = E + (size_t)(pc + mt * 16) + ld * (size_t)kc;
-            cD = bnr_tile_update(colrows, E + (size_t)(pc + nt * 16) + ld * (size_t)kc, ld, lane, cD);
-            cB = bnr_tile_update(colrows, E + (size_t)(rho * BNR_NB + nt * 16) + ld * (size_t)kc, ld, lane, cB);
-        }
-#endif
     }
     BNR_STAMP(2);
     // (the factored diagonal block L_pp is needed by nobody after this launch and is NOT written back: every panel workgroup of
     // this launch reads the unfactored block (p,p) whenever it happens to start)
     double *dst = rho != p ? E + (size_t)(rho * BNR_NB) + ld * (size_t)pc : nullptr;
-#if BNR_PANEL_PIPE
 #ifdef BNR_STAMPS
     const int bad = bnr_panel_sweep_pipe(sh, cD, cB, tid, dst, ld, b == 0 ? cd.dbg + 128 + p * 8 : nullptr);
 #else
     const int bad = bnr_panel_sweep_pipe(sh, cD, cB, tid, dst, ld);
 #endif
     if (bad && lane == 0) bnr_flag_gfail(cd);
-#else
-#ifdef BNR_STAMPS
-    const int bad = bnr_panel_sweep(sh, cD, cB, tid, dst, ld, b == 0 ? cd.dbg + 128 + p * 8 : nullptr);
-#else
-    const int bad = bnr_panel_sweep(sh, cD, cB, tid, dst, ld);
-#endif
-    if (bad && tid == 0) bnr_flag_gfail(cd);
-#endif
     BNR_STAMP(3);
     BNR_STAMP(4);
 #ifdef BNR_STAMPS

@@ -413,6 +413,22 @@ def test_late_kernels_sit_behind_the_sweep_kernels_in_the_code_object(tmp_path):
     assert min(late.values()) > max(sweep.values()), (sorted(late.items(), key=lambda kv: kv[1])[:2], sorted(sweep.items(), key=lambda kv: -kv[1])[:2])
 
 
+def test_pipe_lab_compiles_against_the_kernel_header(tmp_path):
+    """tools/pipe_lab.hip times and host-checks bnr_panel_sweep_pipe straight out of csrc/bnr_kernels.h, so every change of that header can break it -- and did,
+    unnoticed for three commits, when k_wsummary began to need bnr_internal.h in front of the header.  Device code only, for gfx950, with the flags of the build line
+    in the tool's own header comment: nothing runs, no GPU needed."""
+    hipcc = "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        pytest.skip("no hipcc here")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    obj = str(tmp_path / "pipe_lab.o")
+    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(root, "bayesiannetworkregression.jl_amd", "csrc"),
+           "--cuda-device-only", "-c", "-o", obj, os.path.join(root, "tools", "pipe_lab.hip")]
+    done = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert done.returncode == 0, done.stdout[-4000:]
+    assert os.path.getsize(obj) > 0
+
+
 def test_gram_k_split_keeps_every_k_group_inside_the_buffer_window():
     """the Gram loops address X through a 2 GiB buffer resource with 32-bit scalar offsets (csrc/bnr_kernels.h, bnr_gram16_task /
     bnr_gram8_task; reference product gibbs.jl:434).  The K split must be raised until one K-group's slice + prefetch distance fits that window --

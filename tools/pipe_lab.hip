@@ -1,24 +1,21 @@
-// Stand-alone timing + check of the panel sweep of the factorization (csrc/bnr_kernels.h: bnr_panel_sweep_pipe, bnr_panel_sweep): ONE workgroup alone on the chip sweeps a random
+// Stand-alone timing + check of the panel sweep of the factorization (csrc/bnr_kernels.h: bnr_panel_sweep_pipe): ONE workgroup alone on the chip sweeps a random
 // 64 x 32 panel [D ; B] (D SPD) `reps` times; cycles from the function's entry to the LAST wave's end (s_memtime), result checked against a host Cholesky.
-//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form [-DBNR_PANEL_PIPE=0 | -D<variant switches>] -I bayesiannetworkregression.jl_amd/csrc -o tools/bin/pipe_lab tools/pipe_lab.hip
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -mllvm -amdgpu-mfma-vgpr-form [-DBNR_LAB_COLD_ICACHE] -I bayesiannetworkregression.jl_amd/csrc -o tools/bin/pipe_lab tools/pipe_lab.hip
+// (the variants of the sweep that this tool once timed through -DBNR_PIPE_* / -DBNR_LAB_* are gone from the header: profiles/round6_experiments_notes.txt keeps what they measured)
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cmath>
 #include <vector>
 #include <random>
+#include "bnr_internal.h"        // (bnr_kernels.h is written to follow it: k_wsummary takes its limits from there)
 #include "bnr_kernels.h"
-#if BNR_PANEL_PIPE
-typedef bnr_panelp_lds bnr_step_lds;
-#else
-typedef bnr_panel_lds bnr_step_lds;
-#endif
 __global__ __launch_bounds__(256, 1) void k_lab(const double *D, const double *B, double *out, unsigned long long *cyc, int reps)
 {
-    __shared__ bnr_step_lds sh;
+    __shared__ bnr_panelp_lds sh;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, mt = wave >> 1, nt = wave & 1, ln = lane & 15, lq = lane >> 4;
     bnr_d4 cD, cB;
     for (int r = 0; r < 4; ++r) { cD[r] = D[(nt * 16 + ln) + 32 * (mt * 16 + lq + 4 * r)]; cB[r] = B[(nt * 16 + ln) + 32 * (mt * 16 + lq + 4 * r)]; }
-    unsigned long long tot = 0, worst = 0, totw[4] = {0, 0, 0, 0}, tots[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    unsigned long long tot = 0, worst = 0, totw[4] = {0, 0, 0, 0};
     __shared__ unsigned long long s_end, s_endw[4];
     for (int rep = 0; rep < reps; ++rep) {
         if (tid == 0) s_end = 0;
@@ -27,22 +24,14 @@ __global__ __launch_bounds__(256, 1) void k_lab(const double *D, const double *B
 #endif
         __syncthreads();
         const unsigned long long t0 = __builtin_amdgcn_s_memtime();
-#if BNR_PANEL_PIPE
         int bad = bnr_panel_sweep_pipe(sh, cD, cB, tid, out, 32);
-#else
-        int bad = bnr_panel_sweep(sh, cD, cB, tid, out, 32);
-#endif
         const unsigned long long t1 = __builtin_amdgcn_s_memtime();
         if (lane == 0) { atomicMax(&s_end, t1 - t0); s_endw[wave] = t1 - t0; }
         __syncthreads();
-        if (tid == 0) { tot += s_end; worst = s_end > worst ? s_end : worst; if (bad) cyc[3] = 1; for (int w = 0; w < 4; ++w) totw[w] += s_endw[w];
-#ifdef BNR_LAB_STAMPS
-            for (int i = 0; i < 8; ++i) tots[i] += bnr_lab_stamp[i] - t0;
-#endif
-        }
+        if (tid == 0) { tot += s_end; worst = s_end > worst ? s_end : worst; if (bad) cyc[3] = 1; for (int w = 0; w < 4; ++w) totw[w] += s_endw[w]; }
         __syncthreads();
     }
-    if (tid == 0) { cyc[0] = tot / reps; cyc[1] = worst; for (int w = 0; w < 4; ++w) cyc[4 + w] = totw[w] / reps; for (int i = 0; i < 8; ++i) cyc[8 + i] = tots[i] / reps; }
+    if (tid == 0) { cyc[0] = tot / reps; cyc[1] = worst; for (int w = 0; w < 4; ++w) cyc[4 + w] = totw[w] / reps; }
 }
 int main()
 {
@@ -74,11 +63,8 @@ int main()
             unsigned long long h2[16]; hipMemcpy(h2, dC, 128, hipMemcpyDeviceToHost);
             if (it >= 8) for (int i = 0; i < 16; ++i) acc[i] += h2[i];
         }
-        printf("one sweep per launch, %2d workgroup(s) (the last one to write its stamps is reported): %llu cycles; waves 0..3 end at %llu %llu %llu %llu; own pivots %llu..%llu  %llu..%llu  %llu..%llu  %llu..%llu\n", wgs, acc[0] / 32, acc[4] / 32, acc[5] / 32,
-               acc[6] / 32, acc[7] / 32, acc[8] / 32, acc[9] / 32, acc[10] / 32, acc[11] / 32, acc[12] / 32, acc[13] / 32, acc[14] / 32, acc[15] / 32);
+        printf("one sweep per launch, %2d workgroup(s) (the last one to write its stamps is reported): %llu cycles; waves 0..3 end at %llu %llu %llu %llu\n", wgs, acc[0] / 32, acc[4] / 32, acc[5] / 32,
+               acc[6] / 32, acc[7] / 32);
     }
-#ifdef BNR_LAB_STAMPS
-    printf("  own pivots of waves 0..3 start..end: %llu..%llu  %llu..%llu  %llu..%llu  %llu..%llu\n", hC[8], hC[9], hC[10], hC[11], hC[12], hC[13], hC[14], hC[15]);
-#endif
     return err < 1e-9 ? 0 : 1;
 }

@@ -1,5 +1,6 @@
-"""Diagnostic (-DBNR_STAMPS build): phases inside bnr_panel_sweep of panel workgroup 0 (shader cycles): stage-in + barrier | first-half loads |
-first 16-column sweep | publish + barrier | MFMA mid update + barrier | second-half loads | second sweep | (hand-back + barrier = rest)."""
+"""Diagnostic (-DBNR_STAMPS build): phases inside the one-wave panel sweep of rounds 1-5 in panel workgroup 0 (shader cycles): stage-in + barrier | first-half loads |
+first 16-column sweep | publish + barrier | MFMA mid update + barrier | second-half loads | second sweep | (hand-back + barrier = rest).
+That sweep is no longer in csrc/bnr_kernels.h; the four-wave pipeline writes the same eight words with its own phases, which stamps_pipe.py reads."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, bnr_amd
