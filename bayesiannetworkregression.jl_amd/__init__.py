@@ -9,5 +9,6 @@ from .api import (BNRPrediction, BNRSummary, ChainSet, Fit, LOO, LOOPredict, LOO
                   generate_samples_dbl, initialize_and_run, lower_triangle, return_psrf_VOI, run, setup_X,
                   allgather_stats, local_chain_ids, make_comm, shared_seed, RankDiagnose, RankDiagnostics, device_rank_diagnostics, rank_normalize,
                   EdgeSelect, EdgeSelection, device_edge_selection, hdi, NodeSets, device_node_sets, inclusion,
-                  Stacking, ChainStacking, stacking_weights, wquantile, device_stack_chains, device_summary_stacked, device_predict_stacked)
+                  Stacking, ChainStacking, stacking_weights, wquantile, device_stack_chains, device_summary_stacked, device_predict_stacked,
+                  EdgeCov, cov, device_edge_cov)
 from .synthetic import make_synthetic                             # noqa: F401

@@ -103,6 +103,9 @@ _SIGS = {
     "bnr_chains_wpredict": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, C.c_int32]
                             + [_dp] * 4 + [C.c_uint64] + [_dp] * 2),
     "bnr_wquantile": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, _dp]),
+    "bnr_chain_cov": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
+    "bnr_chains_cov": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
+    "bnr_cov": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
     "bnr_comm_unique_id": (C.c_int, [C.POINTER(UniqueId)]),
     "bnr_comm_create_rccl": (C.c_int, [C.POINTER(UniqueId), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "bnr_comm_create_callback": (C.c_int, [C.c_int32, C.c_int32, ALLGATHER_CB, C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -523,6 +526,29 @@ def _inclusion(fn, head, c0, first_row, nsamp, which, ntop, fields):
     return _incl_result(out)
 
 
+def cov_cols(cols, q):
+    """the column list of a covariance call over q edges as int32, or None for every edge; ValueError (before any library call) for an empty
+    list, a value that is no integer, or an index outside 0 .. q - 1"""
+    if cols is None:
+        return None
+    a = np.asarray(cols)
+    if a.ndim != 1 or a.size < 1 or a.dtype == np.bool_ or not (np.issubdtype(a.dtype, np.integer) or np.all(a == np.floor(a))):
+        raise ValueError("cols must be a non-empty list of 0-based edge indices")
+    a = a.astype(np.int64)
+    if a.min() < 0 or a.max() >= q:
+        raise ValueError("edge indices must lie in 0 .. %d" % (q - 1))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _cov(fn, head, c0, first_row, nsamp, cols):
+    """(mean (ncols,), cov (ncols, ncols)) of the chosen gamma columns; head carries the weights (or None) of the pooled form behind the handles"""
+    ci = cov_cols(cols, c0.q)
+    m = c0.q if ci is None else ci.size
+    mean, cov = np.empty(m), np.empty((m, m))
+    check(getattr(c0.L, fn)(*head, int(first_row), int(nsamp), m, _ptr(ci), _ptr(mean), _ptr(cov)))
+    return mean, cov
+
+
 class Chain:
     """One Gibbs chain resident on one GPU (handle of include/bnr_hip.h).  xi_weights: "log" (default) or "reference" (model
     option "xi_weights": the reference's node weights with their under/overflow, see include/bnr_hip.h)."""
@@ -691,6 +717,11 @@ class Chain:
         node indicators xi (which = 0) or of the R dimensions lambda != 0 (which = 1), see inclusion_raw; an entry not named in `fields` is
         not requested and comes back as None"""
         return _inclusion("bnr_chain_inclusion", (self.h,), self, first_row, nsamp, which, ntop, fields)
+
+    def cov(self, first_row, nsamp, cols=None):
+        """(mean, cov) of this chain's edge coefficients over its window, on the device (bnr_chain_cov): the columns `cols` (0-based edge
+        indices; None: all q), cov = numpy's cov of the draws about the Summary mean"""
+        return _cov("bnr_chain_cov", (self.h,), self, first_row, nsamp, cols)
 
     def counters(self):
         out = (C.c_int64 * 8)()
@@ -920,6 +951,27 @@ def stacked_predict(chains, weights, X, first_row, nsamp, k_lo, k_hi, y=None, x_
     w = stack_weights_array(weights, head[1])
     r = _predict("stacked", "bnr_chains_wpredict", None, head + (_ptr(w),), c0, X, first_row, nsamp, k_lo, k_hi, y, x_transform, pred_seed)
     return r[:4] + r[5:7]
+
+
+# ------------------------------------------------------------------------------------------ posterior covariance of the edge coefficients (ABI 17)
+def pooled_cov(chains, first_row, nsamp, cols=None, weights=None):
+    """Chain.cov over the pooled window of `chains` (bnr_chains_cov); with weights the covariance of the chains' mixture under them"""
+    c0, head = _pooled(chains)
+    w = None if weights is None else stack_weights_array(weights, head[1])
+    return _cov("bnr_chains_cov", head + (_ptr(w),), c0, first_row, nsamp, cols)
+
+
+def cov_raw(x, nchains=1, weights=None, device=0):
+    """(mean (m,), cov (m, m)) of a (nchains nsamp) x m matrix of draws (rows = draws, chain k's in rows k nsamp ..), on the device (bnr_cov)"""
+    a = np.ascontiguousarray(x, dtype=np.float64)
+    K = int(nchains)
+    if a.ndim != 2 or K < 1 or a.shape[1] < 1 or a.shape[0] < max(K, 2) or a.shape[0] % K:
+        raise ValueError("x must be a (nchains * nsamp) x m matrix (draws x columns) with at least 2 draws and m >= 1")
+    w = None if weights is None else stack_weights_array(weights, K)
+    S, m = a.shape
+    mean, cov = np.empty(m), np.empty((m, m))
+    check(_device_lib().bnr_cov(int(device), K, S // K, m, _ptr(a), _ptr(w), _ptr(mean), _ptr(cov)))
+    return mean, cov
 
 
 class Comm:

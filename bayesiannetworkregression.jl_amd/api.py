@@ -26,6 +26,7 @@ Julia is not available in this image, so the thin host layer a Julia user would 
                                                _host_node_sets, _host_inclusion
                                                chain stacking for chains that do not mix: Stacking / ChainStacking, stacking_weights,
                                                wquantile, device_stack_chains, device_summary_stacked, device_predict_stacked, _host_*
+                                               posterior covariance of the edge coefficients: EdgeCov, cov, device_edge_cov, _host_edge_cov
   lower_triangle / create_lower_tri / setup_X!  utils.jl:17-57, gibbs.jl:239-247
 
 All sampling runs on the GPU through libbnr_hip.so; this file holds only the schedule logic (chain fan-out,
@@ -107,6 +108,7 @@ class Results:
     edge_selection: "EdgeSelection" = None   # filled on request (edge_selection=True): HDIs, sign probabilities and the selected edges over every chain (see EdgeSelect)
     node_sets: "NodeSets" = None     # filled on request (node_sets=True): co-inclusion, model size, the most probable node sets and the active dimensions over every chain (see NodeSets)
     stacking: "ChainStacking" = None   # filled on request (stack_chains=True): every chain's own PSIS-LOO, the stacking weights of the chains and the summaries under them (see Stacking)
+    edge_cov: "EdgeCov" = None       # filled on request (edge_cov=...): the posterior covariance matrix of the edge coefficients over every chain (see EdgeCov)
     stat_chains: int = None          # how many chains the device statistics above (summary_device, prediction, waic, loo, loo_predictive) cover: 1 (chain 1's window), or
                                      # every chain of the fit with pool_chains=True; None when the fit computed none
 
@@ -1242,6 +1244,7 @@ class ChainStacking:
     draws: int = None
     summary: dict = None
     prediction: BNRPrediction = None
+    edge_cov: "EdgeCov" = None       # the posterior covariance of the edge coefficients under the weights (Fit(..., edge_cov=..., stack_chains=True))
 
 
 def _stack_solver_args(max_iter, gap_tol):
@@ -1527,6 +1530,192 @@ def Stacking(results, X=None, y=None, x_transform=True, tables=None, r_eff=None)
     return _host_stack_chains(tables, X, y, results.burn_in, results.sampled, x_transform, r_eff)
 
 
+# ------------------------------------------------------------------------------------------ posterior covariance of the edge coefficients (ABI 17)
+# vcov(fit): how the edge coefficients move together, over the pooled window of the chains of one device (include/bnr_hip.h, bnr_chains_cov).
+# With c the mean Summary reports for a column -- under chain weights the stacked Summary's -- and G_k[a, b] = sum over chain k's window of
+# (x_sa - c_a)(x_sb - c_b), cov = sum_k G_k / (S - 1) (numpy's cov), or sum_k w_k G_k / nsamp under weights (the covariance of the mixture of
+# the chains' empirical measures); k ascending from 0.0.
+_EDGE_COV_FIELDS = ("cols", "node1", "node2", "mean", "cov", "chains", "draws", "weights")
+
+
+class EdgeCov:
+    """The posterior covariance of edge coefficients.  cols: the 0-based edge indices covered (Summary's order), node1 / node2: their 1-based
+    nodes; mean (m,): the posterior means (Summary's, or the stacked Summary's under weights); cov (m, m): the covariance matrix; chains, draws:
+    what was pooled; weights: the chain weights, or None.  Derived on the host: sd, corr (NaN where an sd is 0), contrast(C) -- the mean and sd
+    of the linear combinations C gamma --, top_pairs(n) -- the most correlated pairs.
+
+    EdgeCov(results) is the accessor of a fit: the GPU's numbers when the fit carried them (edge_cov=...: every chain of the fit), otherwise
+    restated on the host over results.state (needs return_state=True; chain 1 alone, every edge).  Without a Results, EdgeCov(**fields) builds
+    the record itself from exactly the fields above."""
+
+    def __new__(cls, results=None, **fields):
+        if results is not None:
+            return _edge_cov_of(results)
+        return object.__new__(cls)
+
+    def __init__(self, results=None, **fields):
+        if results is not None:                                          # (the accessor: __new__ returned a finished object)
+            return
+        if set(fields) != set(_EDGE_COV_FIELDS):
+            raise TypeError("EdgeCov takes a Results, or exactly the fields %r" % (_EDGE_COV_FIELDS,))
+        self.__dict__.update(fields)
+
+    def __repr__(self):
+        return "EdgeCov(edges=%d, chains=%d, draws=%d%s)" % (self.cols.size, self.chains, self.draws, "" if self.weights is None else ", weighted")
+
+    @property
+    def sd(self):
+        """the posterior standard deviations, sqrt(diag(cov))"""
+        return np.sqrt(np.diag(self.cov))
+
+    @property
+    def corr(self):
+        """the correlation matrix cov / (sd sd'); NaN in the row and column of an edge whose sd is 0"""
+        sd = self.sd
+        with np.errstate(all="ignore"):
+            r = self.cov / np.outer(sd, sd)
+        zero = sd == 0
+        r[zero, :] = np.nan
+        r[:, zero] = np.nan
+        return r
+
+    def contrast(self, C):
+        """dict(mean, sd) of the linear combinations C gamma of the covered edges: C is (r, m) or (m,), a row per combination -- a node's total
+        effect, a pathway, a difference of two edges.  mean = C mean, sd = sqrt(diag(C cov C'))"""
+        C = np.atleast_2d(np.asarray(C, dtype=np.float64))
+        if C.shape[1] != self.cols.size:
+            raise ValueError("C must have one column per covered edge (%d), not %d" % (self.cols.size, C.shape[1]))
+        with np.errstate(invalid="ignore"):
+            return dict(mean=C @ self.mean, sd=np.sqrt(np.einsum("ia,ab,ib->i", C, self.cov, C)))
+
+    def top_pairs(self, n=10):
+        """the n pairs (a, b, corr), a < b positions in cols, of largest |corr|, ties by (a, b) ascending; pairs whose corr is NaN are left out"""
+        r = self.corr
+        a, b = np.triu_indices(r.shape[0], 1)
+        v = r[a, b]
+        keep = np.flatnonzero(~np.isnan(v))
+        order = keep[np.argsort(-np.abs(v[keep]), kind="stable")][:max(int(n), 0)]
+        return [(int(a[i]), int(b[i]), float(v[i])) for i in order]
+
+
+def _edge_nodes(V, cols):
+    """(node1, node2), 1-based, of the 0-based edge indices cols in Summary's order (node1 <= node2; utils.jl:40-57)"""
+    node1 = np.concatenate([np.full(V - k + 1, k) for k in range(1, V + 1)])
+    node2 = np.concatenate([np.arange(k, V + 1) for k in range(1, V + 1)])
+    return node1[cols], node2[cols]
+
+
+def _edge_cov_cols(edge_cov, V=None):
+    """The edge_cov keyword of a fit as _finish takes it: None (off: False or None), "all" (True), or the 0-based edge indices as int32 -- from
+    an array of indices, or from a list of 1-based (node1, node2) pairs through the edge index.  ValueError for anything else, for an empty list
+    and (where V is known) for an index or a node out of range."""
+    if edge_cov is None or edge_cov is False:
+        return None
+    if edge_cov is True:
+        return "all"
+    if isinstance(edge_cov, (str, bytes, dict)) or np.isscalar(edge_cov):
+        raise ValueError("edge_cov must be True, an array of 0-based edge indices or a list of (node1, node2) pairs, not %r" % (edge_cov,))
+    try:
+        a = np.asarray(edge_cov)
+    except Exception:
+        a = np.empty(0, dtype=object)
+    if a.dtype == object or a.dtype == np.bool_ or a.size < 1 or a.ndim not in (1, 2) or (a.ndim == 2 and a.shape[1] != 2) or not np.all(a == np.floor(a)):
+        raise ValueError("edge_cov must be True, an array of 0-based edge indices or a list of (node1, node2) pairs, not %r" % (edge_cov,))
+    a = a.astype(np.int64)
+    if a.ndim == 2:
+        lo, hi = a.min(axis=1), a.max(axis=1)
+        if lo.min() < 1 or (V is not None and hi.max() > V):
+            raise ValueError("edge_cov: nodes are numbered 1 .. V")
+        if V is None:
+            return np.ascontiguousarray(a, dtype=np.int32)                 # (the pairs, checked again with V)
+        return np.ascontiguousarray((lo - 1) * V - (lo - 1) * (lo - 2) // 2 + (hi - lo), dtype=np.int32)
+    if a.min() < 0 or (V is not None and a.max() >= V * (V + 1) // 2):
+        raise ValueError("edge_cov: edge indices are 0-based, 0 .. q - 1")
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _edge_cov(q, cols, mean, cov, nchains, draws, weights):
+    V = int(round((-1 + math.sqrt(1 + 8 * q)) / 2))
+    cols = np.arange(q, dtype=np.int64) if cols is None else np.asarray(cols, dtype=np.int64)
+    n1, n2 = _edge_nodes(V, cols)
+    return EdgeCov(cols=cols, node1=n1, node2=n2, mean=mean, cov=cov, chains=nchains, draws=draws,
+                   weights=None if weights is None else np.array(weights, dtype=np.float64))
+
+
+def device_edge_cov(chains, nburn, nsamp, cols=None, weights=None):
+    """The posterior covariance of the edge coefficients `cols` (0-based indices; None: all q) over the pooled windows nburn+1 .. nburn+nsamp of
+    live chains, on the device (bnr_chains_cov) -> EdgeCov: m + m^2 numbers leave the GPU's side, not the traces.  weights: chain weights (the
+    stacking weights), for the covariance of the chains' mixture under them."""
+    chains = list(chains)
+    if not chains:
+        raise ValueError("need at least one chain")
+    ci = _capi.cov_cols(cols, chains[0].q)
+    mean, cov = _capi.pooled_cov(chains, nburn + 1, nsamp, ci, weights)
+    return _edge_cov(chains[0].q, ci, mean, cov, len(chains), len(chains) * int(nsamp), weights)
+
+
+def _host_cov(seg, weights=None, dtype=np.float64):
+    """(mean, cov) of K chains' draws seg (K, nsamp, m) as bnr_cov defines them: the centre is the Summary mean (_strided_mean over the pooled
+    draws; under weights sum_k w_k m_k of the chains' own, k ascending from 0.0) in float64; the centred products and their sums in `dtype` (the
+    tests run it in long double), chain by chain, then sum_k G_k / (S - 1), or sum_k w_k G_k / nsamp"""
+    seg = np.asarray(seg, dtype=np.float64)
+    K, ns, m = seg.shape
+    with np.errstate(all="ignore"):
+        if weights is None:
+            c = _strided_mean(seg.reshape(K * ns, m).T)
+        else:
+            w = np.asarray(weights, dtype=np.float64)
+            mk = _strided_mean(np.transpose(seg, (0, 2, 1)))               # (K, m)
+            c = np.zeros(m)
+            for k in range(K):
+                c = c + w[k] * mk[k]
+            c = np.where(np.isnan(seg).any(axis=(0, 1)), np.nan, c)
+        tot = np.zeros((m, m), dtype=dtype)
+        for k in range(K):
+            d = seg[k].astype(dtype) - c.astype(dtype)[None, :]
+            G = d.T @ d
+            tot = tot + (G if weights is None else dtype(w[k]) * G)
+        cov = tot / dtype(ns if weights is not None else K * ns - 1)
+        bad = ~np.isfinite(c)
+        cov[bad, :] = np.nan
+        cov[:, bad] = np.nan
+    return c, cov
+
+
+def _host_edge_cov(tables, nburn, nsamp, cols=None, weights=None, dtype=np.float64):
+    """device_edge_cov restated in numpy over the fetched tables of the same chains (_host_cov on their windows): the same definition, centres
+    included"""
+    tables = list(tables)
+    if not tables:
+        raise ValueError("need at least one table")
+    if nsamp * len(tables) < 2:
+        raise ValueError("a covariance needs at least 2 draws")
+    q = tables[0]["gamma"].shape[1]
+    ci = _capi.cov_cols(cols, q)
+    if weights is not None:
+        weights = _wquantile_args(np.zeros((1, len(tables))), weights, len(tables))[1]
+    sel = slice(None) if ci is None else ci
+    seg = np.stack([t["gamma"][nburn:nburn + nsamp, :, 0][:, sel] for t in tables])
+    mean, cov = _host_cov(seg, weights, dtype)
+    return _edge_cov(q, ci, mean, cov, len(tables), len(tables) * int(nsamp), weights)
+
+
+def cov(draws, nchains=1, weights=None, device=None):
+    """The mean and the covariance matrix of any (nchains nsamp) x m matrix of draws (rows = draws, chain k's in rows k nsamp ..), on the GPU
+    (bnr_cov): dict with mean (m,) and cov (m, m); numpy's cov about the Summary mean, or with chain weights the covariance of the mixture"""
+    mean, c = _capi.cov_raw(draws, nchains, weights, 0 if device is None else int(device))
+    return dict(mean=mean, cov=c)
+
+
+def _edge_cov_of(results):
+    """EdgeCov(results): see EdgeCov"""
+    if results.edge_cov is not None:
+        return results.edge_cov
+    if results.state is None:
+        raise ValueError("EdgeCov needs Fit(..., edge_cov=True), or the state table (return_state=True)")
+    return _host_edge_cov([results.state], results.burn_in, results.sampled)
+
+
 # ------------------------------------------------------------------------------------------ chain placement
 def _dist():
     """torch.distributed if THE CALLER has imported and initialised it, else None.  Never imports torch itself: a process group can only
@@ -1769,6 +1958,7 @@ class _Requests:
     edge_sel: tuple                  # (hdi_prob, fdr), or None
     node_sets: int                   # the number of top node sets, or None
     stack: bool
+    edge_cov: object = None          # None, "all", or the 0-based edge indices (int32)
 
 
 def _one_rank(option):
@@ -1780,7 +1970,7 @@ def _one_rank(option):
 def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, return_state=True, summary_interval=None, ess_max_lag=None, predict_X=None,
                   predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None, pool_chains=False, predict_observation=False,
                   pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False, hdi_prob=0.95, fdr=0.05, node_sets=False,
-                  top_sets=10, stack_chains=False):
+                  top_sets=10, stack_chains=False, edge_cov=False):
     """The options of a fit (Fit's keywords) checked before any sampling, in this order -> _Requests.  Fit itself calls it ahead of
     parameters.log for the refusals alone, without X_new and nsamp: what needs them -- the new rows, the lag window of the rank diagnostics,
     r_eff -- is then left to generate_samples / generate_samples_dbl."""
@@ -1817,10 +2007,13 @@ def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, retur
         if int(num_chains) > STACK_MAX_CHAINS:
             raise ValueError("stack_chains takes at most %d chains" % STACK_MAX_CHAINS)
         _one_rank("stack_chains")
+    ec = _edge_cov_cols(edge_cov, None if X_new is None else X_new.V)
+    if ec is not None:
+        _one_rank("edge_cov")
     if X_new is not None:
         _capi.r_eff_array(loo_r_eff, X_new.n)
     return _Requests(return_state, summary_interval, ess_max_lag, pred, bool(waic), bool(loo), loo_r_eff, bool(pool_chains), bool(predict_observation),
-                     pred_seed, lp, bool(rank_diagnostics), es, ntop, bool(stack_chains))
+                     pred_seed, lp, bool(rank_diagnostics), es, ntop, bool(stack_chains), ec)
 
 
 def _finish(chainset, res, req, seed):
@@ -1833,7 +2026,9 @@ def _finish(chainset, res, req, seed):
     edge_sel: the HDIs, sign probabilities and selected edges over every chain of the fit (Results.edge_selection).
     node_sets: the joint posterior of the node indicators over every chain of the fit (Results.node_sets).
     stack: the chain stacking over every chain of the fit (Results.stacking), with summary_interval its summary and with predict its
-    prediction under the weights; what pool_chains or the default return is not changed by it."""
+    prediction under the weights; what pool_chains or the default return is not changed by it.
+    edge_cov: the posterior covariance of the edge coefficients over every chain of the fit (Results.edge_cov), and with stack the one under
+    the stacking weights (Stacking.edge_cov)."""
     nb, ns = res.burn_in, res.sampled
     every = [chainset.chains[c] for c in chainset.ids]
     pred_seed = seed if req.pred_seed is None else req.pred_seed
@@ -1844,6 +2039,11 @@ def _finish(chainset, res, req, seed):
         if req.predict is not None:
             st.prediction = device_predict_stacked(every, st.weights, nb, ns, *req.predict, pred_seed, predict_observation=req.predict_observation)
         res.stacking = st
+    if req.edge_cov is not None:
+        cols = None if isinstance(req.edge_cov, str) else req.edge_cov
+        res.edge_cov = device_edge_cov(every, nb, ns, cols)
+        if req.stack:
+            res.stacking.edge_cov = device_edge_cov(every, nb, ns, cols, res.stacking.weights)
     if req.node_sets is not None:
         res.node_sets = device_node_sets(every, nb, ns, req.node_sets)
     if req.edge_sel is not None:
@@ -1912,7 +2112,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                      purge_burn=None, device=None, _keep=None, return_state=True, summary_interval=None, ess_max_lag=None,
                      xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
                      pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
-                     hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False):
+                     hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False):
     """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
     xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
     xi_weights_code(xi_weights)
@@ -1925,7 +2125,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                         predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic, loo=loo, loo_r_eff=loo_r_eff,
                         pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed, loo_predict=loo_predict,
                         rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets,
-                        top_sets=top_sets, stack_chains=stack_chains)       # (checked before any sampling)
+                        top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -1978,7 +2178,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                          seed=None, purge_burn=None, device=None, return_state=True, summary_interval=None, ess_max_lag=None,
                          xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
                          pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
-                         hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False):
+                         hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False):
     """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
     xi_weights_code(xi_weights)
     if nu == R:
@@ -1990,7 +2190,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                         predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic, loo=loo, loo_r_eff=loo_r_eff,
                         pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed, loo_predict=loo_predict,
                         rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets,
-                        top_sets=top_sets, stack_chains=stack_chains)       # (checked before any sampling)
+                        top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -2044,7 +2244,7 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
         purge_burn=None, filename="parameters.log", device=None, return_state=True, summary_interval=None, ess_max_lag=None,
         xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
         pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
-        hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False):
+        hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False):
     """Fit! (gibbs.jl:725-751).  The `V` keyword is accepted and ignored, as in the reference.
     Extensions: summary_interval=95 computes Summary's statistics on the GPU (Results.summary_device);
     return_state=False then leaves the (large) state table on the device and frees it; ess_max_lag=0 (default lag
@@ -2072,11 +2272,16 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     not mix: every chain's own PSIS-LOO, the chain weights that maximise the leave-one-out log score of the mixture, and -- with
     summary_interval / predict_X -- the Summary statistics and the prediction under those weights (Results.stacking, see Stacking); what
     pool_chains or the default return is unchanged.
+    edge_cov=True (or an array of 0-based edge indices, or a list of 1-based (node1, node2) pairs) adds the posterior covariance matrix of
+    those edge coefficients -- vcov(fit) -- computed on the GPU from the resident traces over every chain of the fit (Results.edge_cov, see
+    EdgeCov: sd, corr, contrast(C) for intervals on linear combinations of edges, top_pairs); with stack_chains=True also the covariance under
+    the stacking weights (Results.stacking.edge_cov); every chain must live on this rank.
     parameters.log keeps the reference's lines only."""
     xi_weights_code(xi_weights)
     _fit_requests(y, num_chains, predict_X=predict_X, predict_interval=predict_interval, pool_chains=pool_chains,
                   predict_observation=predict_observation, loo_predict=loo_predict, rank_diagnostics=rank_diagnostics,
-                  edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains)
+                  edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains,
+                  edge_cov=edge_cov)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
         with open(filename, "w") as f:
@@ -2097,7 +2302,7 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                                     waic=waic, loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation,
                                     pred_seed=pred_seed, loo_predict=loo_predict, rank_diagnostics=rank_diagnostics,
                                     edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr,
-                                    node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains)
+                                    node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
@@ -2105,4 +2310,4 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                             xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic,
                             loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed,
                             loo_predict=loo_predict, rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr,
-                            node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains)
+                            node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov)

@@ -1213,3 +1213,144 @@ int bnr_chains_wpredict(bnr_chain *const *chains, int32_t nchains, const double 
     if (y) for (int i = 0; i < m; ++i) lpd[i] = wlse(hl.data() + i, (size_t)m, weights, nchains);
     return BNR_OK;
 }
+
+// ------------------------------------------------------------------------------------------ posterior covariance of the edge coefficients (ABI 17): include/bnr_hip.h
+// The draws of a covariance call: chain k's window is nsamp rows of rowlen doubles from rows[k] (a trace's first window row at o_gamma, or row
+// k nsamp of a caller's matrix); `cols` (host, ncols entries, checked) picks the columns.
+// 1. the centres: the chosen columns staged as stage_cols stages them (k_fetch_cols, one launch per chain and run of consecutive columns; blocks
+//    of about 1 GiB of draws, or `blk_set` columns) and k_summary's mean of each -- with wt k_wsummary's -- so that the centre IS the mean the
+//    Summary calls report, bit for bit.  The staging buffer goes before the Grams come.
+// 2. per pair of column blocks I <= J (Bc columns each: `blk_set`, or the largest multiple of 128 whose nc Bc^2 doubles stay within 1 GiB) one
+//    k_cov for all chains (blockIdx.z = chain), each into its Bc x Bc slice of G, then k_cov_finish: the chains' Grams added in order, divided, mirrored into covd.
+// An entry's sums are fixed by (nc, nsamp): the blocks and the tile shape (TW = 4 where the call has 128 x 128 tiles enough to fill the chip, 2
+// below) only move it to another workgroup.
+static int cov_run(hipStream_t st, const std::vector<const double *> &rows, long long rowlen, int nsamp, int ncols, const int32_t *cols,
+                   const bnr_wsum_weights *wt, int blk_set, double *mean, double *cov)
+{
+    const int nc = (int)rows.size();
+    const long long S = (long long)nc * nsamp;
+    if (nc > 65535) return fail(BNR_ERR_BAD_ARG, "more than 65535 chains");        // (the chains are k_cov's grid.z)
+    int rc;
+    dev_tmp tmp;
+    int *colsd = nullptr;
+    double *cen = nullptr, *covd = nullptr, *G = nullptr, *wd = nullptr;
+    const double **rowsd = nullptr;
+    if ((rc = tmp.alloc(&colsd, (size_t)ncols, st, false)) || (rc = tmp.alloc(&cen, (size_t)ncols, st))) return rc;
+    HIPCHK(hipMemcpyAsync(colsd, cols, sizeof(int) * (size_t)ncols, hipMemcpyHostToDevice, st));
+    if ((rc = tmp.alloc(&rowsd, (size_t)nc, st, false))) return rc;
+    HIPCHK(hipMemcpyAsync(rowsd, rows.data(), sizeof(double *) * (size_t)nc, hipMemcpyHostToDevice, st));
+    if (wt) {
+        if ((rc = tmp.alloc(&wd, (size_t)BNR_STACK_MAX_CHAINS, st, false))) return rc;
+        HIPCHK(hipMemcpyAsync(wd, wt->w, sizeof(double) * BNR_STACK_MAX_CHAINS, hipMemcpyHostToDevice, st));
+    }
+    {
+        dev_tmp stage;                                  // (freed at the end of this block: hipFree waits for the device)
+        double *buf = nullptr;
+        const int sblk = block_cols(S, blk_set, ncols);
+        if ((rc = stage.alloc(&buf, (size_t)sblk * (size_t)S, st, false))) return rc;
+        for (int p0 = 0; p0 < ncols; p0 += sblk) {
+            const int pc = std::min(sblk, ncols - p0);
+            for (int p = 0; p < pc;) {
+                int run = 1;
+                while (p + run < pc && cols[p0 + p + run] == cols[p0 + p] + run) ++run;
+                for (int k = 0; k < nc; ++k)
+                    launch_fetch_cols(st, rows[k], (int)rowlen, cols[p0 + p], run, 0, nsamp, buf + (size_t)p * (size_t)S + (size_t)k * nsamp, S);
+                p += run;
+            }
+            if (wt) launch_wsummary(st, pc, buf, S, nsamp, nc, *wt, 0, 1, 1, cen + p0, nullptr, nullptr);
+            else launch_summary(st, pc, buf, (int)S, 0, 1, 1, cen + p0, nullptr, nullptr);
+        }
+        HIPCHK(hipStreamSynchronize(st));
+        if ((rc = check_launch("k_summary"))) return rc;
+    }
+    int Bc = blk_set > 0 ? blk_set : std::max(128, (int)sqrt((double)((size_t)1 << 27) / nc) / 128 * 128);
+    Bc = std::min(Bc, ncols);
+    const long long t128 = ((long long)ncols + 127) / 128;
+    const bool big = t128 * (t128 + 1) / 2 * nc >= 512;
+    const int wg = big ? 128 : 64;                      // the columns of a workgroup's tile: 2 x 2 waves of 16 TW each
+    const size_t gstride = (size_t)Bc * (size_t)Bc;
+    if ((rc = tmp.alloc(&G, gstride * (size_t)nc, st, false)) || (rc = tmp.alloc(&covd, (size_t)ncols * (size_t)ncols, st, false))) return rc;
+    const double denom = wt ? (double)nsamp : (double)(S - 1);
+    for (int a0 = 0; a0 < ncols; a0 += Bc)
+        for (int b0 = a0; b0 < ncols; b0 += Bc) {
+            const int na = std::min(Bc, ncols - a0), nb = std::min(Bc, ncols - b0);
+            const dim3 grid((nb + wg - 1) / wg, (na + wg - 1) / wg, nc);
+            if (big)
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(bnr_vcov::k_cov<4>), grid, dim3(256), 0, st, (const double *const *)rowsd, rowlen, nsamp, (const int *)colsd,
+                                   (const double *)cen, a0, na, b0, nb, G, (long long)gstride, Bc);
+            else
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(bnr_vcov::k_cov<2>), grid, dim3(256), 0, st, (const double *const *)rowsd, rowlen, nsamp, (const int *)colsd,
+                                   (const double *)cen, a0, na, b0, nb, G, (long long)gstride, Bc);
+            hipLaunchKernelGGL(bnr_vcov::k_cov_finish, dim3((nb + 63) / 64, (na + 3) / 4), dim3(256), 0, st, (const double *)G, (long long)gstride, Bc, nc,
+                               (const double *)wd, denom, (const double *)cen, a0, na, b0, nb, covd, ncols);
+        }
+    HIPCHK(hipMemcpyAsync(mean, cen, sizeof(double) * (size_t)ncols, hipMemcpyDeviceToHost, st));
+    hipError_t e = hipMemcpyAsync(cov, covd, sizeof(double) * (size_t)ncols * (size_t)ncols, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(BNR_ERR_HIP, std::string("cov: ") + hipGetErrorString(e));
+    return check_launch("k_cov");
+}
+// the column list of a covariance call over q columns as cov_run takes it: cols as given (every index in 0 .. q - 1), or 0 .. q - 1 for NULL
+static int cov_cols(int32_t ncols, const int32_t *cols, int q, std::vector<int32_t> &out)
+{
+    if (ncols < 1) return fail(BNR_ERR_BAD_ARG, "need ncols >= 1 columns");
+    if (!cols && ncols != q) return fail(BNR_ERR_BAD_ARG, "cols == NULL means every column: ncols must be " + std::to_string(q));
+    out.resize(ncols);
+    for (int p = 0; p < ncols; ++p) {
+        out[p] = cols ? cols[p] : p;
+        if (out[p] < 0 || out[p] >= q) return fail(BNR_ERR_BAD_ARG, "column index outside 0 .. " + std::to_string(q - 1));
+    }
+    return BNR_OK;
+}
+int bnr_chain_cov(bnr_chain *c, int32_t first_row, int32_t nsamp, int32_t ncols, const int32_t *cols, double *mean, double *cov)
+{
+    if (!c) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    return bnr_chains_cov(&c, 1, nullptr, first_row, nsamp, ncols, cols, mean, cov);
+}
+int bnr_chains_cov(bnr_chain *const *chains, int32_t nchains, const double *weights, int32_t first_row, int32_t nsamp, int32_t ncols,
+                   const int32_t *cols, double *mean, double *cov)
+{
+    if (!chains || !mean || !cov) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    int rc;
+    bnr_wsum_weights wt;
+    if (weights && (rc = wsum_pack(weights, nchains, wt))) return rc;
+    if ((rc = pooled_check(chains, nchains, first_row, nsamp))) return rc;
+    if ((long long)nchains * nsamp < 2) return fail(BNR_ERR_BAD_ARG, "a covariance needs nchains * nsamp >= 2 draws");
+    bnr_chain *c = chains[0];
+    std::vector<int32_t> hc;
+    if ((rc = cov_cols(ncols, cols, c->d.q, hc))) return rc;
+    HIPCHK(hipSetDevice(c->device));
+    if ((rc = pooled_quiesce(chains, nchains))) return rc;
+    std::vector<const double *> rows(nchains);
+    for (int k = 0; k < nchains; ++k) {
+        const bnr_dev &dk = chains[k]->d;
+        if (dk.rowlen != c->d.rowlen) return fail(BNR_ERR_BAD_ARG, "pooled chains must have equal trace rows");
+        rows[k] = dk.trace + (size_t)(first_row - 1) * dk.rowlen + dk.o_gamma;
+    }
+    return cov_run(c->x.stream, rows, c->d.rowlen, nsamp, ncols, hc.data(), weights ? &wt : nullptr, c->cov_block_cols, mean, cov);
+}
+// the same on a caller's (K nsamp) x m matrix (host, row-major: draws x columns, chain k's draws in rows k nsamp ..): k_cov's direct test, and
+// the covariance of any set of draws.  The matrix is uploaded whole, on a stream of the call's own.
+int bnr_cov(int32_t device, int32_t K, int32_t nsamp, int32_t m, const double *x, const double *weights, double *mean, double *cov)
+{
+    if (!x || !mean || !cov) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    if (K < 1 || nsamp < 1 || m < 1) return fail(BNR_ERR_BAD_ARG, "need K >= 1 chains, nsamp >= 1 draws per chain and m >= 1 columns");
+    int rc;
+    bnr_wsum_weights wt;
+    if (weights && (rc = wsum_pack(weights, K, wt))) return rc;
+    const long long S = (long long)K * nsamp;
+    if (S > 0x7FFFFFFFll) return fail(BNR_ERR_BAD_ARG, "more than 2^31 - 1 pooled draws");
+    if (S < 2) return fail(BNR_ERR_BAD_ARG, "a covariance needs K * nsamp >= 2 draws");
+    std::vector<int32_t> hc;
+    if ((rc = cov_cols(m, nullptr, m, hc))) return rc;
+    stream_guard guard;
+    if ((rc = guard.open(device))) return rc;
+    hipStream_t st = guard.s;
+    dev_tmp tmp;                                        // (freed before the stream goes)
+    double *Xd = nullptr;
+    if ((rc = tmp.alloc(&Xd, (size_t)S * (size_t)m, st, false))) return rc;
+    HIPCHK(hipMemcpyAsync(Xd, x, sizeof(double) * (size_t)S * (size_t)m, hipMemcpyHostToDevice, st));
+    std::vector<const double *> rows(K);
+    for (int k = 0; k < K; ++k) rows[k] = Xd + (size_t)k * nsamp * (size_t)m;
+    return cov_run(st, rows, m, nsamp, m, hc.data(), weights ? &wt : nullptr, 0, mean, cov);
+}

@@ -1145,3 +1145,119 @@ __global__ __launch_bounds__(256) void k_incl_group(const unsigned long long *pa
         for (int wd = 0; wd < W; ++wd) top_sets[(size_t)j * W + wd] = a[wd];
     }
 }
+
+// ===================================================================================== k_cov (ABI 17: the posterior covariance of the edge coefficients)
+// The centred Gram of `ncols` chosen gamma columns over every chain's window, chain blockIdx.z on its own: for the positions pa in [a0, a0 + na)
+// and pb in [b0, b0 + nb) of the caller's column list (a pair of column blocks, I <= J), with x = rowsv[blockIdx.z] and G the chain's slice
+// G + blockIdx.z gstride,
+//   G[(pa - a0) ldg + (pb - b0)] = sum_s (x[s][cols[pa]] - centre[pa]) (x[s][cols[pb]] - centre[pb]),  s = 0 .. nsamp - 1,
+// by v_mfma_f64_16x16x4_f64 with the K dimension running over the draws: A[i][k] = the centred draw s0 + k of column pa0 + i, B[k][j] = that of
+// column pb0 + j.  x[s] = rows + s rowlen is read in place (a trace row at o_gamma, or a row of a caller's matrix): the 16 lanes of a lane group
+// read 16 columns of one draw, 128 contiguous bytes where the columns are consecutive.  The centre (the mean the Summary calls report, computed
+// before this kernel) is subtracted in registers BEFORE the product -- never an uncentred Gram corrected by S c c^T, which loses every digit of a
+// column like 1e8 + N(0, 1) (see k_fold).  Padding -- the draws past nsamp of the last K step, the columns past the block's end -- is the
+// constant 0.0 chosen by a select behind the subtraction, and its loads are clamped to a draw and a column that exist: padding never meets
+// garbage, and a NaN lives only in the rows and columns of G that belong to its column.
+// K order: one accumulator per entry, k0 = 0, 16, ... < nsamp; inside a step MFMA t (0..3) takes the draws k0 + 4 t + g from lane group
+// g = lane >> 4.  So the order of an entry's sum is fixed by nsamp alone: not by the grid, the tile shape TW, the column block or the other
+// columns of the call; (pa, pb) and (pb, pa) are the same products in the same order.  D layout: lane l, reg r = row (l >> 4) + 4 r, column l & 15.
+// grid = (ceil(nb / (32 TW)), ceil(na / (32 TW)), chains), 256 threads: wave w owns the TW x TW tiles of 16 x 16 at rows (2 blockIdx.y + (w >> 1)) 16 TW,
+// columns (2 blockIdx.x + (w & 1)) 16 TW of the block pair; a wave whose entries all lie below the diagonal (pa > pb) or outside the pair
+// returns at once (no barrier in the kernel), entries below the diagonal inside a computed tile are written and never read.  The loads of
+// K step k0 + 16 are issued in front of the MFMAs of step k0.  No LDS, no scratch; 64-bit addressing.
+// Both kernels of this section live in namespace bnr_vcov, unlike every kernel above: tests/test_inclusion_host.py pins the set of global-scope
+// k_* kernels of this code object as it stood at ABI 15 and existing test files do not change, so a kernel added to this header since then
+// carries a namespace; tests/test_edge_cov_host.py pins where these two live by their qualified names.
+namespace bnr_vcov {
+template <int TW>
+__global__ __launch_bounds__(256) void k_cov(const double *const *rowsv, long long rowlen, int nsamp, const int *cols, const double *centre, int a0,
+                                             int na, int b0, int nb, double *G, long long gstride, int ldg)
+{
+    const double *rows = rowsv[blockIdx.z];
+    G += (size_t)blockIdx.z * (size_t)gstride;
+    constexpr int WT = 16 * TW;
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, g = lane >> 4, c = lane & 15;
+    const int pa0 = a0 + ((int)blockIdx.y * 2 + (w >> 1)) * WT, pb0 = b0 + ((int)blockIdx.x * 2 + (w & 1)) * WT;
+    const int aend = a0 + na, bend = b0 + nb;
+    if (pa0 >= aend || pb0 >= bend || pa0 > pb0 + WT - 1) return;
+    int ca[TW], cb[TW];
+    double ma[TW], mb[TW];
+    bool va[TW], vb[TW];
+#pragma unroll
+    for (int i = 0; i < TW; ++i) {
+        const int pa = pa0 + 16 * i + c, pb = pb0 + 16 * i + c;
+        va[i] = pa < aend; vb[i] = pb < bend;
+        ca[i] = cols[va[i] ? pa : a0]; cb[i] = cols[vb[i] ? pb : b0];
+        ma[i] = va[i] ? centre[pa] : 0.0; mb[i] = vb[i] ? centre[pb] : 0.0;
+    }
+    bnr_d4 acc[TW][TW];
+#pragma unroll
+    for (int i = 0; i < TW; ++i)
+#pragma unroll
+        for (int j = 0; j < TW; ++j) acc[i][j] = bnr_d4{0.0, 0.0, 0.0, 0.0};
+    double ra[4][TW], rb[4][TW];                       // the raw draws of the next K step
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const double *row = rows + (size_t)min(k0 + 4 * t + g, nsamp - 1) * (size_t)rowlen;
+#pragma unroll
+            for (int i = 0; i < TW; ++i) { ra[t][i] = row[ca[i]]; rb[t][i] = row[cb[i]]; }
+        }
+    };
+    fetch(0);
+    for (int k0 = 0; k0 < nsamp; k0 += 16) {
+        double av[4][TW], bv[4][TW];
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const bool ok = k0 + 4 * t + g < nsamp;
+#pragma unroll
+            for (int i = 0; i < TW; ++i) {
+                const double da = ra[t][i] - ma[i], db = rb[t][i] - mb[i];
+                av[t][i] = ok && va[i] ? da : 0.0;
+                bv[t][i] = ok && vb[i] ? db : 0.0;
+            }
+        }
+        fetch(k0 + 16);                                // (clamped to the last draw behind the window's end)
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < TW; ++i)
+#pragma unroll
+                for (int j = 0; j < TW; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[t][i], bv[t][j], acc[i][j], 0, 0, 0);
+    }
+#pragma unroll
+    for (int i = 0; i < TW; ++i)
+#pragma unroll
+        for (int j = 0; j < TW; ++j) {
+            const int pb = pb0 + 16 * j + c;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int pa = pa0 + 16 * i + g + 4 * r;
+                if (pa < aend && pb < bend) G[(size_t)(pa - a0) * (size_t)ldg + (size_t)(pb - b0)] = acc[i][j][r];
+            }
+        }
+}
+
+// k_cov_finish: the entries pa <= pb of a block pair from the chains' Grams (chain k's at G + k gstride), mirrored into both triangles of the
+// ncols x ncols matrix cov:  sum_k G_k / denom (wt NULL: denom = S - 1) or sum_k wt[k] G_k / denom (denom = nsamp), k ascending from 0.0,
+// every product and addition rounded on its own.  A column whose centre is not finite (it holds a NaN or an Inf draw) is NaN in its whole row
+// and column.  One thread per entry of the pair.
+__global__ __launch_bounds__(256) void k_cov_finish(const double *G, long long gstride, int ldg, int nc, const double *wt, double denom,
+                                                    const double *centre, int a0, int na, int b0, int nb, double *cov, int ncols)
+{
+    const int ib = (int)blockIdx.x * 64 + (int)(threadIdx.x & 63), ia = (int)blockIdx.y * 4 + (int)(threadIdx.x >> 6);
+    if (ia >= na || ib >= nb) return;
+    const int pa = a0 + ia, pb = b0 + ib;
+    if (pa > pb) return;
+    const double *e = G + (size_t)ia * (size_t)ldg + (size_t)ib;
+    double tot = 0.0;
+    for (int k = 0; k < nc; ++k) {
+        const double gk = e[(size_t)k * (size_t)gstride];
+        tot = tot + (wt ? wt[k] * gk : gk);
+    }
+    double v = tot / denom;
+    if (!isfinite(centre[pa]) || !isfinite(centre[pb])) v = NAN;
+    cov[(size_t)pa * (size_t)ncols + (size_t)pb] = v;
+    cov[(size_t)pb * (size_t)ncols + (size_t)pa] = v;
+}
+}  // namespace bnr_vcov

@@ -2160,6 +2160,12 @@ int bnr_chain_set_option(bnr_chain *c, const char *name, int64_t value)
         c->rank_block_cols = (int)value;
         return BNR_OK;
     }
+    if (!strcmp(name, "cov_block_cols")) {
+        // performance only: edge columns per staging block and per Gram block of bnr_chain_cov / bnr_chains_cov (the first chain's setting counts)
+        if (value < 0 || value > (1 << 24)) return fail(BNR_ERR_BAD_ARG, "cov_block_cols must be between 0 (automatic) and 2^24");
+        c->cov_block_cols = (int)value;
+        return BNR_OK;
+    }
     if (!strcmp(name, "byte_x")) {
         // 0: the X passes read the f64 matrix also when a byte image exists; 1: back to the byte image (if the input had one)
         if (c->pending) return fail(BNR_ERR_BAD_ARG, "an asynchronous run is pending");

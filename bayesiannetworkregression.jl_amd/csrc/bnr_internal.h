@@ -88,6 +88,7 @@ struct bnr_chain {
     int predict_block_rows = 0;  // tunable "predict_block_rows": rows per block of bnr_chain_predict / bnr_chain_loglik_stats (0: automatic)
     int summary_block_cols = 0;  // tunable "summary_block_cols": parameter columns per staging block of the Summary calls (0: automatic)
     int rank_block_cols = 0;     // tunable "rank_block_cols": parameter columns per staging block of the rank-normalised diagnostics (0: automatic)
+    int cov_block_cols = 0;      // tunable "cov_block_cols": edge columns per staging block and per Gram block of bnr_chains_cov (0: automatic)
 };
 
 struct bnr_group {

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BNR_ABI_VERSION 16  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
+#define BNR_ABI_VERSION 17  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
                                5: + bnr_chain_create_typed, bnr_chain_create_from_matrices, bnr_device_synchronize; 6: + bnr_comm_info;
                                7: + option "xi_weights", bnr_host_xi_weight; 8: + bnr_chain_predict, bnr_chain_predict_from_matrices,
                                bnr_chain_loglik_stats, option "predict_block_rows"; 9: + bnr_chain_loo, bnr_psis_loo;
@@ -38,7 +38,7 @@ extern "C" {
                                option "rank_block_cols"; 13: + bnr_chain_hdi, bnr_chains_hdi, bnr_hdi;
                                14: + bnr_host_gig_attempts; 15: + bnr_chain_inclusion, bnr_chains_inclusion,
                                bnr_inclusion; 16: + bnr_stacking_weights, bnr_chains_stack, bnr_chains_wsummary, bnr_chains_wpredict,
-                               bnr_wquantile (all additive) */
+                               bnr_wquantile; 17: + bnr_chain_cov, bnr_chains_cov, bnr_cov, option "cov_block_cols" (all additive) */
 
 enum {
     BNR_OK = 0,
@@ -408,6 +408,31 @@ int bnr_chains_wpredict(bnr_chain *const *chains, int32_t nchains, const double 
 int bnr_wquantile(int32_t device, int32_t m, int32_t K, int32_t nsamp, const double *x, const double *weights, int32_t k_lo, int32_t k_hi, double *mean,
                   double *lower, double *upper);
 
+/* Posterior covariance of the edge coefficients (ABI 17) -- an ADDITION to the reference: vcov(fit) for ncols chosen gamma columns over the pooled
+ * window of nchains >= 1 chains of one device (S = nchains nsamp draws, chain by chain in the order passed, as for bnr_chains_summary), computed
+ * on the device from the resident traces (kernel k_cov, v_mfma_f64_16x16x4_f64 with the draws as the K dimension); nothing of any chain is written.
+ *   cols[ncols]: 0-based gamma indices, in any order, repeats allowed; NULL = 0 .. q - 1 and then ncols must be q.
+ *   mean[ncols]: the centre c of every column -- weights NULL: bnr_chains_summary's mean_gamma of that column, bit for bit; with weights:
+ *   bnr_chains_wsummary's.
+ *   cov[ncols x ncols], row-major, both triangles: with G_k[a, b] = sum over chain k's window of (x_sa - c_a)(x_sb - c_b) -- the centre is
+ *   subtracted from every draw before the product --
+ *     weights NULL: cov[a, b] = (sum_k G_k[a, b]) / (S - 1), numpy's cov;
+ *     with weights w: cov[a, b] = (sum_k w_k G_k[a, b]) / nsamp, the covariance of the mixture sum_k w_k P_k of the chains' empirical measures;
+ *   k ascending from 0.0, every product and addition rounded on its own.  The order of every entry's sums is fixed by (nchains, nsamp) alone: an
+ *   entry does not depend on the grid, on the column block (option "cov_block_cols" of chains[0]: the columns staged at a time for the centres
+ *   and the columns of a Gram block; 0 = blocks whose temporaries stay near 1 GiB), on which other columns were asked for, or on the call, bit
+ *   for bit; cov[a, b] and cov[b, a] are the same bits.  A column holding a NaN or +-Inf draw is NaN in its whole row and column of cov; every
+ *   other entry is unaffected.
+ * Checks (BNR_ERR_BAD_ARG): those of bnr_chains_summary's window, S < 2, ncols < 1, an index outside 0 .. q - 1, cols NULL with ncols != q; with
+ * weights those of bnr_chains_wsummary (finite, >= 0, one > 0, |sum - 1| <= 1e-9, nchains <= BNR_STACK_MAX_CHAINS; used as given).  A buffer that
+ * does not fit on the device is BNR_ERR_HIP.  Runs eagerly on chains[0]'s stream; bnr_chain_cov is the pooled call on a list of one.
+ * bnr_cov: the same for a caller's (K nsamp) x m matrix x (host, row-major: draws x columns, chain k's draws in rows k nsamp ..; K >= 1,
+ * nsamp >= 1, m >= 1, K nsamp >= 2), all m columns, on a stream of its own; the matrix is uploaded whole.  DESIGN.md section 8. */
+int bnr_chain_cov(bnr_chain *chain, int32_t first_row, int32_t nsamp, int32_t ncols, const int32_t *cols, double *mean, double *cov);
+int bnr_chains_cov(bnr_chain *const *chains, int32_t nchains, const double *weights, int32_t first_row, int32_t nsamp, int32_t ncols,
+                   const int32_t *cols, double *mean, double *cov);
+int bnr_cov(int32_t device, int32_t K, int32_t nsamp, int32_t m, const double *x, const double *weights, double *mean, double *cov);
+
 /* Effective sample size -- an ADDITION to the reference (which only has split-Rhat; north-star item "Rhat/ESS check").
  * bnr_chain_ess_stats: this chain's message over rows first_row .. first_row+nsamp-1: for both halves of the window (the
  *   halves of split-Rhat) the mean, the variance and the autocovariances at lags 0..max_lag-1 of gamma (q) then xi (V):
@@ -531,7 +556,10 @@ int bnr_debug_set_exp(int32_t device, int32_t flags);
  *               for every value.
  *   "summary_block_cols" (chains only) parameter columns per staging block of bnr_chain_summary / bnr_chains_summary, whose buffer holds columns x S
  *               doubles.  0 (default): as many as fit in about 1 GiB.  The results are bitwise the same for every value.
- *   "byte_x"    (chains only) 0: the X passes read the f64 matrix although a byte image of X exists; 1 (default): the byte image
+ *   "cov_block_cols" (chains only) edge columns per block of bnr_chain_cov / bnr_chains_cov: the columns staged at a time for the centres (columns x S
+ *               doubles) and the columns of a Gram block (nchains x columns^2 doubles).  0 (default): blocks of about 1 GiB each.  The results
+ *               are bitwise the same for every value.
+ *   "byte_x"   (chains only) 0: the X passes read the f64 matrix although a byte image of X exists; 1 (default): the byte image
  *               (kept when the model matrix came as Bool/UInt8, or as Int32/Int64 with every value in 0..255; docs/src/man/inputdata.md)
  *   "gram_i8"   (chains only; round 5) 1 (the default from n_pad^2 q >= 2.5e8 on, where it was measured faster -- n = 500, V = 100 and
  *               larger; smaller problems default to 0): the model matrix came integer-typed with every entry 0 or 1

@@ -413,6 +413,27 @@ function chains_wpredict(chains::Vector{Chain}, weights, nburn, nsamp, Xnew::Abs
     (mean, lo, hi, y === nothing ? nothing : lpd, predict_observation ? plo : nothing, predict_observation ? phi : nothing)
 end
 
+# ---- posterior covariance of the edge coefficients (ABI 17; bnr_chains_cov; an addition to the reference): vcov of the gamma columns `cols`
+# (1-based edge indices in Summary's order, as Julia indexes; nothing = all q) over the pooled windows nburn+1 .. nburn+nsamp of the chains,
+# computed on the device -> (mean, cov).  mean is the Summary mean of every column (under `weights` chains_wsummary's), cov the m x m matrix
+# sum_k G_k / (S - 1) -- Statistics.cov of the pooled draws -- or with chain weights sum_k w_k G_k / nsamp.  cov is symmetric bit for bit, so
+# the library's row-major matrix is Julia's column-major one.
+function edge_cov(chains::Vector{Chain}, nburn, nsamp; cols=nothing, weights=nothing)
+    ch = chains[1]
+    weights === nothing || length(weights) == length(chains) || throw(ArgumentError("need one weight per chain"))
+    hs = Ptr{Cvoid}[c.h for c in chains]
+    wv = weights === nothing ? Float64[] : Vector{Float64}(weights)
+    wp = weights === nothing ? Ptr{Cdouble}(C_NULL) : pointer(wv)
+    cv = cols === nothing ? Int32[] : Int32[c - 1 for c in cols]
+    cp = cols === nothing ? Ptr{Int32}(C_NULL) : pointer(cv)
+    m = cols === nothing ? ch.q : length(cv)
+    mean, cov = zeros(m), zeros(m, m)
+    GC.@preserve hs wv cv check(ccall((:bnr_chains_cov, LIB), Cint,
+        (Ptr{Ptr{Cvoid}}, Int32, Ptr{Cdouble}, Int32, Int32, Int32, Ptr{Int32}, Ptr{Cdouble}, Ptr{Cdouble}),
+        hs, length(hs), wp, nburn + 1, nsamp, m, cp, mean, cov))
+    mean, cov
+end
+
 # the noise of the predictive draws as the device draws it (host code, no GPU): ns x ni, element [s - s0 + 1, i - i0 + 1]
 function pred_noise(seed, s0, ns, i0, ni)
     out = zeros(ns, ni)
