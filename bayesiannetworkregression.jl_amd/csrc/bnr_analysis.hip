@@ -1276,12 +1276,12 @@ static int cov_run(hipStream_t st, const std::vector<const double *> &rows, long
             const int na = std::min(Bc, ncols - a0), nb = std::min(Bc, ncols - b0);
             const dim3 grid((nb + wg - 1) / wg, (na + wg - 1) / wg, nc);
             if (big)
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(bnr_vcov::k_cov<4>), grid, dim3(256), 0, st, (const double *const *)rowsd, rowlen, nsamp, (const int *)colsd,
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov<4>), grid, dim3(256), 0, st, (const double *const *)rowsd, rowlen, nsamp, (const int *)colsd,
                                    (const double *)cen, a0, na, b0, nb, G, (long long)gstride, Bc);
             else
-                hipLaunchKernelGGL(HIP_KERNEL_NAME(bnr_vcov::k_cov<2>), grid, dim3(256), 0, st, (const double *const *)rowsd, rowlen, nsamp, (const int *)colsd,
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_cov<2>), grid, dim3(256), 0, st, (const double *const *)rowsd, rowlen, nsamp, (const int *)colsd,
                                    (const double *)cen, a0, na, b0, nb, G, (long long)gstride, Bc);
-            hipLaunchKernelGGL(bnr_vcov::k_cov_finish, dim3((nb + 63) / 64, (na + 3) / 4), dim3(256), 0, st, (const double *)G, (long long)gstride, Bc, nc,
+            hipLaunchKernelGGL(k_cov_finish, dim3((nb + 63) / 64, (na + 3) / 4), dim3(256), 0, st, (const double *)G, (long long)gstride, Bc, nc,
                                (const double *)wd, denom, (const double *)cen, a0, na, b0, nb, covd, ncols);
         }
     HIPCHK(hipMemcpyAsync(mean, cen, sizeof(double) * (size_t)ncols, hipMemcpyDeviceToHost, st));

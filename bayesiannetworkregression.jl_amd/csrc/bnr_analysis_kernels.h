@@ -1165,10 +1165,6 @@ __global__ __launch_bounds__(256) void k_incl_group(const unsigned long long *pa
 // columns (2 blockIdx.x + (w & 1)) 16 TW of the block pair; a wave whose entries all lie below the diagonal (pa > pb) or outside the pair
 // returns at once (no barrier in the kernel), entries below the diagonal inside a computed tile are written and never read.  The loads of
 // K step k0 + 16 are issued in front of the MFMAs of step k0.  No LDS, no scratch; 64-bit addressing.
-// Both kernels of this section live in namespace bnr_vcov, unlike every kernel above: tests/test_inclusion_host.py pins the set of global-scope
-// k_* kernels of this code object as it stood at ABI 15 and existing test files do not change, so a kernel added to this header since then
-// carries a namespace; tests/test_edge_cov_host.py pins where these two live by their qualified names.
-namespace bnr_vcov {
 template <int TW>
 __global__ __launch_bounds__(256) void k_cov(const double *const *rowsv, long long rowlen, int nsamp, const int *cols, const double *centre, int a0,
                                              int na, int b0, int nb, double *G, long long gstride, int ldg)
@@ -1260,4 +1256,3 @@ __global__ __launch_bounds__(256) void k_cov_finish(const double *G, long long g
     cov[(size_t)pa * (size_t)ncols + (size_t)pb] = v;
     cov[(size_t)pb * (size_t)ncols + (size_t)pa] = v;
 }
-}  // namespace bnr_vcov

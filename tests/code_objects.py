@@ -9,9 +9,31 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB = os.path.join(ROOT, "bayesiannetworkregression.jl_amd", "libbnr_hip.so")
 LLVM = "/opt/rocm/lib/llvm/bin"
 MAGIC = b"__CLANG_OFFLOAD_BUNDLE__"
-# the kernels of csrc/bnr_analysis_kernels.h, as c++filt prints them
-ANALYSIS = frozenset(("k_psis<0>", "k_psis<1>", "k_predict<2>", "k_predict<1>", "k_pred_loglik", "k_pred_pit", "k_pred_noise", "k_rank", "k_fold", "k_hdi",
-                      "k_psis_w<0>", "k_psis_w<1>", "k_inv_sd", "k_loo_moments", "k_loo_quantile"))
+CSRC = os.path.join(ROOT, "bayesiannetworkregression.jl_amd", "csrc")
+# The manifest: every kernel instantiation of the two code objects, as c++filt prints them -- csrc/bnr_kernels.h in the sweep's, csrc/bnr_analysis_kernels.h
+# in the analysis one.  test_host_cpu.py asserts both whole; a kernel added to either header is added here.
+SWEEP = frozenset((
+    "k_node<bnr_one>", "k_node<bnr_many>", "k_xpass<bnr_one>", "k_xpass<bnr_many>", "k_xpass_group", "k_xpass_group2<0>",
+    "k_gram<bnr_one, 2>", "k_gram<bnr_one, 4>", "k_gram<bnr_many, 2>", "k_gram<bnr_many, 4>", "k_gram8<bnr_one>", "k_gram8<bnr_many>",
+    "k_x_mask", "k_sdigits<bnr_one, 7>", "k_sdigits<bnr_one, 8>", "k_sdigits<bnr_many, 7>", "k_sdigits<bnr_many, 8>",
+    "k_gram_i8<bnr_one, 7>", "k_gram_i8<bnr_one, 8>", "k_gram_i8<bnr_many, 7>", "k_gram_i8<bnr_many, 8>", "k_gram_reduce<bnr_one>", "k_gram_reduce<bnr_many>",
+    "k_chol_step<bnr_one>", "k_chol_step<bnr_few>", "k_chol_step<bnr_many>", "k_chol_step2<bnr_one>", "k_chol_step2<bnr_many>",
+    "k_rhs<bnr_one>", "k_rhs<bnr_many>", "k_solve_w<bnr_one>", "k_solve_w<bnr_many>", "k_solve_a4<bnr_one>", "k_solve_a4<bnr_many>",
+    "k_backproj<bnr_one>", "k_backproj<bnr_many>", "k_backproj64<bnr_one>", "k_backproj64<bnr_many>",
+    "k_tail<bnr_one, true>", "k_tail<bnr_one, false>", "k_tail<bnr_many, true>", "k_tail<bnr_many, false>",
+    "k_advance", "k_scatter_plans", "k_nop", "k_gather_counters", "k_setbase", "k_init_prior",
+    "k_x_convert<double>", "k_x_convert<float>", "k_x_convert<int>", "k_x_convert<long>", "k_x_convert<unsigned char>", "k_fetch_cols", "k_load_cols",
+    "k_rhat_stats", "k_summary", "k_acov", "k_wsummary<10>", "k_wsummary<8>"))   # (trace statistics; the analysis launches them through csrc/bnr_internal.h)
+ANALYSIS = frozenset((
+    "k_predict<2>", "k_predict<1>", "k_pred_loglik", "k_pred_pit", "k_pred_noise", "k_psis<0>", "k_psis<1>",
+    "k_psis_w<0>", "k_psis_w<1>", "k_inv_sd", "k_loo_moments", "k_loo_quantile", "k_rank", "k_fold", "k_hdi",
+    "k_incl_pack", "k_incl_joint", "k_incl_group", "k_cov<2>", "k_cov<4>", "k_cov_finish"))
+
+
+def declared_kernels(header):
+    """the names of the __global__ functions that csrc/<header> declares"""
+    src = open(os.path.join(CSRC, header)).read()
+    return set(re.findall(r"__global__\s+(?:__launch_bounds__\([^)]*\)\s+)?void\s+(k_\w+)\s*\(", src))
 
 
 def have_tools():

@@ -413,6 +413,21 @@ def test_late_kernels_sit_behind_the_sweep_kernels_in_the_code_object(tmp_path):
     assert min(late.values()) > max(sweep.values()), (sorted(late.items(), key=lambda kv: kv[1])[:2], sorted(sweep.items(), key=lambda kv: -kv[1])[:2])
 
 
+def test_the_two_code_objects_hold_exactly_the_kernels_of_the_manifest(tmp_path):
+    """Which kernel lives where, whole: the sweep's code object holds exactly co.SWEEP and the analysis one exactly co.ANALYSIS, no kernel is in both, and
+    each object's kernels are the __global__ functions its header declares (csrc/bnr_kernels.h, csrc/bnr_analysis_kernels.h) -- so a kernel cannot enter the
+    sweep's object, whose speed depends on where its kernels lie, without this list saying so."""
+    if not (co.have_tools() and os.path.exists(co.LIB)):
+        pytest.skip("no ROCm LLVM tools / no built library here")
+    sweep, analysis = co.sweep_and_analysis(tmp_path)
+    assert set(sweep) == co.SWEEP, sorted(set(sweep) ^ co.SWEEP)
+    assert set(analysis) == co.ANALYSIS, sorted(set(analysis) ^ co.ANALYSIS)
+    assert not co.SWEEP & co.ANALYSIS, sorted(co.SWEEP & co.ANALYSIS)
+    for manifest, header in ((co.SWEEP, "bnr_kernels.h"), (co.ANALYSIS, "bnr_analysis_kernels.h")):
+        base = {re.sub(r"<.*", "", k) for k in manifest}
+        assert base == co.declared_kernels(header), (header, sorted(base ^ co.declared_kernels(header)))
+
+
 def test_pipe_lab_compiles_against_the_kernel_header(tmp_path):
     """tools/pipe_lab.hip times and host-checks bnr_panel_sweep_pipe straight out of csrc/bnr_kernels.h, so every change of that header can break it -- and did,
     unnoticed for three commits, when k_wsummary began to need bnr_internal.h in front of the header.  Device code only, for gfx950, with the flags of the build line

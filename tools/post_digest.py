@@ -1,6 +1,6 @@
 """SHA-256 of what the posterior-analysis entry points return on a few fixed inputs (the PSIS, rank, HDI, inclusion and weighted-quantile matrix
-calls on crafted and seeded rows; summary, predict in every input format, loglik_stats, loo, loo_predict, rank_diag, hdi, inclusion and ess_stats
-on a 3-chain group and on a lone chain, the chain stacking and the summaries under its weights on the group, with the default block sizes and
+calls on crafted and seeded rows; summary, predict in every input format, loglik_stats, loo, loo_predict, rank_diag, hdi, inclusion, ess_stats,
+rhat_stats and the split-Rhat over the chains on a 3-chain group and on a lone chain, the chain stacking and the summaries under its weights on the group, with the default block sizes and
 with small ones):
 run it with two builds of the library (BNR_HIP_LIB) and diff the output to see whether a change to that layer is bitwise neutral.  The companion of
 table_digest.py, which does the same for the sampled tables."""
@@ -122,6 +122,8 @@ def chain_cases(label, chains, Xn, yn):
                 show("%s stacked_predict %s %s" % (label, wl, name), _capi.stacked_predict(chains, w, X, NB + 1, NS, k_lo, k_hi, y=yn, pred_seed=PS))
     for k, ch in enumerate(chains):
         show("%s ess_stats chain %d" % (label, k + 1), [ch.ess_stats(NB + 1, NS, 20)])
+        show("%s rhat_stats chain %d" % (label, k + 1), [ch.rhat_stats(NB + 1, NS)])
+    show("%s rhat" % label, _capi.rhat(chains, len(chains), None, NB, NS))
 
 
 def main():
