@@ -187,10 +187,11 @@ def _run_case(n, V, R, Xkind, Skind, opts, group=False, seed=11):
         S *= 2.0 ** min(0, int(np.floor(np.log2(1e8 / max(1.0, Xm.norm_abs_gram_inf(S))))))
         t["S"][0, :, 0] = S
         ch.load(t, 1, 1)
-    if group:
-        mates = [bnr_amd.Chain.like(ch, seed, 2)]
-        mates[0].init_prior()
-        g = bnr_amd.Group([mates[0], ch])
+    if group:                           # True: two members; a count N: N members, the checked chain (id 1) the last of them
+        mates = [bnr_amd.Chain.like(ch, seed, c) for c in range(2, (2 if group is True else int(group)) + 1)]
+        for m in mates:
+            m.init_prior()
+        g = bnr_amd.Group(mates + [ch])
         for k, v in opts.items():
             if k != "gram_i8":
                 g.set_option(k, v)

@@ -474,3 +474,30 @@ def test_gram_k_split_keeps_every_k_group_inside_the_buffer_window():
             k1 = (k1 + 15) // 16 * 16
             assert (k1 // 2 + 80) * n_pad * 8 > 0x7FFFFFFF
     assert L.bnr_host_gram_plan(0, 5, 256, out) != 0
+
+
+def test_large_group_shapes_reach_their_branches_at_256_compute_units():
+    """tests/test_large_group_gpu.py restates the dispatch rules of launch_chol, launch_gram, launch_xpass and launch_backproj to know which kernel a
+    group of nine or more chains runs; here its expectations are evaluated for the MI355X's 256 compute units, and the restated K split is held
+    against the library's own (bnr_host_gram_plan).  Pure host arithmetic: no GPU."""
+    import ctypes as C
+    import test_large_group_gpu as lg
+    c = lg.expect_chol_one_panel(256)
+    assert "block" in c["n370"][2:] and "super" in c["n370"][2:]                                       # (a) both update forms at steps p >= 2
+    assert set(c["n100"][1:]) == {"block"}
+    assert max(c["spw_cap4"]) == 4                                                                     # (b)
+    assert c["freecu_17x470"] < 0 and all(v < 0 for v in lg.expect_chol_two_panel(256).values())       # (c)
+    x = lg.expect_xpass(256)
+    assert all(v[1] <= 64 and v[3] == 65 for v in x.values()) and [x[nb][4][-1] for nb in (9, 12, 16, 17)] == [1, 4, 8, 1]   # (d), the last batches
+    g = lg.expect_gram(256)
+    assert g[(470, 9)] == "k_gram<2>" and g[(470, 17)] == "k_gram8"                                    # (e)
+    b = lg.expect_backproj(256)
+    assert b[(45, 9)][0] == "k_backproj64" and {v[1] for v in b.values()} == {2, 8}                   # (f), both nslot values
+    out = (C.c_int32 * 4)()
+    for n, V in lg.GRAM_SHAPES:
+        assert bnr_amd.lib().bnr_host_gram_plan(n, V, 256, out) == 0 and out[0] == lg.gram_plan(9, n, V)["ksplit"]
+    # a group of eight still takes the by-value argument at p >= 2: nine is where the tested code begins
+    assert [s["arg"] for s in lg.chol_plan(8, 370, 4, 0)][:3] == ["bnr_many", "bnr_many", "bnr_few"]
+    # on a smaller card the expectations do not hold as they stand (the GPU tests skip there, for that reason alone)
+    with pytest.raises(AssertionError):
+        lg.expect_chol_one_panel(64)
