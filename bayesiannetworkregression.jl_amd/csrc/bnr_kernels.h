@@ -900,7 +900,7 @@ __global__ __launch_bounds__(KG * 256, 4 / KG) void k_gram(const SRC chain_src, 
 // instruction issued between f64 MFMAs takes 6-14 cycles from the matrix pipe, tools/mfma_f64_mix.hip; the pipe itself issues at the spec
 // rate of 64 cycles per MFMA from ONE wave -- the round-1 "issue rate grows with the waves per SIMD" was a microbenchmark artefact,
 // profiles/round5_mfma_f64_peak.txt).  Three 512-thread workgroups per CU = 6 waves per SIMD: __launch_bounds__(512, 6) -- the second
-// argument is the minimum number of WAVES PER SIMD, not of blocks per CU -- caps the kernel at 80 VGPRs (74 used, no spills), and
+// argument is the minimum number of WAVES PER SIMD, not of blocks per CU -- caps the kernel at 80 VGPRs (78 used, no spills), and
 // batches of 8 columns keep a workgroup at 32 KiB of LDS (half the staging registers and half the image of k_gram's 16:
 // 2 K-groups x 2 buffers x [I | J] x 8 x 64 doubles; a barrier per 8 MFMAs of a wave), with a K-group reduction that needs one tile
 // of LDS instead of two (K-group 1 parks its tile, K-group 0 adds its registers and stores).  Eight waves per SIMD (64 VGPRs through
@@ -931,81 +931,108 @@ __device__ __forceinline__ void bnr_gram8_task(const bnr_gram_geom &cd, const do
     const double *xb = bnr_sgpr_global(cd.X + (size_t)eb * ld);
     const double *sb = bnr_sgpr_global(Sp + eb);       // S is followed by q_pad - q + BNR_GRAM_PREFETCH_COLS zeros in every trace row (bnr_chain_create): no clamp; X is zero there
     constexpr int PANEL = KB * BNR_GT;                 // doubles per panel (8 columns x 64 rows)
-    double *stg = sred + (size_t)kg * (4 * PANEL);     // [buf][I|J][col][row ^ swizzle]
-    const int woff = c * BNR_GT + ((2 * rp) ^ ((c & 1) << 4));
+    // LDS image of a K-group: [buf][I|J][col][row ^ swizzle].  A lane's five positions in it (its staging slot, and rows ra0, ra1 of J and rb0, rb1 of I
+    // in column lk) are formed once, as LDS pointers, and made opaque: every LDS address of the loops is then one of these five registers + an
+    // immediate, in the trips and in the odd batch behind them alike (left to itself the compiler forms the addresses of the odd batch again from
+    // the row numbers, which then stay live across the loop -- three registers more than the 80 there are)
+    typedef __attribute__((address_space(3))) double lds_f64;
+    typedef __attribute__((address_space(3))) bnr_d2 lds_d2;
     const int sw = (lk & 1) << 4;
-    const int ra0 = (wj * 32 + li) ^ sw, ra1 = (wj * 32 + 16 + li) ^ sw, rb0 = (wi * 32 + li) ^ sw, rb1 = (wi * 32 + 16 + li) ^ sw;
+    lds_f64 *const stg = (lds_f64 *)sred + kg * (4 * PANEL);
+    lds_f64 *pw = stg + c * BNR_GT + ((2 * rp) ^ ((c & 1) << 4));
+    lds_f64 *pa0 = stg + PANEL + lk * BNR_GT + ((wj * 32 + li) ^ sw), *pa1 = stg + PANEL + lk * BNR_GT + ((wj * 32 + 16 + li) ^ sw);
+    lds_f64 *pb0 = stg + lk * BNR_GT + ((wi * 32 + li) ^ sw), *pb1 = stg + lk * BNR_GT + ((wi * 32 + 16 + li) ^ sw);
+    asm volatile("" : "+v"(pw), "+v"(pa0), "+v"(pa1), "+v"(pb0), "+v"(pb1));
     bnr_d4 c00 = {0, 0, 0, 0}, c01 = {0, 0, 0, 0}, c10 = {0, 0, 0, 0}, c11 = {0, 0, 0, 0};   // c[jt][it]
-    bnr_d2 ri, rj;
-    double sv;
+    // two staging register sets, the set of a batch = its parity: batch b + 2 is loaded at the TOP of batch b into the set that batch b's own
+    // columns left in the middle of batch b - 1, and goes to LDS between the two k-steps of batch b + 1.  A load therefore leads the store that
+    // consumes it by a batch and a half (12 MFMAs of a wave, 9 on a diagonal block), and the wait in front of the store is for batch b + 2 only,
+    // with batch b + 3 still in flight: never a wait for everything.  (With one set -- first k-step, store, load, second k-step -- the compiler
+    // gave the second half of its two-batch trip registers of the MFMA operands, sank those loads behind the half's last MFMA and opened the
+    // next trip with s_waitcnt vmcnt(0) right behind the barrier: tools/gram_loop_sched.py, profiles/gram_prefetch_distance.txt.)
+    bnr_d2 ri0, rj0, ri1, rj1;
+    double sv0, sv1;
     const __amdgpu_buffer_rsrc_t rX = bnr_rsrc(xb), rS = bnr_rsrc(sb);
     const int bstep = KB * (int)ld * 8;                // bytes per batch (scalar)
-#define BNR_G8_LOAD(BIDX)                                                                    \
+#define BNR_G8_LOAD(SET, BIDX)                                                               \
     do {                                                                                      \
-        sv = bnr_bufload_f64(rS, offS, (BIDX) * (KB * 8));                                    \
-        ri = bnr_bufload_d2(rX, offI, (BIDX) * bstep);                                        \
-        rj = bnr_bufload_d2(rX, offJ, (BIDX) * bstep);                                        \
+        sv##SET = bnr_bufload_f64(rS, offS, (BIDX) * (KB * 8));                               \
+        ri##SET = bnr_bufload_d2(rX, offI, (BIDX) * bstep);                                   \
+        rj##SET = bnr_bufload_d2(rX, offJ, (BIDX) * bstep);                                   \
     } while (0)
-#define BNR_G8_STORE(BUF)                                                                     \
+#define BNR_G8_STORE(SET, BUF)                                                                \
     do {                                                                                      \
-        double *nx_ = stg + (size_t)(BUF) * (2 * PANEL);                                      \
-        *(bnr_d2 *)(nx_ + woff) = ri * sv;                                                    \
-        *(bnr_d2 *)(nx_ + PANEL + woff) = rj;                                                 \
+        *(lds_d2 *)(pw + (BUF) * (2 * PANEL)) = ri##SET * sv##SET;                            \
+        *(lds_d2 *)(pw + (BUF) * (2 * PANEL) + PANEL) = rj##SET;                              \
     } while (0)
-#define BNR_G8_COMPUTE(BUF, K2, DIAG)                                                         \
+    // the fragments of both k-steps of a batch (the two columns of a lane, lk and lk + 4, come with one ds_read2st64_b64 per fragment row)
+#define BNR_G8_READ(BUF)                                                                      \
+    constexpr int o0_ = (BUF) * (2 * PANEL), o1_ = o0_ + 4 * BNR_GT;                          \
+    const double a00 = pa0[o0_], a01 = pa0[o1_], a10 = pa1[o0_], a11 = pa1[o1_];              \
+    const double b00 = pb0[o0_], b01 = pb0[o1_], b10 = pb1[o0_], b11 = pb1[o1_]
+#define BNR_G8_MFMA(K2, DIAG)                                                                 \
     do {                                                                                      \
-        const double *bufI = stg + (size_t)(BUF) * (2 * PANEL), *bufJ = bufI + PANEL;         \
-        const int kk = (4 * (K2) + lk) * BNR_GT;                                              \
-        double a0 = bufJ[kk + ra0], a1 = bufJ[kk + ra1];                                      \
-        double b0 = bufI[kk + rb0], b1 = bufI[kk + rb1];                                      \
-        c00 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, c00, 0, 0, 0);                     \
-        c01 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b1, c01, 0, 0, 0);                     \
-        if (!(DIAG)) c10 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b0, c10, 0, 0, 0);        \
-        c11 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, c11, 0, 0, 0);                     \
+        c00 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0##K2, b0##K2, c00, 0, 0, 0);             \
+        c01 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0##K2, b1##K2, c01, 0, 0, 0);             \
+        if (!(DIAG)) c10 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1##K2, b0##K2, c10, 0, 0, 0); \
+        c11 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1##K2, b1##K2, c11, 0, 0, 0);             \
     } while (0)
     // batches past the end of the slice read the following columns or the zero-padded tail of X (q_pad + BNR_GRAM_PREFETCH_COLS columns are
     // allocated); they are stored but never used by a compute step
-    BNR_G8_LOAD(0);
-    BNR_G8_STORE(0);
-    BNR_G8_LOAD(1);
+    BNR_G8_LOAD(0, 0);
+    BNR_G8_STORE(0, 0);
+    BNR_G8_LOAD(1, 1);
     __syncthreads();
 #ifdef BNR_STAMPS
     // both clocks around the K loop: shader cycles / 100 MHz ticks = the clock the PRODUCT kernel's loop runs at (tools/stamps_gram_clock.py)
     if (clk && tid == 0) { clk[0] = __builtin_amdgcn_s_memtime(); clk[1] = __builtin_amdgcn_s_memrealtime(); }
 #endif
-    // first k-step of batch b, then the staging of batch b + 1 (its buffer was released by the last barrier), then the second k-step;
-    // two batches per trip with the buffer parity a literal: every LDS address is "lane base + immediate"
-#define BNR_G8_BATCH_L(B, PAR, DIAG)                                                          \
+    // batch B of parity PAR: the loads of batch B + 2, the first k-step, the staging of batch B + 1 (its buffer was released by the last barrier),
+    // the second k-step.  Two batches per trip with the parity a literal: every LDS address is "lane base + immediate", the register sets have
+    // names.  The scheduling barriers keep the compiler from moving the loads down or the stores to a barrier's side (nothing crosses them).
+#define BNR_G8_BATCH_L(B, PAR, NPAR, DIAG)                                                    \
     do {                                                                                      \
-        BNR_G8_COMPUTE(PAR, 0, DIAG);                                                         \
-        BNR_G8_STORE((PAR) ^ 1);                                                              \
-        BNR_G8_LOAD((B) + 2);                                                                 \
-        BNR_G8_COMPUTE(PAR, 1, DIAG);                                                         \
+        BNR_G8_LOAD(PAR, (B) + 2);                                                            \
+        __builtin_amdgcn_sched_barrier(0);                                                    \
+        BNR_G8_READ(PAR);                                                                     \
+        BNR_G8_MFMA(0, DIAG);                                                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                    \
+        BNR_G8_STORE(NPAR, NPAR);                                                             \
+        __builtin_amdgcn_sched_barrier(0);                                                    \
+        BNR_G8_MFMA(1, DIAG);                                                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                    \
+        __syncthreads();                                                                      \
+    } while (0)
+#define BNR_G8_BATCH_DEAD(B, PAR, NPAR)                                                       \
+    do {                                                                                      \
+        BNR_G8_LOAD(PAR, (B) + 2);                                                            \
+        __builtin_amdgcn_sched_barrier(0);                                                    \
+        BNR_G8_STORE(NPAR, NPAR);                                                             \
         __syncthreads();                                                                      \
     } while (0)
     if (ti == tj && wi == 0 && wj == 1) {
         // dead block of a diagonal tile (see bnr_gram16_task): staging and barriers only, zeros out
         int b = 0;
-        for (; b + 1 < nbatch; b += 2) {
-            BNR_G8_STORE(1); BNR_G8_LOAD(b + 2); __syncthreads();
-            BNR_G8_STORE(0); BNR_G8_LOAD(b + 3); __syncthreads();
-        }
-        if (b < nbatch) { BNR_G8_STORE(1); BNR_G8_LOAD(b + 2); __syncthreads(); }
+        for (; b + 1 < nbatch; b += 2) { BNR_G8_BATCH_DEAD(b, 0, 1); BNR_G8_BATCH_DEAD(b + 1, 1, 0); }
+        if (b < nbatch) BNR_G8_BATCH_DEAD(b, 0, 1);
     } else if (ti == tj && wi == wj) {
         // a diagonal 32 x 32 block: three MFMAs per k-step (see bnr_gram16_task)
         int b = 0;
-        for (; b + 1 < nbatch; b += 2) { BNR_G8_BATCH_L(b, 0, true); BNR_G8_BATCH_L(b + 1, 1, true); }
-        if (b < nbatch) BNR_G8_BATCH_L(b, 0, true);
+        for (; b + 1 < nbatch; b += 2) { BNR_G8_BATCH_L(b, 0, 1, true); BNR_G8_BATCH_L(b + 1, 1, 0, true); }
+        if (b < nbatch) BNR_G8_BATCH_L(b, 0, 1, true);
     } else {
         int b = 0;
-        for (; b + 1 < nbatch; b += 2) { BNR_G8_BATCH_L(b, 0, false); BNR_G8_BATCH_L(b + 1, 1, false); }
-        if (b < nbatch) BNR_G8_BATCH_L(b, 0, false);
+        for (; b + 1 < nbatch; b += 2) { BNR_G8_BATCH_L(b, 0, 1, false); BNR_G8_BATCH_L(b + 1, 1, 0, false); }
+        if (b < nbatch) BNR_G8_BATCH_L(b, 0, 1, false);
     }
 #ifdef BNR_STAMPS
     if (clk && tid == 0) { clk[2] = __builtin_amdgcn_s_memtime(); clk[3] = __builtin_amdgcn_s_memrealtime(); }
 #endif
     // tile element (i,j) lives at [j*64 + i]; this lane: j = wj*32 + jt*16 + (lane>>4) + 4 r, i = wi*32 + it*16 + (lane&15)
-    const int jb = wj * 32 + (lane >> 4), ib = wi * 32 + (lane & 15);
+    // (formed from an opaque copy of the thread index: nothing of the epilogue's addressing is kept in registers across the loops)
+    int tid_e = tid;
+    asm volatile("" : "+v"(tid_e));
+    const int jb = ((tid_e >> 6) & 1) * 32 + ((tid_e & 63) >> 4), ib = ((tid_e >> 7) & 1) * 32 + (tid_e & 15);
     if (kg == 1) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
