@@ -684,6 +684,26 @@ static void launch_gram(bnr_exec &x, int s, hipStream_t st, bool timed)
     if (!reduce_in_chol(x)) BNR_LAUNCH(k_gram_reduce, dim3(ntl, 8, x.nb), dim3(256), 0, st, x, s);
 }
 static void launch_rhs(bnr_exec &x, int s) { BNR_LAUNCH(k_rhs, dim3(x.shape->n_pad / 64, 1, x.nb), dim3(256), 0, x.stream, x, s); }
+// Launch 0 of the one-panel factorization with the reduction inside: eighths of a partial tile per reduction workgroup of a group (bnr_reduce_parts; a chain alone
+// always runs one eighth each: 305 workgroups at the headline size, one round).  Every workgroup of the launch has the panel role's registers and LDS, four fit a
+// CU.  Four eighths each where the launch is then one round (the headline group: 136 panel + 576 reduction workgroups instead of 136 + 2 304), one each where
+// even that is not.
+// Measured, us per sweep at reduce_epw 1 / 2 / 4, two repeats each (tools/ab_opt.py, 1 500 sweeps; profiles/launch0_reduce.txt, section 3):
+//   n=500 V=100 R=7 (n_pad 512, K split 7)   x 16  603.2 603.4 / 604.5 604.6 / 604.3 604.5 (1 424 workgroups at 4: two rounds all the same)
+//                                             x 8   347.7 347.2 / 348.4 347.6 / 347.2 345.9     x 4  269.9 269.8 / 270.5 270.8 / 268.6 268.8
+//                                             x 2   202.8 203.3 / 203.4 204.1 / 202.3 202.9
+//   n=200 V=50 R=5 (n_pad 256)                x 8   115.9 115.8 / 116.1 116.2 / 115.0 115.6     x 4  109.8 109.1 / 109.4 109.6 / 107.6 108.1
+//                                             x 2   102.1 102.0 / 102.2 101.7 / 101.3 100.9
+//   n=100 V=50 R=5 (n_pad 128)                x 8   89.0 88.4 / 88.6 88.6 / 87.9 88.5           x 4  83.1 83.2 / 83.6 83.6 / 82.5 82.7
+//                                             x 2   81.1 80.5 / 80.3 80.0 / 79.9 80.2
+// Four wins or ties wherever it makes the launch one round, by 0.3 to 1.6 us; two never wins (kept as an option value only).  The differences are small against the
+// step from the parent (352.3 -> 347.4 at one eighth each already: every slice in flight, four workgroups per CU).  The x 16 point does not decide anything: 0.2 %
+// from two repeats is no measured difference -- launches of more than one round at four eighths simply keep one each, as before this rule existed.
+// (The round is counted with BNR_CHOL_WG_PER_CU, the number k_chol_step's launch bound and LDS are held to.)
+static int reduce_epw_default(const bnr_exec &x, int npan, int ntl)
+{
+    return (long)x.nb * (npan + 2 * ntl) <= (long)BNR_CHOL_WG_PER_CU * x.ncu ? 4 : 1;
+}
 static void launch_chol(bnr_exec &x, int s, hipStream_t st, int rec_p = -1, hipEvent_t rec_ev = nullptr)
 {
     const int nbk = x.shape->n_pad / BNR_NB;
@@ -717,8 +737,8 @@ static void launch_chol(bnr_exec &x, int s, hipStream_t st, int rec_p = -1, hipE
         const int npan = bnr_chol_npanel(nbk, p), ntile = bnr_chol_ntile(nbk, p);
         if (p == 0 && fuse0) {
             // launch 0: the first panel (its workgroups sum the partial tiles of column block 0 themselves) beside the reduction of all the other tiles
-            const int ntl = x.shape->ntile * (x.shape->ntile + 1) / 2;
-            BNR_LAUNCH(k_chol_step, dim3(x.nb, npan + 8 * ntl), dim3(256), 0, st, x, p, s, 1, 1, 1);
+            const int ntl = x.shape->ntile * (x.shape->ntile + 1) / 2, epw = x.nb == 1 ? 1 : x.reduce_epw ? x.reduce_epw : reduce_epw_default(x, npan, ntl);
+            BNR_LAUNCH(k_chol_step, dim3(x.nb, npan + (8 * ntl + epw - 1) / epw), dim3(256), 0, st, x, p, s, epw, 1, 1);
             BNR_CHOL_LAUNCHED();
             continue;
         }
@@ -1243,6 +1263,10 @@ static int exec_set_option(bnr_exec &x, const char *name, int64_t value)
     if (!strcmp(name, "fuse_reduce")) {
         if (value < -1 || value > 1) return fail(BNR_ERR_BAD_ARG, "fuse_reduce must be -1 (default: on), 0 or 1");
         x.fuse_reduce = (int)value; drop_graph(x); return BNR_OK;
+    }
+    if (!strcmp(name, "reduce_epw")) {
+        if (value != 0 && value != 1 && value != 2 && value != 4) return fail(BNR_ERR_BAD_ARG, "reduce_epw must be 0 (default: chosen per launch), 1, 2 or 4");
+        x.reduce_epw = (int)value; drop_graph(x); return BNR_OK;
     }
     if (!strcmp(name, "group_xpass")) {
         if (value < -1 || value > 1) return fail(BNR_ERR_BAD_ARG, "group_xpass must be -1 (default: on), 0 or 1");

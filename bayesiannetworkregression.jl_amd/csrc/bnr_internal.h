@@ -35,6 +35,7 @@ struct bnr_exec {
     int overlap = 1;
     int gram_variant = 0;                               // 0: chosen per launch; 8 / 16: k_gram8 / k_gram forced (tests, experiments)
     int fuse_reduce = -1;                               // -1 / 1: launch 0 of the one-panel factorization also sums the Gram's K-split partials (no k_gram_reduce launch); 0: separate pass
+    int reduce_epw = 0;                                 // eighths of a partial tile per reduction workgroup of that launch 0: 0 chosen per launch (reduce_epw_default); 1, 2, 4 forced (tests, measurements)
     int group_xpass = -1;                               // -1 / 1: a group whose members share X runs the X pass with one workgroup per chunk for all chains; 0: per chain
     bnr_plan_entry *gplan_pin = nullptr, *gplan_dev = nullptr;   // groups: the members' plans of a run call, staged for one copy
     int gplan_cap = 0;                                  // entries per member in there

@@ -58,12 +58,14 @@ __device__ __forceinline__ bnr_dev bnr_globalized(const bnr_dev *src)
 }
 struct bnr_one {
     bnr_dev d;
+    static constexpr bool whole = true, lone = true;     // whole: the chain's whole descriptor is at hand; lone: a launch of one chain
     __device__ __forceinline__ const bnr_dev &get() const { return d; }
     __device__ __forceinline__ const bnr_dev &get_x() const { return d; }
     __device__ __forceinline__ const bnr_dev &at(int) const { return d; }
 };
 struct bnr_many {
     const bnr_dev *p;
+    static constexpr bool whole = true, lone = false;
     __device__ __forceinline__ bnr_dev get() const { return bnr_globalized(p + blockIdx.z); }
     __device__ __forceinline__ bnr_dev get_x() const { return bnr_globalized(p + blockIdx.x); }
     __device__ __forceinline__ bnr_dev at(int c) const { return bnr_globalized(p + c); }
@@ -77,6 +79,7 @@ struct bnr_few {
     long long *counters[8];
     unsigned long long *dbg[8];
     int n_pad;
+    static constexpr bool whole = false, lone = false;
     __device__ __forceinline__ bnr_dev get_x() const
     {
         bnr_dev d{};
@@ -1603,42 +1606,83 @@ __device__ __forceinline__ void bnr_gsum_frag(const bnr_dev &cd, int rho, int c,
                 for (int r = 0; r < 4; ++r) if (16 * (bt0 + bt) + ln == 16 * (at0 + at) + lq + 4 * r) out[at][bt][r] += 1.0;
     }
 }
-// One k_gram_reduce workgroup's work (tile t, eighth `part`) done by a workgroup of launch 0 of the factorization (fuse0): the same sums
-// in the same order, the same Y = I share and stamp -- except what launch 0's own panel workgroups produce at the same time: the
-// first 32 columns of E's matrix part (they read the partial tiles themselves and write the swept blocks) and the block Y[0:32, 0:32].
-__device__ __forceinline__ void bnr_reduce_part(const bnr_dev &cd, int t, int part, int nwg, int wg, int s)
+// The work of EPW k_gram_reduce workgroups (tile t, the eighths part0 .. part0 + EPW - 1; g0 = 8 t + part0, EPW divides 8) done by ONE workgroup of launch 0 of the
+// factorization (fuse0): the same sums in the same order, a share of Y = I and the same stamp words -- except what launch 0's own panel workgroups produce at the
+// same time: the first 32 columns of E's matrix part (they read the partial tiles themselves and write the swept blocks) and the block Y[0:32, 0:32].
+// The launch is a chain of round trips per workgroup, not a stream (profiles/launch0_reduce.txt): every workgroup carries the panel role's registers and LDS, so four
+// of them share a CU.  Hence fewer, fatter workgroups, and nothing that does not depend on the partial tiles waits for them: a thread issues the loads of all its
+// slices -- EPW eighths x KB slices of 16 bytes, at most 16 in flight = 64 VGPRs, well inside the panel role's count -- then its Y = I stores and the gprog reset,
+// and only then waits and adds, every element in ascending ks from +0.0 (k_gram_reduce's order), K splits above KB in batches of KB (8; 4 with four eighths, for the
+// 64 VGPRs).
+template <int EPW>
+__device__ __forceinline__ void bnr_reduce_parts(const bnr_dev &cd, int g0, int nwg, int wg, int s)
 {
+    constexpr int KB = EPW == 4 ? 4 : 8;
+    const int tid = threadIdx.x, t = g0 >> 3, part0 = g0 & 7;
+    const int ntl = cd.ntile * (cd.ntile + 1) / 2, ksplit = cd.ksplit;
+    const size_t ld = (size_t)2 * cd.n_pad + BNR_NB, tsz = BNR_GT * BNR_GT, plane = (size_t)ntl * tsz;
+    const double *src = cd.Gpart + (size_t)t * tsz + part0 * 512 + 2 * tid;
+    bnr_d2 v[KB][EPW], acc[EPW];
+    // the stamp's iteration number is two dependent loads: the first goes out in front of the slice loads (volatile: it stays there), the second behind them, once
+    // the first is back -- loads return in order, so neither waits for a slice nor holds the stamp up at the end.  Nothing but the compiler's present scheduling
+    // holds that order and no test can see it: written as one expression behind the slice loads both round trips sat in front of the Y stores again
+    // (profiles/launch0_reduce.txt, 6c).  After a compiler change look at the role's disassembly, or at slot 7 of step 0 in a -DBNR_STAMPS build.
+    const int pb = *(const volatile int *)cd.pbase;
+    // (ks < ksplit is wave-uniform: scalar branches round the loads, which stay in flight across them)
+#define BNR_RP_LOAD(KS0)                                                                                                          \
+    _Pragma("unroll") for (int u = 0; u < KB; ++u) {                                                                              \
+        _Pragma("unroll") for (int e = 0; e < EPW; ++e) v[u][e] = bnr_d2{0.0, 0.0};                                               \
+        if ((KS0) + u < ksplit) {                                                                                                 \
+            _Pragma("unroll") for (int e = 0; e < EPW; ++e) v[u][e] = *(const bnr_d2 *)(src + (size_t)((KS0) + u) * plane + e * 512); \
+        }                                                                                                                         \
+    }
+    BNR_RP_LOAD(0)
+    const unsigned int it = cd.plan[pb + s].it;
+    const int np = cd.n_pad;
+    for (size_t e = ((size_t)wg * 256 + tid) * 2; e < (size_t)np * np; e += (size_t)nwg * 512) {
+        const int r = (int)(e % np), c = (int)(e / np);
+        if ((r < BNR_NB && c < BNR_NB) || r / BNR_NB > c / BNR_NB) continue;   // (below the diagonal block Y is never written and never read)
+        bnr_d2 y = {(r == c) ? 1.0 : 0.0, (r + 1 == c) ? 1.0 : 0.0};
+        *(bnr_d2 *)(cd.E + (size_t)(np + r) + ld * c) = y;
+    }
+    if (wg == 0 && tid <= cd.ntile) cd.gprog[tid] = 0u;
+#pragma unroll
+    for (int e = 0; e < EPW; ++e) acc[e] = bnr_d2{0.0, 0.0};
+    for (int ks0 = 0;;) {
+#pragma unroll
+        for (int u = 0; u < KB; ++u)
+            if (ks0 + u < ksplit) {
+#pragma unroll
+                for (int e = 0; e < EPW; ++e) acc[e] += v[u][e];
+            }
+        ks0 += KB;
+        if (ks0 >= ksplit) break;
+        BNR_RP_LOAD(ks0)
+    }
+#undef BNR_RP_LOAD
     int ti = 0;
     while ((ti + 1) * (ti + 2) / 2 <= t) ++ti;
     const int tj = t - ti * (ti + 1) / 2;
-    const int ntl = cd.ntile * (cd.ntile + 1) / 2;
-    const size_t ld = (size_t)2 * cd.n_pad + BNR_NB, tsz = BNR_GT * BNR_GT;
-    const int idx = part * 512 + 2 * threadIdx.x;
-    const double *src = cd.Gpart + (size_t)t * tsz + idx;
-    bnr_d2 acc = {0.0, 0.0};
-    int ks = 0;
-    for (; ks + 3 < cd.ksplit; ks += 4) {
-        bnr_d2 v0 = *(const bnr_d2 *)(src + (size_t)ks * ntl * tsz), v1 = *(const bnr_d2 *)(src + (size_t)(ks + 1) * ntl * tsz);
-        bnr_d2 v2 = *(const bnr_d2 *)(src + (size_t)(ks + 2) * ntl * tsz), v3 = *(const bnr_d2 *)(src + (size_t)(ks + 3) * ntl * tsz);
-        acc += v0; acc += v1; acc += v2; acc += v3;
+#pragma unroll
+    for (int e = 0; e < EPW; ++e) {
+        const int idx = (part0 + e) * 512 + 2 * tid;
+        const int i = ti * BNR_GT + idx % BNR_GT, j = tj * BNR_GT + idx / BNR_GT;
+        if (i == j) acc[e][0] += 1.0;
+        if (i + 1 == j) acc[e][1] += 1.0;
+        if (j >= BNR_NB) *(bnr_d2 *)(cd.E + (size_t)i + ld * j) = acc[e];
     }
-    for (; ks < cd.ksplit; ++ks) acc += *(const bnr_d2 *)(src + (size_t)ks * ntl * tsz);
-    const int i = ti * BNR_GT + idx % BNR_GT, j = tj * BNR_GT + idx / BNR_GT;
-    if (i == j) acc[0] += 1.0;
-    if (i + 1 == j) acc[1] += 1.0;
-    if (j >= BNR_NB) *(bnr_d2 *)(cd.E + (size_t)i + ld * j) = acc;
-    const int np = cd.n_pad;
-    for (size_t e = ((size_t)wg * 256 + threadIdx.x) * 2; e < (size_t)np * np; e += (size_t)nwg * 512) {
-        const int r = (int)(e % np), c = (int)(e / np);
-        if ((r < BNR_NB && c < BNR_NB) || r / BNR_NB > c / BNR_NB) continue;   // (below the diagonal block Y is never written and never read)
-        bnr_d2 v = {(r == c) ? 1.0 : 0.0, (r + 1 == c) ? 1.0 : 0.0};
-        *(bnr_d2 *)(cd.E + (size_t)(np + r) + ld * c) = v;
-    }
-    if (threadIdx.x == 0) cd.stamp[t * 8 + part] = cd.plan[cd.pbase[0] + s].it;
-    if (wg == 0 && (int)threadIdx.x <= cd.ntile) cd.gprog[threadIdx.x] = 0u;
+    if (tid < EPW) cd.stamp[g0 + tid] = it;                  // one word per eighth, as k_gram_reduce writes them
+#ifdef BNR_STAMPS
+    if (tid == 0) atomicMax((unsigned long long *)&cd.dbg[7], (unsigned long long)__builtin_amdgcn_s_memrealtime());     // slot 7 of step 0: the latest reduction workgroup's end
+#endif
 }
+// (__launch_bounds__(256, BNR_CHOL_WG_PER_CU): four waves per SIMD, i.e. at most 128 VGPRs.  Without it bnr_one takes 126 and bnr_many 128, but bnr_few took 130 once the
+// reduction role changed, against 128 before -- three waves per SIMD instead of four at every step p >= 2 of a group.  With it all three take 126, no scratch.)
+// BNR_CHOL_WG_PER_CU: workgroups of k_chol_step (four waves, one per SIMD) that share a CU.  The launch bound holds the registers to it, the static assertion in
+// the kernel the LDS (160 KiB per CU); the host's choice for launch 0 (reduce_epw_default) counts a round of workgroups with the same number.
+#define BNR_CHOL_WG_PER_CU 4
 template <class SRC>
-__global__ __launch_bounds__(256, 1) void k_chol_step(const SRC chain_src, int p, int s, int tpw, int spw, int fuse0)
+__global__ __launch_bounds__(256, BNR_CHOL_WG_PER_CU) void k_chol_step(const SRC chain_src, int p, int s, int tpw, int spw, int fuse0)
 {
     BNR_CRITICAL_PATH();
 #ifdef BNR_STAMPS
@@ -1647,6 +1691,7 @@ __global__ __launch_bounds__(256, 1) void k_chol_step(const SRC chain_src, int p
     const bnr_dev &cd = chain_src.get_x();               // grid = (chains, workgroups): blockIdx.x = chain, blockIdx.y = workgroup
     __shared__ bnr_panelp_lds sh;
     static_assert(sizeof(sh.sL) == 2 * BNR_NB * BNR_NB * sizeof(double), "the two fetched blocks of panel p - 1 live where the sweep's published columns will be");
+    static_assert(BNR_CHOL_WG_PER_CU * sizeof(bnr_panelp_lds) <= 160 * 1024, "BNR_CHOL_WG_PER_CU workgroups must fit a CU's LDS");
     double (*sPO)[BNR_NB * BNR_NB] = (double (*)[BNR_NB * BNR_NB])&sh.sL[0][0];   // (no LDS of their own: the update workgroups of the launch carry the same static allocation)
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, nbk = cd.n_pad / BNR_NB;
     const size_t ld = bnr_ldE(cd.n_pad);
@@ -1655,10 +1700,13 @@ __global__ __launch_bounds__(256, 1) void k_chol_step(const SRC chain_src, int p
     const int mt = wave >> 1, nt = wave & 1;               // this wave's 16x16 tile of a 32x32 block: columns mt, rows nt
     const int ln = lane & 15, lq = lane >> 4;
     double *E = cd.E;
-    if (p == 0 && (int)blockIdx.y >= npanel) {
+    if (SRC::whole && p == 0 && (int)blockIdx.y >= npanel) {               // (bnr_few: steps p >= 2 only, and no Gram in its descriptor)
         // ------------------------------------------------ launch 0 with fuse0: the reduction of the Gram's K-split partial tiles, beside the first panel
-        const int wg = (int)blockIdx.y - npanel;
-        bnr_reduce_part(cd, wg >> 3, wg & 7, (int)gridDim.y - npanel, wg, s);
+        // (tpw = the eighths of a tile per workgroup: 1, 2 or 4, the host's choice per launch)
+        const int wg = (int)blockIdx.y - npanel, nwg = (int)gridDim.y - npanel;
+        if (SRC::lone || tpw == 1) bnr_reduce_parts<1>(cd, wg, nwg, wg, s);      // (a chain alone: one eighth each whatever tpw says -- only that copy is compiled into its kernel)
+        else if (tpw == 4) bnr_reduce_parts<4>(cd, 4 * wg, nwg, wg, s);
+        else bnr_reduce_parts<2>(cd, 2 * wg, nwg, wg, s);
         return;
     }
     if ((int)blockIdx.y >= npanel) {

@@ -533,6 +533,9 @@ int bnr_debug_set_exp(int32_t device, int32_t flags);
  *               chain k_chol_small -- experiments of rounds 3-4, removed in round 5 and refused)
  *   "fuse_reduce" 1 / -1 (default): launch 0 of the one-panel factorization also sums the Gram's K-split partial tiles (no k_gram_reduce
  *               launch); 0: separate reduction pass
+ *   "reduce_epw" 0 (default): how many eighths of a partial tile a reduction workgroup of that launch 0 sums is chosen per launch (4 where the launch is then one
+ *               round of workgroups, else 1); 1, 2, 4 force it for a lockstep group (a chain alone always runs 1).  The same sums in the same order: bitwise
+ *               the same tables.
  *   "group_xpass" -1 (default): a lockstep group whose members share the device copy of X (bnr_chain_create_like) runs ONE X pass
  *               for all members (k_xpass_group) when X has 8 MB or more per chain; 1: always; 0: one pass per member
  *   "split_sums" -1 (default): a chain run alone computes the back-projection's partial sums (update_theta!, update_Lambda!) in a launch of
