@@ -7,7 +7,7 @@ import os
 
 import numpy as np
 
-from ._build import LIB
+from ._build import LIB, MLOO_LIB
 
 BNR_OK, BNR_ERR_BAD_ARG, BNR_ERR_HIP, BNR_ERR_CHOLESKY, BNR_ERR_SAMPLER = 0, 1, 2, 3, 4
 BNR_ERR_SAMPLER_CAP = BNR_ERR_SAMPLER
@@ -30,8 +30,16 @@ ALLGATHER_CB = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_double), C.POINTER
 
 class UniqueId(C.Structure):
     _fields_ = [("bytes", C.c_char * 128)]
+
+
+class ChainView(C.Structure):
+    """bnr_chain_view of include/bnr_hip.h: the device side of a chain, for a companion library"""
+    _fields_ = ([(k, C.c_int32) for k in ("device", "n", "n_pad", "V", "R", "q", "q_pad", "tot", "rowlen", "o_tau2", "o_mu", "o_lam", "o_u", "o_gamma",
+                                          "o_S", "ldx")]
+                + [(k, C.c_void_p) for k in ("X", "y", "ek", "el", "trace")])
 _dp = C.c_void_p
 _lib = None
+_mloo = None
 
 _SIGS = {
     "bnr_abi_version": (C.c_int, []),
@@ -106,6 +114,8 @@ _SIGS = {
     "bnr_chain_cov": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
     "bnr_chains_cov": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
     "bnr_cov": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp]),
+    "bnr_chain_device_view": (C.c_int, [C.c_void_p, C.POINTER(ChainView)]),
+    "bnr_set_last_error": (C.c_int, [C.c_int, C.c_char_p]),
     "bnr_comm_unique_id": (C.c_int, [C.POINTER(UniqueId)]),
     "bnr_comm_create_rccl": (C.c_int, [C.POINTER(UniqueId), C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "bnr_comm_create_callback": (C.c_int, [C.c_int32, C.c_int32, ALLGATHER_CB, C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -140,6 +150,16 @@ for _u in ("tau2", "u_xi", "gamma", "D", "theta", "Delta", "M", "mu", "Lambda", 
     _SIGS["bnr_update_" + _u] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int64])
 
 EXPORTS = sorted(_SIGS)
+
+# libbnr_mloo.so (include/bnr_mloo.h): marginal PSIS-LOO, a library of its own beside libbnr_hip.so
+_MLOO_SIGS = {
+    "bnr_mloo_abi_version": (C.c_int, []),
+    "bnr_marginal_loglik": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 10 + [C.POINTER(C.c_int32)]),
+    "bnr_chains_marginal_loo": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 7 + [C.POINTER(C.c_int32)]),
+    "bnr_mloo_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
+}
+MLOO_EXPORTS = sorted(_MLOO_SIGS)
+MLOO_MAX_N = 2048
 
 
 _foreign_hip = None      # set by lib(): why chains must not be created in this process (GPU-free entry points stay usable)
@@ -185,6 +205,29 @@ def lib():
             f.argtypes = args
         _lib = L
     return _lib
+
+
+def mloo_lib():
+    """Load libbnr_mloo.so, after libbnr_hip.so (which it is linked against); raises if it has not been built"""
+    global _mloo
+    if _mloo is None:
+        lib()
+        if not os.path.exists(MLOO_LIB):
+            raise ImportError("libbnr_mloo.so is missing at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'`; there is no "
+                              "CPU fallback" % MLOO_LIB)
+        L = C.CDLL(MLOO_LIB)
+        for name, (res, args) in _MLOO_SIGS.items():
+            f = getattr(L, name)
+            f.restype = res
+            f.argtypes = args
+        _mloo = L
+    return _mloo
+
+
+def _device_mloo():
+    """mloo_lib() for the calls that open a device, refused like _device_lib()"""
+    _device_lib()
+    return mloo_lib()
 
 
 def _device_lib():
@@ -562,6 +605,7 @@ class Chain:
         if yf.shape != (n,):
             raise ValueError("y must have one entry per row of X")
         self.n, self.q, self.V, self.R, self.tot = n, q, V, int(R), int(tot_save)
+        self.y = yf.copy()                                  # (the training responses, for the totals of the LOO calls)
         self.h = C.c_void_p()
         hy = Hyper(eta, zeta, iota, aDelta, bDelta, float(nu))
         self.L = _device_lib()
@@ -582,6 +626,7 @@ class Chain:
         """Another chain of the same fit (same X, y, hyper-parameters and xi_weights; device inputs shared with `donor`)."""
         self = cls.__new__(cls)
         self.n, self.q, self.V, self.R = donor.n, donor.q, donor.V, donor.R
+        self.y = donor.y
         self.tot = int(donor.tot if tot_save is None else tot_save)
         self.h = C.c_void_p()
         self.L = donor.L
@@ -722,6 +767,12 @@ class Chain:
         """(mean, cov) of this chain's edge coefficients over its window, on the device (bnr_chain_cov): the columns `cols` (0-based edge
         indices; None: all q), cov = numpy's cov of the draws about the Summary mean"""
         return _cov("bnr_chain_cov", (self.h,), self, first_row, nsamp, cols)
+
+    def device_view(self):
+        """bnr_chain_device_view: the sizes, row offsets and device pointers of this chain as a ChainView"""
+        v = ChainView()
+        check(self.L.bnr_chain_device_view(self.h, C.byref(v)))
+        return v
 
     def counters(self):
         out = (C.c_int64 * 8)()
@@ -972,6 +1023,67 @@ def cov_raw(x, nchains=1, weights=None, device=0):
     mean, cov = np.empty(m), np.empty((m, m))
     check(_device_lib().bnr_cov(int(device), K, S // K, m, _ptr(a), _ptr(w), _ptr(mean), _ptr(cov)))
     return mean, cov
+
+
+# ------------------------------------------------------------------------------------------ marginal PSIS-LOO (libbnr_mloo.so, include/bnr_mloo.h)
+MLOO_FIELDS = ("loglik", "resid", "var", "logml")
+
+
+def mloo_set_option(name, value):
+    check(mloo_lib().bnr_mloo_set_option(name.encode(), int(value)))
+
+
+def marginal_loglik_raw(X, y, tau2, mu, S, W=None, device=0, fields=MLOO_FIELDS):
+    """(loglik, resid, var (n x D each), logml (D,), n_bad) of D draws phi = (tau2, mu, S, W) for one n x q model matrix, the edge coefficients
+    integrated out, on the device (bnr_marginal_loglik); an entry not named in `fields` is not requested and comes back as None.  ValueError
+    (before any library call) for shapes that do not fit, n > 2048 or no matrix asked for"""
+    Xf = np.asfortranarray(X, dtype=np.float64)
+    if Xf.ndim != 2 or Xf.shape[0] < 1 or Xf.shape[1] < 1:
+        raise ValueError("X must be an n x q matrix with n, q >= 1")
+    n, q = Xf.shape
+    if n > MLOO_MAX_N:
+        raise ValueError("n = %d: more than %d rows are not supported by this version" % (n, MLOO_MAX_N))
+    yf = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+    t2 = np.ascontiguousarray(np.atleast_1d(np.asarray(tau2, dtype=np.float64))).reshape(-1)
+    D = t2.size
+    m = np.ascontiguousarray(np.atleast_1d(np.asarray(mu, dtype=np.float64))).reshape(-1)
+    Sf = np.ascontiguousarray(np.asarray(S, dtype=np.float64).reshape(-1, q))
+    Wf = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1, q))
+    if yf.shape != (n,) or D < 1 or m.shape != (D,) or Sf.shape != (D, q) or (Wf is not None and Wf.shape != (D, q)):
+        raise ValueError("need y (n,), tau2 and mu (D,), S and W (D, q) for X (n, q)")
+    fields = tuple(fields)
+    if [f for f in fields if f not in MLOO_FIELDS] or not set(fields) & {"loglik", "resid", "var"}:
+        raise ValueError("fields must name loglik, resid or var (and logml), not %r" % (fields,))
+    out = [np.empty((n, D)) if f in fields else None for f in MLOO_FIELDS[:3]] + [np.empty(D) if "logml" in fields else None]
+    nb = C.c_int32(0)
+    check(_device_mloo().bnr_marginal_loglik(int(device), n, q, D, _ptr(Xf), _ptr(yf), _ptr(t2), _ptr(m), _ptr(Sf), _ptr(Wf), *[_ptr(o) for o in out],
+                                             C.byref(nb)))
+    return tuple(out) + (nb.value,)
+
+
+def mloo_thin_draws(nsamp, thin):
+    """(thin, the draws per chain ceil(nsamp / thin)) of a marginal LOO call; ValueError unless thin >= 1 and nsamp >= 1"""
+    nsamp, thin = int(nsamp), int(thin)
+    if thin < 1 or nsamp < 1:
+        raise ValueError("need thin >= 1 and nsamp >= 1, not thin = %d, nsamp = %d" % (thin, nsamp))
+    return thin, (nsamp + thin - 1) // thin
+
+
+def chains_marginal_loo(chains, first_row, nsamp, thin=1, r_eff=None, loglik=False):
+    """(elpd_loo, pareto_k, loo_mean, loo_sd (n,), logml (K draws,), loglik (n, K draws) or None, n_bad) over rows first_row + j thin of every
+    chain listed (bnr_chains_marginal_loo)"""
+    c0, (arr, K) = _pooled(chains)
+    thin, nd = mloo_thin_draws(nsamp, thin)
+    if c0.n > MLOO_MAX_N:
+        raise ValueError("n = %d: more than %d rows are not supported by this version" % (c0.n, MLOO_MAX_N))
+    n, D = c0.n, K * nd
+    r = r_eff_array(r_eff, n)
+    el, kh, lm, ls, ml = np.empty(n), np.empty(n), np.empty(n), np.empty(n), np.empty(D)
+    ll = np.empty((n, D)) if loglik else None
+    nb = C.c_int32(0)
+    check(_device_mloo().bnr_chains_marginal_loo(arr, K, int(first_row), int(nsamp), thin, _ptr(r), _ptr(el), _ptr(kh), _ptr(lm), _ptr(ls), _ptr(ml),
+                                                 _ptr(ll), C.byref(nb)))
+    return el, kh, lm, ls, ml, ll, nb.value
 
 
 class Comm:

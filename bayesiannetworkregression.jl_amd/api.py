@@ -27,6 +27,8 @@ Julia is not available in this image, so the thin host layer a Julia user would 
                                                chain stacking for chains that do not mix: Stacking / ChainStacking, stacking_weights,
                                                wquantile, device_stack_chains, device_summary_stacked, device_predict_stacked, _host_*
                                                posterior covariance of the edge coefficients: EdgeCov, cov, device_edge_cov, _host_edge_cov
+                                               marginal PSIS-LOO (edge coefficients integrated out): MarginalLOO, marginal_loglik,
+                                               device_marginal_loo, _host_marginal_loglik
   lower_triangle / create_lower_tri / setup_X!  utils.jl:17-57, gibbs.jl:239-247
 
 All sampling runs on the GPU through libbnr_hip.so; this file holds only the schedule logic (chain fan-out,
@@ -109,6 +111,7 @@ class Results:
     node_sets: "NodeSets" = None     # filled on request (node_sets=True): co-inclusion, model size, the most probable node sets and the active dimensions over every chain (see NodeSets)
     stacking: "ChainStacking" = None   # filled on request (stack_chains=True): every chain's own PSIS-LOO, the stacking weights of the chains and the summaries under them (see Stacking)
     edge_cov: "EdgeCov" = None       # filled on request (edge_cov=...): the posterior covariance matrix of the edge coefficients over every chain (see EdgeCov)
+    marginal_loo: dict = None        # filled on request (marginal_loo=True): PSIS-LOO with the edge coefficients integrated out, computed on the GPU (see MarginalLOO)
     stat_chains: int = None          # how many chains the device statistics above (summary_device, prediction, waic, loo, loo_predictive) cover: 1 (chain 1's window), or
                                      # every chain of the fit with pool_chains=True; None when the fit computed none
 
@@ -1716,6 +1719,172 @@ def _edge_cov_of(results):
     return _host_edge_cov([results.state], results.burn_in, results.sampled)
 
 
+# ------------------------------------------------------------------------------------------ marginal PSIS-LOO (an addition to the reference)
+# PSIS-LOO with the edge coefficients integrated out (integrated importance sampling: Vehtari, Mononen, Tolvanen, Sivula & Winther 2016, JMLR 17;
+# include/bnr_mloo.h, libbnr_mloo.so; DESIGN.md section 8, "Marginal PSIS-LOO").  Given phi = (tau2, mu, u, lambda, S) of a table row,
+# y | phi ~ N(mu + X W, tau2 A) with A = I + X diag(S) X^T and W_e = sum_t lambda_t u_{t,k(e)} u_{t,l(e)}; the importance ratios
+# 1 / p(y_i | y_-i, phi) have far thinner tails than the conditional ones of LOO, which condition on all q edge coefficients.  The _host_*
+# functions restate the definitions in numpy: the fallback of MarginalLOO and the yardstick of the tests.
+MLOO_MAX_N = _capi.MLOO_MAX_N
+
+
+def _solve_lower(L, b):
+    """L^-1 b for a lower triangular L: scipy's triangular solve where scipy is there, numpy's general solve otherwise"""
+    try:
+        from scipy.linalg import solve_triangular
+    except ImportError:
+        return np.linalg.solve(L, b)
+    return solve_triangular(L, b, lower=True, check_finite=False)
+
+
+def _host_marginal_terms(X, y, tau2, mu, S, W=None):
+    """(loglik, resid, var (n x D), logml (D,), n_bad) of D draws for one n x q matrix X: the definitions of include/bnr_mloo.h in numpy, per draw
+    np.linalg.cholesky of A = I + X diag(S) X^T, L^-1 by a triangular solve (its column norms give c), z = L^-1 r and g = L^-T z.  A draw whose
+    S, tau2 or mu is not finite or whose A is not positive definite is NaN and counted"""
+    X = np.asarray(X, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    n, q = X.shape
+    tau2, mu = np.atleast_1d(np.asarray(tau2, dtype=np.float64)), np.atleast_1d(np.asarray(mu, dtype=np.float64))
+    D = tau2.size
+    S = np.asarray(S, dtype=np.float64).reshape(D, q)
+    W = None if W is None else np.asarray(W, dtype=np.float64).reshape(D, q)
+    ll, rs, vr, ml = np.full((n, D), np.nan), np.full((n, D), np.nan), np.full((n, D), np.nan), np.full(D, np.nan)
+    n_bad = 0
+    eye = np.eye(n)
+    for s in range(D):
+        ok = np.isfinite(tau2[s]) and np.isfinite(mu[s]) and np.all(np.isfinite(S[s]))
+        L = None
+        if ok:
+            try:
+                L = np.linalg.cholesky(eye + (X * S[s][None, :]) @ X.T)
+            except np.linalg.LinAlgError:
+                L = None
+            if L is not None and not np.all(np.isfinite(L)):
+                L = None
+        if L is None:
+            n_bad += 1
+            continue
+        r = y - mu[s] - (X @ W[s] if W is not None else 0.0)
+        Li = _solve_lower(L, eye)
+        c = np.sum(Li * Li, axis=0)
+        z = _solve_lower(L, r)
+        g = _solve_lower(L[::-1, ::-1].T, z[::-1])[::-1]       # L^T g = z, as a lower triangular solve of the reversed system
+        rs[:, s] = g / c
+        vr[:, s] = tau2[s] / c
+        ll[:, s] = -0.5 * (math.log(2 * math.pi) + np.log(vr[:, s])) - 0.5 * rs[:, s] ** 2 / vr[:, s]
+        ml[s] = -0.5 * n * math.log(2 * math.pi * tau2[s]) - np.sum(np.log(np.diag(L))) - 0.5 * float(z @ z) / tau2[s]
+    return ll, rs, vr, ml, n_bad
+
+
+def _edge_nodes_all(V):
+    """(ek, el): the column node and the row node (l >= k) of every edge in the column-wise lower-triangle order of utils.jl:50-55"""
+    ek = np.concatenate([np.full(V - k, k) for k in range(V)])
+    el = np.concatenate([np.arange(k, V) for k in range(V)])
+    return ek, el
+
+
+def _host_marginal_draws(states, nburn, nsamp, thin):
+    """(tau2, mu (D,), S, W (D, q)) of rows nburn + 1 + j thin, j = 0 .. ceil(nsamp / thin) - 1, of every fetched table in order: W_e =
+    sum_t u_{t,l(e)} lambda_t u_{t,k(e)}, t ascending, from u and lambda of the same row"""
+    thin, nd = _capi.mloo_thin_draws(nsamp, thin)
+    t2, mu, S, W = [], [], [], []
+    for st in states:
+        rows = nburn + thin * np.arange(nd)
+        u, lam = st["u"][rows], st["lam"][rows, :, 0]            # (nd, R, V), (nd, R)
+        ek, el = _edge_nodes_all(u.shape[2])
+        w = np.zeros((nd, ek.size))
+        for t in range(u.shape[1]):
+            w = w + u[:, t, :][:, el] * lam[:, t][:, None] * u[:, t, :][:, ek]
+        t2.append(st["tau2"][rows, 0, 0]); mu.append(st["mu"][rows, 0, 0]); S.append(st["S"][rows, :, 0]); W.append(w)
+    return np.concatenate(t2), np.concatenate(mu), np.concatenate(S), np.concatenate(W)
+
+
+def _host_marginal_loglik(states, X, y, nburn, nsamp, thin=1):
+    """(loglik, resid, var (n x D), logml (D,), n_bad) over rows nburn + 1 + j thin of the fetched tables `states` (chain k's draws first in
+    order k) and the training X (n x q), y: bnr_chains_marginal_loo's three matrices restated in numpy (_host_marginal_terms)"""
+    return _host_marginal_terms(X, y, *_host_marginal_draws(list(states), nburn, nsamp, thin))
+
+
+def marginal_loglik(X, y, tau2, mu, S, W=None, device=None):
+    """The marginal leave-one-out terms of D draws phi = (tau2, mu, S, W) for one n x q model matrix on the GPU (bnr_marginal_loglik): dict with
+    loglik, resid, var (n x D: log p(y_i | y_-i, phi), y_i - E[y_i | y_-i, phi], Var[y_i | y_-i, phi]), logml (D,: log p(y | phi)) and n_bad
+    (the draws that are NaN: S, tau2 or mu not finite, or A not positive definite).  tau2, mu: (D,); S, W: (D, q), W None = 0"""
+    ll, rs, vr, ml, nb = _capi.marginal_loglik_raw(X, y, tau2, mu, S, W, 0 if device is None else int(device))
+    return dict(loglik=ll, resid=rs, var=vr, logml=ml, n_bad=nb)
+
+
+def _row_lme(ll):
+    """log mean exp of every row of an m x S matrix (NaN for a row holding one)"""
+    ll = np.asarray(ll, dtype=np.float64)
+    mx = ll.max(axis=1)
+    with np.errstate(invalid="ignore"):
+        return mx + np.log(np.mean(np.exp(ll - mx[:, None]), axis=1))
+
+
+def _marginal_loo(y, lpd, elpd, k, loo_mean, loo_sd, logml, thin, draws, n_bad):
+    """the dict device_marginal_loo returns, from the pointwise numbers"""
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    out = _loo_from_pointwise(lpd, elpd, k, draws)
+    err = y - loo_mean
+    sst = float(np.sum((y - y.mean()) ** 2))
+    out.update(loo_mean=loo_mean, loo_sd=loo_sd, rmse_loo=float(math.sqrt(np.mean(err ** 2))),
+               r2_loo=1.0 - float(np.sum(err ** 2)) / sst if sst > 0 else math.nan, logml=logml, thin=int(thin), draws=int(draws), n_bad=int(n_bad))
+    return out
+
+
+def device_marginal_loo(chains, nburn, nsamp, thin=1, r_eff=None, per_chain=False):
+    """Marginal PSIS-LOO of the training rows over rows nburn + 1 + j thin (j = 0 .. ceil(nsamp / thin) - 1) of ALL the chains listed, pooled, on
+    the GPU (bnr_chains_marginal_loo): the dict of LOO -- elpd_loo, p_loo, looic, se, elpd_loo_i, p_loo_i, lpd_i, pareto_k, khat_threshold,
+    n_high_k, here of the ratios 1 / p(y_i | y_-i, phi) with the edge coefficients integrated out -- plus loo_mean / loo_sd (the LOO predictive
+    mean and sd of every row), rmse_loo, r2_loo, logml (log p(y | phi) of every draw), thin, draws and n_bad.  per_chain=True adds elpd_chain
+    and pareto_k_chain (K x n, one call per chain), which feed the chain stacking:
+
+        r = device_marginal_loo(chains, nburn, nsamp, thin=10, per_chain=True)
+        w = stacking_weights(r["elpd_chain"].T)["weights"]
+    """
+    chains = list(chains)
+    thin, nd = _capi.mloo_thin_draws(nsamp, thin)
+    el, kh, lm, ls, ml, ll, nb = _capi.chains_marginal_loo(chains, nburn + 1, nsamp, thin, r_eff, loglik=True)
+    out = _marginal_loo(chains[0].y, _row_lme(ll), el, kh, lm, ls, ml, thin, nd * len(chains), nb)
+    if per_chain:
+        each = [_capi.chains_marginal_loo([c], nburn + 1, nsamp, thin, r_eff) for c in chains]
+        out.update(elpd_chain=np.array([e[0] for e in each]), pareto_k_chain=np.array([e[1] for e in each]))
+    return out
+
+
+def _host_marginal_loo(states, X, y, nburn, nsamp, thin=1, r_eff=None):
+    """device_marginal_loo restated in numpy over the fetched tables of the same chains and the training X (n x q), y"""
+    states = list(states)
+    thin, nd = _capi.mloo_thin_draws(nsamp, thin)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    ll, rs, vr, ml, nb = _host_marginal_loglik(states, X, y, nburn, nsamp, thin)
+    lpd = _row_lme(ll)
+    lwn, e, k = _psis_weights_host(ll, r_eff)
+    w = np.exp(lwn)
+    mean = y - np.sum(w * rs, axis=1)
+    with np.errstate(invalid="ignore"):
+        sd = np.sqrt(np.sum(w * (vr + (y[:, None] - rs) ** 2), axis=1) - mean ** 2)
+    return _marginal_loo(y, lpd, e, k, mean, sd, ml, thin, nd * len(states), nb)
+
+
+def MarginalLOO(results, X=None, y=None, x_transform=True):
+    """Marginal PSIS-LOO of the training rows (see device_marginal_loo for the dict).  Uses the GPU's numbers when the fit carried them
+    (marginal_loo=True); otherwise the host restatement over results.state (chain 1's window, every draw) with the training X, y passed in."""
+    if results.marginal_loo is not None:
+        return results.marginal_loo
+    if results.state is None or X is None or y is None:
+        raise ValueError("MarginalLOO needs Fit(..., marginal_loo=True), or the state table (return_state=True) together with the training X and y")
+    xi = _new_rows(X, x_transform, results.state["gamma"].shape[1], y)
+    return _host_marginal_loo([results.state], _dense_rows(xi), y, results.burn_in, results.sampled)
+
+
+def _marginal_loo_thin(nsamp, draws):
+    """thin = ceil(nsamp / marginal_loo_draws); ValueError unless marginal_loo_draws is an integer >= 1"""
+    if isinstance(draws, bool) or int(draws) != draws or int(draws) < 1:
+        raise ValueError("marginal_loo_draws must be an integer >= 1, not %r" % (draws,))
+    return max(1, -(-int(nsamp) // int(draws)))
+
+
 # ------------------------------------------------------------------------------------------ chain placement
 def _dist():
     """torch.distributed if THE CALLER has imported and initialised it, else None.  Never imports torch itself: a process group can only
@@ -1959,6 +2128,7 @@ class _Requests:
     node_sets: int                   # the number of top node sets, or None
     stack: bool
     edge_cov: object = None          # None, "all", or the 0-based edge indices (int32)
+    marginal_loo: int = None         # the draws per chain of the marginal PSIS-LOO (marginal_loo_draws), or None
 
 
 def _one_rank(option):
@@ -1970,7 +2140,7 @@ def _one_rank(option):
 def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, return_state=True, summary_interval=None, ess_max_lag=None, predict_X=None,
                   predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None, pool_chains=False, predict_observation=False,
                   pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False, hdi_prob=0.95, fdr=0.05, node_sets=False,
-                  top_sets=10, stack_chains=False, edge_cov=False):
+                  top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False, marginal_loo_draws=2000):
     """The options of a fit (Fit's keywords) checked before any sampling, in this order -> _Requests.  Fit itself calls it ahead of
     parameters.log for the refusals alone, without X_new and nsamp: what needs them -- the new rows, the lag window of the rank diagnostics,
     r_eff -- is then left to generate_samples / generate_samples_dbl."""
@@ -2010,10 +2180,17 @@ def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, retur
     ec = _edge_cov_cols(edge_cov, None if X_new is None else X_new.V)
     if ec is not None:
         _one_rank("edge_cov")
+    ml = None
+    if marginal_loo:
+        _one_rank("marginal_loo")
+        _marginal_loo_thin(1, marginal_loo_draws)
+        ml = int(marginal_loo_draws)
+        if X_new is not None and X_new.n > MLOO_MAX_N:
+            raise ValueError("marginal_loo takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
     if X_new is not None:
         _capi.r_eff_array(loo_r_eff, X_new.n)
     return _Requests(return_state, summary_interval, ess_max_lag, pred, bool(waic), bool(loo), loo_r_eff, bool(pool_chains), bool(predict_observation),
-                     pred_seed, lp, bool(rank_diagnostics), es, ntop, bool(stack_chains), ec)
+                     pred_seed, lp, bool(rank_diagnostics), es, ntop, bool(stack_chains), ec, ml)
 
 
 def _finish(chainset, res, req, seed):
@@ -2078,7 +2255,10 @@ def _finish(chainset, res, req, seed):
         res.loo = _loo_from_pointwise(lp.lpd_i, lp.elpd_loo_i, lp.pareto_k, S)
     elif req.loo:
         res.loo = _loo_from_pointwise(*(_capi.pooled_loo(chains, nb + 1, ns, req.loo_r_eff) if pooled else ch.loo(nb + 1, ns, req.loo_r_eff)), S)
-    if req.summary_interval is not None or req.predict is not None or req.waic or req.loo or req.loo_predict is not None:
+    if req.marginal_loo is not None:
+        res.marginal_loo = device_marginal_loo(chains, nb, ns, _marginal_loo_thin(ns, req.marginal_loo), req.loo_r_eff)
+    if (req.summary_interval is not None or req.predict is not None or req.waic or req.loo or req.loo_predict is not None
+            or req.marginal_loo is not None):
         res.stat_chains = len(chains)
     return res
 
@@ -2112,7 +2292,8 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                      purge_burn=None, device=None, _keep=None, return_state=True, summary_interval=None, ess_max_lag=None,
                      xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
                      pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
-                     hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False):
+                     hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
+                     marginal_loo_draws=2000):
     """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
     xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
     xi_weights_code(xi_weights)
@@ -2125,7 +2306,8 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                         predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic, loo=loo, loo_r_eff=loo_r_eff,
                         pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed, loo_predict=loo_predict,
                         rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets,
-                        top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov)       # (checked before any sampling)
+                        top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
+                        marginal_loo_draws=marginal_loo_draws)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -2178,7 +2360,8 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                          seed=None, purge_burn=None, device=None, return_state=True, summary_interval=None, ess_max_lag=None,
                          xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
                          pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
-                         hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False):
+                         hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
+                         marginal_loo_draws=2000):
     """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
     xi_weights_code(xi_weights)
     if nu == R:
@@ -2190,7 +2373,8 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                         predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic, loo=loo, loo_r_eff=loo_r_eff,
                         pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed, loo_predict=loo_predict,
                         rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets,
-                        top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov)       # (checked before any sampling)
+                        top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
+                        marginal_loo_draws=marginal_loo_draws)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -2244,7 +2428,8 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
         purge_burn=None, filename="parameters.log", device=None, return_state=True, summary_interval=None, ess_max_lag=None,
         xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
         pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
-        hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False):
+        hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
+        marginal_loo_draws=2000):
     """Fit! (gibbs.jl:725-751).  The `V` keyword is accepted and ignored, as in the reference.
     Extensions: summary_interval=95 computes Summary's statistics on the GPU (Results.summary_device);
     return_state=False then leaves the (large) state table on the device and frees it; ess_max_lag=0 (default lag
@@ -2276,12 +2461,17 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     those edge coefficients -- vcov(fit) -- computed on the GPU from the resident traces over every chain of the fit (Results.edge_cov, see
     EdgeCov: sd, corr, contrast(C) for intervals on linear combinations of edges, top_pairs); with stack_chains=True also the covariance under
     the stacking weights (Results.stacking.edge_cov); every chain must live on this rank.
+    marginal_loo=True adds PSIS-LOO with the edge coefficients integrated out (Results.marginal_loo, see MarginalLOO and device_marginal_loo):
+    the importance ratios 1 / p(y_i | y_-i, tau2, mu, u, lambda, S) instead of LOO's 1 / p(y_i | gamma, mu, tau2), whose Pareto k-hat is above
+    the threshold on most rows where q >> n.  It uses every thin-th row of the window, thin = ceil(nsamples / marginal_loo_draws) (default 2000
+    draws per chain), over chain 1's window or every chain's with pool_chains=True, honours loo_r_eff, needs every chain of the fit on this rank
+    and at most 2048 training rows; what loo, loo_predict and stack_chains return is not changed by it.
     parameters.log keeps the reference's lines only."""
     xi_weights_code(xi_weights)
     _fit_requests(y, num_chains, predict_X=predict_X, predict_interval=predict_interval, pool_chains=pool_chains,
                   predict_observation=predict_observation, loo_predict=loo_predict, rank_diagnostics=rank_diagnostics,
                   edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains,
-                  edge_cov=edge_cov)
+                  edge_cov=edge_cov, marginal_loo=marginal_loo, marginal_loo_draws=marginal_loo_draws)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
         with open(filename, "w") as f:
@@ -2302,7 +2492,8 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                                     waic=waic, loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation,
                                     pred_seed=pred_seed, loo_predict=loo_predict, rank_diagnostics=rank_diagnostics,
                                     edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr,
-                                    node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov)
+                                    node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov,
+                                    marginal_loo=marginal_loo, marginal_loo_draws=marginal_loo_draws)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
@@ -2310,4 +2501,5 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                             xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic,
                             loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed,
                             loo_predict=loo_predict, rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr,
-                            node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov)
+                            node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
+                            marginal_loo_draws=marginal_loo_draws)

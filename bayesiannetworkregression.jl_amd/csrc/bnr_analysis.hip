@@ -1354,3 +1354,22 @@ int bnr_cov(int32_t device, int32_t K, int32_t nsamp, int32_t m, const double *x
     for (int k = 0; k < K; ++k) rows[k] = Xd + (size_t)k * nsamp * (size_t)m;
     return cov_run(st, rows, m, nsamp, m, hc.data(), weights ? &wt : nullptr, 0, mean, cov);
 }
+
+// ------------------------------------------------------------------------------------------ the device side of a chain (ABI 18): include/bnr_hip.h
+// What a companion library (libbnr_mloo.so) needs to read a chain's table in place: sizes, row offsets and device pointers, after everything the
+// chain's stream and its group's still hold has finished.  A pending asynchronous run stays pending for bnr_chain_sync.  Host code only.
+int bnr_chain_device_view(bnr_chain *c, bnr_chain_view *out)
+{
+    if (!c || !out) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->x.stream));
+    if (c->group) HIPCHK(hipStreamSynchronize(c->group->x.stream));
+    const bnr_dev &d = c->d;
+    out->device = c->device;
+    out->n = d.n; out->n_pad = d.n_pad; out->V = d.V; out->R = d.R; out->q = d.q; out->q_pad = d.q_pad; out->tot = d.tot; out->rowlen = d.rowlen;
+    out->o_tau2 = ROW_TAU2; out->o_mu = ROW_MU; out->o_lam = d.o_lam; out->o_u = d.o_u; out->o_gamma = d.o_gamma; out->o_S = d.o_S;
+    out->ldx = d.n_pad;
+    out->X = d.X; out->y = d.y; out->ek = d.ek; out->el = d.el; out->trace = d.trace;
+    return BNR_OK;
+}
+int bnr_set_last_error(int code, const char *msg) { return fail(code, msg ? msg : ""); }

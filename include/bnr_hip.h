@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BNR_ABI_VERSION 17  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
+#define BNR_ABI_VERSION 18  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
                                5: + bnr_chain_create_typed, bnr_chain_create_from_matrices, bnr_device_synchronize; 6: + bnr_comm_info;
                                7: + option "xi_weights", bnr_host_xi_weight; 8: + bnr_chain_predict, bnr_chain_predict_from_matrices,
                                bnr_chain_loglik_stats, option "predict_block_rows"; 9: + bnr_chain_loo, bnr_psis_loo;
@@ -38,7 +38,8 @@ extern "C" {
                                option "rank_block_cols"; 13: + bnr_chain_hdi, bnr_chains_hdi, bnr_hdi;
                                14: + bnr_host_gig_attempts; 15: + bnr_chain_inclusion, bnr_chains_inclusion,
                                bnr_inclusion; 16: + bnr_stacking_weights, bnr_chains_stack, bnr_chains_wsummary, bnr_chains_wpredict,
-                               bnr_wquantile; 17: + bnr_chain_cov, bnr_chains_cov, bnr_cov, option "cov_block_cols" (all additive) */
+                               bnr_wquantile; 17: + bnr_chain_cov, bnr_chains_cov, bnr_cov, option "cov_block_cols";
+                               18: + bnr_chain_device_view, bnr_set_last_error (all additive) */
 
 enum {
     BNR_OK = 0,
@@ -432,6 +433,26 @@ int bnr_chain_cov(bnr_chain *chain, int32_t first_row, int32_t nsamp, int32_t nc
 int bnr_chains_cov(bnr_chain *const *chains, int32_t nchains, const double *weights, int32_t first_row, int32_t nsamp, int32_t ncols,
                    const int32_t *cols, double *mean, double *cov);
 int bnr_cov(int32_t device, int32_t K, int32_t nsamp, int32_t m, const double *x, const double *weights, double *mean, double *cov);
+
+/* The device side of a chain, for a companion library (ABI 18) -- libbnr_mloo.so (include/bnr_mloo.h) reads the chains' tables through it; no
+ * kernel of this library is involved.  Row r (0-based) of the table starts at trace + r * rowlen doubles; inside a row tau2 is the double at
+ * o_tau2, mu at o_mu, lambda_t at o_lam + t, u_{t,v} at o_u + t + R v, gamma_e at o_gamma + e, S_e at o_S + e.  X is column-major with leading
+ * dimension ldx >= n_pad: rows n .. n_pad - 1 and columns q .. q_pad - 1 hold 0.0.  ek[e] / el[e]: the column node and the row node of edge e.
+ * The pointers stay valid until the chain is destroyed or resized (bnr_chain_resize moves trace and changes tot); chains made with
+ * bnr_chain_create_like share X, y, ek, el.  The call waits for whatever the chain's stream (and its group's) still holds -- a pending
+ * bnr_chain_run_async included, which stays pending for bnr_chain_sync -- so what the pointers show is complete.  Nothing is written.
+ * bnr_set_last_error: the companion library's way to leave its message where bnr_last_error() finds it; returns code. */
+typedef struct bnr_chain_view {
+    int32_t device;
+    int32_t n, n_pad, V, R, q, q_pad, tot, rowlen;
+    int32_t o_tau2, o_mu, o_lam, o_u, o_gamma, o_S;
+    int32_t ldx;
+    const double *X, *y;
+    const int32_t *ek, *el;
+    const double *trace;
+} bnr_chain_view;
+int bnr_chain_device_view(bnr_chain *chain, bnr_chain_view *out);
+int bnr_set_last_error(int code, const char *msg);
 
 /* Effective sample size -- an ADDITION to the reference (which only has split-Rhat; north-star item "Rhat/ESS check").
  * bnr_chain_ess_stats: this chain's message over rows first_row .. first_row+nsamp-1: for both halves of the window (the
