@@ -1,20 +1,21 @@
-"""Build libbnr_hip.so and libbnr_mloo.so (hipcc, gfx950) in-tree."""
+"""Build libbnr_hip.so, libbnr_mloo.so and libbnr_medge.so (hipcc, gfx950) in-tree."""
 import os
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.environ.get("BNR_HIP_LIB") or os.path.join(HERE, "libbnr_hip.so")     # BNR_HIP_LIB: another build of the library (the sanitizer build of tools/sanitize_cpu.sh; julia/BNRHip.jl honours the same variable)
 MLOO_LIB = os.path.join(HERE, "libbnr_mloo.so")                              # marginal PSIS-LOO: a library of its own, linked against libbnr_hip.so beside it
+MEDGE_LIB = os.path.join(HERE, "libbnr_medge.so")                            # Rao-Blackwellised edge summaries: a third library, built and linked like libbnr_mloo.so
 
 
 def build(force=False, verbose=False):
     if os.environ.get("BNR_HIP_LIB"):
         return LIB
     csrc = os.path.join(HERE, "csrc")
-    cmd = ["make", "-j3", "-C", csrc] + (["-B"] if force else [])          # three translation units, side by side
+    cmd = ["make", "-j4", "-C", csrc] + (["-B"] if force else [])          # four translation units, side by side
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if verbose or r.returncode:
         print(r.stdout)
     if r.returncode:
-        raise RuntimeError("building libbnr_hip.so / libbnr_mloo.so failed")
+        raise RuntimeError("building libbnr_hip.so / libbnr_mloo.so / libbnr_medge.so failed")
     return LIB

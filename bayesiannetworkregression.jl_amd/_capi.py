@@ -7,7 +7,7 @@ import os
 
 import numpy as np
 
-from ._build import LIB, MLOO_LIB
+from ._build import LIB, MLOO_LIB, MEDGE_LIB
 
 BNR_OK, BNR_ERR_BAD_ARG, BNR_ERR_HIP, BNR_ERR_CHOLESKY, BNR_ERR_SAMPLER = 0, 1, 2, 3, 4
 BNR_ERR_SAMPLER_CAP = BNR_ERR_SAMPLER
@@ -40,6 +40,7 @@ class ChainView(C.Structure):
 _dp = C.c_void_p
 _lib = None
 _mloo = None
+_medge = None
 
 _SIGS = {
     "bnr_abi_version": (C.c_int, []),
@@ -161,6 +162,17 @@ _MLOO_SIGS = {
 MLOO_EXPORTS = sorted(_MLOO_SIGS)
 MLOO_MAX_N = 2048
 
+# libbnr_medge.so (include/bnr_medge.h): Rao-Blackwellised edge summaries, a third library beside the two
+_MEDGE_SIGS = {
+    "bnr_medge_abi_version": (C.c_int, []),
+    "bnr_marginal_gamma": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 8 + [C.POINTER(C.c_int32)]),
+    "bnr_mixture_summary": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 3 + [C.c_double, C.c_double] + [_dp] * 7),
+    "bnr_chains_marginal_edges": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double] + [_dp] * 9
+                                  + [C.POINTER(C.c_int32)]),
+    "bnr_medge_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
+}
+MEDGE_EXPORTS = sorted(_MEDGE_SIGS)
+
 
 _foreign_hip = None      # set by lib(): why chains must not be created in this process (GPU-free entry points stay usable)
 
@@ -222,6 +234,29 @@ def mloo_lib():
             f.argtypes = args
         _mloo = L
     return _mloo
+
+
+def medge_lib():
+    """Load libbnr_medge.so, after libbnr_hip.so (which it is linked against); raises if it has not been built"""
+    global _medge
+    if _medge is None:
+        lib()
+        if not os.path.exists(MEDGE_LIB):
+            raise ImportError("libbnr_medge.so is missing at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'`; there is no "
+                              "CPU fallback" % MEDGE_LIB)
+        L = C.CDLL(MEDGE_LIB)
+        for name, (res, args) in _MEDGE_SIGS.items():
+            f = getattr(L, name)
+            f.restype = res
+            f.argtypes = args
+        _medge = L
+    return _medge
+
+
+def _device_medge():
+    """medge_lib() for the calls that open a device, refused like _device_lib()"""
+    _device_lib()
+    return medge_lib()
 
 
 def _device_mloo():
@@ -1084,6 +1119,78 @@ def chains_marginal_loo(chains, first_row, nsamp, thin=1, r_eff=None, loglik=Fal
     check(_device_mloo().bnr_chains_marginal_loo(arr, K, int(first_row), int(nsamp), thin, _ptr(r), _ptr(el), _ptr(kh), _ptr(lm), _ptr(ls), _ptr(ml),
                                                  _ptr(ll), C.byref(nb)))
     return el, kh, lm, ls, ml, ll, nb.value
+
+
+# ------------------------------------------------------------------------------------------ Rao-Blackwellised edge summaries (libbnr_medge.so, include/bnr_medge.h)
+MEDGE_SUMMARY_FIELDS = ("mean", "sd", "var_within", "p_pos", "p_neg", "lower", "upper")
+
+
+def medge_set_option(name, value):
+    check(medge_lib().bnr_medge_set_option(name.encode(), int(value)))
+
+
+def marginal_gamma_raw(X, y, tau2, mu, S, W=None, device=0):
+    """(m, v (D x q each), n_bad): the conditional mean and variance of every edge coefficient given each of D draws phi = (tau2, mu, S, W) for
+    one n x q model matrix, on the device (bnr_marginal_gamma).  ValueError (before any library call) for shapes that do not fit or n > 2048"""
+    Xf = np.asfortranarray(X, dtype=np.float64)
+    if Xf.ndim != 2 or Xf.shape[0] < 1 or Xf.shape[1] < 1:
+        raise ValueError("X must be an n x q matrix with n, q >= 1")
+    n, q = Xf.shape
+    if n > MLOO_MAX_N:
+        raise ValueError("n = %d: more than %d rows are not supported by this version" % (n, MLOO_MAX_N))
+    yf = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+    t2 = np.ascontiguousarray(np.atleast_1d(np.asarray(tau2, dtype=np.float64))).reshape(-1)
+    D = t2.size
+    mu_ = np.ascontiguousarray(np.atleast_1d(np.asarray(mu, dtype=np.float64))).reshape(-1)
+    Sf = np.ascontiguousarray(np.asarray(S, dtype=np.float64).reshape(-1, q))
+    Wf = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1, q))
+    if yf.shape != (n,) or D < 1 or mu_.shape != (D,) or Sf.shape != (D, q) or (Wf is not None and Wf.shape != (D, q)):
+        raise ValueError("need y (n,), tau2 and mu (D,), S and W (D, q) for X (n, q)")
+    m, v = np.empty((D, q)), np.empty((D, q))
+    nb = C.c_int32(0)
+    check(_device_medge().bnr_marginal_gamma(int(device), n, q, D, _ptr(Xf), _ptr(yf), _ptr(t2), _ptr(mu_), _ptr(Sf), _ptr(Wf), _ptr(m), _ptr(v),
+                                             C.byref(nb)))
+    return m, v, nb.value
+
+
+def _medge_outputs(q, fields):
+    fields = tuple(fields)
+    if not fields or [f for f in fields if f not in MEDGE_SUMMARY_FIELDS] or (("lower" in fields) != ("upper" in fields)):
+        raise ValueError("fields must name some of %r, lower and upper together, not %r" % (MEDGE_SUMMARY_FIELDS, fields))
+    return [np.empty(q) if f in fields else None for f in MEDGE_SUMMARY_FIELDS]
+
+
+def mixture_summary_raw(m, v, nchains=1, weights=None, p_lo=0.025, p_hi=0.975, device=0, fields=MEDGE_SUMMARY_FIELDS):
+    """the tuple MEDGE_SUMMARY_FIELDS (q values each) of the mixtures of normals in the columns of the (nchains nd) x q matrices m, v, on the
+    device (bnr_mixture_summary); an entry not named in `fields` is not requested and comes back as None"""
+    mf, vf = np.ascontiguousarray(m, dtype=np.float64), np.ascontiguousarray(v, dtype=np.float64)
+    K = int(nchains)
+    if mf.ndim != 2 or mf.shape != vf.shape or K < 1 or mf.shape[1] < 1 or mf.shape[0] < K or mf.shape[0] % K:
+        raise ValueError("m and v must be (nchains * nd) x q matrices of one shape with nd, q >= 1")
+    w = None if weights is None else stack_weights_array(weights, K)
+    p_lo, p_hi = loo_probs(p_lo, p_hi)
+    D, q = mf.shape
+    out = _medge_outputs(q, fields)
+    check(_device_medge().bnr_mixture_summary(int(device), q, K, D // K, _ptr(mf), _ptr(vf), _ptr(w), p_lo, p_hi, *[_ptr(o) for o in out]))
+    return tuple(out)
+
+
+def chains_marginal_edges(chains, first_row, nsamp, thin=1, weights=None, p_lo=0.025, p_hi=0.975, per_draw=False, fields=MEDGE_SUMMARY_FIELDS):
+    """(the tuple MEDGE_SUMMARY_FIELDS (q,), m, v (K nd x q) or None, n_bad) over rows first_row + j thin of every chain listed
+    (bnr_chains_marginal_edges)"""
+    c0, (arr, K) = _pooled(chains)
+    thin, nd = mloo_thin_draws(nsamp, thin)
+    if c0.n > MLOO_MAX_N:
+        raise ValueError("n = %d: more than %d rows are not supported by this version" % (c0.n, MLOO_MAX_N))
+    w = None if weights is None else stack_weights_array(weights, K)
+    p_lo, p_hi = loo_probs(p_lo, p_hi)
+    q = c0.q
+    out = _medge_outputs(q, fields)
+    m, v = (np.empty((K * nd, q)), np.empty((K * nd, q))) if per_draw else (None, None)
+    nb = C.c_int32(0)
+    check(_device_medge().bnr_chains_marginal_edges(arr, K, _ptr(w), int(first_row), int(nsamp), thin, p_lo, p_hi, *[_ptr(o) for o in out], _ptr(m),
+                                                    _ptr(v), C.byref(nb)))
+    return tuple(out), m, v, nb.value
 
 
 class Comm:

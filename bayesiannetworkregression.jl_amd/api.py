@@ -112,6 +112,7 @@ class Results:
     stacking: "ChainStacking" = None   # filled on request (stack_chains=True): every chain's own PSIS-LOO, the stacking weights of the chains and the summaries under them (see Stacking)
     edge_cov: "EdgeCov" = None       # filled on request (edge_cov=...): the posterior covariance matrix of the edge coefficients over every chain (see EdgeCov)
     marginal_loo: dict = None        # filled on request (marginal_loo=True): PSIS-LOO with the edge coefficients integrated out, computed on the GPU (see MarginalLOO)
+    marginal_edges: "MarginalEdges" = None   # filled on request (marginal_edges=True): the edge table with gamma integrated out, computed on the GPU (see MarginalEdges)
     stat_chains: int = None          # how many chains the device statistics above (summary_device, prediction, waic, loo, loo_predictive) cover: 1 (chain 1's window), or
                                      # every chain of the fit with pool_chains=True; None when the fit computed none
 
@@ -1248,6 +1249,7 @@ class ChainStacking:
     summary: dict = None
     prediction: BNRPrediction = None
     edge_cov: "EdgeCov" = None       # the posterior covariance of the edge coefficients under the weights (Fit(..., edge_cov=..., stack_chains=True))
+    marginal_edges: "MarginalEdges" = None   # the edge table with gamma integrated out under the weights (Fit(..., marginal_edges=True, stack_chains=True))
 
 
 def _stack_solver_args(max_iter, gap_tol):
@@ -1885,6 +1887,219 @@ def _marginal_loo_thin(nsamp, draws):
     return max(1, -(-int(nsamp) // int(draws)))
 
 
+# ------------------------------------------------------------------------------------------ Rao-Blackwellised edge summaries (an addition to the reference)
+# The edge table with gamma integrated out (include/bnr_medge.h, libbnr_medge.so; DESIGN.md section 8, "Rao-Blackwellised edge summaries").  Given
+# phi = (tau2, mu, u, lambda, S) of a table row, gamma_e | phi, y ~ N(m_e, v_e) in closed form, so the posterior of gamma_e is the mixture of
+# those normals over the draws of phi: its mean, sd, interval and sign probabilities carry none of the within-draw noise of the gamma draws.
+# The _host_* functions restate the definitions in numpy: the fallback of MarginalEdges and the yardstick of the tests.
+_MEDGE_FIELDS = ("node1", "node2", "estimate", "sd", "lower_bound", "upper_bound", "p_pos", "p_neg", "var_within", "interval", "chains", "draws", "thin",
+                 "n_bad", "weights", "m", "v")
+
+
+def _host_gamma_terms(X, y, tau2, mu, S, W=None):
+    """(m, v (D x q), n_bad) of D draws for one n x q matrix X: the definitions of include/bnr_medge.h in numpy, per draw np.linalg.cholesky of
+    A = I + X diag(S) X^T, T = L^-1 X by a triangular solve (t_e = its column norms squared), g = A^-1 r by two, p = X^T g, m = W + S p,
+    v = (tau2 S) max(1 - S t, 0).  A draw whose S, tau2 or mu is not finite or whose A is not positive definite is NaN and counted"""
+    X = np.asarray(X, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    n, q = X.shape
+    tau2, mu = np.atleast_1d(np.asarray(tau2, dtype=np.float64)), np.atleast_1d(np.asarray(mu, dtype=np.float64))
+    D = tau2.size
+    S = np.asarray(S, dtype=np.float64).reshape(D, q)
+    W = None if W is None else np.asarray(W, dtype=np.float64).reshape(D, q)
+    m, v = np.full((D, q), np.nan), np.full((D, q), np.nan)
+    n_bad = 0
+    eye = np.eye(n)
+    for s in range(D):
+        ok = np.isfinite(tau2[s]) and np.isfinite(mu[s]) and np.all(np.isfinite(S[s]))
+        L = None
+        if ok:
+            try:
+                L = np.linalg.cholesky(eye + (X * S[s][None, :]) @ X.T)
+            except np.linalg.LinAlgError:
+                L = None
+            if L is not None and not np.all(np.isfinite(L)):
+                L = None
+        if L is None:
+            n_bad += 1
+            continue
+        r = y - mu[s] - (X @ W[s] if W is not None else 0.0)
+        T = _solve_lower(L, X)
+        t = np.sum(T * T, axis=0)
+        z = _solve_lower(L, r)
+        g = _solve_lower(L[::-1, ::-1].T, z[::-1])[::-1]       # L^T g = z, as a lower triangular solve of the reversed system
+        m[s] = (W[s] if W is not None else 0.0) + S[s] * (X.T @ g)
+        v[s] = (tau2[s] * S[s]) * np.fmax(1.0 - S[s] * t, 0.0)
+    return m, v, n_bad
+
+
+def _host_marginal_gamma(states, X, y, nburn, nsamp, thin=1):
+    """(m, v (D x q), n_bad) over rows nburn + 1 + j thin of the fetched tables `states` (chain k's draws first in order k) and the training
+    X (n x q), y: the two matrices of bnr_chains_marginal_edges restated in numpy (_host_gamma_terms)"""
+    return _host_gamma_terms(X, y, *_host_marginal_draws(list(states), nburn, nsamp, thin))
+
+
+def _medge_chain_sum(terms):
+    """the chain sum of include/bnr_medge.h for every column of an nd x q matrix of terms: partial sum l (0 .. 63) takes rows l, l + 64, ... in
+    order from 0.0; the partial sums are then added pairwise, l with l + 32, then 16, 8, 4, 2, 1"""
+    nd, q = terms.shape
+    rows = -(-nd // 64)
+    pad = np.zeros((rows * 64, q))
+    pad[:nd] = terms
+    acc = np.zeros((64, q))
+    for r in range(rows):
+        acc = acc + pad[r * 64:(r + 1) * 64]
+    off = 32
+    while off:
+        acc = acc[:off] + acc[off:2 * off]
+        off //= 2
+    return acc[0]
+
+
+def _medge_stat(terms, K, w):
+    """sum_k (chain sum of chain k's rows / nd) w_k, k ascending from 0.0"""
+    nd = terms.shape[0] // K
+    tot = np.zeros(terms.shape[1])
+    for k in range(K):
+        tot = tot + (_medge_chain_sum(terms[k * nd:(k + 1) * nd]) / float(nd)) * w[k]
+    return tot
+
+
+def _host_mixture_summary(m, v, nchains=1, weights=None, p_lo=0.025, p_hi=0.975):
+    """bnr_mixture_summary restated in numpy with its summation order: dict of mean, sd, var_within, p_pos, p_neg, lower, upper (q,) for the
+    (nchains nd) x q matrices m, v.  The quantiles by _bisect_quantile from the bracket of _loo_bracket_c; erfc is scipy's (or math's), so the
+    three statistics that go through it agree with the device to rounding, the others bit for bit"""
+    m, v = np.asarray(m, dtype=np.float64), np.asarray(v, dtype=np.float64)
+    K = int(nchains)
+    D, q = m.shape
+    w = np.full(K, 1.0 / K) if weights is None else np.asarray(weights, dtype=np.float64).reshape(K)
+    p_lo, p_hi = _capi.loo_probs(p_lo, p_hi)
+    c = _loo_bracket_c(p_lo, p_hi)
+    h = 0.70710678118654752440
+    point = v == 0.0
+    with np.errstate(all="ignore"):
+        sd = np.sqrt(v)
+        r = m / sd
+        out = dict(mean=_medge_stat(m, K, w), var_within=_medge_stat(v, K, w))
+        out["sd"] = np.sqrt(np.fmax(_medge_stat(v + m * m, K, w) - out["mean"] * out["mean"], 0.0))
+        out["p_pos"] = _medge_stat(np.where(point, (m > 0).astype(np.float64), 0.5 * _erfc(r * -h)), K, w)
+        out["p_neg"] = _medge_stat(np.where(point, (m < 0).astype(np.float64), 0.5 * _erfc(r * h)), K, w)
+        lo, hi = np.min(m - c * sd, axis=0), np.max(m + c * sd, axis=0)
+        lower, upper = np.full(q, np.nan), np.full(q, np.nan)
+        nan = np.any(np.isnan(m) | np.isnan(v), axis=0)
+        for e in range(q):
+            if nan[e]:
+                continue
+            me, se, pe = m[:, e:e + 1], sd[:, e:e + 1], point[:, e:e + 1]
+
+            def F(t, me=me, se=se, pe=pe):
+                return float(_medge_stat(np.where(pe, (t >= me).astype(np.float64), 0.5 * _erfc(((t - me) / se) * -h)), K, w)[0])
+            lower[e] = _bisect_quantile(F, p_lo, float(lo[e]), float(hi[e]))
+            upper[e] = _bisect_quantile(F, p_hi, float(lo[e]), float(hi[e]))
+    for k in ("mean", "sd", "var_within", "p_pos", "p_neg"):
+        out[k] = np.where(nan, np.nan, out[k])
+    out.update(lower=lower, upper=upper)
+    return out
+
+
+class MarginalEdges:
+    """The edge table with gamma integrated out.  node1 / node2: the 1-based nodes of every edge (Summary's order); estimate, sd: the mean and
+    standard deviation of the mixture sum_s omega_s N(m_se, v_se); lower_bound / upper_bound: its central interval% interval; p_pos / p_neg: its
+    mass above / below 0, each summed on its own; var_within: sum_s omega_s v_se.  Derived: lfsr = min(p_pos, p_neg), rb_share = var_within /
+    sd^2 -- the share of the posterior variance that Rao-Blackwellisation removes from the estimator's noise.  chains, draws, thin: what was
+    pooled; n_bad: the draws that could not be factorised (every summary is NaN while n_bad > 0); weights: the chain weights, or None; m, v: the
+    per-draw conditional means and variances (draws x q), or None.
+
+    MarginalEdges(results, X, y) is the accessor of a fit: the GPU's numbers when the fit carried them (marginal_edges=True), otherwise restated
+    on the host over results.state (needs return_state=True and the training X, y; chain 1's window, every draw).  Without a Results,
+    MarginalEdges(**fields) builds the record itself from exactly the fields above."""
+
+    def __new__(cls, results=None, X=None, y=None, x_transform=True, **fields):
+        if results is not None:
+            return _marginal_edges_of(results, X, y, x_transform)
+        return object.__new__(cls)
+
+    def __init__(self, results=None, X=None, y=None, x_transform=True, **fields):
+        if results is not None:                                          # (the accessor: __new__ returned a finished object)
+            return
+        if set(fields) != set(_MEDGE_FIELDS):
+            raise TypeError("MarginalEdges takes a Results, or exactly the fields %r" % (_MEDGE_FIELDS,))
+        self.__dict__.update(fields)
+
+    def __repr__(self):
+        return "MarginalEdges(edges=%d, chains=%d, draws=%d%s)" % (self.estimate.size, self.chains, self.draws, "" if self.weights is None else ", weighted")
+
+    @property
+    def lfsr(self):
+        """the local false sign rate min(p_pos, p_neg) of every edge"""
+        return np.fmin(self.p_pos, self.p_neg) + 0.0 * (self.p_pos + self.p_neg)       # (NaN where either is)
+
+    @property
+    def rb_share(self):
+        """var_within / sd^2 (NaN where sd is 0)"""
+        with np.errstate(all="ignore"):
+            return np.where(self.sd > 0, self.var_within / (self.sd * self.sd), np.nan)
+
+
+def _marginal_edges(stats, m, v, interval, nchains, draws, thin, n_bad, weights):
+    q = stats["mean"].size
+    V = int(round((-1 + math.sqrt(1 + 8 * q)) / 2))
+    if V * (V + 1) // 2 == q:
+        n1, n2 = _edge_nodes(V, np.arange(q))
+    else:                                                               # (a raw matrix whose columns are no lower triangle)
+        n1 = n2 = np.arange(1, q + 1)
+    return MarginalEdges(node1=n1, node2=n2, estimate=stats["mean"], sd=stats["sd"], lower_bound=stats["lower"], upper_bound=stats["upper"],
+                         p_pos=stats["p_pos"], p_neg=stats["p_neg"], var_within=stats["var_within"], interval=interval, chains=int(nchains),
+                         draws=int(draws), thin=int(thin), n_bad=int(n_bad), weights=None if weights is None else np.array(weights, dtype=np.float64),
+                         m=m, v=v)
+
+
+def marginal_gamma(X, y, tau2, mu, S, W=None, device=None):
+    """The conditional posterior of every edge coefficient given each of D draws phi = (tau2, mu, S, W), for one n x q model matrix, on the GPU
+    (bnr_marginal_gamma): dict with m, v (D x q: gamma_e | phi, y ~ N(m, v)) and n_bad (the draws that are NaN: S, tau2 or mu not finite, or A
+    not positive definite).  tau2, mu: (D,); S, W: (D, q), W None = 0"""
+    m, v, nb = _capi.marginal_gamma_raw(X, y, tau2, mu, S, W, 0 if device is None else int(device))
+    return dict(m=m, v=v, n_bad=nb)
+
+
+def mixture_summary(m, v, nchains=1, weights=None, interval=95, device=None):
+    """The summary of the q mixtures of normals in the columns of the (nchains nd) x q matrices m, v (chain k's draws in rows k nd ..) on the GPU
+    (bnr_mixture_summary): dict with mean, sd, var_within, p_pos, p_neg, lower, upper (q,) -- the central interval% interval.  weights: chain
+    weights (default 1 / nchains each)"""
+    p_lo, p_hi = _loo_interval_probs(interval)
+    return dict(zip(_capi.MEDGE_SUMMARY_FIELDS, _capi.mixture_summary_raw(m, v, nchains, weights, p_lo, p_hi, 0 if device is None else int(device))))
+
+
+def device_marginal_edges(chains, nburn, nsamp, thin=1, weights=None, interval=95, per_draw=False):
+    """The edge table with gamma integrated out over rows nburn + 1 + j thin (j = 0 .. ceil(nsamp / thin) - 1) of ALL the chains listed, pooled
+    (under `weights`, the chain weights, where given), on the GPU (bnr_chains_marginal_edges) -> MarginalEdges.  The per-draw m and v stay on the
+    device unless per_draw=True asks for them."""
+    chains = list(chains)
+    thin, nd = _capi.mloo_thin_draws(nsamp, thin)
+    p_lo, p_hi = _loo_interval_probs(interval)
+    out, m, v, nb = _capi.chains_marginal_edges(chains, nburn + 1, nsamp, thin, weights, p_lo, p_hi, per_draw)
+    return _marginal_edges(dict(zip(_capi.MEDGE_SUMMARY_FIELDS, out)), m, v, interval, len(chains), nd * len(chains), thin, nb, weights)
+
+
+def _host_marginal_edges(states, X, y, nburn, nsamp, thin=1, weights=None, interval=95, per_draw=False):
+    """device_marginal_edges restated in numpy over the fetched tables of the same chains and the training X (n x q), y"""
+    states = list(states)
+    thin, nd = _capi.mloo_thin_draws(nsamp, thin)
+    p_lo, p_hi = _loo_interval_probs(interval)
+    m, v, nb = _host_marginal_gamma(states, X, y, nburn, nsamp, thin)
+    stats = _host_mixture_summary(m, v, len(states), weights, p_lo, p_hi)
+    return _marginal_edges(stats, m if per_draw else None, v if per_draw else None, interval, len(states), nd * len(states), thin, nb, weights)
+
+
+def _marginal_edges_of(results, X=None, y=None, x_transform=True):
+    if results.marginal_edges is not None:
+        return results.marginal_edges
+    if results.state is None or X is None or y is None:
+        raise ValueError("MarginalEdges needs Fit(..., marginal_edges=True), or the state table (return_state=True) together with the training X and y")
+    xi = _new_rows(X, x_transform, results.state["gamma"].shape[1], y)
+    return _host_marginal_edges([results.state], _dense_rows(xi), y, results.burn_in, results.sampled)
+
+
 # ------------------------------------------------------------------------------------------ chain placement
 def _dist():
     """torch.distributed if THE CALLER has imported and initialised it, else None.  Never imports torch itself: a process group can only
@@ -2129,6 +2344,7 @@ class _Requests:
     stack: bool
     edge_cov: object = None          # None, "all", or the 0-based edge indices (int32)
     marginal_loo: int = None         # the draws per chain of the marginal PSIS-LOO (marginal_loo_draws), or None
+    marginal_edges: tuple = None     # (the draws per chain of the Rao-Blackwellised edge table (marginal_edges_draws), interval), or None
 
 
 def _one_rank(option):
@@ -2140,7 +2356,8 @@ def _one_rank(option):
 def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, return_state=True, summary_interval=None, ess_max_lag=None, predict_X=None,
                   predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None, pool_chains=False, predict_observation=False,
                   pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False, hdi_prob=0.95, fdr=0.05, node_sets=False,
-                  top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False, marginal_loo_draws=2000):
+                  top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False, marginal_loo_draws=2000, marginal_edges=False,
+                  marginal_edges_draws=2000):
     """The options of a fit (Fit's keywords) checked before any sampling, in this order -> _Requests.  Fit itself calls it ahead of
     parameters.log for the refusals alone, without X_new and nsamp: what needs them -- the new rows, the lag window of the rank diagnostics,
     r_eff -- is then left to generate_samples / generate_samples_dbl."""
@@ -2187,10 +2404,19 @@ def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, retur
         ml = int(marginal_loo_draws)
         if X_new is not None and X_new.n > MLOO_MAX_N:
             raise ValueError("marginal_loo takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
+    me = None
+    if marginal_edges:
+        _one_rank("marginal_edges")
+        if isinstance(marginal_edges_draws, bool) or int(marginal_edges_draws) != marginal_edges_draws or int(marginal_edges_draws) < 1:
+            raise ValueError("marginal_edges_draws must be an integer >= 1, not %r" % (marginal_edges_draws,))
+        _loo_interval_probs(predict_interval)
+        me = (int(marginal_edges_draws), predict_interval)
+        if X_new is not None and X_new.n > MLOO_MAX_N:
+            raise ValueError("marginal_edges takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
     if X_new is not None:
         _capi.r_eff_array(loo_r_eff, X_new.n)
     return _Requests(return_state, summary_interval, ess_max_lag, pred, bool(waic), bool(loo), loo_r_eff, bool(pool_chains), bool(predict_observation),
-                     pred_seed, lp, bool(rank_diagnostics), es, ntop, bool(stack_chains), ec, ml)
+                     pred_seed, lp, bool(rank_diagnostics), es, ntop, bool(stack_chains), ec, ml, me)
 
 
 def _finish(chainset, res, req, seed):
@@ -2221,6 +2447,9 @@ def _finish(chainset, res, req, seed):
         res.edge_cov = device_edge_cov(every, nb, ns, cols)
         if req.stack:
             res.stacking.edge_cov = device_edge_cov(every, nb, ns, cols, res.stacking.weights)
+    if req.marginal_edges is not None and req.stack:
+        res.stacking.marginal_edges = device_marginal_edges(every, nb, ns, _marginal_loo_thin(ns, req.marginal_edges[0]), res.stacking.weights,
+                                                            req.marginal_edges[1])
     if req.node_sets is not None:
         res.node_sets = device_node_sets(every, nb, ns, req.node_sets)
     if req.edge_sel is not None:
@@ -2257,8 +2486,10 @@ def _finish(chainset, res, req, seed):
         res.loo = _loo_from_pointwise(*(_capi.pooled_loo(chains, nb + 1, ns, req.loo_r_eff) if pooled else ch.loo(nb + 1, ns, req.loo_r_eff)), S)
     if req.marginal_loo is not None:
         res.marginal_loo = device_marginal_loo(chains, nb, ns, _marginal_loo_thin(ns, req.marginal_loo), req.loo_r_eff)
+    if req.marginal_edges is not None:
+        res.marginal_edges = device_marginal_edges(chains, nb, ns, _marginal_loo_thin(ns, req.marginal_edges[0]), None, req.marginal_edges[1])
     if (req.summary_interval is not None or req.predict is not None or req.waic or req.loo or req.loo_predict is not None
-            or req.marginal_loo is not None):
+            or req.marginal_loo is not None or req.marginal_edges is not None):
         res.stat_chains = len(chains)
     return res
 
@@ -2293,7 +2524,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                      xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
                      pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
                      hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
-                     marginal_loo_draws=2000):
+                     marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000):
     """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
     xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
     xi_weights_code(xi_weights)
@@ -2307,7 +2538,8 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                         pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed, loo_predict=loo_predict,
                         rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets,
                         top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
-                        marginal_loo_draws=marginal_loo_draws)       # (checked before any sampling)
+                        marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
+                        marginal_edges_draws=marginal_edges_draws)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -2361,7 +2593,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                          xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
                          pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
                          hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
-                         marginal_loo_draws=2000):
+                         marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000):
     """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
     xi_weights_code(xi_weights)
     if nu == R:
@@ -2374,7 +2606,8 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                         pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed, loo_predict=loo_predict,
                         rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets,
                         top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
-                        marginal_loo_draws=marginal_loo_draws)       # (checked before any sampling)
+                        marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
+                        marginal_edges_draws=marginal_edges_draws)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -2429,7 +2662,7 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
         xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
         pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
         hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
-        marginal_loo_draws=2000):
+        marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000):
     """Fit! (gibbs.jl:725-751).  The `V` keyword is accepted and ignored, as in the reference.
     Extensions: summary_interval=95 computes Summary's statistics on the GPU (Results.summary_device);
     return_state=False then leaves the (large) state table on the device and frees it; ess_max_lag=0 (default lag
@@ -2466,12 +2699,18 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     the threshold on most rows where q >> n.  It uses every thin-th row of the window, thin = ceil(nsamples / marginal_loo_draws) (default 2000
     draws per chain), over chain 1's window or every chain's with pool_chains=True, honours loo_r_eff, needs every chain of the fit on this rank
     and at most 2048 training rows; what loo, loo_predict and stack_chains return is not changed by it.
+    marginal_edges=True adds the edge table with gamma integrated out (Results.marginal_edges, see MarginalEdges and device_marginal_edges): mean,
+    sd, the predict_interval% interval and the sign probabilities of every edge coefficient from the mixture of its conditional normals
+    N(m_e, v_e | tau2, mu, u, lambda, S) over the draws, free of the within-draw noise of the gamma draws.  Draws, chains and limits as for
+    marginal_loo (marginal_edges_draws, default 2000 per chain); with stack_chains=True also under the stacking weights over every chain
+    (Results.stacking.marginal_edges).  Every other field of the Results is what it is without it.
     parameters.log keeps the reference's lines only."""
     xi_weights_code(xi_weights)
     _fit_requests(y, num_chains, predict_X=predict_X, predict_interval=predict_interval, pool_chains=pool_chains,
                   predict_observation=predict_observation, loo_predict=loo_predict, rank_diagnostics=rank_diagnostics,
                   edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains,
-                  edge_cov=edge_cov, marginal_loo=marginal_loo, marginal_loo_draws=marginal_loo_draws)
+                  edge_cov=edge_cov, marginal_loo=marginal_loo, marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
+                        marginal_edges_draws=marginal_edges_draws)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
         with open(filename, "w") as f:
@@ -2493,7 +2732,8 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                                     pred_seed=pred_seed, loo_predict=loo_predict, rank_diagnostics=rank_diagnostics,
                                     edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr,
                                     node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov,
-                                    marginal_loo=marginal_loo, marginal_loo_draws=marginal_loo_draws)
+                                    marginal_loo=marginal_loo, marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
+                        marginal_edges_draws=marginal_edges_draws)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
@@ -2502,4 +2742,5 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                             loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed,
                             loo_predict=loo_predict, rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr,
                             node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
-                            marginal_loo_draws=marginal_loo_draws)
+                            marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
+                        marginal_edges_draws=marginal_edges_draws)
