@@ -99,6 +99,7 @@ void bnr_host_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[
     bnr_u4 r = bnr_philox4x32_10(ctr[0], ctr[1], ctr[2], ctr[3], key[0], key[1]);
     out[0] = r.x; out[1] = r.y; out[2] = r.z; out[3] = r.w;
 }
+double bnr_host_unit(uint64_t w) { return bnr_unit(w); }
 void bnr_host_uniform2(uint64_t seed, uint32_t it, uint32_t site, uint32_t elem, uint32_t att, double out[2])
 { bnr_draw2(seed, it, site, elem, att, out[0], out[1]); }
 double bnr_host_normal(uint64_t seed, uint32_t it, uint32_t site, uint32_t elem, uint32_t att)

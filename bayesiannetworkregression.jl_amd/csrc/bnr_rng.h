@@ -45,14 +45,23 @@ BNR_HD bnr_u4 bnr_philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t 
     return o;
 }
 
-// two uniforms in the open interval (0,1), 53 bits each
+// The uniform of a 64-bit word, in the open interval (0,1): (y + 1/2) 2^-53 from the word's top 53 bits y = w >> 11, in float64.  The grid it lands on:
+// below 1/2 (y < 2^52) y + 1/2 is exact and the values are the odd multiples of 2^-54; from 1/2 upward y + 1/2 is a tie that rounds to even, so the values
+// are multiples of 2^-52 (two words y each, the value 1/2 itself is reached by y = 2^52).  y = 2^53 - 1 would round to 1.0: it gives the largest double
+// below 1 instead (log of a uniform is never 0).  That one word in 2^53 is the only one whose value differs from the bare formula.
+BNR_HD double bnr_unit(uint64_t w)
+{
+    return fmin(((double)(w >> 11) + 0.5) * 0x1.0p-53, 1.0 - 0x1.0p-53);      // (one v_min_f64 per uniform)
+}
+
+// two uniforms in the open interval (0,1) from the two 64-bit halves of one Philox block (bnr_unit)
 BNR_HD void bnr_draw2(uint64_t seed, uint32_t it, uint32_t site, uint32_t elem, uint32_t att, double &ua, double &ub)
 {
     bnr_u4 r = bnr_philox4x32_10(it, site, elem, att, (uint32_t)seed, (uint32_t)(seed >> 32));
     uint64_t a = (uint64_t)r.x | ((uint64_t)r.y << 32);
     uint64_t b = (uint64_t)r.z | ((uint64_t)r.w << 32);
-    ua = ((double)(a >> 11) + 0.5) * 0x1.0p-53;
-    ub = ((double)(b >> 11) + 0.5) * 0x1.0p-53;
+    ua = bnr_unit(a);
+    ub = bnr_unit(b);
 }
 
 // cos(2 pi u) with an exact quadrant reduction: sin/cos are only evaluated on [-pi/4, pi/4]

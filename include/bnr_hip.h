@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define BNR_ABI_VERSION 18  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
+#define BNR_ABI_VERSION 19  /* 2: + bnr_chain_create_like, bnr_group_*, bnr_chain_summary; 3: + bnr_*_prepare; 4: + bnr_comm_*, bnr_rhat;
                                5: + bnr_chain_create_typed, bnr_chain_create_from_matrices, bnr_device_synchronize; 6: + bnr_comm_info;
                                7: + option "xi_weights", bnr_host_xi_weight; 8: + bnr_chain_predict, bnr_chain_predict_from_matrices,
                                bnr_chain_loglik_stats, option "predict_block_rows"; 9: + bnr_chain_loo, bnr_psis_loo;
@@ -39,7 +39,7 @@ extern "C" {
                                14: + bnr_host_gig_attempts; 15: + bnr_chain_inclusion, bnr_chains_inclusion,
                                bnr_inclusion; 16: + bnr_stacking_weights, bnr_chains_stack, bnr_chains_wsummary, bnr_chains_wpredict,
                                bnr_wquantile; 17: + bnr_chain_cov, bnr_chains_cov, bnr_cov, option "cov_block_cols";
-                               18: + bnr_chain_device_view, bnr_set_last_error (all additive) */
+                               18: + bnr_chain_device_view, bnr_set_last_error; 19: + bnr_host_unit (all additive) */
 
 enum {
     BNR_OK = 0,
@@ -599,6 +599,9 @@ int bnr_chain_set_option(bnr_chain *chain, const char *name, int64_t value);
 /* Host-side copies of the draw-site primitives (same source as the device functions), exported so that the
  * CPU test-suite can check the product's RNG contract against the oracle without a GPU. */
 void bnr_host_philox(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4]);
+/* the uniform of one 64-bit word (ABI 19), what both halves of bnr_host_uniform2 go through: ((w >> 11) + 1/2) 2^-53 in float64, strictly inside
+ * (0, 1) -- odd multiples of 2^-54 below 1/2, multiples of 2^-52 from 1/2 upward (1/2 itself included), 1 - 2^-53 where the formula would round to 1 */
+double bnr_host_unit(uint64_t w);
 void bnr_host_uniform2(uint64_t seed, uint32_t it, uint32_t site, uint32_t elem, uint32_t att, double out[2]);
 double bnr_host_normal(uint64_t seed, uint32_t it, uint32_t site, uint32_t elem, uint32_t att);
 double bnr_host_gamma(uint64_t seed, double shape, uint32_t it, uint32_t site, uint32_t elem);

@@ -106,7 +106,17 @@ static inline void philox4x32_10(const uint32_t c_in[4], const uint32_t k_in[2],
 }
 void orc_philox(const uint32_t c[4], const uint32_t k[2], uint32_t out[4]) { philox4x32_10(c, k, out); }
 
-/* one draw = two uniforms in the open interval (0,1), 53 bits each */
+/* the uniform of a 64-bit word, in the open interval (0,1): (y + 1/2) 2^-53, y = w >> 11, in float64.  Below 1/2 the sum is exact: odd multiples
+ * of 2^-54.  From 1/2 upward y + 1/2 is a tie rounded to even: multiples of 2^-52, 1/2 itself reachable; y = 2^53 - 1 would give 1.0 and is mapped
+ * to the largest double below 1. */
+static inline double unit(uint64_t w)
+{
+    double u = ((double)(w >> 11) + 0.5) * 0x1.0p-53;
+    return u < 1.0 ? u : 1.0 - 0x1.0p-53;
+}
+double orc_unit(uint64_t w) { return unit(w); }
+
+/* one draw = two uniforms in the open interval (0,1), one per 64-bit half of the Philox block */
 static inline void draw2(uint64_t seed, uint32_t it, uint32_t site, uint32_t elem, uint32_t att,
                          double *ua, double *ub)
 {
@@ -114,8 +124,8 @@ static inline void draw2(uint64_t seed, uint32_t it, uint32_t site, uint32_t ele
     philox4x32_10(c, k, r);
     uint64_t a = (uint64_t)r[0] | ((uint64_t)r[1] << 32);
     uint64_t b = (uint64_t)r[2] | ((uint64_t)r[3] << 32);
-    *ua = ((double)(a >> 11) + 0.5) * 0x1.0p-53;
-    *ub = ((double)(b >> 11) + 0.5) * 0x1.0p-53;
+    *ua = unit(a);
+    *ub = unit(b);
 }
 void orc_uniform2(uint64_t seed, uint32_t it, uint32_t site, uint32_t elem, uint32_t att, double *out)
 { draw2(seed, it, site, elem, att, &out[0], &out[1]); }

@@ -51,6 +51,8 @@ def lib():
         assert _lib.orc_sizeof() == C.sizeof(_Orc), (_lib.orc_sizeof(), C.sizeof(_Orc))
         _lib.orc_normal.restype = C.c_double
         _lib.orc_normal.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32]
+        _lib.orc_unit.restype = C.c_double
+        _lib.orc_unit.argtypes = [C.c_uint64]
         _lib.orc_uniform2.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]
         _lib.orc_gamma.restype = C.c_double
         _lib.orc_gamma.argtypes = [C.c_void_p, C.c_double, C.c_uint32, C.c_uint32, C.c_uint32]
@@ -106,6 +108,10 @@ def philox(ctr, key):
     out = (C.c_uint32 * 4)()
     lib().orc_philox((C.c_uint32 * 4)(*ctr), (C.c_uint32 * 2)(*key), out)
     return list(out)
+
+
+def unit(w):
+    return lib().orc_unit(int(w))
 
 
 def uniform2(seed, it, site, elem, att=0):

@@ -44,7 +44,8 @@ def f64(x):
 
 # ------------------------------------------------------------------------------------------------------------------ variates
 class Variates:
-    """The draw-site primitives of the library's host copy (bitwise the device's arithmetic, up to libm): bnr_host_*"""
+    """The draw-site primitives of the library's host copy (bitwise the device's arithmetic, up to libm): bnr_host_*.  That copy and the device's
+    own variates are held to an independent reference by tests/rng_ref.py (a normal's VARIATE_ULPS follows there from LIBM_ULPS)"""
 
     def __init__(self, lib, seed):
         import ctypes as C
