@@ -1,4 +1,4 @@
-"""Build libbnr_hip.so, libbnr_mloo.so and libbnr_medge.so (hipcc, gfx950) in-tree."""
+"""Build libbnr_hip.so, libbnr_mloo.so, libbnr_medge.so and libbnr_mpred.so (hipcc, gfx950) in-tree."""
 import os
 import subprocess
 
@@ -6,16 +6,17 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.environ.get("BNR_HIP_LIB") or os.path.join(HERE, "libbnr_hip.so")     # BNR_HIP_LIB: another build of the library (the sanitizer build of tools/sanitize_cpu.sh; julia/BNRHip.jl honours the same variable)
 MLOO_LIB = os.path.join(HERE, "libbnr_mloo.so")                              # marginal PSIS-LOO: a library of its own, linked against libbnr_hip.so beside it
 MEDGE_LIB = os.path.join(HERE, "libbnr_medge.so")                            # Rao-Blackwellised edge summaries: a third library, built and linked like libbnr_mloo.so
+MPRED_LIB = os.path.join(HERE, "libbnr_mpred.so")                            # Rao-Blackwellised prediction of new rows: a fourth library, built and linked like libbnr_medge.so
 
 
 def build(force=False, verbose=False):
     if os.environ.get("BNR_HIP_LIB"):
         return LIB
     csrc = os.path.join(HERE, "csrc")
-    cmd = ["make", "-j4", "-C", csrc] + (["-B"] if force else [])          # four translation units, side by side
+    cmd = ["make", "-j5", "-C", csrc] + (["-B"] if force else [])          # five translation units, side by side
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if verbose or r.returncode:
         print(r.stdout)
     if r.returncode:
-        raise RuntimeError("building libbnr_hip.so / libbnr_mloo.so / libbnr_medge.so failed")
+        raise RuntimeError("building libbnr_hip.so / libbnr_mloo.so / libbnr_medge.so / libbnr_mpred.so failed")
     return LIB

@@ -7,7 +7,7 @@ import os
 
 import numpy as np
 
-from ._build import LIB, MLOO_LIB, MEDGE_LIB
+from ._build import LIB, MLOO_LIB, MEDGE_LIB, MPRED_LIB
 
 BNR_OK, BNR_ERR_BAD_ARG, BNR_ERR_HIP, BNR_ERR_CHOLESKY, BNR_ERR_SAMPLER = 0, 1, 2, 3, 4
 BNR_ERR_SAMPLER_CAP = BNR_ERR_SAMPLER
@@ -41,6 +41,7 @@ _dp = C.c_void_p
 _lib = None
 _mloo = None
 _medge = None
+_mpred = None
 
 _SIGS = {
     "bnr_abi_version": (C.c_int, []),
@@ -174,6 +175,17 @@ _MEDGE_SIGS = {
 }
 MEDGE_EXPORTS = sorted(_MEDGE_SIGS)
 
+# libbnr_mpred.so (include/bnr_mpred.h): Rao-Blackwellised prediction of new rows, a fourth library beside the three
+_MPRED_SIGS = {
+    "bnr_mpred_abi_version": (C.c_int, []),
+    "bnr_marginal_predict": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 9 + [C.POINTER(C.c_int32)]),
+    "bnr_mixture_score": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 6),
+    "bnr_chains_marginal_predict": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, C.c_double,
+                                              C.c_double] + [_dp] * 12 + [C.POINTER(C.c_int32)]),
+    "bnr_mpred_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
+}
+MPRED_EXPORTS = sorted(_MPRED_SIGS)
+
 
 _foreign_hip = None      # set by lib(): why chains must not be created in this process (GPU-free entry points stay usable)
 
@@ -252,6 +264,29 @@ def medge_lib():
             f.argtypes = args
         _medge = L
     return _medge
+
+
+def mpred_lib():
+    """Load libbnr_mpred.so, after libbnr_hip.so (which it is linked against); raises if it has not been built"""
+    global _mpred
+    if _mpred is None:
+        lib()
+        if not os.path.exists(MPRED_LIB):
+            raise ImportError("libbnr_mpred.so is missing at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'`; there is no "
+                              "CPU fallback" % MPRED_LIB)
+        L = C.CDLL(MPRED_LIB)
+        for name, (res, args) in _MPRED_SIGS.items():
+            f = getattr(L, name)
+            f.restype = res
+            f.argtypes = args
+        _mpred = L
+    return _mpred
+
+
+def _device_mpred():
+    """mpred_lib() for the calls that open a device, refused like _device_lib()"""
+    _device_lib()
+    return mpred_lib()
 
 
 def _device_medge():
@@ -1192,6 +1227,95 @@ def chains_marginal_edges(chains, first_row, nsamp, thin=1, weights=None, p_lo=0
     check(_device_medge().bnr_chains_marginal_edges(arr, K, _ptr(w), int(first_row), int(nsamp), thin, p_lo, p_hi, *[_ptr(o) for o in out], _ptr(m),
                                                     _ptr(v), C.byref(nb)))
     return tuple(out), m, v, nb.value
+
+
+# ------------------------------------------------------------------------------------------ Rao-Blackwellised prediction of new rows (libbnr_mpred.so, include/bnr_mpred.h)
+MPRED_SUMMARY_FIELDS = ("mean", "sd", "var_within", "lower", "upper", "pred_sd", "pred_lower", "pred_upper", "lpd", "pit")
+
+
+def mpred_set_option(name, value):
+    check(mpred_lib().bnr_mpred_set_option(name.encode(), int(value)))
+
+
+def marginal_predict_raw(X, y, X_new, tau2, mu, S, W=None, device=0):
+    """(mean, var (D x m each), n_bad): the conditional mean and variance of the mean response of every row of X_new (m x q) given each of D draws
+    phi = (tau2, mu, S, W) for one n x q model matrix, on the device (bnr_marginal_predict).  ValueError (before any library call) for shapes
+    that do not fit or n > 2048"""
+    Xf = np.asfortranarray(X, dtype=np.float64)
+    if Xf.ndim != 2 or Xf.shape[0] < 1 or Xf.shape[1] < 1:
+        raise ValueError("X must be an n x q matrix with n, q >= 1")
+    n, q = Xf.shape
+    if n > MLOO_MAX_N:
+        raise ValueError("n = %d: more than %d rows are not supported by this version" % (n, MLOO_MAX_N))
+    Xn = np.asfortranarray(X_new, dtype=np.float64)
+    if Xn.ndim != 2 or Xn.shape[0] < 1 or Xn.shape[1] != q:
+        raise ValueError("X_new must be an m x q matrix with m >= 1 and the q columns of X")
+    m = Xn.shape[0]
+    yf = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+    t2 = np.ascontiguousarray(np.atleast_1d(np.asarray(tau2, dtype=np.float64))).reshape(-1)
+    D = t2.size
+    mu_ = np.ascontiguousarray(np.atleast_1d(np.asarray(mu, dtype=np.float64))).reshape(-1)
+    Sf = np.ascontiguousarray(np.asarray(S, dtype=np.float64).reshape(-1, q))
+    Wf = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1, q))
+    if yf.shape != (n,) or D < 1 or mu_.shape != (D,) or Sf.shape != (D, q) or (Wf is not None and Wf.shape != (D, q)):
+        raise ValueError("need y (n,), tau2 and mu (D,), S and W (D, q) for X (n, q)")
+    mean, var = np.empty((D, m)), np.empty((D, m))
+    nb = C.c_int32(0)
+    check(_device_mpred().bnr_marginal_predict(int(device), n, q, m, D, _ptr(Xf), _ptr(yf), _ptr(Xn), _ptr(t2), _ptr(mu_), _ptr(Sf), _ptr(Wf),
+                                               _ptr(mean), _ptr(var), C.byref(nb)))
+    return mean, var, nb.value
+
+
+def mixture_score_raw(mean, vobs, y, nchains=1, weights=None, device=0, fields=("lpd", "pit")):
+    """(lpd, pit) (m values each) of the responses y under the mixtures of normals in the columns of the (nchains nd) x m matrices mean, vobs,
+    on the device (bnr_mixture_score); an entry not named in `fields` is not requested and comes back as None"""
+    mf, vf = np.ascontiguousarray(mean, dtype=np.float64), np.ascontiguousarray(vobs, dtype=np.float64)
+    K = int(nchains)
+    if mf.ndim != 2 or mf.shape != vf.shape or K < 1 or mf.shape[1] < 1 or mf.shape[0] < K or mf.shape[0] % K:
+        raise ValueError("mean and vobs must be (nchains * nd) x m matrices of one shape with nd, m >= 1")
+    D, m = mf.shape
+    yf = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+    if yf.shape != (m,):
+        raise ValueError("y must hold one response per column of mean")
+    fields = tuple(fields)
+    if not fields or [f for f in fields if f not in ("lpd", "pit")]:
+        raise ValueError("fields must name lpd or pit, not %r" % (fields,))
+    w = None if weights is None else stack_weights_array(weights, K)
+    out = [np.empty(m) if f in fields else None for f in ("lpd", "pit")]
+    check(_device_mpred().bnr_mixture_score(int(device), m, K, D // K, _ptr(mf), _ptr(vf), _ptr(yf), _ptr(w), _ptr(out[0]), _ptr(out[1])))
+    return tuple(out)
+
+
+def chains_marginal_predict(chains, first_row, nsamp, X_new, y_new=None, thin=1, weights=None, p_lo=0.025, p_hi=0.975, per_draw=False,
+                            fields=None):
+    """(the tuple MPRED_SUMMARY_FIELDS (m,) -- lpd and pit None without y_new --, mean, var (K nd x m) or None, n_bad) over rows first_row + j thin
+    of every chain listed, for the rows of the dense m x q matrix X_new (bnr_chains_marginal_predict)"""
+    c0, (arr, K) = _pooled(chains)
+    thin, nd = mloo_thin_draws(nsamp, thin)
+    if c0.n > MLOO_MAX_N:
+        raise ValueError("n = %d: more than %d rows are not supported by this version" % (c0.n, MLOO_MAX_N))
+    q = c0.q
+    Xn = np.asfortranarray(X_new, dtype=np.float64)
+    if Xn.ndim != 2 or Xn.shape[0] < 1 or Xn.shape[1] != q:
+        raise ValueError("X_new must be an m x q matrix with m >= 1 and q = %d columns" % q)
+    m = Xn.shape[0]
+    yn = None if y_new is None else np.ascontiguousarray(y_new, dtype=np.float64).reshape(-1)
+    if yn is not None and yn.shape != (m,):
+        raise ValueError("y_new must hold one response per row of X_new")
+    w = None if weights is None else stack_weights_array(weights, K)
+    p_lo, p_hi = loo_probs(p_lo, p_hi)
+    if fields is None:
+        fields = MPRED_SUMMARY_FIELDS if yn is not None else MPRED_SUMMARY_FIELDS[:8]
+    fields = tuple(fields)
+    if (not fields and not per_draw) or [f for f in fields if f not in MPRED_SUMMARY_FIELDS] or (("lower" in fields) != ("upper" in fields)) \
+            or (("pred_lower" in fields) != ("pred_upper" in fields)) or (yn is None and set(fields) & {"lpd", "pit"}):
+        raise ValueError("fields must name some of %r, lower and upper together, lpd and pit only with y_new, not %r" % (MPRED_SUMMARY_FIELDS, fields))
+    out = [np.empty(m) if f in fields else None for f in MPRED_SUMMARY_FIELDS]
+    dm, dv = (np.empty((K * nd, m)), np.empty((K * nd, m))) if per_draw else (None, None)
+    nb = C.c_int32(0)
+    check(_device_mpred().bnr_chains_marginal_predict(arr, K, _ptr(w), int(first_row), int(nsamp), thin, _ptr(Xn), m, _ptr(yn), p_lo, p_hi,
+                                                      *[_ptr(o) for o in out], _ptr(dm), _ptr(dv), C.byref(nb)))
+    return tuple(out), dm, dv, nb.value
 
 
 class Comm:

@@ -115,6 +115,7 @@ class Results:
     marginal_edges: "MarginalEdges" = None   # filled on request (marginal_edges=True): the edge table with gamma integrated out, computed on the GPU (see MarginalEdges)
     stat_chains: int = None          # how many chains the device statistics above (summary_device, prediction, waic, loo, loo_predictive) cover: 1 (chain 1's window), or
                                      # every chain of the fit with pool_chains=True; None when the fit computed none
+    marginal_prediction: "MarginalPrediction" = None   # filled on request (marginal_predict=True): the prediction of predict_X with gamma integrated out, computed on the GPU (see MarginalPredict)
 
 
 @dataclass
@@ -2100,6 +2101,187 @@ def _marginal_edges_of(results, X=None, y=None, x_transform=True):
     return _host_marginal_edges([results.state], _dense_rows(xi), y, results.burn_in, results.sampled)
 
 
+# ------------------------------------------------------------------------------------------ Rao-Blackwellised prediction of new rows (an addition to the reference)
+# The prediction of new rows with gamma integrated out (include/bnr_mpred.h, libbnr_mpred.so; DESIGN.md section 8, "Rao-Blackwellised prediction").
+# Given phi = (tau2, mu, u, lambda, S) of a table row, the mean response of a new row x* is N(mean, var) in closed form, so its posterior is the
+# mixture of those normals over the draws of phi and the predictive distribution of a new observation the same mixture with var + tau2: no
+# within-draw noise of gamma, no predictive noise to draw.  The _host_* functions restate the definitions in numpy: the fallback of
+# MarginalPredict and the yardstick of the tests.
+_LOG_2PI = 1.8378770664093454835606594728112      # (MLOO_LOG_2PI of csrc/bnr_mloo_kernels.h)
+_MPRED_FIELDS = ("estimate", "sd", "lower_bound", "upper_bound", "var_within", "pred_sd", "pred_lower_bound", "pred_upper_bound", "lpd", "elpd", "pit",
+                 "interval", "chains", "draws", "thin", "n_bad", "weights", "mean", "var")
+
+
+def _host_predict_terms(X, y, X_new, tau2, mu, S, W=None):
+    """(mean, var (D x m), n_bad) of D draws for one n x q matrix X and the m x q new rows X_new: the definitions of include/bnr_mpred.h in numpy,
+    per draw np.linalg.cholesky of A = I + X diag(S) X^T, C = (X S) X*^T, T = L^-1 C by a triangular solve (t_j = its column norms squared),
+    g = A^-1 r by two, h = C^T g, a = X* W, d_j = sum_e (x*_je S_e) x*_je, mean = (mu + a) + h, var = tau2 max(d - t, 0).  A draw whose S, tau2
+    or mu is not finite or whose A is not positive definite is NaN and counted"""
+    X = np.asarray(X, dtype=np.float64)
+    Xn = np.asarray(X_new, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    n, q = X.shape
+    m = Xn.shape[0]
+    tau2, mu = np.atleast_1d(np.asarray(tau2, dtype=np.float64)), np.atleast_1d(np.asarray(mu, dtype=np.float64))
+    D = tau2.size
+    S = np.asarray(S, dtype=np.float64).reshape(D, q)
+    W = None if W is None else np.asarray(W, dtype=np.float64).reshape(D, q)
+    mean, var = np.full((D, m), np.nan), np.full((D, m), np.nan)
+    n_bad = 0
+    eye = np.eye(n)
+    for s in range(D):
+        ok = np.isfinite(tau2[s]) and np.isfinite(mu[s]) and np.all(np.isfinite(S[s]))
+        L = None
+        if ok:
+            XS = X * S[s][None, :]
+            try:
+                L = np.linalg.cholesky(eye + XS @ X.T)
+            except np.linalg.LinAlgError:
+                L = None
+            if L is not None and not np.all(np.isfinite(L)):
+                L = None
+        if L is None:
+            n_bad += 1
+            continue
+        r = y - mu[s] - (X @ W[s] if W is not None else 0.0)
+        Cm = XS @ Xn.T
+        T = _solve_lower(L, Cm)
+        t = np.sum(T * T, axis=0)
+        z = _solve_lower(L, r)
+        g = _solve_lower(L[::-1, ::-1].T, z[::-1])[::-1]       # L^T g = z, as a lower triangular solve of the reversed system
+        a = Xn @ W[s] if W is not None else 0.0
+        d = np.sum((Xn * S[s][None, :]) * Xn, axis=1)
+        mean[s] = (mu[s] + a) + Cm.T @ g
+        var[s] = tau2[s] * np.fmax(d - t, 0.0)
+    return mean, var, n_bad
+
+
+def _host_mixture_score(mean, vobs, y, nchains=1, weights=None):
+    """bnr_mixture_score restated in numpy with its summation order: dict of lpd, pit (m,) for the (nchains nd) x m matrices mean, vobs and the
+    responses y (m,).  A component with vobs = 0 is the point mass at mean (pit: [y >= mean]; lpd: nothing unless y == mean, then +inf; -inf where
+    every weighted component is a point mass elsewhere); a row with a NaN y, a NaN mean or vobs in any draw of any chain or a vobs < 0 is NaN in
+    both.  pit agrees with the device bit for bit where no erfc is involved, otherwise to erfc's rounding; lpd to the rounding of exp and log"""
+    me, vo = np.asarray(mean, dtype=np.float64), np.asarray(vobs, dtype=np.float64)
+    K = int(nchains)
+    D, m = me.shape
+    nd = D // K
+    yv = np.asarray(y, dtype=np.float64).reshape(m)
+    w = np.full(K, 1.0 / K) if weights is None else np.asarray(weights, dtype=np.float64).reshape(K)
+    h = 0.70710678118654752440
+    with np.errstate(all="ignore"):
+        dlt = yv[None, :] - me
+        point = vo == 0.0
+        l = np.where(point, np.where(dlt == 0.0, np.inf, -np.inf), -0.5 * (_LOG_2PI + np.log(vo)) - 0.5 * ((dlt * dlt) / vo))
+        nan = np.isnan(yv) | np.any(np.isnan(me) | np.isnan(vo) | np.isnan(l), axis=0)
+        pit = _medge_stat(np.where(point, (yv[None, :] >= me).astype(np.float64), 0.5 * _erfc((dlt / np.sqrt(vo)) * -h)), K, w)
+        on = np.repeat(w > 0.0, nd)
+        mx = np.max(np.where(np.isnan(l[on]), -np.inf, l[on]), axis=0)
+        tot = np.zeros(m)
+        fin = np.isfinite(mx)
+        mxs = np.where(fin, mx, 0.0)
+        for k in range(K):
+            if w[k] > 0.0:
+                lk = np.where(point[k * nd:(k + 1) * nd], -np.inf, l[k * nd:(k + 1) * nd])
+                tot = tot + (_medge_chain_sum(np.exp(lk - mxs[None, :])) / float(nd)) * w[k]
+        lpd = np.where(fin, mxs + np.log(tot), mx)
+    return dict(lpd=np.where(nan, np.nan, lpd), pit=np.where(nan, np.nan, pit))
+
+
+class MarginalPrediction:
+    """The prediction of new rows with gamma integrated out.  estimate, sd: the mean and standard deviation of the mixture sum_s omega_s
+    N(mean_sj, var_sj), the posterior of the mean response of every new row; lower_bound / upper_bound: its central interval% interval;
+    var_within: sum_s omega_s var_sj; pred_sd, pred_lower_bound / pred_upper_bound: the same of the predictive distribution of a new observation,
+    the mixture with var + tau2; lpd, pit: the log predictive density and the probability integral transform of the observed y_new under it (None
+    without y_new), elpd: the sum of lpd.  Derived: rb_share = var_within / sd^2 -- the share of the posterior variance of the mean response that
+    Rao-Blackwellisation removes from the estimator's noise.  chains, draws, thin: what was pooled; n_bad: the draws that could not be factorised
+    (every summary is NaN while n_bad > 0); weights: the chain weights, or None; mean, var: the per-draw conditional means and variances (draws x
+    m), or None.  MarginalPrediction(**fields) builds the record from exactly the fields above; MarginalPredict is the accessor of a fit."""
+
+    def __init__(self, **fields):
+        if set(fields) != set(_MPRED_FIELDS):
+            raise TypeError("MarginalPrediction takes exactly the fields %r" % (_MPRED_FIELDS,))
+        self.__dict__.update(fields)
+
+    def __repr__(self):
+        return "MarginalPrediction(rows=%d, chains=%d, draws=%d%s)" % (self.estimate.size, self.chains, self.draws, "" if self.weights is None else ", weighted")
+
+    @property
+    def rb_share(self):
+        """var_within / sd^2 (NaN where sd is 0)"""
+        with np.errstate(all="ignore"):
+            return np.where(self.sd > 0, self.var_within / (self.sd * self.sd), np.nan)
+
+
+def _marginal_prediction(stats, mean, var, interval, nchains, draws, thin, n_bad, weights):
+    lpd = stats.get("lpd")
+    return MarginalPrediction(estimate=stats["mean"], sd=stats["sd"], lower_bound=stats["lower"], upper_bound=stats["upper"], var_within=stats["var_within"],
+                              pred_sd=stats["pred_sd"], pred_lower_bound=stats["pred_lower"], pred_upper_bound=stats["pred_upper"], lpd=lpd,
+                              elpd=None if lpd is None else float(np.sum(lpd)), pit=stats.get("pit"), interval=interval, chains=int(nchains),
+                              draws=int(draws), thin=int(thin), n_bad=int(n_bad), weights=None if weights is None else np.array(weights, dtype=np.float64),
+                              mean=mean, var=var)
+
+
+def marginal_predict_terms(X, y, X_new, tau2, mu, S, W=None, device=None):
+    """The conditional posterior of the mean response of every row of X_new (m x q) given each of D draws phi = (tau2, mu, S, W), for one n x q
+    model matrix, on the GPU (bnr_marginal_predict): dict with mean, var (D x m: eta*_j | phi, y ~ N(mean, var); a new observation has
+    var + tau2) and n_bad.  tau2, mu: (D,); S, W: (D, q), W None = 0"""
+    mean, var, nb = _capi.marginal_predict_raw(X, y, X_new, tau2, mu, S, W, 0 if device is None else int(device))
+    return dict(mean=mean, var=var, n_bad=nb)
+
+
+def mixture_score(mean, vobs, y, nchains=1, weights=None, device=None):
+    """The log predictive density and the PIT of the responses y (m,) under the m mixtures of normals in the columns of the (nchains nd) x m
+    matrices mean, vobs (chain k's draws in rows k nd ..) on the GPU (bnr_mixture_score): dict with lpd, pit (m,)"""
+    lpd, pit = _capi.mixture_score_raw(mean, vobs, y, nchains, weights, 0 if device is None else int(device))
+    return dict(lpd=lpd, pit=pit)
+
+
+def device_marginal_predict(chains, nburn, nsamp, X_new, y_new=None, thin=1, weights=None, interval=95, per_draw=False, x_transform=False):
+    """The prediction of the rows X_new (y_new: their observed responses, or None) with gamma integrated out over rows nburn + 1 + j thin
+    (j = 0 .. ceil(nsamp / thin) - 1) of ALL the chains listed, pooled (under `weights`, the chain weights, where given), on the GPU
+    (bnr_chains_marginal_predict) -> MarginalPrediction.  The per-draw mean and var stay on the device unless per_draw=True asks for them."""
+    chains = list(chains)
+    thin, nd = _capi.mloo_thin_draws(nsamp, thin)
+    p_lo, p_hi = _loo_interval_probs(interval)
+    xi = _new_rows(X_new, x_transform, chains[0].q, y_new)
+    out, dm, dv, nb = _capi.chains_marginal_predict(chains, nburn + 1, nsamp, _dense_rows(xi), y_new, thin, weights, p_lo, p_hi, per_draw)
+    return _marginal_prediction(dict(zip(_capi.MPRED_SUMMARY_FIELDS, out)), dm, dv, interval, len(chains), nd * len(chains), thin, nb, weights)
+
+
+def _host_marginal_predict(states, X, y, X_new, y_new, nburn, nsamp, thin=1, weights=None, interval=95, per_draw=False):
+    """device_marginal_predict restated in numpy over the fetched tables of the same chains, the training X (n x q), y and the dense new rows
+    X_new (m x q)"""
+    states = list(states)
+    thin, nd = _capi.mloo_thin_draws(nsamp, thin)
+    p_lo, p_hi = _loo_interval_probs(interval)
+    t2, mu, S, W = _host_marginal_draws(states, nburn, nsamp, thin)
+    mean, var, nb = _host_predict_terms(X, y, X_new, t2, mu, S, W)
+    vobs = var + t2[:, None]
+    K = len(states)
+    eta = _host_mixture_summary(mean, var, K, weights, p_lo, p_hi)
+    obs = _host_mixture_summary(mean, vobs, K, weights, p_lo, p_hi)
+    stats = dict(mean=eta["mean"], sd=eta["sd"], var_within=eta["var_within"], lower=eta["lower"], upper=eta["upper"], pred_sd=obs["sd"],
+                 pred_lower=obs["lower"], pred_upper=obs["upper"])
+    if y_new is not None:
+        stats.update(_host_mixture_score(mean, vobs, y_new, K, weights))
+    return _marginal_prediction(stats, mean if per_draw else None, var if per_draw else None, interval, K, nd * K, thin, nb, weights)
+
+
+def MarginalPredict(results, X=None, y=None, X_new=None, y_new=None, x_transform=True):
+    """The accessor of a fit's prediction with gamma integrated out -> MarginalPrediction: the GPU's numbers when the fit carried them
+    (marginal_predict=True), otherwise restated on the host over results.state (needs return_state=True, the training X, y and the new rows X_new;
+    chain 1's window, every draw)."""
+    if results.marginal_prediction is not None:
+        return results.marginal_prediction
+    if results.state is None or X is None or y is None or X_new is None:
+        raise ValueError("MarginalPredict needs Fit(..., marginal_predict=True), or the state table (return_state=True) together with the training X, y "
+                         "and the new rows")
+    q = results.state["gamma"].shape[1]
+    xi = _new_rows(X, x_transform, q, y)
+    xn = _new_rows(X_new, x_transform, q, y_new)
+    return _host_marginal_predict([results.state], _dense_rows(xi), y, _dense_rows(xn), y_new, results.burn_in, results.sampled)
+
+
 # ------------------------------------------------------------------------------------------ chain placement
 def _dist():
     """torch.distributed if THE CALLER has imported and initialised it, else None.  Never imports torch itself: a process group can only
@@ -2345,6 +2527,7 @@ class _Requests:
     edge_cov: object = None          # None, "all", or the 0-based edge indices (int32)
     marginal_loo: int = None         # the draws per chain of the marginal PSIS-LOO (marginal_loo_draws), or None
     marginal_edges: tuple = None     # (the draws per chain of the Rao-Blackwellised edge table (marginal_edges_draws), interval), or None
+    marginal_predict: int = None     # the draws per chain of the Rao-Blackwellised prediction of predict_X (marginal_predict_draws), or None
 
 
 def _one_rank(option):
@@ -2357,7 +2540,7 @@ def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, retur
                   predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None, pool_chains=False, predict_observation=False,
                   pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False, hdi_prob=0.95, fdr=0.05, node_sets=False,
                   top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False, marginal_loo_draws=2000, marginal_edges=False,
-                  marginal_edges_draws=2000):
+                  marginal_edges_draws=2000, marginal_predict=False, marginal_predict_draws=2000):
     """The options of a fit (Fit's keywords) checked before any sampling, in this order -> _Requests.  Fit itself calls it ahead of
     parameters.log for the refusals alone, without X_new and nsamp: what needs them -- the new rows, the lag window of the rank diagnostics,
     r_eff -- is then left to generate_samples / generate_samples_dbl."""
@@ -2413,10 +2596,21 @@ def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, retur
         me = (int(marginal_edges_draws), predict_interval)
         if X_new is not None and X_new.n > MLOO_MAX_N:
             raise ValueError("marginal_edges takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
+    mp_ = None
+    if marginal_predict:
+        if predict_X is None:
+            raise ValueError("marginal_predict needs predict_X")
+        _one_rank("marginal_predict")
+        if isinstance(marginal_predict_draws, bool) or int(marginal_predict_draws) != marginal_predict_draws or int(marginal_predict_draws) < 1:
+            raise ValueError("marginal_predict_draws must be an integer >= 1, not %r" % (marginal_predict_draws,))
+        _loo_interval_probs(predict_interval)
+        mp_ = int(marginal_predict_draws)
+        if X_new is not None and X_new.n > MLOO_MAX_N:
+            raise ValueError("marginal_predict takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
     if X_new is not None:
         _capi.r_eff_array(loo_r_eff, X_new.n)
     return _Requests(return_state, summary_interval, ess_max_lag, pred, bool(waic), bool(loo), loo_r_eff, bool(pool_chains), bool(predict_observation),
-                     pred_seed, lp, bool(rank_diagnostics), es, ntop, bool(stack_chains), ec, ml, me)
+                     pred_seed, lp, bool(rank_diagnostics), es, ntop, bool(stack_chains), ec, ml, me, mp_)
 
 
 def _finish(chainset, res, req, seed):
@@ -2450,6 +2644,9 @@ def _finish(chainset, res, req, seed):
     if req.marginal_edges is not None and req.stack:
         res.stacking.marginal_edges = device_marginal_edges(every, nb, ns, _marginal_loo_thin(ns, req.marginal_edges[0]), res.stacking.weights,
                                                             req.marginal_edges[1])
+    if req.marginal_predict is not None and req.stack:                  # (set only when asked for)
+        res.stacking.marginal_prediction = device_marginal_predict(every, nb, ns, req.predict[0], req.predict[1], _marginal_loo_thin(ns, req.marginal_predict),
+                                                                   res.stacking.weights, req.predict[2])
     if req.node_sets is not None:
         res.node_sets = device_node_sets(every, nb, ns, req.node_sets)
     if req.edge_sel is not None:
@@ -2488,6 +2685,9 @@ def _finish(chainset, res, req, seed):
         res.marginal_loo = device_marginal_loo(chains, nb, ns, _marginal_loo_thin(ns, req.marginal_loo), req.loo_r_eff)
     if req.marginal_edges is not None:
         res.marginal_edges = device_marginal_edges(chains, nb, ns, _marginal_loo_thin(ns, req.marginal_edges[0]), None, req.marginal_edges[1])
+    if req.marginal_predict is not None:
+        res.marginal_prediction = device_marginal_predict(chains, nb, ns, req.predict[0], req.predict[1], _marginal_loo_thin(ns, req.marginal_predict), None,
+                                                          req.predict[2])
     if (req.summary_interval is not None or req.predict is not None or req.waic or req.loo or req.loo_predict is not None
             or req.marginal_loo is not None or req.marginal_edges is not None):
         res.stat_chains = len(chains)
@@ -2524,7 +2724,8 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                      xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
                      pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
                      hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
-                     marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000):
+                     marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000,
+        marginal_predict=False, marginal_predict_draws=2000):
     """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
     xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
     xi_weights_code(xi_weights)
@@ -2539,7 +2740,8 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                         rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets,
                         top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
                         marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
-                        marginal_edges_draws=marginal_edges_draws)       # (checked before any sampling)
+                        marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
+                        marginal_predict_draws=marginal_predict_draws)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -2593,7 +2795,8 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                          xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
                          pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
                          hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
-                         marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000):
+                         marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000,
+        marginal_predict=False, marginal_predict_draws=2000):
     """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
     xi_weights_code(xi_weights)
     if nu == R:
@@ -2607,7 +2810,8 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                         rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets,
                         top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
                         marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
-                        marginal_edges_draws=marginal_edges_draws)       # (checked before any sampling)
+                        marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
+                        marginal_predict_draws=marginal_predict_draws)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -2662,7 +2866,8 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
         xi_weights="log", predict_X=None, predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None,
         pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
         hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
-        marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000):
+        marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000,
+        marginal_predict=False, marginal_predict_draws=2000):
     """Fit! (gibbs.jl:725-751).  The `V` keyword is accepted and ignored, as in the reference.
     Extensions: summary_interval=95 computes Summary's statistics on the GPU (Results.summary_device);
     return_state=False then leaves the (large) state table on the device and frees it; ess_max_lag=0 (default lag
@@ -2704,13 +2909,20 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     N(m_e, v_e | tau2, mu, u, lambda, S) over the draws, free of the within-draw noise of the gamma draws.  Draws, chains and limits as for
     marginal_loo (marginal_edges_draws, default 2000 per chain); with stack_chains=True also under the stacking weights over every chain
     (Results.stacking.marginal_edges).  Every other field of the Results is what it is without it.
+    marginal_predict=True adds the prediction of predict_X with gamma integrated out (Results.marginal_prediction, see MarginalPrediction and
+    device_marginal_predict): per new row the mean, sd and interval of the mixture of N(mean_j, var_j | tau2, mu, u, lambda, S) over the draws, the
+    predictive sd and interval of a new observation and, with predict_y, lpd / elpd and the PIT -- no predictive noise is drawn, so pred_seed plays
+    no part.  It needs predict_X; predict_y and predict_interval are used as given.  Draws, chains and limits as for marginal_loo
+    (marginal_predict_draws, default 2000 per chain); with stack_chains=True also under the stacking weights over every chain
+    (Results.stacking.marginal_prediction).  Every other field of the Results is what it is without it.
     parameters.log keeps the reference's lines only."""
     xi_weights_code(xi_weights)
     _fit_requests(y, num_chains, predict_X=predict_X, predict_interval=predict_interval, pool_chains=pool_chains,
                   predict_observation=predict_observation, loo_predict=loo_predict, rank_diagnostics=rank_diagnostics,
                   edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains,
                   edge_cov=edge_cov, marginal_loo=marginal_loo, marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
-                        marginal_edges_draws=marginal_edges_draws)
+                        marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
+                        marginal_predict_draws=marginal_predict_draws)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
         with open(filename, "w") as f:
@@ -2733,7 +2945,8 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                                     edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr,
                                     node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov,
                                     marginal_loo=marginal_loo, marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
-                        marginal_edges_draws=marginal_edges_draws)
+                        marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
+                        marginal_predict_draws=marginal_predict_draws)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
@@ -2743,4 +2956,5 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                             loo_predict=loo_predict, rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr,
                             node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
                             marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
-                        marginal_edges_draws=marginal_edges_draws)
+                        marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
+                        marginal_predict_draws=marginal_predict_draws)

@@ -1,12 +1,14 @@
 // bnr_medge.hip -- libbnr_medge.so behind include/bnr_medge.h: Rao-Blackwellised summaries of the edge coefficients, gamma integrated out on the
 // device.  A library and a gfx950 code object of its own: the four kernels of bnr_mloo_kernels.h (by #include, through the driver shared with
-// libbnr_mloo.so, bnr_mloo_job.h) plus k_medge_proj and k_medge_summary (bnr_medge_kernels.h).  It reaches a chain through
-// bnr_chain_device_view and leaves its messages with bnr_set_last_error -- exported calls of libbnr_hip.so, nothing of bnr_internal.h.
+// libbnr_mloo.so, bnr_mloo_job.h) plus k_medge_proj and k_medge_summary (bnr_medge_kernels.h); the summary's host driver is bnr_medge_summary.h,
+// shared with libbnr_mpred.so.  It reaches a chain through bnr_chain_device_view and leaves its messages with bnr_set_last_error -- exported calls
+// of libbnr_hip.so, nothing of bnr_internal.h.
 // Linked with bnr_medge.map: only the functions of the header are exported, so that neither this library nor libbnr_mloo.so, loaded into one
 // process, can bind the other's kernel handles or host stubs.
 #include "../../include/bnr_medge.h"
 #include "bnr_medge_kernels.h"
 #include "bnr_mloo_job.h"
+#include "bnr_medge_summary.h"
 
 namespace {
 // m and v of every draw of the job, edge-major on the device (Md, Vd: q x ndraws), by k_medge_proj behind every batch's k_mloo_factor
@@ -22,72 +24,6 @@ int gamma_job(call_guard &g, mloo_job &job, double *Md, double *Vd, std::vector<
         return BNR_OK;
     };
     return run_job(g, job, ll, rs, vr, lm, bad, hook);
-}
-
-// an edge-major device matrix (q x D) to the host as D x q
-int fetch_transposed(call_guard &g, const double *dev, int q, int D, double *out)
-{
-    std::vector<double> t((size_t)q * (size_t)D);
-    HIPCHK(hipMemcpyAsync(t.data(), dev, sizeof(double) * t.size(), hipMemcpyDeviceToHost, g.st));
-    HIPCHK(hipStreamSynchronize(g.st));
-    for (int s = 0; s < D; ++s)
-        for (int e = 0; e < q; ++e) out[(size_t)s * q + e] = t[(size_t)e * D + s];
-    return BNR_OK;
-}
-
-struct summary_out { double *mean, *sd, *var_within, *p_pos, *p_neg, *lower, *upper; };
-
-// the checks of a summary's arguments that do not need the shapes; c: the bracket's half-width in sds
-int summary_check(const summary_out &o, double p_lo, double p_hi, double &c)
-{
-    if (!o.mean && !o.sd && !o.var_within && !o.p_pos && !o.p_neg && !o.lower && !o.upper) return fail(BNR_ERR_BAD_ARG, "ask for at least one summary");
-    if ((o.lower == nullptr) != (o.upper == nullptr)) return fail(BNR_ERR_BAD_ARG, "lower and upper come together");
-    c = 1.0;
-    if (o.lower) {
-        if (!(p_lo > 0.0 && p_lo < p_hi && p_hi < 1.0)) return fail(BNR_ERR_BAD_ARG, "need 0 < p_lo < p_hi < 1");
-        const double pm = 0.5 * std::min(p_lo, 1.0 - p_hi);
-        for (c = 1.0; !(0.5 * std::erfc(c * 0.70710678118654752440) < pm) && c < 40.0; c += 0.5) { }
-    }
-    return BNR_OK;
-}
-
-// the chain weights of a summary: as given after bnr_chains_wsummary's checks, or 1 / K each
-int summary_weights(const double *weights, int K, std::vector<double> &w)
-{
-    w.assign((size_t)K, 1.0 / (double)K);
-    if (!weights) return BNR_OK;
-    if (K > 32) return fail(BNR_ERR_BAD_ARG, "need 1 <= nchains <= 32 for a weighted call");
-    double s = 0.0;
-    bool any = false;
-    for (int k = 0; k < K; ++k) {
-        if (!std::isfinite(weights[k]) || weights[k] < 0.0) return fail(BNR_ERR_BAD_ARG, "weights must be finite and >= 0");
-        any = any || weights[k] > 0.0;
-        s += weights[k];
-        w[k] = weights[k];
-    }
-    if (!any) return fail(BNR_ERR_BAD_ARG, "at least one weight must be > 0");
-    if (!(std::fabs(s - 1.0) <= 1e-9)) return fail(BNR_ERR_BAD_ARG, "weights must sum to 1 (within 1e-9)");
-    return BNR_OK;
-}
-
-// k_medge_summary on the edge-major device matrices Md, Vd (q x K nd) and its results to the host
-int summary_run(call_guard &g, int q, int K, int nd, const double *Md, const double *Vd, const std::vector<double> &w, double c, double p_lo, double p_hi,
-                const summary_out &o)
-{
-    int rc;
-    double *wd = nullptr, *out = nullptr;
-    if ((rc = g.upload(&wd, w.data(), (size_t)K))) return rc;
-    if ((rc = g.alloc(&out, (size_t)7 * q))) return rc;
-    double *host[7] = {o.mean, o.sd, o.var_within, o.p_pos, o.p_neg, o.lower, o.upper}, *dev[7];
-    for (int f = 0; f < 7; ++f) dev[f] = host[f] ? out + (size_t)f * q : nullptr;
-    hipLaunchKernelGGL(k_medge_summary, dim3((q + 3) / 4), dim3(256), 0, g.st, Md, Vd, (long long)K * nd, q, K, nd, (const double *)wd, c, p_lo, p_hi, dev[0],
-                       dev[1], dev[2], dev[3], dev[4], dev[5], dev[6]);
-    HIPCHK(hipGetLastError());
-    for (int f = 0; f < 7; ++f)
-        if (host[f]) HIPCHK(hipMemcpyAsync(host[f], dev[f], sizeof(double) * (size_t)q, hipMemcpyDeviceToHost, g.st));
-    HIPCHK(hipStreamSynchronize(g.st));
-    HIPCHK(hipGetLastError());
-    return BNR_OK;
 }
 }   // namespace
 
