@@ -232,73 +232,58 @@ def lib():
     return _lib
 
 
+def _side_lib(path, sigs, what):
+    """Load the library at `path` that is linked against libbnr_hip.so, after it, and give its functions the signatures `sigs`; raises if it has
+    not been built"""
+    lib()
+    if not os.path.exists(path):
+        raise ImportError("%s is missing at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'`; there is no CPU fallback"
+                          % (what, path))
+    L = C.CDLL(path)
+    for name, (res, args) in sigs.items():
+        f = getattr(L, name)
+        f.restype = res
+        f.argtypes = args
+    return L
+
+
 def mloo_lib():
     """Load libbnr_mloo.so, after libbnr_hip.so (which it is linked against); raises if it has not been built"""
     global _mloo
-    if _mloo is None:
-        lib()
-        if not os.path.exists(MLOO_LIB):
-            raise ImportError("libbnr_mloo.so is missing at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'`; there is no "
-                              "CPU fallback" % MLOO_LIB)
-        L = C.CDLL(MLOO_LIB)
-        for name, (res, args) in _MLOO_SIGS.items():
-            f = getattr(L, name)
-            f.restype = res
-            f.argtypes = args
-        _mloo = L
+    _mloo = _mloo or _side_lib(MLOO_LIB, _MLOO_SIGS, "libbnr_mloo.so")
     return _mloo
 
 
 def medge_lib():
     """Load libbnr_medge.so, after libbnr_hip.so (which it is linked against); raises if it has not been built"""
     global _medge
-    if _medge is None:
-        lib()
-        if not os.path.exists(MEDGE_LIB):
-            raise ImportError("libbnr_medge.so is missing at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'`; there is no "
-                              "CPU fallback" % MEDGE_LIB)
-        L = C.CDLL(MEDGE_LIB)
-        for name, (res, args) in _MEDGE_SIGS.items():
-            f = getattr(L, name)
-            f.restype = res
-            f.argtypes = args
-        _medge = L
+    _medge = _medge or _side_lib(MEDGE_LIB, _MEDGE_SIGS, "libbnr_medge.so")
     return _medge
 
 
 def mpred_lib():
     """Load libbnr_mpred.so, after libbnr_hip.so (which it is linked against); raises if it has not been built"""
     global _mpred
-    if _mpred is None:
-        lib()
-        if not os.path.exists(MPRED_LIB):
-            raise ImportError("libbnr_mpred.so is missing at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'`; there is no "
-                              "CPU fallback" % MPRED_LIB)
-        L = C.CDLL(MPRED_LIB)
-        for name, (res, args) in _MPRED_SIGS.items():
-            f = getattr(L, name)
-            f.restype = res
-            f.argtypes = args
-        _mpred = L
+    _mpred = _mpred or _side_lib(MPRED_LIB, _MPRED_SIGS, "libbnr_mpred.so")
     return _mpred
 
 
-def _device_mpred():
-    """mpred_lib() for the calls that open a device, refused like _device_lib()"""
+def _device_side(side_lib):
+    """side_lib() for the calls that open a device, refused like _device_lib()"""
     _device_lib()
-    return mpred_lib()
+    return side_lib()
+
+
+def _device_mpred():
+    return _device_side(mpred_lib)
 
 
 def _device_medge():
-    """medge_lib() for the calls that open a device, refused like _device_lib()"""
-    _device_lib()
-    return medge_lib()
+    return _device_side(medge_lib)
 
 
 def _device_mloo():
-    """mloo_lib() for the calls that open a device, refused like _device_lib()"""
-    _device_lib()
-    return mloo_lib()
+    return _device_side(mloo_lib)
 
 
 def _device_lib():
@@ -1104,10 +1089,9 @@ def mloo_set_option(name, value):
     check(mloo_lib().bnr_mloo_set_option(name.encode(), int(value)))
 
 
-def marginal_loglik_raw(X, y, tau2, mu, S, W=None, device=0, fields=MLOO_FIELDS):
-    """(loglik, resid, var (n x D each), logml (D,), n_bad) of D draws phi = (tau2, mu, S, W) for one n x q model matrix, the edge coefficients
-    integrated out, on the device (bnr_marginal_loglik); an entry not named in `fields` is not requested and comes back as None.  ValueError
-    (before any library call) for shapes that do not fit, n > 2048 or no matrix asked for"""
+def _phi_arrays(X, y, tau2, mu, S, W):
+    """(Xf, yf, t2, mu, Sf, Wf, n, q, D): the model matrix (column-major) and D draws phi = (tau2, mu, S, W) of a raw marginal call as contiguous
+    float64 arrays; ValueError for shapes that do not fit or n > 2048"""
     Xf = np.asfortranarray(X, dtype=np.float64)
     if Xf.ndim != 2 or Xf.shape[0] < 1 or Xf.shape[1] < 1:
         raise ValueError("X must be an n x q matrix with n, q >= 1")
@@ -1117,11 +1101,19 @@ def marginal_loglik_raw(X, y, tau2, mu, S, W=None, device=0, fields=MLOO_FIELDS)
     yf = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
     t2 = np.ascontiguousarray(np.atleast_1d(np.asarray(tau2, dtype=np.float64))).reshape(-1)
     D = t2.size
-    m = np.ascontiguousarray(np.atleast_1d(np.asarray(mu, dtype=np.float64))).reshape(-1)
+    mu_ = np.ascontiguousarray(np.atleast_1d(np.asarray(mu, dtype=np.float64))).reshape(-1)
     Sf = np.ascontiguousarray(np.asarray(S, dtype=np.float64).reshape(-1, q))
     Wf = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1, q))
-    if yf.shape != (n,) or D < 1 or m.shape != (D,) or Sf.shape != (D, q) or (Wf is not None and Wf.shape != (D, q)):
+    if yf.shape != (n,) or D < 1 or mu_.shape != (D,) or Sf.shape != (D, q) or (Wf is not None and Wf.shape != (D, q)):
         raise ValueError("need y (n,), tau2 and mu (D,), S and W (D, q) for X (n, q)")
+    return Xf, yf, t2, mu_, Sf, Wf, n, q, D
+
+
+def marginal_loglik_raw(X, y, tau2, mu, S, W=None, device=0, fields=MLOO_FIELDS):
+    """(loglik, resid, var (n x D each), logml (D,), n_bad) of D draws phi = (tau2, mu, S, W) for one n x q model matrix, the edge coefficients
+    integrated out, on the device (bnr_marginal_loglik); an entry not named in `fields` is not requested and comes back as None.  ValueError
+    (before any library call) for shapes that do not fit, n > 2048 or no matrix asked for"""
+    Xf, yf, t2, m, Sf, Wf, n, q, D = _phi_arrays(X, y, tau2, mu, S, W)
     fields = tuple(fields)
     if [f for f in fields if f not in MLOO_FIELDS] or not set(fields) & {"loglik", "resid", "var"}:
         raise ValueError("fields must name loglik, resid or var (and logml), not %r" % (fields,))
@@ -1140,13 +1132,19 @@ def mloo_thin_draws(nsamp, thin):
     return thin, (nsamp + thin - 1) // thin
 
 
-def chains_marginal_loo(chains, first_row, nsamp, thin=1, r_eff=None, loglik=False):
-    """(elpd_loo, pareto_k, loo_mean, loo_sd (n,), logml (K draws,), loglik (n, K draws) or None, n_bad) over rows first_row + j thin of every
-    chain listed (bnr_chains_marginal_loo)"""
+def _pooled_window(chains, nsamp, thin):
+    """(the first chain, the chain array, K, thin, the draws per chain) of a chain-form marginal call; ValueError for a bad window or n > 2048"""
     c0, (arr, K) = _pooled(chains)
     thin, nd = mloo_thin_draws(nsamp, thin)
     if c0.n > MLOO_MAX_N:
         raise ValueError("n = %d: more than %d rows are not supported by this version" % (c0.n, MLOO_MAX_N))
+    return c0, arr, K, thin, nd
+
+
+def chains_marginal_loo(chains, first_row, nsamp, thin=1, r_eff=None, loglik=False):
+    """(elpd_loo, pareto_k, loo_mean, loo_sd (n,), logml (K draws,), loglik (n, K draws) or None, n_bad) over rows first_row + j thin of every
+    chain listed (bnr_chains_marginal_loo)"""
+    c0, arr, K, thin, nd = _pooled_window(chains, nsamp, thin)
     n, D = c0.n, K * nd
     r = r_eff_array(r_eff, n)
     el, kh, lm, ls, ml = np.empty(n), np.empty(n), np.empty(n), np.empty(n), np.empty(D)
@@ -1168,20 +1166,7 @@ def medge_set_option(name, value):
 def marginal_gamma_raw(X, y, tau2, mu, S, W=None, device=0):
     """(m, v (D x q each), n_bad): the conditional mean and variance of every edge coefficient given each of D draws phi = (tau2, mu, S, W) for
     one n x q model matrix, on the device (bnr_marginal_gamma).  ValueError (before any library call) for shapes that do not fit or n > 2048"""
-    Xf = np.asfortranarray(X, dtype=np.float64)
-    if Xf.ndim != 2 or Xf.shape[0] < 1 or Xf.shape[1] < 1:
-        raise ValueError("X must be an n x q matrix with n, q >= 1")
-    n, q = Xf.shape
-    if n > MLOO_MAX_N:
-        raise ValueError("n = %d: more than %d rows are not supported by this version" % (n, MLOO_MAX_N))
-    yf = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-    t2 = np.ascontiguousarray(np.atleast_1d(np.asarray(tau2, dtype=np.float64))).reshape(-1)
-    D = t2.size
-    mu_ = np.ascontiguousarray(np.atleast_1d(np.asarray(mu, dtype=np.float64))).reshape(-1)
-    Sf = np.ascontiguousarray(np.asarray(S, dtype=np.float64).reshape(-1, q))
-    Wf = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1, q))
-    if yf.shape != (n,) or D < 1 or mu_.shape != (D,) or Sf.shape != (D, q) or (Wf is not None and Wf.shape != (D, q)):
-        raise ValueError("need y (n,), tau2 and mu (D,), S and W (D, q) for X (n, q)")
+    Xf, yf, t2, mu_, Sf, Wf, n, q, D = _phi_arrays(X, y, tau2, mu, S, W)
     m, v = np.empty((D, q)), np.empty((D, q))
     nb = C.c_int32(0)
     check(_device_medge().bnr_marginal_gamma(int(device), n, q, D, _ptr(Xf), _ptr(yf), _ptr(t2), _ptr(mu_), _ptr(Sf), _ptr(Wf), _ptr(m), _ptr(v),
@@ -1214,10 +1199,7 @@ def mixture_summary_raw(m, v, nchains=1, weights=None, p_lo=0.025, p_hi=0.975, d
 def chains_marginal_edges(chains, first_row, nsamp, thin=1, weights=None, p_lo=0.025, p_hi=0.975, per_draw=False, fields=MEDGE_SUMMARY_FIELDS):
     """(the tuple MEDGE_SUMMARY_FIELDS (q,), m, v (K nd x q) or None, n_bad) over rows first_row + j thin of every chain listed
     (bnr_chains_marginal_edges)"""
-    c0, (arr, K) = _pooled(chains)
-    thin, nd = mloo_thin_draws(nsamp, thin)
-    if c0.n > MLOO_MAX_N:
-        raise ValueError("n = %d: more than %d rows are not supported by this version" % (c0.n, MLOO_MAX_N))
+    c0, arr, K, thin, nd = _pooled_window(chains, nsamp, thin)
     w = None if weights is None else stack_weights_array(weights, K)
     p_lo, p_hi = loo_probs(p_lo, p_hi)
     q = c0.q
@@ -1241,24 +1223,11 @@ def marginal_predict_raw(X, y, X_new, tau2, mu, S, W=None, device=0):
     """(mean, var (D x m each), n_bad): the conditional mean and variance of the mean response of every row of X_new (m x q) given each of D draws
     phi = (tau2, mu, S, W) for one n x q model matrix, on the device (bnr_marginal_predict).  ValueError (before any library call) for shapes
     that do not fit or n > 2048"""
-    Xf = np.asfortranarray(X, dtype=np.float64)
-    if Xf.ndim != 2 or Xf.shape[0] < 1 or Xf.shape[1] < 1:
-        raise ValueError("X must be an n x q matrix with n, q >= 1")
-    n, q = Xf.shape
-    if n > MLOO_MAX_N:
-        raise ValueError("n = %d: more than %d rows are not supported by this version" % (n, MLOO_MAX_N))
+    Xf, yf, t2, mu_, Sf, Wf, n, q, D = _phi_arrays(X, y, tau2, mu, S, W)
     Xn = np.asfortranarray(X_new, dtype=np.float64)
     if Xn.ndim != 2 or Xn.shape[0] < 1 or Xn.shape[1] != q:
         raise ValueError("X_new must be an m x q matrix with m >= 1 and the q columns of X")
     m = Xn.shape[0]
-    yf = np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
-    t2 = np.ascontiguousarray(np.atleast_1d(np.asarray(tau2, dtype=np.float64))).reshape(-1)
-    D = t2.size
-    mu_ = np.ascontiguousarray(np.atleast_1d(np.asarray(mu, dtype=np.float64))).reshape(-1)
-    Sf = np.ascontiguousarray(np.asarray(S, dtype=np.float64).reshape(-1, q))
-    Wf = None if W is None else np.ascontiguousarray(np.asarray(W, dtype=np.float64).reshape(-1, q))
-    if yf.shape != (n,) or D < 1 or mu_.shape != (D,) or Sf.shape != (D, q) or (Wf is not None and Wf.shape != (D, q)):
-        raise ValueError("need y (n,), tau2 and mu (D,), S and W (D, q) for X (n, q)")
     mean, var = np.empty((D, m)), np.empty((D, m))
     nb = C.c_int32(0)
     check(_device_mpred().bnr_marginal_predict(int(device), n, q, m, D, _ptr(Xf), _ptr(yf), _ptr(Xn), _ptr(t2), _ptr(mu_), _ptr(Sf), _ptr(Wf),
@@ -1290,10 +1259,7 @@ def chains_marginal_predict(chains, first_row, nsamp, X_new, y_new=None, thin=1,
                             fields=None):
     """(the tuple MPRED_SUMMARY_FIELDS (m,) -- lpd and pit None without y_new --, mean, var (K nd x m) or None, n_bad) over rows first_row + j thin
     of every chain listed, for the rows of the dense m x q matrix X_new (bnr_chains_marginal_predict)"""
-    c0, (arr, K) = _pooled(chains)
-    thin, nd = mloo_thin_draws(nsamp, thin)
-    if c0.n > MLOO_MAX_N:
-        raise ValueError("n = %d: more than %d rows are not supported by this version" % (c0.n, MLOO_MAX_N))
+    c0, arr, K, thin, nd = _pooled_window(chains, nsamp, thin)
     q = c0.q
     Xn = np.asfortranarray(X_new, dtype=np.float64)
     if Xn.ndim != 2 or Xn.shape[0] < 1 or Xn.shape[1] != q:

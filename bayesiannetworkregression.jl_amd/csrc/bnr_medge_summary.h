@@ -1,6 +1,6 @@
 // bnr_medge_summary.h -- the host driver of k_medge_summary that libbnr_medge.so (bnr_medge.hip) and libbnr_mpred.so (bnr_mpred.hip) share: the
-// checks of a summary's arguments, the chain weights, the launch and the way an item-major device matrix reaches the host.  Internal: included by
-// those two translation units after bnr_medge_kernels.h and bnr_mloo_job.h, each into its own library and code object; every name here has
+// checks of a summary's arguments, the chain weights, the launch and the way an item-major device matrix reaches the host (fetch_transposed) and
+// a draw-major host matrix the device (upload_transposed).  Internal: included by those two translation units after bnr_medge_kernels.h and bnr_mloo_job.h, each into its own library and code object; every name here has
 // internal linkage (the way bnr_mloo_job.h was split off bnr_mloo.hip).
 #pragma once
 #include "bnr_medge_kernels.h"
@@ -15,6 +15,18 @@ int fetch_transposed(call_guard &g, const double *dev, int q, int D, double *out
     HIPCHK(hipStreamSynchronize(g.st));
     for (int s = 0; s < D; ++s)
         for (int e = 0; e < q; ++e) out[(size_t)s * q + e] = t[(size_t)e * D + s];
+    return BNR_OK;
+}
+
+// a host (D x q) matrix, a draw's q values contiguous, to the device as q x D
+int upload_transposed(call_guard &g, const double *src, int q, int D, double **dev)
+{
+    std::vector<double> t((size_t)q * (size_t)D);
+    for (int s = 0; s < D; ++s)
+        for (int e = 0; e < q; ++e) t[(size_t)e * D + s] = src[(size_t)s * q + e];
+    int rc;
+    if ((rc = g.upload(dev, t.data(), t.size()))) return rc;
+    HIPCHK(hipStreamSynchronize(g.st));                                  // (t leaves scope)
     return BNR_OK;
 }
 

@@ -1,7 +1,8 @@
-// bnr_mloo_job.h -- the host driver that libbnr_mloo.so (bnr_mloo.hip) and libbnr_medge.so (bnr_medge.hip) share: the device memory and the
-// stream of one call (call_guard), what the batches of a call work on (mloo_job) and the batches themselves (run_job) over the kernels of
-// bnr_mloo_kernels.h.  Internal: included by those two translation units after the kernels, each into its own library and code object; every
-// name here has internal linkage, so each library launches its own copy of the kernels and keeps its own batch option.
+// bnr_mloo_job.h -- the host driver that libbnr_mloo.so (bnr_mloo.hip), libbnr_medge.so (bnr_medge.hip) and libbnr_mpred.so (bnr_mpred.hip)
+// share: the device memory and the stream of one call (call_guard), what the batches of a call work on (mloo_job), how an entry point fills it
+// in from its arguments (check_chain_list and open_chain_job for the chain form, open_raw_job for the raw form) and the batches themselves
+// (run_job) over the kernels of bnr_mloo_kernels.h.  Internal: included by those translation units after the kernels, each into its own library
+// and code object; every name here has internal linkage, so each library launches its own copy of the kernels and keeps its own batch option.
 #pragma once
 #include "../../include/bnr_mloo.h"
 #include "bnr_mloo_kernels.h"
@@ -59,6 +60,15 @@ struct call_guard {
         HIPCHK(hipMemcpyAsync(*out, src, count * sizeof(T), hipMemcpyHostToDevice, st));
         return BNR_OK;
     }
+    // count values to the host, finished when this returns; a NULL out asks for nothing
+    template <typename T>
+    int fetch(T *out, const T *dev, size_t count)
+    {
+        if (!out) return BNR_OK;
+        HIPCHK(hipMemcpyAsync(out, dev, count * sizeof(T), hipMemcpyDeviceToHost, st));
+        HIPCHK(hipStreamSynchronize(st));
+        return BNR_OK;
+    }
 };
 
 // What the batches of a call work on.  X, y on the device; per draw s of the call tau2[s], mu[s] and the pointer Sp[s] to its q values of S.
@@ -67,14 +77,79 @@ struct call_guard {
 struct mloo_job {
     int n = 0, q = 0, ndraws = 0, ldx = 0;
     const double *X = nullptr, *y = nullptr;
-    bnr_chain_view v{};                                 // chain form
+    bnr_chain_view v{};                                 // chain form: the first chain's view (its device, y, offsets and edge lists serve all)
     const double *const *rowp = nullptr;                // chain form: device array of ndraws row pointers
-    const double *const *hrow = nullptr;                // ... and the same on the host
+    std::vector<const double *> hrow;                   // ... and the same on the host
     const double *hS = nullptr, *hW = nullptr;          // raw form: host S, W
     bool chain_form = false, has_w = false;
     double *tau2 = nullptr, *mu = nullptr;              // ndraws each (raw form: uploaded; chain form: written by k_mloo_w)
     bool want_ll = false, want_resid = false, want_var = false;
 };
+
+// The checks of a chain-form call that need no chain: the counts and the list.  also: a refusal of the caller's own that ranks between the two
+// (NULL: none).
+int check_chain_list(bnr_chain *const *chains, int nchains, int thin, const char *also = nullptr)
+{
+    if (nchains < 1) return fail(BNR_ERR_BAD_ARG, "need nchains >= 1");
+    if (thin < 1) return fail(BNR_ERR_BAD_ARG, "need thin >= 1");
+    if (also) return fail(BNR_ERR_BAD_ARG, also);
+    for (int i = 0; i < nchains; ++i) {
+        if (!chains[i]) return fail(BNR_ERR_BAD_ARG, "NULL chain");
+        for (int k = 0; k < i; ++k) if (chains[k] == chains[i]) return fail(BNR_ERR_BAD_ARG, "chain listed twice");
+    }
+    return BNR_OK;
+}
+
+// The job of a chain-form call over rows first_row + j thin, j = 0 .. nd - 1, of every chain of a checked list (draw k nd + j: chain k's j-th), and
+// the call's device and stream: the chains' views and what they must share, the window, the row pointers on both sides, tau2 and mu allocated.
+int open_chain_job(call_guard &g, mloo_job &job, bnr_chain *const *chains, int nchains, int first_row, int nsamp, int thin, int &nd)
+{
+    std::vector<bnr_chain_view> v(nchains);
+    int rc;
+    for (int i = 0; i < nchains; ++i) {
+        if ((rc = bnr_chain_device_view(chains[i], &v[i]))) return rc;
+        if (v[i].device != v[0].device || v[i].n != v[0].n || v[i].V != v[0].V || v[i].R != v[0].R || v[i].rowlen != v[0].rowlen)
+            return fail(BNR_ERR_BAD_ARG, "pooled chains must live on one device and have equal n, V, R");
+    }
+    for (int i = 0; i < nchains; ++i)
+        if (first_row < 1 || nsamp < 1 || (long long)first_row + nsamp - 1 > v[i].tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
+    nd = (nsamp + thin - 1) / thin;
+    if ((long long)nchains * nd > 0x7FFFFFFFll) return fail(BNR_ERR_BAD_ARG, "more than 2^31 - 1 pooled draws");
+    const int D = nchains * nd;
+    if (v[0].n > BNR_MLOO_MAX_N) return fail(BNR_ERR_BAD_ARG, "n > 2048 is not supported by this version");
+    if ((rc = g.open(v[0].device))) return rc;
+    job.n = v[0].n; job.q = v[0].q; job.ndraws = D; job.ldx = v[0].ldx; job.X = v[0].X; job.y = v[0].y; job.v = v[0];
+    job.chain_form = true; job.has_w = true;
+    job.hrow.resize(D);
+    for (int k = 0; k < nchains; ++k)
+        for (int j = 0; j < nd; ++j) job.hrow[(size_t)k * nd + j] = v[k].trace + ((size_t)(first_row - 1) + (size_t)j * thin) * (size_t)v[k].rowlen;
+    const double **rowp = nullptr;
+    if ((rc = g.upload(&rowp, job.hrow.data(), (size_t)D))) return rc;
+    HIPCHK(hipStreamSynchronize(g.st));
+    job.rowp = rowp;
+    if ((rc = g.alloc(&job.tau2, (size_t)D))) return rc;
+    return g.alloc(&job.mu, (size_t)D);
+}
+
+// The job of a raw-form call and the call's device and stream: the checks of the shapes (also: a refusal of the caller's own that ranks between
+// them, NULL: none), X, y, tau2 and mu uploaded, S and W left to the batches.
+int open_raw_job(call_guard &g, mloo_job &job, int device, int n, int q, int ndraws, const double *X, const double *y, const double *tau2,
+                 const double *mu, const double *S, const double *W, const char *also = nullptr)
+{
+    if (n < 1 || q < 1 || ndraws < 1) return fail(BNR_ERR_BAD_ARG, "need n >= 1 rows, q >= 1 edges and ndraws >= 1 draws");
+    if (also) return fail(BNR_ERR_BAD_ARG, also);
+    if (n > BNR_MLOO_MAX_N) return fail(BNR_ERR_BAD_ARG, "n > 2048 is not supported by this version");
+    int rc;
+    if ((rc = g.open(device))) return rc;
+    job.n = n; job.q = q; job.ndraws = ndraws; job.ldx = n;
+    double *Xd = nullptr, *yd = nullptr;
+    if ((rc = g.upload(&Xd, X, (size_t)n * (size_t)q))) return rc;
+    if ((rc = g.upload(&yd, y, (size_t)n))) return rc;
+    if ((rc = g.upload(&job.tau2, tau2, (size_t)ndraws))) return rc;
+    if ((rc = g.upload(&job.mu, mu, (size_t)ndraws))) return rc;
+    job.X = Xd; job.y = yd; job.hS = S; job.hW = W; job.has_w = W != nullptr;
+    return BNR_OK;
+}
 
 // What a per-batch hook of run_job sees, everything on the device and in order on the call's stream behind the batch's k_mloo_factor: the draws
 // s0 .. s0 + nb - 1 of the call; G, draw b's L and L^-1 at G + b mat (np (np + 1) doubles, k_mloo_factor's layout); tau2, mu and Sp of draw
@@ -90,12 +165,24 @@ struct mloo_batch {
 };
 using mloo_hook = std::function<int(const mloo_batch &)>;
 
+// What run_job leaves: on the device (the call_guard's) n x ndraws loglik / resid / var (those wanted, else NULL) and logml (ndraws); on the host
+// the bad flags.
+struct mloo_out {
+    const double *loglik = nullptr, *resid = nullptr, *var = nullptr, *logml = nullptr;
+    std::vector<int> bad;
+};
+int count_bad(const std::vector<int> &bad)
+{
+    int nb = 0;
+    for (int f : bad) nb += f != 0;
+    return nb;
+}
+
 int round_up(int a, int b) { return (a + b - 1) / b * b; }
 
-// the batches of a call; on return (status OK, stream synchronised) the host vectors hold n x ndraws loglik / resid / var (those wanted), logml and
-// the bad flags.  hook (optional): called once per batch, after the batch's k_mloo_factor was enqueued and before the next batch touches G.
-int run_job(call_guard &g, mloo_job &job, std::vector<double> &ll, std::vector<double> &resid, std::vector<double> &var, std::vector<double> &logml,
-            std::vector<int> &bad, const mloo_hook &hook = nullptr)
+// the batches of a call; on return (status OK, stream synchronised) out is filled in.  hook (optional): called once per batch, after the batch's
+// k_mloo_factor was enqueued and before the next batch touches G.
+int run_job(call_guard &g, mloo_job &job, mloo_out &out, const mloo_hook &hook = nullptr)
 {
     const int n = job.n, q = job.q, D = job.ndraws, np = round_up(n, MLOO_TILE);
     const size_t mat = (size_t)np * (size_t)(np + 1);   // a draw's L and, above it, L^-1 (k_mloo_factor)
@@ -149,13 +236,9 @@ int run_job(call_guard &g, mloo_job &job, std::vector<double> &ll, std::vector<d
         }
         if (!job.chain_form) HIPCHK(hipStreamSynchronize(g.st));   // (the next batch's uploads overwrite Sbuf / Wbuf: a pageable source may be staged at once)
     }
-    logml.resize(D); bad.resize(D);
-    if (job.want_ll) { ll.resize(nout); HIPCHK(hipMemcpyAsync(ll.data(), d_ll, sizeof(double) * nout, hipMemcpyDeviceToHost, g.st)); }
-    if (job.want_resid) { resid.resize(nout); HIPCHK(hipMemcpyAsync(resid.data(), d_resid, sizeof(double) * nout, hipMemcpyDeviceToHost, g.st)); }
-    if (job.want_var) { var.resize(nout); HIPCHK(hipMemcpyAsync(var.data(), d_var, sizeof(double) * nout, hipMemcpyDeviceToHost, g.st)); }
-    HIPCHK(hipMemcpyAsync(logml.data(), d_logml, sizeof(double) * (size_t)D, hipMemcpyDeviceToHost, g.st));
-    HIPCHK(hipMemcpyAsync(bad.data(), d_bad, sizeof(int) * (size_t)D, hipMemcpyDeviceToHost, g.st));
-    HIPCHK(hipStreamSynchronize(g.st));
+    out.loglik = d_ll; out.resid = d_resid; out.var = d_var; out.logml = d_logml;
+    out.bad.resize(D);
+    if ((rc = g.fetch(out.bad.data(), (const int *)d_bad, (size_t)D))) return rc;
     HIPCHK(hipGetLastError());
     return BNR_OK;
 }

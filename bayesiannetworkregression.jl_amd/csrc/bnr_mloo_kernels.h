@@ -3,10 +3,10 @@
 //     A_b = I + X diag(S_b) X^T = L L^T,   r = y - mu_b - X W_b,   z = L^-1 r,   g = L^-T z = A^-1 r,   c_i = (A^-1)_ii = sum_j (L^-1)_ji^2
 //     resid_i = g_i / c_i,   var_i = tau2_b / c_i,   loglik_i = -(log 2 pi + log var_i) / 2 - (resid_i^2 / var_i) / 2
 //     logml = -(n / 2) log(2 pi tau2_b) - sum_j log L_jj - (||z||^2 / tau2_b) / 2
-// Four kernels: k_mloo_w (W and the scalars of a batch out of the chains' table rows), k_mloo_rhs (r), k_mloo_gram (A on the f64 matrix pipe)
-// and k_mloo_factor (everything behind A, one workgroup per draw).  Every sum of every output runs in an order fixed by (n, q) alone: no
-// result depends on the batch, on the other draws of a call, on the grid or on the call, bit for bit.  Plain C++, MFMA builtins and vector
-// stores; no atomics.  Compiled with -ffp-contract=off: every product and every sum is rounded on its own.
+// Four kernels: k_mloo_w (W and the scalars of a batch out of the chains' table rows), k_mloo_rhs (r), k_mloo_gram (A on the f64 matrix pipe,
+// over mloo_gram_tile) and k_mloo_factor (everything behind A, one workgroup per draw).  Every sum of every output runs in an order fixed by
+// (n, q) alone: no result depends on the batch, on the other draws of a call, on the grid or on the call, bit for bit.  Plain C++, MFMA
+// builtins and vector stores; no atomics.  Compiled with -ffp-contract=off: every product and every sum is rounded on its own.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -67,30 +67,26 @@ __global__ __launch_bounds__(256) void k_mloo_rhs(const double *X, int ldx, cons
         if (b0 + d < B) r[(size_t)(b0 + d) * (size_t)np + i] = in ? (y[i] - mu[b0 + d]) - acc[d] : 0.0;
 }
 
-// ===================================================================================== k_mloo_gram
-// A_b = I + X diag(S_b) X^T for the draws of a batch, lower tiles only, by v_mfma_f64_16x16x4_f64 with the edges as the K dimension.
-// grid = (nt (nt + 1) / 2, ceil(B / MLOO_DB)) with nt = np / MLOO_TILE, 256 threads.  Workgroup (p, y): the tile pair (ti >= tj) number p and the
-// draws b0 = y MLOO_DB .. b0 + MLOO_DB - 1.  Per K step of MLOO_KC edges the two panels of X (rows of tile ti, rows of tile tj) and the draws' S
-// are staged in LDS once; wave w owns the 16 x 16 tile (w >> 1, w & 1) of the pair and keeps one accumulator per draw: the A operand is
-// x[i][e] S_b[e] (one multiply per element and draw), the B operand x[j][e] as staged -- the panels are read from LDS once per MFMA step for all
-// MLOO_DB draws.  Padding -- rows past n, edges past q, draws past B -- is the constant 0.0 chosen at staging, never memory that was not asked for.
-// K order of an entry: one accumulator, edges 0, 4, 8, ... in steps of 4, inside a step the MFMA's own order (lane group g = lane >> 4 holds
-// edge k + g): fixed by q alone.  The identity is added once, to the finished sum.  A[(i, j)] is stored at G_b[i + j np], G_b = G + b gstride (i >= j within the lower
-// tiles; the diagonal tiles whole).  MFMA layouts as in k_cov: A lane l = row l & 15, k = l >> 4; B lane l = k = l >> 4, column l & 15; D lane l,
-// reg t = row (l >> 4) + 4 t, column l & 15.
-__global__ __launch_bounds__(256) void k_mloo_gram(const double *X, int ldx, int n, int q, const double *const *Sp, int B, double *G, int np,
-                                                   long long gstride)
+// ===================================================================================== mloo_gram_tile, k_mloo_gram
+// One 32 x 32 tile of P_b = Xi diag(S_b) Xj^T (IDENT: of I + that) for MLOO_DB draws of a batch, by v_mfma_f64_16x16x4_f64 with the edges as the K
+// dimension: the body of k_mloo_gram and of k_mpred_cross (bnr_mpred_kernels.h).  Called by all 256 threads of workgroup (., y), draws b0 =
+// y MLOO_DB .. b0 + MLOO_DB - 1.  xi / xj: this thread's row of the two row panels (row sr = tid & 31 of tile ti of Xi, of tile tj of Xj), already
+// clamped into its matrix, leading dimensions ldi / ldj; vi / vj: whether that row exists.  Per K step of MLOO_KC edges the two panels and the
+// draws' S are staged in LDS once; wave w owns the 16 x 16 tile (w >> 1, w & 1) of the pair and keeps one accumulator per draw: the A operand is
+// xi[i][e] S_b[e] (one multiply per element and draw), the B operand xj[j][e] as staged -- the panels are read from LDS once per MFMA step for all
+// MLOO_DB draws.  Padding -- rows that do not exist, edges past q, draws past B -- is the constant 0.0 chosen at staging, never memory that was not
+// asked for.  K order of an entry: one accumulator, edges 0, 4, 8, ... in steps of 4, inside a step the MFMA's own order (lane group g = lane >> 4
+// holds edge k + g): fixed by q alone.  The identity is added once, to the finished sum.  Entry (i, j) of the tile pair is stored at
+// out + b stride + i + j np, all 32 x 32 of them.  MFMA layouts as in k_cov: A lane l = row l & 15, k = l >> 4; B lane l = k = l >> 4, column
+// l & 15; D lane l, reg t = row (l >> 4) + 4 t, column l & 15.
+template <bool IDENT>
+__device__ __forceinline__ void mloo_gram_tile(const double *xi, int ldi, bool vi, const double *xj, int ldj, bool vj, int ti, int tj, int q,
+                                               const double *const *Sp, int B, double *out, int np, long long stride)
 {
     __shared__ double sXi[MLOO_KC * MLOO_LDT], sXj[MLOO_KC * MLOO_LDT], sS[MLOO_DB * MLOO_KC];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, c = lane & 15;
-    int ti = (int)((sqrt(8.0 * (double)blockIdx.x + 1.0) - 1.0) * 0.5);
-    while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.x) ++ti;
-    while (ti * (ti + 1) / 2 > (int)blockIdx.x) --ti;
-    const int tj = (int)blockIdx.x - ti * (ti + 1) / 2;
     const int b0 = (int)blockIdx.y * MLOO_DB;
     const int sr = tid & 31, sk = tid >> 5;                              // staging: row sr of a panel, edges sk, sk + 8, sk + 16, sk + 24 of the step
-    const int rowi = ti * MLOO_TILE + sr, rowj = tj * MLOO_TILE + sr;
-    const double *xi = X + min(rowi, n - 1), *xj = X + min(rowj, n - 1);
     const double *sp = Sp[min(b0 + sk, B - 1)];                          // staging of S: draw b0 + sk, edge sr of the step
     const bool sv = b0 + sk < B;
     const int ra = (w >> 1) * 16 + c, rb = (w & 1) * 16 + c;
@@ -101,11 +97,10 @@ __global__ __launch_bounds__(256) void k_mloo_gram(const double *X, int ldx, int
         __syncthreads();
 #pragma unroll
         for (int p = 0; p < MLOO_KC / 8; ++p) {
-            const int k = sk + 8 * p, e = k0 + k;
-            const size_t off = (size_t)min(e, q - 1) * (size_t)ldx;
-            const double vi = xi[off], vj = xj[off];
-            sXi[k * MLOO_LDT + sr] = (e < q && rowi < n) ? vi : 0.0;
-            sXj[k * MLOO_LDT + sr] = (e < q && rowj < n) ? vj : 0.0;
+            const int k = sk + 8 * p, e = k0 + k, ec = min(e, q - 1);
+            const double a = xi[(size_t)ec * (size_t)ldi], b = xj[(size_t)ec * (size_t)ldj];
+            sXi[k * MLOO_LDT + sr] = (e < q && vi) ? a : 0.0;
+            sXj[k * MLOO_LDT + sr] = (e < q && vj) ? b : 0.0;
         }
         {
             const int e = k0 + sr;
@@ -125,13 +120,27 @@ __global__ __launch_bounds__(256) void k_mloo_gram(const double *X, int ldx, int
 #pragma unroll
     for (int d = 0; d < MLOO_DB; ++d) {
         if (b0 + d >= B) break;
-        double *Gb = G + (size_t)(b0 + d) * (size_t)gstride;
+        double *ob = out + (size_t)(b0 + d) * (size_t)stride;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             const int row = ti * MLOO_TILE + (w >> 1) * 16 + g + 4 * t;
-            Gb[(size_t)row + (size_t)col * (size_t)np] = acc[d][t] + (row == col ? 1.0 : 0.0);
+            ob[(size_t)row + (size_t)col * (size_t)np] = IDENT ? acc[d][t] + (row == col ? 1.0 : 0.0) : acc[d][t];
         }
     }
+}
+
+// A_b = I + X diag(S_b) X^T for the draws of a batch, lower tiles only.  grid = (nt (nt + 1) / 2, ceil(B / MLOO_DB)) with nt = np / MLOO_TILE, 256
+// threads: workgroup (p, y) is the tile pair (ti >= tj) number p, both panels rows of X.  A[(i, j)] is stored at G_b[i + j np], G_b = G + b gstride
+// (i >= j within the lower tiles; the diagonal tiles whole).
+__global__ __launch_bounds__(256) void k_mloo_gram(const double *X, int ldx, int n, int q, const double *const *Sp, int B, double *G, int np,
+                                                   long long gstride)
+{
+    int ti = (int)((sqrt(8.0 * (double)blockIdx.x + 1.0) - 1.0) * 0.5);
+    while ((ti + 1) * (ti + 2) / 2 <= (int)blockIdx.x) ++ti;
+    while (ti * (ti + 1) / 2 > (int)blockIdx.x) --ti;
+    const int tj = (int)blockIdx.x - ti * (ti + 1) / 2;
+    const int sr = (int)threadIdx.x & 31, rowi = ti * MLOO_TILE + sr, rowj = tj * MLOO_TILE + sr;
+    mloo_gram_tile<true>(X + min(rowi, n - 1), ldx, rowi < n, X + min(rowj, n - 1), ldx, rowj < n, ti, tj, q, Sp, B, G, np, gstride);
 }
 
 // ===================================================================================== k_mloo_factor

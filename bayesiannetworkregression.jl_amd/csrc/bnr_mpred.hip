@@ -1,6 +1,7 @@
 // bnr_mpred.hip -- libbnr_mpred.so behind include/bnr_mpred.h: Rao-Blackwellised prediction of new rows, gamma integrated out on the device.
 // A library and a gfx950 code object of its own: the four kernels of bnr_mloo_kernels.h and the two of bnr_medge_kernels.h (by #include, through
-// the drivers shared with libbnr_mloo.so and libbnr_medge.so, bnr_mloo_job.h and bnr_medge_summary.h; k_medge_proj rides along unused) plus the
+// the drivers shared with libbnr_mloo.so and libbnr_medge.so: bnr_mloo_job.h opens the job of either form and runs its batches,
+// bnr_medge_summary.h holds the summary and the transposing copies; k_medge_proj rides along unused) plus the
 // four of bnr_mpred_kernels.h.  It reaches a chain through bnr_chain_device_view and leaves its messages with bnr_set_last_error -- exported
 // calls of libbnr_hip.so, nothing of bnr_internal.h.  Linked with bnr_mpred.map: only the functions of the header are exported.
 #include "../../include/bnr_mpred.h"
@@ -12,11 +13,10 @@ namespace {
 std::atomic<long long> opt_block_rows{0};               // "mpred_block_rows" (0: automatic)
 
 // mean, var and var + tau2 of every draw of the job for the new rows Xn (m x q column-major on the device), row-major per new row on the device
-// (Md, Vd, Pd: m x ndraws), behind every batch's k_mloo_factor: k_mpred_rhs once per batch, then k_mpred_cross and k_mpred_proj per block of rows
-int predict_job(call_guard &g, mloo_job &job, const double *Xn, int m, double *Md, double *Vd, double *Pd, std::vector<int> &bad)
+// (Md, Vd, Pd: m x ndraws; resid and var stay there too), behind every batch's k_mloo_factor: k_mpred_rhs once per batch, then k_mpred_cross and k_mpred_proj per block of rows
+int predict_job(call_guard &g, mloo_job &job, const double *Xn, int m, double *Md, double *Vd, double *Pd, mloo_out &out)
 {
     job.want_ll = false; job.want_resid = true; job.want_var = true;
-    std::vector<double> ll, rs, vr, lm;
     const long long D = job.ndraws;
     double *a = nullptr, *dq = nullptr, *C = nullptr;
     int MB = 0;                                         // new rows per block; a draw's block of C: np x round_up(MB, MLOO_TILE) doubles
@@ -48,7 +48,7 @@ int predict_job(call_guard &g, mloo_job &job, const double *Xn, int m, double *M
         HIPCHK(hipGetLastError());
         return BNR_OK;
     };
-    return run_job(g, job, ll, rs, vr, lm, bad, hook);
+    return run_job(g, job, out, hook);
 }
 
 // k_mpred_score on the row-major device matrices Md, Pd (m x K nd) and its results to the host
@@ -66,18 +66,6 @@ int score_run(call_guard &g, int m, int K, int nd, const double *Md, const doubl
     if (pit) HIPCHK(hipMemcpyAsync(pit, dp, sizeof(double) * (size_t)m, hipMemcpyDeviceToHost, g.st));
     HIPCHK(hipStreamSynchronize(g.st));
     HIPCHK(hipGetLastError());
-    return BNR_OK;
-}
-
-// a host (D x m) matrix, a draw's m values contiguous, to the device as m x D
-int upload_transposed(call_guard &g, const double *src, int m, int D, double **dev)
-{
-    std::vector<double> t((size_t)m * (size_t)D);
-    for (int s = 0; s < D; ++s)
-        for (int j = 0; j < m; ++j) t[(size_t)j * D + s] = src[(size_t)s * m + j];
-    int rc;
-    if ((rc = g.upload(dev, t.data(), t.size()))) return rc;
-    HIPCHK(hipStreamSynchronize(g.st));                                  // (t leaves scope)
     return BNR_OK;
 }
 }   // namespace
@@ -105,29 +93,20 @@ int bnr_marginal_predict(int32_t device, int32_t n, int32_t q, int32_t m, int32_
 {
     if (!X || !y || !Xnew || !tau2 || !mu || !S) return fail(BNR_ERR_BAD_ARG, "NULL argument");
     if (!mean && !var) return fail(BNR_ERR_BAD_ARG, "ask for mean or var");
-    if (n < 1 || q < 1 || ndraws < 1) return fail(BNR_ERR_BAD_ARG, "need n >= 1 rows, q >= 1 edges and ndraws >= 1 draws");
-    if (m < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 new rows");
-    if (n > BNR_MLOO_MAX_N) return fail(BNR_ERR_BAD_ARG, "n > 2048 is not supported by this version");
     call_guard g;
-    int rc;
-    if ((rc = g.open(device))) return rc;
     mloo_job job;
-    job.n = n; job.q = q; job.ndraws = ndraws; job.ldx = n;
-    double *Xd = nullptr, *yd = nullptr, *Xn = nullptr, *Md = nullptr, *Vd = nullptr, *Pd = nullptr;
-    if ((rc = g.upload(&Xd, X, (size_t)n * (size_t)q))) return rc;
-    if ((rc = g.upload(&yd, y, (size_t)n))) return rc;
+    int rc;
+    if ((rc = open_raw_job(g, job, device, n, q, ndraws, X, y, tau2, mu, S, W, m < 1 ? "need m >= 1 new rows" : nullptr))) return rc;
+    double *Xn = nullptr, *Md = nullptr, *Vd = nullptr, *Pd = nullptr;
     if ((rc = g.upload(&Xn, Xnew, (size_t)m * (size_t)q))) return rc;
-    if ((rc = g.upload(&job.tau2, tau2, (size_t)ndraws))) return rc;
-    if ((rc = g.upload(&job.mu, mu, (size_t)ndraws))) return rc;
     if ((rc = g.alloc(&Md, (size_t)m * (size_t)ndraws))) return rc;
     if ((rc = g.alloc(&Vd, (size_t)m * (size_t)ndraws))) return rc;
     if ((rc = g.alloc(&Pd, (size_t)m * (size_t)ndraws))) return rc;
-    job.X = Xd; job.y = yd; job.hS = S; job.hW = W; job.has_w = W != nullptr;
-    std::vector<int> bad;
-    if ((rc = predict_job(g, job, Xn, m, Md, Vd, Pd, bad))) return rc;
+    mloo_out out;
+    if ((rc = predict_job(g, job, Xn, m, Md, Vd, Pd, out))) return rc;
     if (mean && (rc = fetch_transposed(g, Md, m, ndraws, mean))) return rc;
     if (var && (rc = fetch_transposed(g, Vd, m, ndraws, var))) return rc;
-    if (n_bad) { int nb = 0; for (int f : bad) nb += f != 0; *n_bad = nb; }
+    if (n_bad) *n_bad = count_bad(out.bad);
     return BNR_OK;
 }
 
@@ -157,63 +136,34 @@ int bnr_chains_marginal_predict(bnr_chain *const *chains, int32_t nchains, const
                                 double *lpd, double *pit, double *dmean, double *dvar, int32_t *n_bad)
 {
     if (!chains || !Xnew) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (nchains < 1) return fail(BNR_ERR_BAD_ARG, "need nchains >= 1");
-    if (thin < 1) return fail(BNR_ERR_BAD_ARG, "need thin >= 1");
-    if (m < 1) return fail(BNR_ERR_BAD_ARG, "need m >= 1 new rows");
-    for (int i = 0; i < nchains; ++i) {
-        if (!chains[i]) return fail(BNR_ERR_BAD_ARG, "NULL chain");
-        for (int k = 0; k < i; ++k) if (chains[k] == chains[i]) return fail(BNR_ERR_BAD_ARG, "chain listed twice");
-    }
+    int rc, nd;
+    if ((rc = check_chain_list(chains, nchains, thin, m < 1 ? "need m >= 1 new rows" : nullptr))) return rc;
     const summary_out oe{mean, sd, var_within, nullptr, nullptr, lower, upper}, op{nullptr, pred_sd, nullptr, nullptr, nullptr, pred_lower, pred_upper};
     const bool want_e = mean || sd || var_within || lower || upper, want_p = pred_sd || pred_lower || pred_upper;
     if (!want_e && !want_p && !lpd && !pit && !dmean && !dvar) return fail(BNR_ERR_BAD_ARG, "ask for at least one output");
     if ((lpd || pit) && !ynew) return fail(BNR_ERR_BAD_ARG, "lpd and pit need ynew");
     double ce = 1.0, cp = 1.0;
-    int rc;
     if (want_e && (rc = summary_check(oe, p_lo, p_hi, ce))) return rc;
     if (want_p && (rc = summary_check(op, p_lo, p_hi, cp))) return rc;
     std::vector<double> w;
     if ((rc = summary_weights(weights, nchains, w))) return rc;
-    std::vector<bnr_chain_view> vw(nchains);
-    for (int i = 0; i < nchains; ++i) {
-        if ((rc = bnr_chain_device_view(chains[i], &vw[i]))) return rc;
-        if (vw[i].device != vw[0].device || vw[i].n != vw[0].n || vw[i].V != vw[0].V || vw[i].R != vw[0].R || vw[i].rowlen != vw[0].rowlen)
-            return fail(BNR_ERR_BAD_ARG, "pooled chains must live on one device and have equal n, V, R");
-    }
-    for (int i = 0; i < nchains; ++i)
-        if (first_row < 1 || nsamp < 1 || (long long)first_row + nsamp - 1 > vw[i].tot) return fail(BNR_ERR_BAD_ARG, "row window outside the table");
-    const int nd = (nsamp + thin - 1) / thin;
-    if ((long long)nchains * nd > 0x7FFFFFFFll) return fail(BNR_ERR_BAD_ARG, "more than 2^31 - 1 pooled draws");
-    const int n = vw[0].n, q = vw[0].q, D = nchains * nd;
-    if (n > BNR_MLOO_MAX_N) return fail(BNR_ERR_BAD_ARG, "n > 2048 is not supported by this version");
     call_guard g;
-    if ((rc = g.open(vw[0].device))) return rc;
     mloo_job job;
-    job.n = n; job.q = q; job.ndraws = D; job.ldx = vw[0].ldx; job.X = vw[0].X; job.y = vw[0].y; job.v = vw[0];
-    job.chain_form = true; job.has_w = true;
-    std::vector<const double *> hrow(D);
-    for (int k = 0; k < nchains; ++k)
-        for (int j = 0; j < nd; ++j) hrow[(size_t)k * nd + j] = vw[k].trace + ((size_t)(first_row - 1) + (size_t)j * thin) * (size_t)vw[k].rowlen;
-    const double **rowp = nullptr;
-    double *Xn = nullptr, *yd = nullptr;
-    if ((rc = g.upload(&rowp, hrow.data(), (size_t)D))) return rc;
+    if ((rc = open_chain_job(g, job, chains, nchains, first_row, nsamp, thin, nd))) return rc;
+    const int q = job.q, D = job.ndraws;
+    double *Xn = nullptr, *yd = nullptr, *Md = nullptr, *Vd = nullptr, *Pd = nullptr;
     if ((rc = g.upload(&Xn, Xnew, (size_t)m * (size_t)q))) return rc;
     if (ynew && (rc = g.upload(&yd, ynew, (size_t)m))) return rc;
-    HIPCHK(hipStreamSynchronize(g.st));
-    job.rowp = rowp; job.hrow = hrow.data();
-    if ((rc = g.alloc(&job.tau2, (size_t)D))) return rc;
-    if ((rc = g.alloc(&job.mu, (size_t)D))) return rc;
-    double *Md = nullptr, *Vd = nullptr, *Pd = nullptr;
     if ((rc = g.alloc(&Md, (size_t)m * (size_t)D))) return rc;
     if ((rc = g.alloc(&Vd, (size_t)m * (size_t)D))) return rc;
     if ((rc = g.alloc(&Pd, (size_t)m * (size_t)D))) return rc;
-    std::vector<int> bad;
-    if ((rc = predict_job(g, job, Xn, m, Md, Vd, Pd, bad))) return rc;
+    mloo_out out;
+    if ((rc = predict_job(g, job, Xn, m, Md, Vd, Pd, out))) return rc;
     if (want_e && (rc = summary_run(g, m, nchains, nd, Md, Vd, w, ce, p_lo, p_hi, oe))) return rc;
     if (want_p && (rc = summary_run(g, m, nchains, nd, Md, Pd, w, cp, p_lo, p_hi, op))) return rc;
     if ((lpd || pit) && (rc = score_run(g, m, nchains, nd, Md, Pd, yd, w, lpd, pit))) return rc;
     if (dmean && (rc = fetch_transposed(g, Md, m, D, dmean))) return rc;
     if (dvar && (rc = fetch_transposed(g, Vd, m, D, dvar))) return rc;
-    if (n_bad) { int nb = 0; for (int f : bad) nb += f != 0; *n_bad = nb; }
+    if (n_bad) *n_bad = count_bad(out.bad);
     return BNR_OK;
 }

@@ -4,12 +4,12 @@
 // L L^T, M = L^-1 and g = A^-1 r as k_mloo_factor leaves them:
 //     C = X D X*^T (n x m),   a_j = sum_e x*_je W_e,   d_j = sum_e (x*_je S_e) x*_je,   h_j = sum_i C_ij g_i,   t_j = ||M C_j||^2
 //     mean_j = (mu + a_j) + h_j,   var_j = tau2 fmax(d_j - t_j, 0),   vobs_j = var_j + tau2
-// Four kernels: k_mpred_rhs (a, d), k_mpred_cross (C on the f64 matrix pipe, k_mloo_gram's schedule with two different row panels),
-// k_mpred_proj (T = M C on the f64 matrix pipe, k_medge_proj's schedule with the draw's own right operand; mean, var, vobs) and k_mpred_score
-// (one wave per new row).  Every sum of the first three runs in an order fixed by (n, q) alone, every sum of k_mpred_score in one fixed by
-// (K, nd) alone: no result depends on the batch, on the other draws or new rows, on how the new rows are blocked, on the grid or on the call, bit
-// for bit.  Plain C++, MFMA builtins and vector stores; no atomics.  Compiled with -ffp-contract=off: every product and every sum is rounded on
-// its own.  Every out-of-range element is the constant 0.0 selected at staging; no address is formed outside its operand.
+// Four kernels: k_mpred_rhs (a, d), k_mpred_cross (C on the f64 matrix pipe, by mloo_gram_tile), k_mpred_proj (T = M C on the f64 matrix pipe;
+// mean, var, vobs) and k_mpred_score (one wave per new row).  Every sum of the first three runs in an order fixed by (n, q) alone, every sum of
+// k_mpred_score in one fixed by (K, nd) alone: no result depends on the batch, on the other draws or new rows, on how the new rows are blocked, on
+// the grid or on the call, bit for bit.  Plain C++, MFMA builtins and vector stores; no atomics.  Compiled with -ffp-contract=off: every product
+// and every sum is rounded on its own.  Every out-of-range element is the constant 0.0 selected at staging; no address is formed outside its
+// operand.
 #pragma once
 #include "bnr_medge_kernels.h"
 
@@ -56,67 +56,19 @@ __global__ __launch_bounds__(256) void k_mpred_rhs(const double *Xn, int ldn, in
 }
 
 // ===================================================================================== k_mpred_cross
-// C_b = X diag(S_b) X*^T for the draws of a batch and the block j0 .. j0 + mblk - 1 of new rows, by v_mfma_f64_16x16x4_f64 with the edges as the K
-// dimension: k_mloo_gram's schedule with two different row panels.  grid = (nt ntj, ceil(B / MLOO_DB)) with nt = np / MLOO_TILE row tiles of X and
-// ntj = ceil(mblk / MLOO_TILE) tiles of new rows, 256 threads.  Workgroup (p, y): tiles ti = p / ntj of X and tj = p % ntj of the block, draws
-// b0 = y MLOO_DB ..  Per K step of MLOO_KC edges the panel of X (rows of tile ti), the panel of X* (rows of tile tj) and the draws' S are staged in
-// LDS once; wave w owns the 16 x 16 tile (w >> 1, w & 1) and keeps one accumulator per draw: the A operand is x[i][e] S_b[e] (one multiply per
-// element and draw), the B operand x*[j][e] as staged.  No triangle, no identity.  Padding -- rows of X past n, new rows past the block, edges past
-// q, draws past B -- is the constant 0.0 chosen at staging, never memory that was not asked for: every address stays inside X (n x q), X* (m x q)
-// and S_b (q).  K order of an entry: one accumulator, edges 0, 4, 8, ... in steps of 4, inside a step the MFMA's own order: fixed by q alone.
-// C_b[(i, jl)], jl = j - j0, is stored at C + b cstride + i + jl np: a column C_j is contiguous along i (the layout k_medge_proj reads X in); all np
-// rows and all 32 ntj columns of the block are written (the padding as 0.0), cstride >= np 32 ntj.  MFMA layouts as in k_mloo_gram.
+// C_b = X diag(S_b) X*^T for the draws of a batch and the block j0 .. j0 + mblk - 1 of new rows, over mloo_gram_tile (bnr_mloo_kernels.h): no
+// triangle, no identity, the second panel rows of X*.  grid = (nt ntj, ceil(B / MLOO_DB)) with nt = np / MLOO_TILE row tiles of X and ntj =
+// ceil(mblk / MLOO_TILE) tiles of new rows, 256 threads: workgroup (p, y) is the tiles ti = p / ntj of X and tj = p % ntj of the block.  Every
+// address stays inside X (n x q), X* (m x q) and S_b (q).  C_b[(i, jl)], jl = j - j0, is stored at C + b cstride + i + jl np: a column C_j is
+// contiguous along i (the layout k_mpred_proj reads it in); all np rows and all 32 ntj columns of the block are written (the padding -- rows of X
+// past n, new rows past the block -- as 0.0), cstride >= np 32 ntj.
 __global__ __launch_bounds__(256) void k_mpred_cross(const double *X, int ldx, int n, int q, const double *Xn, int ldn, int j0, int mblk,
                                                      const double *const *Sp, int B, double *C, int np, long long cstride)
 {
-    __shared__ double sXi[MLOO_KC * MLOO_LDT], sXj[MLOO_KC * MLOO_LDT], sS[MLOO_DB * MLOO_KC];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, g = lane >> 4, c = lane & 15;
     const int ntj = (mblk + MLOO_TILE - 1) / MLOO_TILE;
     const int ti = (int)blockIdx.x / ntj, tj = (int)blockIdx.x % ntj;
-    const int b0 = (int)blockIdx.y * MLOO_DB;
-    const int sr = tid & 31, sk = tid >> 5;                              // staging: row sr of a panel, edges sk, sk + 8, sk + 16, sk + 24 of the step
-    const int rowi = ti * MLOO_TILE + sr, rowj = tj * MLOO_TILE + sr;    // (rowj: within the block)
-    const double *xi = X + min(rowi, n - 1), *xj = Xn + (j0 + min(rowj, mblk - 1));
-    const double *sp = Sp[min(b0 + sk, B - 1)];                          // staging of S: draw b0 + sk, edge sr of the step
-    const bool sv = b0 + sk < B;
-    const int ra = (w >> 1) * 16 + c, rb = (w & 1) * 16 + c;
-    mloo_d4 acc[MLOO_DB];
-#pragma unroll
-    for (int d = 0; d < MLOO_DB; ++d) acc[d] = mloo_d4{0.0, 0.0, 0.0, 0.0};
-    for (int k0 = 0; k0 < q; k0 += MLOO_KC) {
-        __syncthreads();
-#pragma unroll
-        for (int p = 0; p < MLOO_KC / 8; ++p) {
-            const int k = sk + 8 * p, e = k0 + k, ec = min(e, q - 1);
-            const double vi = xi[(size_t)ec * (size_t)ldx], vj = xj[(size_t)ec * (size_t)ldn];
-            sXi[k * MLOO_LDT + sr] = (e < q && rowi < n) ? vi : 0.0;
-            sXj[k * MLOO_LDT + sr] = (e < q && rowj < mblk) ? vj : 0.0;
-        }
-        {
-            const int e = k0 + sr;
-            const double v = sp[min(e, q - 1)];
-            sS[sk * MLOO_KC + sr] = (sv && e < q) ? v : 0.0;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int ks = 0; ks < MLOO_KC; ks += 4) {
-            const int k = ks + g;
-            const double xa = sXi[k * MLOO_LDT + ra], xb = sXj[k * MLOO_LDT + rb];
-#pragma unroll
-            for (int d = 0; d < MLOO_DB; ++d) acc[d] = __builtin_amdgcn_mfma_f64_16x16x4f64(xa * sS[d * MLOO_KC + k], xb, acc[d], 0, 0, 0);
-        }
-    }
-    const int col = tj * MLOO_TILE + (w & 1) * 16 + c;                   // (< 32 ntj)
-#pragma unroll
-    for (int d = 0; d < MLOO_DB; ++d) {
-        if (b0 + d >= B) break;
-        double *Cb = C + (size_t)(b0 + d) * (size_t)cstride;
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int row = ti * MLOO_TILE + (w >> 1) * 16 + g + 4 * t;  // (< np)
-            Cb[(size_t)row + (size_t)col * (size_t)np] = acc[d][t];
-        }
-    }
+    const int sr = (int)threadIdx.x & 31, rowi = ti * MLOO_TILE + sr, rowj = tj * MLOO_TILE + sr;    // (rowj: within the block)
+    mloo_gram_tile<false>(X + min(rowi, n - 1), ldx, rowi < n, Xn + (j0 + min(rowj, mblk - 1)), ldn, rowj < mblk, ti, tj, q, Sp, B, C, np, cstride);
 }
 
 // ===================================================================================== k_mpred_proj
@@ -129,7 +81,7 @@ __global__ __launch_bounds__(256) void k_mpred_cross(const double *X, int ldx, i
 //   2. T = M C_b by v_mfma_f64_16x16x4_f64, 16 rows r of M at a time (row tile rt), K = the rows i of C in steps of 4 from 0 up to the first
 //      multiple of 32 past the tile's diagonal (M is lower triangular); one accumulator per column tile.  The squares of a finished tile are added
 //      to a lane's t: lane group g = lane >> 4 holds rows 16 rt + g + 4 j, j = 0 .. 3, and sums them j ascending, rt ascending, from 0.0; at the end
-//      t_j = ((t_g0 + t_g1) + t_g2) + t_g3.  (k_medge_proj's triangular K loop, masks and t reduction.)
+//      t_j = ((t_g0 + t_g1) + t_g2) + t_g3.
 //   Masks, all by selecting the constant 0.0 at staging: M[r][i] with i > r (those slots hold entries of L), r >= n or i >= n (never written by the
 //   factor kernel), rows of C past n, new rows past the block.  Every address formed stays inside the np mblk doubles of the draw's block of C,
 //   inside the np (np + 1) doubles of the draw's factor and inside resid / var.
