@@ -1,4 +1,4 @@
-"""Build libbnr_hip.so, libbnr_mloo.so, libbnr_medge.so and libbnr_mpred.so (hipcc, gfx950) in-tree."""
+"""Build libbnr_hip.so, libbnr_mloo.so, libbnr_medge.so, libbnr_mpred.so and libbnr_mcheck.so (hipcc, gfx950) in-tree."""
 import os
 import subprocess
 
@@ -7,16 +7,17 @@ LIB = os.environ.get("BNR_HIP_LIB") or os.path.join(HERE, "libbnr_hip.so")     #
 MLOO_LIB = os.path.join(HERE, "libbnr_mloo.so")                              # marginal PSIS-LOO: a library of its own, linked against libbnr_hip.so beside it
 MEDGE_LIB = os.path.join(HERE, "libbnr_medge.so")                            # Rao-Blackwellised edge summaries: a third library, built and linked like libbnr_mloo.so
 MPRED_LIB = os.path.join(HERE, "libbnr_mpred.so")                            # Rao-Blackwellised prediction of new rows: a fourth library, built and linked like libbnr_medge.so
+MCHECK_LIB = os.path.join(HERE, "libbnr_mcheck.so")                          # LOO predictive checks under the marginal PSIS weights: a fifth library, built and linked like libbnr_mpred.so
 
 
 def build(force=False, verbose=False):
     if os.environ.get("BNR_HIP_LIB"):
         return LIB
     csrc = os.path.join(HERE, "csrc")
-    cmd = ["make", "-j5", "-C", csrc] + (["-B"] if force else [])          # five translation units, side by side
+    cmd = ["make", "-j6", "-C", csrc] + (["-B"] if force else [])          # six translation units, side by side
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if verbose or r.returncode:
         print(r.stdout)
     if r.returncode:
-        raise RuntimeError("building libbnr_hip.so / libbnr_mloo.so / libbnr_medge.so / libbnr_mpred.so failed")
+        raise RuntimeError("building libbnr_hip.so / libbnr_mloo.so / libbnr_medge.so / libbnr_mpred.so / libbnr_mcheck.so failed")
     return LIB

@@ -7,7 +7,7 @@ import os
 
 import numpy as np
 
-from ._build import LIB, MLOO_LIB, MEDGE_LIB, MPRED_LIB
+from ._build import LIB, MLOO_LIB, MEDGE_LIB, MPRED_LIB, MCHECK_LIB
 
 BNR_OK, BNR_ERR_BAD_ARG, BNR_ERR_HIP, BNR_ERR_CHOLESKY, BNR_ERR_SAMPLER = 0, 1, 2, 3, 4
 BNR_ERR_SAMPLER_CAP = BNR_ERR_SAMPLER
@@ -42,6 +42,7 @@ _lib = None
 _mloo = None
 _medge = None
 _mpred = None
+_mcheck = None
 
 _SIGS = {
     "bnr_abi_version": (C.c_int, []),
@@ -186,6 +187,16 @@ _MPRED_SIGS = {
 }
 MPRED_EXPORTS = sorted(_MPRED_SIGS)
 
+# libbnr_mcheck.so (include/bnr_mcheck.h): the LOO predictive checks under the marginal PSIS weights, a fifth library beside the four
+_MCHECK_SIGS = {
+    "bnr_mcheck_abi_version": (C.c_int, []),
+    "bnr_weighted_mixture": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_dp] * 4 + [C.c_double, C.c_double] + [_dp] * 5),
+    "bnr_chains_marginal_loo_predict": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_double, C.c_double]
+                                        + [_dp] * 9 + [C.POINTER(C.c_int32)]),
+    "bnr_mcheck_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
+}
+MCHECK_EXPORTS = sorted(_MCHECK_SIGS)
+
 
 _foreign_hip = None      # set by lib(): why chains must not be created in this process (GPU-free entry points stay usable)
 
@@ -268,6 +279,13 @@ def mpred_lib():
     return _mpred
 
 
+def mcheck_lib():
+    """Load libbnr_mcheck.so, after libbnr_hip.so (which it is linked against); raises if it has not been built"""
+    global _mcheck
+    _mcheck = _mcheck or _side_lib(MCHECK_LIB, _MCHECK_SIGS, "libbnr_mcheck.so")
+    return _mcheck
+
+
 def _device_side(side_lib):
     """side_lib() for the calls that open a device, refused like _device_lib()"""
     _device_lib()
@@ -276,6 +294,10 @@ def _device_side(side_lib):
 
 def _device_mpred():
     return _device_side(mpred_lib)
+
+
+def _device_mcheck():
+    return _device_side(mcheck_lib)
 
 
 def _device_medge():
@@ -1282,6 +1304,68 @@ def chains_marginal_predict(chains, first_row, nsamp, X_new, y_new=None, thin=1,
     check(_device_mpred().bnr_chains_marginal_predict(arr, K, _ptr(w), int(first_row), int(nsamp), thin, _ptr(Xn), m, _ptr(yn), p_lo, p_hi,
                                                       *[_ptr(o) for o in out], _ptr(dm), _ptr(dv), C.byref(nb)))
     return tuple(out), dm, dv, nb.value
+
+
+# ------------------------------------------------------------------------------------------ marginal LOO predictive checks (libbnr_mcheck.so, include/bnr_mcheck.h)
+MCHECK_FIELDS = ("mean", "sd", "pit", "lower", "upper")
+
+
+def mcheck_set_option(name, value):
+    check(mcheck_lib().bnr_mcheck_set_option(name.encode(), int(value)))
+
+
+def _mcheck_fields(fields, has_y):
+    fields = tuple(fields)
+    if not fields or [f for f in fields if f not in MCHECK_FIELDS] or ("pit" in fields and not has_y):
+        raise ValueError("fields must name some of %r, pit only with y, not %r" % (MCHECK_FIELDS, fields))
+    return fields
+
+
+def weighted_mixture_raw(mean, var, log_weights, y=None, p_lo=0.025, p_hi=0.975, device=0, fields=None):
+    """the tuple MCHECK_FIELDS (rows values each) of the weighted mixtures of normals in the rows of the rows x D matrices mean, var under the
+    normalised log weights log_weights (rows x D), on the device (bnr_weighted_mixture); y (rows,) or None (then no pit); an entry not named in
+    `fields` is not requested and comes back as None.  ValueError (before any library call) for shapes that do not fit or rows D >= 2^31"""
+    shape = np.shape(mean)
+    if len(shape) != 2 or np.shape(var) != shape or np.shape(log_weights) != shape:
+        raise ValueError("mean, var and log_weights must be rows x D matrices of one shape")
+    if shape[0] * shape[1] >= 2 ** 31:
+        raise ValueError("rows x D must stay below 2^31, not %d x %d" % shape)
+    mf = _matrix(mean, "mean")
+    vf, lf = np.ascontiguousarray(var, dtype=np.float64), np.ascontiguousarray(log_weights, dtype=np.float64)
+    rows, D = mf.shape
+    yf = None if y is None else np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+    if yf is not None and yf.shape != (rows,):
+        raise ValueError("y must hold one response per row of mean")
+    if fields is None:
+        fields = MCHECK_FIELDS if yf is not None else ("mean", "sd", "lower", "upper")
+    fields = _mcheck_fields(fields, yf is not None)
+    if set(fields) & {"lower", "upper"}:
+        p_lo, p_hi = loo_probs(p_lo, p_hi)
+    out = [np.empty(rows) if f in fields else None for f in MCHECK_FIELDS]
+    check(_device_mcheck().bnr_weighted_mixture(int(device), rows, D, _ptr(mf), _ptr(vf), _ptr(lf), _ptr(yf), float(p_lo), float(p_hi),
+                                                *[_ptr(o) for o in out]))
+    return tuple(out)
+
+
+def chains_marginal_loo_predict(chains, first_row, nsamp, thin=1, r_eff=None, p_lo=0.025, p_hi=0.975, loglik=False, fields=MCHECK_FIELDS):
+    """(elpd_loo, pareto_k (n,), the tuple MCHECK_FIELDS (n,: loo_mean, loo_sd, loo_pit, loo_lower, loo_upper; an entry not named in `fields` is
+    not requested and comes back as None), logml (K draws,), loglik (n, K draws) or None, n_bad) over rows first_row + j thin of every chain
+    listed (bnr_chains_marginal_loo_predict)"""
+    c0, arr, K, thin, nd = _pooled_window(chains, nsamp, thin)
+    n, D = c0.n, K * nd
+    r = r_eff_array(r_eff, n)
+    fields = tuple(fields)
+    if [f for f in fields if f not in MCHECK_FIELDS]:
+        raise ValueError("fields must name some of %r, not %r" % (MCHECK_FIELDS, fields))
+    if set(fields) & {"lower", "upper"}:
+        p_lo, p_hi = loo_probs(p_lo, p_hi)
+    el, kh, ml = np.empty(n), np.empty(n), np.empty(D)
+    out = [np.empty(n) if f in fields else None for f in MCHECK_FIELDS]
+    ll = np.empty((n, D)) if loglik else None
+    nb = C.c_int32(0)
+    check(_device_mcheck().bnr_chains_marginal_loo_predict(arr, K, int(first_row), int(nsamp), thin, _ptr(r), float(p_lo), float(p_hi), _ptr(el),
+                                                           _ptr(kh), *[_ptr(o) for o in out], _ptr(ml), _ptr(ll), C.byref(nb)))
+    return el, kh, tuple(out), ml, ll, nb.value
 
 
 class Comm:

@@ -29,6 +29,9 @@ Julia is not available in this image, so the thin host layer a Julia user would 
                                                posterior covariance of the edge coefficients: EdgeCov, cov, device_edge_cov, _host_edge_cov
                                                marginal PSIS-LOO (edge coefficients integrated out): MarginalLOO, marginal_loglik,
                                                device_marginal_loo, _host_marginal_loglik
+                                               marginal LOO predictive checks (PIT and intervals under the marginal weights):
+                                               MarginalLOOPredict / MarginalLOOPredictive, weighted_mixture, device_marginal_loo_predict,
+                                               _host_weighted_mixture, _host_marginal_loo_predict
   lower_triangle / create_lower_tri / setup_X!  utils.jl:17-57, gibbs.jl:239-247
 
 All sampling runs on the GPU through libbnr_hip.so; this file holds only the schedule logic (chain fan-out,
@@ -116,6 +119,7 @@ class Results:
     stat_chains: int = None          # how many chains the device statistics above (summary_device, prediction, waic, loo, loo_predictive) cover: 1 (chain 1's window), or
                                      # every chain of the fit with pool_chains=True; None when the fit computed none
     marginal_prediction: "MarginalPrediction" = None   # filled on request (marginal_predict=True): the prediction of predict_X with gamma integrated out, computed on the GPU (see MarginalPredict)
+    marginal_loo_predictive: "MarginalLOOPredictive" = None   # filled on request (marginal_loo_predict=True): the LOO predictive checks of the training rows under the marginal PSIS weights (see MarginalLOOPredict)
 
 
 @dataclass
@@ -1888,6 +1892,136 @@ def _marginal_loo_thin(nsamp, draws):
     return max(1, -(-int(nsamp) // int(draws)))
 
 
+# ------------------------------------------------------------------------------------------ marginal LOO predictive checks (an addition to the reference)
+# LOOPredict's checks under the marginal PSIS weights (include/bnr_mcheck.h, libbnr_mcheck.so; DESIGN.md section 8, "Marginal LOO predictive
+# checks").  With gamma integrated out, the leave-one-out predictive distribution of y_i is the mixture sum_s w_is N(y_i - resid_is, var_is) under
+# the weights of the ratios 1 / p(y_i | y_-i, phi_s): a weight and a variance per (row, draw).  The _host_* functions restate the definitions in
+# numpy: the fallback of MarginalLOOPredict and the yardstick of the tests.
+@dataclass
+class MarginalLOOPredictive:
+    """LOOPredictive (its fields, with its totals) under the marginal PSIS weights: the mixture of every row is sum_s w_is N(m_is, var_is) with
+    m_is = y_i - resid_is and var_is = Var[y_i | y_-i, phi_s] (gamma integrated out), lpd_i / elpd_loo_i / pareto_k those of MarginalLOO.
+    thin, chains, draws: what was pooled; n_bad: the draws that could not be factorised (every row is NaN while n_bad > 0); logml: log p(y | phi)
+    of every draw; loo: the dict of MarginalLOO (device_marginal_loo) from the same call's arrays."""
+    loo_mean: np.ndarray
+    loo_sd: np.ndarray
+    loo_pit: np.ndarray
+    loo_lower: np.ndarray
+    loo_upper: np.ndarray
+    lpd_i: np.ndarray
+    elpd_loo_i: np.ndarray
+    pareto_k: np.ndarray
+    rmse_loo: float
+    r2_loo: float
+    coverage: float
+    ks: float
+    interval: float
+    draws: int
+    khat_threshold: float
+    n_high_k: int
+    thin: int = None
+    chains: int = None
+    n_bad: int = None
+    logml: np.ndarray = None
+    loo: dict = None
+
+
+def _host_weighted_mixture(mean, var, log_weights, y, p_lo, p_hi, solver=None):
+    """bnr_weighted_mixture restated in numpy: (mean, sd, pit, lower, upper, bracket width) per row of the rows x D matrices mean, var and the
+    normalised log weights; y (rows,) or None (then mean = sum w m and pit is NaN).  _loo_predict_rows with a sd per (row, draw); a row that holds
+    a point mass (var = 0: Phi -> [t >= m]) goes through the library's bisection, the others through _mixture_quantile.  A row with a NaN or
+    negative var, a NaN mean or a log weight that is not finite is NaN; a NaN y makes mean, sd and pit NaN."""
+    m, v, lw = (np.asarray(a, dtype=np.float64) for a in (mean, var, log_weights))
+    rows = m.shape[0]
+    yv = None if y is None else np.asarray(y, dtype=np.float64).reshape(-1)
+    c = _loo_bracket_c(p_lo, p_hi)
+    out = np.full((6, rows), np.nan)
+    h = 0.70710678118654752440
+    for i in range(rows):
+        if not np.all(np.isfinite(lw[i])) or np.any(np.isnan(m[i])) or np.any(np.isnan(v[i])) or np.any(v[i] < 0):
+            continue
+        w, sd = np.exp(lw[i]), np.sqrt(v[i])
+        point = v[i] == 0.0
+
+        def F(t, w=w, mi=m[i], sd=sd, point=point):
+            with np.errstate(all="ignore"):
+                return float(np.sum(w * np.where(point, (t >= mi).astype(np.float64), 0.5 * _erfc(((t - mi) / sd) * -h))))
+        if yv is not None and not math.isnan(yv[i]):
+            mu = float(yv[i] - np.sum(w * (yv[i] - m[i])))
+            out[2, i] = F(yv[i]) if point.any() else _mixture_cdf(yv[i], w, m[i], sd)
+        elif yv is None:
+            mu = float(np.sum(w * m[i]))
+        else:
+            mu = math.nan
+        out[0, i] = mu
+        out[1, i] = math.sqrt(max(float(np.sum(w * (v[i] + m[i] ** 2))) - mu * mu, 0.0)) if not math.isnan(mu) else math.nan
+        if point.any():
+            lo, hi = float(np.min(m[i] - c * sd)), float(np.max(m[i] + c * sd))
+            out[5, i] = hi - lo
+            out[3, i], out[4, i] = _bisect_quantile(F, p_lo, lo, hi), _bisect_quantile(F, p_hi, lo, hi)
+        else:
+            out[3, i], out[5, i] = _mixture_quantile(p_lo, w, m[i], sd, c, solver)
+            out[4, i], _ = _mixture_quantile(p_hi, w, m[i], sd, c, solver)
+    return tuple(out)
+
+
+def weighted_mixture(mean, var, log_weights, y=None, interval=95, device=None):
+    """The summary of one weighted mixture of normals per row, sum_s exp(log_weights_is) N(mean_is, var_is), of rows x D matrices on the GPU
+    (bnr_weighted_mixture): dict with mean, sd, pit (= F_i(y_i); None without y), lower, upper (rows,) -- the central interval% interval -- and
+    interval.  log_weights: normalised log weights, e.g. psis_weights(...)["log_weights"]."""
+    p_lo, p_hi = _loo_interval_probs(interval)
+    out = dict(zip(_capi.MCHECK_FIELDS, _capi.weighted_mixture_raw(mean, var, log_weights, y, p_lo, p_hi, 0 if device is None else int(device))))
+    out["interval"] = interval
+    return out
+
+
+def _marginal_loo_predictive(y, lpd, elpd, k, mean, sd, pit, lower, upper, logml, interval, thin, nchains, draws, n_bad):
+    """MarginalLOOPredictive from the pointwise arrays: _loo_predictive's totals, and MarginalLOO's dict from the same arrays"""
+    lp = _loo_predictive(y, lpd, elpd, k, mean, sd, pit, lower, upper, interval, draws)
+    with np.errstate(invalid="ignore"):
+        loo = _marginal_loo(y, lpd, elpd, k, lp.loo_mean, lp.loo_sd, logml, thin, draws, n_bad)
+    return MarginalLOOPredictive(**{f.name: getattr(lp, f.name) for f in dataclasses.fields(lp)}, thin=int(thin), chains=int(nchains), n_bad=int(n_bad),
+                                 logml=logml, loo=loo)
+
+
+def device_marginal_loo_predict(chains, nburn, nsamp, thin=1, interval=95, r_eff=None):
+    """The LOO predictive checks of the training rows under the marginal PSIS weights over rows nburn + 1 + j thin (j = 0 .. ceil(nsamp / thin)
+    - 1) of ALL the chains listed, pooled, on the GPU (bnr_chains_marginal_loo_predict) -> MarginalLOOPredictive.  One call: the factorizations of
+    device_marginal_loo, PSIS on their loglik, and the mixture kernels on the device-resident resid and var; `loo` of the record is that
+    function's dict (without per_chain)."""
+    chains = list(chains)
+    thin, nd = _capi.mloo_thin_draws(nsamp, thin)
+    p_lo, p_hi = _loo_interval_probs(interval)
+    el, kh, (mean, sd, pit, lo, hi), ml, ll, nb = _capi.chains_marginal_loo_predict(chains, nburn + 1, nsamp, thin, r_eff, p_lo, p_hi, loglik=True)
+    return _marginal_loo_predictive(chains[0].y, _row_lme(ll), el, kh, mean, sd, pit, lo, hi, ml, interval, thin, len(chains), nd * len(chains), nb)
+
+
+def _host_marginal_loo_predict(states, X, y, nburn, nsamp, thin=1, interval=95, r_eff=None):
+    """device_marginal_loo_predict restated in numpy over the fetched tables of the same chains and the training X (n x q), y"""
+    states = list(states)
+    thin, nd = _capi.mloo_thin_draws(nsamp, thin)
+    p_lo, p_hi = _loo_interval_probs(interval)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    ll, rs, vr, ml, nb = _host_marginal_loglik(states, X, y, nburn, nsamp, thin)
+    lwn, e, k = _psis_weights_host(ll, r_eff)
+    mean, sd, pit, lo, hi, _w = _host_weighted_mixture(y[:, None] - rs, vr, lwn, y, p_lo, p_hi)
+    return _marginal_loo_predictive(y, _row_lme(ll), e, k, mean, sd, pit, lo, hi, ml, interval, thin, len(states), nd * len(states), nb)
+
+
+def MarginalLOOPredict(results, X=None, y=None, x_transform=True, interval=None):
+    """The LOO predictive checks of the training rows under the marginal PSIS weights -> MarginalLOOPredictive.  Uses the GPU's numbers when the
+    fit carried them (marginal_loo_predict=True) and the interval is the fit's; otherwise the host restatement over results.state (chain 1's
+    window, every draw) with the training X, y passed in (interval default 95)."""
+    rec = results.marginal_loo_predictive
+    if rec is not None and (interval is None or interval == rec.interval):
+        return rec
+    if results.state is None or X is None or y is None:
+        raise ValueError("MarginalLOOPredict needs Fit(..., marginal_loo_predict=True), or the state table (return_state=True) together with the "
+                         "training X and y")
+    xi = _new_rows(X, x_transform, results.state["gamma"].shape[1], y)
+    return _host_marginal_loo_predict([results.state], _dense_rows(xi), y, results.burn_in, results.sampled, 1, 95 if interval is None else interval)
+
+
 # ------------------------------------------------------------------------------------------ Rao-Blackwellised edge summaries (an addition to the reference)
 # The edge table with gamma integrated out (include/bnr_medge.h, libbnr_medge.so; DESIGN.md section 8, "Rao-Blackwellised edge summaries").  Given
 # phi = (tau2, mu, u, lambda, S) of a table row, gamma_e | phi, y ~ N(m_e, v_e) in closed form, so the posterior of gamma_e is the mixture of
@@ -2528,6 +2662,7 @@ class _Requests:
     marginal_loo: int = None         # the draws per chain of the marginal PSIS-LOO (marginal_loo_draws), or None
     marginal_edges: tuple = None     # (the draws per chain of the Rao-Blackwellised edge table (marginal_edges_draws), interval), or None
     marginal_predict: int = None     # the draws per chain of the Rao-Blackwellised prediction of predict_X (marginal_predict_draws), or None
+    marginal_loo_predict: tuple = None   # (the draws per chain of the marginal LOO predictive checks (marginal_loo_draws), interval), or None
 
 
 def _one_rank(option):
@@ -2540,7 +2675,7 @@ def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, retur
                   predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None, pool_chains=False, predict_observation=False,
                   pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False, hdi_prob=0.95, fdr=0.05, node_sets=False,
                   top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False, marginal_loo_draws=2000, marginal_edges=False,
-                  marginal_edges_draws=2000, marginal_predict=False, marginal_predict_draws=2000):
+                  marginal_edges_draws=2000, marginal_predict=False, marginal_predict_draws=2000, marginal_loo_predict=False):
     """The options of a fit (Fit's keywords) checked before any sampling, in this order -> _Requests.  Fit itself calls it ahead of
     parameters.log for the refusals alone, without X_new and nsamp: what needs them -- the new rows, the lag window of the rank diagnostics,
     r_eff -- is then left to generate_samples / generate_samples_dbl."""
@@ -2607,10 +2742,18 @@ def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, retur
         mp_ = int(marginal_predict_draws)
         if X_new is not None and X_new.n > MLOO_MAX_N:
             raise ValueError("marginal_predict takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
+    mlp = None
+    if marginal_loo_predict:
+        _one_rank("marginal_loo_predict")
+        _marginal_loo_thin(1, marginal_loo_draws)
+        _loo_interval_probs(predict_interval)
+        mlp = (int(marginal_loo_draws), predict_interval)
+        if X_new is not None and X_new.n > MLOO_MAX_N:
+            raise ValueError("marginal_loo_predict takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
     if X_new is not None:
         _capi.r_eff_array(loo_r_eff, X_new.n)
     return _Requests(return_state, summary_interval, ess_max_lag, pred, bool(waic), bool(loo), loo_r_eff, bool(pool_chains), bool(predict_observation),
-                     pred_seed, lp, bool(rank_diagnostics), es, ntop, bool(stack_chains), ec, ml, me, mp_)
+                     pred_seed, lp, bool(rank_diagnostics), es, ntop, bool(stack_chains), ec, ml, me, mp_, mlp)
 
 
 def _finish(chainset, res, req, seed):
@@ -2625,7 +2768,9 @@ def _finish(chainset, res, req, seed):
     stack: the chain stacking over every chain of the fit (Results.stacking), with summary_interval its summary and with predict its
     prediction under the weights; what pool_chains or the default return is not changed by it.
     edge_cov: the posterior covariance of the edge coefficients over every chain of the fit (Results.edge_cov), and with stack the one under
-    the stacking weights (Stacking.edge_cov)."""
+    the stacking weights (Stacking.edge_cov).
+    marginal_loo_predict: the LOO predictive checks under the marginal PSIS weights (Results.marginal_loo_predictive) over chain 1's window or,
+    with pool_chains, every chain's; a call of its own, which reads and sets nothing of the stacking record."""
     nb, ns = res.burn_in, res.sampled
     every = [chainset.chains[c] for c in chainset.ids]
     pred_seed = seed if req.pred_seed is None else req.pred_seed
@@ -2688,8 +2833,11 @@ def _finish(chainset, res, req, seed):
     if req.marginal_predict is not None:
         res.marginal_prediction = device_marginal_predict(chains, nb, ns, req.predict[0], req.predict[1], _marginal_loo_thin(ns, req.marginal_predict), None,
                                                           req.predict[2])
+    if req.marginal_loo_predict is not None:
+        res.marginal_loo_predictive = device_marginal_loo_predict(chains, nb, ns, _marginal_loo_thin(ns, req.marginal_loo_predict[0]),
+                                                                  req.marginal_loo_predict[1], req.loo_r_eff)
     if (req.summary_interval is not None or req.predict is not None or req.waic or req.loo or req.loo_predict is not None
-            or req.marginal_loo is not None or req.marginal_edges is not None):
+            or req.marginal_loo is not None or req.marginal_edges is not None or req.marginal_loo_predict is not None):
         res.stat_chains = len(chains)
     return res
 
@@ -2725,7 +2873,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                      pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
                      hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
                      marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000,
-        marginal_predict=False, marginal_predict_draws=2000):
+        marginal_predict=False, marginal_predict_draws=2000, marginal_loo_predict=False):
     """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
     xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
     xi_weights_code(xi_weights)
@@ -2741,7 +2889,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                         top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
                         marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
                         marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws)       # (checked before any sampling)
+                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -2796,7 +2944,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                          pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
                          hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
                          marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000,
-        marginal_predict=False, marginal_predict_draws=2000):
+        marginal_predict=False, marginal_predict_draws=2000, marginal_loo_predict=False):
     """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
     xi_weights_code(xi_weights)
     if nu == R:
@@ -2811,7 +2959,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                         top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
                         marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
                         marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws)       # (checked before any sampling)
+                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -2867,7 +3015,7 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
         pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
         hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
         marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000,
-        marginal_predict=False, marginal_predict_draws=2000):
+        marginal_predict=False, marginal_predict_draws=2000, marginal_loo_predict=False):
     """Fit! (gibbs.jl:725-751).  The `V` keyword is accepted and ignored, as in the reference.
     Extensions: summary_interval=95 computes Summary's statistics on the GPU (Results.summary_device);
     return_state=False then leaves the (large) state table on the device and frees it; ess_max_lag=0 (default lag
@@ -2915,6 +3063,12 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     no part.  It needs predict_X; predict_y and predict_interval are used as given.  Draws, chains and limits as for marginal_loo
     (marginal_predict_draws, default 2000 per chain); with stack_chains=True also under the stacking weights over every chain
     (Results.stacking.marginal_prediction).  Every other field of the Results is what it is without it.
+    marginal_loo_predict=True adds the LOO predictive checks of the training rows under the marginal PSIS weights (Results.marginal_loo_predictive,
+    see MarginalLOOPredict and device_marginal_loo_predict): what loo_predict returns -- the leave-one-out mean, sd, PIT and predict_interval%
+    interval of every row, RMSE, R2, coverage and the KS distance of the PITs -- from the weights of marginal_loo, which stay below the k-hat
+    threshold where loo_predict's do not, with the kernels on the device-resident matrices; its field `loo` is the dict of marginal_loo from the
+    same call.  Draws (marginal_loo_draws), chains, loo_r_eff and limits as for marginal_loo; marginal_loo=True beside it still makes its own
+    call.  Every other field of the Results is what it is without it.
     parameters.log keeps the reference's lines only."""
     xi_weights_code(xi_weights)
     _fit_requests(y, num_chains, predict_X=predict_X, predict_interval=predict_interval, pool_chains=pool_chains,
@@ -2922,7 +3076,7 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                   edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains,
                   edge_cov=edge_cov, marginal_loo=marginal_loo, marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
                         marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws)
+                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
         with open(filename, "w") as f:
@@ -2946,7 +3100,7 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                                     node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov,
                                     marginal_loo=marginal_loo, marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
                         marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws)
+                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
@@ -2957,4 +3111,4 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                             node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
                             marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
                         marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws)
+                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict)
