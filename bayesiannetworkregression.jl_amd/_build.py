@@ -1,4 +1,4 @@
-"""Build libbnr_hip.so, libbnr_mloo.so, libbnr_medge.so, libbnr_mpred.so and libbnr_mcheck.so (hipcc, gfx950) in-tree."""
+"""Build libbnr_hip.so, libbnr_mloo.so, libbnr_medge.so, libbnr_mpred.so, libbnr_mcheck.so and libbnr_mstack.so (hipcc, gfx950) in-tree."""
 import os
 import subprocess
 
@@ -8,16 +8,17 @@ MLOO_LIB = os.path.join(HERE, "libbnr_mloo.so")                              # m
 MEDGE_LIB = os.path.join(HERE, "libbnr_medge.so")                            # Rao-Blackwellised edge summaries: a third library, built and linked like libbnr_mloo.so
 MPRED_LIB = os.path.join(HERE, "libbnr_mpred.so")                            # Rao-Blackwellised prediction of new rows: a fourth library, built and linked like libbnr_medge.so
 MCHECK_LIB = os.path.join(HERE, "libbnr_mcheck.so")                          # LOO predictive checks under the marginal PSIS weights: a fifth library, built and linked like libbnr_mpred.so
+MSTACK_LIB = os.path.join(HERE, "libbnr_mstack.so")                          # chain stacking on the marginal PSIS-LOO: a sixth library, built and linked like libbnr_mcheck.so
 
 
 def build(force=False, verbose=False):
     if os.environ.get("BNR_HIP_LIB"):
         return LIB
     csrc = os.path.join(HERE, "csrc")
-    cmd = ["make", "-j6", "-C", csrc] + (["-B"] if force else [])          # six translation units, side by side
+    cmd = ["make", "-j7", "-C", csrc] + (["-B"] if force else [])          # seven translation units, side by side
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if verbose or r.returncode:
         print(r.stdout)
     if r.returncode:
-        raise RuntimeError("building libbnr_hip.so / libbnr_mloo.so / libbnr_medge.so / libbnr_mpred.so / libbnr_mcheck.so failed")
+        raise RuntimeError("building libbnr_hip.so / libbnr_mloo.so / libbnr_medge.so / libbnr_mpred.so / libbnr_mcheck.so / libbnr_mstack.so failed")
     return LIB

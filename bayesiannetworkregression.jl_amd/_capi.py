@@ -7,7 +7,7 @@ import os
 
 import numpy as np
 
-from ._build import LIB, MLOO_LIB, MEDGE_LIB, MPRED_LIB, MCHECK_LIB
+from ._build import LIB, MLOO_LIB, MEDGE_LIB, MPRED_LIB, MCHECK_LIB, MSTACK_LIB
 
 BNR_OK, BNR_ERR_BAD_ARG, BNR_ERR_HIP, BNR_ERR_CHOLESKY, BNR_ERR_SAMPLER = 0, 1, 2, 3, 4
 BNR_ERR_SAMPLER_CAP = BNR_ERR_SAMPLER
@@ -43,6 +43,7 @@ _mloo = None
 _medge = None
 _mpred = None
 _mcheck = None
+_mstack = None
 
 _SIGS = {
     "bnr_abi_version": (C.c_int, []),
@@ -197,6 +198,16 @@ _MCHECK_SIGS = {
 }
 MCHECK_EXPORTS = sorted(_MCHECK_SIGS)
 
+# libbnr_mstack.so (include/bnr_mstack.h): chain stacking on the marginal PSIS-LOO and the checks of the stacked mixture, a sixth library beside the five
+_MSTACK_SIGS = {
+    "bnr_mstack_abi_version": (C.c_int, []),
+    "bnr_stacked_mixture": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 5 + [C.c_double, C.c_double] + [_dp] * 5),
+    "bnr_chains_marginal_stack": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, C.c_int32, C.c_double, C.c_double,
+                                            C.c_double] + [_dp] * 4 + [C.POINTER(C.c_double), C.POINTER(C.c_int32)] + [_dp] * 6 + [C.POINTER(C.c_int32)]),
+    "bnr_mstack_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
+}
+MSTACK_EXPORTS = sorted(_MSTACK_SIGS)
+
 
 _foreign_hip = None      # set by lib(): why chains must not be created in this process (GPU-free entry points stay usable)
 
@@ -286,6 +297,13 @@ def mcheck_lib():
     return _mcheck
 
 
+def mstack_lib():
+    """Load libbnr_mstack.so, after libbnr_hip.so (which it is linked against); raises if it has not been built"""
+    global _mstack
+    _mstack = _mstack or _side_lib(MSTACK_LIB, _MSTACK_SIGS, "libbnr_mstack.so")
+    return _mstack
+
+
 def _device_side(side_lib):
     """side_lib() for the calls that open a device, refused like _device_lib()"""
     _device_lib()
@@ -298,6 +316,10 @@ def _device_mpred():
 
 def _device_mcheck():
     return _device_side(mcheck_lib)
+
+
+def _device_mstack():
+    return _device_side(mstack_lib)
 
 
 def _device_medge():
@@ -1366,6 +1388,66 @@ def chains_marginal_loo_predict(chains, first_row, nsamp, thin=1, r_eff=None, p_
     check(_device_mcheck().bnr_chains_marginal_loo_predict(arr, K, int(first_row), int(nsamp), thin, _ptr(r), float(p_lo), float(p_hi), _ptr(el),
                                                            _ptr(kh), *[_ptr(o) for o in out], _ptr(ml), _ptr(ll), C.byref(nb)))
     return el, kh, tuple(out), ml, ll, nb.value
+
+
+# ------------------------------------------------------------------------------------------ chain stacking on the marginal PSIS-LOO (libbnr_mstack.so, include/bnr_mstack.h)
+def mstack_set_option(name, value):
+    check(mstack_lib().bnr_mstack_set_option(name.encode(), int(value)))
+
+
+def stacked_mixture_raw(mean, var, log_weights, weights, nchains, y=None, p_lo=0.025, p_hi=0.975, device=0, fields=None):
+    """the tuple MCHECK_FIELDS (rows values each) of the stacked mixtures of normals in the rows of the rows x (nchains nd) matrices mean, var
+    (chain k's components in columns k nd .. (k + 1) nd - 1) under the chain weights `weights` and the log weights log_weights, normalised within
+    every chain, on the device (bnr_stacked_mixture); y (rows,) or None (then no pit); an entry not named in `fields` is not requested and comes
+    back as None.  ValueError (before any library call) for shapes that do not fit or rows D >= 2^31"""
+    shape = np.shape(mean)
+    K = int(nchains)
+    if len(shape) != 2 or np.shape(var) != shape or np.shape(log_weights) != shape:
+        raise ValueError("mean, var and log_weights must be rows x (nchains * nd) matrices of one shape")
+    if K < 1 or shape[1] < K or shape[1] % K:
+        raise ValueError("mean, var and log_weights must be rows x (nchains * nd) matrices with nd >= 1")
+    if shape[0] * shape[1] >= 2 ** 31:
+        raise ValueError("rows x D must stay below 2^31, not %d x %d" % shape)
+    mf = _matrix(mean, "mean")
+    vf, lf = np.ascontiguousarray(var, dtype=np.float64), np.ascontiguousarray(log_weights, dtype=np.float64)
+    rows, D = mf.shape
+    w = stack_weights_array(weights, K)
+    yf = None if y is None else np.ascontiguousarray(y, dtype=np.float64).reshape(-1)
+    if yf is not None and yf.shape != (rows,):
+        raise ValueError("y must hold one response per row of mean")
+    if fields is None:
+        fields = MCHECK_FIELDS if yf is not None else ("mean", "sd", "lower", "upper")
+    fields = _mcheck_fields(fields, yf is not None)
+    if set(fields) & {"lower", "upper"}:
+        p_lo, p_hi = loo_probs(p_lo, p_hi)
+    out = [np.empty(rows) if f in fields else None for f in MCHECK_FIELDS]
+    check(_device_mstack().bnr_stacked_mixture(int(device), rows, K, D // K, _ptr(mf), _ptr(vf), _ptr(lf), _ptr(w), _ptr(yf), float(p_lo),
+                                               float(p_hi), *[_ptr(o) for o in out]))
+    return tuple(out)
+
+
+def chains_marginal_stack(chains, first_row, nsamp, thin=1, r_eff=None, weights=None, max_iter=100000, gap_tol=1e-9, p_lo=0.025, p_hi=0.975,
+                          fields=MCHECK_FIELDS):
+    """(weights (K,), elpd_chain, pareto_k_chain (K x n), elpd_stack (n,), gap, iterations, the tuple MCHECK_FIELDS (n,: loo_mean, loo_sd,
+    loo_pit, loo_lower, loo_upper of the stacked mixture; an entry not named in `fields` is not requested and comes back as None), logml
+    (K draws,), n_bad) over rows first_row + j thin of every chain listed (bnr_chains_marginal_stack); weights: chain weights to use instead of
+    the solver's, or None"""
+    c0, arr, K, thin, nd = _pooled_window(chains, nsamp, thin)
+    n, D = c0.n, K * nd
+    r = r_eff_array(r_eff, n)
+    fw = None if weights is None else stack_weights_array(weights, K)
+    fields = tuple(fields)
+    if [f for f in fields if f not in MCHECK_FIELDS]:
+        raise ValueError("fields must name some of %r, not %r" % (MCHECK_FIELDS, fields))
+    if set(fields) & {"lower", "upper"}:
+        p_lo, p_hi = loo_probs(p_lo, p_hi)
+    w, el, kh, es, ml = np.empty(K), np.empty((K, n)), np.empty((K, n)), np.empty(n), np.empty(D)
+    out = [np.empty(n) if f in fields else None for f in MCHECK_FIELDS]
+    g, it, nb = C.c_double(0.0), C.c_int32(0), C.c_int32(0)
+    check(_device_mstack().bnr_chains_marginal_stack(arr, K, int(first_row), int(nsamp), thin, _ptr(r), _ptr(fw), int(max_iter), float(gap_tol),
+                                                     float(p_lo), float(p_hi), _ptr(w), _ptr(el), _ptr(kh), _ptr(es), C.byref(g), C.byref(it),
+                                                     *[_ptr(o) for o in out], _ptr(ml), C.byref(nb)))
+    return w, el, kh, es, g.value, it.value, tuple(out), ml, nb.value
 
 
 class Comm:

@@ -32,6 +32,9 @@ Julia is not available in this image, so the thin host layer a Julia user would 
                                                marginal LOO predictive checks (PIT and intervals under the marginal weights):
                                                MarginalLOOPredict / MarginalLOOPredictive, weighted_mixture, device_marginal_loo_predict,
                                                _host_weighted_mixture, _host_marginal_loo_predict
+                                               chain stacking on the marginal PSIS-LOO, one factorization pass: MarginalStack /
+                                               MarginalStacking, stacked_mixture, device_marginal_stack, _host_stacked_mixture,
+                                               _host_marginal_stack
   lower_triangle / create_lower_tri / setup_X!  utils.jl:17-57, gibbs.jl:239-247
 
 All sampling runs on the GPU through libbnr_hip.so; this file holds only the schedule logic (chain fan-out,
@@ -119,6 +122,7 @@ class Results:
     stat_chains: int = None          # how many chains the device statistics above (summary_device, prediction, waic, loo, loo_predictive) cover: 1 (chain 1's window), or
                                      # every chain of the fit with pool_chains=True; None when the fit computed none
     marginal_prediction: "MarginalPrediction" = None   # filled on request (marginal_predict=True): the prediction of predict_X with gamma integrated out, computed on the GPU (see MarginalPredict)
+    marginal_stacking: "MarginalStacking" = None   # filled on request (marginal_stack=True): the stacking weights of the chains from every chain's marginal PSIS-LOO and the LOO predictive checks of the stacked mixture (see MarginalStack)
     marginal_loo_predictive: "MarginalLOOPredictive" = None   # filled on request (marginal_loo_predict=True): the LOO predictive checks of the training rows under the marginal PSIS weights (see MarginalLOOPredict)
 
 
@@ -1931,16 +1935,25 @@ def _host_weighted_mixture(mean, var, log_weights, y, p_lo, p_hi, solver=None):
     normalised log weights; y (rows,) or None (then mean = sum w m and pit is NaN).  _loo_predict_rows with a sd per (row, draw); a row that holds
     a point mass (var = 0: Phi -> [t >= m]) goes through the library's bisection, the others through _mixture_quantile.  A row with a NaN or
     negative var, a NaN mean or a log weight that is not finite is NaN; a NaN y makes mean, sd and pit NaN."""
-    m, v, lw = (np.asarray(a, dtype=np.float64) for a in (mean, var, log_weights))
+    lw = np.asarray(log_weights, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        w = np.where(np.isfinite(lw), np.exp(lw), np.nan)
+    return _host_mixture_rows(mean, var, w, y, p_lo, p_hi, solver)
+
+
+def _host_mixture_rows(mean, var, w, y, p_lo, p_hi, solver=None):
+    """_host_weighted_mixture's six rows for component weights given as they are (rows x D; a NaN weight marks a log weight that was not
+    finite): the part it shares with _host_stacked_mixture"""
+    m, v, wt = (np.ascontiguousarray(a, dtype=np.float64) for a in (mean, var, w))    # (row-major: numpy's sums do not depend on the caller's layout)
     rows = m.shape[0]
     yv = None if y is None else np.asarray(y, dtype=np.float64).reshape(-1)
     c = _loo_bracket_c(p_lo, p_hi)
     out = np.full((6, rows), np.nan)
     h = 0.70710678118654752440
     for i in range(rows):
-        if not np.all(np.isfinite(lw[i])) or np.any(np.isnan(m[i])) or np.any(np.isnan(v[i])) or np.any(v[i] < 0):
+        if np.any(np.isnan(wt[i])) or np.any(np.isnan(m[i])) or np.any(np.isnan(v[i])) or np.any(v[i] < 0):
             continue
-        w, sd = np.exp(lw[i]), np.sqrt(v[i])
+        w, sd = wt[i], np.sqrt(v[i])
         point = v[i] == 0.0
 
         def F(t, w=w, mi=m[i], sd=sd, point=point):
@@ -2020,6 +2033,155 @@ def MarginalLOOPredict(results, X=None, y=None, x_transform=True, interval=None)
                          "training X and y")
     xi = _new_rows(X, x_transform, results.state["gamma"].shape[1], y)
     return _host_marginal_loo_predict([results.state], _dense_rows(xi), y, results.burn_in, results.sampled, 1, 95 if interval is None else interval)
+
+
+# ------------------------------------------------------------------------------------------ chain stacking on the marginal PSIS-LOO (an addition to the reference)
+# Stacking's weights from every chain's MARGINAL PSIS-LOO (gamma integrated out: importance ratios that PSIS can use), from one pass over the
+# pooled draws, and MarginalLOOPredict's checks of the stacked mixture (include/bnr_mstack.h, libbnr_mstack.so; DESIGN.md section 8, "Chain
+# stacking on the marginal LOO").  The _host_* functions restate the definitions in numpy: the fallback of MarginalStack and the yardstick of
+# the tests.
+@dataclass
+class MarginalStacking:
+    """ChainStacking's fields from every chain's marginal PSIS-LOO over its own nd = ceil(nsamp / thin) draws (weights, elpd_chain, elpd_chain_i,
+    pareto_k, n_high_k, elpd_stack, se, elpd_uniform, gap, iterations, elpd_stack_i, n_used, khat_threshold, chains, draws = K nd), and the
+    leave-one-out predictive checks of the stacked mixture sum_{k: w_k > 0} sum_s w_k w_kis N(y_i - resid_kis, var_kis): loo_mean, loo_sd,
+    loo_pit, loo_lower, loo_upper (n,), coverage of the interval% interval, ks (the distance of the PITs from U(0, 1)), rmse_loo, r2_loo over the
+    rows whose five checks are finite.  thin: what was pooled; n_bad: the draws that could not be factorised (every weight is 1 / K and every
+    check NaN while n_bad > 0); logml: log p(y | phi) of every draw.  summary, prediction, edge_cov, marginal_edges, marginal_prediction: the
+    fit's other requests under the weights (where requested)."""
+    weights: np.ndarray
+    elpd_chain: np.ndarray
+    elpd_chain_i: np.ndarray
+    pareto_k: np.ndarray
+    n_high_k: np.ndarray
+    elpd_stack: float
+    se: float
+    elpd_uniform: float
+    gap: float
+    iterations: int
+    elpd_stack_i: np.ndarray
+    n_used: int
+    khat_threshold: float
+    chains: int
+    draws: int
+    loo_mean: np.ndarray
+    loo_sd: np.ndarray
+    loo_pit: np.ndarray
+    loo_lower: np.ndarray
+    loo_upper: np.ndarray
+    coverage: float
+    ks: float
+    rmse_loo: float
+    r2_loo: float
+    interval: float
+    thin: int
+    n_bad: int
+    logml: np.ndarray = None
+    summary: dict = None
+    prediction: BNRPrediction = None
+    edge_cov: "EdgeCov" = None
+    marginal_edges: "MarginalEdges" = None
+    marginal_prediction: "MarginalPrediction" = None
+
+
+def _host_stacked_mixture(mean, var, log_weights, weights, nchains, y, p_lo, p_hi, solver=None):
+    """bnr_stacked_mixture restated in numpy: _host_weighted_mixture's six rows for the rows x (nchains nd) matrices mean, var and the log weights
+    normalised within every chain, under the chain weights: the columns of the chains with w_k > 0 side by side in chain order, every component's
+    weight the product w_k exp(lw) (NaN where lw is not finite); the dropped chains' columns are not read"""
+    m, v, lw = (np.asarray(a, dtype=np.float64) for a in (mean, var, log_weights))
+    K = int(nchains)
+    w = _capi.stack_weights_array(weights, K)
+    if m.ndim != 2 or m.shape[1] % K or m.shape[1] < K:
+        raise ValueError("mean must be a rows x (nchains * nd) matrix")
+    nd = m.shape[1] // K
+    keep = np.concatenate([np.arange(k * nd, (k + 1) * nd) for k in range(K) if w[k] > 0])
+    wk = np.repeat(w[w > 0], nd)
+    with np.errstate(all="ignore"):
+        wt = np.where(np.isfinite(lw[:, keep]), wk[None, :] * np.exp(lw[:, keep]), np.nan)
+    return _host_mixture_rows(m[:, keep], v[:, keep], wt, y, p_lo, p_hi, solver)
+
+
+def stacked_mixture(mean, var, log_weights, weights, nchains, y=None, interval=95, device=None):
+    """The summary of one stacked mixture of normals per row, sum_{k: w_k > 0} sum_s w_k exp(log_weights_iks) N(mean_iks, var_iks), of rows x
+    (nchains nd) matrices (chain k's components in columns k nd .. (k + 1) nd - 1) on the GPU (bnr_stacked_mixture): dict with mean, sd, pit
+    (= F_i(y_i); None without y), lower, upper (rows,) -- the central interval% interval --, interval and weights.  log_weights: the log weights
+    normalised within every chain, e.g. psis_weights of every chain's slice."""
+    p_lo, p_hi = _loo_interval_probs(interval)
+    out = dict(zip(_capi.MCHECK_FIELDS, _capi.stacked_mixture_raw(mean, var, log_weights, weights, nchains, y, p_lo, p_hi,
+                                                                  0 if device is None else int(device))))
+    out.update(interval=interval, weights=np.array(weights, dtype=np.float64))
+    return out
+
+
+def _marginal_stacking(y, weights, el, kh, gap, iterations, nd, mean, sd, pit, lower, upper, logml, interval, thin, n_bad):
+    """MarginalStacking from the weights, the per-chain pointwise numbers (K x n) and the checks of the stacked mixture: _stacking's totals with
+    nd as the per-chain sample size, _loo_predictive's over the rows whose checks are finite"""
+    st = _stacking(weights, el, kh, gap, iterations, nd)
+    lp = _loo_predictive(y, st.elpd_stack_i, st.elpd_stack_i, np.zeros(0), mean, sd, pit, lower, upper, interval, st.draws)
+    base = {f.name: getattr(st, f.name) for f in dataclasses.fields(st) if f.name in MarginalStacking.__dataclass_fields__ and f.name not in
+            ("summary", "prediction", "edge_cov", "marginal_edges", "marginal_prediction")}
+    return MarginalStacking(**base, loo_mean=lp.loo_mean, loo_sd=lp.loo_sd, loo_pit=lp.loo_pit, loo_lower=lp.loo_lower, loo_upper=lp.loo_upper,
+                            coverage=lp.coverage, ks=lp.ks, rmse_loo=lp.rmse_loo, r2_loo=lp.r2_loo, interval=interval, thin=int(thin), n_bad=int(n_bad),
+                            logml=logml)
+
+
+def device_marginal_stack(chains, nburn, nsamp, thin=1, interval=95, r_eff=None, weights=None, max_iter=100000, gap_tol=1e-9):
+    """Chain stacking on the marginal PSIS-LOO of every chain over rows nburn + 1 + j thin (j = 0 .. ceil(nsamp / thin) - 1), and the LOO
+    predictive checks of the stacked mixture, on the GPU (bnr_chains_marginal_stack) -> MarginalStacking.  One call and one pass: the
+    factorizations of device_marginal_loo over all chains at once, PSIS on every chain's slice of their loglik, the solver of stacking_weights
+    on the host, and the mixture kernels on the device-resident resid and var.  weights: chain weights to use instead of the solver's."""
+    chains = list(chains)
+    thin, nd = _capi.mloo_thin_draws(nsamp, thin)
+    p_lo, p_hi = _loo_interval_probs(interval)
+    max_iter, gap_tol = _stack_solver_args(max_iter, gap_tol)
+    w, el, kh, _es, gap, it, (mean, sd, pit, lo, hi), ml, nb = _capi.chains_marginal_stack(chains, nburn + 1, nsamp, thin, r_eff, weights, max_iter, gap_tol,
+                                                                                           p_lo, p_hi)
+    return _marginal_stacking(chains[0].y, w, el, kh, gap, it, nd, mean, sd, pit, lo, hi, ml, interval, thin, nb)
+
+
+def _host_marginal_stack(states, X, y, nburn, nsamp, thin=1, interval=95, r_eff=None, weights=None, max_iter=100000, gap_tol=1e-9):
+    """device_marginal_stack restated in numpy over the fetched tables of the same chains and the training X (n x q), y: _host_marginal_loglik
+    once, _psis_weights_host on every chain's slice, _host_stacking_weights over the rows that are finite in every chain, _host_stacked_mixture"""
+    states = list(states)
+    K = len(states)
+    if not 1 <= K <= STACK_MAX_CHAINS:
+        raise ValueError("need between 1 and %d tables" % STACK_MAX_CHAINS)
+    thin, nd = _capi.mloo_thin_draws(nsamp, thin)
+    p_lo, p_hi = _loo_interval_probs(interval)
+    max_iter, gap_tol = _stack_solver_args(max_iter, gap_tol)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    ll, rs, vr, ml, nb = _host_marginal_loglik(states, X, y, nburn, nsamp, thin)
+    lwn, el, kh = np.empty_like(ll), [], []
+    for k in range(K):
+        lwn[:, k * nd:(k + 1) * nd], e, kk = _psis_weights_host(ll[:, k * nd:(k + 1) * nd], r_eff)
+        el.append(e)
+        kh.append(kk)
+    el, kh = np.array(el), np.array(kh)
+    used = np.isfinite(el).all(axis=0)
+    if weights is not None:
+        w, gap, it = _capi.stack_weights_array(weights, K), math.nan, 0
+    elif used.any():
+        r = _host_stacking_weights(el[:, used].T, max_iter, gap_tol)
+        w, gap, it = r["weights"], r["gap"], r["iterations"]
+    else:
+        w, gap, it = np.full(K, 1.0 / K), math.nan, 0
+    mean, sd, pit, lo, hi, _w = _host_stacked_mixture(y[:, None] - rs, vr, lwn, w, K, y, p_lo, p_hi)
+    return _marginal_stacking(y, w, el, kh, gap, it, nd, mean, sd, pit, lo, hi, ml, interval, thin, nb)
+
+
+def MarginalStack(results, X=None, y=None, tables=None, x_transform=True):
+    """The chain stacking of a fit on the marginal PSIS-LOO -> MarginalStacking.  Uses the GPU's numbers when the fit carried them
+    (marginal_stack=True); otherwise restates them on the host (_host_marginal_stack, every draw, interval 95) over the fetched tables of the
+    chains -- `tables`, or results.state where that is a list of tables -- with the training X, y passed in."""
+    if results.marginal_stacking is not None:
+        return results.marginal_stacking
+    if tables is None and isinstance(results.state, (list, tuple)):
+        tables = results.state
+    if tables is None or len(tables) < 2 or X is None or y is None:
+        raise ValueError("MarginalStack needs Fit(..., marginal_stack=True), or the state tables of at least two chains together with the "
+                         "training X and y")
+    xi = _new_rows(X, x_transform, tables[0]["gamma"].shape[1], y)
+    return _host_marginal_stack(tables, _dense_rows(xi), y, results.burn_in, results.sampled)
 
 
 # ------------------------------------------------------------------------------------------ Rao-Blackwellised edge summaries (an addition to the reference)
@@ -2663,6 +2825,7 @@ class _Requests:
     marginal_edges: tuple = None     # (the draws per chain of the Rao-Blackwellised edge table (marginal_edges_draws), interval), or None
     marginal_predict: int = None     # the draws per chain of the Rao-Blackwellised prediction of predict_X (marginal_predict_draws), or None
     marginal_loo_predict: tuple = None   # (the draws per chain of the marginal LOO predictive checks (marginal_loo_draws), interval), or None
+    marginal_stack: tuple = None     # (the draws per chain of the stacking on the marginal PSIS-LOO (marginal_loo_draws), interval), or None
 
 
 def _one_rank(option):
@@ -2675,7 +2838,7 @@ def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, retur
                   predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None, pool_chains=False, predict_observation=False,
                   pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False, hdi_prob=0.95, fdr=0.05, node_sets=False,
                   top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False, marginal_loo_draws=2000, marginal_edges=False,
-                  marginal_edges_draws=2000, marginal_predict=False, marginal_predict_draws=2000, marginal_loo_predict=False):
+                  marginal_edges_draws=2000, marginal_predict=False, marginal_predict_draws=2000, marginal_stack=False, marginal_loo_predict=False):
     """The options of a fit (Fit's keywords) checked before any sampling, in this order -> _Requests.  Fit itself calls it ahead of
     parameters.log for the refusals alone, without X_new and nsamp: what needs them -- the new rows, the lag window of the rank diagnostics,
     r_eff -- is then left to generate_samples / generate_samples_dbl."""
@@ -2750,10 +2913,22 @@ def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, retur
         mlp = (int(marginal_loo_draws), predict_interval)
         if X_new is not None and X_new.n > MLOO_MAX_N:
             raise ValueError("marginal_loo_predict takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
+    mst = None
+    if marginal_stack:
+        if int(num_chains) < 2:
+            raise ValueError("marginal_stack needs num_chains >= 2: one chain has nothing to be weighted against")
+        if int(num_chains) > STACK_MAX_CHAINS:
+            raise ValueError("marginal_stack takes at most %d chains" % STACK_MAX_CHAINS)
+        _one_rank("marginal_stack")
+        _marginal_loo_thin(1, marginal_loo_draws)
+        _loo_interval_probs(predict_interval)
+        mst = (int(marginal_loo_draws), predict_interval)
+        if X_new is not None and X_new.n > MLOO_MAX_N:
+            raise ValueError("marginal_stack takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
     if X_new is not None:
         _capi.r_eff_array(loo_r_eff, X_new.n)
     return _Requests(return_state, summary_interval, ess_max_lag, pred, bool(waic), bool(loo), loo_r_eff, bool(pool_chains), bool(predict_observation),
-                     pred_seed, lp, bool(rank_diagnostics), es, ntop, bool(stack_chains), ec, ml, me, mp_, mlp)
+                     pred_seed, lp, bool(rank_diagnostics), es, ntop, bool(stack_chains), ec, ml, me, mp_, mlp, mst)
 
 
 def _finish(chainset, res, req, seed):
@@ -2770,7 +2945,10 @@ def _finish(chainset, res, req, seed):
     edge_cov: the posterior covariance of the edge coefficients over every chain of the fit (Results.edge_cov), and with stack the one under
     the stacking weights (Stacking.edge_cov).
     marginal_loo_predict: the LOO predictive checks under the marginal PSIS weights (Results.marginal_loo_predictive) over chain 1's window or,
-    with pool_chains, every chain's; a call of its own, which reads and sets nothing of the stacking record."""
+    with pool_chains, every chain's; a call of its own, which reads and sets nothing of the stacking record.
+    marginal_stack: the chain stacking on the marginal PSIS-LOO over every chain of the fit (Results.marginal_stacking), with summary_interval,
+    predict, edge_cov, marginal_edges and marginal_predict those requests under its weights; a record of its own, which reads and sets nothing
+    of Results.stacking or of what pool_chains or the default return."""
     nb, ns = res.burn_in, res.sampled
     every = [chainset.chains[c] for c in chainset.ids]
     pred_seed = seed if req.pred_seed is None else req.pred_seed
@@ -2792,6 +2970,20 @@ def _finish(chainset, res, req, seed):
     if req.marginal_predict is not None and req.stack:                  # (set only when asked for)
         res.stacking.marginal_prediction = device_marginal_predict(every, nb, ns, req.predict[0], req.predict[1], _marginal_loo_thin(ns, req.marginal_predict),
                                                                    res.stacking.weights, req.predict[2])
+    if req.marginal_stack is not None:
+        ms = device_marginal_stack(every, nb, ns, _marginal_loo_thin(ns, req.marginal_stack[0]), req.marginal_stack[1], req.loo_r_eff)
+        if req.summary_interval is not None:
+            ms.summary = device_summary_stacked(every, ms.weights, nb, ns, req.summary_interval)
+        if req.predict is not None:
+            ms.prediction = device_predict_stacked(every, ms.weights, nb, ns, *req.predict, pred_seed, predict_observation=req.predict_observation)
+        if req.edge_cov is not None:
+            ms.edge_cov = device_edge_cov(every, nb, ns, None if isinstance(req.edge_cov, str) else req.edge_cov, ms.weights)
+        if req.marginal_edges is not None:
+            ms.marginal_edges = device_marginal_edges(every, nb, ns, _marginal_loo_thin(ns, req.marginal_edges[0]), ms.weights, req.marginal_edges[1])
+        if req.marginal_predict is not None:
+            ms.marginal_prediction = device_marginal_predict(every, nb, ns, req.predict[0], req.predict[1], _marginal_loo_thin(ns, req.marginal_predict),
+                                                             ms.weights, req.predict[2])
+        res.marginal_stacking = ms
     if req.node_sets is not None:
         res.node_sets = device_node_sets(every, nb, ns, req.node_sets)
     if req.edge_sel is not None:
@@ -2873,7 +3065,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                      pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
                      hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
                      marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000,
-        marginal_predict=False, marginal_predict_draws=2000, marginal_loo_predict=False):
+        marginal_predict=False, marginal_predict_draws=2000, marginal_stack=False, marginal_loo_predict=False):
     """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
     xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
     xi_weights_code(xi_weights)
@@ -2889,7 +3081,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                         top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
                         marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
                         marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict)       # (checked before any sampling)
+                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict, marginal_stack=marginal_stack)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -2944,7 +3136,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                          pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
                          hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
                          marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000,
-        marginal_predict=False, marginal_predict_draws=2000, marginal_loo_predict=False):
+        marginal_predict=False, marginal_predict_draws=2000, marginal_stack=False, marginal_loo_predict=False):
     """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
     xi_weights_code(xi_weights)
     if nu == R:
@@ -2959,7 +3151,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                         top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
                         marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
                         marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict)       # (checked before any sampling)
+                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict, marginal_stack=marginal_stack)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -3015,7 +3207,7 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
         pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
         hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
         marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000,
-        marginal_predict=False, marginal_predict_draws=2000, marginal_loo_predict=False):
+        marginal_predict=False, marginal_predict_draws=2000, marginal_stack=False, marginal_loo_predict=False):
     """Fit! (gibbs.jl:725-751).  The `V` keyword is accepted and ignored, as in the reference.
     Extensions: summary_interval=95 computes Summary's statistics on the GPU (Results.summary_device);
     return_state=False then leaves the (large) state table on the device and frees it; ess_max_lag=0 (default lag
@@ -3069,6 +3261,12 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     threshold where loo_predict's do not, with the kernels on the device-resident matrices; its field `loo` is the dict of marginal_loo from the
     same call.  Draws (marginal_loo_draws), chains, loo_r_eff and limits as for marginal_loo; marginal_loo=True beside it still makes its own
     call.  Every other field of the Results is what it is without it.
+    marginal_stack=True adds the chain stacking on the marginal PSIS-LOO (Results.marginal_stacking, see MarginalStack and
+    device_marginal_stack): stack_chains' weights, per-chain and stacked scores from every chain's marginal PSIS-LOO over its own
+    marginal_loo_draws draws, all chains in one factorization pass, and the leave-one-out mean, sd, PIT and predict_interval% interval of the
+    stacked mixture with their coverage and KS distance.  With summary_interval, predict_X, edge_cov, marginal_edges or marginal_predict the
+    record also holds those under its weights.  It needs 2 to 32 chains on one rank and at most 2048 training rows; stack_chains=True beside
+    it fills Results.stacking as before, independently.  Every other field of the Results is what it is without it.
     parameters.log keeps the reference's lines only."""
     xi_weights_code(xi_weights)
     _fit_requests(y, num_chains, predict_X=predict_X, predict_interval=predict_interval, pool_chains=pool_chains,
@@ -3076,7 +3274,7 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                   edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains,
                   edge_cov=edge_cov, marginal_loo=marginal_loo, marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
                         marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict)
+                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict, marginal_stack=marginal_stack)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
         with open(filename, "w") as f:
@@ -3100,7 +3298,7 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                                     node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov,
                                     marginal_loo=marginal_loo, marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
                         marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict)
+                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict, marginal_stack=marginal_stack)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
@@ -3111,4 +3309,4 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                             node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
                             marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
                         marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict)
+                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict, marginal_stack=marginal_stack)
