@@ -33,6 +33,39 @@
 #define BNR_NB 32            // Cholesky block size
 #define BNR_GT 64            // Gram workgroup tile
 
+// What a kernel of the sweep hands to a LATER launch can go to memory through the L2 (write-through) instead of staying dirty in the XCD's write-back L2 until
+// the flush at the kernel boundary: same values, same addresses, only the moment the bytes leave the L2 moves.  BNR_STORE_THROUGH: one bit per site; a set bit
+// compiles the through form, a cleared one the plain store.  What the same launch reads back (progress, stamp and counter words) is never stored this way.
+// The default holds the sites that paid at the headline shape (profiles/store_through.txt): the update roles (8 chains: 2.3 -> 1.75 us between two panel steps for
+// 0.1-0.3 us more in the step), the Gram's tiles and launch 0's E and Y (0.8 and 0.9 us off the gap behind them).  The swept block of a panel workgroup stays plain: that
+// workgroup ends its launch, and waiting for its own write-through costs the step more than the flush; the small vectors and the scalar queue's PW / PA move nothing.
+enum { BNR_ST_GRAM = 1,       // partial tiles of k_gram / k_gram8 / k_gram_i8
+       BNR_ST_LAUNCH0 = 2,    // E and Y = I from the reduction (launch 0 of the factorization, k_gram_reduce)
+       BNR_ST_UPDATE = 4,     // both update roles of k_chol_step
+       BNR_ST_PANEL = 8,      // the swept own block of a panel workgroup
+       BNR_ST_RHS = 16,       // xw, a3, b of k_rhs, w of k_solve_w, a4 and xg of k_solve_a4
+       BNR_ST_XPASS = 32,     // PW / PA of k_xpass and k_xpass_group
+       BNR_ST_BACKPROJ = 64 };  // gamma, S and Psum of k_backproj / k_backproj64
+#ifndef BNR_STORE_THROUGH
+#define BNR_STORE_THROUGH (BNR_ST_GRAM | BNR_ST_LAUNCH0 | BNR_ST_UPDATE)
+#endif
+// 8 bytes: a relaxed agent-scope atomic store is a global_store_dwordx2 with sc1
+template <int SITE>
+__device__ __forceinline__ void bnr_st8(double *p, double v)
+{
+    if constexpr ((BNR_STORE_THROUGH & SITE) != 0) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else *p = v;
+}
+// 16 bytes (16-byte aligned): there is no 16-byte atomic, so the instruction is written out.  s_nop 1: a store of more than 8 bytes reads its data registers over
+// two more cycles, and the compiler, which does not look into the string, may overwrite them with its very next instruction
+template <int SITE>
+__device__ __forceinline__ void bnr_st16(double *p, const double __attribute__((ext_vector_type(2))) v)
+{
+    typedef double d2 __attribute__((ext_vector_type(2)));
+    if constexpr ((BNR_STORE_THROUGH & SITE) != 0) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(v) : "memory");
+    else *(d2 *)p = v;
+}
+
 
 // How a sweep kernel finds its chain.  One chain: the struct travels by value in the kernel arguments (no dependent
 // load in front of the first useful one -- the sweep of a single chain is a latency chain of ~30 launches).  Lockstep
@@ -617,8 +650,8 @@ __global__ __launch_bounds__(256) void k_xpass(const SRC chain_src, int s, int w
         }
         if (cd.X8) { const unsigned char *xp = cd.X8 + (size_t)e0 * ld + i; BNR_XPASS_BODY(xp) }
         else { const double *xp = cd.X + (size_t)e0 * ld + i; BNR_XPASS_BODY(xp) }
-        if (which & 1) cd.PW[(size_t)bid * ld + i] = aw;
-        if (which & 2) cd.PA[(size_t)bid * ld + i] = aa;
+        if (which & 1) bnr_st8<BNR_ST_XPASS>(cd.PW + (size_t)bid * ld + i, aw);
+        if (which & 2) bnr_st8<BNR_ST_XPASS>(cd.PA + (size_t)bid * ld + i, aa);
         if (which & 4) cd.PG[(size_t)bid * ld + i] = ag;
     }
     BNR_TL_OUT(cd, TL_XPASS);
@@ -681,7 +714,7 @@ __global__ __launch_bounds__(256) void k_xpass_group(const bnr_many chain_src, i
         else { const double *xp = c0.X + (size_t)e0 * ld + ic; BNR_XG_BODY(xp) }
 #pragma unroll
         for (int c = 0; c < 8; ++c)
-            if (c < nc && live) { s_pw[c][(size_t)bid * ld + i] = aw[c]; s_pa[c][(size_t)bid * ld + i] = aa[c]; }
+            if (c < nc && live) { bnr_st8<BNR_ST_XPASS>(s_pw[c] + (size_t)bid * ld + i, aw[c]); bnr_st8<BNR_ST_XPASS>(s_pa[c] + (size_t)bid * ld + i, aa[c]); }
     }
 }
 
@@ -749,9 +782,9 @@ __host__ __device__ inline long long bnr_gram_span_bytes(int n_pad, int kchunk, 
 // Grid (1-D) = round_up(tasks, 8) x chains.  Workgroup id -> XCD label id % 8 (round-robin dispatch), and within one
 // XCD's sequence the chains of a lockstep group are innermost: the 8 (or C) workgroups that need the same panels of X
 // (same tile, same K slice, different S) run next to each other on the same XCD and share them through its L2.
-// a partial-tile element goes to memory as a plain store (consumed after the kernel boundary).  The stores stay behind this helper: with
+// a partial-tile element goes to memory through the L2 (BNR_ST_GRAM; consumed after the kernel boundary, on other XCDs).  The stores stay behind this helper: with
 // "out[idx] = ..." written out in the task bodies the compiler schedules all six Gram kernels differently (profiles/kernel_variants_cleanup.txt)
-__device__ __forceinline__ void bnr_gstore(double *p, double v) { *p = v; }
+__device__ __forceinline__ void bnr_gstore(double *p, double v) { bnr_st8<BNR_ST_GRAM>(p, v); }
 // what a Gram task needs besides the chain's S row and its partial-tile buffer: equal for all members of a lockstep group
 struct bnr_gram_geom { const double *X; int n_pad, q_pad, ksplit, q, ntile; };
 __device__ __forceinline__ bnr_gram_geom bnr_geom_of(const bnr_dev &cd) { return bnr_gram_geom{cd.X, cd.n_pad, cd.q_pad, cd.ksplit, cd.q, cd.ntile}; }
@@ -1242,7 +1275,7 @@ __global__ __launch_bounds__(256, 2) void k_gram_i8(const SRC chain_src, int s, 
             double v = (double)acc[0][jt][r];
 #pragma unroll
             for (int l = 1; l < L; ++l) v = v * 256.0 + (double)acc[l][jt][r];
-            out[(jt * 16 + 4 * lq + r) * BNR_GT + wave * 16 + ln] = v * sc;
+            bnr_gstore(out + (jt * 16 + 4 * lq + r) * BNR_GT + wave * 16 + ln, v * sc);
         }
 }
 
@@ -1283,14 +1316,14 @@ __global__ __launch_bounds__(256) void k_gram_reduce(const SRC chain_src, int s)
     const int i = ti * BNR_GT + idx % BNR_GT, j = tj * BNR_GT + idx / BNR_GT;
     if (i == j) acc[0] += 1.0;
     if (i + 1 == j) acc[1] += 1.0;
-    *(bnr_d2 *)(cd.E + (size_t)i + ld * j) = acc;
+    bnr_st16<BNR_ST_LAUNCH0>(cd.E + (size_t)i + ld * j, acc);
     // Y = I (all n_pad x n_pad entries), spread over the whole grid, 16 bytes per store
     const int nwg = gridDim.x * gridDim.y, wg = blockIdx.x * gridDim.y + blockIdx.y, np = cd.n_pad;
     for (size_t e = ((size_t)wg * 256 + threadIdx.x) * 2; e < (size_t)np * np; e += (size_t)nwg * 512) {
         int r = (int)(e % np), c = (int)(e / np);
         if (r / BNR_NB > c / BNR_NB) continue;             // below the diagonal block Y = L^-T is never written and never read (k_solve_w, k_solve_a4)
         bnr_d2 v = {(r == c) ? 1.0 : 0.0, (r + 1 == c) ? 1.0 : 0.0};
-        *(bnr_d2 *)(cd.E + (size_t)(np + r) + ld * c) = v;
+        bnr_st16<BNR_ST_LAUNCH0>(cd.E + (size_t)(np + r) + ld * c, v);
     }
     if (threadIdx.x == 0) cd.stamp[blockIdx.x * 8 + blockIdx.y] = cd.plan[cd.pbase[0] + s].it;
     if (blockIdx.x == 0 && blockIdx.y == 0 && (int)threadIdx.x <= cd.ntile) cd.gprog[threadIdx.x] = 0u;   // all of G has been consumed
@@ -1519,7 +1552,7 @@ __device__ __forceinline__ int bnr_pipe_wave(bnr_panelp_lds &sh, int lane, doubl
     if (W == 3) BNR_PPH(7);
     if (dst && lane >= 32) {
 #pragma unroll
-        for (int c = 0; c < 8; ++c) dst[(size_t)rr + ld * (size_t)(C0 + c)] = a[c];
+        for (int c = 0; c < 8; ++c) bnr_st8<BNR_ST_PANEL>(dst + (size_t)rr + ld * (size_t)(C0 + c), a[c]);
     }
     return bad;
 }
@@ -1643,7 +1676,7 @@ __device__ __forceinline__ void bnr_reduce_parts(const bnr_dev &cd, int g0, int 
         const int r = (int)(e % np), c = (int)(e / np);
         if ((r < BNR_NB && c < BNR_NB) || r / BNR_NB > c / BNR_NB) continue;   // (below the diagonal block Y is never written and never read)
         bnr_d2 y = {(r == c) ? 1.0 : 0.0, (r + 1 == c) ? 1.0 : 0.0};
-        *(bnr_d2 *)(cd.E + (size_t)(np + r) + ld * c) = y;
+        bnr_st16<BNR_ST_LAUNCH0>(cd.E + (size_t)(np + r) + ld * c, y);
     }
     if (wg == 0 && tid <= cd.ntile) cd.gprog[tid] = 0u;
 #pragma unroll
@@ -1669,7 +1702,7 @@ __device__ __forceinline__ void bnr_reduce_parts(const bnr_dev &cd, int g0, int 
         const int i = ti * BNR_GT + idx % BNR_GT, j = tj * BNR_GT + idx / BNR_GT;
         if (i == j) acc[e][0] += 1.0;
         if (i + 1 == j) acc[e][1] += 1.0;
-        if (j >= BNR_NB) *(bnr_d2 *)(cd.E + (size_t)i + ld * j) = acc[e];
+        if (j >= BNR_NB) bnr_st16<BNR_ST_LAUNCH0>(cd.E + (size_t)i + ld * j, acc[e]);
     }
     if (tid < EPW) cd.stamp[g0 + tid] = it;                  // one word per eighth, as k_gram_reduce writes them
 #ifdef BNR_STAMPS
@@ -1764,7 +1797,7 @@ __global__ __launch_bounds__(256, BNR_CHOL_WG_PER_CU) void k_chol_step(const SRC
 #pragma unroll
                     for (int b = 0; b < 2; ++b)
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) cp[(size_t)(16 * b) + ld * (size_t)(16 * a + 4 * r)] = c[a][b][r];
+                        for (int r = 0; r < 4; ++r) bnr_st8<BNR_ST_UPDATE>(cp + (size_t)(16 * b) + ld * (size_t)(16 * a + 4 * r), c[a][b][r]);
             }
 #ifdef BNR_STAMPS
             if (tid == 0) atomicMax((unsigned long long *)&cd.dbg[p * 8 + 7], (unsigned long long)__builtin_amdgcn_s_memrealtime());
@@ -1792,7 +1825,7 @@ __global__ __launch_bounds__(256, BNR_CHOL_WG_PER_CU) void k_chol_step(const SRC
             for (int r = 0; r < 4; ++r) c[r] = cp[ld * (size_t)(4 * r)];
             c = bnr_tile_update(E + (size_t)(j * BNR_NB + mt * 16) + ld * (size_t)kc, E + (size_t)(rho * BNR_NB + nt * 16) + ld * (size_t)kc, ld, lane, c);
 #pragma unroll
-            for (int r = 0; r < 4; ++r) cp[ld * (size_t)(4 * r)] = c[r];
+            for (int r = 0; r < 4; ++r) bnr_st8<BNR_ST_UPDATE>(cp + ld * (size_t)(4 * r), c[r]);
         }
 #ifdef BNR_STAMPS
         if (tid == 0) atomicMax((unsigned long long *)&cd.dbg[p * 8 + 7], (unsigned long long)__builtin_amdgcn_s_memrealtime());
@@ -2208,8 +2241,8 @@ __global__ __launch_bounds__(256) void k_rhs(const SRC chain_src, int s)
         xs = (sa[0][il] + sa[1][il]) + (sa[2][il] + sa[3][il]);
         double z2 = (i < n) ? bnr_normal(cd.seed, P.it, SITE_G_Z2, (uint32_t)i, 0) : 0.0;
         double bb = (i < n) ? ((cd.y[i] - xw - mu) / tau - (xs + z2)) : 0.0;
-        cd.xw[i] = xw; cd.a3[i] = xs;          // a3 buffer keeps X sz (without z2)
-        cd.bw[i] = bb;                         // b, kept for the bookkeeping after the solve
+        bnr_st8<BNR_ST_RHS>(cd.xw + i, xw); bnr_st8<BNR_ST_RHS>(cd.a3 + i, xs);          // a3 buffer keeps X sz (without z2)
+        bnr_st8<BNR_ST_RHS>(cd.bw + i, bb);    // b, kept for the bookkeeping after the solve
     }
     BNR_TL_OUT(cd, TL_RHS);
 }
@@ -2231,7 +2264,7 @@ __global__ __launch_bounds__(256) void k_solve_w(const SRC chain_src)
     double acc = 0.0;
     for (int r = lane; r < rend; r += 64) acc = fma(col[r], cd.bw[r], acc);
     acc = wave_sum(acc);
-    if (lane == 0) cd.wv[c] = acc;
+    if (lane == 0) bnr_st8<BNR_ST_RHS>(cd.wv + c, acc);
     if (blockIdx.x == 0 && threadIdx.x == 0 && cd.counters[9]) {    // (see bnr_flag_gfail: the healthy path reads one word off the solve's own chain)
         cd.counters[9] = 0;
         atomicAdd((unsigned long long *)&cd.counters[3], 1ull); atomicAdd((unsigned long long *)&cd.counters[7], 1ull);
@@ -2267,8 +2300,8 @@ __global__ __launch_bounds__(1024) void k_solve_a4(const SRC chain_src)
         for (int g = 0; g < 32; ++g) a4 += spart[g * 33 + tid];
         const int r = rb * BNR_NB + tid;
         const double tau = cd.scal[SC_TAU], bb = cd.bw[r];
-        cd.a4[r] = a4;
-        cd.xg[r] = (r < cd.n) ? (cd.xw[r] + tau * cd.a3[r] + tau * (bb - a4)) : 0.0;
+        bnr_st8<BNR_ST_RHS>(cd.a4 + r, a4);
+        bnr_st8<BNR_ST_RHS>(cd.xg + r, (r < cd.n) ? (cd.xw[r] + tau * cd.a3[r] + tau * (bb - a4)) : 0.0);
     }
     BNR_TL_OUT(cd, TL_SOLVE_A4);
 }
@@ -2399,7 +2432,7 @@ __global__ __launch_bounds__(256) void k_backproj(const SRC chain_src, int s, in
         if (flags & 1) {
             double Sp = prev[cd.o_S + e];
             gam = tau * (cd.sz[e] + Sp * sdot[el32]) + W;
-            if (keeper) row[cd.o_gamma + e] = gam;
+            if (keeper) bnr_st8<BNR_ST_BACKPROJ>(row + cd.o_gamma + e, gam);
         } else gam = row[cd.o_gamma + e];
     }
     if (flags & 2) {
@@ -2430,7 +2463,7 @@ __global__ __launch_bounds__(256) void k_backproj(const SRC chain_src, int s, in
             if (!done) { cap = 1; Snew = s_val[0][el32]; }
         }
         if (keeper && act && !loop) Snew = bnr_gig_degenerate(gc, cd.seed, chi, psi, P.it, (uint32_t)e, &cap);
-        if (keeper && act) row[cd.o_S + e] = Snew;
+        if (keeper && act) bnr_st8<BNR_ST_BACKPROJ>(row + cd.o_S + e, Snew);
     } else if (act) Snew = row[cd.o_S + e];
     if (wave != dw) return;
     BNR_BSTAMP(2);
@@ -2459,7 +2492,7 @@ __global__ __launch_bounds__(256) void k_backproj(const SRC chain_src, int s, in
         double acc = 0.0;
 #pragma unroll 8
         for (int e2 = 0; e2 < 32; ++e2) acc += st[j * 33 + e2];
-        ps[j] = acc;
+        bnr_st8<BNR_ST_BACKPROJ>(ps + j, acc);
     }
     BNR_BSTAMP(3);
 #ifdef BNR_STAMPS
@@ -3056,7 +3089,7 @@ __global__ __launch_bounds__(256) void k_xpass_group2(const bnr_many chain_src, 
         else bnr_xg_dispatch(nc, c0.X + (size_t)e0 * ld + ic, ld, ne, sWZ, aw, aa);
 #pragma unroll
         for (int c = 0; c < 8; ++c)
-            if (c < nc && live) { s_pw[c][(size_t)bid * ld + i] = aw[c]; s_pa[c][(size_t)bid * ld + i] = aa[c]; }
+            if (c < nc && live) { bnr_st8<BNR_ST_XPASS>(s_pw[c] + (size_t)bid * ld + i, aw[c]); bnr_st8<BNR_ST_XPASS>(s_pa[c] + (size_t)bid * ld + i, aa[c]); }
     }
 }
 
@@ -3153,6 +3186,7 @@ __global__ __launch_bounds__(256) void k_backproj64(const SRC chain_src, int s, 
     const int pid = (gr / nchains) * 8 + gx;               // this chain's pair of chunks
     const bnr_dev &cd = chain_src.at(gr % nchains);
     if (2 * pid >= cd.nblk_bp) return;
+    BNR_TL_IN(cd, TL_BACKPROJ, pid == 0);
     const int R = cd.R, n_pad = cd.n_pad, nterm = 1 + 3 * R;
     extern __shared__ double sh[];                          // a4 | 64 dots | u products R x 65 | terms (3R + 1) x 65
     double *sa = sh, *sdot = sa + n_pad, *sdr = sdot + 64, *st = sdr + R * 65;
@@ -3207,7 +3241,7 @@ __global__ __launch_bounds__(256) void k_backproj64(const SRC chain_src, int s, 
         W = cd.Wbuf[e];
         const double Sp = prev[cd.o_S + e];
         gam = tau * (cd.sz[e] + Sp * sdot[lane]) + W;
-        if (wave == w2) row[cd.o_gamma + e] = gam;
+        if (wave == w2) bnr_st8<BNR_ST_BACKPROJ>(row + cd.o_gamma + e, gam);
     }
     if (wave == w2 || wave == w3) {
         int cap = 0;
@@ -3220,14 +3254,14 @@ __global__ __launch_bounds__(256) void k_backproj64(const SRC chain_src, int s, 
                 bnr_gig_setup(gc, 0.5, chi, psi);
                 Snew = bnr_gig_degenerate(gc, cd.seed, chi, psi, P.it, (uint32_t)e, &cap);
             }
-            if (kind != 3) { s_S[lane] = Snew; if (act) row[cd.o_S + e] = Snew; }
+            if (kind != 3) { s_S[lane] = Snew; if (act) bnr_st8<BNR_ST_BACKPROJ>(row + cd.o_S + e, Snew); }
         } else {
             const double Snew = bnr_bp_draw<3>(kind == 3, chi, psi, cd.seed, P.it, e0, lane, s_ctx[1], s_res[1], s_open[1], &cap);
-            if (kind == 3) { s_S[lane] = Snew; row[cd.o_S + e] = Snew; }
+            if (kind == 3) { s_S[lane] = Snew; bnr_st8<BNR_ST_BACKPROJ>(row + cd.o_S + e, Snew); }
         }
         if (cap) atomicAdd((unsigned long long *)&cd.counters[2], 1ull);
     }
-    if (!(flags & 4)) return;
+    if (!(flags & 4)) { BNR_TL_OUT(cd, TL_BACKPROJ); return; }
     __syncthreads();                                       // every edge's S is in s_S
     // the partial sums of update_theta! / update_Lambda! (gibbs.jl:476, 603-605): every lane its edge's terms -- wave w those of the factors w, w + 4, ... --, then one thread per
     // chunk and term sums the term over the chunk's 32 edges in k_backproj's order
@@ -3251,9 +3285,10 @@ __global__ __launch_bounds__(256) void k_backproj64(const SRC chain_src, int s, 
             double acc = 0.0;
 #pragma unroll 8
             for (int e2 = 0; e2 < 32; ++e2) acc += st[j * 65 + 32 * half + e2];
-            cd.Psum[(size_t)chunk * nterm + j] = acc;
+            bnr_st8<BNR_ST_BACKPROJ>(cd.Psum + (size_t)chunk * nterm + j, acc);
         }
     }
+    BNR_TL_OUT(cd, TL_BACKPROJ);
 }
 
 // (k_sdigits grew in the third session -- several workgroups per chain -- and moved here with the late kernels: see the note above)
