@@ -1,4 +1,4 @@
-"""Build libbnr_hip.so, libbnr_mloo.so, libbnr_medge.so, libbnr_mpred.so, libbnr_mcheck.so and libbnr_mstack.so (hipcc, gfx950) in-tree."""
+"""Build libbnr_hip.so, libbnr_mloo.so, libbnr_medge.so, libbnr_mpred.so, libbnr_mcheck.so, libbnr_mstack.so and libbnr_mcov.so (hipcc, gfx950) in-tree."""
 import os
 import subprocess
 
@@ -9,16 +9,17 @@ MEDGE_LIB = os.path.join(HERE, "libbnr_medge.so")                            # R
 MPRED_LIB = os.path.join(HERE, "libbnr_mpred.so")                            # Rao-Blackwellised prediction of new rows: a fourth library, built and linked like libbnr_medge.so
 MCHECK_LIB = os.path.join(HERE, "libbnr_mcheck.so")                          # LOO predictive checks under the marginal PSIS weights: a fifth library, built and linked like libbnr_mpred.so
 MSTACK_LIB = os.path.join(HERE, "libbnr_mstack.so")                          # chain stacking on the marginal PSIS-LOO: a sixth library, built and linked like libbnr_mcheck.so
+MCOV_LIB = os.path.join(HERE, "libbnr_mcov.so")                              # Rao-Blackwellised covariance of the edge coefficients: a seventh library, built and linked like libbnr_medge.so
 
 
 def build(force=False, verbose=False):
     if os.environ.get("BNR_HIP_LIB"):
         return LIB
     csrc = os.path.join(HERE, "csrc")
-    cmd = ["make", "-j7", "-C", csrc] + (["-B"] if force else [])          # seven translation units, side by side
+    cmd = ["make", "-j8", "-C", csrc] + (["-B"] if force else [])          # eight translation units, side by side
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if verbose or r.returncode:
         print(r.stdout)
     if r.returncode:
-        raise RuntimeError("building libbnr_hip.so / libbnr_mloo.so / libbnr_medge.so / libbnr_mpred.so / libbnr_mcheck.so / libbnr_mstack.so failed")
+        raise RuntimeError("building libbnr_hip.so / libbnr_mloo.so / libbnr_medge.so / libbnr_mpred.so / libbnr_mcheck.so / libbnr_mstack.so / libbnr_mcov.so failed")
     return LIB

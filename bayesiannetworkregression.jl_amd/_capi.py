@@ -7,7 +7,7 @@ import os
 
 import numpy as np
 
-from ._build import LIB, MLOO_LIB, MEDGE_LIB, MPRED_LIB, MCHECK_LIB, MSTACK_LIB
+from ._build import LIB, MLOO_LIB, MEDGE_LIB, MPRED_LIB, MCHECK_LIB, MSTACK_LIB, MCOV_LIB
 
 BNR_OK, BNR_ERR_BAD_ARG, BNR_ERR_HIP, BNR_ERR_CHOLESKY, BNR_ERR_SAMPLER = 0, 1, 2, 3, 4
 BNR_ERR_SAMPLER_CAP = BNR_ERR_SAMPLER
@@ -44,6 +44,7 @@ _medge = None
 _mpred = None
 _mcheck = None
 _mstack = None
+_mcov = None
 
 _SIGS = {
     "bnr_abi_version": (C.c_int, []),
@@ -208,6 +209,18 @@ _MSTACK_SIGS = {
 }
 MSTACK_EXPORTS = sorted(_MSTACK_SIGS)
 
+# libbnr_mcov.so (include/bnr_mcov.h): the Rao-Blackwellised covariance of the edge coefficients, a seventh library beside the six
+_ip = C.POINTER(C.c_int32)
+_MCOV_SIGS = {
+    "bnr_mcov_abi_version": (C.c_int, []),
+    # device, n, q, K, nd | X, y, tau2, mu, S, W, weights | ncols, cols | mean, cov, within, m, v | n_bad
+    "bnr_marginal_gamma_cov": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 7 + [C.c_int32, _ip] + [_dp] * 5 + [_ip]),
+    # chains, nchains, weights, first_row, nsamp, thin | ncols, cols | mean, cov, within, m, v | n_bad
+    "bnr_chains_marginal_edge_cov": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _ip] + [_dp] * 5 + [_ip]),
+    "bnr_mcov_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
+}
+MCOV_EXPORTS = sorted(_MCOV_SIGS)
+
 
 _foreign_hip = None      # set by lib(): why chains must not be created in this process (GPU-free entry points stay usable)
 
@@ -304,6 +317,13 @@ def mstack_lib():
     return _mstack
 
 
+def mcov_lib():
+    """Load libbnr_mcov.so, after libbnr_hip.so (which it is linked against); raises if it has not been built"""
+    global _mcov
+    _mcov = _mcov or _side_lib(MCOV_LIB, _MCOV_SIGS, "libbnr_mcov.so")
+    return _mcov
+
+
 def _device_side(side_lib):
     """side_lib() for the calls that open a device, refused like _device_lib()"""
     _device_lib()
@@ -320,6 +340,10 @@ def _device_mcheck():
 
 def _device_mstack():
     return _device_side(mstack_lib)
+
+
+def _device_mcov():
+    return _device_side(mcov_lib)
 
 
 def _device_medge():
@@ -1253,6 +1277,47 @@ def chains_marginal_edges(chains, first_row, nsamp, thin=1, weights=None, p_lo=0
     check(_device_medge().bnr_chains_marginal_edges(arr, K, _ptr(w), int(first_row), int(nsamp), thin, p_lo, p_hi, *[_ptr(o) for o in out], _ptr(m),
                                                     _ptr(v), C.byref(nb)))
     return tuple(out), m, v, nb.value
+
+
+# ------------------------------------------------------------------------------------------ Rao-Blackwellised covariance of the edge coefficients (libbnr_mcov.so, include/bnr_mcov.h)
+def mcov_set_option(name, value):
+    check(mcov_lib().bnr_mcov_set_option(name.encode(), int(value)))
+
+
+def _mcov_outputs(D, m, per_draw):
+    return np.empty(m), np.empty((m, m)), np.empty((m, m)), (np.empty((D, m)) if per_draw else None), (np.empty((D, m)) if per_draw else None)
+
+
+def marginal_gamma_cov_raw(X, y, tau2, mu, S, W=None, cols=None, nchains=1, weights=None, device=0, per_draw=True):
+    """(mean (c,), cov, within (c x c), m, v (D x c) or None, n_bad) of the columns `cols` (None: all q) of the mixture of the D = nchains nd
+    conditional normals of gamma given phi = (tau2, mu, S, W), chain k's draws in rows k nd .., on the device (bnr_marginal_gamma_cov)"""
+    Xf, yf, t2, mu_, Sf, Wf, n, q, D = _phi_arrays(X, y, tau2, mu, S, W)
+    K = int(nchains)
+    if K < 1 or D % K:
+        raise ValueError("the %d draws do not split into %d chains" % (D, K))
+    ci = cov_cols(cols, q)
+    w = None if weights is None else stack_weights_array(weights, K)
+    c = q if ci is None else ci.size
+    mean, cov, within, m, v = _mcov_outputs(D, c, per_draw)
+    nb = C.c_int32(0)
+    check(_device_mcov().bnr_marginal_gamma_cov(int(device), n, q, K, D // K, _ptr(Xf), _ptr(yf), _ptr(t2), _ptr(mu_), _ptr(Sf), _ptr(Wf), _ptr(w), c,
+                                                None if ci is None else ci.ctypes.data_as(_ip), _ptr(mean), _ptr(cov), _ptr(within), _ptr(m),
+                                                _ptr(v), C.byref(nb)))
+    return mean, cov, within, m, v, nb.value
+
+
+def chains_marginal_edge_cov(chains, first_row, nsamp, thin=1, cols=None, weights=None, per_draw=False):
+    """(mean (c,), cov, within (c x c), m, v (K nd x c) or None, n_bad) over rows first_row + j thin of every chain listed
+    (bnr_chains_marginal_edge_cov)"""
+    c0, arr, K, thin, nd = _pooled_window(chains, nsamp, thin)
+    ci = cov_cols(cols, c0.q)
+    w = None if weights is None else stack_weights_array(weights, K)
+    c = c0.q if ci is None else ci.size
+    mean, cov, within, m, v = _mcov_outputs(K * nd, c, per_draw)
+    nb = C.c_int32(0)
+    check(_device_mcov().bnr_chains_marginal_edge_cov(arr, K, _ptr(w), int(first_row), int(nsamp), thin, c, None if ci is None else ci.ctypes.data_as(_ip),
+                                                      _ptr(mean), _ptr(cov), _ptr(within), _ptr(m), _ptr(v), C.byref(nb)))
+    return mean, cov, within, m, v, nb.value
 
 
 # ------------------------------------------------------------------------------------------ Rao-Blackwellised prediction of new rows (libbnr_mpred.so, include/bnr_mpred.h)

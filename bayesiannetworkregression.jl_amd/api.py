@@ -122,6 +122,7 @@ class Results:
     stat_chains: int = None          # how many chains the device statistics above (summary_device, prediction, waic, loo, loo_predictive) cover: 1 (chain 1's window), or
                                      # every chain of the fit with pool_chains=True; None when the fit computed none
     marginal_prediction: "MarginalPrediction" = None   # filled on request (marginal_predict=True): the prediction of predict_X with gamma integrated out, computed on the GPU (see MarginalPredict)
+    marginal_edge_cov: "MarginalEdgeCov" = None   # filled on request (marginal_edge_cov=...): the covariance of the edge coefficients with gamma integrated out, computed on the GPU (see MarginalEdgeCov)
     marginal_stacking: "MarginalStacking" = None   # filled on request (marginal_stack=True): the stacking weights of the chains from every chain's marginal PSIS-LOO and the LOO predictive checks of the stacked mixture (see MarginalStack)
     marginal_loo_predictive: "MarginalLOOPredictive" = None   # filled on request (marginal_loo_predict=True): the LOO predictive checks of the training rows under the marginal PSIS weights (see MarginalLOOPredict)
 
@@ -2397,6 +2398,167 @@ def _marginal_edges_of(results, X=None, y=None, x_transform=True):
     return _host_marginal_edges([results.state], _dense_rows(xi), y, results.burn_in, results.sampled)
 
 
+# ------------------------------------------------------------------------------------------ Rao-Blackwellised covariance of the edge coefficients (an addition to the reference)
+# The covariance of the edge coefficients with gamma integrated out (include/bnr_mcov.h, libbnr_mcov.so; DESIGN.md section 8, "Rao-Blackwellised
+# covariance of the edge coefficients").  Given phi of a table row the whole vector gamma is N(m, tau2 (D - D X^T A^-1 X D)), so the covariance
+# of the mixture over the draws is within + between (law of total covariance): within = sum omega_s of the conditional covariances, between =
+# the covariance of the conditional means.  EdgeCov estimates the same matrix from the gamma draws, within-draw noise included.  The _host_*
+# functions restate the definitions in numpy: the fallback of MarginalEdgeCov and the yardstick of the tests.
+_MEDGE_COV_FIELDS = ("cols", "node1", "node2", "mean", "cov", "within", "chains", "draws", "thin", "n_bad", "weights")
+
+
+class MarginalEdgeCov(EdgeCov):
+    """The posterior covariance of edge coefficients with gamma integrated out.  cols, node1 / node2, mean, cov, chains, draws, weights: as in
+    EdgeCov, with mean and cov those of the mixture sum_s omega_s N(m_s, C_s) over the draws of phi; within (m, m): sum_s omega_s C_s, the part
+    that is known in closed form given a draw (its diagonal is not clamped: it may fall a rounding below 0); thin: the row stride; n_bad: the
+    draws that could not be factorised (mean, cov and within are NaN while n_bad > 0).  Derived on the host: EdgeCov's sd, corr, contrast(C)
+    and top_pairs(n), between = cov - within, rb_share = diag(within) / diag(cov).
+
+    MarginalEdgeCov(results, X, y) is the accessor of a fit: the GPU's numbers when the fit carried them (marginal_edge_cov=...), otherwise
+    restated on the host over results.state (needs return_state=True and the training X, y; chain 1's window, every draw, every edge).  Without a
+    Results, MarginalEdgeCov(**fields) builds the record itself from exactly the fields above."""
+
+    def __new__(cls, results=None, X=None, y=None, x_transform=True, **fields):
+        if results is not None:
+            return _marginal_edge_cov_of(results, X, y, x_transform)
+        return object.__new__(cls)
+
+    def __init__(self, results=None, X=None, y=None, x_transform=True, **fields):
+        if results is not None:                                          # (the accessor: __new__ returned a finished object)
+            return
+        if set(fields) != set(_MEDGE_COV_FIELDS):
+            raise TypeError("MarginalEdgeCov takes a Results, or exactly the fields %r" % (_MEDGE_COV_FIELDS,))
+        self.__dict__.update(fields)
+
+    def __repr__(self):
+        return "MarginalEdgeCov(edges=%d, chains=%d, draws=%d%s)" % (self.cols.size, self.chains, self.draws, "" if self.weights is None else ", weighted")
+
+    @property
+    def between(self):
+        """cov - within: the covariance of the conditional means over the draws"""
+        return self.cov - self.within
+
+    @property
+    def rb_share(self):
+        """diag(within) / diag(cov) (NaN where the variance is not > 0): the share of every variance that is known in closed form"""
+        dc, dw = np.diag(self.cov), np.diag(self.within)
+        with np.errstate(all="ignore"):
+            return np.where(dc > 0, dw / dc, np.nan)
+
+
+def _marginal_edge_cov(q, cols, mean, cov, within, nchains, draws, thin, n_bad, weights):
+    V = int(round((-1 + math.sqrt(1 + 8 * q)) / 2))
+    cols = np.arange(q, dtype=np.int64) if cols is None else np.asarray(cols, dtype=np.int64)
+    if V * (V + 1) // 2 == q:
+        n1, n2 = _edge_nodes(V, cols)
+    else:                                                               # (a raw matrix whose columns are no lower triangle)
+        n1 = n2 = cols + 1
+    return MarginalEdgeCov(cols=cols, node1=n1, node2=n2, mean=mean, cov=cov, within=within, chains=int(nchains), draws=int(draws), thin=int(thin),
+                           n_bad=int(n_bad), weights=None if weights is None else np.array(weights, dtype=np.float64))
+
+
+def _host_gamma_cov(X, y, tau2, mu, S, W=None, cols=None):
+    """(m (c,), Cov (c, c)) of ONE draw phi = (tau2, mu, S, W) for the n x q matrix X, in numpy through the A^-1 form: with A = I + X D X^T,
+    m = W + D X^T A^-1 (y - mu - X W) and Cov = tau2 (D - D X^T A^-1 X D), at the columns cols (None: all)"""
+    X = np.asarray(X, dtype=np.float64)
+    y = np.asarray(y, dtype=np.float64).reshape(-1)
+    n, q = X.shape
+    S = np.asarray(S, dtype=np.float64).reshape(q)
+    W = np.zeros(q) if W is None else np.asarray(W, dtype=np.float64).reshape(q)
+    ci = _capi.cov_cols(cols, q)
+    sel = np.arange(q) if ci is None else ci.astype(np.int64)
+    A = np.eye(n) + (X * S[None, :]) @ X.T
+    Xs = X[:, sel]
+    AiX = np.linalg.solve(A, Xs)
+    m = W[sel] + S[sel] * (Xs.T @ np.linalg.solve(A, y - float(mu) - X @ W))
+    # (a repeated column: the diagonal term stands wherever the two edges are the same one)
+    C = float(tau2) * (np.where(sel[:, None] == sel[None, :], S[sel][:, None], 0.0) - (S[sel][:, None] * (Xs.T @ AiX)) * S[sel][None, :])
+    return m, C
+
+
+def _host_gamma_cov_terms(X, y, tau2, mu, S, W, nchains, cols=None, weights=None, dtype=np.float64):
+    """(mean, cov, within, m, v, n_bad) of bnr_marginal_gamma_cov restated in numpy with the header's orders: per draw the scaled panel
+    T' = (sqrt(tau2) S) L^-1 X, the chains' Grams of T' and of m - mean over the draws in order (products and sums in `dtype`), the chain sums
+    of _medge_stat for mean and the diagonal, k ascending"""
+    X = np.asarray(X, dtype=np.float64)
+    n, q = X.shape
+    tau2 = np.atleast_1d(np.asarray(tau2, dtype=np.float64))
+    D, K = tau2.size, int(nchains)
+    nd = D // K
+    S = np.asarray(S, dtype=np.float64).reshape(D, q)
+    ci = _capi.cov_cols(cols, q)
+    sel = np.arange(q) if ci is None else ci.astype(np.int64)
+    c = sel.size
+    w = np.full(K, 1.0 / K) if weights is None else np.asarray(weights, dtype=np.float64).reshape(K)
+    m, v, n_bad = _host_gamma_terms(X, y, tau2, mu, S, W)
+    m, v = m[:, sel], v[:, sel]
+    nanm = np.full((c, c), np.nan)
+    if n_bad:
+        return np.full(c, np.nan), nanm, nanm.copy(), m, v, n_bad
+    Xs, eye = X[:, sel], np.eye(n)
+    Gw = np.zeros((K, c, c), dtype=dtype)
+    for s in range(D):
+        L = np.linalg.cholesky(eye + (X * S[s][None, :]) @ X.T)
+        Tp = ((np.sqrt(tau2[s]) * S[s, sel])[None, :] * _solve_lower(L, Xs)).astype(dtype)
+        Gw[s // nd] = Gw[s // nd] + Tp.T @ Tp
+    mean = _medge_stat(m, K, w)
+    dg = _medge_stat(tau2[:, None] * S[:, sel], K, w)
+    Cm = (m - mean[None, :]).astype(dtype)
+    gw, gb = np.zeros((c, c), dtype=dtype), np.zeros((c, c), dtype=dtype)
+    for k in range(K):
+        Ck = Cm[k * nd:(k + 1) * nd]
+        gw = gw + (Gw[k] / dtype(nd)) * dtype(w[k])
+        gb = gb + ((Ck.T @ Ck) / dtype(nd)) * dtype(w[k])
+    within = np.where(sel[:, None] == sel[None, :], dg.astype(dtype)[:, None], dtype(0.0)) - gw
+    return mean, within + gb, within, m, v, 0
+
+
+def marginal_gamma_cov(X, y, tau2, mu, S, W=None, cols=None, nchains=1, weights=None, device=None):
+    """The covariance of the edge coefficients `cols` (0-based; None: all q) of the mixture of the conditional normals of gamma given each of
+    D = nchains nd draws phi = (tau2, mu, S, W) for one n x q model matrix, on the GPU (bnr_marginal_gamma_cov): dict with mean (c,), cov and
+    within (c, c; cov = within + between), m, v (D x c: the per-draw conditional means and variances) and n_bad.  One draw gives its
+    conditional covariance, cov == within."""
+    mean, cov, within, m, v, nb = _capi.marginal_gamma_cov_raw(X, y, tau2, mu, S, W, cols, nchains, weights, 0 if device is None else int(device))
+    return dict(mean=mean, cov=cov, within=within, m=m, v=v, n_bad=nb)
+
+
+def device_marginal_edge_cov(chains, nburn, nsamp, thin=1, cols=None, weights=None, per_draw=False):
+    """The covariance of the edge coefficients `cols` (0-based; None: all q) with gamma integrated out over rows nburn + 1 + j thin (j = 0 ..
+    ceil(nsamp / thin) - 1) of ALL the chains listed, pooled (under `weights`, the chain weights -- the stacking weights -- where given), on the
+    GPU (bnr_chains_marginal_edge_cov) -> MarginalEdgeCov.  per_draw=True returns (record, m, v) with the per-draw conditional means and
+    variances of the chosen columns."""
+    chains = list(chains)
+    thin, nd = _capi.mloo_thin_draws(nsamp, thin)
+    if not chains:
+        raise ValueError("need at least one chain")
+    ci = _capi.cov_cols(cols, chains[0].q)
+    mean, cov, within, m, v, nb = _capi.chains_marginal_edge_cov(chains, nburn + 1, nsamp, thin, ci, weights, per_draw)
+    rec = _marginal_edge_cov(chains[0].q, ci, mean, cov, within, len(chains), nd * len(chains), thin, nb, weights)
+    return (rec, m, v) if per_draw else rec
+
+
+def _host_marginal_edge_cov(states, X, y, nburn, nsamp, thin=1, cols=None, weights=None, dtype=np.float64):
+    """device_marginal_edge_cov restated in numpy over the fetched tables of the same chains and the training X (n x q), y, with the orders of
+    include/bnr_mcov.h (_host_gamma_cov_terms)"""
+    states = list(states)
+    thin, nd = _capi.mloo_thin_draws(nsamp, thin)
+    X = np.asarray(X, dtype=np.float64)
+    q = X.shape[1]
+    ci = _capi.cov_cols(cols, q)
+    mean, cov, within, _m, _v, nb = _host_gamma_cov_terms(X, y, *_host_marginal_draws(states, nburn, nsamp, thin), len(states), ci, weights, dtype)
+    return _marginal_edge_cov(q, ci, mean, cov, within, len(states), nd * len(states), thin, nb, weights)
+
+
+def _marginal_edge_cov_of(results, X=None, y=None, x_transform=True):
+    if results.marginal_edge_cov is not None:
+        return results.marginal_edge_cov
+    if results.state is None or X is None or y is None:
+        raise ValueError("MarginalEdgeCov needs Fit(..., marginal_edge_cov=True), or the state table (return_state=True) together with the training "
+                         "X and y")
+    xi = _new_rows(X, x_transform, results.state["gamma"].shape[1], y)
+    return _host_marginal_edge_cov([results.state], _dense_rows(xi), y, results.burn_in, results.sampled)
+
+
 # ------------------------------------------------------------------------------------------ Rao-Blackwellised prediction of new rows (an addition to the reference)
 # The prediction of new rows with gamma integrated out (include/bnr_mpred.h, libbnr_mpred.so; DESIGN.md section 8, "Rao-Blackwellised prediction").
 # Given phi = (tau2, mu, u, lambda, S) of a table row, the mean response of a new row x* is N(mean, var) in closed form, so its posterior is the
@@ -2826,6 +2988,7 @@ class _Requests:
     marginal_predict: int = None     # the draws per chain of the Rao-Blackwellised prediction of predict_X (marginal_predict_draws), or None
     marginal_loo_predict: tuple = None   # (the draws per chain of the marginal LOO predictive checks (marginal_loo_draws), interval), or None
     marginal_stack: tuple = None     # (the draws per chain of the stacking on the marginal PSIS-LOO (marginal_loo_draws), interval), or None
+    marginal_edge_cov: tuple = None  # (the draws per chain (marginal_edges_draws), "all" or the 0-based edge indices) of the Rao-Blackwellised covariance, or None
 
 
 def _one_rank(option):
@@ -2838,7 +3001,7 @@ def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, retur
                   predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None, pool_chains=False, predict_observation=False,
                   pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False, hdi_prob=0.95, fdr=0.05, node_sets=False,
                   top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False, marginal_loo_draws=2000, marginal_edges=False,
-                  marginal_edges_draws=2000, marginal_predict=False, marginal_predict_draws=2000, marginal_stack=False, marginal_loo_predict=False):
+                  marginal_edges_draws=2000, marginal_predict=False, marginal_predict_draws=2000, marginal_edge_cov=False, marginal_stack=False, marginal_loo_predict=False):
     """The options of a fit (Fit's keywords) checked before any sampling, in this order -> _Requests.  Fit itself calls it ahead of
     parameters.log for the refusals alone, without X_new and nsamp: what needs them -- the new rows, the lag window of the rank diagnostics,
     r_eff -- is then left to generate_samples / generate_samples_dbl."""
@@ -2894,6 +3057,15 @@ def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, retur
         me = (int(marginal_edges_draws), predict_interval)
         if X_new is not None and X_new.n > MLOO_MAX_N:
             raise ValueError("marginal_edges takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
+    mec = None
+    mc = _edge_cov_cols(marginal_edge_cov, None if X_new is None else X_new.V)
+    if mc is not None:
+        _one_rank("marginal_edge_cov")
+        if isinstance(marginal_edges_draws, bool) or int(marginal_edges_draws) != marginal_edges_draws or int(marginal_edges_draws) < 1:
+            raise ValueError("marginal_edges_draws must be an integer >= 1, not %r" % (marginal_edges_draws,))
+        mec = (int(marginal_edges_draws), mc)
+        if X_new is not None and X_new.n > MLOO_MAX_N:
+            raise ValueError("marginal_edge_cov takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
     mp_ = None
     if marginal_predict:
         if predict_X is None:
@@ -2928,7 +3100,7 @@ def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, retur
     if X_new is not None:
         _capi.r_eff_array(loo_r_eff, X_new.n)
     return _Requests(return_state, summary_interval, ess_max_lag, pred, bool(waic), bool(loo), loo_r_eff, bool(pool_chains), bool(predict_observation),
-                     pred_seed, lp, bool(rank_diagnostics), es, ntop, bool(stack_chains), ec, ml, me, mp_, mlp, mst)
+                     pred_seed, lp, bool(rank_diagnostics), es, ntop, bool(stack_chains), ec, ml, me, mp_, mlp, mst, marginal_edge_cov=mec)
 
 
 def _finish(chainset, res, req, seed):
@@ -2944,6 +3116,8 @@ def _finish(chainset, res, req, seed):
     prediction under the weights; what pool_chains or the default return is not changed by it.
     edge_cov: the posterior covariance of the edge coefficients over every chain of the fit (Results.edge_cov), and with stack the one under
     the stacking weights (Stacking.edge_cov).
+    marginal_edge_cov: the covariance of the edge coefficients with gamma integrated out (Results.marginal_edge_cov) over chain 1's window or,
+    with pool_chains, every chain's.
     marginal_loo_predict: the LOO predictive checks under the marginal PSIS weights (Results.marginal_loo_predictive) over chain 1's window or,
     with pool_chains, every chain's; a call of its own, which reads and sets nothing of the stacking record.
     marginal_stack: the chain stacking on the marginal PSIS-LOO over every chain of the fit (Results.marginal_stacking), with summary_interval,
@@ -3022,6 +3196,9 @@ def _finish(chainset, res, req, seed):
         res.marginal_loo = device_marginal_loo(chains, nb, ns, _marginal_loo_thin(ns, req.marginal_loo), req.loo_r_eff)
     if req.marginal_edges is not None:
         res.marginal_edges = device_marginal_edges(chains, nb, ns, _marginal_loo_thin(ns, req.marginal_edges[0]), None, req.marginal_edges[1])
+    if req.marginal_edge_cov is not None:
+        res.marginal_edge_cov = device_marginal_edge_cov(chains, nb, ns, _marginal_loo_thin(ns, req.marginal_edge_cov[0]),
+                                                         None if isinstance(req.marginal_edge_cov[1], str) else req.marginal_edge_cov[1])
     if req.marginal_predict is not None:
         res.marginal_prediction = device_marginal_predict(chains, nb, ns, req.predict[0], req.predict[1], _marginal_loo_thin(ns, req.marginal_predict), None,
                                                           req.predict[2])
@@ -3065,7 +3242,7 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                      pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
                      hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
                      marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000,
-        marginal_predict=False, marginal_predict_draws=2000, marginal_stack=False, marginal_loo_predict=False):
+        marginal_predict=False, marginal_predict_draws=2000, marginal_edge_cov=False, marginal_stack=False, marginal_loo_predict=False):
     """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
     xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
     xi_weights_code(xi_weights)
@@ -3081,7 +3258,8 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                         top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
                         marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
                         marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict, marginal_stack=marginal_stack)       # (checked before any sampling)
+                        marginal_predict_draws=marginal_predict_draws, marginal_edge_cov=marginal_edge_cov, marginal_loo_predict=marginal_loo_predict,
+                        marginal_stack=marginal_stack)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -3136,7 +3314,7 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                          pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
                          hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
                          marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000,
-        marginal_predict=False, marginal_predict_draws=2000, marginal_stack=False, marginal_loo_predict=False):
+        marginal_predict=False, marginal_predict_draws=2000, marginal_edge_cov=False, marginal_stack=False, marginal_loo_predict=False):
     """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
     xi_weights_code(xi_weights)
     if nu == R:
@@ -3151,7 +3329,8 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                         top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
                         marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
                         marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict, marginal_stack=marginal_stack)       # (checked before any sampling)
+                        marginal_predict_draws=marginal_predict_draws, marginal_edge_cov=marginal_edge_cov, marginal_loo_predict=marginal_loo_predict,
+                        marginal_stack=marginal_stack)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -3207,7 +3386,7 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
         pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
         hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
         marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000,
-        marginal_predict=False, marginal_predict_draws=2000, marginal_stack=False, marginal_loo_predict=False):
+        marginal_predict=False, marginal_predict_draws=2000, marginal_edge_cov=False, marginal_stack=False, marginal_loo_predict=False):
     """Fit! (gibbs.jl:725-751).  The `V` keyword is accepted and ignored, as in the reference.
     Extensions: summary_interval=95 computes Summary's statistics on the GPU (Results.summary_device);
     return_state=False then leaves the (large) state table on the device and frees it; ess_max_lag=0 (default lag
@@ -3249,6 +3428,11 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     N(m_e, v_e | tau2, mu, u, lambda, S) over the draws, free of the within-draw noise of the gamma draws.  Draws, chains and limits as for
     marginal_loo (marginal_edges_draws, default 2000 per chain); with stack_chains=True also under the stacking weights over every chain
     (Results.stacking.marginal_edges).  Every other field of the Results is what it is without it.
+    marginal_edge_cov=True (or an array of 0-based edge indices, or a list of 1-based (node1, node2) pairs, as edge_cov takes them) adds the
+    covariance matrix of those edge coefficients with gamma integrated out (Results.marginal_edge_cov, see MarginalEdgeCov and
+    device_marginal_edge_cov): edge_cov's matrix without the within-draw noise of the gamma draws, split into `within` and `between`, with
+    EdgeCov's sd, corr, contrast(C) and top_pairs.  Draws (marginal_edges_draws), chains and limits as for marginal_edges; the covariance under
+    stacking weights is device_marginal_edge_cov(chains, ..., weights=...).  Every other field of the Results is what it is without it.
     marginal_predict=True adds the prediction of predict_X with gamma integrated out (Results.marginal_prediction, see MarginalPrediction and
     device_marginal_predict): per new row the mean, sd and interval of the mixture of N(mean_j, var_j | tau2, mu, u, lambda, S) over the draws, the
     predictive sd and interval of a new observation and, with predict_y, lpd / elpd and the PIT -- no predictive noise is drawn, so pred_seed plays
@@ -3274,7 +3458,8 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                   edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains,
                   edge_cov=edge_cov, marginal_loo=marginal_loo, marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
                         marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict, marginal_stack=marginal_stack)
+                        marginal_predict_draws=marginal_predict_draws, marginal_edge_cov=marginal_edge_cov, marginal_loo_predict=marginal_loo_predict,
+                        marginal_stack=marginal_stack)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
         with open(filename, "w") as f:
@@ -3298,7 +3483,8 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                                     node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov,
                                     marginal_loo=marginal_loo, marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
                         marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict, marginal_stack=marginal_stack)
+                        marginal_predict_draws=marginal_predict_draws, marginal_edge_cov=marginal_edge_cov, marginal_loo_predict=marginal_loo_predict,
+                        marginal_stack=marginal_stack)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
@@ -3309,4 +3495,5 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
                             node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
                             marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
                         marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws, marginal_loo_predict=marginal_loo_predict, marginal_stack=marginal_stack)
+                        marginal_predict_draws=marginal_predict_draws, marginal_edge_cov=marginal_edge_cov, marginal_loo_predict=marginal_loo_predict,
+                        marginal_stack=marginal_stack)
