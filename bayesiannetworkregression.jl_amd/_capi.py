@@ -3,11 +3,12 @@
 The HIP library is the ONLY compute path of the package: if the shared object is missing or a call fails the
 error is raised, never papered over with a CPU fallback."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
 
-from ._build import LIB, MLOO_LIB, MEDGE_LIB, MPRED_LIB, MCHECK_LIB, MSTACK_LIB, MCOV_LIB
+from ._build import LIB, MARGINAL_LIBS
 
 BNR_OK, BNR_ERR_BAD_ARG, BNR_ERR_HIP, BNR_ERR_CHOLESKY, BNR_ERR_SAMPLER = 0, 1, 2, 3, 4
 BNR_ERR_SAMPLER_CAP = BNR_ERR_SAMPLER
@@ -39,12 +40,7 @@ class ChainView(C.Structure):
                 + [(k, C.c_void_p) for k in ("X", "y", "ek", "el", "trace")])
 _dp = C.c_void_p
 _lib = None
-_mloo = None
-_medge = None
-_mpred = None
-_mcheck = None
-_mstack = None
-_mcov = None
+_mloo = _medge = _mpred = _mcheck = _mstack = _mcov = None       # the marginal libraries once loaded (marginal_lib sets them)
 
 _SIGS = {
     "bnr_abi_version": (C.c_int, []),
@@ -157,69 +153,60 @@ for _u in ("tau2", "u_xi", "gamma", "D", "theta", "Delta", "M", "mu", "Lambda", 
 
 EXPORTS = sorted(_SIGS)
 
-# libbnr_mloo.so (include/bnr_mloo.h): marginal PSIS-LOO, a library of its own beside libbnr_hip.so
-_MLOO_SIGS = {
-    "bnr_mloo_abi_version": (C.c_int, []),
-    "bnr_marginal_loglik": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 10 + [C.POINTER(C.c_int32)]),
-    "bnr_chains_marginal_loo": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 7 + [C.POINTER(C.c_int32)]),
-    "bnr_mloo_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
-}
-MLOO_EXPORTS = sorted(_MLOO_SIGS)
-MLOO_MAX_N = 2048
-
-# libbnr_medge.so (include/bnr_medge.h): Rao-Blackwellised edge summaries, a third library beside the two
-_MEDGE_SIGS = {
-    "bnr_medge_abi_version": (C.c_int, []),
-    "bnr_marginal_gamma": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 8 + [C.POINTER(C.c_int32)]),
-    "bnr_mixture_summary": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 3 + [C.c_double, C.c_double] + [_dp] * 7),
-    "bnr_chains_marginal_edges": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double] + [_dp] * 9
-                                  + [C.POINTER(C.c_int32)]),
-    "bnr_medge_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
-}
-MEDGE_EXPORTS = sorted(_MEDGE_SIGS)
-
-# libbnr_mpred.so (include/bnr_mpred.h): Rao-Blackwellised prediction of new rows, a fourth library beside the three
-_MPRED_SIGS = {
-    "bnr_mpred_abi_version": (C.c_int, []),
-    "bnr_marginal_predict": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 9 + [C.POINTER(C.c_int32)]),
-    "bnr_mixture_score": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 6),
-    "bnr_chains_marginal_predict": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, C.c_double,
-                                              C.c_double] + [_dp] * 12 + [C.POINTER(C.c_int32)]),
-    "bnr_mpred_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
-}
-MPRED_EXPORTS = sorted(_MPRED_SIGS)
-
-# libbnr_mcheck.so (include/bnr_mcheck.h): the LOO predictive checks under the marginal PSIS weights, a fifth library beside the four
-_MCHECK_SIGS = {
-    "bnr_mcheck_abi_version": (C.c_int, []),
-    "bnr_weighted_mixture": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_dp] * 4 + [C.c_double, C.c_double] + [_dp] * 5),
-    "bnr_chains_marginal_loo_predict": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_double, C.c_double]
-                                        + [_dp] * 9 + [C.POINTER(C.c_int32)]),
-    "bnr_mcheck_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
-}
-MCHECK_EXPORTS = sorted(_MCHECK_SIGS)
-
-# libbnr_mstack.so (include/bnr_mstack.h): chain stacking on the marginal PSIS-LOO and the checks of the stacked mixture, a sixth library beside the five
-_MSTACK_SIGS = {
-    "bnr_mstack_abi_version": (C.c_int, []),
-    "bnr_stacked_mixture": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 5 + [C.c_double, C.c_double] + [_dp] * 5),
-    "bnr_chains_marginal_stack": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, C.c_int32, C.c_double, C.c_double,
-                                            C.c_double] + [_dp] * 4 + [C.POINTER(C.c_double), C.POINTER(C.c_int32)] + [_dp] * 6 + [C.POINTER(C.c_int32)]),
-    "bnr_mstack_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
-}
-MSTACK_EXPORTS = sorted(_MSTACK_SIGS)
-
-# libbnr_mcov.so (include/bnr_mcov.h): the Rao-Blackwellised covariance of the edge coefficients, a seventh library beside the six
+# The six marginal libraries beside libbnr_hip.so, each linked against it, by short name: lib<short>.so (MARGINAL_LIBS of _build.py holds the
+# paths, in this order) behind include/bnr_<short>.h, and the signatures of its exports
 _ip = C.POINTER(C.c_int32)
-_MCOV_SIGS = {
-    "bnr_mcov_abi_version": (C.c_int, []),
-    # device, n, q, K, nd | X, y, tau2, mu, S, W, weights | ncols, cols | mean, cov, within, m, v | n_bad
-    "bnr_marginal_gamma_cov": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 7 + [C.c_int32, _ip] + [_dp] * 5 + [_ip]),
-    # chains, nchains, weights, first_row, nsamp, thin | ncols, cols | mean, cov, within, m, v | n_bad
-    "bnr_chains_marginal_edge_cov": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _ip] + [_dp] * 5 + [_ip]),
-    "bnr_mcov_set_option": (C.c_int, [C.c_char_p, C.c_int64]),
+_SET_OPTION = (C.c_int, [C.c_char_p, C.c_int64])
+_MARGINAL_SIGS = {
+    "mloo": {       # marginal PSIS-LOO
+        "bnr_mloo_abi_version": (C.c_int, []),
+        "bnr_marginal_loglik": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 10 + [_ip]),
+        "bnr_chains_marginal_loo": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 7 + [_ip]),
+        "bnr_mloo_set_option": _SET_OPTION,
+    },
+    "medge": {      # Rao-Blackwellised edge summaries
+        "bnr_medge_abi_version": (C.c_int, []),
+        "bnr_marginal_gamma": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 8 + [_ip]),
+        "bnr_mixture_summary": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 3 + [C.c_double, C.c_double] + [_dp] * 7),
+        "bnr_chains_marginal_edges": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double] + [_dp] * 9
+                                      + [_ip]),
+        "bnr_medge_set_option": _SET_OPTION,
+    },
+    "mpred": {      # Rao-Blackwellised prediction of new rows
+        "bnr_mpred_abi_version": (C.c_int, []),
+        "bnr_marginal_predict": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 9 + [_ip]),
+        "bnr_mixture_score": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 6),
+        "bnr_chains_marginal_predict": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, C.c_double,
+                                                  C.c_double] + [_dp] * 12 + [_ip]),
+        "bnr_mpred_set_option": _SET_OPTION,
+    },
+    "mcheck": {     # the LOO predictive checks under the marginal PSIS weights
+        "bnr_mcheck_abi_version": (C.c_int, []),
+        "bnr_weighted_mixture": (C.c_int, [C.c_int32, C.c_int32, C.c_int32] + [_dp] * 4 + [C.c_double, C.c_double] + [_dp] * 5),
+        "bnr_chains_marginal_loo_predict": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_double, C.c_double]
+                                            + [_dp] * 9 + [_ip]),
+        "bnr_mcheck_set_option": _SET_OPTION,
+    },
+    "mstack": {     # chain stacking on the marginal PSIS-LOO and the checks of the stacked mixture
+        "bnr_mstack_abi_version": (C.c_int, []),
+        "bnr_stacked_mixture": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 5 + [C.c_double, C.c_double] + [_dp] * 5),
+        "bnr_chains_marginal_stack": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, C.c_int32, C.c_double, C.c_double,
+                                                C.c_double] + [_dp] * 4 + [C.POINTER(C.c_double), _ip] + [_dp] * 6 + [_ip]),
+        "bnr_mstack_set_option": _SET_OPTION,
+    },
+    "mcov": {       # the Rao-Blackwellised covariance of the edge coefficients
+        "bnr_mcov_abi_version": (C.c_int, []),
+        # device, n, q, K, nd | X, y, tau2, mu, S, W, weights | ncols, cols | mean, cov, within, m, v | n_bad
+        "bnr_marginal_gamma_cov": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [_dp] * 7 + [C.c_int32, _ip] + [_dp] * 5 + [_ip]),
+        # chains, nchains, weights, first_row, nsamp, thin | ncols, cols | mean, cov, within, m, v | n_bad
+        "bnr_chains_marginal_edge_cov": (C.c_int, [C.POINTER(C.c_void_p), C.c_int32, _dp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _ip] + [_dp] * 5 + [_ip]),
+        "bnr_mcov_set_option": _SET_OPTION,
+    },
 }
-MCOV_EXPORTS = sorted(_MCOV_SIGS)
+MLOO_LIB, MEDGE_LIB, MPRED_LIB, MCHECK_LIB, MSTACK_LIB, MCOV_LIB = MARGINAL_LIBS.values()
+_MLOO_SIGS, _MEDGE_SIGS, _MPRED_SIGS, _MCHECK_SIGS, _MSTACK_SIGS, _MCOV_SIGS = (_MARGINAL_SIGS[short] for short in MARGINAL_LIBS)
+MLOO_EXPORTS, MEDGE_EXPORTS, MPRED_EXPORTS, MCHECK_EXPORTS, MSTACK_EXPORTS, MCOV_EXPORTS = (sorted(_MARGINAL_SIGS[short]) for short in MARGINAL_LIBS)
+MLOO_MAX_N = 2048
 
 
 _foreign_hip = None      # set by lib(): why chains must not be created in this process (GPU-free entry points stay usable)
@@ -267,91 +254,40 @@ def lib():
     return _lib
 
 
-def _side_lib(path, sigs, what):
-    """Load the library at `path` that is linked against libbnr_hip.so, after it, and give its functions the signatures `sigs`; raises if it has
-    not been built"""
-    lib()
-    if not os.path.exists(path):
-        raise ImportError("%s is missing at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'`; there is no CPU fallback"
-                          % (what, path))
-    L = C.CDLL(path)
-    for name, (res, args) in sigs.items():
-        f = getattr(L, name)
-        f.restype = res
-        f.argtypes = args
-    return L
+def marginal_lib(short):
+    """Load the marginal library lib<short>.so (once), after libbnr_hip.so, which it is linked against, and give its functions their
+    signatures; raises if it has not been built"""
+    g = globals()
+    if g["_" + short] is None:
+        lib()
+        path = MARGINAL_LIBS[short]
+        if not os.path.exists(path):
+            raise ImportError("%s is missing at %s -- build it with `python -c 'import __graft_entry__ as g; g.build()'`; there is no CPU fallback"
+                              % (os.path.basename(path), path))
+        L = C.CDLL(path)
+        for name, (res, args) in _MARGINAL_SIGS[short].items():
+            f = getattr(L, name)
+            f.restype = res
+            f.argtypes = args
+        g["_" + short] = L
+    return g["_" + short]
 
 
-def mloo_lib():
-    """Load libbnr_mloo.so, after libbnr_hip.so (which it is linked against); raises if it has not been built"""
-    global _mloo
-    _mloo = _mloo or _side_lib(MLOO_LIB, _MLOO_SIGS, "libbnr_mloo.so")
-    return _mloo
+mloo_lib, medge_lib, mpred_lib, mcheck_lib, mstack_lib, mcov_lib = (functools.partial(marginal_lib, short) for short in MARGINAL_LIBS)
 
 
-def medge_lib():
-    """Load libbnr_medge.so, after libbnr_hip.so (which it is linked against); raises if it has not been built"""
-    global _medge
-    _medge = _medge or _side_lib(MEDGE_LIB, _MEDGE_SIGS, "libbnr_medge.so")
-    return _medge
-
-
-def mpred_lib():
-    """Load libbnr_mpred.so, after libbnr_hip.so (which it is linked against); raises if it has not been built"""
-    global _mpred
-    _mpred = _mpred or _side_lib(MPRED_LIB, _MPRED_SIGS, "libbnr_mpred.so")
-    return _mpred
-
-
-def mcheck_lib():
-    """Load libbnr_mcheck.so, after libbnr_hip.so (which it is linked against); raises if it has not been built"""
-    global _mcheck
-    _mcheck = _mcheck or _side_lib(MCHECK_LIB, _MCHECK_SIGS, "libbnr_mcheck.so")
-    return _mcheck
-
-
-def mstack_lib():
-    """Load libbnr_mstack.so, after libbnr_hip.so (which it is linked against); raises if it has not been built"""
-    global _mstack
-    _mstack = _mstack or _side_lib(MSTACK_LIB, _MSTACK_SIGS, "libbnr_mstack.so")
-    return _mstack
-
-
-def mcov_lib():
-    """Load libbnr_mcov.so, after libbnr_hip.so (which it is linked against); raises if it has not been built"""
-    global _mcov
-    _mcov = _mcov or _side_lib(MCOV_LIB, _MCOV_SIGS, "libbnr_mcov.so")
-    return _mcov
-
-
-def _device_side(side_lib):
-    """side_lib() for the calls that open a device, refused like _device_lib()"""
+def _device_marginal(short):
+    """marginal_lib(short) for the calls that open a device, refused like _device_lib()"""
     _device_lib()
-    return side_lib()
+    return marginal_lib(short)
 
 
-def _device_mpred():
-    return _device_side(mpred_lib)
+def _marginal_set_option(short, name, value):
+    check(getattr(marginal_lib(short), "bnr_%s_set_option" % short)(name.encode(), int(value)))
 
 
-def _device_mcheck():
-    return _device_side(mcheck_lib)
-
-
-def _device_mstack():
-    return _device_side(mstack_lib)
-
-
-def _device_mcov():
-    return _device_side(mcov_lib)
-
-
-def _device_medge():
-    return _device_side(medge_lib)
-
-
-def _device_mloo():
-    return _device_side(mloo_lib)
+mloo_set_option, medge_set_option, mpred_set_option, mcheck_set_option, mstack_set_option, mcov_set_option = (
+    functools.partial(_marginal_set_option, short) for short in MARGINAL_LIBS)
 
 
 def _device_lib():
@@ -1153,10 +1089,6 @@ def cov_raw(x, nchains=1, weights=None, device=0):
 MLOO_FIELDS = ("loglik", "resid", "var", "logml")
 
 
-def mloo_set_option(name, value):
-    check(mloo_lib().bnr_mloo_set_option(name.encode(), int(value)))
-
-
 def _phi_arrays(X, y, tau2, mu, S, W):
     """(Xf, yf, t2, mu, Sf, Wf, n, q, D): the model matrix (column-major) and D draws phi = (tau2, mu, S, W) of a raw marginal call as contiguous
     float64 arrays; ValueError for shapes that do not fit or n > 2048"""
@@ -1187,7 +1119,7 @@ def marginal_loglik_raw(X, y, tau2, mu, S, W=None, device=0, fields=MLOO_FIELDS)
         raise ValueError("fields must name loglik, resid or var (and logml), not %r" % (fields,))
     out = [np.empty((n, D)) if f in fields else None for f in MLOO_FIELDS[:3]] + [np.empty(D) if "logml" in fields else None]
     nb = C.c_int32(0)
-    check(_device_mloo().bnr_marginal_loglik(int(device), n, q, D, _ptr(Xf), _ptr(yf), _ptr(t2), _ptr(m), _ptr(Sf), _ptr(Wf), *[_ptr(o) for o in out],
+    check(_device_marginal("mloo").bnr_marginal_loglik(int(device), n, q, D, _ptr(Xf), _ptr(yf), _ptr(t2), _ptr(m), _ptr(Sf), _ptr(Wf), *[_ptr(o) for o in out],
                                              C.byref(nb)))
     return tuple(out) + (nb.value,)
 
@@ -1218,7 +1150,7 @@ def chains_marginal_loo(chains, first_row, nsamp, thin=1, r_eff=None, loglik=Fal
     el, kh, lm, ls, ml = np.empty(n), np.empty(n), np.empty(n), np.empty(n), np.empty(D)
     ll = np.empty((n, D)) if loglik else None
     nb = C.c_int32(0)
-    check(_device_mloo().bnr_chains_marginal_loo(arr, K, int(first_row), int(nsamp), thin, _ptr(r), _ptr(el), _ptr(kh), _ptr(lm), _ptr(ls), _ptr(ml),
+    check(_device_marginal("mloo").bnr_chains_marginal_loo(arr, K, int(first_row), int(nsamp), thin, _ptr(r), _ptr(el), _ptr(kh), _ptr(lm), _ptr(ls), _ptr(ml),
                                                  _ptr(ll), C.byref(nb)))
     return el, kh, lm, ls, ml, ll, nb.value
 
@@ -1227,17 +1159,13 @@ def chains_marginal_loo(chains, first_row, nsamp, thin=1, r_eff=None, loglik=Fal
 MEDGE_SUMMARY_FIELDS = ("mean", "sd", "var_within", "p_pos", "p_neg", "lower", "upper")
 
 
-def medge_set_option(name, value):
-    check(medge_lib().bnr_medge_set_option(name.encode(), int(value)))
-
-
 def marginal_gamma_raw(X, y, tau2, mu, S, W=None, device=0):
     """(m, v (D x q each), n_bad): the conditional mean and variance of every edge coefficient given each of D draws phi = (tau2, mu, S, W) for
     one n x q model matrix, on the device (bnr_marginal_gamma).  ValueError (before any library call) for shapes that do not fit or n > 2048"""
     Xf, yf, t2, mu_, Sf, Wf, n, q, D = _phi_arrays(X, y, tau2, mu, S, W)
     m, v = np.empty((D, q)), np.empty((D, q))
     nb = C.c_int32(0)
-    check(_device_medge().bnr_marginal_gamma(int(device), n, q, D, _ptr(Xf), _ptr(yf), _ptr(t2), _ptr(mu_), _ptr(Sf), _ptr(Wf), _ptr(m), _ptr(v),
+    check(_device_marginal("medge").bnr_marginal_gamma(int(device), n, q, D, _ptr(Xf), _ptr(yf), _ptr(t2), _ptr(mu_), _ptr(Sf), _ptr(Wf), _ptr(m), _ptr(v),
                                              C.byref(nb)))
     return m, v, nb.value
 
@@ -1260,7 +1188,7 @@ def mixture_summary_raw(m, v, nchains=1, weights=None, p_lo=0.025, p_hi=0.975, d
     p_lo, p_hi = loo_probs(p_lo, p_hi)
     D, q = mf.shape
     out = _medge_outputs(q, fields)
-    check(_device_medge().bnr_mixture_summary(int(device), q, K, D // K, _ptr(mf), _ptr(vf), _ptr(w), p_lo, p_hi, *[_ptr(o) for o in out]))
+    check(_device_marginal("medge").bnr_mixture_summary(int(device), q, K, D // K, _ptr(mf), _ptr(vf), _ptr(w), p_lo, p_hi, *[_ptr(o) for o in out]))
     return tuple(out)
 
 
@@ -1274,16 +1202,12 @@ def chains_marginal_edges(chains, first_row, nsamp, thin=1, weights=None, p_lo=0
     out = _medge_outputs(q, fields)
     m, v = (np.empty((K * nd, q)), np.empty((K * nd, q))) if per_draw else (None, None)
     nb = C.c_int32(0)
-    check(_device_medge().bnr_chains_marginal_edges(arr, K, _ptr(w), int(first_row), int(nsamp), thin, p_lo, p_hi, *[_ptr(o) for o in out], _ptr(m),
+    check(_device_marginal("medge").bnr_chains_marginal_edges(arr, K, _ptr(w), int(first_row), int(nsamp), thin, p_lo, p_hi, *[_ptr(o) for o in out], _ptr(m),
                                                     _ptr(v), C.byref(nb)))
     return tuple(out), m, v, nb.value
 
 
 # ------------------------------------------------------------------------------------------ Rao-Blackwellised covariance of the edge coefficients (libbnr_mcov.so, include/bnr_mcov.h)
-def mcov_set_option(name, value):
-    check(mcov_lib().bnr_mcov_set_option(name.encode(), int(value)))
-
-
 def _mcov_outputs(D, m, per_draw):
     return np.empty(m), np.empty((m, m)), np.empty((m, m)), (np.empty((D, m)) if per_draw else None), (np.empty((D, m)) if per_draw else None)
 
@@ -1300,7 +1224,7 @@ def marginal_gamma_cov_raw(X, y, tau2, mu, S, W=None, cols=None, nchains=1, weig
     c = q if ci is None else ci.size
     mean, cov, within, m, v = _mcov_outputs(D, c, per_draw)
     nb = C.c_int32(0)
-    check(_device_mcov().bnr_marginal_gamma_cov(int(device), n, q, K, D // K, _ptr(Xf), _ptr(yf), _ptr(t2), _ptr(mu_), _ptr(Sf), _ptr(Wf), _ptr(w), c,
+    check(_device_marginal("mcov").bnr_marginal_gamma_cov(int(device), n, q, K, D // K, _ptr(Xf), _ptr(yf), _ptr(t2), _ptr(mu_), _ptr(Sf), _ptr(Wf), _ptr(w), c,
                                                 None if ci is None else ci.ctypes.data_as(_ip), _ptr(mean), _ptr(cov), _ptr(within), _ptr(m),
                                                 _ptr(v), C.byref(nb)))
     return mean, cov, within, m, v, nb.value
@@ -1315,17 +1239,13 @@ def chains_marginal_edge_cov(chains, first_row, nsamp, thin=1, cols=None, weight
     c = c0.q if ci is None else ci.size
     mean, cov, within, m, v = _mcov_outputs(K * nd, c, per_draw)
     nb = C.c_int32(0)
-    check(_device_mcov().bnr_chains_marginal_edge_cov(arr, K, _ptr(w), int(first_row), int(nsamp), thin, c, None if ci is None else ci.ctypes.data_as(_ip),
+    check(_device_marginal("mcov").bnr_chains_marginal_edge_cov(arr, K, _ptr(w), int(first_row), int(nsamp), thin, c, None if ci is None else ci.ctypes.data_as(_ip),
                                                       _ptr(mean), _ptr(cov), _ptr(within), _ptr(m), _ptr(v), C.byref(nb)))
     return mean, cov, within, m, v, nb.value
 
 
 # ------------------------------------------------------------------------------------------ Rao-Blackwellised prediction of new rows (libbnr_mpred.so, include/bnr_mpred.h)
 MPRED_SUMMARY_FIELDS = ("mean", "sd", "var_within", "lower", "upper", "pred_sd", "pred_lower", "pred_upper", "lpd", "pit")
-
-
-def mpred_set_option(name, value):
-    check(mpred_lib().bnr_mpred_set_option(name.encode(), int(value)))
 
 
 def marginal_predict_raw(X, y, X_new, tau2, mu, S, W=None, device=0):
@@ -1339,7 +1259,7 @@ def marginal_predict_raw(X, y, X_new, tau2, mu, S, W=None, device=0):
     m = Xn.shape[0]
     mean, var = np.empty((D, m)), np.empty((D, m))
     nb = C.c_int32(0)
-    check(_device_mpred().bnr_marginal_predict(int(device), n, q, m, D, _ptr(Xf), _ptr(yf), _ptr(Xn), _ptr(t2), _ptr(mu_), _ptr(Sf), _ptr(Wf),
+    check(_device_marginal("mpred").bnr_marginal_predict(int(device), n, q, m, D, _ptr(Xf), _ptr(yf), _ptr(Xn), _ptr(t2), _ptr(mu_), _ptr(Sf), _ptr(Wf),
                                                _ptr(mean), _ptr(var), C.byref(nb)))
     return mean, var, nb.value
 
@@ -1360,7 +1280,7 @@ def mixture_score_raw(mean, vobs, y, nchains=1, weights=None, device=0, fields=(
         raise ValueError("fields must name lpd or pit, not %r" % (fields,))
     w = None if weights is None else stack_weights_array(weights, K)
     out = [np.empty(m) if f in fields else None for f in ("lpd", "pit")]
-    check(_device_mpred().bnr_mixture_score(int(device), m, K, D // K, _ptr(mf), _ptr(vf), _ptr(yf), _ptr(w), _ptr(out[0]), _ptr(out[1])))
+    check(_device_marginal("mpred").bnr_mixture_score(int(device), m, K, D // K, _ptr(mf), _ptr(vf), _ptr(yf), _ptr(w), _ptr(out[0]), _ptr(out[1])))
     return tuple(out)
 
 
@@ -1388,17 +1308,13 @@ def chains_marginal_predict(chains, first_row, nsamp, X_new, y_new=None, thin=1,
     out = [np.empty(m) if f in fields else None for f in MPRED_SUMMARY_FIELDS]
     dm, dv = (np.empty((K * nd, m)), np.empty((K * nd, m))) if per_draw else (None, None)
     nb = C.c_int32(0)
-    check(_device_mpred().bnr_chains_marginal_predict(arr, K, _ptr(w), int(first_row), int(nsamp), thin, _ptr(Xn), m, _ptr(yn), p_lo, p_hi,
+    check(_device_marginal("mpred").bnr_chains_marginal_predict(arr, K, _ptr(w), int(first_row), int(nsamp), thin, _ptr(Xn), m, _ptr(yn), p_lo, p_hi,
                                                       *[_ptr(o) for o in out], _ptr(dm), _ptr(dv), C.byref(nb)))
     return tuple(out), dm, dv, nb.value
 
 
 # ------------------------------------------------------------------------------------------ marginal LOO predictive checks (libbnr_mcheck.so, include/bnr_mcheck.h)
 MCHECK_FIELDS = ("mean", "sd", "pit", "lower", "upper")
-
-
-def mcheck_set_option(name, value):
-    check(mcheck_lib().bnr_mcheck_set_option(name.encode(), int(value)))
 
 
 def _mcheck_fields(fields, has_y):
@@ -1429,7 +1345,7 @@ def weighted_mixture_raw(mean, var, log_weights, y=None, p_lo=0.025, p_hi=0.975,
     if set(fields) & {"lower", "upper"}:
         p_lo, p_hi = loo_probs(p_lo, p_hi)
     out = [np.empty(rows) if f in fields else None for f in MCHECK_FIELDS]
-    check(_device_mcheck().bnr_weighted_mixture(int(device), rows, D, _ptr(mf), _ptr(vf), _ptr(lf), _ptr(yf), float(p_lo), float(p_hi),
+    check(_device_marginal("mcheck").bnr_weighted_mixture(int(device), rows, D, _ptr(mf), _ptr(vf), _ptr(lf), _ptr(yf), float(p_lo), float(p_hi),
                                                 *[_ptr(o) for o in out]))
     return tuple(out)
 
@@ -1450,16 +1366,12 @@ def chains_marginal_loo_predict(chains, first_row, nsamp, thin=1, r_eff=None, p_
     out = [np.empty(n) if f in fields else None for f in MCHECK_FIELDS]
     ll = np.empty((n, D)) if loglik else None
     nb = C.c_int32(0)
-    check(_device_mcheck().bnr_chains_marginal_loo_predict(arr, K, int(first_row), int(nsamp), thin, _ptr(r), float(p_lo), float(p_hi), _ptr(el),
+    check(_device_marginal("mcheck").bnr_chains_marginal_loo_predict(arr, K, int(first_row), int(nsamp), thin, _ptr(r), float(p_lo), float(p_hi), _ptr(el),
                                                            _ptr(kh), *[_ptr(o) for o in out], _ptr(ml), _ptr(ll), C.byref(nb)))
     return el, kh, tuple(out), ml, ll, nb.value
 
 
 # ------------------------------------------------------------------------------------------ chain stacking on the marginal PSIS-LOO (libbnr_mstack.so, include/bnr_mstack.h)
-def mstack_set_option(name, value):
-    check(mstack_lib().bnr_mstack_set_option(name.encode(), int(value)))
-
-
 def stacked_mixture_raw(mean, var, log_weights, weights, nchains, y=None, p_lo=0.025, p_hi=0.975, device=0, fields=None):
     """the tuple MCHECK_FIELDS (rows values each) of the stacked mixtures of normals in the rows of the rows x (nchains nd) matrices mean, var
     (chain k's components in columns k nd .. (k + 1) nd - 1) under the chain weights `weights` and the log weights log_weights, normalised within
@@ -1486,7 +1398,7 @@ def stacked_mixture_raw(mean, var, log_weights, weights, nchains, y=None, p_lo=0
     if set(fields) & {"lower", "upper"}:
         p_lo, p_hi = loo_probs(p_lo, p_hi)
     out = [np.empty(rows) if f in fields else None for f in MCHECK_FIELDS]
-    check(_device_mstack().bnr_stacked_mixture(int(device), rows, K, D // K, _ptr(mf), _ptr(vf), _ptr(lf), _ptr(w), _ptr(yf), float(p_lo),
+    check(_device_marginal("mstack").bnr_stacked_mixture(int(device), rows, K, D // K, _ptr(mf), _ptr(vf), _ptr(lf), _ptr(w), _ptr(yf), float(p_lo),
                                                float(p_hi), *[_ptr(o) for o in out]))
     return tuple(out)
 
@@ -1509,7 +1421,7 @@ def chains_marginal_stack(chains, first_row, nsamp, thin=1, r_eff=None, weights=
     w, el, kh, es, ml = np.empty(K), np.empty((K, n)), np.empty((K, n)), np.empty(n), np.empty(D)
     out = [np.empty(n) if f in fields else None for f in MCHECK_FIELDS]
     g, it, nb = C.c_double(0.0), C.c_int32(0), C.c_int32(0)
-    check(_device_mstack().bnr_chains_marginal_stack(arr, K, int(first_row), int(nsamp), thin, _ptr(r), _ptr(fw), int(max_iter), float(gap_tol),
+    check(_device_marginal("mstack").bnr_chains_marginal_stack(arr, K, int(first_row), int(nsamp), thin, _ptr(r), _ptr(fw), int(max_iter), float(gap_tol),
                                                      float(p_lo), float(p_hi), _ptr(w), _ptr(el), _ptr(kh), _ptr(es), C.byref(g), C.byref(it),
                                                      *[_ptr(o) for o in out], _ptr(ml), C.byref(nb)))
     return w, el, kh, es, g.value, it.value, tuple(out), ml, nb.value

@@ -44,6 +44,7 @@ the per-chain split-Rhat statistics are all-gathered (RCCL on GPUs, gloo on CPU 
 """
 import dataclasses
 import datetime
+import inspect
 import math
 import random
 import sys
@@ -1890,11 +1891,16 @@ def MarginalLOO(results, X=None, y=None, x_transform=True):
     return _host_marginal_loo([results.state], _dense_rows(xi), y, results.burn_in, results.sampled)
 
 
+def _positive_int(option, value):
+    """int(value); ValueError, naming the option, unless it is an integer >= 1"""
+    if isinstance(value, bool) or int(value) != value or int(value) < 1:
+        raise ValueError("%s must be an integer >= 1, not %r" % (option, value))
+    return int(value)
+
+
 def _marginal_loo_thin(nsamp, draws):
     """thin = ceil(nsamp / marginal_loo_draws); ValueError unless marginal_loo_draws is an integer >= 1"""
-    if isinstance(draws, bool) or int(draws) != draws or int(draws) < 1:
-        raise ValueError("marginal_loo_draws must be an integer >= 1, not %r" % (draws,))
-    return max(1, -(-int(nsamp) // int(draws)))
+    return max(1, -(-int(nsamp) // _positive_int("marginal_loo_draws", draws)))
 
 
 # ------------------------------------------------------------------------------------------ marginal LOO predictive checks (an addition to the reference)
@@ -2997,6 +3003,18 @@ def _one_rank(option):
         raise ValueError("%s needs every chain of the fit on one rank: the chains are spread over %d torch.distributed ranks" % (option, _rank_world()[1]))
 
 
+def _marginal_request(option, draws_option, draws, X_new, *interval):
+    """The four checks that the marginal options of a fit share, in this order -> the draws per chain: every chain on one rank, the draws per
+    chain (draws_option names them in the refusal), the interval where the option takes one, at most MLOO_MAX_N training rows"""
+    _one_rank(option)
+    draws = _positive_int(draws_option, draws)
+    for level in interval:
+        _loo_interval_probs(level)
+    if X_new is not None and X_new.n > MLOO_MAX_N:
+        raise ValueError("%s takes at most %d training rows in this version, not %d" % (option, MLOO_MAX_N, X_new.n))
+    return draws
+
+
 def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, return_state=True, summary_interval=None, ess_max_lag=None, predict_X=None,
                   predict_y=None, predict_interval=95, waic=False, loo=False, loo_r_eff=None, pool_chains=False, predict_observation=False,
                   pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False, hdi_prob=0.95, fdr=0.05, node_sets=False,
@@ -3041,66 +3059,62 @@ def _fit_requests(y, num_chains, X_new=None, nsamp=None, x_transform=True, retur
     ec = _edge_cov_cols(edge_cov, None if X_new is None else X_new.V)
     if ec is not None:
         _one_rank("edge_cov")
-    ml = None
+    ml = me = mec = mp_ = mlp = mst = None
     if marginal_loo:
-        _one_rank("marginal_loo")
-        _marginal_loo_thin(1, marginal_loo_draws)
-        ml = int(marginal_loo_draws)
-        if X_new is not None and X_new.n > MLOO_MAX_N:
-            raise ValueError("marginal_loo takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
-    me = None
+        ml = _marginal_request("marginal_loo", "marginal_loo_draws", marginal_loo_draws, X_new)
     if marginal_edges:
-        _one_rank("marginal_edges")
-        if isinstance(marginal_edges_draws, bool) or int(marginal_edges_draws) != marginal_edges_draws or int(marginal_edges_draws) < 1:
-            raise ValueError("marginal_edges_draws must be an integer >= 1, not %r" % (marginal_edges_draws,))
-        _loo_interval_probs(predict_interval)
-        me = (int(marginal_edges_draws), predict_interval)
-        if X_new is not None and X_new.n > MLOO_MAX_N:
-            raise ValueError("marginal_edges takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
-    mec = None
+        me = (_marginal_request("marginal_edges", "marginal_edges_draws", marginal_edges_draws, X_new, predict_interval), predict_interval)
     mc = _edge_cov_cols(marginal_edge_cov, None if X_new is None else X_new.V)
     if mc is not None:
-        _one_rank("marginal_edge_cov")
-        if isinstance(marginal_edges_draws, bool) or int(marginal_edges_draws) != marginal_edges_draws or int(marginal_edges_draws) < 1:
-            raise ValueError("marginal_edges_draws must be an integer >= 1, not %r" % (marginal_edges_draws,))
-        mec = (int(marginal_edges_draws), mc)
-        if X_new is not None and X_new.n > MLOO_MAX_N:
-            raise ValueError("marginal_edge_cov takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
-    mp_ = None
+        mec = (_marginal_request("marginal_edge_cov", "marginal_edges_draws", marginal_edges_draws, X_new), mc)
     if marginal_predict:
         if predict_X is None:
             raise ValueError("marginal_predict needs predict_X")
-        _one_rank("marginal_predict")
-        if isinstance(marginal_predict_draws, bool) or int(marginal_predict_draws) != marginal_predict_draws or int(marginal_predict_draws) < 1:
-            raise ValueError("marginal_predict_draws must be an integer >= 1, not %r" % (marginal_predict_draws,))
-        _loo_interval_probs(predict_interval)
-        mp_ = int(marginal_predict_draws)
-        if X_new is not None and X_new.n > MLOO_MAX_N:
-            raise ValueError("marginal_predict takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
-    mlp = None
+        mp_ = _marginal_request("marginal_predict", "marginal_predict_draws", marginal_predict_draws, X_new, predict_interval)
     if marginal_loo_predict:
-        _one_rank("marginal_loo_predict")
-        _marginal_loo_thin(1, marginal_loo_draws)
-        _loo_interval_probs(predict_interval)
-        mlp = (int(marginal_loo_draws), predict_interval)
-        if X_new is not None and X_new.n > MLOO_MAX_N:
-            raise ValueError("marginal_loo_predict takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
-    mst = None
+        mlp = (_marginal_request("marginal_loo_predict", "marginal_loo_draws", marginal_loo_draws, X_new, predict_interval), predict_interval)
     if marginal_stack:
         if int(num_chains) < 2:
             raise ValueError("marginal_stack needs num_chains >= 2: one chain has nothing to be weighted against")
         if int(num_chains) > STACK_MAX_CHAINS:
             raise ValueError("marginal_stack takes at most %d chains" % STACK_MAX_CHAINS)
-        _one_rank("marginal_stack")
-        _marginal_loo_thin(1, marginal_loo_draws)
-        _loo_interval_probs(predict_interval)
-        mst = (int(marginal_loo_draws), predict_interval)
-        if X_new is not None and X_new.n > MLOO_MAX_N:
-            raise ValueError("marginal_stack takes at most %d training rows in this version, not %d" % (MLOO_MAX_N, X_new.n))
+        mst = (_marginal_request("marginal_stack", "marginal_loo_draws", marginal_loo_draws, X_new, predict_interval), predict_interval)
     if X_new is not None:
         _capi.r_eff_array(loo_r_eff, X_new.n)
     return _Requests(return_state, summary_interval, ess_max_lag, pred, bool(waic), bool(loo), loo_r_eff, bool(pool_chains), bool(predict_observation),
                      pred_seed, lp, bool(rank_diagnostics), es, ntop, bool(stack_chains), ec, ml, me, mp_, mlp, mst, marginal_edge_cov=mec)
+
+
+def _weighted_trace_requests(rec, every, nb, ns, req, pred_seed):
+    """the summary and the prediction of a fit's requests under the chain weights of the record `rec` (Results.stacking or
+    Results.marginal_stacking), each set only when it was asked for"""
+    if req.summary_interval is not None:
+        rec.summary = device_summary_stacked(every, rec.weights, nb, ns, req.summary_interval)
+    if req.predict is not None:
+        rec.prediction = device_predict_stacked(every, rec.weights, nb, ns, *req.predict, pred_seed, predict_observation=req.predict_observation)
+
+
+def _weighted_edge_requests(rec, every, nb, ns, req):
+    """edge_cov, marginal_edges and marginal_predict of a fit's requests under the chain weights of the record `rec`, each set only when it was
+    asked for"""
+    if req.edge_cov is not None:
+        rec.edge_cov = device_edge_cov(every, nb, ns, None if isinstance(req.edge_cov, str) else req.edge_cov, rec.weights)
+    if req.marginal_edges is not None:
+        rec.marginal_edges = device_marginal_edges(every, nb, ns, _marginal_loo_thin(ns, req.marginal_edges[0]), rec.weights, req.marginal_edges[1])
+    if req.marginal_predict is not None:
+        rec.marginal_prediction = device_marginal_predict(every, nb, ns, req.predict[0], req.predict[1], _marginal_loo_thin(ns, req.marginal_predict),
+                                                          rec.weights, req.predict[2])
+
+
+# The analysis options of a fit: _fit_requests' parameters after x_transform.  Fit, generate_samples and generate_samples_dbl repeat them in
+# their signatures (the documentation; tests/test_finish_host.py holds the four lists equal) and hand them on as one dict.
+_ANALYSIS_OPTIONS = tuple(inspect.signature(_fit_requests).parameters)
+_ANALYSIS_OPTIONS = _ANALYSIS_OPTIONS[_ANALYSIS_OPTIONS.index("x_transform") + 1:]
+
+
+def _analysis_options(local):
+    """the analysis options of a fit out of the locals() of a function that takes them as keywords, for _fit_requests(..., **options)"""
+    return {name: local[name] for name in _ANALYSIS_OPTIONS}
 
 
 def _finish(chainset, res, req, seed):
@@ -3127,37 +3141,16 @@ def _finish(chainset, res, req, seed):
     every = [chainset.chains[c] for c in chainset.ids]
     pred_seed = seed if req.pred_seed is None else req.pred_seed
     if req.stack:
-        st = device_stack_chains(every, nb, ns, req.loo_r_eff)
-        if req.summary_interval is not None:
-            st.summary = device_summary_stacked(every, st.weights, nb, ns, req.summary_interval)
-        if req.predict is not None:
-            st.prediction = device_predict_stacked(every, st.weights, nb, ns, *req.predict, pred_seed, predict_observation=req.predict_observation)
-        res.stacking = st
+        res.stacking = device_stack_chains(every, nb, ns, req.loo_r_eff)
+        _weighted_trace_requests(res.stacking, every, nb, ns, req, pred_seed)
     if req.edge_cov is not None:
-        cols = None if isinstance(req.edge_cov, str) else req.edge_cov
-        res.edge_cov = device_edge_cov(every, nb, ns, cols)
-        if req.stack:
-            res.stacking.edge_cov = device_edge_cov(every, nb, ns, cols, res.stacking.weights)
-    if req.marginal_edges is not None and req.stack:
-        res.stacking.marginal_edges = device_marginal_edges(every, nb, ns, _marginal_loo_thin(ns, req.marginal_edges[0]), res.stacking.weights,
-                                                            req.marginal_edges[1])
-    if req.marginal_predict is not None and req.stack:                  # (set only when asked for)
-        res.stacking.marginal_prediction = device_marginal_predict(every, nb, ns, req.predict[0], req.predict[1], _marginal_loo_thin(ns, req.marginal_predict),
-                                                                   res.stacking.weights, req.predict[2])
+        res.edge_cov = device_edge_cov(every, nb, ns, None if isinstance(req.edge_cov, str) else req.edge_cov)
+    if req.stack:
+        _weighted_edge_requests(res.stacking, every, nb, ns, req)
     if req.marginal_stack is not None:
-        ms = device_marginal_stack(every, nb, ns, _marginal_loo_thin(ns, req.marginal_stack[0]), req.marginal_stack[1], req.loo_r_eff)
-        if req.summary_interval is not None:
-            ms.summary = device_summary_stacked(every, ms.weights, nb, ns, req.summary_interval)
-        if req.predict is not None:
-            ms.prediction = device_predict_stacked(every, ms.weights, nb, ns, *req.predict, pred_seed, predict_observation=req.predict_observation)
-        if req.edge_cov is not None:
-            ms.edge_cov = device_edge_cov(every, nb, ns, None if isinstance(req.edge_cov, str) else req.edge_cov, ms.weights)
-        if req.marginal_edges is not None:
-            ms.marginal_edges = device_marginal_edges(every, nb, ns, _marginal_loo_thin(ns, req.marginal_edges[0]), ms.weights, req.marginal_edges[1])
-        if req.marginal_predict is not None:
-            ms.marginal_prediction = device_marginal_predict(every, nb, ns, req.predict[0], req.predict[1], _marginal_loo_thin(ns, req.marginal_predict),
-                                                             ms.weights, req.predict[2])
-        res.marginal_stacking = ms
+        res.marginal_stacking = device_marginal_stack(every, nb, ns, _marginal_loo_thin(ns, req.marginal_stack[0]), req.marginal_stack[1], req.loo_r_eff)
+        _weighted_trace_requests(res.marginal_stacking, every, nb, ns, req, pred_seed)
+        _weighted_edge_requests(res.marginal_stacking, every, nb, ns, req)
     if req.node_sets is not None:
         res.node_sets = device_node_sets(every, nb, ns, req.node_sets)
     if req.edge_sel is not None:
@@ -3242,24 +3235,17 @@ def generate_samples(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1
                      pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
                      hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
                      marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000,
-        marginal_predict=False, marginal_predict_draws=2000, marginal_edge_cov=False, marginal_stack=False, marginal_loo_predict=False):
+                     marginal_predict=False, marginal_predict_draws=2000, marginal_edge_cov=False, marginal_stack=False, marginal_loo_predict=False):
     """generate_samples! (gibbs.jl:897-1020): "traditional" scheme with PSRF-driven top-up rounds.
     xi_weights="reference" samples xi with the reference's own weight arithmetic (include/bnr_hip.h, option "xi_weights")."""
+    opts = _analysis_options(locals())
     xi_weights_code(xi_weights)
     if nu < R:
         pass                                       # the reference constructs an ArgumentError without throwing it (901-902)
     elif nu == R:
         print("Warning: ν==R may give poor accuracy. Consider increasing ν")
     X_new = XInput(X, x_transform)                 # X_new of gibbs.jl:907-918: element type kept, setup_X! runs on the device
-    req = _fit_requests(y, num_chains, X_new, nsamp, x_transform, return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
-                        predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic, loo=loo, loo_r_eff=loo_r_eff,
-                        pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed, loo_predict=loo_predict,
-                        rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets,
-                        top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
-                        marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
-                        marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws, marginal_edge_cov=marginal_edge_cov, marginal_loo_predict=marginal_loo_predict,
-                        marginal_stack=marginal_stack)       # (checked before any sampling)
+    req = _fit_requests(y, num_chains, X_new, nsamp, x_transform, **opts)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -3314,23 +3300,16 @@ def generate_samples_dbl(X, y, R, eta=1.01, zeta=1.0, iota=1.0, aDelta=1.0, bDel
                          pool_chains=False, predict_observation=False, pred_seed=None, loo_predict=False, rank_diagnostics=False, edge_selection=False,
                          hdi_prob=0.95, fdr=0.05, node_sets=False, top_sets=10, stack_chains=False, edge_cov=False, marginal_loo=False,
                          marginal_loo_draws=2000, marginal_edges=False, marginal_edges_draws=2000,
-        marginal_predict=False, marginal_predict_draws=2000, marginal_edge_cov=False, marginal_stack=False, marginal_loo_predict=False):
+                         marginal_predict=False, marginal_predict_draws=2000, marginal_edge_cov=False, marginal_stack=False, marginal_loo_predict=False):
     """generate_samples_dbl! (gibbs.jl:1051-1198): "doubling generation" scheme.  xi_weights as for generate_samples."""
+    opts = _analysis_options(locals())
     xi_weights_code(xi_weights)
     if nu == R:
         print("Warning: ν==R may give poor accuracy. Consider increasing ν")
     nburn = _julia_round(mingen / 2)
     nsamp = mingen - nburn
     X_new = XInput(X, x_transform)
-    req = _fit_requests(y, num_chains, X_new, nsamp, x_transform, return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
-                        predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic, loo=loo, loo_r_eff=loo_r_eff,
-                        pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed, loo_predict=loo_predict,
-                        rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets,
-                        top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
-                        marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
-                        marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws, marginal_edge_cov=marginal_edge_cov, marginal_loo_predict=marginal_loo_predict,
-                        marginal_stack=marginal_stack)       # (checked before any sampling)
+    req = _fit_requests(y, num_chains, X_new, nsamp, x_transform, **opts)       # (checked before any sampling)
     y = np.asarray(y, dtype=np.float64)
     total = nburn + nsamp
     prog_freq = 1000
@@ -3452,14 +3431,9 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     record also holds those under its weights.  It needs 2 to 32 chains on one rank and at most 2048 training rows; stack_chains=True beside
     it fills Results.stacking as before, independently.  Every other field of the Results is what it is without it.
     parameters.log keeps the reference's lines only."""
+    opts = _analysis_options(locals())
     xi_weights_code(xi_weights)
-    _fit_requests(y, num_chains, predict_X=predict_X, predict_interval=predict_interval, pool_chains=pool_chains,
-                  predict_observation=predict_observation, loo_predict=loo_predict, rank_diagnostics=rank_diagnostics,
-                  edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr, node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains,
-                  edge_cov=edge_cov, marginal_loo=marginal_loo, marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
-                        marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws, marginal_edge_cov=marginal_edge_cov, marginal_loo_predict=marginal_loo_predict,
-                        marginal_stack=marginal_stack)
+    _fit_requests(y, num_chains, **opts)
     seed = shared_seed(seed, lambda: random.randrange(1, 55556))          # sample(1:55555) :739; drawn on rank 0, the same on every rank
     if _rank_world()[0] == 0 and filename:
         with open(filename, "w") as f:
@@ -3474,26 +3448,8 @@ def Fit(X, y, R, eta=1.01, V=30, zeta=1.0, iota=1.0, aDelta=1.0, bDelta=1.0, nu=
     if mingen > 0 and maxgen > 0:
         return generate_samples_dbl(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, mingen=mingen,
                                     maxgen=maxgen, psrf_cutoff=psrf_cutoff, x_transform=x_transform, suppress_timer=suppress_timer,
-                                    num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
-                                    return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
-                                    xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval,
-                                    waic=waic, loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation,
-                                    pred_seed=pred_seed, loo_predict=loo_predict, rank_diagnostics=rank_diagnostics,
-                                    edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr,
-                                    node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov,
-                                    marginal_loo=marginal_loo, marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
-                        marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws, marginal_edge_cov=marginal_edge_cov, marginal_loo_predict=marginal_loo_predict,
-                        marginal_stack=marginal_stack)
+                                    num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device, xi_weights=xi_weights, **opts)
     return generate_samples(X, y, R, eta=eta, zeta=zeta, iota=iota, aDelta=aDelta, bDelta=bDelta, nu=nu, nburn=nburn, nsamp=nsamples,
                             maxburn=nburn + nsamples, psrf_cutoff=psrf_cutoff, x_transform=x_transform,
                             suppress_timer=suppress_timer, num_chains=num_chains, seed=seed, purge_burn=purge_burn, device=device,
-                            return_state=return_state, summary_interval=summary_interval, ess_max_lag=ess_max_lag,
-                            xi_weights=xi_weights, predict_X=predict_X, predict_y=predict_y, predict_interval=predict_interval, waic=waic,
-                            loo=loo, loo_r_eff=loo_r_eff, pool_chains=pool_chains, predict_observation=predict_observation, pred_seed=pred_seed,
-                            loo_predict=loo_predict, rank_diagnostics=rank_diagnostics, edge_selection=edge_selection, hdi_prob=hdi_prob, fdr=fdr,
-                            node_sets=node_sets, top_sets=top_sets, stack_chains=stack_chains, edge_cov=edge_cov, marginal_loo=marginal_loo,
-                            marginal_loo_draws=marginal_loo_draws, marginal_edges=marginal_edges,
-                        marginal_edges_draws=marginal_edges_draws, marginal_predict=marginal_predict,
-                        marginal_predict_draws=marginal_predict_draws, marginal_edge_cov=marginal_edge_cov, marginal_loo_predict=marginal_loo_predict,
-                        marginal_stack=marginal_stack)
+                            xi_weights=xi_weights, **opts)

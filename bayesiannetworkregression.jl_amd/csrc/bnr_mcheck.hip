@@ -1,29 +1,16 @@
 // bnr_mcheck.hip -- libbnr_mcheck.so behind include/bnr_mcheck.h: the leave-one-out predictive checks of the training rows under the marginal
 // PSIS weights, on the device.  A library and a gfx950 code object of its own: the four kernels of bnr_mloo_kernels.h (by #include, through
-// bnr_mloo_job.h, the driver shared with libbnr_mloo.so, libbnr_medge.so and libbnr_mpred.so: open_chain_job, run_job without a hook, and mloo_out,
-// which leaves loglik, resid and var on the device) plus the three of bnr_mcheck_kernels.h.  It reaches a chain through bnr_chain_device_view, runs
-// PSIS through bnr_psis_weights and leaves its messages with bnr_set_last_error -- exported calls of libbnr_hip.so, nothing of bnr_internal.h.
-// Linked with bnr_mcheck.map: only the functions of the header are exported.
+// bnr_mloo_job.h, the driver shared with the other marginal libraries: open_chain_job, run_job without a hook, and mloo_out, which leaves
+// loglik, resid and var on the device) plus the three of bnr_mcheck_kernels.h; the outputs' checks and the launch loop of the two row kernels
+// are bnr_mcheck_rows.h, shared with libbnr_mstack.so.  It reaches a chain through bnr_chain_device_view, runs PSIS through bnr_psis_weights and
+// leaves its messages with bnr_set_last_error -- exported calls of libbnr_hip.so, nothing of bnr_internal.h.  Linked with bnr_mcheck.map: only
+// the functions of the header are exported.
 #include "../../include/bnr_mcheck.h"
 #include "bnr_mcheck_kernels.h"
 #include "bnr_mloo_job.h"
+#include "bnr_mcheck_rows.h"
 
 namespace {
-struct mix_out { double *mean, *sd, *pit, *lower, *upper; };
-
-// the checks of a mixture's arguments that need no shapes; c: the bracket's half-width in sds (summary_check's loop)
-const char *mix_check(const mix_out &o, bool has_y, double p_lo, double p_hi, double &c)
-{
-    c = 1.0;
-    if (o.pit && !has_y) return "pit needs y";
-    if (o.lower || o.upper) {
-        if (!(p_lo > 0.0 && p_lo < p_hi && p_hi < 1.0)) return "need 0 < p_lo < p_hi < 1";
-        const double pm = 0.5 * std::min(p_lo, 1.0 - p_hi);
-        for (c = 1.0; !(0.5 * std::erfc(c * 0.70710678118654752440) < pm) && c < 40.0; c += 0.5) { }
-    }
-    return nullptr;
-}
-
 // The three kernels on the device matrices A, V, LW (rows x D, a row's draws contiguous) and yd (rows, NULL: none), and the outputs asked for
 // to the host.  a_is_resid: A holds resid = y - m (the chain form; it needs yd), else m itself.
 int mix_run(call_guard &g, int rows, int D, const double *A, bool a_is_resid, const double *V, const double *LW, const double *yd, double c,
@@ -31,49 +18,20 @@ int mix_run(call_guard &g, int rows, int D, const double *A, bool a_is_resid, co
 {
     int rc;
     const size_t total = (size_t)rows * (size_t)D;
-    double *Wt = nullptr, *Isd = nullptr, *Mo = nullptr, *out = nullptr, *brk = nullptr;
-    int *flag = nullptr;
+    double *Wt = nullptr, *Isd = nullptr, *Mo = nullptr;
     if ((rc = g.alloc(&Wt, total))) return rc;
     if ((rc = g.alloc(&Isd, total))) return rc;
     if (a_is_resid && (rc = g.alloc(&Mo, total))) return rc;
-    if ((rc = g.alloc(&out, (size_t)5 * rows))) return rc;
-    if ((rc = g.alloc(&flag, (size_t)rows))) return rc;
-    const bool bounds = o.lower || o.upper;
-    if (bounds && (rc = g.alloc(&brk, (size_t)2 * rows))) return rc;
-    double *host[5] = {o.mean, o.sd, o.pit, o.lower, o.upper}, *dev[5];
-    for (int f = 0; f < 5; ++f) dev[f] = host[f] ? out + (size_t)f * rows : nullptr;
     const unsigned sblocks = (unsigned)std::min<size_t>((total + 255) / 256, (size_t)1 << 16);
-    hipLaunchKernelGGL(k_mcheck_stage, dim3(sblocks), dim3(256), 0, g.st, LW, V, A, yd, (long long)total, D, Wt, Isd, Mo);
-    const double *M = a_is_resid ? Mo : A;
-    for (int i0 = 0; i0 < rows; i0 += MCHECK_ROWS_PER_LAUNCH) {
-        const int nr = std::min(MCHECK_ROWS_PER_LAUNCH, rows - i0);
-        hipLaunchKernelGGL(k_mcheck_moments, dim3(nr), dim3(256), 0, g.st, M, V, (const double *)Wt, (const double *)Isd, yd, D, i0, c, dev[0], dev[1],
-                           dev[2], brk, flag);
-        if (bounds)
-            hipLaunchKernelGGL(k_mcheck_quantile, dim3(nr, 2), dim3(256), 0, g.st, M, (const double *)Wt, (const double *)Isd, D, i0,
-                               (const double *)brk, (const int *)flag, p_lo, p_hi, dev[3], dev[4]);
-    }
-    HIPCHK(hipGetLastError());
-    for (int f = 0; f < 5; ++f)
-        if (host[f]) HIPCHK(hipMemcpyAsync(host[f], dev[f], sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost, g.st));
-    HIPCHK(hipStreamSynchronize(g.st));
-    HIPCHK(hipGetLastError());
-    return BNR_OK;
+    return mix_rows(g, rows, D, a_is_resid ? Mo : A, V, Wt, Isd, yd, c, p_lo, p_hi, o, [&] {
+        hipLaunchKernelGGL(k_mcheck_stage, dim3(sblocks), dim3(256), 0, g.st, LW, V, A, yd, (long long)total, D, Wt, Isd, Mo);
+    });
 }
 }   // namespace
 
 int bnr_mcheck_abi_version(void) { return BNR_MCHECK_ABI_VERSION; }
 
-int bnr_mcheck_set_option(const char *name, int64_t value)
-{
-    if (!name) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (std::string(name) == "mcheck_batch_draws") {
-        if (value < 0) return fail(BNR_ERR_BAD_ARG, "mcheck_batch_draws must be >= 0");
-        opt_batch_draws.store(value);
-        return BNR_OK;
-    }
-    return fail(BNR_ERR_BAD_ARG, std::string("unknown option ") + name);
-}
+int bnr_mcheck_set_option(const char *name, int64_t value) { return set_batch_draws("mcheck", name, value); }
 
 int bnr_weighted_mixture(int32_t device, int32_t rows, int32_t ndraws, const double *mean, const double *var, const double *logw, const double *y,
                          double p_lo, double p_hi, double *out_mean, double *out_sd, double *out_pit, double *out_lower, double *out_upper)

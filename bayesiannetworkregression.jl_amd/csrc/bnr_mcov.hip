@@ -103,16 +103,7 @@ int cov_job(call_guard &g, mloo_job &job, int K, int nd, const std::vector<doubl
 
 int bnr_mcov_abi_version(void) { return BNR_MCOV_ABI_VERSION; }
 
-int bnr_mcov_set_option(const char *name, int64_t value)
-{
-    if (!name) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (std::string(name) == "mcov_batch_draws") {
-        if (value < 0) return fail(BNR_ERR_BAD_ARG, "mcov_batch_draws must be >= 0");
-        opt_batch_draws.store(value);
-        return BNR_OK;
-    }
-    return fail(BNR_ERR_BAD_ARG, std::string("unknown option ") + name);
-}
+int bnr_mcov_set_option(const char *name, int64_t value) { return set_batch_draws("mcov", name, value); }
 
 int bnr_marginal_gamma_cov(int32_t device, int32_t n, int32_t q, int32_t K, int32_t nd, const double *X, const double *y, const double *tau2,
                            const double *mu, const double *S, const double *W, const double *weights, int32_t ncols, const int32_t *cols,

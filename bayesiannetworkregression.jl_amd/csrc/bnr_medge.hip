@@ -1,8 +1,9 @@
 // bnr_medge.hip -- libbnr_medge.so behind include/bnr_medge.h: Rao-Blackwellised summaries of the edge coefficients, gamma integrated out on the
 // device.  A library and a gfx950 code object of its own: the four kernels of bnr_mloo_kernels.h (by #include, through the driver shared with
-// libbnr_mloo.so and libbnr_mpred.so, bnr_mloo_job.h: it opens the job of either form and runs its batches) plus k_medge_proj and k_medge_summary
-// (bnr_medge_kernels.h); the summary's host driver and the transposing copies are bnr_medge_summary.h, shared with libbnr_mpred.so.  It reaches a chain through bnr_chain_device_view and leaves its messages with bnr_set_last_error -- exported calls
-// of libbnr_hip.so, nothing of bnr_internal.h.
+// the other marginal libraries, bnr_mloo_job.h: it opens the job of either form and runs its batches) plus k_medge_proj and k_medge_summary
+// (bnr_medge_kernels.h); the summary's host driver and the transposing copies are bnr_medge_summary.h, shared with libbnr_mpred.so and
+// libbnr_mcov.so.  It reaches a chain through bnr_chain_device_view and leaves its messages with bnr_set_last_error -- exported calls of
+// libbnr_hip.so, nothing of bnr_internal.h.
 // Linked with bnr_medge.map: only the functions of the header are exported, so that neither this library nor libbnr_mloo.so, loaded into one
 // process, can bind the other's kernel handles or host stubs.
 #include "../../include/bnr_medge.h"
@@ -29,16 +30,7 @@ int gamma_job(call_guard &g, mloo_job &job, double *Md, double *Vd, mloo_out &ou
 
 int bnr_medge_abi_version(void) { return BNR_MEDGE_ABI_VERSION; }
 
-int bnr_medge_set_option(const char *name, int64_t value)
-{
-    if (!name) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (std::string(name) == "medge_batch_draws") {
-        if (value < 0) return fail(BNR_ERR_BAD_ARG, "medge_batch_draws must be >= 0");
-        opt_batch_draws.store(value);
-        return BNR_OK;
-    }
-    return fail(BNR_ERR_BAD_ARG, std::string("unknown option ") + name);
-}
+int bnr_medge_set_option(const char *name, int64_t value) { return set_batch_draws("medge", name, value); }
 
 int bnr_marginal_gamma(int32_t device, int32_t n, int32_t q, int32_t ndraws, const double *X, const double *y, const double *tau2, const double *mu,
                        const double *S, const double *W, double *m, double *v, int32_t *n_bad)

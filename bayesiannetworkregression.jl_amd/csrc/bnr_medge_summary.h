@@ -1,7 +1,8 @@
-// bnr_medge_summary.h -- the host driver of k_medge_summary that libbnr_medge.so (bnr_medge.hip) and libbnr_mpred.so (bnr_mpred.hip) share: the
-// checks of a summary's arguments, the chain weights, the launch and the way an item-major device matrix reaches the host (fetch_transposed) and
-// a draw-major host matrix the device (upload_transposed).  Internal: included by those two translation units after bnr_medge_kernels.h and bnr_mloo_job.h, each into its own library and code object; every name here has
-// internal linkage (the way bnr_mloo_job.h was split off bnr_mloo.hip).
+// bnr_medge_summary.h -- the host driver of k_medge_summary that libbnr_medge.so (bnr_medge.hip), libbnr_mpred.so (bnr_mpred.hip) and
+// libbnr_mcov.so (bnr_mcov.hip) share: the checks of a summary's arguments, the chain weights, the launch and the way an item-major device
+// matrix reaches the host (fetch_transposed) and a draw-major host matrix the device (upload_transposed).  Internal: included by those
+// translation units after bnr_medge_kernels.h and bnr_mloo_job.h, each into its own library and code object; every name here has internal
+// linkage (the way bnr_mloo_job.h was split off bnr_mloo.hip).
 #pragma once
 #include "bnr_medge_kernels.h"
 #include "bnr_mloo_job.h"
@@ -40,28 +41,19 @@ int summary_check(const summary_out &o, double p_lo, double p_hi, double &c)
     c = 1.0;
     if (o.lower) {
         if (!(p_lo > 0.0 && p_lo < p_hi && p_hi < 1.0)) return fail(BNR_ERR_BAD_ARG, "need 0 < p_lo < p_hi < 1");
-        const double pm = 0.5 * std::min(p_lo, 1.0 - p_hi);
-        for (c = 1.0; !(0.5 * std::erfc(c * 0.70710678118654752440) < pm) && c < 40.0; c += 0.5) { }
+        c = bracket_halfwidth(p_lo, p_hi);
     }
     return BNR_OK;
 }
 
-// the chain weights of a summary: as given after bnr_chains_wsummary's checks, or 1 / K each
+// the chain weights of a summary: as given after weight_check, or 1 / K each
 int summary_weights(const double *weights, int K, std::vector<double> &w)
 {
     w.assign((size_t)K, 1.0 / (double)K);
     if (!weights) return BNR_OK;
     if (K > 32) return fail(BNR_ERR_BAD_ARG, "need 1 <= nchains <= 32 for a weighted call");
-    double s = 0.0;
-    bool any = false;
-    for (int k = 0; k < K; ++k) {
-        if (!std::isfinite(weights[k]) || weights[k] < 0.0) return fail(BNR_ERR_BAD_ARG, "weights must be finite and >= 0");
-        any = any || weights[k] > 0.0;
-        s += weights[k];
-        w[k] = weights[k];
-    }
-    if (!any) return fail(BNR_ERR_BAD_ARG, "at least one weight must be > 0");
-    if (!(std::fabs(s - 1.0) <= 1e-9)) return fail(BNR_ERR_BAD_ARG, "weights must sum to 1 (within 1e-9)");
+    if (const char *msg = weight_check(weights, K)) return fail(BNR_ERR_BAD_ARG, msg);
+    w.assign(weights, weights + K);
     return BNR_OK;
 }
 

@@ -2,22 +2,13 @@
 // kernels of bnr_mloo_kernels.h.  A library and a gfx950 code object of its own: libbnr_hip.so's two stay what they are.  It reaches a chain
 // through bnr_chain_device_view, runs PSIS through bnr_psis_weights and leaves its messages with bnr_set_last_error -- the exported calls of
 // libbnr_hip.so, nothing of bnr_internal.h.
-// The driver of a call (call_guard, mloo_job, open_chain_job / open_raw_job, run_job) is bnr_mloo_job.h, shared with libbnr_medge.so and
-// libbnr_mpred.so; this library passes run_job no hook and fetches loglik, resid, var and logml as its outputs need them.
+// The driver of a call (call_guard, mloo_job, open_chain_job / open_raw_job, run_job) is bnr_mloo_job.h, shared with the five other marginal
+// libraries; this library passes run_job no hook and fetches loglik, resid, var and logml as its outputs need them.
 #include "bnr_mloo_job.h"
 
 int bnr_mloo_abi_version(void) { return BNR_MLOO_ABI_VERSION; }
 
-int bnr_mloo_set_option(const char *name, int64_t value)
-{
-    if (!name) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (std::string(name) == "mloo_batch_draws") {
-        if (value < 0) return fail(BNR_ERR_BAD_ARG, "mloo_batch_draws must be >= 0");
-        opt_batch_draws.store(value);
-        return BNR_OK;
-    }
-    return fail(BNR_ERR_BAD_ARG, std::string("unknown option ") + name);
-}
+int bnr_mloo_set_option(const char *name, int64_t value) { return set_batch_draws("mloo", name, value); }
 
 int bnr_marginal_loglik(int32_t device, int32_t n, int32_t q, int32_t ndraws, const double *X, const double *y, const double *tau2, const double *mu,
                         const double *S, const double *W, double *loglik, double *resid, double *var, double *logml, int32_t *n_bad)

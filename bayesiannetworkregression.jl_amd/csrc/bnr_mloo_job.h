@@ -1,8 +1,10 @@
-// bnr_mloo_job.h -- the host driver that libbnr_mloo.so (bnr_mloo.hip), libbnr_medge.so (bnr_medge.hip) and libbnr_mpred.so (bnr_mpred.hip)
-// share: the device memory and the stream of one call (call_guard), what the batches of a call work on (mloo_job), how an entry point fills it
-// in from its arguments (check_chain_list and open_chain_job for the chain form, open_raw_job for the raw form) and the batches themselves
-// (run_job) over the kernels of bnr_mloo_kernels.h.  Internal: included by those translation units after the kernels, each into its own library
-// and code object; every name here has internal linkage, so each library launches its own copy of the kernels and keeps its own batch option.
+// bnr_mloo_job.h -- the host driver that the six marginal libraries (bnr_mloo.hip, bnr_medge.hip, bnr_mpred.hip, bnr_mcheck.hip, bnr_mstack.hip,
+// bnr_mcov.hip) share: the device memory and the stream of one call (call_guard), what the batches of a call work on (mloo_job), how an entry
+// point fills it in from its arguments (check_chain_list and open_chain_job for the chain form, open_raw_job for the raw form), the batches
+// themselves (run_job) over the kernels of bnr_mloo_kernels.h, and the checks that several of them make: the library's batch option
+// (set_batch_draws), the chain weights (weight_check) and the half-width of a quantile's bracket (bracket_halfwidth).  Internal: included by
+// those translation units after the kernels, each into its own library and code object; every name here has internal linkage, so each library
+// launches its own copy of the kernels and keeps its own batch option.
 #pragma once
 #include "../../include/bnr_mloo.h"
 #include "bnr_mloo_kernels.h"
@@ -24,6 +26,42 @@ int fail(int code, const std::string &msg) { return bnr_set_last_error(code, msg
     } while (0)
 
 std::atomic<long long> opt_batch_draws{0};              // the library's "*_batch_draws" option (0: automatic)
+
+// bnr_<prefix>_set_option for the option every marginal library has, "<prefix>_batch_draws" (>= 0); any other name is unknown
+int set_batch_draws(const char *prefix, const char *name, int64_t value)
+{
+    if (!name) return fail(BNR_ERR_BAD_ARG, "NULL argument");
+    const std::string option = std::string(prefix) + "_batch_draws";
+    if (option != name) return fail(BNR_ERR_BAD_ARG, std::string("unknown option ") + name);
+    if (value < 0) return fail(BNR_ERR_BAD_ARG, option + " must be >= 0");
+    opt_batch_draws.store(value);
+    return BNR_OK;
+}
+
+// the refusal of the chain weights w[K] of a call, bnr_chains_wsummary's checks (finite, >= 0, one > 0, |sum - 1| <= 1e-9), or NULL
+const char *weight_check(const double *w, int K)
+{
+    double s = 0.0;
+    bool any = false;
+    for (int k = 0; k < K; ++k) {
+        if (!std::isfinite(w[k]) || w[k] < 0.0) return "weights must be finite and >= 0";
+        any = any || w[k] > 0.0;
+        s += w[k];
+    }
+    if (!any) return "at least one weight must be > 0";
+    if (!(std::fabs(s - 1.0) <= 1e-9)) return "weights must sum to 1 (within 1e-9)";
+    return nullptr;
+}
+
+// the half-width c, in sds of a component, of the bracket a mixture's p_lo and p_hi quantiles are searched in (0 < p_lo < p_hi < 1): the first of
+// 1, 1.5, .. 40 with Phi(-c) < min(p_lo, 1 - p_hi) / 2
+double bracket_halfwidth(double p_lo, double p_hi)
+{
+    const double pm = 0.5 * std::min(p_lo, 1.0 - p_hi);
+    double c = 1.0;
+    while (!(0.5 * std::erfc(c * 0.70710678118654752440) < pm) && c < 40.0) c += 0.5;
+    return c;
+}
 
 // the device memory and the stream of one call, released on every path
 struct call_guard {

@@ -1,8 +1,8 @@
 // bnr_mpred.hip -- libbnr_mpred.so behind include/bnr_mpred.h: Rao-Blackwellised prediction of new rows, gamma integrated out on the device.
 // A library and a gfx950 code object of its own: the four kernels of bnr_mloo_kernels.h and the two of bnr_medge_kernels.h (by #include, through
-// the drivers shared with libbnr_mloo.so and libbnr_medge.so: bnr_mloo_job.h opens the job of either form and runs its batches,
-// bnr_medge_summary.h holds the summary and the transposing copies; k_medge_proj rides along unused) plus the
-// four of bnr_mpred_kernels.h.  It reaches a chain through bnr_chain_device_view and leaves its messages with bnr_set_last_error -- exported
+// the drivers shared with the other marginal libraries: bnr_mloo_job.h opens the job of either form and runs its batches, bnr_medge_summary.h
+// (libbnr_medge.so's and libbnr_mcov.so's too) holds the summary and the transposing copies; k_medge_proj rides along unused) plus the four of
+// bnr_mpred_kernels.h.  It reaches a chain through bnr_chain_device_view and leaves its messages with bnr_set_last_error -- exported
 // calls of libbnr_hip.so, nothing of bnr_internal.h.  Linked with bnr_mpred.map: only the functions of the header are exported.
 #include "../../include/bnr_mpred.h"
 #include "bnr_mpred_kernels.h"
@@ -74,18 +74,12 @@ int bnr_mpred_abi_version(void) { return BNR_MPRED_ABI_VERSION; }
 
 int bnr_mpred_set_option(const char *name, int64_t value)
 {
-    if (!name) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (std::string(name) == "mpred_batch_draws") {
-        if (value < 0) return fail(BNR_ERR_BAD_ARG, "mpred_batch_draws must be >= 0");
-        opt_batch_draws.store(value);
-        return BNR_OK;
-    }
-    if (std::string(name) == "mpred_block_rows") {
+    if (name && std::string(name) == "mpred_block_rows") {
         if (value < 0 || value > 0x7FFFFFFFll) return fail(BNR_ERR_BAD_ARG, "mpred_block_rows must be >= 0 and < 2^31");
         opt_block_rows.store(value);
         return BNR_OK;
     }
-    return fail(BNR_ERR_BAD_ARG, std::string("unknown option ") + name);
+    return set_batch_draws("mpred", name, value);
 }
 
 int bnr_marginal_predict(int32_t device, int32_t n, int32_t q, int32_t m, int32_t ndraws, const double *X, const double *y, const double *Xnew,

@@ -2,48 +2,19 @@
 // pooled draws, and the leave-one-out predictive checks of the stacked mixture, on the device.  A library and a gfx950 code object of its own: the
 // four kernels of bnr_mloo_kernels.h (by #include, through bnr_mloo_job.h, the driver shared with the other marginal libraries: open_chain_job,
 // run_job without a hook, and mloo_out, which leaves loglik, resid and var on the device), the kernels of bnr_mcheck_kernels.h (by #include;
-// k_mcheck_moments and k_mcheck_quantile are launched, k_mcheck_stage is only carried along) and k_mstack_stage of bnr_mstack_kernels.h.  It
-// reaches a chain through bnr_chain_device_view, runs PSIS through bnr_psis_weights and the solver through bnr_stacking_weights, and leaves its
-// messages with bnr_set_last_error -- exported calls of libbnr_hip.so, nothing of bnr_internal.h.  Linked with bnr_mstack.map: only the functions
-// of the header are exported.
+// k_mcheck_moments and k_mcheck_quantile are launched through bnr_mcheck_rows.h, the host code shared with libbnr_mcheck.so; k_mcheck_stage is
+// only carried along) and k_mstack_stage of bnr_mstack_kernels.h.  It reaches a chain through bnr_chain_device_view, runs PSIS through
+// bnr_psis_weights and the solver through bnr_stacking_weights, and leaves its messages with bnr_set_last_error -- exported calls of
+// libbnr_hip.so, nothing of bnr_internal.h.  Linked with bnr_mstack.map: only the functions of the header are exported.
 #include "../../include/bnr_mstack.h"
 #include "bnr_mcheck_kernels.h"
 #include "bnr_mstack_kernels.h"
 #include "bnr_mloo_job.h"
+#include "bnr_mcheck_rows.h"
 
 #include <cstring>
 
 namespace {
-struct mix_out { double *mean, *sd, *pit, *lower, *upper; };
-
-// the checks of a mixture's arguments that need no shapes; c: the bracket's half-width in sds (bnr_mcheck.hip's mix_check)
-const char *mix_check(const mix_out &o, bool has_y, double p_lo, double p_hi, double &c)
-{
-    c = 1.0;
-    if (o.pit && !has_y) return "pit needs y";
-    if (o.lower || o.upper) {
-        if (!(p_lo > 0.0 && p_lo < p_hi && p_hi < 1.0)) return "need 0 < p_lo < p_hi < 1";
-        const double pm = 0.5 * std::min(p_lo, 1.0 - p_hi);
-        for (c = 1.0; !(0.5 * std::erfc(c * 0.70710678118654752440) < pm) && c < 40.0; c += 0.5) { }
-    }
-    return nullptr;
-}
-
-// the chain weights of a call, bnr_chains_wsummary's checks: finite, >= 0, one > 0, |sum - 1| <= 1e-9
-const char *weight_check(const double *w, int K)
-{
-    double s = 0.0;
-    bool any = false;
-    for (int k = 0; k < K; ++k) {
-        if (!std::isfinite(w[k]) || w[k] < 0.0) return "weights must be finite and >= 0";
-        any = any || w[k] > 0.0;
-        s += w[k];
-    }
-    if (!any) return "at least one weight must be > 0";
-    if (!(std::fabs(s - 1.0) <= 1e-9)) return "weights must sum to 1 (within 1e-9)";
-    return nullptr;
-}
-
 // log sum_{k: w_k > 0} w_k exp(v_k) with the largest such v_k taken out, k ascending (v: stride ldv) -- bnr_chains_stack's
 double wlse(const double *v, size_t ldv, const double *w, int K)
 {
@@ -56,8 +27,8 @@ double wlse(const double *v, size_t ldv, const double *w, int K)
 
 // The stacked mixture of the device matrices A, V, LW (rows x K nd, a row's components contiguous, chain k's in columns k nd ..) under the host
 // weights w[K] (checked), yd (rows, NULL: none), and the outputs asked for to the host: k_mstack_stage into the compacted rows x D+ matrices, then
-// the two row kernels of bnr_mcheck_kernels.h in bnr_mcheck.hip's launch loop.  a_is_resid: A holds resid = y - m (the chain form; it needs yd),
-// else m itself.
+// the two row kernels of bnr_mcheck_kernels.h in the launch loop of bnr_mcheck_rows.h.  a_is_resid: A holds resid = y - m (the chain form; it
+// needs yd), else m itself.
 int stack_run(call_guard &g, int rows, int K, int nd, const double *w, const double *A, bool a_is_resid, const double *V, const double *LW,
               const double *yd, double c, double p_lo, double p_hi, const mix_out &o)
 {
@@ -68,8 +39,8 @@ int stack_run(call_guard &g, int rows, int K, int nd, const double *w, const dou
         if (w[k] > 0.0) { csel.push_back(k); wsel.push_back(w[k]); }
     const int Kp = (int)csel.size(), D = K * nd, Dp = Kp * nd;
     const size_t total = (size_t)rows * (size_t)Dp;
-    int *cd = nullptr, *flag = nullptr;
-    double *wd = nullptr, *Wt = nullptr, *Isd = nullptr, *Mo = nullptr, *Vo = nullptr, *out = nullptr, *brk = nullptr;
+    int *cd = nullptr;
+    double *wd = nullptr, *Wt = nullptr, *Isd = nullptr, *Mo = nullptr, *Vo = nullptr;
     if ((rc = g.upload(&cd, (const int *)csel.data(), (size_t)Kp))) return rc;
     if ((rc = g.upload(&wd, (const double *)wsel.data(), (size_t)Kp))) return rc;
     HIPCHK(hipStreamSynchronize(g.st));
@@ -77,46 +48,18 @@ int stack_run(call_guard &g, int rows, int K, int nd, const double *w, const dou
     if ((rc = g.alloc(&Isd, total))) return rc;
     if ((rc = g.alloc(&Mo, total))) return rc;
     if (Kp < K && (rc = g.alloc(&Vo, total))) return rc;
-    if ((rc = g.alloc(&out, (size_t)5 * rows))) return rc;
-    if ((rc = g.alloc(&flag, (size_t)rows))) return rc;
-    const bool bounds = o.lower || o.upper;
-    if (bounds && (rc = g.alloc(&brk, (size_t)2 * rows))) return rc;
-    double *host[5] = {o.mean, o.sd, o.pit, o.lower, o.upper}, *dev[5];
-    for (int f = 0; f < 5; ++f) dev[f] = host[f] ? out + (size_t)f * rows : nullptr;
     const unsigned strips = (unsigned)((Dp + MSTACK_STRIP - 1) / MSTACK_STRIP);
     const unsigned gy = (unsigned)std::min<long long>(rows, std::max<long long>(1, std::min<long long>(65535, ((long long)1 << 16) / strips)));
-    hipLaunchKernelGGL(k_mstack_stage, dim3(strips, gy), dim3(256), 0, g.st, LW, V, A, a_is_resid ? yd : nullptr, rows, D, Dp, nd, (const int *)cd,
-                       (const double *)wd, Wt, Isd, Mo, Vo);
-    const double *Vr = Vo ? Vo : V;
-    for (int i0 = 0; i0 < rows; i0 += MCHECK_ROWS_PER_LAUNCH) {
-        const int nr = std::min(MCHECK_ROWS_PER_LAUNCH, rows - i0);
-        hipLaunchKernelGGL(k_mcheck_moments, dim3(nr), dim3(256), 0, g.st, (const double *)Mo, Vr, (const double *)Wt, (const double *)Isd, yd, Dp, i0, c,
-                           dev[0], dev[1], dev[2], brk, flag);
-        if (bounds)
-            hipLaunchKernelGGL(k_mcheck_quantile, dim3(nr, 2), dim3(256), 0, g.st, (const double *)Mo, (const double *)Wt, (const double *)Isd, Dp, i0,
-                               (const double *)brk, (const int *)flag, p_lo, p_hi, dev[3], dev[4]);
-    }
-    HIPCHK(hipGetLastError());
-    for (int f = 0; f < 5; ++f)
-        if (host[f]) HIPCHK(hipMemcpyAsync(host[f], dev[f], sizeof(double) * (size_t)rows, hipMemcpyDeviceToHost, g.st));
-    HIPCHK(hipStreamSynchronize(g.st));
-    HIPCHK(hipGetLastError());
-    return BNR_OK;
+    return mix_rows(g, rows, Dp, Mo, Vo ? Vo : V, Wt, Isd, yd, c, p_lo, p_hi, o, [&] {
+        hipLaunchKernelGGL(k_mstack_stage, dim3(strips, gy), dim3(256), 0, g.st, LW, V, A, a_is_resid ? yd : nullptr, rows, D, Dp, nd, (const int *)cd,
+                           (const double *)wd, Wt, Isd, Mo, Vo);
+    });
 }
 }   // namespace
 
 int bnr_mstack_abi_version(void) { return BNR_MSTACK_ABI_VERSION; }
 
-int bnr_mstack_set_option(const char *name, int64_t value)
-{
-    if (!name) return fail(BNR_ERR_BAD_ARG, "NULL argument");
-    if (std::string(name) == "mstack_batch_draws") {
-        if (value < 0) return fail(BNR_ERR_BAD_ARG, "mstack_batch_draws must be >= 0");
-        opt_batch_draws.store(value);
-        return BNR_OK;
-    }
-    return fail(BNR_ERR_BAD_ARG, std::string("unknown option ") + name);
-}
+int bnr_mstack_set_option(const char *name, int64_t value) { return set_batch_draws("mstack", name, value); }
 
 int bnr_stacked_mixture(int32_t device, int32_t rows, int32_t K, int32_t nd, const double *mean, const double *var, const double *logw,
                         const double *weights, const double *y, double p_lo, double p_hi, double *out_mean, double *out_sd, double *out_pit,

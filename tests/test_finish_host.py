@@ -223,3 +223,148 @@ def test_pool_chains_with_loo_predict_is_one_pooled_call_for_both(fit):
     assert log == FETCH + _pooled_calls(TWO, LW2, HI2, False)[:-1] + [
         ("device_loo_predict", TWO, "arr", NB, NS, INTERVAL, R_EFF), ("pooled_loo_predict", TWO, NB + 1, NS, R_EFF, p_lo, p_hi, _capi.LOO_PREDICT_FIELDS)]
     assert res.loo_predictive.draws == 2 * NS and res.loo["khat_threshold"] == _thr(2 * NS) and res.stat_chains == 2
+
+
+# ------------------------------------------------------------------------------------------ the analysis options, stated once
+# The analysis options of a fit are _fit_requests' parameters after x_transform.  Fit, generate_samples and generate_samples_dbl repeat them in
+# their signatures and hand them on as one dict made from that list: these tests hold the four lists equal and follow every option, with a value
+# of its own, from Fit down to _fit_requests.
+_FIT_REQUESTS_PARAMETERS = list(inspect.signature(api._fit_requests).parameters.values())
+OPTIONS = _FIT_REQUESTS_PARAMETERS[[p.name for p in _FIT_REQUESTS_PARAMETERS].index("x_transform") + 1:]
+OPTION_NAMES = [p.name for p in OPTIONS]
+
+
+def test_the_analysis_keywords_of_the_fit_functions_are_those_of_fit_requests():
+    assert len(OPTIONS) == 30 and OPTION_NAMES[0] == "return_state" and OPTION_NAMES[-1] == "marginal_loo_predict"
+    want = [(p.name, type(p.default), p.default) for p in OPTIONS]
+    for fn in (api.Fit, api.generate_samples, api.generate_samples_dbl):
+        got = [(p.name, type(p.default), p.default) for p in inspect.signature(fn).parameters.values() if p.name in OPTION_NAMES]
+        assert got == want, fn.__name__
+
+
+class _Marked:
+    """a value of an option that is no default and equal to no other"""
+
+    def __init__(self, name):
+        self.name = name
+
+    def __repr__(self):
+        return "<%s>" % self.name
+
+
+def _marked_options():
+    return {name: _Marked(name) for name in OPTION_NAMES}
+
+
+def _same_options(kwargs, given):
+    return all(kwargs[name] is given[name] for name in OPTION_NAMES)
+
+
+@pytest.mark.parametrize("doubling", [False, True])
+def test_fit_hands_every_analysis_option_to_the_check_and_to_the_sampler(monkeypatch, doubling):
+    calls = []
+
+    def recorder(name):
+        def f(*a, **k):
+            calls.append((name, a, k))
+            return name
+        return f
+
+    for name in ("_fit_requests", "generate_samples", "generate_samples_dbl"):
+        monkeypatch.setattr(api, name, recorder(name))
+    given = _marked_options()
+    X, y = np.zeros((N, Q)), np.zeros(N)
+    out = api.Fit(X, y, R, filename=None, seed=5, num_chains=3, **(dict(mingen=10, maxgen=20) if doubling else {}), **given)
+    sampler = "generate_samples_dbl" if doubling else "generate_samples"
+    assert out == sampler and [c[0] for c in calls] == ["_fit_requests", sampler]        # the check first, then the one sampler
+    _, a, k = calls[0]
+    assert len(a) == 2 and a[0] is y and a[1] == 3 and sorted(k) == sorted(OPTION_NAMES) and _same_options(k, given)
+    _, a, k = calls[1]
+    assert a[0] is X and a[1] is y and a[2] == R and _same_options(k, given)
+    assert k["num_chains"] == 3 and k["seed"] == 5 and k["xi_weights"] == "log"
+
+
+class _FakeRun:
+    """what generate_samples / generate_samples_dbl need of a ChainSet that converged at once"""
+    chains = {}
+
+    def __init__(self, *a, **k):
+        pass
+
+    def init_prior(self):
+        pass
+
+    def run(self, *a, **k):
+        pass
+
+    def close(self):
+        pass
+
+
+@pytest.mark.parametrize("sampler, window, nsamp", [("generate_samples", dict(nburn=6, nsamp=4), 4), ("generate_samples_dbl", dict(mingen=9, maxgen=9), 5)])
+def test_the_samplers_hand_every_analysis_option_to_fit_requests(monkeypatch, sampler, window, nsamp):
+    calls, finished = [], []
+    xin = object()
+    monkeypatch.setattr(api, "XInput", lambda X, x_transform: xin)
+    monkeypatch.setattr(api, "ChainSet", _FakeRun)
+    monkeypatch.setattr(api, "return_psrf_VOI", lambda cs, stt, ns, **k: Results(None, np.ones(V), np.ones(Q), stt, ns))
+    monkeypatch.setattr(api, "_fit_requests", lambda *a, **k: calls.append((a, k)) or "the requests")
+    monkeypatch.setattr(api, "_finish", lambda cs, res, req, seed: finished.append((req, seed)) or res)
+    given = _marked_options()
+    y = np.zeros(N)
+    res = getattr(api, sampler)(np.zeros((N, Q)), y, R, seed=5, num_chains=3, x_transform=False, suppress_timer=True, **window, **given)
+    (a, k), = calls
+    assert len(a) == 5 and a[0] is y and a[1] == 3 and a[2] is xin and a[3] == nsamp and a[4] is False
+    assert sorted(k) == sorted(OPTION_NAMES) and _same_options(k, given)
+    assert finished == [("the requests", 5)] and res.sampled == nsamp
+
+
+# the six marginal options: (the option, the keyword of its draws, whether it takes predict_interval, what else the request needs)
+MARGINAL_OPTIONS = [("marginal_loo", "marginal_loo_draws", False, {}), ("marginal_edges", "marginal_edges_draws", True, {}),
+                    ("marginal_edge_cov", "marginal_edges_draws", False, {}), ("marginal_predict", "marginal_predict_draws", True, {"predict_X": "rows"}),
+                    ("marginal_loo_predict", "marginal_loo_draws", True, {}), ("marginal_stack", "marginal_loo_draws", True, {})]
+RANKS_MESSAGE = "%s needs every chain of the fit on one rank: the chains are spread over 2 torch.distributed ranks"
+DRAWS_MESSAGE = "%s must be an integer >= 1, not %r"
+INTERVAL_MESSAGE = "need 0 < p_lo < p_hi < 1, not p_lo = 0.0, p_hi = 1.0"
+ROWS_MESSAGE = "%s takes at most 2048 training rows in this version, not 2049"
+
+
+@pytest.mark.parametrize("option, draws, takes_interval, needs", MARGINAL_OPTIONS)
+def test_the_refusals_of_a_marginal_option_and_their_order(monkeypatch, option, draws, takes_interval, needs):
+    y = np.zeros(N)
+    big = _capi.XInput(np.zeros((_capi.MLOO_MAX_N + 1, 3)))
+
+    def refusal(ranks=1, **kw):
+        with monkeypatch.context() as m:
+            m.setattr(api, "_rank_world", lambda: (0, ranks))
+            m.setattr(api, "_new_rows", lambda *a: "rows")                    # (predict_X is not what is under test)
+            with pytest.raises(ValueError) as e:
+                api._fit_requests(y, 2, **{option: True}, **needs, **kw)
+        return str(e.value)
+
+    for bad in (0, 1.5, True):
+        assert refusal(**{draws: bad}) == DRAWS_MESSAGE % (draws, bad)
+    assert refusal(ranks=2) == RANKS_MESSAGE % option
+    assert refusal(X_new=big, x_transform=False) == ROWS_MESSAGE % option
+    if takes_interval:
+        assert refusal(predict_interval=100) == INTERVAL_MESSAGE
+    # two at once: the ranks before the draws, the draws before the interval (or, without one, the rows), the interval before the rows
+    assert refusal(ranks=2, **{draws: 0}) == RANKS_MESSAGE % option
+    assert refusal(predict_interval=100, X_new=big, x_transform=False, **{draws: 0}) == DRAWS_MESSAGE % (draws, 0)
+    if takes_interval:
+        assert refusal(predict_interval=100, X_new=big, x_transform=False) == INTERVAL_MESSAGE
+    # and what stands in front of the ranks
+    if option == "marginal_predict":
+        with monkeypatch.context() as m:
+            m.setattr(api, "_rank_world", lambda: (0, 2))
+            with pytest.raises(ValueError) as e:
+                api._fit_requests(y, 2, marginal_predict=True)
+        assert str(e.value) == "marginal_predict needs predict_X"
+    if option == "marginal_stack":
+        with monkeypatch.context() as m:
+            m.setattr(api, "_rank_world", lambda: (0, 2))
+            for chains, message in ((1, "marginal_stack needs num_chains >= 2: one chain has nothing to be weighted against"),
+                                    (33, "marginal_stack takes at most 32 chains")):
+                with pytest.raises(ValueError) as e:
+                    api._fit_requests(y, chains, marginal_stack=True)
+                assert str(e.value) == message

@@ -1,6 +1,8 @@
-"""SHA-256 of what the marginal libraries (libbnr_mloo.so, libbnr_medge.so, libbnr_mpred.so) return on fixed inputs: marginal_loglik_raw,
-marginal_gamma_raw, marginal_predict_raw, mixture_summary_raw and mixture_score_raw on seeded arrays at the tile edges (n, q, m around 32, 64 and
-128; 1, 9 and 13 draws; with and without W; the batch option 0 and 5, mpred_block_rows 0 and 32), and the three chain calls on a 2-chain fit.
+"""SHA-256 of what the six marginal libraries return on fixed inputs: marginal_loglik_raw, marginal_gamma_raw, marginal_predict_raw,
+mixture_summary_raw and mixture_score_raw on seeded arrays at the tile edges (n, q, m around 32, 64 and 128; 1, 9 and 13 draws; with and without
+W; the batch option 0 and 5, mpred_block_rows 0 and 32); weighted_mixture_raw and stacked_mixture_raw (1 and 33 rows, 1 and 257 components per
+row, with and without y and the bounds; K = 3 with one weight 0, the compaction of the stacked mixture); marginal_gamma_cov_raw (all columns and
+three of them, with and without weights); and the six chain calls on a 2-chain fit.
 One line per output of a call and setting, over all its shapes in a fixed order (--verbose: one line per shape as well).  Run it in two checkouts
 and diff the output to see whether a change to that layer is bitwise neutral.  The companion of post_digest.py."""
 import sys, os, hashlib, argparse, itertools
@@ -80,6 +82,50 @@ def mixture_cases():
         sc.show()
 
 
+def log_weights(rng, rows, K, nd):
+    """rows x (K nd) log weights that sum to 1 within every chain's nd columns"""
+    w = rng.random((rows, K, nd)) + 0.05
+    return np.log(w / w.sum(axis=2, keepdims=True)).reshape(rows, K * nd)
+
+
+def weighted_cases():
+    """libbnr_mcheck.so and libbnr_mstack.so: the raw mixtures, with and without y (pit) and the bounds (the bracket and the quantile launches)"""
+    for has_y, bounds in itertools.product((True, False), (True, False)):
+        fields = ("mean", "sd") + (("pit",) if has_y else ()) + (("lower", "upper") if bounds else ())
+        tag = "y=%d bounds=%d" % (has_y, bounds)
+        wm, sm = Digests("weighted_mixture_raw " + tag, _capi.MCHECK_FIELDS), Digests("stacked_mixture_raw " + tag, _capi.MCHECK_FIELDS)
+        for rows, D in itertools.product((1, 33), (1, 257)):
+            rng = np.random.default_rng(4099 * rows + D)
+            mean, var, y = rng.standard_normal((rows, D)), rng.random((rows, D)) + 0.1, rng.standard_normal(rows) if has_y else None
+            shape = "rows=%d D=%d" % (rows, D)
+            wm.add(shape, _capi.weighted_mixture_raw(mean, var, log_weights(rng, rows, 1, D), y, 0.05, 0.9, fields=fields))
+            sm.add(shape + " K=1", _capi.stacked_mixture_raw(mean, var, log_weights(rng, rows, 1, D), [1.0], 1, y, 0.05, 0.9, fields=fields))
+        for rows, nd, w in itertools.product((1, 33), (1, 86), ((0.5, 0.25, 0.25), (0.625, 0.0, 0.375))):       # one weight 0: Kp < K
+            rng = np.random.default_rng(4099 * rows + 3 * nd + 7)
+            mean, var, y = rng.standard_normal((rows, 3 * nd)), rng.random((rows, 3 * nd)) + 0.1, rng.standard_normal(rows) if has_y else None
+            sm.add("rows=%d nd=%d K=3 w=%r" % (rows, nd, w), _capi.stacked_mixture_raw(mean, var, log_weights(rng, rows, 3, nd), w, 3, y, 0.05, 0.9,
+                                                                                           fields=fields))
+        wm.show()
+        sm.show()
+
+
+def cov_cases():
+    """libbnr_mcov.so: the raw covariance of two chains' draws, all columns and a subset, pooled and weighted, the batch option 0 and 5"""
+    for batch, subset, weighted in itertools.product((0, 5), (False, True), (False, True)):
+        _capi.mcov_set_option("mcov_batch_draws", batch)
+        cv = Digests("marginal_gamma_cov_raw batch=%d cols=%d weights=%d" % (batch, subset, weighted), ("mean", "cov", "within", "m", "v", "n_bad"))
+        for n, q, nd in itertools.product((31, 33), (3, 33, 70), (1, 9)):
+            rng = np.random.default_rng(1000003 * n + 1009 * q + nd)
+            X, y, t2, mu, S, W = phi(n, q, 2 * nd, rng)
+            cv.add("n=%d q=%d nd=%d" % (n, q, nd), _capi.marginal_gamma_cov_raw(X, y, t2, mu, S, W, cols=(q - 1, 0, q // 2) if subset else None, nchains=2,
+                                                                                   weights=(0.25, 0.75) if weighted else None))
+        cv.show()
+    _capi.mcov_set_option("mcov_batch_draws", 0)
+
+
+LIBS = ("mloo", "medge", "mpred", "mcheck", "mstack", "mcov")
+
+
 def chain_cases():
     X, y, _ = bnr_amd.make_synthetic(20, 6, 2, seed=7)
     tot = 60
@@ -92,7 +138,7 @@ def chain_cases():
     Xn, yn = rng.standard_normal((7, chains[0].q)), rng.standard_normal(7)
     for thin, batch in itertools.product((1, 3), (0, 5)):
         tag = "thin=%d batch=%d" % (thin, batch)
-        for name in ("mloo", "medge", "mpred"):
+        for name in LIBS:
             getattr(_capi, name + "_set_option")(name + "_batch_draws", batch)
         lo = Digests("chains_marginal_loo " + tag, ("elpd_loo", "pareto_k", "loo_mean", "loo_sd", "logml", "loglik", "n_bad"))
         lo.add("", _capi.chains_marginal_loo(chains, 11, 40, thin, loglik=True))
@@ -105,7 +151,22 @@ def chain_cases():
         pr = Digests("chains_marginal_predict " + tag, _capi.MPRED_SUMMARY_FIELDS + ("dmean", "dvar", "n_bad"))
         pr.add("", out + (m, v, nb))
         pr.show()
-    for name in ("mloo", "medge", "mpred"):
+        el, kh, out, ml, ll, nb = _capi.chains_marginal_loo_predict(chains, 11, 40, thin, loglik=True)
+        lp = Digests("chains_marginal_loo_predict " + tag, ("elpd_loo", "pareto_k") + _capi.MCHECK_FIELDS + ("logml", "loglik", "n_bad"))
+        lp.add("", (el, kh) + out + (ml, ll, nb))
+        lp.show()
+        for fixed in (None, (1.0, 0.0)):
+            w, el, kh, es, gap, it, out, ml, nb = _capi.chains_marginal_stack(chains, 11, 40, thin, weights=fixed)
+            st = Digests("chains_marginal_stack %s fixed=%d" % (tag, fixed is not None),
+                         ("weights", "elpd_chain", "pareto_k_chain", "elpd_stack", "gap", "iterations") + _capi.MCHECK_FIELDS + ("logml", "n_bad"))
+            st.add("", (w, el, kh, es, gap, it) + out + (ml, nb))
+            st.show()
+        for cols, weights in itertools.product((None, (5, 0, 2)), (None, (0.25, 0.75))):
+            ec = Digests("chains_marginal_edge_cov %s cols=%d weights=%d" % (tag, cols is not None, weights is not None),
+                         ("mean", "cov", "within", "m", "v", "n_bad"))
+            ec.add("", _capi.chains_marginal_edge_cov(chains, 11, 40, thin, cols=cols, weights=weights, per_draw=True))
+            ec.show()
+    for name in LIBS:
         getattr(_capi, name + "_set_option")(name + "_batch_draws", 0)
     for ch in chains:
         ch.close()
@@ -118,6 +179,8 @@ def main():
     VERBOSE = ap.parse_args().verbose
     raw_cases()
     mixture_cases()
+    weighted_cases()
+    cov_cases()
     chain_cases()
 
 
