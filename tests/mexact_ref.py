@@ -2,8 +2,8 @@
 "Exact references of the marginal kernels").
 
 The construction.  L = diag(2^k_i) + N with N a strictly lower triangle of small integers: a few dense columns at the edges of the 16- and 32-row
-tiles, a dense last row and, at the small shapes, random extras.  A = L L^T is an integer matrix whose Cholesky factor is L: the pivots are 4^k_i, so
-sqrt and every division by a pivot are exact.  The k_i are raised until P = A - I is diagonally dominant; then
+tiles and of the factor kernel's 256-column passes, a dense last row and, at the small shapes, random extras.  A = L L^T is an integer matrix
+whose Cholesky factor is L: the pivots are 4^k_i, so sqrt and every division by a pivot are exact.  The k_i are raised until P = A - I is diagonally dominant; then
     P = sum_{i>j} |P_ij| (e_i +- e_j)(e_i +- e_j)^T + sum_i (P_ii - sum_j |P_ij|) e_i e_i^T = X diag(S) X^T
 with X in {0, +-1} and integer S >= 0.  The draws of a shape share one X, the union of the columns any of them needs; S selects.  On top of that:
 a value of S is split over several columns in chunks of CH significant bits (so that S_e t_e keeps few bits), a column is scaled (x_e 2^a, S_e 4^-a,
@@ -24,10 +24,10 @@ from fractions import Fraction
 import numpy as np
 
 CH = 5                                                                   # significant bits of S per column
-ROWS_257 = (0, 1, 15, 16, 31, 32, 255, 256)                              # n = 257: every edge incident to these rows is checked, plus a sample
+ROWS_257 = (0, 1, 15, 16, 31, 32, 255, 256)                              # large q: every edge incident to these rows (edge_rows) is checked, plus a sample
 SAMPLE_257 = 600
 
-# per n: draws of the pool, dense columns of N, random extras of N, q mod 32 (None: the next q with q mod 4 != 0), new rows
+# per n: draws of the pool, dense columns of N, random extras of N (spots: placed ones), q mod 32 (None: the next q with q mod 4 != 0), new rows
 SHAPES = {
     1: dict(draws=1, dense=(), extras=0, qmod32=0, m=1),
     2: dict(draws=5, dense=(0,), extras=0, qmod32=None, m=1),
@@ -37,6 +37,12 @@ SHAPES = {
     33: dict(draws=5, dense=(0, 15, 16, 31), extras=10, qmod32=None, m=129),
     65: dict(draws=1, dense=(0, 31, 32), extras=0, qmod32=None, m=33),
     257: dict(draws=1, dense=(0, 255), extras=0, qmod32=None, m=129),
+    # past the factor kernel's first 256-column pass (test_marginal_exact_host.test_the_passes_behind_the_first_carry_data): the dense column at a
+    # pass's first column and the dense last row, nine rows behind it, fill one unrolled chunk of eight of that pass; the placed extras in the
+    # first rows give the Cholesky non-zero updates of the last row, 256 and 512 rows below its column.  Column 0 is left out: with it and two
+    # more dense columns no attempt reaches the any-order condition at these sizes.
+    265: dict(draws=1, dense=(255, 256, 263), extras=0, spots=((4, 3), (6, 5), (8, 7)), qmod32=None, m=33),
+    521: dict(draws=1, dense=(256, 512), extras=0, spots=((4, 3), (6, 5), (8, 7)), qmod32=None, m=33),
 }
 TWO53 = 1 << 53
 
@@ -105,6 +111,9 @@ def _factor(n, spec, d, attempt):
         even = [r for r in range(c + 1, n - 1, 2) if r not in spec["dense"]]
         if even:
             N[int(rng.choice(even)), c] = rng.choice([-1, 1])
+    for t, (r, c) in enumerate(spec.get("spots", ())):                   # placed extras (odd column, even row, as above; no random number drawn)
+        assert c % 2 == 1 and r % 2 == 0 and c < r < n - 1 and r not in spec["dense"] and c not in spec["dense"]
+        N[r, c] = 1 - 2 * (t % 2)
     k = rng.integers(0, 2, size=n) + (1 if n <= 2 else 0)
     while True:
         L = N + np.diag(2 ** k)
@@ -200,12 +209,19 @@ def _inputs(n, attempts):
     return out
 
 
+def edge_rows(n):
+    """the rows at the edges of the 16- and 32-row tiles and of the factor kernel's 256-column passes, and the last row (ROWS_257 at n = 257)"""
+    return tuple(sorted(r for r in set(ROWS_257) | {511, 512, n - 1} if r < n))
+
+
 def edges_checked(n):
-    """the columns whose edge outputs are checked: all of them up to n = 65; at n = 257 every live column incident to ROWS_257 and a seeded sample"""
+    """the columns whose edge outputs are checked: all of them up to n = 65 and wherever q <= 2 SAMPLE_257; elsewhere every live column incident
+    to edge_rows(n) and a seeded sample of SAMPLE_257 of the others"""
     c = inputs(n)
-    if n <= 65:
+    if n <= 65 or c["q"] <= 2 * SAMPLE_257:
         return np.arange(c["q"])
-    hit = [e for e, key in enumerate(c["keys"]) if key is not None and (key[0] in ROWS_257 or key[1] in ROWS_257)]
+    rows = edge_rows(n)
+    hit = [e for e, key in enumerate(c["keys"]) if key is not None and (key[0] in rows or key[1] in rows)]
     rest = sorted(set(range(c["q"])) - set(hit))
     extra = np.random.default_rng([47, n]).choice(rest, size=SAMPLE_257, replace=False)
     return np.array(sorted(hit + [int(e) for e in extra]))

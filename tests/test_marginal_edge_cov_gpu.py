@@ -98,8 +98,9 @@ def test_large_entries_of_l_behind_the_mask(gpu, n):
 
 
 # ------------------------------------------------------------------------------------------ against the numpy restatement
-@pytest.mark.parametrize("q", (64, 300))
-@pytest.mark.parametrize("n", (64, 65, 129, 257))
+# (258, 300, 513: the M that k_mcov_proj reads comes out of the second and third 256-column pass of k_mloo_factor; 258 is the first n at which a
+# later pass has a column behind its first, 300 fills full unrolled chunks of the second pass, 513 opens the third -- tests/test_marginal_loo_gpu.py)
+@pytest.mark.parametrize("n,q", [(n, q) for q in (64, 300) for n in (64, 65, 129, 257)] + [(258, 64), (300, 64), (513, 64)])
 def test_raw_call_against_the_restatement(gpu, n, q):
     c = mr.case(n, q)
     r = _call(c, range(3))

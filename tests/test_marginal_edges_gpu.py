@@ -1,9 +1,13 @@
 """GPU tests of the Rao-Blackwellised edge summaries (include/bnr_medge.h, libbnr_medge.so; kernels in csrc/bnr_medge_kernels.h): the raw call
 against the mpmath reference within the derived bound (tests/medge_ref.py) at the edges of the 16-row MFMA tile, of the 32-row padding, of the
-128-edge block and of the K step; against the numpy restatement beyond; cases whose answer is exact; large neighbouring entries of L behind the
+128-edge block and of the K step; against the numpy restatement beyond, up to the limit n = 2048; cases whose answer is exact; large neighbouring entries of L behind the
 triangle's mask; the independence of a draw's bits from its batch, its neighbours and its place; bad draws; bnr_mixture_summary against its host
 mirror and, for the quantiles, against their defining property in mpmath; live chains through the chain form and Fit; and both libraries that hold
 the marginal kernels in one process.
+
+Past 256 rows the M that k_medge_proj reads is the work of the later 256-column passes of k_mloo_factor (tests/test_marginal_loo_gpu.py has
+the list): 258 the first column of the second pass with a k < i, 300 a second pass of 44 columns (also X = I at 300 rows), 513 the third pass,
+521 nine columns of it, 2048 all eight passes.
 
 Choices the issue leaves open, and why:
   - the X = I case uses S_e = 2^k - 1 with EVEN k (as the marginal LOO test does): L_ee = 2^(k / 2) is then a float64, so t_e = 2^-k exactly.
@@ -81,15 +85,13 @@ def test_large_entries_of_l_behind_the_mask(gpu, n):
 
 
 # ------------------------------------------------------------------------------------------ against the numpy restatement
-@pytest.mark.parametrize("q", (64, 65, 300))
-@pytest.mark.parametrize("n", (64, 65, 129, 257))
-def test_raw_call_against_the_restatement(gpu, n, q):
-    c = mr.case(n, q)
-    r = _call(c, range(3))
-    hm, hv, hb = api._host_gamma_terms(c["X"], c["y"], c["tau2"][:3], c["mu"][:3], c["S"][:3], c["W"][:3])
+def _against_the_restatement(c, r, D):
+    """m and v of a call on the first D draws of c against api._host_gamma_terms, each within its own gate of 2"""
+    n, q = c["X"].shape
+    hm, hv, hb = api._host_gamma_terms(c["X"], c["y"], c["tau2"][:D], c["mu"][:D], c["S"][:D], c["W"][:D])
     assert r["n_bad"] == 0 and hb == 0
     worst = 0.0
-    for d in range(3):
+    for d in range(D):
         b = er.numpy_bounds(c["X"], c["y"], c["tau2"][d], c["mu"][d], c["S"][d], c["W"][d])
         assert b["beta_lam"] <= 0.1
         for name, h in (("m", hm), ("v", hv)):
@@ -99,8 +101,22 @@ def test_raw_call_against_the_restatement(gpu, n, q):
     print("n=%d q=%d: worst difference / bound %.3g" % (n, q, worst))
 
 
+# (258, 300, 513, 521: the M that the projection reads comes out of the second and third 256-column pass of k_mloo_factor -- module docstring)
+@pytest.mark.parametrize("n,q", [(n, q) for q in (64, 65, 300) for n in (64, 65, 129, 257)] + [(258, 65), (300, 65), (513, 65), (521, 300)])
+def test_raw_call_against_the_restatement(gpu, n, q):
+    c = mr.case(n, q)
+    _against_the_restatement(c, _call(c, range(3)), 3)
+
+
+def test_the_largest_n(gpu):
+    """n = 2048 = MLOO_MAX_N, q = 9, one draw: the projection over the M of all eight passes of the factor kernel, 128 row tiles (1.4 s on an
+    MI355X, the restatement included)"""
+    c = mr.case(2048, 9)
+    _against_the_restatement(c, _call(c, range(1)), 1)
+
+
 # ------------------------------------------------------------------------------------------ exact cases
-@pytest.mark.parametrize("n,q", ((1, 1), (17, 5), (33, 45), (65, 130)))
+@pytest.mark.parametrize("n,q", ((1, 1), (17, 5), (33, 45), (65, 130), (300, 310)))
 def test_exact_cases(gpu, n, q):
     c = mr.case(n, q)
     D = 5

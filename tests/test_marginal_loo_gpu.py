@@ -1,7 +1,20 @@
 """GPU tests of marginal PSIS-LOO (include/bnr_mloo.h, libbnr_mloo.so; kernels in csrc/bnr_mloo_kernels.h): the raw call against the mpmath
 reference within the derived bound (tests/mloo_ref.py) at the edges of the 16-row MFMA tile, of the 4-deep K step and of the batch; against the
-numpy restatement at the edges of the 32-row workgroup tile, of the 256-thread passes of the factor kernel and beyond; cases whose answer is
-exact; the independence of a draw's bits from its batch, its neighbours and its place; bad draws; and live chains through Fit.
+numpy restatement at the edges of the 32-row workgroup tile and through the 256-column passes of the factor kernel up to its limit; cases whose
+answer is exact; the independence of a draw's bits from its batch, its neighbours and its place; bad draws; and live chains through Fit.
+
+Past 256 rows (k_mloo_factor forms L^-1 in passes of 256 columns, every k loop of a pass from its first column i0, unrolled by 8, selecting 0.0
+for k < i; a Cholesky thread owns the rows j + tid, j + tid + 256, ...; z, c and g are LDS arrays of MLOO_MAX_N = 2048):
+  257   the second pass exists, with one column whose k loops run zero times
+  258   the second pass has a column i > i0: the select k >= i first meets a slot that holds an entry of L (dense random L: every slot counts)
+  300   44 columns in the second pass: full unrolled chunks and the remainder loop; the shape of the exact cases, of the independence from the
+        batch, of the pivot that fails in a column j >= 256 and of the live chains (k_mloo_rhs: two workgroups along the rows)
+  513   the third pass exists; a thread's third Cholesky row
+  521   the third pass has nine columns, one full chunk and the remainder loop (also a shape of tests/mexact_ref.py, as is 265)
+  2048  the limit: eight passes, eight rows per thread, the last element of zs, cs and gs
+Measured on an MI355X: the call on one draw at n = 2048 takes 0.90 s (the estimate had been 1.1e7 dependent multiply-subtracts per thread in each of
+the Cholesky and the inverse, unmeasured), test_the_largest_n 2.4 s with its second call and the restatement; no other case past 256 rows takes
+more than 1.3 s.
 
 Two choices the issue leaves open, and why:
   - the one-hot case uses S_e = 2^k - 1 with EVEN k: c_i comes from the columns of L^-1, L_ii = sqrt(1 + S_e) = 2^(k / 2) has to be a float64
@@ -11,6 +24,7 @@ Two choices the issue leaves open, and why:
     allowances 16 eps (|log(2 pi var) / 2| + resid^2 / (2 var) + 1) plus n eps sum_i (|log(2 pi var_i) / 2| + resid_i^2 / (2 var_i)) for the n
     additions of each of the device's two sums."""
 import math
+import time
 
 import numpy as np
 import pytest
@@ -57,15 +71,13 @@ def test_raw_call_meets_the_bound_on_a_binary_matrix(gpu):
 
 
 # ------------------------------------------------------------------------------------------ against the numpy restatement
-@pytest.mark.parametrize("q", (64, 65, 300))
-@pytest.mark.parametrize("n", (64, 65, 128, 129, 257))
-def test_raw_call_against_the_restatement(gpu, n, q):
-    c = mr.case(n, q)
-    r = _call(c, range(3))
-    h = api._host_marginal_terms(c["X"], c["y"], c["tau2"][:3], c["mu"][:3], c["S"][:3], c["W"][:3])
+def _against_the_restatement(c, r, D):
+    """the four outputs of a call on the first D draws of c against api._host_marginal_terms, each within its own gate of 2"""
+    n, q = c["X"].shape
+    h = api._host_marginal_terms(c["X"], c["y"], c["tau2"][:D], c["mu"][:D], c["S"][:D], c["W"][:D])
     assert r["n_bad"] == 0 and h[4] == 0
     worst = 0.0
-    for d in range(3):
+    for d in range(D):
         b = mr.numpy_bounds(c["X"], c["y"], c["tau2"][d], c["mu"][d], c["S"][d], c["W"][d])
         assert b["beta_lam"] <= 0.1
         for j, name in enumerate(NAMES[:3]):
@@ -76,6 +88,29 @@ def test_raw_call_against_the_restatement(gpu, n, q):
         assert np.isfinite(r["logml"][d]) and ratio <= 4.0, ("logml", d, ratio)
         worst = max(worst, ratio)
     print("n=%d q=%d: worst difference / bound %.3g" % (n, q, worst))
+
+
+# (258: the first column of the second pass with a k < i; 300: 44 columns; 513: the third pass, one column; 521: nine -- module docstring)
+@pytest.mark.parametrize("n,q", [(n, q) for q in (64, 65, 300) for n in (64, 65, 128, 129, 257)] + [(258, 65), (300, 65), (513, 65), (521, 300)])
+def test_raw_call_against_the_restatement(gpu, n, q):
+    c = mr.case(n, q)
+    _against_the_restatement(c, _call(c, range(3)), 3)
+
+
+def test_the_largest_n(gpu):
+    """n = 2048 = MLOO_MAX_N, q = 9, one draw: eight passes of the factor kernel, eight Cholesky rows per thread, and the last element of its
+    three LDS arrays (2049 is refused: test_marginal_loo_host.py).  Against the restatement under the gates of
+    test_raw_call_against_the_restatement, and with X = 0, where resid = y - mu and var = tau2 exactly at all 2048 rows.  0.90 s per call of one
+    draw on an MI355X: two calls, one per library (the other is test_marginal_edges_gpu's), stay far below the 20 s at which they would be merged."""
+    n, q = 2048, 9
+    c = mr.case(n, q)
+    t0 = time.perf_counter()
+    r = _call(c, range(1))
+    print("n=%d q=%d: one draw, the whole call, in %.2f s" % (n, q, time.perf_counter() - t0))
+    _against_the_restatement(c, r, 1)
+    r = bnr_amd.marginal_loglik(np.zeros((n, q)), c["y"], c["tau2"][:1], c["mu"][:1], c["S"][:1], c["W"][:1])
+    assert r["n_bad"] == 0 and np.array_equal(r["resid"], c["y"][:, None] - c["mu"][None, :1]) and np.array_equal(r["var"], np.full((n, 1), c["tau2"][0]))
+    _formula_checks(r, c["tau2"][:1], n)
 
 
 # ------------------------------------------------------------------------------------------ exact cases
@@ -92,7 +127,7 @@ def _formula_checks(r, tau2, n):
     assert np.all(np.abs(r["logml"] - ml) <= allow_ml), float(np.max(np.abs(r["logml"] - ml) / allow_ml))
 
 
-@pytest.mark.parametrize("n,q", ((1, 1), (17, 5), (33, 45), (65, 70)))
+@pytest.mark.parametrize("n,q", ((1, 1), (17, 5), (33, 45), (65, 70), (300, 7), (513, 5), (300, 310)))
 def test_exact_cases(gpu, n, q):
     c = mr.case(n, q)
     D = 5
@@ -123,7 +158,7 @@ def batch_option():
     _capi.mloo_set_option("mloo_batch_draws", 0)
 
 
-@pytest.mark.parametrize("n,q", ((17, 45), (33, 17), (70, 40)))
+@pytest.mark.parametrize("n,q", ((17, 45), (33, 17), (70, 40), (300, 40)))
 def test_a_draw_does_not_depend_on_its_batch_its_neighbours_or_its_place(gpu, batch_option, n, q):
     c = mr.case(n, q)
     full = _call(c, range(17))
@@ -165,13 +200,34 @@ def test_bad_draws_are_nan_counted_and_alone(gpu):
     assert _same(good, r, rest, rest)
 
 
+def test_a_pivot_that_fails_past_the_first_256_columns(gpu):
+    """n = 300: column 7 of X touches only the rows from 256 on and has S = -1e6 in draw 2, so columns 0 .. 255 of that draw factor as they do
+    without it and the first pivot that is not > 0 lies in a column j >= 256, where every thread is on its second row or idle.  Ordinary data and
+    a status, as above."""
+    n, q, D, e = 300, 45, 5, 7
+    c = mr.case(n, q)
+    X = c["X"].copy()
+    X[:256, e] = 0.0
+    assert X[256, e] ** 2 * 1e6 > 1.0 + (X[256] ** 2 * c["S"][2]).sum()                              # A[256][256] < 0: pivot 256 cannot be > 0
+    args = (X, c["y"], c["tau2"][:D], c["mu"][:D])
+    good = bnr_amd.marginal_loglik(*args, c["S"][:D], c["W"][:D])
+    S = c["S"][:D].copy()
+    S[2, e] = -1e6
+    r = bnr_amd.marginal_loglik(*args, S, c["W"][:D])
+    assert good["n_bad"] == 0 and r["n_bad"] == 1
+    for k in NAMES:
+        assert np.isnan(r[k][..., 2]).all() and np.all(np.isfinite(good[k])), k
+    assert _same(good, r, [0, 1, 3, 4], [0, 1, 3, 4])
+    h = api._host_marginal_terms(X[:256], c["y"][:256], c["tau2"][2:3], c["mu"][2:3], S[2:3], c["W"][2:3])
+    assert h[4] == 0                                                                                # the leading 256 x 256 block of that draw factors
+
+
 # ------------------------------------------------------------------------------------------ live chains
 TOT = 60
 
 
-@pytest.fixture(scope="module")
-def fit(gpu):
-    X, y, _ = bnr_amd.make_synthetic(20, 6, 2, seed=7)
+def _fit(n):
+    X, y, _ = bnr_amd.make_synthetic(n, 6, 2, seed=7)
     chains = [bnr_amd.Chain(X, y, 2, TOT, 11, 1)]
     chains += [bnr_amd.Chain.like(chains[0], 11, k, TOT) for k in (2, 3)]
     for ch in chains:
@@ -183,11 +239,32 @@ def fit(gpu):
         ch.close()
 
 
+@pytest.fixture(scope="module")
+def fit(gpu):
+    yield from _fit(20)
+
+
+@pytest.fixture(scope="module")
+def fit300(gpu):
+    """the same chains at n = 300: k_mloo_rhs runs two workgroups along the rows and the factor kernel two passes on live draws"""
+    yield from _fit(300)
+
+
 @pytest.mark.parametrize("thin", (1, 3))
 @pytest.mark.parametrize("nburn,nsamp", ((5, 40), (8, 41)))
 def test_live_chains(fit, nburn, nsamp, thin):
+    _live_chains(fit, 20, nburn, nsamp, thin)
+
+
+@pytest.mark.parametrize("thin", (1, 3))
+@pytest.mark.parametrize("nburn,nsamp", ((5, 40), (8, 41)))
+def test_live_chains_past_256_rows(fit300, nburn, nsamp, thin):
+    _live_chains(fit300, 300, nburn, nsamp, thin)
+
+
+def _live_chains(fit, n, nburn, nsamp, thin):
     X, y, chains, tables = fit
-    n, nd = 20, -(-nsamp // thin)
+    nd = -(-nsamp // thin)
     D = 3 * nd
     before = [(ch.iter, ch.counters()) for ch in chains]
     el, kh, lm, ls, ml, ll, nb = _capi.chains_marginal_loo(chains, nburn + 1, nsamp, thin, loglik=True)

@@ -1,6 +1,7 @@
 """GPU tests of the Rao-Blackwellised prediction of new rows (include/bnr_mpred.h, libbnr_mpred.so; kernels in csrc/bnr_mpred_kernels.h): the raw
 call against the mpmath reference within the derived bound (tests/mpred_ref.py) at the edges of the 16-row MFMA tile, of the 32-row padding, of
-the K step and of k_mpred_proj's 128-row block; against the numpy restatement beyond; cases whose answer is exact; large neighbouring entries of L
+the K step and of k_mpred_proj's 128-row block; against the numpy restatement beyond, through n = 258, 300 and 513 (the second and third
+256-column pass of k_mloo_factor, whose M the projection reads); cases whose answer is exact; large neighbouring entries of L
 behind the triangle's mask; the independence of a draw's bits from its batch, the blocking of the new rows, its neighbours and its place; bad
 draws; bnr_mixture_score against mpmath and its host mirror; live chains through the chain form and Fit; and all four libraries in one process.
 
@@ -95,7 +96,9 @@ def test_large_entries_of_l_behind_the_mask(gpu, n):
 
 
 # ------------------------------------------------------------------------------------------ against the numpy restatement
-@pytest.mark.parametrize("n", (64, 65, 129, 257))
+# (258, 300, 513: the M that k_mpred_proj reads comes out of the second and third 256-column pass of k_mloo_factor; 258 is the first n at which a
+# later pass has a column behind its first, 300 fills full unrolled chunks of the second pass, 513 opens the third -- tests/test_marginal_loo_gpu.py)
+@pytest.mark.parametrize("n", (64, 65, 129, 257, 258, 300, 513))
 def test_raw_call_against_the_restatement(gpu, n):
     q, m = 300, 70
     c = mr.case(n, q)

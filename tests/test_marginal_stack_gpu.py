@@ -160,7 +160,8 @@ TOT = 40
 NBURN, NSAMP = 9, 31
 
 
-@pytest.fixture(scope="module", params=((17, 2), (33, 3)), ids=("n17-K2", "n33-K3"))
+# (n = 300: the job setup of bnr_mloo_job.h with two workgroups of k_mloo_rhs along the rows and two 256-column passes of k_mloo_factor per draw)
+@pytest.fixture(scope="module", params=((17, 2), (33, 3), (300, 2)), ids=("n17-K2", "n33-K3", "n300-K2"))
 def fit(gpu, request):
     n, K = request.param
     X, y, _ = bnr_amd.make_synthetic(n, 6, 2, seed=7)
